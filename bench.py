@@ -13,17 +13,22 @@ observation (alpha=3), RandomAgent actions drawn on device (Philox), episodes of
 same-step autoreset.  One "step" = one env step of every env of the batch: leader move, Vicsek
 update, statuses, rewards, flags, observation, autoreset -- all written to HBM every step.
 
-What is timed.  The cost of a step depends on the episode phase (the all-pairs loop runs over the
-pedestrians that still move: all N after a reset, a third of them late in the episode), so the timed region is
-whole EPISODE SWEEPS: R = 2000/K launches of exactly K steps each (evac_rollout: the state stays in registers between
-the steps of a launch, every step still writes its outputs to HBM), issued back to back -- no host sync and no
-collective between the launches, the queue more than one launch deep; with N > 1 the gather of chunk j-1 runs under
-chunk j (below).  A sweep is bracketed by barrier + torch.cuda.synchronize() on both sides and timed twice: by the
-host clock (t1 after this rank's compute AND comm streams have drained) and by two HIP events on the launching
-stream.  `ms_per_step` = median over --sweeps sweeps of (sweep wall time, MAX over ranks) / 2000 = the EPISODE-AVERAGE
-cost of a step; `value` = total envs / that ("hipEvents around the step loop with no host sync
-inside").  `blocks` keeps the per-block view of rounds 1-3 as a diagnostic: every K-step block bracketed by a device-idle
-sync of its own (what a caller pays who waits for every launch), with the dense and mid-episode figures.
+What is timed.  Exactly --steps K env steps of the whole batch, after --warmup W untimed ones: one block of K steps
+issued as launches of --inner steps each (evac_rollout: the state stays in registers between the steps of a launch, every
+step still writes its outputs to HBM), back to back -- no host sync and no collective between the launches, the queue
+more than one launch deep; with N > 1 the gather of chunk j-1 runs under chunk j (below).  The block is bracketed by
+barrier + torch.cuda.synchronize() on both sides and timed twice: by the host clock (t1 after this rank's compute AND comm
+streams have drained) and by two HIP events on the launching stream.  `ms_per_step` = (block wall time, MAX over ranks) / K;
+`value` = total envs / that ("hipEvents around the step loop with no host sync inside").  The cost of
+a step depends on the episode phase (the all-pairs loop runs over the pedestrians that still move: all N after a reset, a
+third of them late in the episode), so K = 2000 (the default) is the EPISODE-AVERAGE cost of a step and a shorter K the cost
+of steps W .. W+K-1 of the episode.  --blocks B / --sweeps S repeat the K-step block (B x S x K timed steps; the figure is
+the median over the S sweeps) and --sustain-seconds keeps running the same sweeps for a while -- both only when asked for.
+`blocks` keeps the per-block view of rounds 1-3 as a diagnostic: every K-step block bracketed by a device-idle sync of its
+own (what a caller pays who waits for every launch), with the dense and mid-episode figures.
+`--dump-outputs DIR` writes what the timed path computed in its last step -- the arrays a caller of it receives -- as
+DIR/<name>.npy (f32), from inputs that are the same on every run with the same arguments: two builds compare output for
+output.
 
 The gather (N > 1).  The only collective of the path is the all-gather of the returned observation batch.
 `--gather-schedule pipelined` (default): the outputs are double-buffered and the gather of chunk j-1 is issued
@@ -81,14 +86,14 @@ WORKLOADS = {
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=2000, help="timed env steps (of every env of the batch)")
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--envs", type=int, default=0, help="override envs per GPU")
     ap.add_argument("--inner", type=int, default=100, help="env steps per kernel launch (rollout mode)")
     ap.add_argument("--mode", default="rollout", choices=["rollout", "step"])
-    ap.add_argument("--sweeps", type=int, default=0, help="passes over the episode (0: 11, or 1 when a block is a whole episode -- then raised until 20 blocks are timed)")
-    ap.add_argument("--blocks", type=int, default=0, help="override the number of timed K-step blocks")
+    ap.add_argument("--sweeps", type=int, default=0, help="timed sweeps of --blocks K-step blocks each (0: 1); the figure is their median")
+    ap.add_argument("--blocks", type=int, default=0, help="K-step blocks per timed sweep (0: 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-step-api", action="store_true", help="skip the one-launch-per-step side measurement (and the side workloads: the headline kernel only)")
     ap.add_argument("--no-side-workloads", action="store_true",
@@ -99,14 +104,15 @@ def parse_args(argv=None):
     ap.add_argument("--side-only", default="", choices=["", "c2_one_kernel", "c3", "c5_shard", "big_step"],
                     help="run ONLY this entry of `workloads` (exactly as the default line runs it) and print it as the JSON line: what "
                          "tools/final_run.sh puts under rocprofv3, so that a kernel trace covers the launches that entry times and no others")
-    ap.add_argument("--sustain-seconds", type=float, default=2.0,
+    ap.add_argument("--sustain-seconds", type=float, default=0.0,
                     help="after the headline sweeps keep running the same sweeps for this much GPU time (0: skip): `sustained` in the line, "
                          "and `value` becomes the settled median when it differs from the headline sweeps' by more than 2 %%")
     ap.add_argument("--rollout-form", default="auto", choices=["auto", "one", "parts", "chain", "persist"],
                     help="how the handle issues a rollout (evac_options_t): one = ONE kernel per call on the launching stream, every launch "
                          "behind the one before; chain = consecutive launches alternately on two streams the handle owns, ordered per env on "
                          "the device (evac_options_t.chain; evac_join closes a sweep); parts = two half-batch kernels per call on those two "
-                         "streams (evac_options_t.parts); auto = chain on a single GPU without gathers, one otherwise")
+                         "streams (evac_options_t.parts); auto = persist on a single GPU without gathers when the timed K-step block is repeated "
+                         "(--blocks / --sweeps / --sustain-seconds), one otherwise")
     ap.add_argument("--no-gather", action="store_true", help="skip the all-gather of the outputs (N>1)")
     ap.add_argument("--force-gather", action="store_true",
                     help="run the gather path -- process group, collective on the comm stream, double-buffered pipeline -- with "
@@ -131,6 +137,8 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-procs", type=int, default=-1,
                     help="worker processes for the many-core CPU figure (-1: the cores this process may run on; 0/1: skip)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"))
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last step (rank 0's envs) as DIR/<name>.npy, at most 64 MB in all")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / block and gather control flow only, on CPU tensors over gloo (tests; prints no throughput)")
     return ap.parse_args(argv)
@@ -269,15 +277,34 @@ def cpu_baseline(n_ped: int, seconds: float, procs: int):
 
 
 def block_plan(K: int, sweeps: int, blocks: int):
-    """(blocks per sweep, sweeps): consecutive K-step blocks tile the episode."""
-    per_sweep = max(1, math.ceil(EPISODE / K))
-    if sweeps <= 0:
-        sweeps = 1 if per_sweep == 1 else 11             # (SURVEY.md 8(d): median of >= 5 repeats; eleven 20-step sweeps are 50 ms of GPU time)
-    while per_sweep * sweeps < 20:                     # at least 20 timed blocks
-        sweeps += 1
-    if blocks > 0:
-        per_sweep, sweeps = blocks, 1
-    return per_sweep, sweeps
+    """(K-step blocks per sweep, sweeps): one block of K steps unless --blocks / --sweeps ask for more, so that --steps K is
+    the number of timed steps."""
+    return max(1, blocks), max(1, sweeps)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6 - 64 * 1024    # --dump-outputs: 64 MB in all, .npy headers included
+
+
+def dump_outputs(dirname: str, arrays: dict, seed: int) -> dict:
+    """Writes `arrays` (name -> [E, ...] tensor or array, env-major; f64 kept, everything else as f32) as DIR/<name>.npy.  Should
+    they exceed DUMP_LIMIT_BYTES, the same seeded sample of env rows is taken from every array and its indices go to
+    DIR/env_index.npy.  Returns {name: shape}."""
+    import numpy as np
+    host = {}
+    for k, v in arrays.items():
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        host[k] = a if a.dtype == np.float64 else a.astype(np.float32)
+    E = next(iter(host.values())).shape[0]
+    row_bytes = sum(a.nbytes // max(1, a.shape[0]) for a in host.values())
+    keep = min(E, DUMP_LIMIT_BYTES // (row_bytes + 8))
+    if keep < E:
+        idx = np.sort(np.random.default_rng(seed).choice(E, keep, replace=False))
+        host = {k: a[idx] for k, a in host.items()}
+        host["env_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in host.items()}
 
 
 def summarize_blocks(wall_s, phases, per_sweep, K):
@@ -573,6 +600,8 @@ def side_workloads(args, device):
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.side_only:                                         # one entry of `workloads`, exactly as the default line runs it
         import torch
         import evacuation_amd as ea
@@ -653,7 +682,10 @@ def main(argv=None):
     # streams by events recorded behind ONE launch per chunk, so those runs keep one kernel per launch.
     form_req = args.rollout_form
     if form_req == "auto":
-        form_req = "persist" if (world == 1 and not use_dist and args.mode == "rollout") else "one"
+        # the resident kernel pays off over many calls in a row; a timed region of one K-step block (the default) is faster
+        # with plain launches, which need no start-up of the resident kernel (K = 20: 0.65e9 against 0.51e9 env-steps/s)
+        repeated = per_sweep * sweeps > 1 or args.sustain_seconds > 0
+        form_req = "persist" if (world == 1 and not use_dist and args.mode == "rollout" and repeated) else "one"
     if form_req != "one" and use_dist and not args.no_gather:
         raise SystemExit("bench.py: --rollout-form parts / chain with gathers is not supported (the gather pipeline waits on one launch per chunk)")
     kopts = {"one": ea.KernelOptions(parts=1, chain=0), "parts": ea.KernelOptions(parts=2, chain=0),
@@ -731,7 +763,9 @@ def main(argv=None):
         chunks.clear()                                        # (rebuilt for the forms that are left)
         return True
 
-    step_actions = torch.rand((E, 2), device=device) * 2 - 1
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed + rank)                              # (the same actions on every run with the same arguments)
+    step_actions = torch.rand((E, 2), device=device, generator=gen) * 2 - 1
 
     run = {"form": form, "diag": None}      # the gather form in use; diag: {chunk: {...events}} while the instrumented sweep runs
 
@@ -924,6 +958,19 @@ def main(argv=None):
         sweep_dev.append(e0.elapsed_time(e1) * 1e-3)
     pipe.flush()
     barrier()
+    dumped = None
+    if args.dump_outputs and rank == 0:                       # what the last timed step returned to its caller (untimed)
+        if args.mode == "rollout":
+            b = chunk_bufs(sizes[-1], (pipe.next - 1) % nbuf)
+            last = b["slab"][-1]
+            done = (last[:, D + 1] != 0) | (last[:, D + 2] != 0)
+            st = b["episode_stats"][-1]                       # (8 floats + 2 int32 words; rows valid where an episode ended)
+            stats = torch.cat([st[:, :8].double(), st[:, 8:].contiguous().view(torch.int32).double()], dim=1) * done[:, None].double()
+            outs = {"obs": last[:, :D], "reward": last[:, D], "terminated": last[:, D + 1], "truncated": last[:, D + 2],
+                    "episode_stats": stats}
+        else:
+            outs = {"obs": loc.obs, "reward": loc.reward, "terminated": loc.terminated, "truncated": loc.truncated}
+        dumped = dump_outputs(args.dump_outputs, outs, seed)
     sweep_wall_this_rank = list(sweep_wall)                    # (before the max over ranks below: gather_report.per_rank[r].headline)
     # ---- steady state: the SAME sweeps again until --sustain-seconds of GPU time have passed.  The headline's
     # eleven sweeps are ~50 ms; clocks and power settle over seconds.  All ranks run the same number of sweeps (from the max-over-ranks
@@ -1279,26 +1326,26 @@ def main(argv=None):
             gather_desc = f", all-gather of the {what} per {inner}-step chunk on a side stream, {how}"
         out = {
             "metric": "env-steps/s (agent-updates/s) at n=60x4096 envs" if args.workload == "c2" else f"env-steps/s ({args.workload})",
-            "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W,
+            "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W, "timed_steps": sweeps * steps_per_sweep,
             "ms_per_step": step_s * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": desc, "n_pedestrians": n_ped, "envs_per_gpu": E, "total_envs": total_envs,
                        "obs": wrap_kw, "actions": "RandomAgent U(-1,1)^2 drawn on device (Philox4x32-10)",
                        "mode": args.mode, "steps_per_launch": inner, "launches_per_block": len(sizes),
-                       "timing": "whole episode sweeps of 2000/K launches of exactly K steps each, issued back to back (no host sync, no "
+                       "timing": "--steps K timed steps (--blocks x --sweeps K-step blocks on request), issued back to back (no host sync, no "
                                  "barrier collective inside; N > 1: the gather of chunk j-1 on a second hardware queue under chunk j, a "
                                  "chunk's buffer reused only once the host has seen its gather finished -- a query, the host at most "
                                  "gather_buffers - 1 chunks ahead of the device); per sweep: barrier + synchronize (all "
                                  "ranks, device idle) -> t0 -> the launches (+ gathers) -> the rank drains its compute and comm streams "
-                                 "-> t1, max over ranks; ms_per_step = median sweep / 2000 = the episode-average step; `blocks`: the "
+                                 "-> t1, max over ranks; ms_per_step = median sweep / its steps (K = 2000: the episode-average step); `blocks`: the "
                                  "per-block view (a device-idle sync around every K-step launch) as a diagnostic",
                        "sweeps": {"timed": sweeps, "launches_per_sweep": launches_per_sweep, "steps_per_sweep": steps_per_sweep,
                                   "wall_ms": [x * 1e3 for x in sweep_wall], "hip_event_ms": [x * 1e3 for x in sweep_dev],
                                   "gpu_ms_timed_total": sum(sweep_dev) * 1e3,
                                   "value_min_median_max": [total_envs * steps_per_sweep / max(sweep_wall), value,
                                                            total_envs * steps_per_sweep / min(sweep_wall)]},
-                       "timing_method": "r06: median of whole-episode sweeps (11 by default for K-step blocks), back-to-back launches, followed "
-                                        "by the same sweeps for --sustain-seconds of GPU time (`sustained`; `value` = the settled median when "
+                       "timing_method": "median of the timed sweeps (one by default: exactly --steps K steps), back-to-back launches, followed "
+                                        "by the same sweeps for --sustain-seconds of GPU time if asked for (`sustained`; `value` = the settled median when "
                                         "the two differ by more than 2 %); "
                                         "roofline.kernel_ms_per_launch = median sweep (HIP events) / launches -- with gathers in the "
                                         "sweeps: the mean launch of a replayed sweep WITHOUT gathers (the sweep's own figure is "
@@ -1362,6 +1409,8 @@ def main(argv=None):
         }
         if sustained is not None:
             out["sustained"] = sustained
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         ro = loc.resolved_options()
         out["config"]["rollout_form"] = {
             "requested": args.rollout_form, "parts": loc.num_parts, "chain": ro.chain, "own_streams": loc.own_streams,

@@ -1,8 +1,7 @@
 """Load the *real* reference (cinemere/evacuation) from /root/reference -- build container only.
 
-This module is used ONLY by tests/golden/make_golden.py (fixture generation) and by
-tests/test_oracle_vs_reference.py (skipped when /root/reference is absent, e.g. on the
-GPU box).  Nothing in the product (`evacuation_amd/`), in `bench.py` or in
+This module is used ONLY by tests/golden/make_golden.py (fixture generation); the tests read
+the fixtures it writes.  Nothing in the product (`evacuation_amd/`), in `bench.py` or in
 `__graft_entry__.py` imports it.
 
 Two routes, so that the arithmetic pinned by the fixtures never runs through code we wrote:

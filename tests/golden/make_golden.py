@@ -11,6 +11,7 @@ See _reference_loader.py for how the reference is imported without gymnasium/wan
 Fixture kinds
   traj_*.npz     free-running episodes from ``np.random.seed(seed); env.reset()``
   crafted.npz    single steps from hand-built states exercising the edge cases of SURVEY 8(c)
+  reference_runs.npz  the reference's side of the oracle-vs-reference and trajectory-format tests (make_reference_runs)
 """
 from __future__ import annotations
 
@@ -360,6 +361,103 @@ def make_crafted(ref):
     print(f"crafted: {len(names)} cases, {os.path.getsize(path)/1024:.0f} KiB")
 
 
+# The reference's side of tests/test_oracle_vs_reference.py and tests/test_trajectory_format_cpu.py, recorded once so that
+# those tests run on any machine: (n, seed, noise, enslaving degree) of the free-running core runs.
+CORE_RUNS = ((60, 11, 0.2, 1.0), (60, 12, 0.8, 0.5), (17, 13, 0.05, 0.1), (256, 14, 0.2, 1.0))
+
+
+def core_run_steps(n: int) -> int:
+    return 150 if n <= 60 else 30
+
+
+def make_reference_runs(name="reference_runs"):
+    """Three kinds of record in one file:
+    core_<n>_<seed>_*   the stub-free core (load_core) free-running from ``np.random.seed(seed)``, actions from PCG64(seed):
+                        positions / directions / status codes / leader position after every step, the pedestrians' and the
+                        leader's rewards and the intrinsic reward of every step;
+    full_* / fullcore_* the setup_env surface with the gymnasium / wandb shells (n=30, seed 5, grav obs, 40 steps) and the
+                        stub-free core on the same draws: positions after every step and the reward of the step;
+    memory_*            a draw=True EvacuationEnv (n=17, seed 5, 25 steps, actions from default_rng(1)): its own rendering memory
+                        -- pedestrians.memory positions / status codes, agent.memory positions, with the reference's dtypes."""
+    out = {}
+    for n, seed, noise, ens in CORE_RUNS:
+        core = L.load_core()
+        rw = core.reward.Reward(True, True, False, -1.0)
+        area = core.area.Area(rw, 1.0, 1.0, 0.01, noise, 1e-8)
+        agent = core.area.Agent(ens)
+        agent.reset()
+        peds = core.pedestrians.Pedestrians(n)
+        np.random.seed(seed)
+        peds.reset(agent.position, area.exit.position)
+        rec = {k: [] for k in ("pos", "dir", "status", "agent_pos", "reward_ped", "intrinsic", "reward_agent")}
+        reset_pos = peds.positions.copy()
+        act = np.random.Generator(np.random.PCG64(seed))
+        for t in range(core_run_steps(n)):
+            a = act.uniform(-1, 1, 2).astype(np.float32)
+            agent, _, r_a = area.agent_step(a.copy(), agent)
+            peds, _, r_p, r_i = area.pedestrians_step(peds, agent, t + 1)
+            rec["pos"].append(peds.positions.copy())
+            rec["dir"].append(peds.directions.copy())
+            rec["status"].append(L.status_codes(peds.statuses))
+            rec["agent_pos"].append(np.array(agent.position, copy=True))
+            rec["reward_ped"].append(r_p)
+            rec["intrinsic"].append(r_i)
+            rec["reward_agent"].append(r_a)
+        key = f"core_{n}_{seed}_"
+        out[key + "reset_pos"] = reset_pos
+        for k, v in rec.items():
+            out[key + k] = np.array(v)
+
+    full = L.load_full()
+    cfg = full.EnvConfig(number_of_pedestrians=30, wandb_enabled=False, path_logs=L.log_dir(), is_new_exiting_reward=True)
+    env = full.setup_env(cfg, full.EnvWrappersConfig(positions="grav", alpha=3))
+    np.random.seed(5)
+    env.reset()
+    acts = np.random.Generator(np.random.PCG64(5)).uniform(-1, 1, (40, 2)).astype(np.float32)
+    fpos, frew = [], []
+    for a in acts:
+        _, r, _, _, _ = env.step(a)
+        fpos.append(env.unwrapped.pedestrians.positions.copy())
+        frew.append(r)
+    core = L.load_core()
+    rw = core.reward.Reward(True, True, False, -1.0)
+    area = core.area.Area(rw, 1.0, 1.0, 0.01, 0.2, 1e-8)
+    agent = core.area.Agent(1.0)
+    agent.reset()
+    peds = core.pedestrians.Pedestrians(30)
+    np.random.seed(5)
+    peds.reset(agent.position, area.exit.position)
+    cpos, crew = [], []
+    for t, a in enumerate(acts):
+        agent, _, r_a = area.agent_step(a.copy(), agent)
+        peds, _, r_p, r_i = area.pedestrians_step(peds, agent, t + 1)
+        cpos.append(peds.positions.copy())
+        crew.append(r_a + r_p + 0.0 * r_i)
+    out.update(full_actions=acts, full_pos=np.array(fpos), full_reward=np.array(frew, dtype=np.float64),
+               fullcore_pos=np.array(cpos), fullcore_reward=np.array(crew, dtype=np.float64))
+
+    import tempfile
+    pkg = L.load_full()
+    n, T = 17, 25
+    with tempfile.TemporaryDirectory() as tmp:
+        cfg = pkg.EnvConfig(number_of_pedestrians=n, wandb_enabled=False, draw=True, giff_freq=10 ** 9,
+                            path_logs=os.path.join(tmp, "logs"), path_giff=os.path.join(tmp, "giff"), experiment_name="capture")
+        ref = pkg.EvacuationEnv(cfg)
+        np.random.seed(5)
+        ref.reset()
+        rng = np.random.default_rng(1)
+        for _ in range(T):
+            ref.step(rng.uniform(-1, 1, 2).astype(np.float32))
+    pm, am = ref.pedestrians.memory, ref.agent.memory
+    assert sorted(pm) == ["positions", "statuses"] and sorted(am) == ["position"], (sorted(pm), sorted(am))
+    assert all(s.dtype == object for s in pm["statuses"])
+    out.update(memory_n=np.int64(n), memory_T=np.int64(T), memory_positions=np.stack(pm["positions"]),
+               memory_statuses=np.stack([L.status_codes(s) for s in pm["statuses"]]), memory_agent_position=np.stack(am["position"]))
+    path = os.path.join(HERE, name + ".npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path}")
+
+
 def main(argv=None):
     """`make_golden.py` regenerates every fixture; `make_golden.py NAME [NAME ...]` only the named trajectories / "crafted"."""
     only = set(sys.argv[1:] if argv is None else argv)
@@ -394,6 +492,8 @@ def main(argv=None):
         make_terminating_episode(ref)
     if not only or "crafted" in only:
         make_crafted(ref)
+    if not only or "reference_runs" in only:
+        make_reference_runs()
 
 
 if __name__ == "__main__":

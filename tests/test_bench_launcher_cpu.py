@@ -36,7 +36,7 @@ def test_plain_invocation_spawns_its_own_ranks():
 def test_the_multi_rank_line_carries_every_ranks_account_of_the_gather():
     """`gather_report.per_rank` is gathered from ALL ranks (all_gather_object), the form that is timed is decided
     by choose_gather from the probe -- here, without a GPU, the probe says no, so `--gather auto` falls back to the RCCL form."""
-    r = run_bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--dry-run", "--gather", "auto"])
+    r = run_bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--blocks", "4", "--dry-run", "--gather", "auto"])
     assert r.returncode == 0, r.stderr[-2000:]
     rep = json_lines(r.stdout)[0]["gather_report"]
     assert rep["requested"] == "auto" and rep["timed_form"] == "obs" and rep["alternative_form"] is None
@@ -71,7 +71,7 @@ def test_timed_block_has_no_barrier_and_carries_the_previous_blocks_gather():
     """per rank, opening barrier -> t0 -> launches -> drain compute and gather -> local t1; the closing
     barrier is outside the timed region; with one launch per block (the driver's --steps 20) the gather of block b-1 is issued
     after the launch of block b, inside block b (double-buffered), and drained before t1."""
-    r = run_bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--dry-run"])
+    r = run_bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--blocks", "4", "--dry-run"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json_lines(r.stdout)[0]
     assert d["gather_schedule"] == "pipelined" and d["chunk_sizes"] == [20] and d["launches_per_block"] == 1
@@ -183,11 +183,11 @@ def test_torchrun_style_environment_is_honoured():
 def test_block_plan_tiles_the_episode():
     sys.path.insert(0, ROOT)
     import bench
-    assert bench.block_plan(20, 0, 0) == (100, 11)     # the driver's --steps 20: 100 blocks per episode sweep, 11 sweeps
-    assert bench.block_plan(2000, 0, 0) == (1, 20)     # default: a block is a whole episode, 20 of them
-    assert bench.block_plan(500, 0, 0)[0] == 4 and bench.block_plan(500, 0, 0)[0] * bench.block_plan(500, 0, 0)[1] >= 20
+    assert bench.block_plan(20, 0, 0) == (1, 1)        # --steps K times exactly K steps: one K-step block
+    assert bench.block_plan(2000, 0, 0) == (1, 1)      # default: the block is a whole episode
+    assert bench.block_plan(500, 0, 0) == (1, 1)
     per, sw = bench.block_plan(20, 0, 7)
-    assert per * sw == 7
+    assert (per, sw) == (7, 1)                         # --blocks B: B blocks per sweep, on request
     avg, info = bench.summarize_blocks([1.0, 3.0, 1.2, 2.8], [5, 1005, 5, 1005], 2, 10)
     assert abs(avg - (1.1 + 2.9) / 2) < 1e-12 and info["dense"]["episode_phase"] == 5 and info["mid_episode"]["episode_phase"] == 1005
     # K does not divide the episode: blocks are grouped by their ACTUAL phase, never by block index

@@ -92,7 +92,26 @@ def test_gather_report_from_synthetic_timestamps():
     assert rep["gather_ms_under_compute"] is None and rep["launch_slowdown_under_gather"] is None and rep["bytes_received_per_chunk"] == 0
 
 
-def test_sweeps_default_to_eleven_for_k_step_blocks():
-    assert bench.block_plan(20, 0, 0) == (100, 11)              # the driver's --steps 20: 1100 launches, ~50 ms of GPU time
-    assert bench.block_plan(2000, 0, 0) == (1, 20)              # whole-episode blocks: at least 20 of them
-    assert bench.block_plan(20, 3, 0) == (100, 3)
+def test_timed_steps_are_the_steps_asked_for():
+    assert bench.block_plan(20, 0, 0) == (1, 1)                 # --steps 20: one block of 20 timed steps
+    assert bench.block_plan(2000, 0, 0) == (1, 1)               # the default: one whole episode
+    assert bench.block_plan(20, 3, 0) == (1, 3)                 # --sweeps S: S sweeps of one block, on request
+    assert bench.block_plan(20, 3, 100) == (100, 3)
+
+
+def test_dump_outputs_writes_every_array_and_samples_a_large_one_the_same_way(tmp_path):
+    import numpy as np
+    small = {"obs": np.arange(12, dtype=np.float32).reshape(4, 3), "reward": np.ones(4, np.float32), "episode_stats": np.zeros((4, 2))}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), small, 7)
+    assert shapes == {"obs": [4, 3], "reward": [4], "episode_stats": [4, 2]}
+    assert np.load(tmp_path / "a" / "obs.npy").dtype == np.float32 and np.load(tmp_path / "a" / "episode_stats.npy").dtype == np.float64
+    assert (np.load(tmp_path / "a" / "obs.npy") == small["obs"]).all()
+    E = 3_000_000                                                     # 3e6 x (4 + 16) bytes: over the 64 MB limit
+    big = {"reward": np.arange(E, dtype=np.float32), "obs": np.arange(4 * E, dtype=np.float32).reshape(E, 4)}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, 7)
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= 64 * 10 ** 6 and sorted(os.listdir(tmp_path / "b")) == ["env_index.npy", "obs.npy", "reward.npy"]
+    idx = np.load(tmp_path / "b" / "env_index.npy")
+    assert (idx == np.load(tmp_path / "c" / "env_index.npy")).all() and (np.diff(idx) > 0).all()
+    assert (np.load(tmp_path / "b" / "reward.npy") == idx).all() and (np.load(tmp_path / "b" / "obs.npy")[:, 0] == 4 * idx).all()
