@@ -60,6 +60,8 @@ int64_t obs_dim_of(const evac_config_t* c) {
 
 }  // namespace
 
+enum class Form { Plain, Parts, Chain, Persist };   // how a handle issues its rollouts (include/evac.h, evac_options_t.parts / chain)
+
 struct evac_handle {
     evac_config_t cfg;
     evac::Params p;
@@ -72,10 +74,10 @@ struct evac_handle {
     bool default_cfg;   // the configuration the specialised rollout kernels assume (k_rollout_default_config)
     int team_k;         // rollouts of 513..1024-pedestrian envs by teams of 2 / 4 / 8 / 16 workgroups per env (0: one workgroup per env)
     int32_t* sched;     // inside the caller's workspace (evac_bind_workspace): moving[2][E] | perm[2][E], or NULL
-    int sched_gen;      // rollout launches under the schedule so far (< 0: no deal yet): launch g reads perm[g & 1], leaves its loads
+    int sched_gen = -1; // rollout launches under the schedule so far (< 0: no deal yet): launch g reads perm[g & 1], leaves its loads
                         // in moving[g & 1] and deals perm[(g + 1) & 1] from moving[(g - 1) & 1] (rollout_body)
     bool team_bound;    // the workspace holds the teams' exchange areas
-    int team_fit;       // -1: not checked yet; 1 / 0: the team grid fits the device at once (occupancy x CUs >= workgroups) or not
+    int team_fit = -1;  // -1: not checked yet; 1 / 0: the team grid fits the device at once (occupancy x CUs >= workgroups) or not
     size_t team_xchg_bytes;   // the teams' exchange area (records + tile slots), filled with 0xff (the tag of no round) before every team launch
     bool team_coop;     // EVAC_TEAM_COOP=1 (and the device supports it): team kernels are launched with hipLaunchCooperativeKernel
     int cus;            // compute units of the device
@@ -85,39 +87,48 @@ struct evac_handle {
     volatile unsigned* team_flag_host;
     unsigned* team_flag_dev;
     std::string err;
-    std::string variant[4];   // evac_step | evac_rollout with one workgroup (or less) per env | evac_rollout by teams | ... as two parts
-    // evac_options_t.parts = 2: the handle's rollouts go out as two half-batch kernels on two streams it owns (include/evac.h,
+    std::string variant[4];   // evac_step | evac_rollout with one workgroup (or less) per env | evac_rollout by teams | ... in the handle's form
+    evac_options_t opt;       // as resolved at creation (evac_get_options)
+    // How the handle issues its rollouts, fixed at creation (evac_create_ex); evac_team_clear_error falls back to Plain after settling.
+    // Every form but Plain runs on the two streams the handle owns (`own`); whatever is not a plain rollout settles them first (settle).
+    Form form = Form::Plain;
+    struct OwnStreams {
+        hipStream_t s[2];
+        hipEvent_t done[2], fork;
+        bool pending;         // the own streams hold work the caller's stream has not been made to wait for (evac_join)
+        bool forked;          // the own streams have been put behind the caller's stream since the last join (evac_rollout forks once per join)
+    } own;
+    // Form::Parts (evac_options_t.parts = 2): the handle's rollouts go out as two half-batch kernels on the own streams (include/evac.h,
     // evac_join).  part[k] is a complete handle of its own over envs [k E / 2, (k + 1) E / 2) of THIS handle's buffers (state
     // pointers and workspace slices offset, Params::slab_envs = E, env_id_offset + k E / 2: the same global env ids), so a part
     // launches exactly what a handle of that size launches -- schedule, in-kernel deal and generation counter of its own.
-    int n_parts;              // 1 or 2
     evac_handle* part[2];
-    hipStream_t part_stream[2];
-    hipEvent_t part_done[2], fork_ev;
-    bool parts_pending;       // the part streams hold work the caller's stream has not been made to wait for (evac_join)
-    bool forked;              // the own streams have been put behind the caller's stream since the last join (evac_rollout forks once per join)
-    evac_options_t opt;       // as resolved at creation (evac_get_options)
-    // evac_options_t.chain = 1: rollout launch g goes to part_stream[g & 1] and waits PER ENV for launch g - 1 on the device
+    // Form::Chain and Form::Persist: what the handle allocates itself besides its streams
+    char* xchg;               // uncached device memory: Chain's [E] exchange records (evac_common.h); Persist's command ring (+ next_cmd[E], decision[E])
+    size_t xchg_bytes;        // (what the pool handed out: given back with it)
+    unsigned* abort_word;     // device word: a wait timed out (Chain: in the workspace, Persist: behind the ring)
+    hipEvent_t last_ev;       // Chain: behind a restart's import; Persist: behind every persistent kernel (has it left?)
+    // Form::Chain (evac_options_t.chain = 1): rollout launch g goes to own.s[g & 1] and waits PER ENV for launch g - 1 on the device
     // (include/evac.h, evac_common.h ChainArgs).  The schedule is four deep here: launch g reads perm[g & 3], leaves its loads in
     // moving[g & 3] and deals perm[(g + 2) & 3] -- read by the next launch of ITS stream -- from moving[(g - 2) & 3], the last
     // launch of its stream: everything a launch reads was written by a launch its queue has completed.
-    bool chain;               // (requested and possible; used only with the workspace bound)
-    bool chain_bound;
-    bool persist;             // evac_options_t.chain = 2: one persistent rollout kernel per join, every evac_rollout call a command of its ring
-    bool persist_running;     // the kernel is resident (on part_stream[0]) and reads commands
-    int persist_seq;          // the next command's index (its sequence number is index + 1; never reset)
-    int persist_first;        // the first command of the kernel that is running
-    bool chain_small;         // the chain's launches are the 256-thread workgroups of one-wave envs (four envs each: no deal, no pace keeping)
-    int chain_gen;            // rollout launches of the chain so far = the generation the next launch waits for
-    int chain_start;          // the launch at which the chain (re)started: deals begin two launches later
-    bool chain_restart;       // the state was written by something else than the chain's last launch: fill the generation words first
-    int32_t* chain_sched;     // moving[4][E] | perm[4][E]
-    size_t chain_xchg_bytes;  // (what the pool handed out: given back with it)
-    char* chain_xchg;         // [E] exchange records (evac_common.h): the state between the chain's launches
-    unsigned* chain_abort;    // device word: a wait timed out
-    bool chain_dirty;         // the records are ahead of the caller's state arrays (k_chain_export at the next join)
-    unsigned long long chain_wgs;   // workgroups of the chain's launches enqueued since its last restart (the gate's target)
-    hipEvent_t chain_ev;
+    struct ChainState {
+        bool bound;           // the workspace is bound (chained launches need it; without it the handle issues plain launches)
+        bool small;           // the chain's launches are the 256-thread workgroups of one-wave envs (four envs each: no deal, no pace keeping)
+        bool restart = true;  // the state was written by something else than the chain's last launch: fill the generation words first
+        bool dirty;           // the records are ahead of the caller's state arrays (k_chain_export at the next join)
+        int gen = 1;          // rollout launches of the chain so far = the generation the next launch waits for
+        int start = 1;        // the launch at which the chain (re)started: deals begin two launches later
+                              // (never 0: a zero-filled workspace must not look like a published generation)
+        int32_t* sched;       // moving[4][E] | perm[4][E]
+        unsigned long long wgs;   // workgroups of the chain's launches enqueued since its last restart (the gate's target)
+    } chain;
+    // Form::Persist (evac_options_t.chain = 2): one persistent rollout kernel per join, every evac_rollout call a command of its ring
+    struct PersistState {
+        bool running;         // the kernel is resident (on own.s[0]) and reads commands
+        int seq;              // the next command's index (its sequence number is index + 1; never reset)
+        int first;            // the first command of the kernel that is running
+    } persist;
 };
 
 namespace {
@@ -127,23 +138,18 @@ int fail(evac_handle_t h, int code, const std::string& msg) {
     return code;
 }
 
-// A team rollout of this handle lost a member (evac_team.h): the outputs of that launch are void.  Sticky until
-// evac_team_clear_error; the handle runs the one-workgroup-per-env kernels from then on.
+// A team rollout of this handle lost a member (evac_team.h), or a chained launch waited in vain: the outputs of that launch are void.
+// Sticky until evac_team_clear_error, which settles the handle and leaves it on plain launches of one workgroup per env.
 int team_aborted(evac_handle_t h, const char* what) {
-    if (h->team_flag_host && *h->team_flag_host != 0u && h->chain) {
-        h->chain = false;
+    if (!h->team_flag_host || *h->team_flag_host == 0u) return EVAC_OK;
+    if (h->form == Form::Chain)
         return fail(h, EVAC_ERR_TEAM_ABORTED,
                     std::string(what) + ": a chained rollout launch waited in vain for an env's state (a launch of the chain was lost); the "
                     "outputs since are void -- call evac_team_clear_error(), then reset or restore the batch; the handle issues plain launches from now on");
-    }
-    if (h->team_flag_host && *h->team_flag_host != 0u) {
-        h->team_k = 0;
-        return fail(h, EVAC_ERR_TEAM_ABORTED,
-                    std::string(what) + ": an earlier team rollout lost a member (the workgroups of a team were not resident together); "
-                    "the outputs of that launch are void and the env it carried kept its pre-launch state -- call "
-                    "evac_team_clear_error(), then reset or restore the batch; the handle uses one workgroup per env from now on");
-    }
-    return EVAC_OK;
+    return fail(h, EVAC_ERR_TEAM_ABORTED,
+                std::string(what) + ": an earlier team rollout lost a member (the workgroups of a team were not resident together); "
+                "the outputs of that launch are void and the env it carried kept its pre-launch state -- call "
+                "evac_team_clear_error(), then reset or restore the batch; the handle uses one workgroup per env from now on");
 }
 
 int check_launch(evac_handle_t h, const char* what) {
@@ -208,22 +214,17 @@ constexpr int kMaxDevices = 64;
 std::mutex g_team_chain_lock;
 hipEvent_t g_team_chain[kMaxDevices] = {};
 
-const void* team_kernel(const evac_handle* h) {
-    const bool grav = h->p.obs_pos == EVAC_POS_GRAV, dflt = h->default_cfg;
-#define EVAC_TEAM_FN(K_)                                                                                                          \
-    (dflt ? (grav ? (const void*)evac::k_rollout_default_config<evac::Team<K_>, true> : (const void*)evac::k_rollout_default_config<evac::Team<K_>, false>) \
-          : (grav ? (const void*)evac::k_rollout<evac::Team<K_>, true> : (const void*)evac::k_rollout<evac::Team<K_>, false>))
-    return h->team_k == 16 ? EVAC_TEAM_FN(16) : (h->team_k == 8 ? EVAC_TEAM_FN(8) : (h->team_k == 4 ? EVAC_TEAM_FN(4) : EVAC_TEAM_FN(2)));
-#undef EVAC_TEAM_FN
-}
-const void* team_persist_kernel(const evac_handle* h) {
-    const bool grav = h->p.obs_pos == EVAC_POS_GRAV, dflt = h->default_cfg;
-#define EVAC_TEAM_FN(K_)                                                                                                          \
-    (dflt ? (grav ? (const void*)evac::k_rollout_persist_default_config<evac::Team<K_>, true> : (const void*)evac::k_rollout_persist_default_config<evac::Team<K_>, false>) \
-          : (grav ? (const void*)evac::k_rollout_persist<evac::Team<K_>, true> : (const void*)evac::k_rollout_persist<evac::Team<K_>, false>))
-    return h->team_k == 16 ? EVAC_TEAM_FN(16) : (h->team_k == 8 ? EVAC_TEAM_FN(8) : (h->team_k == 4 ? EVAC_TEAM_FN(4) : EVAC_TEAM_FN(2)));
-#undef EVAC_TEAM_FN
-}
+// The kernel of a pair -- KDEF specialised for the default configuration (k_rollout_default_config), KGEN generic -- of family F_ for this
+// handle's configuration and observation (gravity or not).  Both kernels of a pair take the same arguments: launch it through the pointer.
+#define EVAC_PICK(h, KDEF, KGEN, F_)                                                                                        \
+    ((h)->default_cfg ? ((h)->p.obs_pos == EVAC_POS_GRAV ? &evac::KDEF<F_, true> : &evac::KDEF<F_, false>)                  \
+                      : ((h)->p.obs_pos == EVAC_POS_GRAV ? &evac::KGEN<F_, true> : &evac::KGEN<F_, false>))
+#define EVAC_PICK_TEAM(h, KDEF, KGEN)                                                                                       \
+    ((h)->team_k == 16 ? (const void*)EVAC_PICK(h, KDEF, KGEN, evac::Team<16>) :                                             \
+     (h)->team_k == 8 ? (const void*)EVAC_PICK(h, KDEF, KGEN, evac::Team<8>) :                                               \
+     (h)->team_k == 4 ? (const void*)EVAC_PICK(h, KDEF, KGEN, evac::Team<4>) : (const void*)EVAC_PICK(h, KDEF, KGEN, evac::Team<2>))
+const void* team_kernel(const evac_handle* h) { return EVAC_PICK_TEAM(h, k_rollout_default_config, k_rollout); }
+const void* team_persist_kernel(const evac_handle* h) { return EVAC_PICK_TEAM(h, k_rollout_persist_default_config, k_rollout_persist); }
 unsigned team_grid(const evac_handle* h) {
     // (EVAC_TEAM_FAULT=1, fault injection for tests/test_gpu_team.py: the last workgroup is never launched, so the team it
     // belongs to loses a member and must time out, flag the error and leave its env's state alone)
@@ -240,6 +241,27 @@ bool team_grid_fits(evac_handle* h) {
         h->team_fit = (long long)per_cu * h->cus >= (long long)team_grid(h) ? 1 : 0;
     }
     return h->team_fit == 1;
+}
+// A team grid on `s`, behind the previous team grid of the device (g_team_chain; `in_chain` = false under stream capture).  coop:
+// hipLaunchCooperativeKernel (EVAC_TEAM_COOP=1), falling back to a plain launch where it fails.
+hipError_t launch_team_grid(evac_handle* h, const void* fn, void** argv, hipStream_t s, bool in_chain, bool coop) {
+    const dim3 grid(team_grid(h)), block(1024);
+    const bool chained = in_chain && h->device >= 0 && h->device < kMaxDevices;
+    std::unique_lock<std::mutex> chain(g_team_chain_lock, std::defer_lock);
+    if (chained) {                               // (see g_team_chain: the previous team grid of this device has drained)
+        chain.lock();
+        hipEvent_t& ev = g_team_chain[h->device];
+        if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); ev = nullptr; }
+        if (ev && hipStreamWaitEvent(s, ev, 0) != hipSuccess) (void)hipGetLastError();      // (a never-recorded event: no wait)
+    }
+    hipError_t le = coop ? hipLaunchCooperativeKernel(fn, grid, block, argv, 0, s) : hipLaunchKernel(fn, grid, block, argv, 0, s);
+    if (le != hipSuccess && coop) {              // (e.g. under stream capture): the occupancy check still holds for a plain launch
+        (void)hipGetLastError();
+        h->team_coop = false;
+        le = hipLaunchKernel(fn, grid, block, argv, 0, s);
+    }
+    if (chained && g_team_chain[h->device] && le == hipSuccess && hipEventRecord(g_team_chain[h->device], s) != hipSuccess) (void)hipGetLastError();
+    return le;
 }
 
 }  // namespace
@@ -373,29 +395,10 @@ int create_impl(const evac_config_t* cfg, int32_t num_envs, int32_t device, uint
         return EVAC_ERR_NO_DEVICE;
     }
     if (device < 0 || device >= count) { g_create_error = "device index out of range"; return EVAC_ERR_INVALID_ARGUMENT; }
-    evac_handle* h = new (std::nothrow) evac_handle();
+    evac_handle* h = new (std::nothrow) evac_handle();   // (value-initialised: every field not set below is zero / as declared)
     if (!h) { g_create_error = "out of host memory"; return EVAC_ERR_INVALID_ARGUMENT; }
     h->cfg = *cfg;
     h->device = device;
-    h->bound = false;
-    h->n_parts = 1;
-    h->part[0] = h->part[1] = nullptr;
-    h->part_stream[0] = h->part_stream[1] = nullptr;
-    h->part_done[0] = h->part_done[1] = h->fork_ev = nullptr;
-    h->parts_pending = false;
-    h->forked = false;
-    h->chain = h->chain_bound = h->chain_small = false;
-    h->persist = h->persist_running = false;
-    h->persist_seq = h->persist_first = 0;
-    h->chain_gen = h->chain_start = 1;          // (never 0: a zero-filled workspace must not look like a published generation)
-    h->chain_restart = true;
-    h->chain_sched = nullptr;
-    h->chain_xchg = nullptr;
-    h->chain_xchg_bytes = 0;
-    h->chain_abort = nullptr;
-    h->chain_dirty = false;
-    h->chain_wgs = 0;
-    h->chain_ev = nullptr;
     const int o_subwave = option_value("EVAC_SUBWAVE", o.subwave), o_cells = option_value("EVAC_CELLS", o.cells);
     const int o_cu_wide = option_value("EVAC_CU_WIDE", o.cu_wide), o_team = option_value("EVAC_TEAM", o.team);
     const int o_specialize = option_value("EVAC_SPECIALIZE", o.specialize);
@@ -483,17 +486,8 @@ int create_impl(const evac_config_t* cfg, int32_t num_envs, int32_t device, uint
         h->default_cfg = h->default_cfg && obs_default && p.small_noise == 2 && p.ens == 1.0f &&
                          p.one_minus_ens == 0.0f &&
                          (p.flags & (evac::kFlagTermOnWall | evac::kFlagNanGuard)) == 0;
-        h->sched = nullptr;
-        h->sched_gen = -1;
         // teams: as many CUs per env as the batch leaves free -- all members must be resident together (one 1024-thread
         // workgroup per CU), teams are laid out in rows of 8 (one per XCD).  EVAC_TEAM=0 disables, 2 / 4 / 8 / 16 forces a size.
-        h->team_k = 0;
-        h->team_bound = false;
-        h->team_fit = -1;
-        h->team_coop = false;
-        h->team_fault = false;
-        h->team_flag_host = nullptr;
-        h->team_flag_dev = nullptr;
         if (cfg->number_of_pedestrians > 512) {
             const int want = o_team;
             const int rows = (num_envs + 7) / 8 * 8;
@@ -568,46 +562,42 @@ float spin_pair_ms(hipStream_t a, hipStream_t b, hipEvent_t e0, hipEvent_t e1, h
     if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { (void)hipGetLastError(); return -1.0f; }
     return ms;
 }
-bool make_part_streams(evac_handle* h) {
+bool make_own_streams(evac_handle* h) {
     DeviceGuard g(h->device);
     hipEvent_t e0 = nullptr, e1 = nullptr, eb = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_pool_mu);
         for (size_t i = 0; i < g_pool_pairs.size(); ++i)
             if (g_pool_pairs[i].device == h->device) {        // a pair an earlier handle found to overlap, idle since that handle was destroyed
-                h->part_stream[0] = g_pool_pairs[i].s[0];
-                h->part_stream[1] = g_pool_pairs[i].s[1];
+                h->own.s[0] = g_pool_pairs[i].s[0];
+                h->own.s[1] = g_pool_pairs[i].s[1];
                 g_pool_pairs.erase(g_pool_pairs.begin() + (long)i);
                 break;
             }
     }
-    if (h->part_stream[0]) {
-        bool ok = true;
-        for (int k = 0; ok && k < 2; ++k) ok = hipEventCreateWithFlags(&h->part_done[k], hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        return ok;
+    bool ok = h->own.s[0] != nullptr;
+    if (!ok) {
+        ok = hipStreamCreateWithFlags(&h->own.s[0], hipStreamNonBlocking) == hipSuccess && hipEventCreate(&e0) == hipSuccess &&
+             hipEventCreate(&e1) == hipSuccess && hipEventCreate(&eb) == hipSuccess;
     }
-    bool ok = hipStreamCreateWithFlags(&h->part_stream[0], hipStreamNonBlocking) == hipSuccess && hipEventCreate(&e0) == hipSuccess &&
-              hipEventCreate(&e1) == hipSuccess && hipEventCreate(&eb) == hipSuccess;
-    if (ok) {
-        (void)spin_pair_ms(h->part_stream[0], nullptr, e0, e1, eb);                 // (first launch: the code object is loaded)
-        const float one = spin_pair_ms(h->part_stream[0], nullptr, e0, e1, eb);
+    if (ok && !h->own.s[1]) {
+        (void)spin_pair_ms(h->own.s[0], nullptr, e0, e1, eb);                 // (first launch: the code object is loaded)
+        const float one = spin_pair_ms(h->own.s[0], nullptr, e0, e1, eb);
         hipStream_t dropped[8];
         int n_dropped = 0;
         for (int c = 0; ok && c < 8; ++c) {
             hipStream_t cand = nullptr;
             if (hipStreamCreateWithFlags(&cand, hipStreamNonBlocking) != hipSuccess) { ok = false; break; }
-            (void)spin_pair_ms(h->part_stream[0], cand, e0, e1, eb);                // (first use: the stream gets its queue here)
-            const float pair = spin_pair_ms(h->part_stream[0], cand, e0, e1, eb);
-            if (c == 7 || (one > 0.0f && pair > 0.0f && pair < 1.5f * one)) { h->part_stream[1] = cand; break; }
+            (void)spin_pair_ms(h->own.s[0], cand, e0, e1, eb);                // (first use: the stream gets its queue here)
+            const float pair = spin_pair_ms(h->own.s[0], cand, e0, e1, eb);
+            if (c == 7 || (one > 0.0f && pair > 0.0f && pair < 1.5f * one)) { h->own.s[1] = cand; break; }
             dropped[n_dropped++] = cand;          // (kept until the search ends: its queue assignment stays used up, which moves the next candidate on)
         }
         for (int k = 0; k < n_dropped; ++k) (void)hipStreamDestroy(dropped[k]);
-        ok = ok && h->part_stream[1] != nullptr;
+        ok = ok && h->own.s[1] != nullptr;
     }
-    for (int k = 0; ok && k < 2; ++k) ok = hipEventCreateWithFlags(&h->part_done[k], hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming) == hipSuccess;
+    for (int k = 0; ok && k < 2; ++k) ok = hipEventCreateWithFlags(&h->own.done[k], hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&h->own.fork, hipEventDisableTiming) == hipSuccess;
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (eb) (void)hipEventDestroy(eb);
@@ -616,146 +606,151 @@ bool make_part_streams(evac_handle* h) {
 }
 // a command for the resident kernel: the payload, a store fence, then the sequence number in the same 64-byte segment (through the BAR)
 void post_command(evac_handle* h, int n_steps, const void* slab, const void* stats, const void* actions) {
-    volatile evac::PersistCmd* c = (volatile evac::PersistCmd*)(h->chain_xchg + (size_t)(h->persist_seq & (evac::kPersistRing - 1)) * 64);
+    volatile evac::PersistCmd* c = (volatile evac::PersistCmd*)(h->xchg + (size_t)(h->persist.seq & (evac::kPersistRing - 1)) * 64);
     c->slab = (unsigned long long)(uintptr_t)slab;
     c->stats = (unsigned long long)(uintptr_t)stats;
     c->actions = (unsigned long long)(uintptr_t)actions;
     c->n_steps = n_steps;
     __atomic_thread_fence(__ATOMIC_SEQ_CST);
-    c->seq = (unsigned)h->persist_seq + 1u;
+    c->seq = (unsigned)h->persist.seq + 1u;
     __atomic_thread_fence(__ATOMIC_SEQ_CST);
-    h->persist_seq += 1;
+    h->persist.seq += 1;
 }
-void destroy_parts(evac_handle* h) {
+// gives back what the handle took for its form (evac_destroy, or a form that could not be set up): the own streams to the pool, the
+// parts, the uncached area; the handle is Plain afterwards.  (evac_destroy has settled first: the own streams are only drained here.)
+void release_own(evac_handle* h) {
     DeviceGuard g(h->device);
-    if (h->persist && h->persist_running) {            // (a handle destroyed without a join: the resident kernel is told to end)
-        post_command(h, 0, nullptr, nullptr, nullptr);     //  -- and would leave by itself for lack of commands anyway
-        h->persist_running = false;
-    }
     for (int k = 0; k < 2; ++k)
-        if (h->part_stream[k]) (void)hipStreamSynchronize(h->part_stream[k]);
-    if (h->part_stream[0] && h->part_stream[1] && pools_on()) {
+        if (h->own.s[k]) (void)hipStreamSynchronize(h->own.s[k]);
+    if (h->own.s[0] && h->own.s[1] && pools_on()) {
         std::lock_guard<std::mutex> lk(g_pool_mu);
-        g_pool_pairs.push_back(PooledPair{h->device, {h->part_stream[0], h->part_stream[1]}});
-        h->part_stream[0] = h->part_stream[1] = nullptr;
+        g_pool_pairs.push_back(PooledPair{h->device, {h->own.s[0], h->own.s[1]}});
+        h->own.s[0] = h->own.s[1] = nullptr;
     }
     for (int k = 0; k < 2; ++k) {
-        if (h->part_stream[k]) (void)hipStreamDestroy(h->part_stream[k]);
-        if (h->part_done[k]) (void)hipEventDestroy(h->part_done[k]);
+        if (h->own.s[k]) (void)hipStreamDestroy(h->own.s[k]);
+        if (h->own.done[k]) (void)hipEventDestroy(h->own.done[k]);
         if (h->part[k]) {
             give_error_word(h->device, (void*)h->part[k]->team_flag_host, (void*)h->part[k]->team_flag_dev);
             delete h->part[k];
         }
-        h->part_stream[k] = nullptr; h->part_done[k] = nullptr; h->part[k] = nullptr;
+        h->part[k] = nullptr;
     }
-    if (h->fork_ev) (void)hipEventDestroy(h->fork_ev);
-    if (h->chain_ev) (void)hipEventDestroy(h->chain_ev);
-    give_uncached(h->device, h->chain_xchg, h->chain_xchg_bytes);
-    h->chain_xchg = nullptr;
-    h->fork_ev = h->chain_ev = nullptr;
-    h->chain = false;
-    h->persist = false;
-    h->n_parts = 1;
-    h->parts_pending = false;
+    if (h->own.fork) (void)hipEventDestroy(h->own.fork);
+    if (h->last_ev) (void)hipEventDestroy(h->last_ev);
+    give_uncached(h->device, h->xchg, h->xchg_bytes);
+    h->own = {};
+    h->xchg = nullptr;
+    h->xchg_bytes = 0;
+    h->last_ev = nullptr;
+    h->form = Form::Plain;
 }
-// `stream` waits for everything the part streams have been given so far (evac_join; implied by every call that is not a plain rollout)
+// the explicit deal (k_schedule) on `s`: evac_reschedule, and the first launch under a fresh schedule
 void deal_now(evac_handle_t h, hipStream_t s, bool both);
+// What the next launch under the schedule (moving[2][E] | perm[2][E]) gets: launch g reads perm[g & 1] and leaves its loads in
+// moving[g & 1]; `deals`: its workgroup 0 also deals perm[(g + 1) & 1] for the next launch from the loads in moving[(g + 1) & 1]
+struct Deal { const int32_t* perm; int32_t* moving; const int32_t* loads; int32_t* next; };
+Deal deal_of(const evac_handle* h, bool deals) {
+    const int E = h->p.n_envs, g = h->sched_gen;
+    const bool dealt = h->sched && g >= 0;                  // (never dealt yet, e.g. a first launch under capture: identity)
+    deals = deals && dealt;
+    return Deal{dealt ? h->sched + (2 + (g & 1)) * E : nullptr, h->sched ? h->sched + (dealt ? (g & 1) : 0) * E : nullptr,
+                deals ? h->sched + ((g + 1) & 1) * E : nullptr, deals ? h->sched + (2 + ((g + 1) & 1)) * E : nullptr};
+}
 // The persistent rollout kernel on the handle's stream.  fresh: the first kernel after a join -- every env starts at command
-// h->persist_seq, workgroup 0 deals the next kernel's envs as it starts; resume: every env at the command it had reached when the kernel
+// h->persist.seq, workgroup 0 deals the next kernel's envs as it starts; resume: every env at the command it had reached when the kernel
 // before left; stop_at: the index of a STOP command that is already in the ring (the finisher of a join), else INT_MAX.
 int launch_persistent(evac_handle* h, int resume, int stop_at, bool fresh) {
     using FW = evac::Wave<1, 1024>;
     using FW4 = evac::Wave<4, 1024>;
-    hipStream_t S = h->part_stream[0];
+    hipStream_t S = h->own.s[0];
     const int E = h->p.n_envs;
     if (h->sched && h->sched_gen < 0) deal_now(h, S, true);
-    const int g_ = h->sched_gen;
-    const bool dealt = h->sched && g_ >= 0;
-    const bool deals = dealt && fresh;
-    const int32_t* perm = dealt ? h->sched + (2 + (g_ & 1)) * E : nullptr;
-    int32_t* moving = h->sched ? h->sched + (dealt ? (g_ & 1) : 0) * E : nullptr;
-    const int32_t* deal_loads = deals ? h->sched + ((g_ + 1) & 1) * E : nullptr;       // (workgroup 0 deals the NEXT fresh kernel's envs as it starts)
-    int32_t* deal_perm = deals ? h->sched + (2 + ((g_ + 1) & 1)) * E : nullptr;
-    if (deals) h->sched_gen = g_ + 1;
-    evac::ChainArgs ca{h->chain_xchg, h->persist_seq, nullptr, nullptr, 0, nullptr, resume, stop_at};
-#define EVAC_PERSIST_ARGS h->p, (const int*)perm, (int*)moving, (const int*)deal_loads, (int*)deal_perm, ca
+    const Deal d = deal_of(h, fresh);                       // (workgroup 0 deals the NEXT fresh kernel's envs as it starts)
+    if (d.next) h->sched_gen += 1;
+    evac::ChainArgs ca{h->xchg, h->persist.seq, nullptr, nullptr, 0, nullptr, resume, stop_at};
     if (h->team_k) {
         // a team grid (evac_team.h): the exchange area starts with the tag of no round, the teams' verdicts at zero; team grids of one
         // device take turns (g_team_chain), whatever handle or stream they come from
-        int32_t* decision = (int32_t*)(h->chain_xchg + (size_t)evac::kPersistRing * 64 + 128) + E;
+        int32_t* decision = (int32_t*)(h->xchg + (size_t)evac::kPersistRing * 64 + 128) + E;
         if (hipMemsetAsync(h->p.team_rec, 0xff, h->team_xchg_bytes, S) != hipSuccess || hipMemsetAsync(decision, 0, 4 * (size_t)E, S) != hipSuccess) {
             (void)hipGetLastError();
             return fail(h, EVAC_ERR_HIP, "evac_rollout (persistent team kernel): hipMemsetAsync failed");
         }
-        const dim3 grid(team_grid(h)), block(1024);
         const int* np_ = nullptr;
         int* nq_ = nullptr;
         void* argv[] = {(void*)&h->p, (void*)&np_, (void*)&nq_, (void*)&np_, (void*)&nq_, (void*)&ca};
-        const bool chained = h->device >= 0 && h->device < kMaxDevices;
-        std::unique_lock<std::mutex> chain(g_team_chain_lock, std::defer_lock);
-        if (chained) {
-            chain.lock();
-            hipEvent_t& ev = g_team_chain[h->device];
-            if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); ev = nullptr; }
-            if (ev && hipStreamWaitEvent(S, ev, 0) != hipSuccess) (void)hipGetLastError();
-        }
-        const hipError_t le = hipLaunchKernel(team_persist_kernel(h), grid, block, argv, 0, S);
-        if (chained && g_team_chain[h->device] && le == hipSuccess && hipEventRecord(g_team_chain[h->device], S) != hipSuccess) (void)hipGetLastError();
-        if (chained) chain.unlock();
+        const hipError_t le = launch_team_grid(h, team_persist_kernel(h), argv, S, /*in_chain=*/true, /*coop=*/false);
         if (le != hipSuccess) return fail(h, EVAC_ERR_HIP, std::string("evac_rollout (persistent team kernel): ") + hipGetErrorString(le));
-    } else if (h->cu_wide4) {
-        const dim3 grid((unsigned)(E / FW4::kEnvsPerBlock));
-        if (h->default_cfg && h->p.obs_pos == EVAC_POS_GRAV)
-            hipLaunchKernelGGL((evac::k_rollout_persist_default_config<FW4, true>), grid, dim3(FW4::kBlock), 0, S, EVAC_PERSIST_ARGS);
-        else if (h->default_cfg)
-            hipLaunchKernelGGL((evac::k_rollout_persist_default_config<FW4, false>), grid, dim3(FW4::kBlock), 0, S, EVAC_PERSIST_ARGS);
-        else if (h->p.obs_pos == EVAC_POS_GRAV)
-            hipLaunchKernelGGL((evac::k_rollout_persist<FW4, true>), grid, dim3(FW4::kBlock), 0, S, EVAC_PERSIST_ARGS);
-        else
-            hipLaunchKernelGGL((evac::k_rollout_persist<FW4, false>), grid, dim3(FW4::kBlock), 0, S, EVAC_PERSIST_ARGS);
     } else {
-        const dim3 grid((unsigned)(E / FW::kEnvsPerBlock));
-        if (h->default_cfg && h->p.obs_pos == EVAC_POS_GRAV)
-            hipLaunchKernelGGL((evac::k_rollout_persist_default_config<FW, true>), grid, dim3(FW::kBlock), 0, S, EVAC_PERSIST_ARGS);
-        else if (h->default_cfg)
-            hipLaunchKernelGGL((evac::k_rollout_persist_default_config<FW, false>), grid, dim3(FW::kBlock), 0, S, EVAC_PERSIST_ARGS);
-        else if (h->p.obs_pos == EVAC_POS_GRAV)
-            hipLaunchKernelGGL((evac::k_rollout_persist<FW, true>), grid, dim3(FW::kBlock), 0, S, EVAC_PERSIST_ARGS);
-        else
-            hipLaunchKernelGGL((evac::k_rollout_persist<FW, false>), grid, dim3(FW::kBlock), 0, S, EVAC_PERSIST_ARGS);
+        const bool four = h->cu_wide4;
+        const auto fn = four ? EVAC_PICK(h, k_rollout_persist_default_config, k_rollout_persist, FW4)
+                             : EVAC_PICK(h, k_rollout_persist_default_config, k_rollout_persist, FW);
+        const dim3 grid((unsigned)(E / (four ? FW4::kEnvsPerBlock : FW::kEnvsPerBlock)));
+        hipLaunchKernelGGL(fn, grid, dim3(four ? FW4::kBlock : FW::kBlock), 0, S, h->p, d.perm, d.moving, d.loads, d.next, ca);
     }
-#undef EVAC_PERSIST_ARGS
     if (const int lc = check_launch(h, "evac_rollout (persistent kernel)"); lc != EVAC_OK) return lc;
-    if (hipEventRecord(h->chain_ev, S) != hipSuccess) { (void)hipGetLastError(); return fail(h, EVAC_ERR_HIP, "evac_rollout: event record behind the persistent kernel failed"); }
+    if (hipEventRecord(h->last_ev, S) != hipSuccess) { (void)hipGetLastError(); return fail(h, EVAC_ERR_HIP, "evac_rollout: event record behind the persistent kernel failed"); }
     return EVAC_OK;
 }
 // STOP, and behind the resident kernel a FINISHER: a kernel that takes up every env that has not yet run everything up to the STOP (the
 // resident kernel may have left, or be leaving, for lack of commands) and ends at once where there is nothing to do.
 int stop_persistent(evac_handle* h) {
-    const int stop_index = h->persist_seq;
+    const int stop_index = h->persist.seq;
     post_command(h, 0, nullptr, nullptr, nullptr);
-    h->persist_running = false;
+    h->persist.running = false;
     return launch_persistent(h, /*resume=*/1, stop_index, /*fresh=*/false);
 }
-int join_parts(evac_handle* h, hipStream_t stream) {
-    if (!h->part_stream[0] || !h->parts_pending) return EVAC_OK;
+// SETTLE the handle: `stream` waits for everything the own streams have been given so far, and the caller's state arrays are the state
+// again, whatever the form -- a resident persistent kernel is told to STOP (+ the finisher), the chain's records are exported and the chain
+// starts afresh behind whatever follows, since that may write the state.  evac_join is this; every call on the handle that is not a
+// rollout in its form does it first (include/evac.h).  host_wait: the host waits for the settled work too -- before a rebind, whose old
+// buffers the launches in flight still use.
+int settle(evac_handle* h, hipStream_t stream, bool host_wait = false) {
+    if (h->form == Form::Chain) h->chain.restart = true;
+    if (!h->own.pending) return EVAC_OK;
     DeviceGuard g(h->device);
-    if (h->persist && h->persist_running)              // STOP: the waves store their state and the kernel ends (+ the finisher)
+    if (h->form == Form::Persist && h->persist.running)     // STOP: the waves store their state and the kernel ends (+ the finisher)
         if (const int rc = stop_persistent(h); rc != EVAC_OK) return rc;
     for (int k = 0; k < 2; ++k)
-        if (hipEventRecord(h->part_done[k], h->part_stream[k]) != hipSuccess || hipStreamWaitEvent(stream, h->part_done[k], 0) != hipSuccess) {
+        if (hipEventRecord(h->own.done[k], h->own.s[k]) != hipSuccess || hipStreamWaitEvent(stream, h->own.done[k], 0) != hipSuccess) {
             (void)hipGetLastError();
             return fail(h, EVAC_ERR_HIP, "evac_join: event record / wait failed");
         }
-    h->parts_pending = false;
-    h->forked = false;
-    if (h->chain && h->chain_dirty && h->chain_xchg) {     // the chain's launches kept the state in the exchange records: back to the caller's arrays
+    h->own.pending = false;
+    h->own.forked = false;
+    if (h->form == Form::Chain && h->chain.dirty) {     // the chain's launches kept the state in the exchange records: back to the caller's arrays
         const int wpe = h->cu_wide4 ? 4 : 1;
-        hipLaunchKernelGGL(evac::k_chain_export, dim3((unsigned)((h->p.n_envs * wpe + 3) / 4)), dim3(256), 0, stream, h->p, (const char*)h->chain_xchg, wpe);
-        h->chain_dirty = false;
+        hipLaunchKernelGGL(evac::k_chain_export, dim3((unsigned)((h->p.n_envs * wpe + 3) / 4)), dim3(256), 0, stream, h->p, (const char*)h->xchg, wpe);
+        h->chain.dirty = false;
         if (hipGetLastError() != hipSuccess) return fail(h, EVAC_ERR_HIP, "evac_join: export of the chain's state failed");
     }
+    if (host_wait && hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); return fail(h, EVAC_ERR_HIP, "hipDeviceSynchronize failed"); }
     return EVAC_OK;
+}
+// What the chained and the persistent form allocate themselves, in the device's pools: the own streams, an error word (a handle has one:
+// the teams' serves the form too), `bytes` of uncached device memory (zeroed) and last_ev.  false: the handle keeps none of it but the word.
+bool take_form_resources(evac_handle* h, size_t bytes) {
+    bool ok = make_own_streams(h);
+    DeviceGuard g(h->device);
+    if (ok && !h->team_flag_host) {
+        void* host = nullptr;
+        void* dev = nullptr;
+        ok = take_error_word(h->device, &host, &dev);
+        h->team_flag_host = (volatile unsigned*)host;
+        h->team_flag_dev = (unsigned*)dev;
+    }
+    ok = ok && hipEventCreateWithFlags(&h->last_ev, hipEventDisableTiming) == hipSuccess;
+    if (ok) {
+        h->xchg = (char*)take_uncached(h->device, bytes, &h->xchg_bytes);
+        ok = h->xchg != nullptr;
+    }
+    if (ok && (hipMemset(h->xchg, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) ok = false;   // (hipMemset does not wait)
+    if (!ok) {
+        (void)hipGetLastError();
+        release_own(h);
+    }
+    return ok;
 }
 }  // namespace
 
@@ -789,87 +784,41 @@ int evac_create_ex(const evac_config_t* cfg, int32_t num_envs, int32_t device, u
     // ... and the 256-thread workgroups of one-wave envs (four envs each), on request only (chain = 1 with cu_wide = 0)
     const bool chain_small = chain_opt == 1 && !h->cu_wide && !h->cu_wide4 && h->sub_lanes == 0 && !h->cells && !h->team_k &&
                              waves_per_env(h->p.n_ped) == 1 && num_envs % 4 == 0 && num_envs >= 8;
-    h->chain_small = chain_small;
     // chain = 2: ONE PERSISTENT KERNEL PER JOIN (evac_common.h, PersistCmd).  The CU-wide kernels only (every workgroup resident at once: the grid
     // must fit the device), and only where the host can write device memory directly (large BAR): the command ring lives in uncached device
     // memory, written by the CPU -- no stream operation of ours could run while the resident kernel holds every CU.
-    if (chain_opt == 2) {
-        int large_bar = 0;
-        if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, device) != hipSuccess) { (void)hipGetLastError(); large_bar = 0; }
-        const int per_wg = h->cu_wide4 ? 4 : 16;
-        // (teams -- one env on K CUs: the grid's fit is checked where it is for plain team launches, at the call, once the exchange areas are bound)
-        const bool fits = ((h->cu_wide || h->cu_wide4) && num_envs % per_wg == 0 && num_envs / per_wg <= h->cus) || (h->team_k != 0 && !h->team_fault);
-        bool ok = large_bar != 0 && fits && make_part_streams(h);
-        if (ok) {
-            DeviceGuard g(device);
-            void* host = (void*)h->team_flag_host;
-            void* dev = (void*)h->team_flag_dev;
-            if (!host && !take_error_word(device, &host, &dev)) ok = false;
-            if (ok) { h->team_flag_host = (volatile unsigned*)host; h->team_flag_dev = (unsigned*)dev; }
-            ok = ok && hipEventCreateWithFlags(&h->chain_ev, hipEventDisableTiming) == hipSuccess;      // (behind every persistent kernel: has it left?)
-            void* ring = nullptr;
-            const size_t rbytes = (size_t)evac::kPersistRing * 64 + 128 + 8 * (size_t)num_envs;      // the ring, a line of diagnostics, next_cmd[E], decision[E] (teams)
-            if (ok) { ring = take_uncached(device, rbytes, &h->chain_xchg_bytes); ok = ring != nullptr; }
-            if (ok && (hipMemset(ring, 0, rbytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { (void)hipGetLastError(); ok = false; }
-            h->chain_xchg = (char*)ring;
-            if (ok) h->chain_abort = (unsigned*)((char*)ring + (size_t)evac::kPersistRing * 64);
-        }
-        if (ok) {
-            h->persist = true;
-            h->opt.chain = 2;
-            h->variant[3] = h->variant[1] + ", one persistent kernel per join";
-            return EVAC_OK;
-        }
-        if (h->part_stream[0]) destroy_parts(h);       // (not possible here: chained launches if they are, else plain ones)
+    // Where a form cannot be set up, the handle falls back to the next one: persistent, chained, parts, plain.
+    int large_bar = 0;
+    if (chain_opt == 2 && hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, device) != hipSuccess) { (void)hipGetLastError(); large_bar = 0; }
+    const int per_wg = h->cu_wide4 ? 4 : 16;
+    // (teams -- one env on K CUs: the grid's fit is checked where it is for plain team launches, at the call, once the exchange areas are bound)
+    const bool persist_fits = ((h->cu_wide || h->cu_wide4) && num_envs % per_wg == 0 && num_envs / per_wg <= h->cus) || (h->team_k != 0 && !h->team_fault);
+    const size_t ring_bytes = (size_t)evac::kPersistRing * 64 + 128 + 8 * (size_t)num_envs;      // the ring, a line of diagnostics, next_cmd[E], decision[E] (teams)
+    if (chain_opt == 2 && large_bar != 0 && persist_fits && take_form_resources(h, ring_bytes)) {
+        h->abort_word = (unsigned*)(h->xchg + (size_t)evac::kPersistRing * 64);
+        h->form = Form::Persist;
+        h->opt.chain = 2;
+        h->variant[3] = h->variant[1] + ", one persistent kernel per join";
+        return EVAC_OK;
     }
-    if (chain_opt != 0 && can_wait_value && (chain_one_wave || chain_four_waves || chain_small)) {
-        bool ok = make_part_streams(h);
-        {
-            DeviceGuard g(device);
-            void* host = nullptr;
-            void* dev = nullptr;
-            ok = ok && hipEventCreateWithFlags(&h->chain_ev, hipEventDisableTiming) == hipSuccess;
-            if (ok && h->team_flag_host) {          // (a handle has one error word: the teams' serves the chain too)
-                host = (void*)h->team_flag_host;
-                dev = (void*)h->team_flag_dev;
-            } else if (ok && !take_error_word(device, &host, &dev)) {
-                ok = false;
-            }
-            if (ok) {
-                h->team_flag_host = (volatile unsigned*)host;
-                h->team_flag_dev = (unsigned*)dev;
-            } else {
-                (void)hipGetLastError();
-            }
-            // The exchange records (evac_common.h) live in UNCACHED device memory, the second thing a chained handle allocates
-            // itself.  In ordinary hipMalloc memory -- the caller's workspace -- a record line can sit in the L2 of an XCD that once
-            // touched it with a plain access (the workspace's zero fill, the import), and another XCD's write-through store does not
-            // refresh that copy: an import written with `sc1` stores over the zero-filled workspace read back as zeros in ~1.5 of a
-            // record's 12 lines (tools/chain_debug.py, round 6).  A plain-store import cured that case, but the same can happen to the
-            // import's own lines once a batch that fills the chip lets workgroups land on whatever XCD has room.  Memory that no L2
-            // ever holds removes the question: 1.5 KB per env and launch at memory speed is nothing next to 20 steps.
-            void* xchg = nullptr;
-            const size_t xbytes = (size_t)num_envs * (size_t)evac::xchg_bytes(h->cu_wide4 ? 256 : 64);
-            if (ok) {
-                xchg = take_uncached(device, xbytes, &h->chain_xchg_bytes);
-                ok = xchg != nullptr;
-            }
-            if (ok && (hipMemset(xchg, 0, xbytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { (void)hipGetLastError(); ok = false; }   // (hipMemset does not wait)
-            h->chain_xchg = (char*)xchg;
-        }
-        if (ok) {
-            h->chain = true;
-            h->opt.chain = 1;
-            h->variant[3] = h->variant[1] + ", chained launches on 2 streams";
-            (void)chain_one_wave;
-            return EVAC_OK;
-        }
-        destroy_parts(h);                              // (no second queue: plain launches)
+    // The exchange records (evac_common.h) live in UNCACHED device memory, the second thing a chained handle allocates
+    // itself.  In ordinary hipMalloc memory -- the caller's workspace -- a record line can sit in the L2 of an XCD that once
+    // touched it with a plain access (the workspace's zero fill, the import), and another XCD's write-through store does not
+    // refresh that copy: an import written with `sc1` stores over the zero-filled workspace read back as zeros in ~1.5 of a
+    // record's 12 lines (tools/chain_debug.py, round 6).  A plain-store import cured that case, but the same can happen to the
+    // import's own lines once a batch that fills the chip lets workgroups land on whatever XCD has room.  Memory that no L2
+    // ever holds removes the question: 1.5 KB per env and launch at memory speed is nothing next to 20 steps.
+    const size_t xchg_bytes = (size_t)num_envs * (size_t)evac::xchg_bytes(h->cu_wide4 ? 256 : 64);
+    if (chain_opt != 0 && can_wait_value && (chain_one_wave || chain_four_waves || chain_small) && take_form_resources(h, xchg_bytes)) {
+        h->chain.small = chain_small;
+        h->form = Form::Chain;
+        h->opt.chain = 1;
+        h->variant[3] = h->variant[1] + ", chained launches on 2 streams";
+        return EVAC_OK;
     }
     // Two parts: where it pays by itself (-1) -- CU-wide rollouts whose halves are whole CU-wide workgroups; the halves keep the
     // CU-wide form although each alone would not fill the device (pace keeping and the in-kernel deal are what they are to keep) --
     // or on request (2) for every handle but the teams' (their grids run one at a time: evac_rollout).
-    const int per_wg = h->cu_wide4 ? 4 : 16;
     const int parts_opt = option_value("EVAC_PARTS", o.parts);
     const bool can = h->team_k == 0 && num_envs >= 2 && num_envs % 2 == 0;
     const bool pays = (h->cu_wide || h->cu_wide4) && num_envs % (2 * per_wg) == 0;
@@ -878,15 +827,15 @@ int evac_create_ex(const evac_config_t* cfg, int32_t num_envs, int32_t device, u
     po.parts = 1;
     po.chain = 0;
     const int32_t half = num_envs / 2;
-    bool ok = make_part_streams(h);
+    bool ok = make_own_streams(h);
     for (int k = 0; ok && k < 2; ++k) {
         evac_handle_t c = nullptr;
         ok = create_impl(cfg, half, device, seed, env_id_offset + (uint64_t)k * (uint64_t)half, po, &c) == EVAC_OK;
         h->part[k] = c;
         if (ok) c->p.slab_envs = num_envs;
     }
-    if (!ok) { destroy_parts(h); return EVAC_OK; }     // (no second queue, no parts: the handle works as one)
-    h->n_parts = 2;
+    if (!ok) { release_own(h); return EVAC_OK; }      // (no second queue, no parts: the handle works as one)
+    h->form = Form::Parts;
     h->opt.parts = 2;
     h->variant[3] = h->part[0]->variant[1] + " x 2 streams";
     return EVAC_OK;
@@ -900,37 +849,40 @@ int evac_get_options(evac_handle_t h, evac_options_t* out) {
 
 int evac_join(evac_handle_t h, void* stream) {
     if (!h) return EVAC_ERR_INVALID_ARGUMENT;
-    return join_parts(h, (hipStream_t)stream);
+    return settle(h, (hipStream_t)stream);
 }
 int evac_order_next_rollout(evac_handle_t h) {
     if (!h) return EVAC_ERR_INVALID_ARGUMENT;
-    h->forked = false;
+    h->own.forked = false;
     return EVAC_OK;
 }
-int32_t evac_num_parts(evac_handle_t h) { return h ? h->n_parts : -1; }
-int32_t evac_own_streams(evac_handle_t h) { return h ? ((h->n_parts > 1 || h->chain || h->persist) && h->part_stream[0] ? 2 : 0) : -1; }
-void* evac_part_stream(evac_handle_t h, int32_t part) { return (h && evac_own_streams(h) == 2 && part >= 0 && part < 2) ? (void*)h->part_stream[part] : nullptr; }
+int32_t evac_num_parts(evac_handle_t h) { return h ? (h->form == Form::Parts ? 2 : 1) : -1; }
+int32_t evac_own_streams(evac_handle_t h) { return h ? (h->own.s[0] ? 2 : 0) : -1; }     // (the streams stay when evac_team_clear_error falls back)
+void* evac_part_stream(evac_handle_t h, int32_t part) { return (h && h->own.s[0] && part >= 0 && part < 2) ? (void*)h->own.s[part] : nullptr; }
 
 const char* evac_kernel_variant(evac_handle_t h, int32_t rollout) {
     if (!h) return "";
     if (!rollout) return h->variant[0].c_str();
-    if (h->persist) {          // (teams: the persistent form of the team kernel, once its exchange areas are bound and its grid fits)
+    if (h->form == Form::Persist) {          // (teams: the persistent form of the team kernel, once its exchange areas are bound and its grid fits)
         const bool team = h->team_k && h->team_bound && h->team_fit != 0;
         if (h->team_k && !team) return h->variant[1].c_str();
         h->variant[3] = h->variant[team ? 2 : 1] + ", one persistent kernel per join";
         return h->variant[3].c_str();
     }
-    if (h->n_parts > 1 || (h->chain && h->chain_bound)) return h->variant[3].c_str();
+    if (h->form == Form::Parts || (h->form == Form::Chain && h->chain.bound)) return h->variant[3].c_str();
     // the path evac_rollout takes right now: teams only with their exchange areas bound and a grid that fits the device
     return h->variant[(h->team_k && h->team_bound && h->team_fit != 0) ? 2 : 1].c_str();
 }
 
 int evac_destroy(evac_handle_t h) {
-    if (h && (h->n_parts > 1 || h->part_stream[0] || h->chain)) destroy_parts(h);
-    if (h && h->team_flag_host) {
-        DeviceGuard g(h->device);
-        give_error_word(h->device, (void*)h->team_flag_host, (void*)h->team_flag_dev);
-    }
+    if (!h) return EVAC_OK;
+    DeviceGuard g(h->device);
+    (void)settle(h, nullptr);
+    // Nothing the handle launched may still run when its streams and its error word go back to the pools -- the plain team launches on the
+    // caller's streams included: one that timed out later would raise the word of whatever handle takes it next.
+    if (h->own.s[0] || h->team_flag_host) (void)hipDeviceSynchronize();
+    release_own(h);
+    give_error_word(h->device, (void*)h->team_flag_host, (void*)h->team_flag_dev);
     delete h;
     return EVAC_OK;
 }
@@ -950,14 +902,14 @@ int evac_bind_state(evac_handle_t h, float* ped, uint8_t* status, float* agent, 
     if (!ped || !status || !agent || !clock || !acc) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_bind_state: NULL buffer");
     if (((uintptr_t)ped | (uintptr_t)agent | (uintptr_t)clock | (uintptr_t)acc) & 15u)
         return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_bind_state: ped/agent/clock/acc must be 16-byte aligned");
+    if (const int rc = settle(h, nullptr, /*host_wait=*/true); rc != EVAC_OK) return rc;      // (launches in flight use the old buffers)
     h->p.ped = (float4*)ped;
     h->p.status = status;
     h->p.agent = (float4*)agent;
     h->p.clock = (int4*)clock;
     h->p.acc = (float4*)acc;
     h->bound = true;
-    h->chain_restart = true;
-    for (int k = 0; k < (h->n_parts > 1 ? h->n_parts : 0); ++k) {      // the parts: the same buffers from their first env on
+    for (int k = 0; k < (h->form == Form::Parts ? 2 : 0); ++k) {      // the parts: the same buffers from their first env on
         const size_t first = (size_t)k * (size_t)h->part[k]->p.n_envs, N = (size_t)h->p.n_ped;
         const int rc = evac_bind_state(h->part[k], ped + first * N * 4, status + first * N, agent + first * 4, clock + first * 4, acc + first * 4);
         if (rc != EVAC_OK) return fail(h, rc, std::string("evac_bind_state (part): ") + h->part[k]->err);
@@ -976,7 +928,7 @@ WorkspaceLayout workspace_layout(const evac_handle* h) {
     size_t o = 0;
     w.sched = o; o = up(o + 4 * E * sizeof(int32_t));          // moving[2][E] | perm[2][E]
     w.stats = o; o = up(o + 64);
-    if (h->chain) {                                            // moving[4][E] | perm[4][E] | the abort word + started-workgroups counter
+    if (h->form == Form::Chain) {                              // moving[4][E] | perm[4][E] | the abort word + started-workgroups counter
         w.chain_sched = o; o = up(o + 8 * E * sizeof(int32_t));    // (the exchange records are NOT here: they need memory the L2s do not cache,
         w.chain_abort = o; o = up(o + 128);                        //  which the library allocates itself: evac_create_ex)
     }
@@ -993,28 +945,24 @@ WorkspaceLayout workspace_layout(const evac_handle* h) {
 int64_t evac_workspace_bytes(evac_handle_t h) {
     if (!h) return -1;
     size_t total = workspace_layout(h).total, parts = 0;
-    for (int k = 0; k < (h->n_parts > 1 ? h->n_parts : 0); ++k) parts += workspace_layout(h->part[k]).total;   // (the parts carve it up between them)
+    for (int k = 0; k < (h->form == Form::Parts ? 2 : 0); ++k) parts += workspace_layout(h->part[k]).total;   // (the parts carve it up between them)
     return (int64_t)(parts > total ? parts : total);
 }
 
 int evac_bind_workspace(evac_handle_t h, void* workspace, int64_t bytes) {
     if (!h) return EVAC_ERR_INVALID_ARGUMENT;
+    if (const int rc = settle(h, nullptr, /*host_wait=*/true); rc != EVAC_OK) return rc;    // (launches in flight use the old workspace)
     h->sched = nullptr;
     h->sched_gen = -1;
     h->team_bound = false;
-    if ((h->chain && (h->parts_pending || h->chain_dirty)) || (h->persist && h->parts_pending)) {      // (launches in flight still use the old workspace; the chain's state lives in it)
-        DeviceGuard g(h->device);
-        (void)join_parts(h, nullptr);
-        (void)hipDeviceSynchronize();
-    }
-    h->chain_bound = false;
-    if (h->n_parts > 1) {
+    h->chain.bound = false;
+    if (h->form == Form::Parts) {
         // the parts schedule themselves: each gets a slice (moving[2][E/2] | perm[2][E/2] of its own); this handle's own rollouts --
         // the diagnostic face only -- run without a schedule
         if (workspace && (bytes < evac_workspace_bytes(h) || ((uintptr_t)workspace & 255u)))
             return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_bind_workspace: workspace smaller than evac_workspace_bytes() or not 256-byte aligned");
         size_t o = 0;
-        for (int k = 0; k < h->n_parts; ++k) {
+        for (int k = 0; k < 2; ++k) {
             const size_t t = workspace_layout(h->part[k]).total;
             const int rc = evac_bind_workspace(h->part[k], workspace ? (char*)workspace + o : nullptr, (int64_t)t);
             if (rc != EVAC_OK) return fail(h, rc, std::string("evac_bind_workspace (part): ") + h->part[k]->err);
@@ -1028,14 +976,12 @@ int evac_bind_workspace(evac_handle_t h, void* workspace, int64_t bytes) {
     if ((uintptr_t)workspace & 255u) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_bind_workspace: workspace must be 256-byte aligned");
     char* base = (char*)workspace;
     h->sched = (int32_t*)(base + w.sched);
-    h->chain_bound = false;
-    if (h->chain) {
-        h->chain_sched = (int32_t*)(base + w.chain_sched);
-        h->chain_abort = (unsigned*)(base + w.chain_abort);
-        h->chain_dirty = false;
-        h->chain_wgs = 0;                             // (the workspace comes zero-filled: include/evac.h)
-        h->chain_bound = true;
-        h->chain_restart = true;
+    if (h->form == Form::Chain) {
+        h->chain.sched = (int32_t*)(base + w.chain_sched);
+        h->abort_word = (unsigned*)(base + w.chain_abort);
+        h->chain.dirty = false;
+        h->chain.wgs = 0;                             // (the workspace comes zero-filled: include/evac.h)
+        h->chain.bound = true;
     }
     if (h->team_k) {
         h->p.team_err = h->team_flag_dev;           // (host-mapped memory of the handle, not part of the workspace)
@@ -1064,26 +1010,22 @@ void deal_now(evac_handle_t h, hipStream_t s, bool both) {
 
 int evac_reschedule(evac_handle_t h, void* stream) {
     if (!h) return EVAC_ERR_INVALID_ARGUMENT;
-    if (h->chain) {                                    // (the chain deals itself again when it restarts)
-        h->chain_restart = true;
-        return join_parts(h, (hipStream_t)stream);
-    }
-    if (h->n_parts > 1) {                              // (on the caller's stream, behind everything the parts have been given)
-        if (const int rc = join_parts(h, (hipStream_t)stream); rc != EVAC_OK) return rc;
-        for (int k = 0; k < h->n_parts; ++k)
+    // (on the caller's stream, behind everything the own streams have been given: a resident kernel keeps the deal it started with)
+    if (const int rc = settle(h, (hipStream_t)stream); rc != EVAC_OK) return rc;
+    if (h->form == Form::Chain) return EVAC_OK;       // (the chain deals itself again when it restarts)
+    if (h->form == Form::Parts) {
+        for (int k = 0; k < 2; ++k)
             if (const int rc = evac_reschedule(h->part[k], stream); rc != EVAC_OK) return fail(h, rc, h->part[k]->err);
         return EVAC_OK;
     }
     if (!h->sched || !(h->cu_wide || h->cu_wide4)) return EVAC_OK;       // nothing to deal
-    if (h->persist && h->parts_pending)                                   // (the resident kernel keeps the deal it started with: it ends first)
-        if (const int rc = join_parts(h, (hipStream_t)stream); rc != EVAC_OK) return rc;
     DeviceGuard g(h->device);
     deal_now(h, (hipStream_t)stream, true);
     return check_launch(h, "evac_reschedule");
 }
 
 int32_t evac_schedule_generation(evac_handle_t h) {
-    if (h && h->n_parts > 1) return evac_schedule_generation(h->part[0]);
+    if (h && h->form == Form::Parts) return evac_schedule_generation(h->part[0]);
     return (h && h->sched && (h->cu_wide || h->cu_wide4)) ? h->sched_gen : -1;
 }
 
@@ -1136,26 +1078,27 @@ int evac_team_error_nosync(evac_handle_t h, int32_t* out) {
 
 int evac_team_clear_error(evac_handle_t h) {
     if (!h) return EVAC_ERR_INVALID_ARGUMENT;
-    if (h->team_flag_host) {
-        if (*h->team_flag_host != 0u) { h->team_k = 0; h->chain = false; h->persist = false; }     // the handle stays on one workgroup per env / on plain launches
-        *h->team_flag_host = 0u;
+    if (!h->team_flag_host) return EVAC_OK;
+    if (const int rc = settle(h, nullptr, /*host_wait=*/true); rc != EVAC_OK) return rc;
+    if (*h->team_flag_host != 0u) {                  // the handle stays on one workgroup per env and on plain launches
+        h->team_k = 0;
+        h->form = Form::Plain;
     }
+    *h->team_flag_host = 0u;
     return EVAC_OK;
 }
 
-// (a handle with two parts: whatever is not a plain rollout first makes the caller's stream wait for the parts' streams)
 #define EVAC_REQUIRE_BOUND(h, name)                                               \
     if (!(h)) return EVAC_ERR_INVALID_ARGUMENT;                                  \
     if (!(h)->bound) return fail((h), EVAC_ERR_NOT_BOUND, name ": call evac_bind_state first"); \
     if (const int ta_ = team_aborted((h), name); ta_ != EVAC_OK) return ta_
-#define EVAC_JOIN_FIRST(h, stream)                                                \
-    (h)->chain_restart = true;      /* (whatever follows may write the state: the chain starts afresh behind it) */ \
-    if ((h)->parts_pending)                                                       \
-        if (const int jn_ = join_parts((h), (hipStream_t)(stream)); jn_ != EVAC_OK) return jn_
+// (whatever is not a rollout in the handle's form settles it first: the caller's arrays are the state, `stream` behind the own streams)
+#define EVAC_REQUIRE_SETTLED(h, name, stream)                                     \
+    EVAC_REQUIRE_BOUND(h, name);                                                  \
+    if (const int st_ = settle((h), (hipStream_t)(stream)); st_ != EVAC_OK) return st_
 
 int evac_reset(evac_handle_t h, const uint8_t* mask, const float* draws, float* obs_out, void* stream) {
-    EVAC_REQUIRE_BOUND(h, "evac_reset");
-    EVAC_JOIN_FIRST(h, stream);
+    EVAC_REQUIRE_SETTLED(h, "evac_reset", stream);
     if (draws && ((uintptr_t)draws & 15u)) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_reset: draws must be 16-byte aligned");
     DeviceGuard g(h->device);
     EVAC_DISPATCH(h, k_reset, stream, h->p, mask, (const float4*)draws, obs_out);
@@ -1181,8 +1124,7 @@ static int step_common(evac_handle_t h, const char* name, const float* actions, 
 int evac_step(evac_handle_t h, const float* actions, const float* noise, float* obs_out, float* reward_out,
               uint8_t* terminated_out, uint8_t* truncated_out, int32_t autoreset, float* final_obs,
               evac_episode_stats_t* final_stats, void* stream) {
-    EVAC_REQUIRE_BOUND(h, "evac_step");
-    EVAC_JOIN_FIRST(h, stream);
+    EVAC_REQUIRE_SETTLED(h, "evac_step", stream);
     return step_common(h, "evac_step", actions, noise, obs_out, reward_out, terminated_out, truncated_out, autoreset, final_obs,
                        final_stats, evac::NormArgs{nullptr, 0.f, 0.f, 0.f, 0.f}, stream);
 }
@@ -1191,11 +1133,227 @@ int evac_step_normalized(evac_handle_t h, const float* actions, const float* noi
                          uint8_t* terminated_out, uint8_t* truncated_out, int32_t autoreset, float* final_obs,
                          evac_episode_stats_t* final_stats, double* norm_state, float gamma, float obs_clip,
                          float reward_clip, float epsilon, void* stream) {
-    EVAC_REQUIRE_BOUND(h, "evac_step_normalized");
-    EVAC_JOIN_FIRST(h, stream);
+    EVAC_REQUIRE_SETTLED(h, "evac_step_normalized", stream);
     if (!norm_state) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_step_normalized: norm_state is NULL");
     return step_common(h, "evac_step_normalized", actions, noise, obs_out, reward_out, terminated_out, truncated_out, autoreset,
                        final_obs, final_stats, evac::NormArgs{norm_state, gamma, obs_clip, reward_clip, epsilon}, stream);
+}
+
+// ---- evac_rollout, one function per form ----
+static bool capturing(hipStream_t s) {
+    hipStreamCaptureStatus c = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &c) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return c != hipStreamCaptureStatusNone;
+}
+
+// Form::Parts: two half-batch kernels on the handle's own streams, both behind what `stream` holds so far; `stream` is NOT made to
+// wait for them (evac_join): consecutive rollout calls must not meet, or the halves would run in lock-step
+static int rollout_parts(evac_handle* h, int32_t n_steps, const float* actions, float* slab_out, evac_episode_stats_t* final_stats, hipStream_t s_) {
+    // (the fork costs a barrier packet in front of each kernel -- 7-10 us on this platform whether or not the event has fired,
+    // DESIGN.md 6 -- which is more than the parts gain.  So the own streams are put behind the caller's stream ONCE per join: at
+    // the first rollout call after evac_join / any other call on the handle, and at every call that brings inputs (actions).
+    // Asking the stream instead -- hipStreamQuery -- was tried: the query leaves a marker in the stream, the next query finds it
+    // busy, and the handle falls into forking at every call: a second, 15-40 % slower mode of the same program.)
+    if (!h->own.forked || actions != nullptr) {
+        if (hipEventRecord(h->own.fork, s_) != hipSuccess) { (void)hipGetLastError(); return fail(h, EVAC_ERR_HIP, "evac_rollout: hipEventRecord failed"); }
+        for (int k = 0; k < 2; ++k)
+            if (hipStreamWaitEvent(h->own.s[k], h->own.fork, 0) != hipSuccess) { (void)hipGetLastError(); return fail(h, EVAC_ERR_HIP, "evac_rollout: hipStreamWaitEvent failed"); }
+        h->own.forked = true;
+    }
+    const size_t row = (size_t)h->p.obs_dim + 3;
+    for (int k = 0; k < 2; ++k) {
+        evac_handle* c = h->part[k];
+        const size_t first = (size_t)k * (size_t)c->p.n_envs;
+        h->own.pending = true;
+        const int rc = evac_rollout(c, n_steps, actions ? actions + first * 2 : nullptr, nullptr, slab_out + first * row,
+                                    final_stats ? final_stats + first : nullptr, 0, nullptr, nullptr, h->own.s[k]);
+        if (rc != EVAC_OK) return fail(h, rc, std::string("evac_rollout (part): ") + c->err);
+    }
+    return EVAC_OK;
+}
+
+// Form::Persist: ONE PERSISTENT KERNEL PER JOIN: the call becomes a command of the resident kernel's ring.  The kernel is started -- behind
+// what the caller's stream holds at this moment, as the parts' fork -- by the first call after a join (or after
+// evac_order_next_rollout); the calls that follow cost the host a 64-byte write through the BAR and the device nothing but the
+// steps: the state stays in registers.  A kernel that found no command for ~150 us has LEFT by itself (every env's state and place
+// in the ring stored): the call then starts one that takes every env up where it stopped.  (Given actions take the plain path:
+// their buffer is the caller's stream's business.)
+static int rollout_persist(evac_handle* h, int32_t n_steps, float* slab_out, evac_episode_stats_t* final_stats, hipStream_t s_) {
+    hipStream_t S = h->own.s[0];
+    if (h->persist.running && !h->own.forked)            // the caller touched a buffer (evac_order_next_rollout): a new kernel behind a new fork
+        if (const int rc = stop_persistent(h); rc != EVAC_OK) return rc;
+    if (h->persist.running && h->persist.seq - h->persist.first >= evac::kPersistRing - 2) {
+        // the ring is about to lap the slowest env: the kernel is stopped and WAITED FOR on the host (once per ~1000 calls without a join)
+        if (const int rc = stop_persistent(h); rc != EVAC_OK) return rc;
+        if (hipStreamSynchronize(S) != hipSuccess) { (void)hipGetLastError(); return fail(h, EVAC_ERR_HIP, "evac_rollout: the persistent kernel did not end"); }
+    }
+    if (!h->persist.running) {
+        if (hipEventRecord(h->own.fork, s_) != hipSuccess || hipStreamWaitEvent(S, h->own.fork, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, EVAC_ERR_HIP, "evac_rollout: fork of the persistent kernel failed");
+        }
+        h->own.forked = true;
+        if (const int rc = launch_persistent(h, /*resume=*/0, /*stop_at=*/0x7fffffff, /*fresh=*/true); rc != EVAC_OK) return rc;
+        h->persist.running = true;
+        h->persist.first = h->persist.seq;
+    } else if (hipEventQuery(h->last_ev) == hipSuccess) {
+        // the kernel has left (idle): one that resumes.  (A kernel that is leaving RIGHT NOW is seen at the next call or at the join,
+        // whose finisher runs whatever an env has not run yet: no command is lost, it only waits for that kernel.)
+        if (const int rc = launch_persistent(h, /*resume=*/1, /*stop_at=*/0x7fffffff, /*fresh=*/false); rc != EVAC_OK) return rc;
+    } else {
+        (void)hipGetLastError();                         // (hipErrorNotReady: resident)
+    }
+    post_command(h, (int)n_steps, slab_out, final_stats, nullptr);
+    h->own.pending = true;
+    return EVAC_OK;
+}
+
+// Form::Chain: launch g on stream g & 1, ordered per env on the device (include/evac.h).  Both streams start behind what the
+// caller's stream holds -- once per join (below): a barrier packet per launch costs more than the chain gains.
+static int rollout_chain(evac_handle* h, int32_t n_steps, const float* actions, float* slab_out, evac_episode_stats_t* final_stats, hipStream_t s_) {
+    using FW = evac::Wave<1, 1024>;
+    using FW4 = evac::Wave<4, 1024>;
+    using FS = evac::Wave<1, 256>;
+    evac_handle::ChainState& ch = h->chain;
+    const int wpe = h->cu_wide4 ? 4 : 1, per_wg = (h->cu_wide4 || ch.small) ? 4 : 16;
+    const int E = h->p.n_envs, c = ch.gen;
+    hipStream_t S = h->own.s[c & 1], O = h->own.s[(c + 1) & 1];
+    // THE INVARIANT OF THE CHAIN: launch g + 1 must not start being dispatched before every workgroup of launch g has a CU.
+    // A workgroup of g + 1 holds its CU while it waits for envs of launch g; were workgroups of g still waiting for CUs then,
+    // the dispatcher -- which deals a grid's workgroups to the XCDs in order -- could find an XCD's CUs all held by waiting
+    // workgroups of g + 1 and launch g would never be placed (seen: both streams released by ONE event started launches g and
+    // g + 1 together and the second launch of a sweep timed out once in ~2000 sweeps; another kernel holding CUs while the
+    // chain runs does the same; short of a deadlock the interleaved start left the pipeline in a 15-40 % slower rhythm for
+    // the whole sweep).  So every workgroup of a chained launch counts itself in `started` when it gets its CU, and the QUEUE
+    // of launch g + 1 waits -- hipStreamWaitValue64: the runtime's one-wave wait kernel (__amd_rocclr_streamOpsWait in a kernel
+    // trace), one wave slot held, no workgroup of ours -- until the counter says that all workgroups of
+    // launches <= g have started (+0.5 us per launch: tools/microbench/waitvalue.hip).  With it every wait inside a kernel is
+    // for a workgroup that is resident or done, by induction down to the oldest launch in flight, which waits for nothing.
+    const bool fork = ch.restart || !h->own.forked || actions != nullptr;      // (once per join, and with every new input: see rollout_parts)
+    if (fork) {
+        if (hipEventRecord(h->own.fork, s_) != hipSuccess || hipStreamWaitEvent(S, h->own.fork, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, EVAC_ERR_HIP, "evac_rollout: fork of the chain failed");
+        }
+        h->own.forked = true;
+    }
+    int32_t* moving = ch.sched;
+    int32_t* perm = ch.sched + 4 * (size_t)E;
+    if (ch.restart) {
+        // the state in memory is whatever the caller's stream left: every env at generation c, one deal in all four
+        // permutation buffers, the other stream behind both
+        hipLaunchKernelGGL(evac::k_chain_import, dim3((unsigned)((E * wpe + 3) / 4)), dim3(256), 0, S, h->p, h->xchg, c, h->abort_word, ch.wgs, wpe);
+        if (!ch.small) {
+            hipLaunchKernelGGL(evac::k_schedule, dim3(1), dim3(1024), 0, S, E, (const int*)(moving + ((c + 3) & 3) * (size_t)E),
+                               perm + (c & 3) * (size_t)E, (int32_t*)nullptr, per_wg, wpe == 4 ? 4 : 1, option_value("EVAC_CHAIN_DEAL", 0));
+            hipLaunchKernelGGL(evac::k_copy_perm3, dim3(64), dim3(256), 0, S, E, (const int*)(perm + (c & 3) * (size_t)E),
+                               perm + ((c + 1) & 3) * (size_t)E, perm + ((c + 2) & 3) * (size_t)E, perm + ((c + 3) & 3) * (size_t)E);
+        }
+        // ... and the OTHER queue behind all of this.  Its gate alone does not order it: until the import has set the counter the
+        // word holds whatever the workspace's memory held -- the caller's zero fill may not have run yet on this queue's
+        // timeline, a recycled allocation carries the count of the handle that used it before -- and a gate that passes on such a
+        // value starts launch c + 1 before the deal above exists: it then reads a permutation of ANOTHER batch (seen: a 64-env
+        // handle in memory a 512-env handle had used took env indices up to 511 -- tests/test_gpu_parity.py, whole file only).
+        if (hipEventRecord(h->last_ev, S) != hipSuccess || hipStreamWaitEvent(O, h->last_ev, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, EVAC_ERR_HIP, "evac_rollout: restart of the chain failed");
+        }
+        ch.start = c;
+        ch.restart = false;
+    }
+    const bool deals = !ch.small && c - ch.start >= 2;          // (the loads of launch c - 2, the last launch of this stream)
+    const int32_t* deal_loads = deals ? moving + ((c + 2) & 3) * (size_t)E : nullptr;
+    int32_t* deal_perm = deals ? perm + ((c + 2) & 3) * (size_t)E : nullptr;
+    unsigned long long* started = (unsigned long long*)(h->abort_word + 8);      // (the same line as the abort word: bytes 32..39)
+    // (the counter is never reset while the workspace is bound: a restart's first launch is gated too -- on the launches before
+    // the restart, long done -- and the launch after it on the restart's own workgroups, hence behind its import and deal)
+    if (ch.wgs > 0 && hipStreamWaitValue64(S, started, ch.wgs, hipStreamWaitValueGte, ~0ull) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, EVAC_ERR_HIP, "evac_rollout: hipStreamWaitValue64 (the chain's dispatch gate) failed");
+    }
+    static const int deal_mode = option_value("EVAC_CHAIN_DEAL", 0);                    // (diagnostic: A/B runs of one binary)
+    evac::ChainArgs ca{h->xchg, c, h->abort_word, h->team_flag_dev, deal_mode, started};
+    evac::Params pp = h->p;
+    if (h->team_fault && c == ch.start + 1) pp.n_envs = E - per_wg;    // fault injection: the last workgroup of ONE launch is never run
+    // (chain.small: four one-wave envs per 256-thread workgroup, env = slot: the dispatcher places a workgroup of the next launch wherever
+    // four waves have retired, so the chain needs no deal and no pace keeping to keep the CUs full)
+    const auto fn = ch.small ? EVAC_PICK(h, k_rollout_chain_default_config, k_rollout_chain, FS)
+                  : h->cu_wide4 ? EVAC_PICK(h, k_rollout_chain_default_config, k_rollout_chain, FW4)
+                                : EVAC_PICK(h, k_rollout_chain_default_config, k_rollout_chain, FW);
+    const dim3 grid((unsigned)(E / per_wg)), block(ch.small ? FS::kBlock : (h->cu_wide4 ? FW4::kBlock : FW::kBlock));
+    hipLaunchKernelGGL(fn, grid, block, 0, S, pp, (int)n_steps, (const float2*)actions, slab_out, final_stats,
+                       (const int*)(ch.small ? nullptr : perm + (c & 3) * (size_t)E), (int*)(ch.small ? nullptr : moving + (c & 3) * (size_t)E),
+                       deal_loads, deal_perm, ca);
+    if (const int lc = check_launch(h, "evac_rollout (chained)"); lc != EVAC_OK) return lc;      // (a launch that never starts must not be waited for)
+    ch.wgs += (unsigned long long)grid.x;
+    ch.gen = c + 1;
+    h->own.pending = true;
+    ch.dirty = true;
+    return EVAC_OK;
+}
+
+// 513..1024 pedestrians, few envs: K workgroups (CUs) per env (evac_team.h).  Workgroup b = j * 8 + xcd carries team (j / K) * 8 + xcd.  All members of a team spin on its
+// counter, so the whole grid must be resident at once: checked by team_grid_fits (occupancy x CUs >= workgroups; a grid
+// that does not fit runs the one-workgroup-per-env kernels).  A foreign kernel on another stream (the sharded
+// env's all-gather) can delay a member, not starve it -- it ends, the member starts, and the bounded waits (~1 s) outlast
+// it: tests/test_gpu_team.py keeps a second stream busy throughout.  EVAC_TEAM_COOP=1 launches cooperatively instead
+// (the runtime then guarantees co-residency); it costs 3-4 % of the C5 shard's throughput and is not the default.
+static int rollout_team(evac_handle* h, int32_t n_steps, const float* actions, float* slab_out, evac_episode_stats_t* final_stats, hipStream_t s_) {
+    // every slot of the exchange area starts a launch with tag 31 in every word -- no round's (the previous launch left tagged data)
+    if (hipMemsetAsync(h->p.team_rec, 0xff, h->team_xchg_bytes, s_) != hipSuccess) return fail(h, EVAC_ERR_HIP, "evac_rollout: hipMemsetAsync failed");
+    int n_steps_ = (int)n_steps;
+    const float2* actions_ = (const float2*)actions;
+    const int* perm_ = nullptr;
+    int* moving_ = nullptr;
+    void* argv[] = {(void*)&h->p, (void*)&n_steps_, (void*)&actions_, (void*)&slab_out, (void*)&final_stats, (void*)&perm_, (void*)&moving_,
+                    (void*)&perm_, (void*)&moving_};
+    const hipError_t le = launch_team_grid(h, team_kernel(h), argv, s_, /*in_chain=*/!capturing(s_), h->team_coop);
+    if (le != hipSuccess) return fail(h, EVAC_ERR_HIP, std::string("evac_rollout (team launch): ") + hipGetErrorString(le));
+    return EVAC_OK;
+}
+
+// Form::Plain (and every other form's diagnostic faces, given actions on Persist, stream capture on Chain / Persist, after settle): ONE
+// kernel on the caller's stream
+static int rollout_plain(evac_handle* h, int32_t n_steps, const float* actions, float* actions_out, float* slab_out,
+                         evac_episode_stats_t* final_stats, int32_t capture_envs, float* capture, const float* noise, hipStream_t stream) {
+    if (capture || actions_out || noise) {
+        EVAC_DISPATCH(h, k_rollout_diag, stream, h->p, (int)n_steps, (const float2*)actions, (float2*)actions_out, slab_out,
+                      final_stats, (int)capture_envs, capture, noise);
+    } else if (h->team_k && h->team_bound && team_grid_fits(h)) {
+        return rollout_team(h, n_steps, actions, slab_out, final_stats, stream);
+    } else if (h->cu_wide || h->cu_wide4) {
+        // one-wave envs, batch >= 16 envs per CU (or four-wave envs, >= 4 per CU): CU-wide workgroups, envs dealt to the SIMDs by
+        // load when a schedule scratch is bound.  Launch g reads perm[g & 1], leaves its loads in moving[g & 1] and -- workgroup 0,
+        // which carries the lightest envs, before it starts stepping (rollout_body) -- deals perm[(g + 1) & 1] for the next launch
+        // from the loads launch g - 1 left in moving[(g - 1) & 1]: no launch is spent on sorting, and no buffer is read and
+        // written by the same launch.
+        using FW = evac::Wave<1, 1024>;
+        using FW4 = evac::Wave<4, 1024>;
+        const int E = h->p.n_envs;
+        // (while the stream is being captured into a hipGraph the host-side generation must not decide what the graph contains:
+        // a captured launch runs under the deal at hand, deals nothing and does not advance the generation -- any permutation
+        // gives the same results; call evac_reschedule outside the graph to refresh the deal)
+        const bool cap = capturing(stream);
+        // Long launches (>= 50 steps): the deal as a launch of its own in front of every rollout launch -- 6.5 us next to >= 100,
+        // by the loads the previous launch has just left.  Short launches (the driver's 20 steps): the deal of the NEXT launch is
+        // made inside this one (rollout_body: workgroup 0, before it starts stepping), by the loads of the launch before.
+        const bool in_kernel = n_steps < 50 && E >= (h->cu_wide4 ? 4 : 16);     // (workgroup 0 sorts: it must be a full one)
+        if (h->sched && !cap && (h->sched_gen < 0 || !in_kernel)) deal_now(h, stream, h->sched_gen < 0);
+        const Deal d = deal_of(h, !cap && in_kernel);
+        if (h->sched && h->sched_gen >= 0 && !cap) h->sched_gen += 1;
+        const bool four = h->cu_wide4;
+        const auto fn = four ? EVAC_PICK(h, k_rollout_default_config, k_rollout, FW4) : EVAC_PICK(h, k_rollout_default_config, k_rollout, FW);
+        const int per_block = four ? FW4::kEnvsPerBlock : FW::kEnvsPerBlock;
+        hipLaunchKernelGGL(fn, dim3((unsigned)((E + per_block - 1) / per_block)), dim3(four ? FW4::kBlock : FW::kBlock), 0, stream,
+                           h->p, (int)n_steps, (const float2*)actions, slab_out, final_stats, d.perm, d.moving, d.loads, d.next);
+    } else if (h->default_cfg) {
+        EVAC_DISPATCH(h, k_rollout_default_config, stream, h->p, (int)n_steps, (const float2*)actions, slab_out, final_stats,
+                      (const int*)nullptr, (int*)nullptr, (const int*)nullptr, (int*)nullptr);
+    } else {
+        EVAC_DISPATCH(h, k_rollout, stream, h->p, (int)n_steps, (const float2*)actions, slab_out, final_stats, (const int*)nullptr,
+                      (int*)nullptr, (const int*)nullptr, (int*)nullptr);
+    }
+    return check_launch(h, "evac_rollout");
 }
 
 int evac_rollout(evac_handle_t h, int32_t n_steps, const float* actions, float* actions_out, float* slab_out,
@@ -1209,288 +1367,19 @@ int evac_rollout(evac_handle_t h, int32_t n_steps, const float* actions, float* 
     DeviceGuard g(h->device);
     if (capture && (capture_envs < 1 || capture_envs > h->p.n_envs))
         return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_rollout: capture_envs must be in [1, num_envs] when capture is given");
-    if (h->n_parts > 1 && !(capture || actions_out || noise)) {
-        // two half-batch kernels on the handle's own streams, both behind what `stream` holds so far; `stream` is NOT made to
-        // wait for them (evac_join): consecutive rollout calls must not meet, or the halves would run in lock-step
-        hipStream_t s_ = (hipStream_t)stream;
-        // (the fork costs a barrier packet in front of each kernel -- 7-10 us on this platform whether or not the event has fired,
-        // DESIGN.md 6 -- which is more than the parts gain.  So the own streams are put behind the caller's stream ONCE per join: at
-        // the first rollout call after evac_join / any other call on the handle, and at every call that brings inputs (actions).
-        // Asking the stream instead -- hipStreamQuery -- was tried: the query leaves a marker in the stream, the next query finds it
-        // busy, and the handle falls into forking at every call: a second, 15-40 % slower mode of the same program.)
-        const bool fork = !h->forked || actions != nullptr;
-        if (fork) {
-            if (hipEventRecord(h->fork_ev, s_) != hipSuccess) { (void)hipGetLastError(); return fail(h, EVAC_ERR_HIP, "evac_rollout: hipEventRecord failed"); }
-            h->forked = true;
-        }
-        const size_t row = (size_t)h->p.obs_dim + 3;
-        for (int k = 0; k < h->n_parts; ++k) {
-            evac_handle* c = h->part[k];
-            const size_t first = (size_t)k * (size_t)c->p.n_envs;
-            if (fork && hipStreamWaitEvent(h->part_stream[k], h->fork_ev, 0) != hipSuccess) { (void)hipGetLastError(); return fail(h, EVAC_ERR_HIP, "evac_rollout: hipStreamWaitEvent failed"); }
-            h->parts_pending = true;
-            const int rc = evac_rollout(c, n_steps, actions ? actions + first * 2 : nullptr, nullptr, slab_out + first * row,
-                                        final_stats ? final_stats + first : nullptr, 0, nullptr, nullptr, h->part_stream[k]);
-            if (rc != EVAC_OK) return fail(h, rc, std::string("evac_rollout (part): ") + c->err);
-        }
-        return EVAC_OK;
+    hipStream_t s_ = (hipStream_t)stream;
+    if (!(capture || actions_out || noise)) {        // (the diagnostic faces: one kernel on `stream` in every form)
+        if (h->form == Form::Parts) return rollout_parts(h, n_steps, actions, slab_out, final_stats, s_);
+        if (h->form == Form::Persist && !actions && (!h->team_k || (h->team_bound && team_grid_fits(h))) && !capturing(s_))
+            return rollout_persist(h, n_steps, slab_out, final_stats, s_);
+        if (h->form == Form::Chain && h->chain.bound && !capturing(s_)) return rollout_chain(h, n_steps, actions, slab_out, final_stats, s_);
     }
-    if (h->persist && !(capture || actions_out || noise || actions) && (!h->team_k || (h->team_bound && team_grid_fits(h)))) {
-        hipStream_t s_ = (hipStream_t)stream;
-        hipStreamCaptureStatus pcap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s_, &pcap) != hipSuccess) { (void)hipGetLastError(); pcap = hipStreamCaptureStatusNone; }
-        if (pcap == hipStreamCaptureStatusNone) {
-            // ONE PERSISTENT KERNEL PER JOIN: the call becomes a command of the resident kernel's ring.  The kernel is started -- behind
-            // what the caller's stream holds at this moment, as the parts' fork -- by the first call after a join (or after
-            // evac_order_next_rollout); the calls that follow cost the host a 64-byte write through the BAR and the device nothing but the
-            // steps: the state stays in registers.  A kernel that found no command for ~150 us has LEFT by itself (every env's state and place
-            // in the ring stored): the call then starts one that takes every env up where it stopped.  (Given actions take the plain path
-            // below: their buffer is the caller's stream's business.)
-            hipStream_t S = h->part_stream[0];
-            if (h->persist_running && !h->forked)            // the caller touched a buffer (evac_order_next_rollout): a new kernel behind a new fork
-                if (const int rc = stop_persistent(h); rc != EVAC_OK) return rc;
-            if (h->persist_running && h->persist_seq - h->persist_first >= evac::kPersistRing - 2) {
-                // the ring is about to lap the slowest env: the kernel is stopped and WAITED FOR on the host (once per ~1000 calls without a join)
-                if (const int rc = stop_persistent(h); rc != EVAC_OK) return rc;
-                if (hipStreamSynchronize(S) != hipSuccess) { (void)hipGetLastError(); return fail(h, EVAC_ERR_HIP, "evac_rollout: the persistent kernel did not end"); }
-            }
-            if (!h->persist_running) {
-                if (hipEventRecord(h->fork_ev, s_) != hipSuccess || hipStreamWaitEvent(S, h->fork_ev, 0) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return fail(h, EVAC_ERR_HIP, "evac_rollout: fork of the persistent kernel failed");
-                }
-                h->forked = true;
-                if (const int rc = launch_persistent(h, /*resume=*/0, /*stop_at=*/0x7fffffff, /*fresh=*/true); rc != EVAC_OK) return rc;
-                h->persist_running = true;
-                h->persist_first = h->persist_seq;
-            } else if (hipEventQuery(h->chain_ev) == hipSuccess) {
-                // the kernel has left (idle): one that resumes.  (A kernel that is leaving RIGHT NOW is seen at the next call or at the join,
-                // whose finisher runs whatever an env has not run yet: no command is lost, it only waits for that kernel.)
-                if (const int rc = launch_persistent(h, /*resume=*/1, /*stop_at=*/0x7fffffff, /*fresh=*/false); rc != EVAC_OK) return rc;
-            } else {
-                (void)hipGetLastError();                         // (hipErrorNotReady: resident)
-            }
-            post_command(h, (int)n_steps, slab_out, final_stats, nullptr);
-            h->parts_pending = true;
-            return EVAC_OK;
-        }
-    }
-    if (h->chain && h->chain_bound && !(capture || actions_out || noise)) {
-        hipStream_t s_ = (hipStream_t)stream;
-        hipStreamCaptureStatus ccap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s_, &ccap) != hipSuccess) { (void)hipGetLastError(); ccap = hipStreamCaptureStatusNone; }
-        if (ccap == hipStreamCaptureStatusNone) {
-            // CHAINED: launch g on stream g & 1, ordered per env on the device (include/evac.h).  Both streams start behind what the
-            // caller's stream holds -- once per join (below): a barrier packet per launch costs more than the chain gains.
-            using FW = evac::Wave<1, 1024>;
-            using FW4 = evac::Wave<4, 1024>;
-            using FS = evac::Wave<1, 256>;
-            const int wpe = h->cu_wide4 ? 4 : 1, per_wg = (h->cu_wide4 || h->chain_small) ? 4 : 16;
-            const int E = h->p.n_envs, c = h->chain_gen;
-            hipStream_t S = h->part_stream[c & 1], O = h->part_stream[(c + 1) & 1];
-            // THE INVARIANT OF THE CHAIN: launch g + 1 must not start being dispatched before every workgroup of launch g has a CU.
-            // A workgroup of g + 1 holds its CU while it waits for envs of launch g; were workgroups of g still waiting for CUs then,
-            // the dispatcher -- which deals a grid's workgroups to the XCDs in order -- could find an XCD's CUs all held by waiting
-            // workgroups of g + 1 and launch g would never be placed (seen: both streams released by ONE event started launches g and
-            // g + 1 together and the second launch of a sweep timed out once in ~2000 sweeps; another kernel holding CUs while the
-            // chain runs does the same; short of a deadlock the interleaved start left the pipeline in a 15-40 % slower rhythm for
-            // the whole sweep).  So every workgroup of a chained launch counts itself in `started` when it gets its CU, and the QUEUE
-            // of launch g + 1 waits -- hipStreamWaitValue64: the runtime's one-wave wait kernel (__amd_rocclr_streamOpsWait in a kernel
-            // trace), one wave slot held, no workgroup of ours -- until the counter says that all workgroups of
-            // launches <= g have started (+0.5 us per launch: tools/microbench/waitvalue.hip).  With it every wait inside a kernel is
-            // for a workgroup that is resident or done, by induction down to the oldest launch in flight, which waits for nothing.
-            const bool fork = h->chain_restart || !h->forked || actions != nullptr;      // (once per join, and with every new input: see the parts' fork above)
-            if (fork) {
-                if (hipEventRecord(h->fork_ev, s_) != hipSuccess || hipStreamWaitEvent(S, h->fork_ev, 0) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return fail(h, EVAC_ERR_HIP, "evac_rollout: fork of the chain failed");
-                }
-                h->forked = true;
-            }
-            int32_t* moving = h->chain_sched;
-            int32_t* perm = h->chain_sched + 4 * (size_t)E;
-            if (h->chain_restart) {
-                // the state in memory is whatever the caller's stream left: every env at generation c, one deal in all four
-                // permutation buffers, the other stream behind both
-                hipLaunchKernelGGL(evac::k_chain_import, dim3((unsigned)((E * wpe + 3) / 4)), dim3(256), 0, S, h->p, h->chain_xchg, c, h->chain_abort, h->chain_wgs, wpe);
-                if (!h->chain_small) {
-                    hipLaunchKernelGGL(evac::k_schedule, dim3(1), dim3(1024), 0, S, E, (const int*)(moving + ((c + 3) & 3) * (size_t)E),
-                                       perm + (c & 3) * (size_t)E, (int32_t*)nullptr, per_wg, wpe == 4 ? 4 : 1, option_value("EVAC_CHAIN_DEAL", 0));
-                    hipLaunchKernelGGL(evac::k_copy_perm3, dim3(64), dim3(256), 0, S, E, (const int*)(perm + (c & 3) * (size_t)E),
-                                       perm + ((c + 1) & 3) * (size_t)E, perm + ((c + 2) & 3) * (size_t)E, perm + ((c + 3) & 3) * (size_t)E);
-                }
-                // ... and the OTHER queue behind all of this.  Its gate alone does not order it: until the import has set the counter the
-                // word holds whatever the workspace's memory held -- the caller's zero fill may not have run yet on this queue's
-                // timeline, a recycled allocation carries the count of the handle that used it before -- and a gate that passes on such a
-                // value starts launch c + 1 before the deal above exists: it then reads a permutation of ANOTHER batch (seen: a 64-env
-                // handle in memory a 512-env handle had used took env indices up to 511 -- tests/test_gpu_parity.py, whole file only).
-                if (hipEventRecord(h->chain_ev, S) != hipSuccess || hipStreamWaitEvent(O, h->chain_ev, 0) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return fail(h, EVAC_ERR_HIP, "evac_rollout: restart of the chain failed");
-                }
-                h->chain_start = c;
-                h->chain_restart = false;
-            }
-            const bool deals = !h->chain_small && c - h->chain_start >= 2;          // (the loads of launch c - 2, the last launch of this stream)
-            const int32_t* deal_loads = deals ? moving + ((c + 2) & 3) * (size_t)E : nullptr;
-            int32_t* deal_perm = deals ? perm + ((c + 2) & 3) * (size_t)E : nullptr;
-            unsigned long long* started = (unsigned long long*)(h->chain_abort + 8);      // (the same line as the abort word: bytes 32..39)
-            // (the counter is never reset while the workspace is bound: a restart's first launch is gated too -- on the launches before
-            // the restart, long done -- and the launch after it on the restart's own workgroups, hence behind its import and deal)
-            if (h->chain_wgs > 0 && hipStreamWaitValue64(S, started, h->chain_wgs, hipStreamWaitValueGte, ~0ull) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(h, EVAC_ERR_HIP, "evac_rollout: hipStreamWaitValue64 (the chain's dispatch gate) failed");
-            }
-            static const int deal_mode = option_value("EVAC_CHAIN_DEAL", 0);                    // (diagnostic: A/B runs of one binary)
-            evac::ChainArgs ca{h->chain_xchg, c, h->chain_abort, h->team_flag_dev, deal_mode, started};
-            evac::Params pp = h->p;
-            if (h->team_fault && c == h->chain_start + 1) pp.n_envs = E - per_wg;    // fault injection: the last workgroup of ONE launch is never run
-#define EVAC_CHAIN_ARGS pp, (int)n_steps, (const float2*)actions, slab_out, final_stats, (const int*)(h->chain_small ? nullptr : perm + (c & 3) * (size_t)E), (int*)(h->chain_small ? nullptr : moving + (c & 3) * (size_t)E), (const int*)deal_loads, (int*)deal_perm, ca
-            const dim3 grid((unsigned)(E / per_wg));
-            if (h->chain_small) {
-                // four one-wave envs per 256-thread workgroup, env = slot: the dispatcher places a workgroup of the next launch wherever
-                // four waves have retired, so the chain needs no deal and no pace keeping to keep the CUs full
-                if (h->default_cfg && h->p.obs_pos == EVAC_POS_GRAV)
-                    hipLaunchKernelGGL((evac::k_rollout_chain_default_config<FS, true>), grid, dim3(FS::kBlock), 0, S, EVAC_CHAIN_ARGS);
-                else if (h->default_cfg)
-                    hipLaunchKernelGGL((evac::k_rollout_chain_default_config<FS, false>), grid, dim3(FS::kBlock), 0, S, EVAC_CHAIN_ARGS);
-                else if (h->p.obs_pos == EVAC_POS_GRAV)
-                    hipLaunchKernelGGL((evac::k_rollout_chain<FS, true>), grid, dim3(FS::kBlock), 0, S, EVAC_CHAIN_ARGS);
-                else
-                    hipLaunchKernelGGL((evac::k_rollout_chain<FS, false>), grid, dim3(FS::kBlock), 0, S, EVAC_CHAIN_ARGS);
-            } else if (h->cu_wide4) {
-                if (h->default_cfg && h->p.obs_pos == EVAC_POS_GRAV)
-                    hipLaunchKernelGGL((evac::k_rollout_chain_default_config<FW4, true>), grid, dim3(FW4::kBlock), 0, S, EVAC_CHAIN_ARGS);
-                else if (h->default_cfg)
-                    hipLaunchKernelGGL((evac::k_rollout_chain_default_config<FW4, false>), grid, dim3(FW4::kBlock), 0, S, EVAC_CHAIN_ARGS);
-                else if (h->p.obs_pos == EVAC_POS_GRAV)
-                    hipLaunchKernelGGL((evac::k_rollout_chain<FW4, true>), grid, dim3(FW4::kBlock), 0, S, EVAC_CHAIN_ARGS);
-                else
-                    hipLaunchKernelGGL((evac::k_rollout_chain<FW4, false>), grid, dim3(FW4::kBlock), 0, S, EVAC_CHAIN_ARGS);
-            } else if (h->default_cfg && h->p.obs_pos == EVAC_POS_GRAV)
-                hipLaunchKernelGGL((evac::k_rollout_chain_default_config<FW, true>), grid, dim3(FW::kBlock), 0, S, EVAC_CHAIN_ARGS);
-            else if (h->default_cfg)
-                hipLaunchKernelGGL((evac::k_rollout_chain_default_config<FW, false>), grid, dim3(FW::kBlock), 0, S, EVAC_CHAIN_ARGS);
-            else if (h->p.obs_pos == EVAC_POS_GRAV)
-                hipLaunchKernelGGL((evac::k_rollout_chain<FW, true>), grid, dim3(FW::kBlock), 0, S, EVAC_CHAIN_ARGS);
-            else
-                hipLaunchKernelGGL((evac::k_rollout_chain<FW, false>), grid, dim3(FW::kBlock), 0, S, EVAC_CHAIN_ARGS);
-#undef EVAC_CHAIN_ARGS
-            if (const int lc = check_launch(h, "evac_rollout (chained)"); lc != EVAC_OK) return lc;      // (a launch that never starts must not be waited for)
-            h->chain_wgs += (unsigned long long)grid.x;
-            h->chain_gen = c + 1;
-            h->parts_pending = true;
-            h->chain_dirty = true;
-            return EVAC_OK;
-        }
-    }
-    h->chain_restart = true;
-    if (h->parts_pending)
-        if (const int jn = join_parts(h, (hipStream_t)stream); jn != EVAC_OK) return jn;
-    if (capture || actions_out || noise)
-        EVAC_DISPATCH(h, k_rollout_diag, stream, h->p, (int)n_steps, (const float2*)actions, (float2*)actions_out, slab_out,
-                      final_stats, (int)capture_envs, capture, noise);
-    else if (h->team_k && h->team_bound && team_grid_fits(h)) {
-        // 513..1024 pedestrians, few envs: K workgroups (CUs) per env (evac_team.h).  Workgroup b = j * 8 + xcd carries team (j / K) * 8 + xcd.  All members of a team spin on its
-        // counter, so the whole grid must be resident at once: checked by team_grid_fits (occupancy x CUs >= workgroups; a grid
-        // that does not fit runs the one-workgroup-per-env kernels below).  A foreign kernel on another stream (the sharded
-        // env's all-gather) can delay a member, not starve it -- it ends, the member starts, and the bounded waits (~1 s) outlast
-        // it: tests/test_gpu_team.py keeps a second stream busy throughout.  EVAC_TEAM_COOP=1 launches cooperatively instead
-        // (the runtime then guarantees co-residency); it costs 3-4 % of the C5 shard's throughput and is not the default.
-        hipStream_t s_ = (hipStream_t)stream;
-        // every slot of the exchange area starts a launch with tag 31 in every word -- no round's (the previous launch left tagged data)
-        if (hipMemsetAsync(h->p.team_rec, 0xff, h->team_xchg_bytes, s_) != hipSuccess) return fail(h, EVAC_ERR_HIP, "evac_rollout: hipMemsetAsync failed");
-        const dim3 grid(team_grid(h)), block(1024);
-        int n_steps_ = (int)n_steps;
-        const float2* actions_ = (const float2*)actions;
-        const int* perm_ = nullptr;
-        int* moving_ = nullptr;
-        void* argv[] = {(void*)&h->p, (void*)&n_steps_, (void*)&actions_, (void*)&slab_out, (void*)&final_stats, (void*)&perm_, (void*)&moving_,
-                        (void*)&perm_, (void*)&moving_};
-        const void* fn = team_kernel(h);
-        hipStreamCaptureStatus tcap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s_, &tcap) != hipSuccess) { (void)hipGetLastError(); tcap = hipStreamCaptureStatusNone; }
-        const bool chained = tcap == hipStreamCaptureStatusNone && h->device >= 0 && h->device < kMaxDevices;
-        std::unique_lock<std::mutex> chain(g_team_chain_lock, std::defer_lock);
-        if (chained) {                               // (see g_team_chain: the previous team grid of this device has drained)
-            chain.lock();
-            hipEvent_t& ev = g_team_chain[h->device];
-            if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); ev = nullptr; }
-            if (ev && hipStreamWaitEvent(s_, ev, 0) != hipSuccess) (void)hipGetLastError();      // (a never-recorded event: no wait)
-        }
-        hipError_t le = h->team_coop ? hipLaunchCooperativeKernel(fn, grid, block, argv, 0, s_) : hipLaunchKernel(fn, grid, block, argv, 0, s_);
-        if (le != hipSuccess && h->team_coop) {      // (e.g. under stream capture): the occupancy check still holds for a plain launch
-            (void)hipGetLastError();
-            h->team_coop = false;
-            le = hipLaunchKernel(fn, grid, block, argv, 0, s_);
-        }
-        if (chained && g_team_chain[h->device] && le == hipSuccess && hipEventRecord(g_team_chain[h->device], s_) != hipSuccess) (void)hipGetLastError();
-        if (chained) chain.unlock();
-        if (le != hipSuccess) return fail(h, EVAC_ERR_HIP, std::string("evac_rollout (team launch): ") + hipGetErrorString(le));
-    } else if (h->cu_wide || h->cu_wide4) {
-        // one-wave envs, batch >= 16 envs per CU (or four-wave envs, >= 4 per CU): CU-wide workgroups, envs dealt to the SIMDs by
-        // load when a schedule scratch is bound.  Launch g reads perm[g & 1], leaves its loads in moving[g & 1] and -- workgroup 0,
-        // which carries the lightest envs, before it starts stepping (rollout_body) -- deals perm[(g + 1) & 1] for the next launch
-        // from the loads launch g - 1 left in moving[(g - 1) & 1]: no launch is spent on sorting, and no buffer is read and
-        // written by the same launch.
-        using FW = evac::Wave<1, 1024>;
-        using FW4 = evac::Wave<4, 1024>;
-        hipStream_t s_ = (hipStream_t)stream;
-        const int E = h->p.n_envs;
-        // (while the stream is being captured into a hipGraph the host-side generation must not decide what the graph contains:
-        // a captured launch runs under the deal at hand, deals nothing and does not advance the generation -- any permutation
-        // gives the same results; call evac_reschedule outside the graph to refresh the deal)
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s_, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-        const bool capturing = cap != hipStreamCaptureStatusNone;
-        // Long launches (>= 50 steps): the deal as a launch of its own in front of every rollout launch -- 6.5 us next to >= 100,
-        // by the loads the previous launch has just left.  Short launches (the driver's 20 steps): the deal of the NEXT launch is
-        // made inside this one (rollout_body: workgroup 0, before it starts stepping), by the loads of the launch before.
-        const bool in_kernel = n_steps < 50 && E >= (h->cu_wide4 ? 4 : 16);     // (workgroup 0 sorts: it must be a full one)
-        if (h->sched && !capturing && (h->sched_gen < 0 || !in_kernel)) deal_now(h, s_, h->sched_gen < 0);
-        const int g_ = h->sched_gen;
-        const bool dealt = h->sched && g_ >= 0;                                // (never dealt yet, e.g. a first launch under capture: identity)
-        const bool deals = dealt && !capturing && in_kernel;
-        const int32_t* perm = dealt ? h->sched + (2 + (g_ & 1)) * E : nullptr;
-        int32_t* moving = h->sched ? h->sched + (dealt ? (g_ & 1) : 0) * E : nullptr;
-        const int32_t* deal_loads = deals ? h->sched + ((g_ + 1) & 1) * E : nullptr;
-        int32_t* deal_perm = deals ? h->sched + (2 + ((g_ + 1) & 1)) * E : nullptr;
-        if (dealt && !capturing) h->sched_gen = g_ + 1;
-#define EVAC_CUWIDE_ARGS h->p, (int)n_steps, (const float2*)actions, slab_out, final_stats, (const int*)perm, (int*)moving, (const int*)deal_loads, (int*)deal_perm
-        if (h->cu_wide4) {
-            const dim3 grid4((unsigned)((E + FW4::kEnvsPerBlock - 1) / FW4::kEnvsPerBlock));
-            if (h->default_cfg && h->p.obs_pos == EVAC_POS_GRAV)
-                hipLaunchKernelGGL((evac::k_rollout_default_config<FW4, true>), grid4, dim3(FW4::kBlock), 0, s_, EVAC_CUWIDE_ARGS);
-            else if (h->default_cfg)
-                hipLaunchKernelGGL((evac::k_rollout_default_config<FW4, false>), grid4, dim3(FW4::kBlock), 0, s_, EVAC_CUWIDE_ARGS);
-            else if (h->p.obs_pos == EVAC_POS_GRAV)
-                hipLaunchKernelGGL((evac::k_rollout<FW4, true>), grid4, dim3(FW4::kBlock), 0, s_, EVAC_CUWIDE_ARGS);
-            else
-                hipLaunchKernelGGL((evac::k_rollout<FW4, false>), grid4, dim3(FW4::kBlock), 0, s_, EVAC_CUWIDE_ARGS);
-            return check_launch(h, "evac_rollout");
-        }
-        const dim3 grid((unsigned)((E + FW::kEnvsPerBlock - 1) / FW::kEnvsPerBlock));
-        if (h->default_cfg && h->p.obs_pos == EVAC_POS_GRAV)
-            hipLaunchKernelGGL((evac::k_rollout_default_config<FW, true>), grid, dim3(FW::kBlock), 0, s_, EVAC_CUWIDE_ARGS);
-        else if (h->default_cfg)
-            hipLaunchKernelGGL((evac::k_rollout_default_config<FW, false>), grid, dim3(FW::kBlock), 0, s_, EVAC_CUWIDE_ARGS);
-        else if (h->p.obs_pos == EVAC_POS_GRAV)
-            hipLaunchKernelGGL((evac::k_rollout<FW, true>), grid, dim3(FW::kBlock), 0, s_, EVAC_CUWIDE_ARGS);
-        else
-            hipLaunchKernelGGL((evac::k_rollout<FW, false>), grid, dim3(FW::kBlock), 0, s_, EVAC_CUWIDE_ARGS);
-#undef EVAC_CUWIDE_ARGS
-    } else if (h->default_cfg)
-        EVAC_DISPATCH(h, k_rollout_default_config, stream, h->p, (int)n_steps, (const float2*)actions, slab_out, final_stats,
-                      (const int*)nullptr, (int*)nullptr, (const int*)nullptr, (int*)nullptr);
-    else
-        EVAC_DISPATCH(h, k_rollout, stream, h->p, (int)n_steps, (const float2*)actions, slab_out, final_stats, (const int*)nullptr,
-                      (int*)nullptr, (const int*)nullptr, (int*)nullptr);
-    return check_launch(h, "evac_rollout");
+    if (const int rc = settle(h, s_); rc != EVAC_OK) return rc;
+    return rollout_plain(h, n_steps, actions, actions_out, slab_out, final_stats, capture_envs, capture, noise, s_);
 }
 
 int evac_observe(evac_handle_t h, float* obs_out, void* stream) {
-    EVAC_REQUIRE_BOUND(h, "evac_observe");
-    EVAC_JOIN_FIRST(h, stream);
+    EVAC_REQUIRE_SETTLED(h, "evac_observe", stream);
     if (!obs_out) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_observe: obs_out is NULL");
     DeviceGuard g(h->device);
     EVAC_DISPATCH(h, k_observe, stream, h->p, obs_out);
@@ -1505,8 +1394,7 @@ static unsigned state_grid(const evac::Params& p) {
 
 int evac_get_state(evac_handle_t h, float* pos, float* dir, uint8_t* status, float* agent_pos, float* agent_dir,
                    int32_t* now, void* stream) {
-    EVAC_REQUIRE_BOUND(h, "evac_get_state");
-    EVAC_JOIN_FIRST(h, stream);
+    EVAC_REQUIRE_SETTLED(h, "evac_get_state", stream);
     DeviceGuard g(h->device);
     hipLaunchKernelGGL(evac::k_get_state, dim3(state_grid(h->p)), dim3(256), 0, (hipStream_t)stream, h->p, (float2*)pos,
                        (float2*)dir, status, (float2*)agent_pos, (float2*)agent_dir, now);
@@ -1515,8 +1403,7 @@ int evac_get_state(evac_handle_t h, float* pos, float* dir, uint8_t* status, flo
 
 int evac_set_state(evac_handle_t h, const float* pos, const float* dir, const uint8_t* status, const float* agent_pos,
                    const float* agent_dir, const int32_t* now, void* stream) {
-    EVAC_REQUIRE_BOUND(h, "evac_set_state");
-    EVAC_JOIN_FIRST(h, stream);
+    EVAC_REQUIRE_SETTLED(h, "evac_set_state", stream);
     DeviceGuard g(h->device);
     hipLaunchKernelGGL(evac::k_set_state, dim3(state_grid(h->p)), dim3(256), 0, (hipStream_t)stream, h->p,
                        (const float2*)pos, (const float2*)dir, status, (const float2*)agent_pos,
@@ -1529,6 +1416,7 @@ int64_t evac_norm_state_doubles(evac_handle_t h) { return h ? 3ll * h->p.obs_dim
 int evac_norm_init(evac_handle_t h, double* norm_state, void* stream) {
     if (!h) return EVAC_ERR_INVALID_ARGUMENT;
     if (!norm_state) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_norm_init: norm_state is NULL");
+    if (const int rc = settle(h, (hipStream_t)stream); rc != EVAC_OK) return rc;
     DeviceGuard g(h->device);
     hipLaunchKernelGGL(evac::k_norm_init, dim3(1024), dim3(256), 0, (hipStream_t)stream, h->p.n_envs, h->p.obs_dim, norm_state);
     return check_launch(h, "evac_norm_init");
@@ -1544,6 +1432,7 @@ int evac_norm_reset(evac_handle_t h, const uint8_t* mask, float* obs, double* no
                     void* stream) {
     if (!h) return EVAC_ERR_INVALID_ARGUMENT;
     if (!obs || !norm_state) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_norm_reset: obs / norm_state is NULL");
+    if (const int rc = settle(h, (hipStream_t)stream); rc != EVAC_OK) return rc;
     DeviceGuard g(h->device);
     hipLaunchKernelGGL(evac::k_norm_step, dim3(norm_grid(h->p)), dim3(256), 0, (hipStream_t)stream, h->p.n_envs, h->p.obs_dim,
                        obs, (float*)nullptr, (float*)nullptr, (const uint8_t*)nullptr, (const uint8_t*)nullptr, mask, norm_state,
@@ -1557,6 +1446,7 @@ int evac_norm_step(evac_handle_t h, float* obs, float* final_obs, float* reward,
     if (!h) return EVAC_ERR_INVALID_ARGUMENT;
     if (!obs || !reward || !terminated || !truncated || !norm_state)
         return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_norm_step: obs/reward/terminated/truncated/norm_state must be non-NULL");
+    if (const int rc = settle(h, (hipStream_t)stream); rc != EVAC_OK) return rc;
     DeviceGuard g(h->device);
     hipLaunchKernelGGL(evac::k_norm_step, dim3(norm_grid(h->p)), dim3(256), 0, (hipStream_t)stream, h->p.n_envs, h->p.obs_dim,
                        obs, final_obs, reward, terminated, truncated, (const uint8_t*)nullptr, norm_state, gamma, obs_clip,
