@@ -47,7 +47,8 @@ def test_capture_reproduces_the_reference_trajectory(ea, name):
 
 
 def test_step_writes_the_trainers_storage_directly(ea):
-    """rpo_agent.py:158-163,182-196: obs[step] / rewards[step] / dones[step] rows are the step's destinations."""
+    """rpo_agent.py:158-163,182-196: obs[step] / rewards[step] / dones[step] rows are the step's destinations: the same as a twin env's
+    own outputs, and (two reference episodes, teacher-forced into columns of a wider buffer) within compare_step of the oracle."""
     import torch
     n, E, T = 60, 32, 12
     cfg = ea.EnvConfig(number_of_pedestrians=n, max_timesteps=5)           # episodes end inside the window: autoreset rows too
@@ -75,6 +76,32 @@ def test_step_writes_the_trainers_storage_directly(ea):
     with pytest.raises(ValueError):
         a.step(acts[0], out_reward=rew[0].double())
     a.close(); b.close()
+    # the same destination form against the oracle: reference episodes teacher-forced, every step into rows of a larger buffer
+    from tests.test_gpu_parity import compare_step
+    for name in ("traj_n60_s1_noise05_ens05", "traj_n256_s5"):
+        d = np.load(os.path.join(H.GOLDEN, name + ".npz"))
+        p = H.load_params(d["params_json"])
+        K, n, E, W = len(d["action"]), p.number_of_pedestrians, 3, 8       # W: the trainer's envs; this env writes columns 2..4
+        env = ea.BatchedEvacuationEnv(cfg_from_params(ea, p), wrap, num_envs=E, autoreset=False)
+        D = env.obs_dim
+        obs = torch.full((K, W, D), float("nan"), device=env.device)
+        rew = torch.full((K, W), float("nan"), device=env.device)
+        term = torch.full((K, W), 7, dtype=torch.uint8, device=env.device)
+        trunc = torch.full((K, W), 7, dtype=torch.uint8, device=env.device)
+        rep = lambda x, dt=np.float32: np.broadcast_to(np.asarray(x, dtype=dt)[None], (E,) + np.shape(x)).copy()   # noqa: E731
+        for k in range(K):
+            pre = H.state_at(d, k)
+            env.set_state(pos=rep(pre.pos), dir=rep(pre.dir), status=rep(pre.status, np.uint8), agent_pos=rep(pre.agent_pos),
+                          agent_dir=rep(pre.agent_dir), now=rep(pre.now, np.int32))
+            env.step(rep(d["action"][k]), noise=rep(d["noise"][k]), out_obs=obs[k, 2:2 + E], out_reward=rew[k, 2:2 + E],
+                     out_terminated=term[k, 2:2 + E], out_truncated=trunc[k, 2:2 + E])
+            st = {key: v.cpu().numpy() for key, v in env.get_state().items()}
+            got = dict(obs=obs[k, 2:2 + E].cpu().numpy(), reward=rew[k, 2:2 + E].cpu().numpy(), terminated=term[k, 2:2 + E].cpu().numpy().astype(bool),
+                       truncated=trunc[k, 2:2 + E].cpu().numpy().astype(bool), **st)
+            compare_step(p, wrap, [pre] * E, rep(d["action"][k]), rep(d["noise"][k]), got, min_checked=0)
+        assert torch.isnan(obs[:, :2]).all() and torch.isnan(obs[:, 2 + E:]).all() and (term[:, :2] == 7).all() and (trunc[:, 2 + E:] == 7).all()
+        assert not torch.isnan(obs[:, 2:2 + E]).any() and not torch.isnan(rew[:, 2:2 + E]).any() and (term[:, 2:2 + E] < 2).all()
+        env.close()
 
 
 def test_step_launchers_equal_step(ea):

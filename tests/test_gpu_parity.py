@@ -112,7 +112,22 @@ def legal_statuses(p, pos_i, agent_pos):
     return out
 
 
-def compare_step(p, wrap, pre_states, actions, noise, got, min_checked=1, label=None):
+def oracle_step(p, pre, action, noise):
+    """The oracle's step from the f32-rounded pre-state: (post-state, env_step's dict, per-pedestrian near-tie mask, pre-step
+    statuses, whether the post-state is finite) -- what compare_step holds a kernel's outputs against."""
+    st = f32_state(pre)
+    pre_pos = st.pos.copy()
+    old_status = st.status.copy()
+    with np.errstate(all="ignore"):
+        out = O.env_step(p, st, np.asarray(action, dtype=np.float32), np.asarray(noise, dtype=np.float32).astype(np.float64))
+    finite = np.isfinite(st.pos).all()
+    tied = np.zeros(len(st.status), bool)
+    if finite:
+        tied = O.threshold_margins_per_pedestrian(st.pos, st.agent_pos, pre_pos, p.width, p.height, st.status) < TIE
+    return st, out, tied, old_status, finite
+
+
+def compare_step(p, wrap, pre_states, actions, noise, got, min_checked=1, label=None, oracle=None, reset=None, counts=None):
     """Oracle (reference precision) from the same f32-representable inputs vs the GPU outputs.  A comparison whose f64 margin is
     below TIE may legitimately flip in f32: the pedestrians it involves are left out of the element-wise comparison (positions,
     directions, statuses of every OTHER pedestrian of that env are still compared).  The env-level outputs of such an env (rewards,
@@ -120,33 +135,35 @@ def compare_step(p, wrap, pre_states, actions, noise, got, min_checked=1, label=
     the status thresholds -- the pedestrian's position and direction agree with the oracle's, only its class is in question --
     the GPU's class must be one of the legal outcomes, and the oracle's reward / termination / observation are re-evaluated with it;
     only a tie that changed a pedestrian's MOTION (a pair of the neighbour test, a wall test) still skips the env-level outputs.
-    All counts are returned and logged."""
+    All counts are returned and logged.
+
+    `oracle`: the `oracle_step` of every env, computed beforehand (a caller that compares several kernels on the same inputs
+    steps the oracle once).  `reset[e]`: env e autoreset in the same step (a rollout kernel), so its state and observation are
+    the reset's and the caller checks them: only the flags and the reward are compared here, and a near-tie in that env skips
+    them.  `counts` (a dict) accumulates the envs whose env-level outputs were checked and the pedestrians left out."""
     checked = ties = resolved = peds_out = 0
     worst = 0.0
     for e, pre in enumerate(pre_states):
-        st = f32_state(pre)
-        pre_pos = st.pos.copy()
-        old_status = st.status.copy()
-        with np.errstate(all="ignore"):
-            out = O.env_step(p, st, np.asarray(actions[e], dtype=np.float32), np.asarray(noise[e], dtype=np.float32).astype(np.float64))
-        finite = np.isfinite(st.pos).all()
-        tied = np.zeros(len(st.status), bool)
-        if finite:
-            tied = O.threshold_margins_per_pedestrian(st.pos, st.agent_pos, pre_pos, p.width, p.height, st.status) < TIE
+        st, out, tied, old_status, finite = oracle[e] if oracle is not None else oracle_step(p, pre, actions[e], noise[e])
+        st = st.copy()
+        moved = reset is None or not reset[e]
         ok = ~tied
-        np.testing.assert_array_equal(got["status"][e][ok], st.status[ok], err_msg=f"env {e} status")
-        np.testing.assert_allclose(got["pos"][e][ok], st.pos[ok], rtol=0, atol=ATOL, equal_nan=True, err_msg=f"env {e} pos")
-        np.testing.assert_allclose(got["dir"][e][ok], st.dir[ok], rtol=0, atol=ATOL, equal_nan=True, err_msg=f"env {e} dir")
-        np.testing.assert_allclose(got["agent_pos"][e], st.agent_pos, rtol=0, atol=1e-7)
-        np.testing.assert_allclose(got["agent_dir"][e], st.agent_dir, rtol=0, atol=1e-8)
-        assert got["now"][e] == st.now
+        if moved:
+            np.testing.assert_array_equal(got["status"][e][ok], st.status[ok], err_msg=f"env {e} status")
+            np.testing.assert_allclose(got["pos"][e][ok], st.pos[ok], rtol=0, atol=ATOL, equal_nan=True, err_msg=f"env {e} pos")
+            np.testing.assert_allclose(got["dir"][e][ok], st.dir[ok], rtol=0, atol=ATOL, equal_nan=True, err_msg=f"env {e} dir")
+            np.testing.assert_allclose(got["agent_pos"][e], st.agent_pos, rtol=0, atol=1e-7)
+            np.testing.assert_allclose(got["agent_dir"][e], st.agent_dir, rtol=0, atol=1e-8)
+            assert got["now"][e] == st.now
         assert bool(got["truncated"][e]) == out["truncated"], f"env {e} truncated"
-        if finite and ok.any():
+        if moved and finite and ok.any():
             worst = max(worst, float(np.abs(got["pos"][e][ok] - st.pos[ok]).max()), float(np.abs(got["dir"][e][ok] - st.dir[ok]).max()))
         ref_reward, ref_term = out["reward"], out["terminated"]
         if tied.any():
             ties += 1
             peds_out += int(tied.sum())
+            if not moved:
+                continue                                                   # (the state is the reset's: the tie's outcome cannot be seen)
             # status-only ties: same motion, class in question -> take the GPU's class if it is a legal one and re-evaluate
             idx = np.nonzero(tied)[0]
             same_motion = (np.abs(got["pos"][e][idx] - st.pos[idx]).max() <= ATOL) and (np.abs(got["dir"][e][idx] - st.dir[idx]).max() <= ATOL)
@@ -166,6 +183,8 @@ def compare_step(p, wrap, pre_states, actions, noise, got, min_checked=1, label=
         checked += 1
         np.testing.assert_allclose(got["reward"][e], ref_reward, rtol=1e-5, atol=1e-5, equal_nan=True, err_msg=f"env {e} reward")
         assert bool(got["terminated"][e]) == ref_term, f"env {e} terminated"
+        if not moved:
+            continue                                                       # (the observation is the reset's: the caller checks it)
         ref_obs = flat_oracle_obs(st, wrap, p.eps)
         if wrap.positions == "grav":
             tol_p, tol_e = grav_tolerance(st, wrap.alpha, p.eps)
@@ -175,6 +194,9 @@ def compare_step(p, wrap, pre_states, actions, noise, got, min_checked=1, label=
         else:
             np.testing.assert_allclose(got["obs"][e], ref_obs, rtol=0, atol=ATOL, equal_nan=True, err_msg=f"env {e} obs")
     assert checked >= min_checked, (checked, ties)
+    if counts is not None:
+        counts["checked"] = counts.get("checked", 0) + checked
+        counts["peds_out"] = counts.get("peds_out", 0) + peds_out
     if label is not None:
         TIE_LOG.append((label, len(pre_states), ties, resolved, peds_out))
     return checked, ties, worst
@@ -250,37 +272,37 @@ def test_reset_from_injected_draws(ea, path):
         obs, _ = env.reset(draws=draws)
         obs = obs.cpu().numpy().copy()
         st = {k: v.cpu().numpy() for k, v in env.get_state().items()}
-        ref = O.env_reset(p, draws[0, :, 0:2].astype(np.float64), draws[0, :, 2:4].astype(np.float64))
-        np.testing.assert_array_equal(st["pos"][0], ref.pos.astype(np.float32))
-        np.testing.assert_allclose(st["dir"][0], ref.dir, rtol=0, atol=1e-6)
-        if O.threshold_margin(ref.pos, ref.agent_pos, None, p.width, p.height) > TIE:
-            np.testing.assert_array_equal(st["status"][0], ref.status)
-            ref_obs = flat_oracle_obs(ref, wrap, p.eps)
-            if wrap.positions == "grav":
-                tol_p, tol_e = grav_tolerance(ref, wrap.alpha, p.eps)
-                np.testing.assert_allclose(obs[0][4:6], ref_obs[4:6], rtol=2e-5, atol=tol_p)
-                np.testing.assert_allclose(obs[0][0:4], ref_obs[0:4], rtol=2e-5, atol=tol_e)
-            else:
-                np.testing.assert_allclose(obs[0], ref_obs, rtol=0, atol=ATOL)
-        assert (st["agent_pos"] == 0).all() and (st["agent_dir"] == 0).all() and st["now"][0] == 0
+        check_reset(p, wrap, draws[0], {k: v[0] for k, v in st.items()}, obs[0])
         env.close()
+
+
+def check_reset(p, wrap, draws, st, obs, label=""):
+    """One env's state `st` (get_state, one row) and observation `obs` after a reset from `draws` [N, 4] against O.env_reset:
+    positions bit-equal, directions to 1e-6; statuses and the observation where no status threshold lies within TIE.
+    Returns whether those were compared."""
+    ref = O.env_reset(p, draws[:, 0:2].astype(np.float64), draws[:, 2:4].astype(np.float64))
+    np.testing.assert_array_equal(st["pos"], ref.pos.astype(np.float32), err_msg=f"{label} reset pos")
+    np.testing.assert_allclose(st["dir"], ref.dir, rtol=0, atol=1e-6, err_msg=f"{label} reset dir")
+    compared = O.threshold_margin(ref.pos, ref.agent_pos, None, p.width, p.height) > TIE
+    if compared:
+        np.testing.assert_array_equal(st["status"], ref.status, err_msg=f"{label} reset status")
+        ref_obs = flat_oracle_obs(ref, wrap, p.eps)
+        if wrap.positions == "grav":
+            tol_p, tol_e = grav_tolerance(ref, wrap.alpha, p.eps)
+            np.testing.assert_allclose(obs[4:6], ref_obs[4:6], rtol=2e-5, atol=tol_p, err_msg=f"{label} reset obs")
+            np.testing.assert_allclose(obs[0:4], ref_obs[0:4], rtol=2e-5, atol=tol_e, err_msg=f"{label} reset obs")
+        else:
+            np.testing.assert_allclose(obs, ref_obs, rtol=0, atol=ATOL, err_msg=f"{label} reset obs")
+    assert (st["agent_pos"] == 0).all() and (st["agent_dir"] == 0).all() and st["now"] == 0, label
+    return compared
 
 
 @pytest.mark.parametrize("n", [1, 2, 33, 64, 65, 100, 256, 300, 512, 600, 1024])
 def test_random_states_all_sizes(ea, n):
     """Kernel geometry edges (1 wave, 4/8/16-wave workgroups, ragged last wave) on oracle-generated
     states: random reset, a few oracle steps to mix statuses, then one teacher-forced step."""
-    rng = np.random.default_rng(100 + n)
-    p = O.OracleParams(number_of_pedestrians=n, is_new_exiting_reward=True, intrinsic_reward_coef=0.5, enslaving_degree=0.7)
-    E = 6 if n <= 256 else 3
-    pre, acts, nzs = [], [], []
-    for e in range(E):
-        st = O.env_reset(p, rng.uniform(-1, 1, (n, 2)), rng.uniform(-1, 1, (n, 2)))
-        for _ in range(e * 3):
-            O.env_step(p, st, rng.uniform(-1, 1, 2).astype(np.float32), rng.uniform(-0.1, 0.1, n))
-        pre.append(st)
-        acts.append(rng.uniform(-1, 1, 2).astype(np.float32))
-        nzs.append(rng.uniform(-0.1, 0.1, n).astype(np.float32))
+    p, pre, acts, nzs = H.random_states(n)
+    E = len(pre)
     for w in (dict(positions="grav", alpha=3), dict(positions="rel", statuses="ohe", type="Box")):
         wrap = ea.EnvWrappersConfig(**w)
         got = gpu_step_batch(ea, p, wrap, pre, acts, nzs)
@@ -294,33 +316,7 @@ def test_late_episode_states_with_few_rows(ea, n):
     families) or deal the rows to the waves and sweep the tile with the lanes (cell-list family, N > 512).  Crafted states of
     that kind -- 80 % escaped, a flock around the leader, a handful of loners, one dense knot -- one teacher-forced step
     against the reference-precision oracle."""
-    rng = np.random.default_rng(7000 + n)
-    p = O.OracleParams(number_of_pedestrians=n, is_new_exiting_reward=True, is_new_followers_reward=True, enslaving_degree=1.0)
-    pre, acts, nzs = [], [], []
-    for e in range(4):
-        pos = rng.uniform(-1, 1, (n, 2))
-        d = rng.uniform(-1, 1, (n, 2))
-        agent = rng.uniform(-0.6, 0.6, 2).astype(np.float32)
-        k_esc = int(n * (0.8 if e < 3 else 0.5))
-        esc = rng.permutation(n)[:k_esc]
-        rest = np.setdiff1d(np.arange(n), esc)
-        flock = rest[: max(1, (2 * len(rest)) // 3)]                          # followers: inside the leader's radius
-        pos[flock] = agent + rng.uniform(-0.12, 0.12, (len(flock), 2))
-        knot = rest[len(flock):][: max(0, len(rest) // 6)]                    # loners that see each other
-        pos[knot] = np.array([0.7, 0.6]) + rng.uniform(-0.05, 0.05, (len(knot), 2))
-        pos[esc] = O.EXIT_POSITION
-        d[esc] = 0.0
-        with np.errstate(all="ignore"):
-            st = O.env_reset(p, pos, d)               # (normalises the directions: 0 / 0 for the escaped, overwritten below)
-        st.dir[esc] = 0.0
-        st.agent_pos = agent.copy()
-        st.agent_dir = (rng.uniform(-1, 1, 2) * 0.01).astype(np.float32)
-        st.status = O.classify_statuses(st.pos, st.agent_pos, O.EXIT_POSITION, st.pos.dtype)
-        st.now = 1200 + e
-        assert (st.status == O.ESCAPED).sum() >= k_esc and (st.status == O.VISCEK).sum() <= max(8, n // 4)
-        pre.append(st)
-        acts.append(rng.uniform(-1, 1, 2).astype(np.float32))
-        nzs.append(rng.uniform(-0.1, 0.1, n).astype(np.float32))
+    p, pre, acts, nzs = H.late_episode_states(n)
     for w in (dict(positions="grav", alpha=3), dict(positions="rel", statuses="ohe", type="Box")):
         wrap = ea.EnvWrappersConfig(**w)
         got = gpu_step_batch(ea, p, wrap, pre, acts, nzs)
