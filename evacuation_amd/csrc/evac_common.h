@@ -541,9 +541,14 @@ __device__ __forceinline__ void rms_update1(double& mean, double& var, double& c
     var = m2 / tot;
     count = tot;
 }
+// np.clip (the chain's TransformObservation / TransformReward): a NaN stays NaN -- fmin / fmax alone would return -clip for it
+// (the reference's NaN poisoning, area.py:101, reaches the observation; the running statistics are NaN from then on anyway)
+__device__ __forceinline__ float clip_like_np(double v, float clip) {
+    return v != v ? (float)v : (float)fmin(fmax(v, -(double)clip), (double)clip);
+}
 __device__ __forceinline__ float norm_clip(double x, double mean, double var, double eps, float clip) {
     const double v = (x - mean) / sqrt(var + eps);
-    return (float)fmin(fmax(v, -(double)clip), (double)clip);
+    return clip_like_np(v, clip);
 }
 // what evac_step_normalized passes to the step kernel (state == nullptr: plain evac_step)
 struct NormArgs {

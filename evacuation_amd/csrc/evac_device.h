@@ -478,7 +478,7 @@ __device__ __forceinline__ void step_outputs(const Params& p, typename F::Ctx& w
             ret = ret * (double)na.gamma * (o.terminated ? 0.0 : 1.0) + (double)r;
             rms_update1(mean, var, cnt, ret);
             const double v = (double)r / sqrt(var + (double)na.eps);
-            r = (float)fmin(fmax(v, -(double)na.reward_clip), (double)na.reward_clip);
+            r = clip_like_np(v, na.reward_clip);
             ns[3 * D] = mean; ns[3 * D + 1] = var; ns[3 * D + 2] = cnt; ns[3 * D + 3] = ret;
         }
         reward_out[w.env] = r;
@@ -1280,7 +1280,7 @@ __global__ void k_norm_step(int n_envs, int D, float* __restrict__ obs, float* _
             ret = ret * (double)gamma * (1.0 - ((terminated && terminated[e]) ? 1.0 : 0.0)) + r;
             rms_update1(mean, var, cnt, ret);
             const double v = r / sqrt(var + (double)eps);
-            reward[e] = (float)fmin(fmax(v, -(double)reward_clip), (double)reward_clip);
+            reward[e] = clip_like_np(v, reward_clip);
             s[3 * D] = mean; s[3 * D + 1] = var; s[3 * D + 2] = cnt; s[3 * D + 3] = ret;
         }
     }

@@ -96,7 +96,7 @@ __device__ __forceinline__ void step_kernel_body_sub(
             ret = ret * (double)na.gamma * (o.terminated ? 0.0 : 1.0) + (double)r;
             rms_update1(mean, var, cnt, ret);
             const double v = (double)r / sqrt(var + (double)na.eps);
-            r = (float)fmin(fmax(v, -(double)na.reward_clip), (double)na.reward_clip);
+            r = clip_like_np(v, na.reward_clip);
             ns[3 * D] = mean; ns[3 * D + 1] = var; ns[3 * D + 2] = cnt; ns[3 * D + 3] = ret;
         }
         reward_out[w.env] = r;

@@ -488,6 +488,32 @@ def main(argv=None):
          step_size=0.05, is_new_exiting_reward=True, intrinsic_reward_coef=1.0)
     traj("traj_n256_s10_noreward", 10, 64, obs_every=16, number_of_pedestrians=256,
          is_new_followers_reward=False, init_reward_each_step=0.0, noise_coef=0.05)
+    # the configuration space off the defaults: rooms W != H (H < 1 < W, both > 1, W < 1 < H), the three sin/cos regimes of the
+    # noise (|noise| / 2 <= 0.2, <= pi / 4, above), eps 1e-4 / 1e-3, enslaving degree 0 / 0.05, init reward 0.5, intrinsic
+    # coefficient 3, both reward switches in both states, wall termination, step sizes 0.03 .. 0.08.  The "only_*" ones are
+    # eligible for the default-configuration kernels (evac_create's default_cfg) in every respect but the one named; the
+    # "eligible_*" ones are eligible in every respect, with a room, an eps and a step size those kernels keep as run-time values.
+    traj("traj_n10_s11_room25_noise25_ens005_trunc", 11, 40, obs_every=4, number_of_pedestrians=10, width=2.5, height=2.5,
+         noise_coef=2.5, eps=1e-4, enslaving_degree=0.05, step_size=0.08, init_reward_each_step=0.5, intrinsic_reward_coef=3.0,
+         is_new_exiting_reward=True, is_new_followers_reward=False, max_timesteps=30)
+    traj("traj_n32_s12_room07x13_noise1_ens0", 12, 48, obs_every=4, number_of_pedestrians=32, width=0.7, height=1.3,
+         noise_coef=1.0, eps=1e-3, enslaving_degree=0.0, step_size=0.03, intrinsic_reward_coef=3.0)
+    traj("traj_n60_s127_room16x06_noise25_wallterm", 127, 64, obs_every=4, number_of_pedestrians=60, width=1.6, height=0.6,
+         noise_coef=2.5, eps=1e-3, is_termination_agent_wall_collision=True, init_reward_each_step=0.5, step_size=0.05,
+         is_new_exiting_reward=True)
+    traj("traj_n60_s14_only_noise06", 14, 32, obs_every=4, number_of_pedestrians=60, noise_coef=0.6)
+    traj("traj_n100_s69_only_wallterm", 69, 64, obs_every=8, number_of_pedestrians=100, width=1.6, height=0.6, step_size=0.07,
+         is_termination_agent_wall_collision=True)
+    traj("traj_n256_s16_only_noise25", 16, 16, obs_every=8, number_of_pedestrians=256, width=1.6, height=0.6, noise_coef=2.5)
+    traj("traj_n512_s17_only_ens0999", 17, 16, obs_every=16, number_of_pedestrians=512, width=0.7, height=1.3, eps=1e-4,
+         enslaving_degree=0.999)
+    traj("traj_n512_s18_eligible_room16x06_eps1e4_step04", 18, 16, obs_every=16, number_of_pedestrians=512, width=1.6, height=0.6,
+         eps=1e-4, step_size=0.04, init_reward_each_step=0.5, intrinsic_reward_coef=3.0, is_new_exiting_reward=True,
+         is_new_followers_reward=False)
+    traj("traj_n1024_s25_eligible_room16x06_eps1e3_step07", 25, 4, obs_every=4, number_of_pedestrians=1024, width=1.6, height=0.6,
+         eps=1e-3, step_size=0.07, init_reward_each_step=0.5, is_new_exiting_reward=True)
+    traj("traj_n1024_s20_room25_noise12_ens0", 20, 4, obs_every=4, number_of_pedestrians=1024, width=2.5, height=2.5,
+         noise_coef=1.2, enslaving_degree=0.0, intrinsic_reward_coef=3.0)
     if not only or "episode_all_escaped" in only:
         make_terminating_episode(ref)
     if not only or "crafted" in only:

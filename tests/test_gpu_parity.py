@@ -153,7 +153,9 @@ def compare_step(p, wrap, pre_states, actions, noise, got, min_checked=1, label=
             np.testing.assert_allclose(got["pos"][e][ok], st.pos[ok], rtol=0, atol=ATOL, equal_nan=True, err_msg=f"env {e} pos")
             np.testing.assert_allclose(got["dir"][e][ok], st.dir[ok], rtol=0, atol=ATOL, equal_nan=True, err_msg=f"env {e} dir")
             np.testing.assert_allclose(got["agent_pos"][e], st.agent_pos, rtol=0, atol=1e-7)
-            np.testing.assert_allclose(got["agent_dir"][e], st.agent_dir, rtol=0, atol=1e-8)
+            # (1e-8, or 2.5 ulp of the step size where that is more -- from a step of 0.06 on: the kernel multiplies by a reciprocal
+            # where area.py:190 divides, which may differ by 2 ulp of the direction)
+            np.testing.assert_allclose(got["agent_dir"][e], st.agent_dir, rtol=0, atol=max(1e-8, 2.5 * float(np.spacing(np.float32(p.step_size)))))
             assert got["now"][e] == st.now
         assert bool(got["truncated"][e]) == out["truncated"], f"env {e} truncated"
         if moved and finite and ok.any():
@@ -221,7 +223,7 @@ def test_teacher_forced_steps_match_reference_fixtures(ea, path):
     # near-tie from step to step, so the bound scales with the fixture's length; the counts are printed at the end of the session
     # (TIE_LOG), so that a silent growth is visible.
     total_ties = 0
-    for i, w in enumerate(WRAPS if p.number_of_pedestrians <= 256 else WRAPS[:1] + WRAPS[8:9]):
+    for i, w in enumerate(WRAPS):
         wrap = ea.EnvWrappersConfig(**w)
         got = gpu_step_batch(ea, p, wrap, pre, d["action"], d["noise"])
         checked, ties, worst = compare_step(p, wrap, pre, d["action"], d["noise"], got, min_checked=max(1, K - max(4, K // 5)),
