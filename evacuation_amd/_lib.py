@@ -37,6 +37,13 @@ class EvacOptions(C.Structure):
     _fields_ = [(f, C.c_int32) for f in ("subwave", "cells", "cu_wide", "team", "specialize", "parts", "team_coop", "team_fault", "chain")]
 
 
+class EvacMlpPolicy(C.Structure):
+    """evac_mlp_policy_t: the actor-critic's tensors (torch layouts) for evac_policy_rollout"""
+    _fields_ = [("obs_dim", C.c_int32), ("hidden", C.c_int32)] + [
+        (f, C.c_void_p) for f in ("actor_w1", "actor_b1", "actor_w2", "actor_b2", "actor_w3", "actor_b3", "actor_logstd",
+                                  "critic_w1", "critic_b1", "critic_w2", "critic_b2", "critic_w3", "critic_b3")]
+
+
 class EvacError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"libevac error {code}: {msg}")
@@ -84,6 +91,8 @@ SIGNATURES = {
     "evac_norm_init": (C.c_int, [_P, _P, _P]),
     "evac_norm_reset": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, _P]),
     "evac_norm_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    "evac_policy_rollout": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                      C.c_float, C.c_float, C.c_float, C.c_float, _P]),
 }
 
 _lib = None

@@ -16,6 +16,7 @@
 #include "evac_subwave.h"
 #include "evac_team.h"
 #include "evac_gather.h"
+#include "evac_policy.h"
 
 namespace {
 
@@ -1452,6 +1453,48 @@ int evac_norm_step(evac_handle_t h, float* obs, float* final_obs, float* reward,
                        obs, final_obs, reward, terminated, truncated, (const uint8_t*)nullptr, norm_state, gamma, obs_clip,
                        reward_clip, epsilon, 0);
     return check_launch(h, "evac_norm_step");
+}
+
+// ---- evac_policy_rollout: the trainer's collection loop with the actor-critic inside the launch (evac_policy.h) ----
+int evac_policy_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_t* policy, float* next_obs, float* next_done,
+                        float* obs_out, float* actions_out, float* logprob_out, float* value_out, float* reward_out, float* done_out,
+                        float* next_value_out, evac_episode_stats_t* final_stats, double* norm_state, float gamma, float obs_clip,
+                        float reward_clip, float epsilon, void* stream) {
+    EVAC_REQUIRE_BOUND(h, "evac_policy_rollout");
+    if (h->p.n_ped > evac::kWave)
+        return fail(h, EVAC_ERR_UNSUPPORTED, "evac_policy_rollout: rooms of more than 64 pedestrians are not supported (one wave per env)");
+    if (n_steps < 1) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout: n_steps must be >= 1");
+    if (!policy || !next_obs || !next_done || !obs_out || !actions_out || !logprob_out || !value_out || !reward_out || !done_out ||
+        !next_value_out)
+        return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout: policy and every output buffer but final_stats / norm_state must be non-NULL");
+    const evac_mlp_policy_t& P = *policy;
+    if (!P.actor_w1 || !P.actor_b1 || !P.actor_w2 || !P.actor_b2 || !P.actor_w3 || !P.actor_b3 || !P.actor_logstd || !P.critic_w1 ||
+        !P.critic_b1 || !P.critic_w2 || !P.critic_b2 || !P.critic_w3 || !P.critic_b3)
+        return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout: a tensor pointer of the policy is NULL");
+    if (P.hidden != evac::kHidden) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout: hidden must be 64");
+    if (P.obs_dim != h->p.obs_dim)
+        return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout: policy obs_dim " + std::to_string(P.obs_dim) + " != evac_obs_dim " +
+                                                      std::to_string(h->p.obs_dim));
+    if ((uintptr_t)actions_out & 7u) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout: actions_out must be 8-byte aligned");
+    // (parts / chained / persistent handles: joined first, then ONE kernel on `stream` over the whole batch)
+    if (const int st = settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
+    DeviceGuard g(h->device);
+    const evac::PolicyArgs a{P.actor_w1, P.actor_b1, P.actor_w2, P.actor_b2, P.actor_w3, P.actor_b3, P.actor_logstd,
+                             P.critic_w1, P.critic_b1, P.critic_w2, P.critic_b2, P.critic_w3, P.critic_b3,
+                             next_obs, next_done, obs_out, actions_out, logprob_out, value_out, reward_out, done_out, next_value_out,
+                             final_stats};
+    const evac::NormArgs na{norm_state, gamma, obs_clip, reward_clip, epsilon};
+    const bool grav = h->p.obs_pos == EVAC_POS_GRAV, norm = norm_state != nullptr, def = h->default_cfg;
+    using evac::k_policy_rollout;
+    void (*fn)(evac::Params, int, evac::PolicyArgs, evac::NormArgs) =
+        grav ? (norm ? (def ? k_policy_rollout<true, true, true> : k_policy_rollout<true, true, false>)
+                     : (def ? k_policy_rollout<true, false, true> : k_policy_rollout<true, false, false>))
+             : (norm ? (def ? k_policy_rollout<false, true, true> : k_policy_rollout<false, true, false>)
+                     : (def ? k_policy_rollout<false, false, true> : k_policy_rollout<false, false, false>));
+    const int per_block = evac::PolicyFamily::kEnvsPerBlock;
+    hipLaunchKernelGGL(fn, dim3((unsigned)((h->p.n_envs + per_block - 1) / per_block)), dim3(evac::PolicyFamily::kBlock), 0,
+                       (hipStream_t)stream, h->p, (int)n_steps, a, na);
+    return check_launch(h, "evac_policy_rollout");
 }
 
 #ifdef EVAC_STEP_TIMES

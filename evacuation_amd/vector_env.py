@@ -555,6 +555,47 @@ class BatchedEvacuationEnv:
         self.join()                   # (two parts: the returned tensors are ordered behind the launch on the current stream, as ever)
         return out
 
+    def policy_rollout(self, net, n_steps: int, next_obs: torch.Tensor, next_done: torch.Tensor, out: Optional[TDict] = None,
+                       _norm=None):
+        """``n_steps`` iterations of the trainer's collection loop (rpo_agent.py:180-196) in ONE kernel launch
+        (``evac_policy_rollout``): per step the actor-critic ``net`` (RPOLinearNetwork's attribute names: ``actor_mean``,
+        ``critic``, ``actor_logstd``; e.g. ``evacuation_amd.policy.LinearActorCritic``) samples the action on the device from
+        the current observation, and the env steps with it.  ``next_obs`` [E,D] and ``next_done`` [E] (f32 0/1) are the
+        trainer's carried tensors, read and written in place.  Returns the trainer's storage, time-major: ``obs`` [T,E,D],
+        ``actions`` [T,E,2], ``logprobs``, ``values``, ``rewards``, ``dones`` [T,E], ``next_value`` [E] (the bootstrap
+        ``get_value(next_obs)``), ``episode_stats`` [T,E,10] (rows valid where an episode ended), and ``next_obs`` /
+        ``next_done``.  Pass a previous result as ``out`` to reuse it.  Raw observations and rewards here;
+        ``NormalizedVectorEnv.policy_rollout`` runs the trainer's normalisation chain.  No host synchronisation: the call can
+        be captured into a graph, and the kernel reads the parameters in place at every replay."""
+        from .policy import MAX_PEDESTRIANS, PolicyBinder
+        if self.n_ped > MAX_PEDESTRIANS:
+            raise NotImplementedError(f"policy_rollout runs one wave per env: rooms of at most {MAX_PEDESTRIANS} pedestrians "
+                                      f"(this env has {self.n_ped})")
+        T, E, D = int(n_steps), self.num_envs, self.obs_dim
+        if T < 1:
+            raise ValueError("policy_rollout: n_steps must be >= 1")
+        binder = getattr(self, "_policy_binder", None)
+        if binder is None:
+            binder = self._policy_binder = PolicyBinder(D, self.device)
+        pol = binder(net)
+        next_obs = self._check_tensor(next_obs, (E, D), torch.float32, "next_obs")
+        next_done = self._check_tensor(next_done, (E,), torch.float32, "next_done")
+        dev, f32 = self.device, torch.float32
+        shapes = {"obs": (T, E, D), "actions": (T, E, 2), "logprobs": (T, E), "values": (T, E), "rewards": (T, E), "dones": (T, E),
+                  "next_value": (E,), "episode_stats": (T, E, STATS_WORDS)}
+        if out is None:
+            out = {k: (torch.zeros if k == "episode_stats" else torch.empty)(s, dtype=f32, device=dev) for k, s in shapes.items()}
+        else:
+            for k, s in shapes.items():
+                self._check_tensor(out[k], s, f32, k)
+        state, gamma, obs_clip, reward_clip, eps = _norm if _norm is not None else (None, 0.0, 0.0, 0.0, 0.0)
+        _lib.check(self.lib.evac_policy_rollout(
+            self._h, T, C.byref(pol), _ptr(next_obs), _ptr(next_done), _ptr(out["obs"]), _ptr(out["actions"]), _ptr(out["logprobs"]),
+            _ptr(out["values"]), _ptr(out["rewards"]), _ptr(out["dones"]), _ptr(out["next_value"]), _ptr(out["episode_stats"]),
+            _ptr(state), gamma, obs_clip, reward_clip, eps, self._stream()), self._h)
+        out["next_obs"], out["next_done"] = next_obs, next_done
+        return out
+
     def observe(self, out: Optional[torch.Tensor] = None):
         """Observation of the current state without stepping (env.py:98-104 through the wrappers)."""
         out = self.obs if out is None else self._check_tensor(out, (self.num_envs, self.obs_dim), torch.float32, "out")

@@ -61,6 +61,13 @@ class NormalizedVectorEnv:
                                            self.reward_clip, self.epsilon, self.env._stream()), self.env._h)
         return obs, reward, term, trunc, infos
 
+    def policy_rollout(self, net, n_steps: int, next_obs, next_done, out=None):
+        """``BatchedEvacuationEnv.policy_rollout`` through the trainer's chain: observations and rewards come out normalised and
+        clipped, and ``norm_state`` is updated -- exactly as ``n_steps`` calls of ``step`` with the sampled actions would
+        (``next_obs`` is the normalised observation, as the trainer carries it)."""
+        return self.env.policy_rollout(net, n_steps, next_obs, next_done, out=out,
+                                       _norm=(self.norm_state, self.gamma, self.obs_clip, self.reward_clip, self.epsilon))
+
     def final_info_list(self, infos):
         return self.env.final_info_list(infos)
 

@@ -372,6 +372,41 @@ int evac_norm_step(evac_handle_t h, float* obs, float* final_obs_or_null, float*
                    const uint8_t* truncated, double* norm_state, float gamma, float obs_clip, float reward_clip,
                    float epsilon, void* stream);
 
+/* ---- Policy rollout: the trainer's collection loop inside ONE launch (rpo_agent.py:180-196) ----
+ * The actor-critic of RPOLinearNetwork (rpo_linear_agent_network.py:19-61):
+ *   actor_mean = Linear(D,64) Tanh Linear(64,64) Tanh Linear(64,2);  critic = Linear(D,64) Tanh Linear(64,64) Tanh Linear(64,1);
+ *   actor_logstd [1][2].
+ * Tensors in torch layouts (W [out][in] row-major, b [out], f32), read through the pointers WHEN THE KERNEL RUNS: a trainer that
+ * updates its parameters in place (torch optimisers) can capture the call into a graph once and replay it across updates. */
+typedef struct evac_mlp_policy {
+    int32_t obs_dim, hidden;   /* obs_dim == evac_obs_dim(h); hidden == 64 (the reference's default num_hidden) */
+    const float *actor_w1, *actor_b1, *actor_w2, *actor_b2, *actor_w3, *actor_b3, *actor_logstd;
+    const float *critic_w1, *critic_b1, *critic_w2, *critic_b2, *critic_w3, *critic_b3;
+} evac_mlp_policy_t;
+/* n_steps iterations of rpo_agent.py:180-196, per env, with x = next_obs and d = next_done carried in and out:
+ *   obs_out[t] = x; done_out[t] = d;
+ *   mu = actor_mean(x), sigma = exp(actor_logstd), a = mu + sigma * z: z = Box-Muller of Philox4x32-10 at counter
+ *   (env id, 0, total steps of the env, 'POLI'): u1 = ((w0 >> 8) + 1) 2^-24, u2 = (w1 >> 8) 2^-24, r = sqrt(-2 ln u1),
+ *   z = (r cos 2 pi u2, r sin 2 pi u2) -- statistically equivalent to Normal.sample, not bit-identical to torch;
+ *   actions_out[t] = a (unclipped), logprob_out[t] = Normal(mu, sigma).log_prob(a).sum(), value_out[t] = critic(x);
+ *   the env steps with a exactly as evac_step (norm_state NULL) / evac_step_normalized would (ClipAction, noise, autoreset,
+ *   episode records; the terminal observation of a finished episode is always counted in the statistics);
+ *   reward_out[t] = the (normalised) reward; d = terminated | truncated; x = the new (normalised, reset) observation;
+ *   final_stats_or_null[t] = the episode record of envs that finished at step t.
+ * Then next_obs = x, next_done = d, next_value_out = critic(x) (the bootstrap get_value(next_obs)).
+ *   next_obs [E][D], next_done [E] (f32 0/1): in/out;  obs_out [T][E][D], actions_out [T][E][2], logprob_out / value_out /
+ *   reward_out / done_out [T][E], next_value_out [E], final_stats_or_null [T][E].
+ * One wave per env: EVAC_ERR_UNSUPPORTED for rooms of more than 64 pedestrians.  EVAC_ERR_INVALID_ARGUMENT for a NULL pointer,
+ * hidden != 64 or obs_dim != evac_obs_dim(h).  Handles with parts = 2 or chain = 1 / 2 are joined first; the call is ONE kernel
+ * on `stream`. */
+int evac_policy_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_t* policy,
+                        float* next_obs, float* next_done,
+                        float* obs_out, float* actions_out, float* logprob_out,
+                        float* value_out, float* reward_out, float* done_out,
+                        float* next_value_out, evac_episode_stats_t* final_stats_or_null,
+                        double* norm_state_or_null, float gamma, float obs_clip, float reward_clip, float epsilon,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
