@@ -6,7 +6,7 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# EVAC_LIB overrides the library path (profiling builds made by tools/ablate.sh only)
+# EVAC_LIB overrides the library path (builds of another tree for A/B runs: tools/ab_bench.sh, tools/chain_trace.sh)
 LIB_PATH = os.environ.get("EVAC_LIB") or os.path.join(HERE, "libevac.so")
 
 EVAC_OK = 0

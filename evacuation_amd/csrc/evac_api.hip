@@ -1497,60 +1497,4 @@ int evac_policy_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_
     return check_launch(h, "evac_policy_rollout");
 }
 
-#ifdef EVAC_STEP_TIMES
-// diagnostic build only: the shader clock right now -- a one-wave kernel on `stream` that reads s_memtime (shader clock) and
-// s_memrealtime (100 MHz) at both ends of ~20 us; out2[0] = shader cycles, out2[1] = 100 MHz ticks (device memory, 16 bytes)
-__global__ void k_debug_clock(unsigned long long* out2) {
-    unsigned long long c0, c1, r0, r1;
-    asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(c0), "=s"(r0)::"memory");
-    unsigned n = 0;
-    do { asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r1)::"memory"); } while (r1 - r0 < 2000ull && ++n < (1u << 20));
-    asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(c1), "=s"(r1)::"memory");
-    out2[0] = c1 - c0;
-    out2[1] = r1 - r0;
-}
-int evac_debug_clock(unsigned long long* out2_dev, void* stream) {
-    hipLaunchKernelGGL(k_debug_clock, dim3(1), dim3(64), 0, (hipStream_t)stream, out2_dev);
-    return hipGetLastError() == hipSuccess ? EVAC_OK : EVAC_ERR_HIP;
-}
-int evac_debug_step_times(unsigned long long* out2048) {
-    if (hipMemcpyFromSymbol(out2048, HIP_SYMBOL(g_step_times), 16 * 128 * sizeof(unsigned long long)) != hipSuccess) return EVAC_ERR_HIP;
-    return EVAC_OK;
-}
-#endif
-#ifdef EVAC_STEP_TIMES
-int evac_debug_launch_marks(unsigned long long* out8192) {
-    if (hipMemcpyFromSymbol(out8192, HIP_SYMBOL(g_launch_marks), 64 * 2 * 16 * 8 * sizeof(unsigned long long)) != hipSuccess) return EVAC_ERR_HIP;
-    return EVAC_OK;
-}
-#endif
-#ifdef EVAC_STEP_TIMES
-int evac_debug_launch_span(unsigned long long* out32768) {
-    if (hipMemcpyFromSymbol(out32768, HIP_SYMBOL(g_launch_span), 64 * 256 * 2 * sizeof(unsigned long long)) != hipSuccess) return EVAC_ERR_HIP;
-    return EVAC_OK;
-}
-#endif
-#ifdef EVAC_STAMP_WAVES
-int evac_debug_stamp_block(int block, unsigned long long* slowest) {      // set the reporting workgroup; read and clear the slowest-workgroup word
-    unsigned long long z = 0;
-    if (slowest && hipMemcpyFromSymbol(slowest, HIP_SYMBOL(g_slowest), 8) != hipSuccess) return EVAC_ERR_HIP;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_slowest), &z, 8) != hipSuccess) return EVAC_ERR_HIP;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_block), &block, 4) != hipSuccess) return EVAC_ERR_HIP;
-    return EVAC_OK;
-}
-int evac_debug_wave_stamps(unsigned long long* out256) {
-    if (hipMemcpyFromSymbol(out256, HIP_SYMBOL(g_wave_stamps), 256 * sizeof(unsigned long long)) != hipSuccess) return EVAC_ERR_HIP;
-    return EVAC_OK;
-}
-#endif
-#ifdef EVAC_STAMP
-// diagnostic build only: read and clear the per-phase cycle sums
-int evac_debug_stamps(unsigned long long* out16) {
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_stamps), 16 * sizeof(unsigned long long)) != hipSuccess) return EVAC_ERR_HIP;
-    unsigned long long z[16] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof(z)) != hipSuccess) return EVAC_ERR_HIP;
-    return EVAC_OK;
-}
-#endif
-
 }  // extern "C"

@@ -17,54 +17,6 @@
 
 #include "../../include/evac.h"
 
-// Profiling-only phase ablation (tools/ablate.sh builds side libraries with -DEVAC_ABLATE=mask; the
-// shipped library is always built with 0).  1: no pair loop, 2: no observation epilogue,
-// 4: no Philox (constant action / noise), 8: no status/reward reductions, 16: no per-step stores.  (Round 4's mask 32 -- waves
-// without a row to evaluate skip their step -- is gone: a skipped env's clock stops, it is never reset, and over a benchmark's
-// sweeps the batch drifts into that frozen state; what it timed was another workload, not a bound: DESIGN.md 9.)
-#ifndef EVAC_ABLATE
-#define EVAC_ABLATE 0
-#endif
-
-// Diagnostic build only (-DEVAC_STAMP, tools/stamps.sh): s_memtime stamps around the phases of a step,
-// summed per phase over all waves into g_stamps.  No stamp executes in the shipped library.
-// Diagnostic build only (-DEVAC_STEP_TIMES, tools/step_times.py): s_memrealtime at the top of every step of the 16 waves of
-// workgroup 0 -- how the waves of one CU progress through a launch.  (Separate from EVAC_STAMP: the phase stamps end every wave
-// with atomics on 16 shared words, which stall the waves still running and distort exactly this picture.)
-#ifdef EVAC_STEP_TIMES
-#ifndef EVAC_STEP_TIMES_BLOCK
-#define EVAC_STEP_TIMES_BLOCK 0      // (the workgroup whose waves are stamped)
-#endif
-__device__ unsigned long long g_step_times[16][128];
-// ... and, for the waves of workgroups 0 and 100, the 100 MHz clock at kernel entry / at the top of the first step / after the last step /
-// in front of the state write-back (+ four marks inside the prologue), for the last 64 launches (tools/launch_edges.py: what a launch boundary is made of)
-__device__ unsigned long long g_launch_marks[64][2][16][8];
-__device__ unsigned long long g_launch_span[64][256][2];      // ... and entry / exit of wave 0 of EVERY workgroup: the true kernel boundary
-#endif
-#ifdef EVAC_STAMP
-__device__ unsigned long long g_stamps[16];
-#ifdef EVAC_STAMP_WAVES
-__device__ unsigned long long g_wave_stamps[16][16];
-__device__ int g_stamp_block;                 // the workgroup whose waves report (tools/wave_stamps.py sets it to the slowest one of a first pass)
-__device__ unsigned long long g_slowest;      // max over workgroups of (lifetime of wave 0 << 20 | workgroup)
-#endif
-struct StampState {
-    unsigned long long acc[16] = {};
-    unsigned long long last = 0;
-};
-#define EVAC_T(c, k)                                                                      \
-    do {                                                                                  \
-        unsigned long long now_;                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory");      \
-        __builtin_amdgcn_sched_barrier(0);                                                \
-        (c).stamp.acc[k] += now_ - (c).stamp.last;                                        \
-        (c).stamp.last = now_;                                                            \
-    } while (0)
-#else
-#define EVAC_T(c, k) do { } while (0)
-#endif
-
 namespace evac {
 
 constexpr int kViscek = 1, kFollower = 2, kExiting = 3, kEscaped = 4;   // statuses.py:16-27
@@ -790,7 +742,7 @@ __device__ __forceinline__ bool chain_wait(const ChainArgs& ch, int env) {
 // (the abort line keeps what the last wave to give up waited for: word 1 the generation, word 2 the env -- diagnostics of a run that
 // is void anyway.  Kept this small on purpose: a version that also carried the last value polled out of chain_wait -- one more live
 // scalar through the prologue -- left the kernel, instruction for instruction the same in its step loop, 15-45 % slower in its steps
-// in every run (tools/chain_rhythm.py; profiles/r06_*_chain_bisect.txt): this kernel's register allocation is at its limits.)
+// in every run (profiles/r06_*_chain_bisect.txt): this kernel's register allocation is at its limits.)
 __device__ __forceinline__ void chain_give_up(const ChainArgs& ch, int lane, int env) {
     if (lane == 0) {
         store_dev_i32(ch.abort + 1, ch.gen);
@@ -884,6 +836,19 @@ __device__ __forceinline__ bool persist_wait(const char* ring, int idx, int lane
         if (polls < 8) __builtin_amdgcn_s_sleep(1); else __builtin_amdgcn_s_sleep(4);
     }
     return false;
+}
+// A command as one wave read it, handed to the other waves of its env (of its member workgroup, in a team) through a row of six
+// ints in LDS: the wave that read it puts it there (one lane), the others get it behind the barrier that follows -- wave-uniform.
+__device__ __forceinline__ void persist_put_cmd(int* pc, bool got, int steps, unsigned long long slab, unsigned long long stats) {
+    pc[0] = got ? 1 : 0; pc[1] = steps;
+    pc[2] = (int)(unsigned)slab; pc[3] = (int)(unsigned)(slab >> 32);
+    pc[4] = (int)(unsigned)stats; pc[5] = (int)(unsigned)(stats >> 32);
+}
+__device__ __forceinline__ void persist_get_cmd(const int* pc, bool& got, int& steps, unsigned long long& slab, unsigned long long& stats) {
+    got = __builtin_amdgcn_readfirstlane(pc[0]) != 0;
+    steps = __builtin_amdgcn_readfirstlane(pc[1]);
+    slab = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(pc[3]) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(pc[2]);
+    stats = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(pc[5]) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(pc[4]);
 }
 
 // the episode record: env.py:115-125 (nine keys) + Time.n_episodes

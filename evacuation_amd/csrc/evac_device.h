@@ -102,12 +102,10 @@ __device__ __forceinline__ void step_env(const Params& p, typename F::Ctx& c, bo
     if (work) pp = pre_pair(p, q);
     const bool efv = pp.efv, fv = pp.fv, fol = pp.fol, row = pp.row;
     const float ux = pp.ux, uy = pp.uy;
-    EVAC_T(c, 1);   // leader + per-lane pre-pair work
 
     // ---- neighbour sum: area.py:104-119 ----
     float sx, sy;
     F::neighbour_sum(p, c, q, efv, row, ux, uy, sx, sy);
-    EVAC_T(c, 3);   // neighbour sum
 
     Sums s{};
     unsigned long long pred[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -163,7 +161,6 @@ __device__ __forceinline__ void step_env(const Params& p, typename F::Ctx& c, bo
         q.dx = (mx != 0.0f) ? -q.dx : q.dx;
         q.dy = (my != 0.0f) ? -q.dy : q.dy;
     }
-    EVAC_T(c, 4);   // heading, blend, move, reflect
 
     // ---- statuses, rewards, termination: area.py:155-178, statuses.py:29-48, reward.py:19-47 ----
     // The first idle lane (i == N, if the env does not fill its lanes) stands on the exit: it evaluates the
@@ -198,19 +195,17 @@ __device__ __forceinline__ void step_env(const Params& p, typename F::Ctx& c, bo
     }   // work
     if constexpr (GRAV) F::exit_publish(c, exit_lane, gx, gy);
     if constexpr (F::kPipelined) F::stage_next(p, c, q, work);   // team kernels: the next step's tile entry travels with this reduction
-    if constexpr (!(EVAC_ABLATE & 8)) {
-        if constexpr (F::kPipelined) {
-            // team kernels: the reduction is a round trip through global memory; the step's observation row -- per-lane data that does
-            // not depend on it -- is stored between the publish and the poll, under that latency (rollout_body stores it again, over
-            // this one, on the rare step that ends an episode: the reset observation)
-            F::reduce_publish(p, c, s, pred);
-            if constexpr (!GRAV) {
-                if (work && c.obs_dst != nullptr) write_obs_generic(p, c.i, active, q, e, StorePlain{c.obs_dst});
-            }
-            F::reduce_collect(p, c, s);
-        } else {
-            F::template reduce<false>(p, c, s, pred);
+    if constexpr (F::kPipelined) {
+        // team kernels: the reduction is a round trip through global memory; the step's observation row -- per-lane data that does
+        // not depend on it -- is stored between the publish and the poll, under that latency (rollout_body stores it again, over
+        // this one, on the rare step that ends an episode: the reset observation)
+        F::reduce_publish(p, c, s, pred);
+        if constexpr (!GRAV) {
+            if (work && c.obs_dst != nullptr) write_obs_generic(p, c.i, active, q, e, StorePlain{c.obs_dst});
         }
+        F::reduce_collect(p, c, s);
+    } else {
+        F::template reduce<false>(p, c, s, pred);
     }
     out.reward = out.gx = out.gy = out.ex = out.ey = 0.0f;
     if (GRAV && work) {                       // (helper waves store no observation)
@@ -226,7 +221,6 @@ __device__ __forceinline__ void step_env(const Params& p, typename F::Ctx& c, bo
         out.gx = s.f1;
         out.gy = s.f2;
     }
-    EVAC_T(c, 5);   // classify + reductions
     out.n_escaped = s.i[2];
     out.n_follower = s.i[4];
     out.n_exiting = out.n_viscek = 0;   // filled by finish_counts() when the episode ends
@@ -266,7 +260,6 @@ __device__ __forceinline__ void step_env(const Params& p, typename F::Ctx& c, bo
     e.acc_ret += out.reward;                                                // env.py:168-170
     e.acc_intr += intrinsic;
     e.acc_stat += r_agent + r_ped;
-    EVAC_T(c, 6);   // rewards, flags
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -561,6 +554,23 @@ EVAC_STEP_KERNEL_DEFAULT(k_step_default_config, false)
 EVAC_STEP_KERNEL_DEFAULT(k_step_norm_default_config, true)
 #undef EVAC_STEP_KERNEL_DEFAULT
 
+// Trajectory capture for rendering (Pedestrians.save / Agent.save, pedestrians.py:33-35, area.py:32-33): the post-step, pre-reset
+// state of env `env` at step t, capture[t][capture_envs][N + 1][3]; row N holds the leader.
+__device__ __forceinline__ void capture_state(const Params& p, float* __restrict__ capture, int capture_envs, int t, int env, int i,
+                                              bool active, bool owner, const Ped& q, const Env& e) {
+    float* cp = capture + (((size_t)t * capture_envs + env) * (p.n_ped + 1)) * 3;
+    if (active) {
+        cp[3 * i + 0] = q.x;
+        cp[3 * i + 1] = q.y;
+        cp[3 * i + 2] = (float)q.st;
+    }
+    if (owner) {
+        cp[3 * p.n_ped + 0] = e.ax;
+        cp[3 * p.n_ped + 1] = e.ay;
+        cp[3 * p.n_ped + 2] = 0.0f;
+    }
+}
+
 // T steps per launch, state in registers (rpo_agent.py:180-203 rollout loop, RandomAgent or given actions).
 // Output: ONE packed f32 slab [T][E][D+3] = [obs(D) | reward | terminated | truncated] -- a single message
 // for the all-gather and a single coalesced store stream for the kernel.  GRAV kernels stage the 9 words
@@ -579,11 +589,6 @@ __device__ __forceinline__ void rollout_body(
     float* __restrict__ capture, const float* __restrict__ noise_in, const int* __restrict__ perm = nullptr,
     int* __restrict__ moving_out = nullptr, const int* __restrict__ deal_loads = nullptr, int* __restrict__ deal_perm = nullptr,
     ChainArgs chain = ChainArgs{nullptr, 0, nullptr, nullptr}) {
-#ifdef EVAC_STEP_TIMES
-    unsigned long long mark_entry_, mark_loop_ = 0, mark_done_, mark_perm_, mark_init_, mark_act_, mark_state_;
-#define EVAC_MARK(M) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(M)::"memory")
-    EVAC_MARK(mark_entry_);
-#endif
     if constexpr (CHAIN) {      // this workgroup has its CU: counted for the gate in front of the next launch (system scope: the queue's processor reads it)
         if (threadIdx.x == 0) (void)__hip_atomic_fetch_add(chain.started, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
@@ -592,20 +597,13 @@ __device__ __forceinline__ void rollout_body(
     // the schedule of the CU-wide workgroups: which env this wave carries; any permutation gives the same results
     const int my_slot = w.env;
     if (perm) w.env = __builtin_amdgcn_readfirstlane(perm[w.env]);
-#ifdef EVAC_STEP_TIMES
-    asm volatile("" ::"s"(w.env));
-    EVAC_MARK(mark_perm_);
-#endif
     F::init(w);
-#ifdef EVAC_STEP_TIMES
-    EVAC_MARK(mark_init_);
-#endif
     const bool active = w.i < p.n_ped;
     Ped q;
     Env e;
     if constexpr (!CHAIN) load_env(p, w.env, w.i, active, q, e);
     // THE DEAL OF THE NEXT LAUNCH IS MADE INSIDE THIS ONE, by workgroup 0 before it starts stepping: it carries the lightest
-    // envs of the batch (schedule_slot), which are done 20-30 % before the launch ends (tools/step_times.py) -- the ~3 us of the
+    // envs of the batch (schedule_slot), which are done 20-30 % before the launch ends -- the ~3 us of the
     // sort disappear in that slack.  It sorts by the loads the PREVIOUS launch left (complete, unlike this launch's) into the
     // permutation buffer this launch does not read.  A launch of its own for the sort costs 6.5 us next to a 45 us rollout
     // launch, so rounds 2-3 dealt only every 50-200 env steps; a fresh deal is worth 3 us per launch late in an episode
@@ -664,26 +662,17 @@ __device__ __forceinline__ void rollout_body(
     auto draw_actions = [&](int t_first) {
         if (actions) {
             if (t_first + w.lane < n_steps) lane_act = actions[(size_t)(t_first + w.lane) * E + w.env];
-        } else if constexpr (EVAC_ABLATE & 4) {
-            lane_act = make_float2(0.3f, -0.7f);
         } else {
             lane_act = philox_action(p, gid, e.total + (uint32_t)w.lane);   // e.total grows by exactly 1 per step
         }
         lane_adir = agent_direction(p, lane_act.x, lane_act.y);
     };
     if constexpr (!PERSIST) draw_actions(0);
-#ifdef EVAC_STEP_TIMES
-    asm volatile("" ::"v"(lane_adir.x), "v"(lane_adir.y));
-    EVAC_MARK(mark_act_);
-#endif
     // flush mapping of the staged outputs: lane l carries word l % 9 of staged step l / 9
     const int fl_s = w.lane / kGravRow, fl_k = w.lane - fl_s * kGravRow;
     // Retire the state loads HERE, or their first use inside the loop puts `s_waitcnt vmcnt(0)` -- which
     // also waits for the previous step's stores -- into every iteration.
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) only
-#ifdef EVAC_STEP_TIMES
-    EVAC_MARK(mark_state_);
-#endif
     // (the wave's place among its SIMD-mates: recomputed where it is used rather than held in two more scalar registers)
 #define EVAC_PACE_SIMD (F::WPE == 1 ? (w.slot & 3) : (w.wave_in_env & 3))
 #define EVAC_PACE_K (F::WPE == 1 ? (w.slot >> 2) : w.slot)
@@ -697,17 +686,11 @@ __device__ __forceinline__ void rollout_body(
     constexpr bool kRotate = !F::kPace && std::is_same<F, Wave<F::WPE>>::value && F::WPE < 16;
     int prio_slot = 0;
     if constexpr (kRotate) prio_slot = simd_wave_slot();
-#ifdef EVAC_STAMP
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w.stamp.last)::"memory");
-    unsigned long long rt0_;   // constant 100 MHz counter next to the shader-clock one: their ratio is the clock the kernel ran at
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt0_)::"memory");
-    const unsigned long long ck0_ = w.stamp.last;
-#endif
     // Start-of-launch priorities.  With a schedule (k_schedule) the SIMD's k-th wave carries an env of the k-th load quartile
     // (the heaviest in the SIMD's OLDEST wave, so that age -- the arbiter's tie-break -- works for it too),
     // and the heaviest wave of a SIMD ends the launch: it starts with the highest priority instead of earning it over the
     // first steps (pace_step's information is a step old; with equal priorities the twelve lighter waves of the CU ran their
-    // first steps first and the heavy ones began 3-4 us late: tools/step_times.py).  `pace_seen` is seeded so that step 0
+    // first steps first and the heavy ones began 3-4 us late).  `pace_seen` is seeded so that step 0
     // confirms that rank.
     int pace_seen = 0, pace_prio = 0;
     if constexpr (F::kPace && F::WPE == 1) {
@@ -741,19 +724,10 @@ __device__ __forceinline__ void rollout_body(
                 if (run && !got)                        // the team runs it: it is in the ring, or about to show
                     for (int tries = 0; tries < 8192 && !got; ++tries) got = persist_wait(chain.xchg, cmd_index, w.lane, c_steps, c_slab, c_stats);
                 if (!run) got = false;                  // the team has left before this command
-                if (w.lane == 0) {
-                    int* pc = sm.persist_cmd[0];
-                    pc[0] = got ? 1 : 0; pc[1] = c_steps;
-                    pc[2] = (int)(unsigned)c_slab; pc[3] = (int)(unsigned)(c_slab >> 32);
-                    pc[4] = (int)(unsigned)c_stats; pc[5] = (int)(unsigned)(c_stats >> 32);
-                }
+                if (w.lane == 0) persist_put_cmd(sm.persist_cmd[0], got, c_steps, c_slab, c_stats);
             }
             __syncthreads();
-            const int* pc = sm.persist_cmd[0];
-            got = __builtin_amdgcn_readfirstlane(pc[0]) != 0;
-            c_steps = __builtin_amdgcn_readfirstlane(pc[1]);
-            c_slab = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(pc[3]) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(pc[2]);
-            c_stats = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(pc[5]) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(pc[4]);
+            persist_get_cmd(sm.persist_cmd[0], got, c_steps, c_slab, c_stats);
             // (the next write to persist_cmd lies behind this command's steps and their workgroup barriers)
         } else if constexpr (F::WPE == 1) {
             got = persist_wait(chain.xchg, cmd_index, w.lane, c_steps, c_slab, c_stats);
@@ -762,19 +736,10 @@ __device__ __forceinline__ void rollout_body(
             // waves of an env must not disagree on whether a command came in time
             if (w.wave_in_env == 0) {
                 got = persist_wait(chain.xchg, cmd_index, w.lane, c_steps, c_slab, c_stats);
-                if (w.lane == 0) {
-                    int* pc = sm.persist_cmd[w.slot];
-                    pc[0] = got ? 1 : 0; pc[1] = c_steps;
-                    pc[2] = (int)(unsigned)c_slab; pc[3] = (int)(unsigned)(c_slab >> 32);
-                    pc[4] = (int)(unsigned)c_stats; pc[5] = (int)(unsigned)(c_stats >> 32);
-                }
+                if (w.lane == 0) persist_put_cmd(sm.persist_cmd[w.slot], got, c_steps, c_slab, c_stats);
             }
             F::sync(w);
-            const int* pc = sm.persist_cmd[w.slot];
-            got = __builtin_amdgcn_readfirstlane(pc[0]) != 0;
-            c_steps = __builtin_amdgcn_readfirstlane(pc[1]);
-            c_slab = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(pc[3]) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(pc[2]);
-            c_stats = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(pc[5]) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(pc[4]);
+            persist_get_cmd(sm.persist_cmd[w.slot], got, c_steps, c_slab, c_stats);
             // (the next write to persist_cmd lies behind this command's steps and their barriers: no second barrier here)
         }
         if (!got) break;                                // IDLE: nothing came for ~150 us -- the env's state and its place in the ring are stored, the wave leaves
@@ -792,14 +757,6 @@ __device__ __forceinline__ void rollout_body(
     int stage_off = 0, stage_t0 = 0, flush_t = min(kStageSteps, n_steps) - 1;
     constexpr int kStageRowBytes = (int)sizeof(sm.stage[0][0]);
     for (int t = 0; t < n_steps; ++t) {
-#ifdef EVAC_STEP_TIMES
-        if (w.lane == 0 && t < 128 && blockIdx.x == EVAC_STEP_TIMES_BLOCK && threadIdx.x < 1024) {
-            unsigned long long now_;
-            asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory");
-            g_step_times[threadIdx.x >> 6][t] = now_;
-        }
-        if (t == 0) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(mark_loop_)::"memory");
-#endif
         if constexpr (kRotate) {
             if (p.fair) {
                 // workgroup-per-env kernels: longest job first -- the env's load (its moving pedestrians, known from the last
@@ -814,7 +771,6 @@ __device__ __forceinline__ void rollout_body(
             }
         }
         if constexpr (F::kPace) pace_step(pace_slot, &sm.progress[EVAC_PACE_SIMD * 4], w.lane, t_base + t, pace_seen, pace_prio);
-        EVAC_T(w, 12);  // (sub-phase of the diagnostic build: loop top + pace keeping)
 #undef EVAC_PACE_SIMD
 #undef EVAC_PACE_K
         const int slot64 = t & 63;
@@ -836,7 +792,7 @@ __device__ __forceinline__ void rollout_body(
         if constexpr (F::kHelpers) draws = !w.helper;
         float nz = 0.0f;
         const bool wants_noise = ballot(needs_row(p, q.st)) != 0ull;
-        if (draws && wants_noise && !(EVAC_ABLATE & 4)) {
+        if (draws && wants_noise) {
             const int group = (int)(e.total >> 2);
             if (group != noise_group) {
                 asm volatile("");
@@ -856,25 +812,11 @@ __device__ __forceinline__ void rollout_body(
             if (noise_in) nz = active ? noise_in[((size_t)t * E + w.env) * p.n_ped + w.i] : 0.0f;   // injection mode
         }
         StepOut o{};
-        EVAC_T(w, 0);   // action fetch + noise Philox
         float* rowp = slab_out + ((size_t)t * E + w.env) * row;
-        if constexpr (F::kPipelined && !GRAV && !(EVAC_ABLATE & 2)) w.obs_dst = rowp;     // (team kernels: step_env stores the observation row itself)
+        if constexpr (F::kPipelined && !GRAV) w.obs_dst = rowp;     // (team kernels: step_env stores the observation row itself)
         step_env<F, GRAV>(p, w, active, q, e, adir, nz, o);
-        // trajectory capture for rendering (Pedestrians.save / Agent.save, pedestrians.py:33-35, area.py:32-33):
-        // the post-step, pre-reset state of the first `capture_envs` envs; row N holds the leader.
-        if (DIAG && capture && w.env < capture_envs) {   // wave-/workgroup-uniform; compiled out of the default kernel
-            float* cp = capture + (((size_t)t * capture_envs + w.env) * (p.n_ped + 1)) * 3;
-            if (active) {
-                cp[3 * w.i + 0] = q.x;
-                cp[3 * w.i + 1] = q.y;
-                cp[3 * w.i + 2] = (float)q.st;
-            }
-            if (w.owner) {
-                cp[3 * p.n_ped + 0] = e.ax;
-                cp[3 * p.n_ped + 1] = e.ay;
-                cp[3 * p.n_ped + 2] = 0.0f;
-            }
-        }
+        // trajectory capture of the first `capture_envs` envs: wave-/workgroup-uniform; compiled out of the default kernel
+        if (DIAG && capture && w.env < capture_envs) capture_state(p, capture, capture_envs, t, w.env, w.i, active, w.owner, q, e);
         float o6[6] = {e.ax, e.ay, o.ex, o.ey, o.gx, o.gy};
         float f_term = 0.0f, f_trunc = 0.0f;
         if (o.done) {                        // wave-/workgroup-uniform, rare
@@ -890,37 +832,32 @@ __device__ __forceinline__ void rollout_body(
             if constexpr (GRAV) grav_observation<F>(p, w, active, q, e, o6);
         }
         if constexpr (GRAV) {
-            if constexpr (!(EVAC_ABLATE & 16)) {
-                if (w.owner) {
-                    float* st = (float*)((char*)sm.stage[w.slot][0] + stage_off);
-                    *(f4*)(st + 0) = f4{o6[0], o6[1], o6[2], o6[3]};
-                    *(f4*)(st + 4) = f4{o6[4], o6[5], o.reward, f_term};
-                    st[8] = f_trunc;
-                }
-                stage_off += kStageRowBytes;
-                EVAC_T(w, 14);  // (sub-phase: end-of-episode check, staging of the step's row)
-                if (t == flush_t) {
-                    if (w.wave_in_env == 0) {   // the wave that staged them: in-order LDS, no barrier needed
-                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                        if (fl_s <= t - stage_t0) {
-                            const float v = sm.stage[w.slot][fl_s][fl_k];
-                            float* dst = &slab_out[((size_t)(stage_t0 + fl_s) * E + w.env) * kGravRow + fl_k];
-                            *dst = v;
-                        }
+            if (w.owner) {
+                float* st = (float*)((char*)sm.stage[w.slot][0] + stage_off);
+                *(f4*)(st + 0) = f4{o6[0], o6[1], o6[2], o6[3]};
+                *(f4*)(st + 4) = f4{o6[4], o6[5], o.reward, f_term};
+                st[8] = f_trunc;
+            }
+            stage_off += kStageRowBytes;
+            if (t == flush_t) {
+                if (w.wave_in_env == 0) {   // the wave that staged them: in-order LDS, no barrier needed
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    if (fl_s <= t - stage_t0) {
+                        const float v = sm.stage[w.slot][fl_s][fl_k];
+                        float* dst = &slab_out[((size_t)(stage_t0 + fl_s) * E + w.env) * kGravRow + fl_k];
+                        *dst = v;
                     }
-                    stage_off = 0;
-                    stage_t0 = t + 1;
-                    flush_t = min(t + kStageSteps, n_steps - 1);
                 }
+                stage_off = 0;
+                stage_t0 = t + 1;
+                flush_t = min(t + kStageSteps, n_steps - 1);
             }
         } else {
-            if constexpr (!(EVAC_ABLATE & 2)) {
-                bool stores = true;             // (team kernels: waves without pedestrians store no observation)
-                if constexpr (F::kHelpers) stores = !w.helper;
-                if constexpr (F::kPipelined) stores = stores && o.done;   // (... and the row went out inside step_env: only the reset observation of a finished episode is left)
-                if (stores) write_obs_generic(p, w.i, active, q, e, StorePlain{rowp});
-            }
-            if (w.owner && !(EVAC_ABLATE & 16)) {
+            bool stores = true;             // (team kernels: waves without pedestrians store no observation)
+            if constexpr (F::kHelpers) stores = !w.helper;
+            if constexpr (F::kPipelined) stores = stores && o.done;   // (... and the row went out inside step_env: only the reset observation of a finished episode is left)
+            if (stores) write_obs_generic(p, w.i, active, q, e, StorePlain{rowp});
+            if (w.owner) {
                 rowp[p.obs_dim + 0] = o.reward;
                 rowp[p.obs_dim + 1] = f_term;
                 rowp[p.obs_dim + 2] = f_trunc;
@@ -930,38 +867,11 @@ __device__ __forceinline__ void rollout_body(
             asm volatile("");
             if (t + 1 < n_steps) draw_actions(t + 1);
         }
-        EVAC_T(w, 7);   // autoreset check, observation epilogue, output stores
     }
     if constexpr (!PERSIST) break;
     cmd_index += 1;
     t_base += n_steps;
     }
-#ifdef EVAC_STAMP
-    unsigned long long rt1_;
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt1_)::"memory");
-    bool stamp_me = w.lane == 0;
-    if constexpr (F::kHelpers) stamp_me = stamp_me && !w.helper;   // team kernels: the critical path runs through the ped waves
-#ifdef EVAC_STAMP_WAVES   // per wave of workgroup 0, plain stores: the heaviest wave's own phase breakdown (tools/wave_stamps.py)
-    if (w.lane == 0 && threadIdx.x == 0) atomicMax(&g_slowest, ((rt1_ - rt0_) << 20) | (unsigned long long)blockIdx.x);
-    if (w.lane == 0 && (int)blockIdx.x == g_stamp_block && threadIdx.x < 1024) {
-        for (int k = 0; k < 16; ++k) g_wave_stamps[threadIdx.x >> 6][k] = w.stamp.acc[k];
-        g_wave_stamps[threadIdx.x >> 6][8] = w.stamp.last - ck0_;
-        g_wave_stamps[threadIdx.x >> 6][9] = rt1_ - rt0_;
-    }
-    stamp_me = false;
-#endif
-    if (stamp_me) {
-        for (int k = 0; k < 8; ++k) atomicAdd(&g_stamps[k], w.stamp.acc[k]);
-        for (int k = 12; k < 16; ++k) atomicAdd(&g_stamps[k], w.stamp.acc[k]);   // family-specific sub-phases
-        atomicAdd(&g_stamps[8], w.stamp.last - ck0_);
-        atomicAdd(&g_stamps[9], rt1_ - rt0_);
-        atomicMax(&g_stamps[10], rt1_ - rt0_);                      // slowest / fastest wave of the launch
-        atomicMax(&g_stamps[11], ~0ull - (rt1_ - rt0_));
-    }
-#endif
-#ifdef EVAC_STEP_TIMES
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(mark_done_)::"memory");
-#endif
     if constexpr (F::kEnvBarrier) {               // (multi-wave envs: the load is the column count the last reduction delivered)
         if (moving_out && w.owner) moving_out[w.env] = w.have_next ? w.next_cols : p.n_ped;
     }
@@ -993,28 +903,6 @@ __device__ __forceinline__ void rollout_body(
             if (w.owner) store_dev_i32(persist_next_cmd(chain.xchg) + w.env, cmd_index);
         }
     }
-#ifdef EVAC_STEP_TIMES
-    if (w.lane == 0 && (blockIdx.x == 0 || blockIdx.x == 100) && threadIdx.x < 1024 && n_steps > 0) {
-        unsigned long long mark_exit_;
-        asm volatile("s_waitcnt vmcnt(0)\n\ts_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(mark_exit_)::"memory");   // (the state stores have left)
-        unsigned long long* m = g_launch_marks[((e.total - 1u) / (uint32_t)n_steps) & 63][blockIdx.x == 0 ? 0 : 1][threadIdx.x >> 6];
-        m[0] = mark_entry_;
-        m[1] = mark_loop_;
-        m[2] = mark_done_;
-        m[3] = mark_exit_;
-        m[4] = mark_perm_;
-        m[5] = mark_init_;
-        m[6] = mark_act_;
-        m[7] = mark_state_;
-    }
-    if (threadIdx.x == 0 && blockIdx.x < 256 && n_steps > 0) {
-        unsigned long long mark_exit_;
-        asm volatile("s_waitcnt vmcnt(0)\n\ts_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(mark_exit_)::"memory");
-        unsigned long long* m = g_launch_span[((e.total - 1u) / (uint32_t)n_steps) & 63][blockIdx.x];
-        m[0] = mark_entry_;
-        m[1] = mark_exit_;
-    }
-#endif
 }
 
 template <class F, bool GRAV>

@@ -84,9 +84,6 @@ struct Wave {
         // how many in the waves before this one), which the step's own reduction delivers for free
         int par = 0, next_cols = 0, next_base = 0, next_rows = 0, next_rbase = 0;   // (rows: the pedestrians whose row is needed)
         bool have_next = false;
-#ifdef EVAC_STAMP
-        StampState stamp;
-#endif
         __device__ __forceinline__ explicit Ctx(Smem& s) : sm(s) {
             const int t = threadIdx.x;
             slot = t / kThreadsPerEnv;
@@ -312,7 +309,6 @@ struct Wave {
             poisoned = sm.poison[par][c.slot] != 0;
             if (c.wave_in_env == 0 && c.lane == 0) sm.poison[par ^ 1][c.slot] = 0;   // the other parity's flag: last read before this barrier
         }
-        EVAC_T(c, 2);   // tile write
         sx = 0.0f;
         sy = 0.0f;
         const f4* __restrict__ tile = sm.tile[par][c.slot];
@@ -325,42 +321,40 @@ struct Wave {
             const float XI = q.x * kTileScale, YI = q.y * kTileScale;
             // peers per LDS round trip: 16 (3.31 vs 3.34 us at 8, 3.49 at 4)
             constexpr int B = 16;
-            if constexpr (!(EVAC_ABLATE & 1)) {
-                // two columns per packed instruction (pair2_accumulate): 3 vector instructions per column instead of 5
-                const f2 P = f2{XI, YI}, r2b2 = f2{r2b, r2b};
-                f2 sx2 = f2{0.0f, 0.0f}, sy2 = f2{0.0f, 0.0f};
-                const f4* __restrict__ txy = tile;             // pair m: (X, X', Y, Y')
-                const f4* __restrict__ tuv = tile + kPairs;    //         (ux, ux', uy, uy')
-                int m = 0;                                     // pair index = column / 2
-                const int mp = n8 >> 1;
-                for (; m + B / 2 <= mp; m += B / 2) {          // full batches: 16 columns = 8 pairs = 16 tile reads
-                    f4 a[B / 2], u[B / 2];
+            // two columns per packed instruction (pair2_accumulate): 3 vector instructions per column instead of 5
+            const f2 P = f2{XI, YI}, r2b2 = f2{r2b, r2b};
+            f2 sx2 = f2{0.0f, 0.0f}, sy2 = f2{0.0f, 0.0f};
+            const f4* __restrict__ txy = tile;             // pair m: (X, X', Y, Y')
+            const f4* __restrict__ tuv = tile + kPairs;    //         (ux, ux', uy, uy')
+            int m = 0;                                     // pair index = column / 2
+            const int mp = n8 >> 1;
+            for (; m + B / 2 <= mp; m += B / 2) {          // full batches: 16 columns = 8 pairs = 16 tile reads
+                f4 a[B / 2], u[B / 2];
 #pragma unroll
-                    for (int k = 0; k < B / 2; ++k) { a[k] = txy[m + k]; u[k] = tuv[m + k]; }
+                for (int k = 0; k < B / 2; ++k) { a[k] = txy[m + k]; u[k] = tuv[m + k]; }
 #pragma unroll
-                    for (int k = 0; k < B / 2; ++k) pair2_accumulate(P, a[k], u[k], r2b2, sx2, sy2);
-                }
-                // the remainder (4, 8 or 12 columns: n8 is a multiple of 4) in at most two batches, 8 + 4 -- two LDS round trips,
-                // not one per group of 4 (the heaviest envs, 57..60 moving pedestrians, have 12 left: their wave ends the
-                // launch; a 12-column batch -- one trip -- was measured in round 4: no gain, profiles/r04_f_c2_ab_tail12_reflect_skip_no_gain.txt)
-                if (mp - m >= 4) {
-                    f4 a[4], u[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) { a[k] = txy[m + k]; u[k] = tuv[m + k]; }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) pair2_accumulate(P, a[k], u[k], r2b2, sx2, sy2);
-                    m += 4;
-                }
-                if (m < mp) {
-                    f4 a[2], u[2];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) { a[k] = txy[m + k]; u[k] = tuv[m + k]; }
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) pair2_accumulate(P, a[k], u[k], r2b2, sx2, sy2);
-                }
-                sx = hsum2(sx2);                   // even columns + odd columns
-                sy = hsum2(sy2);
+                for (int k = 0; k < B / 2; ++k) pair2_accumulate(P, a[k], u[k], r2b2, sx2, sy2);
             }
+            // the remainder (4, 8 or 12 columns: n8 is a multiple of 4) in at most two batches, 8 + 4 -- two LDS round trips,
+            // not one per group of 4 (the heaviest envs, 57..60 moving pedestrians, have 12 left: their wave ends the
+            // launch; a 12-column batch -- one trip -- was measured in round 4: no gain, profiles/r04_f_c2_ab_tail12_reflect_skip_no_gain.txt)
+            if (mp - m >= 4) {
+                f4 a[4], u[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { a[k] = txy[m + k]; u[k] = tuv[m + k]; }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) pair2_accumulate(P, a[k], u[k], r2b2, sx2, sy2);
+                m += 4;
+            }
+            if (m < mp) {
+                f4 a[2], u[2];
+#pragma unroll
+                for (int k = 0; k < 2; ++k) { a[k] = txy[m + k]; u[k] = tuv[m + k]; }
+#pragma unroll
+                for (int k = 0; k < 2; ++k) pair2_accumulate(P, a[k], u[k], r2b2, sx2, sy2);
+            }
+            sx = hsum2(sx2);                   // even columns + odd columns
+            sy = hsum2(sy2);
         } else {
             // this wave: up to kRows row slices (64 compacted rows each) of its group of kRows waves, column share `share`
             // (all of this is wave-uniform: kept in scalar registers, unsigned so that the divisions are shifts)
@@ -373,60 +367,58 @@ struct Wave {
             const unsigned per = (groups + (unsigned)kRows - 1u) / (unsigned)kRows;
             const int jbeg = (int)(share_u * per * 4u);
             const int jend = (int)(min((share_u + 1u) * per, groups) * 4u);
-            if constexpr (!(EVAC_ABLATE & 1)) {
-                // R row slices per lane (slots beyond n_rows hold stale positions: computed, never read)
-                auto sweep = [&](auto r_tag) {
-                    constexpr int R = decltype(r_tag)::value;
-                    constexpr int R2 = R / 2;         // pairs of rows taken in packed arithmetic (pair_accumulate_rows2)
-                    float X[R], Y[R], ax[R], ay[R];
-                    f2 X2[R2 ? R2 : 1], Y2[R2 ? R2 : 1], ax2[R2 ? R2 : 1], ay2[R2 ? R2 : 1];
+            // R row slices per lane (slots beyond n_rows hold stale positions: computed, never read)
+            auto sweep = [&](auto r_tag) {
+                constexpr int R = decltype(r_tag)::value;
+                constexpr int R2 = R / 2;         // pairs of rows taken in packed arithmetic (pair_accumulate_rows2)
+                float X[R], Y[R], ax[R], ay[R];
+                f2 X2[R2 ? R2 : 1], Y2[R2 ? R2 : 1], ax2[R2 ? R2 : 1], ay2[R2 ? R2 : 1];
 #pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        const float2 rp = sm.rowpos[par][c.slot][gbase + r * kWave];
-                        X[r] = rp.x; Y[r] = rp.y;
-                        ax[r] = 0.0f; ay[r] = 0.0f;
-                    }
-#pragma unroll
-                    for (int r = 0; r < R2; ++r) {
-                        X2[r] = f2{X[2 * r], X[2 * r + 1]}; Y2[r] = f2{Y[2 * r], Y[2 * r + 1]};
-                        ax2[r] = f2{0.0f, 0.0f}; ay2[r] = f2{0.0f, 0.0f};
-                    }
-                    const f2 r2b2 = f2{r2b, r2b};
-                    auto column = [&](f4 t) {
-#pragma unroll
-                        for (int r = 0; r < R2; ++r) pair_accumulate_rows2(X2[r], Y2[r], t, r2b2, ax2[r], ay2[r]);
-#pragma unroll
-                        for (int r = 2 * R2; r < R; ++r) pair_accumulate(X[r], Y[r], t, r2b, ax[r], ay[r]);
-                    };
-                    constexpr int B = (R <= 2 && !(kEnvBarrier && R == 2)) ? 8 : 4;   // peers per LDS round trip (register budget)
-                    int j = jbeg;
-                    for (; j + B <= jend; j += B) {
-                        f4 t[B];
-#pragma unroll
-                        for (int k = 0; k < B; ++k) t[k] = tile[j + k];
-#pragma unroll
-                        for (int k = 0; k < B; ++k) column(t[k]);
-                    }
-                    if constexpr (B == 8) {
-                        if (j < jend) {
-                            f4 t[4];
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) t[k] = tile[j + k];
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) column(t[k]);
-                        }
-                    }
-#pragma unroll
-                    for (int r = 0; r < R2; ++r) { ax[2 * r] = ax2[r].x; ax[2 * r + 1] = ax2[r].y; ay[2 * r] = ay2[r].x; ay[2 * r + 1] = ay2[r].y; }
-#pragma unroll
-                    for (int r = 0; r < R; ++r) sm.part[share][c.slot][gbase + r * kWave] = make_float2(ax[r], ay[r]);
-                };
-                if (slices == 1) sweep(std::integral_constant<int, 1>{});
-                else if (slices == 2) sweep(std::integral_constant<int, 2>{});
-                else if constexpr (kRows == 4) {
-                    if (slices == 3) sweep(std::integral_constant<int, 3>{});
-                    else if (slices == 4) sweep(std::integral_constant<int, 4>{});
+                for (int r = 0; r < R; ++r) {
+                    const float2 rp = sm.rowpos[par][c.slot][gbase + r * kWave];
+                    X[r] = rp.x; Y[r] = rp.y;
+                    ax[r] = 0.0f; ay[r] = 0.0f;
                 }
+#pragma unroll
+                for (int r = 0; r < R2; ++r) {
+                    X2[r] = f2{X[2 * r], X[2 * r + 1]}; Y2[r] = f2{Y[2 * r], Y[2 * r + 1]};
+                    ax2[r] = f2{0.0f, 0.0f}; ay2[r] = f2{0.0f, 0.0f};
+                }
+                const f2 r2b2 = f2{r2b, r2b};
+                auto column = [&](f4 t) {
+#pragma unroll
+                    for (int r = 0; r < R2; ++r) pair_accumulate_rows2(X2[r], Y2[r], t, r2b2, ax2[r], ay2[r]);
+#pragma unroll
+                    for (int r = 2 * R2; r < R; ++r) pair_accumulate(X[r], Y[r], t, r2b, ax[r], ay[r]);
+                };
+                constexpr int B = (R <= 2 && !(kEnvBarrier && R == 2)) ? 8 : 4;   // peers per LDS round trip (register budget)
+                int j = jbeg;
+                for (; j + B <= jend; j += B) {
+                    f4 t[B];
+#pragma unroll
+                    for (int k = 0; k < B; ++k) t[k] = tile[j + k];
+#pragma unroll
+                    for (int k = 0; k < B; ++k) column(t[k]);
+                }
+                if constexpr (B == 8) {
+                    if (j < jend) {
+                        f4 t[4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) t[k] = tile[j + k];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) column(t[k]);
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < R2; ++r) { ax[2 * r] = ax2[r].x; ax[2 * r + 1] = ax2[r].y; ay[2 * r] = ay2[r].x; ay[2 * r + 1] = ay2[r].y; }
+#pragma unroll
+                for (int r = 0; r < R; ++r) sm.part[share][c.slot][gbase + r * kWave] = make_float2(ax[r], ay[r]);
+            };
+            if (slices == 1) sweep(std::integral_constant<int, 1>{});
+            else if (slices == 2) sweep(std::integral_constant<int, 2>{});
+            else if constexpr (kRows == 4) {
+                if (slices == 3) sweep(std::integral_constant<int, 3>{});
+                else if (slices == 4) sweep(std::integral_constant<int, 4>{});
             }
             sync(c);
             if (fv) {
@@ -502,9 +494,6 @@ struct Cells {
         Smem& sm;
         int env, slot, wave_in_env, lane, i;
         bool owner;
-#ifdef EVAC_STAMP
-        StampState stamp;
-#endif
         __device__ __forceinline__ explicit Ctx(Smem& s) : sm(s) {
             const int t = threadIdx.x;
             slot = 0;
@@ -589,7 +578,6 @@ struct Cells {
         }
         if (c.i < kPad) sm.tile[0][n_cols + c.i] = f4{__builtin_inff(), 0.0f, 0.0f, 0.0f};
         __syncthreads();
-        EVAC_T(c, 2);   // binning
         // ---- 4'. FEW needed rows (most of an episode under enslaving_degree 1: only the VISCEK pedestrians have one) against
         // a tile of any size: one active lane per wave walking its cells is the worst use of the machine.  The needed rows are
         // dealt to the waves instead (in ticket order: arbitrary, and irrelevant for integer sums) and the LANES hold the
@@ -597,7 +585,6 @@ struct Cells {
         const int n_need = __builtin_amdgcn_readfirstlane(sm.cnt[kCells + 1]);
         const int n_cols_u = __builtin_amdgcn_readfirstlane(n_cols);
         const bool transposed = n_need * ((n_cols_u + kWave - 1) / kWave) <= kTransposedWork;
-        if constexpr (!(EVAC_ABLATE & 1)) {
           if (transposed) {
             const f4* __restrict__ tile = sm.tile[0];
             const int wv = __builtin_amdgcn_readfirstlane(c.wave_in_env);
@@ -643,7 +630,6 @@ struct Cells {
                 sm.res[wc & 0x7fff] = i2{ax, ay};
             }
           }
-        }
         __syncthreads();
         // ---- 5. back to the owner of the pedestrian ----
         const i2 r = sm.res[c.i];
@@ -685,9 +671,6 @@ struct Sub {
         int env, slot, lane, sub, i, li;
         unsigned long long gmask;   // this group's lanes in a 64-bit ballot
         bool owner;                 // the group's last lane: the DPP sums are valid there
-#ifdef EVAC_STAMP
-        StampState stamp;
-#endif
         __device__ __forceinline__ explicit Ctx(Smem& s) : sm(s) {
             const int t = threadIdx.x;
             lane = t & (kWave - 1);

@@ -187,19 +187,7 @@ __device__ __forceinline__ void rollout_body_sub(typename Sub<G>::Smem& sm, cons
         }
         StepOut o;
         step_env<F, GRAV>(p, w, active, q, e, adir, nz, o);
-        if (DIAG && capture && valid && w.env < capture_envs) {
-            float* cp = capture + (((size_t)t * capture_envs + w.env) * (p.n_ped + 1)) * 3;
-            if (active) {
-                cp[3 * w.i + 0] = q.x;
-                cp[3 * w.i + 1] = q.y;
-                cp[3 * w.i + 2] = (float)q.st;
-            }
-            if (w.owner) {
-                cp[3 * p.n_ped + 0] = e.ax;
-                cp[3 * p.n_ped + 1] = e.ay;
-                cp[3 * p.n_ped + 2] = 0.0f;
-            }
-        }
+        if (DIAG && capture && valid && w.env < capture_envs) capture_state(p, capture, capture_envs, t, w.env, w.i, active, w.owner, q, e);
         float o6[6] = {e.ax, e.ay, o.ex, o.ey, o.gx, o.gy};
         const bool done = o.terminated || o.truncated;
         if (ballot(done) != 0ull)

@@ -119,9 +119,6 @@ struct Team {
         // the tile in LDS: valid for the coming step?  its size, its NaN headings, this lane's row slot in it
         bool tile_valid = false, staged = false;
         int n_cols = 0, n_nan = 0, row_slot = 0;
-#ifdef EVAC_STAMP
-        StampState stamp;
-#endif
         __device__ __forceinline__ explicit Ctx(Smem& s) : sm(s) {
             // workgroup b = j * 8 + xcd: team (j / K) * 8 + xcd, member j % K -- the K members of a team share an XCD
             const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
@@ -324,14 +321,10 @@ struct Team {
     static __device__ __forceinline__ void reduce_collect(const Params& p, C& c, Sums& s) {
         const bool staged = c.staged;          // uniform over the team: this round also carries the next step's tile
         c.staged = false;
-        EVAC_T(c, 12);   // (sub-phase: per-pedestrian work of the ped waves, record stores)
         const Fetched f = exchange<true>(p, c, staged);
-        EVAC_T(c, 13);   // (sub-phase: the round -- waiting for the member's ped waves, polls, folds)
         const f4 rf = c.sm.red_f;
         const i4 ri = c.sm.red_i;
-        EVAC_T(c, 14);
         if (staged) place_tile(c, f);
-        EVAC_T(c, 15);   // (sub-phase: LDS tile of the next step)
         s.f0 = rf.x;
         s.f1 = rf.y;
         s.f2 = rf.z;
@@ -359,7 +352,6 @@ struct Team {
             place_tile(c, exchange<false>(p, c, true));
         }
         c.tile_valid = false;     // consumed: the step's reduction brings the next one
-        EVAC_T(c, 2);   // exchange (only when the tile was not delivered by the previous step)
         const int n_cols = __builtin_amdgcn_readfirstlane(c.n_cols);
         int n_rows[PW], n_rows_all = 0;
 #pragma unroll
@@ -367,200 +359,198 @@ struct Team {
             n_rows[pw] = __builtin_amdgcn_readfirstlane(sm.rows[pw]);
             n_rows_all += n_rows[pw];
         }
-        if constexpr (!(EVAC_ABLATE & 1)) {
-          if (n_rows_all <= kFewRows) {
-            // ---- FEW rows (most of an episode: only the VISCEK pedestrians of the member need one under enslaving_degree 1):
-            // the sweep is transposed.  The rows are dealt to the 16 waves round-robin and the LANES hold the columns, 64 per
-            // pass, the row's position uniform: r * ceil(n_cols / 64) passes of 7 instructions in all instead of n_cols * 14 per
-            // sixteenth, whatever r is (6 rows against 200 columns: 24 passes instead of 200 column visits).  The lanes' shares
-            // are folded with DPP and lane 63 adds the total to the row's accumulator (integers: the order does not matter).
-            // Round 4: the rows are taken in PAIRS (pair_accumulate_rows2: the two rows' positions uniform in the halves of a
-            // register pair, the column per lane) and the heading sums in packed f32 -- the tile holds the integer headings as
-            // floats (|h| < 2^22) and a lane adds at most kTeamExactBatch = 8 of them before the partial sum goes to its integer
-            // accumulator: exact, the same bits as the integer multiply-adds gave.  6 packed instructions per pass and PAIR of
-            // rows where shift + integer multiply-adds took 7 plain ones per row.
-            const f4* __restrict__ tile = sm.tile;
-            const f2 r2b2 = f2{kRPed2Big, kRPed2Big};
-            // the member's rows numbered across its ped waves: row g of the member = (ped wave, slot); pair k = rows 2k, 2k + 1
-            auto row_of = [&](int g, int& pw_out) {      // (compile-time indices into n_rows: it lives in scalar registers)
-                int pw = 0;
+        if (n_rows_all <= kFewRows) {
+          // ---- FEW rows (most of an episode: only the VISCEK pedestrians of the member need one under enslaving_degree 1):
+          // the sweep is transposed.  The rows are dealt to the 16 waves round-robin and the LANES hold the columns, 64 per
+          // pass, the row's position uniform: r * ceil(n_cols / 64) passes of 7 instructions in all instead of n_cols * 14 per
+          // sixteenth, whatever r is (6 rows against 200 columns: 24 passes instead of 200 column visits).  The lanes' shares
+          // are folded with DPP and lane 63 adds the total to the row's accumulator (integers: the order does not matter).
+          // Round 4: the rows are taken in PAIRS (pair_accumulate_rows2: the two rows' positions uniform in the halves of a
+          // register pair, the column per lane) and the heading sums in packed f32 -- the tile holds the integer headings as
+          // floats (|h| < 2^22) and a lane adds at most kTeamExactBatch = 8 of them before the partial sum goes to its integer
+          // accumulator: exact, the same bits as the integer multiply-adds gave.  6 packed instructions per pass and PAIR of
+          // rows where shift + integer multiply-adds took 7 plain ones per row.
+          const f4* __restrict__ tile = sm.tile;
+          const f2 r2b2 = f2{kRPed2Big, kRPed2Big};
+          // the member's rows numbered across its ped waves: row g of the member = (ped wave, slot); pair k = rows 2k, 2k + 1
+          auto row_of = [&](int g, int& pw_out) {      // (compile-time indices into n_rows: it lives in scalar registers)
+              int pw = 0;
 #pragma unroll
-                for (int q2 = 0; q2 + 1 < PW; ++q2) {
-                    const bool next = pw == q2 && g >= n_rows[q2];
-                    g -= next ? n_rows[q2] : 0;
-                    pw += next ? 1 : 0;
-                }
-                pw_out = pw;
-                return g;
-            };
-            if (n_rows_all <= WPE) {
-                // at most one row per wave (late in an episode: 2-3 VISCEK rows per member): nothing to pair -- one row, one wave
-                int before = 0;                               // rows of the ped waves before this one: the deal goes on across them
+              for (int q2 = 0; q2 + 1 < PW; ++q2) {
+                  const bool next = pw == q2 && g >= n_rows[q2];
+                  g -= next ? n_rows[q2] : 0;
+                  pw += next ? 1 : 0;
+              }
+              pw_out = pw;
+              return g;
+          };
+          if (n_rows_all <= WPE) {
+              // at most one row per wave (late in an episode: 2-3 VISCEK rows per member): nothing to pair -- one row, one wave
+              int before = 0;                               // rows of the ped waves before this one: the deal goes on across them
 #pragma unroll
-                for (int pw = 0; pw < PW; ++pw) {
-                    for (int r = (c.wave - PW - before) & (WPE - 1); r < n_rows[pw]; r += WPE) {   // (the helper waves first: the ped waves come late)
-                        const float2 rp = sm.rowpos[pw][r];   // (uniform address: a broadcast)
-                        int ax = 0, ay = 0;
-                        for (int j1 = 0; j1 < n_cols; j1 += kTeamExactBatch * kWave) {
-                            float fx = 0.0f, fy = 0.0f;
-                            const int jn = min(n_cols, j1 + kTeamExactBatch * kWave);
-                            for (int j0 = j1; j0 < jn; j0 += kWave)
-                                pair_accumulate(rp.x, rp.y, tile[min(j0 + c.lane, n_cols)], kRPed2Big, fx, fy);   // entry n_cols: padding, weight 0
-                            ax += (int)fx; ay += (int)fy;
-                        }
-                        wave_sum2_int_lane63(ax, ay);         // (64 lanes adding to ONE LDS word would be serialised: fold in registers first)
-                        if (c.lane == kWave - 1) {
-                            lds_add(&sm.acc[pw][r][0], ax);
-                            lds_add(&sm.acc[pw][r][1], ay);
-                        }
-                    }
-                    before += n_rows[pw];
-                }
-            }
-            const int n_pairs = n_rows_all <= WPE ? 0 : (n_rows_all + 1) >> 1;
-            for (int k = (c.wave - PW) & (WPE - 1); k < n_pairs; k += WPE) {      // (the helper waves first: the ped waves come late)
-                int pwa, pwb;
-                const int ra = row_of(2 * k, pwa);
-                const bool two = 2 * k + 1 < n_rows_all;
-                const int rb = two ? row_of(2 * k + 1, pwb) : (pwb = pwa, ra);
-                const float2 pa = sm.rowpos[pwa][ra], pb = sm.rowpos[pwb][rb];     // (uniform addresses: broadcasts)
-                const f2 X2 = f2{pa.x, pb.x}, Y2 = f2{pa.y, pb.y};
-                int ax = 0, ay = 0, bx = 0, by = 0;
-                for (int j1 = 0; j1 < n_cols; j1 += kTeamExactBatch * kWave) {            // (one trip unless the tile has more than 512 columns)
-                    f2 ax2 = f2{0.0f, 0.0f}, ay2 = f2{0.0f, 0.0f};
-                    const int jn = min(n_cols, j1 + kTeamExactBatch * kWave);
-                    for (int j0 = j1; j0 < jn; j0 += kWave)
-                        pair_accumulate_rows2(X2, Y2, tile[min(j0 + c.lane, n_cols)], r2b2, ax2, ay2);   // entry n_cols: padding, weight 0
-                    ax += (int)ax2.x; ay += (int)ay2.x; bx += (int)ax2.y; by += (int)ay2.y;
-                }
-                wave_sum2_int_lane63(ax, ay);                 // (64 lanes adding to ONE LDS word would be serialised: fold in registers first)
-                wave_sum2_int_lane63(bx, by);
-                if (c.lane == kWave - 1) {
-                    lds_add(&sm.acc[pwa][ra][0], ax);
-                    lds_add(&sm.acc[pwa][ra][1], ay);
-                    if (two) {
-                        lds_add(&sm.acc[pwb][rb][0], bx);
-                        lds_add(&sm.acc[pwb][rb][1], by);
-                    }
-                }
-            }
-          } else {
-            // ---- the member's rows against the tile: two ped waves (two rows per lane) per pass, 1/16 of the columns per wave ----
-            const int groups = (n_cols + 3) >> 2;
-            const int per = (groups + WPE - 1) / WPE;
-            const int jbeg = __builtin_amdgcn_readfirstlane(c.wave * per * 4);
-            const int jend = __builtin_amdgcn_readfirstlane(min((c.wave + 1) * per, groups) * 4);
-            const f4* __restrict__ tile = sm.tile;
-            if constexpr (PW == 1) {       // teams of 16: one ped wave per member, one row per lane
-                if (sm.rows[0] != 0) {
-                    const float2 rr = sm.rowpos[0][c.lane];
-                    int ax = 0, ay = 0;
-                    for (int j = jbeg; j < jend; j += 4) {
-                        f4 t[4];
-                        float fx = 0.0f, fy = 0.0f;          // (four integer headings: the float sums are exact)
+              for (int pw = 0; pw < PW; ++pw) {
+                  for (int r = (c.wave - PW - before) & (WPE - 1); r < n_rows[pw]; r += WPE) {   // (the helper waves first: the ped waves come late)
+                      const float2 rp = sm.rowpos[pw][r];   // (uniform address: a broadcast)
+                      int ax = 0, ay = 0;
+                      for (int j1 = 0; j1 < n_cols; j1 += kTeamExactBatch * kWave) {
+                          float fx = 0.0f, fy = 0.0f;
+                          const int jn = min(n_cols, j1 + kTeamExactBatch * kWave);
+                          for (int j0 = j1; j0 < jn; j0 += kWave)
+                              pair_accumulate(rp.x, rp.y, tile[min(j0 + c.lane, n_cols)], kRPed2Big, fx, fy);   // entry n_cols: padding, weight 0
+                          ax += (int)fx; ay += (int)fy;
+                      }
+                      wave_sum2_int_lane63(ax, ay);         // (64 lanes adding to ONE LDS word would be serialised: fold in registers first)
+                      if (c.lane == kWave - 1) {
+                          lds_add(&sm.acc[pw][r][0], ax);
+                          lds_add(&sm.acc[pw][r][1], ay);
+                      }
+                  }
+                  before += n_rows[pw];
+              }
+          }
+          const int n_pairs = n_rows_all <= WPE ? 0 : (n_rows_all + 1) >> 1;
+          for (int k = (c.wave - PW) & (WPE - 1); k < n_pairs; k += WPE) {      // (the helper waves first: the ped waves come late)
+              int pwa, pwb;
+              const int ra = row_of(2 * k, pwa);
+              const bool two = 2 * k + 1 < n_rows_all;
+              const int rb = two ? row_of(2 * k + 1, pwb) : (pwb = pwa, ra);
+              const float2 pa = sm.rowpos[pwa][ra], pb = sm.rowpos[pwb][rb];     // (uniform addresses: broadcasts)
+              const f2 X2 = f2{pa.x, pb.x}, Y2 = f2{pa.y, pb.y};
+              int ax = 0, ay = 0, bx = 0, by = 0;
+              for (int j1 = 0; j1 < n_cols; j1 += kTeamExactBatch * kWave) {            // (one trip unless the tile has more than 512 columns)
+                  f2 ax2 = f2{0.0f, 0.0f}, ay2 = f2{0.0f, 0.0f};
+                  const int jn = min(n_cols, j1 + kTeamExactBatch * kWave);
+                  for (int j0 = j1; j0 < jn; j0 += kWave)
+                      pair_accumulate_rows2(X2, Y2, tile[min(j0 + c.lane, n_cols)], r2b2, ax2, ay2);   // entry n_cols: padding, weight 0
+                  ax += (int)ax2.x; ay += (int)ay2.x; bx += (int)ax2.y; by += (int)ay2.y;
+              }
+              wave_sum2_int_lane63(ax, ay);                 // (64 lanes adding to ONE LDS word would be serialised: fold in registers first)
+              wave_sum2_int_lane63(bx, by);
+              if (c.lane == kWave - 1) {
+                  lds_add(&sm.acc[pwa][ra][0], ax);
+                  lds_add(&sm.acc[pwa][ra][1], ay);
+                  if (two) {
+                      lds_add(&sm.acc[pwb][rb][0], bx);
+                      lds_add(&sm.acc[pwb][rb][1], by);
+                  }
+              }
+          }
+        } else {
+          // ---- the member's rows against the tile: two ped waves (two rows per lane) per pass, 1/16 of the columns per wave ----
+          const int groups = (n_cols + 3) >> 2;
+          const int per = (groups + WPE - 1) / WPE;
+          const int jbeg = __builtin_amdgcn_readfirstlane(c.wave * per * 4);
+          const int jend = __builtin_amdgcn_readfirstlane(min((c.wave + 1) * per, groups) * 4);
+          const f4* __restrict__ tile = sm.tile;
+          if constexpr (PW == 1) {       // teams of 16: one ped wave per member, one row per lane
+              if (sm.rows[0] != 0) {
+                  const float2 rr = sm.rowpos[0][c.lane];
+                  int ax = 0, ay = 0;
+                  for (int j = jbeg; j < jend; j += 4) {
+                      f4 t[4];
+                      float fx = 0.0f, fy = 0.0f;          // (four integer headings: the float sums are exact)
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) t[k] = tile[j + k];
+                      for (int k = 0; k < 4; ++k) t[k] = tile[j + k];
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) pair_accumulate(rr.x, rr.y, t[k], kRPed2Big, fx, fy);
-                        ax += (int)fx; ay += (int)fy;
-                    }
-                    lds_add(&sm.acc[0][c.lane][0], ax);
-                    lds_add(&sm.acc[0][c.lane][1], ay);
-                }
-            }
+                      for (int k = 0; k < 4; ++k) pair_accumulate(rr.x, rr.y, t[k], kRPed2Big, fx, fy);
+                      ax += (int)fx; ay += (int)fy;
+                  }
+                  lds_add(&sm.acc[0][c.lane][0], ax);
+                  lds_add(&sm.acc[0][c.lane][1], ay);
+              }
+          }
 #pragma unroll
-            for (int pw = 0; pw + 1 < PW; pw += 2) {
-                const int na = sm.rows[pw], nb = sm.rows[pw + 1];
-                if (na + nb == 0) continue;                                    // uniform
-                if (na != 0 && nb != 0 && na + nb <= kWave) {
-                    // the rows of BOTH ped waves fit one lane each (the middle of an episode: 33 .. 64 needed rows per member): one
-                    // row per lane -- lanes [0, na) the first wave's, [na, na + nb) the second's -- in plain arithmetic, 6
-                    // instructions per column + 4 per eight where the two-rows-per-lane form spends 6 PACKED ones (1.6x the pipe
-                    // time each) + 10 on register pairs that are half empty
-                    const bool second = c.lane >= na;
-                    const float2 rr = second ? sm.rowpos[pw + 1][min(c.lane - na, kWave - 1)] : sm.rowpos[pw][c.lane];
-                    int ax = 0, ay = 0;
-                    int j = jbeg;
-                    for (; j + 8 <= jend; j += 8) {
-                        f4 t[8];
-                        float fx = 0.0f, fy = 0.0f;          // (eight integer headings: the float sums are exact)
+          for (int pw = 0; pw + 1 < PW; pw += 2) {
+              const int na = sm.rows[pw], nb = sm.rows[pw + 1];
+              if (na + nb == 0) continue;                                    // uniform
+              if (na != 0 && nb != 0 && na + nb <= kWave) {
+                  // the rows of BOTH ped waves fit one lane each (the middle of an episode: 33 .. 64 needed rows per member): one
+                  // row per lane -- lanes [0, na) the first wave's, [na, na + nb) the second's -- in plain arithmetic, 6
+                  // instructions per column + 4 per eight where the two-rows-per-lane form spends 6 PACKED ones (1.6x the pipe
+                  // time each) + 10 on register pairs that are half empty
+                  const bool second = c.lane >= na;
+                  const float2 rr = second ? sm.rowpos[pw + 1][min(c.lane - na, kWave - 1)] : sm.rowpos[pw][c.lane];
+                  int ax = 0, ay = 0;
+                  int j = jbeg;
+                  for (; j + 8 <= jend; j += 8) {
+                      f4 t[8];
+                      float fx = 0.0f, fy = 0.0f;          // (eight integer headings: the float sums are exact)
 #pragma unroll
-                        for (int k = 0; k < 8; ++k) t[k] = tile[j + k];
+                      for (int k = 0; k < 8; ++k) t[k] = tile[j + k];
 #pragma unroll
-                        for (int k = 0; k < 8; ++k) pair_accumulate(rr.x, rr.y, t[k], kRPed2Big, fx, fy);
-                        ax += (int)fx; ay += (int)fy;
-                    }
-                    if (j < jend) {
-                        f4 t[4];
-                        float fx = 0.0f, fy = 0.0f;
+                      for (int k = 0; k < 8; ++k) pair_accumulate(rr.x, rr.y, t[k], kRPed2Big, fx, fy);
+                      ax += (int)fx; ay += (int)fy;
+                  }
+                  if (j < jend) {
+                      f4 t[4];
+                      float fx = 0.0f, fy = 0.0f;
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) t[k] = tile[j + k];
+                      for (int k = 0; k < 4; ++k) t[k] = tile[j + k];
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) pair_accumulate(rr.x, rr.y, t[k], kRPed2Big, fx, fy);
-                        ax += (int)fx; ay += (int)fy;
-                    }
-                    if (c.lane < na + nb) {
-                        int* dst = second ? sm.acc[pw + 1][c.lane - na] : sm.acc[pw][c.lane];
-                        lds_add(dst, ax);
-                        lds_add(dst + 1, ay);
-                    }
-                    continue;
-                }
-                const float2 ra = sm.rowpos[pw][c.lane], rb = sm.rowpos[pw + 1][c.lane];   // slots beyond the counts hold stale rows: computed, never read
-                int ax0 = 0, ay0 = 0, ax1 = 0, ay1 = 0;
-                if (na != 0 && nb != 0) {
-                    // (round 4: weights AND sums in packed f32 -- kTeamExactBatch = 8 integer headings sum exactly, then the partial
-                    // sum goes to the integer accumulator: the same bits as before --: 6 packed instructions per column + 10 per
-                    // batch where the integer multiply-adds made it 10 per column)
-                    const f2 X2 = f2{ra.x, rb.x}, Y2 = f2{ra.y, rb.y}, r2b2 = f2{kRPed2Big, kRPed2Big};
-                    // (software-pipelined: the four columns after the ones at hand are on their way from LDS while these are
-                    // evaluated -- the asm fences keep the compiler from sinking the loads to their uses; reading up to four
-                    // entries past the wave's share is harmless, the tile is padded)
-                    int j = jbeg;
-                    f4 ta[4], tb[4];
+                      for (int k = 0; k < 4; ++k) pair_accumulate(rr.x, rr.y, t[k], kRPed2Big, fx, fy);
+                      ax += (int)fx; ay += (int)fy;
+                  }
+                  if (c.lane < na + nb) {
+                      int* dst = second ? sm.acc[pw + 1][c.lane - na] : sm.acc[pw][c.lane];
+                      lds_add(dst, ax);
+                      lds_add(dst + 1, ay);
+                  }
+                  continue;
+              }
+              const float2 ra = sm.rowpos[pw][c.lane], rb = sm.rowpos[pw + 1][c.lane];   // slots beyond the counts hold stale rows: computed, never read
+              int ax0 = 0, ay0 = 0, ax1 = 0, ay1 = 0;
+              if (na != 0 && nb != 0) {
+                  // (round 4: weights AND sums in packed f32 -- kTeamExactBatch = 8 integer headings sum exactly, then the partial
+                  // sum goes to the integer accumulator: the same bits as before --: 6 packed instructions per column + 10 per
+                  // batch where the integer multiply-adds made it 10 per column)
+                  const f2 X2 = f2{ra.x, rb.x}, Y2 = f2{ra.y, rb.y}, r2b2 = f2{kRPed2Big, kRPed2Big};
+                  // (software-pipelined: the four columns after the ones at hand are on their way from LDS while these are
+                  // evaluated -- the asm fences keep the compiler from sinking the loads to their uses; reading up to four
+                  // entries past the wave's share is harmless, the tile is padded)
+                  int j = jbeg;
+                  f4 ta[4], tb[4];
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) ta[k] = tile[j + k];
-                    for (; j + 8 <= jend; j += 8) {             // (the wave's share is a multiple of 4 columns)
-                        f2 ax2, ay2;
+                  for (int k = 0; k < 4; ++k) ta[k] = tile[j + k];
+                  for (; j + 8 <= jend; j += 8) {             // (the wave's share is a multiple of 4 columns)
+                      f2 ax2, ay2;
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) tb[k] = tile[j + 4 + k];
-                        asm volatile("" ::: "memory");
-                        pair_start_rows2(X2, Y2, ta[0], r2b2, ax2, ay2);
+                      for (int k = 0; k < 4; ++k) tb[k] = tile[j + 4 + k];
+                      asm volatile("" ::: "memory");
+                      pair_start_rows2(X2, Y2, ta[0], r2b2, ax2, ay2);
 #pragma unroll
-                        for (int k = 1; k < 4; ++k) pair_accumulate_rows2(X2, Y2, ta[k], r2b2, ax2, ay2);
+                      for (int k = 1; k < 4; ++k) pair_accumulate_rows2(X2, Y2, ta[k], r2b2, ax2, ay2);
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) ta[k] = tile[j + 8 + k];
-                        asm volatile("" ::: "memory");
+                      for (int k = 0; k < 4; ++k) ta[k] = tile[j + 8 + k];
+                      asm volatile("" ::: "memory");
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) pair_accumulate_rows2(X2, Y2, tb[k], r2b2, ax2, ay2);
-                        ax0 += (int)ax2.x; ax1 += (int)ax2.y; ay0 += (int)ay2.x; ay1 += (int)ay2.y;
-                    }
-                    if (j < jend) {
-                        f2 ax2, ay2;
-                        pair_start_rows2(X2, Y2, ta[0], r2b2, ax2, ay2);
+                      for (int k = 0; k < 4; ++k) pair_accumulate_rows2(X2, Y2, tb[k], r2b2, ax2, ay2);
+                      ax0 += (int)ax2.x; ax1 += (int)ax2.y; ay0 += (int)ay2.x; ay1 += (int)ay2.y;
+                  }
+                  if (j < jend) {
+                      f2 ax2, ay2;
+                      pair_start_rows2(X2, Y2, ta[0], r2b2, ax2, ay2);
 #pragma unroll
-                        for (int k = 1; k < 4; ++k) pair_accumulate_rows2(X2, Y2, ta[k], r2b2, ax2, ay2);
-                        ax0 += (int)ax2.x; ax1 += (int)ax2.y; ay0 += (int)ay2.x; ay1 += (int)ay2.y;
-                    }
-                } else {
-                    const float2 rr = na != 0 ? ra : rb;
-                    int ax = 0, ay = 0;
-                    for (int j = jbeg; j < jend; j += 4) {
-                        f4 t[4];
-                        float fx = 0.0f, fy = 0.0f;
+                      for (int k = 1; k < 4; ++k) pair_accumulate_rows2(X2, Y2, ta[k], r2b2, ax2, ay2);
+                      ax0 += (int)ax2.x; ax1 += (int)ax2.y; ay0 += (int)ay2.x; ay1 += (int)ay2.y;
+                  }
+              } else {
+                  const float2 rr = na != 0 ? ra : rb;
+                  int ax = 0, ay = 0;
+                  for (int j = jbeg; j < jend; j += 4) {
+                      f4 t[4];
+                      float fx = 0.0f, fy = 0.0f;
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) t[k] = tile[j + k];
+                      for (int k = 0; k < 4; ++k) t[k] = tile[j + k];
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) pair_accumulate(rr.x, rr.y, t[k], kRPed2Big, fx, fy);
-                        ax += (int)fx; ay += (int)fy;
-                    }
-                    ax0 = ax1 = ax;
-                    ay0 = ay1 = ay;
-                }
-                // the 16 partial sums of a row meet in its LDS accumulator (integers: any order gives the same bits)
-                if (na != 0) { lds_add(&sm.acc[pw][c.lane][0], ax0); lds_add(&sm.acc[pw][c.lane][1], ay0); }
-                if (nb != 0) { lds_add(&sm.acc[pw + 1][c.lane][0], ax1); lds_add(&sm.acc[pw + 1][c.lane][1], ay1); }
-            }
+                      for (int k = 0; k < 4; ++k) pair_accumulate(rr.x, rr.y, t[k], kRPed2Big, fx, fy);
+                      ax += (int)fx; ay += (int)fy;
+                  }
+                  ax0 = ax1 = ax;
+                  ay0 = ay1 = ay;
+              }
+              // the 16 partial sums of a row meet in its LDS accumulator (integers: any order gives the same bits)
+              if (na != 0) { lds_add(&sm.acc[pw][c.lane][0], ax0); lds_add(&sm.acc[pw][c.lane][1], ay0); }
+              if (nb != 0) { lds_add(&sm.acc[pw + 1][c.lane][0], ax1); lds_add(&sm.acc[pw + 1][c.lane][1], ay1); }
           }
         }
         __syncthreads();

@@ -1,7 +1,7 @@
 """Why do the headline's sweeps slow down over the first half second (4.44 -> 4.92 ms)?  Clocks, or the batch itself: envs whose
 episode TERMINATES (every pedestrian escaped) before the truncation at 2000 steps are reset early, so over many sweeps the envs'
 episode phases spread out and every launch carries some freshly reset (dense) envs.  Prints, every 25 sweeps, the sweep time, the
-spread of Time.now over the batch at the sweep boundary and the in-kernel clock ratio is left to tools/stamps.sh.  GPU box."""
+spread of Time.now over the batch at the sweep boundary.  GPU box."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
