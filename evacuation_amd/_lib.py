@@ -44,6 +44,16 @@ class EvacMlpPolicy(C.Structure):
                                   "critic_w1", "critic_b1", "critic_w2", "critic_b2", "critic_w3", "critic_b3")]
 
 
+class EvacRpoLossConfig(C.Structure):
+    """evac_rpo_loss_config_t"""
+    _fields_ = [(f, C.c_float) for f in ("clip_coef", "ent_coef", "vf_coef", "rpo_alpha")] + [("norm_adv", C.c_int32), ("clip_vloss", C.c_int32)]
+
+
+class EvacMlpPolicyGrads(C.Structure):
+    """evac_mlp_policy_grads_t: where evac_rpo_minibatch_grad writes the gradients of the 13 tensors"""
+    _fields_ = [(f, C.c_void_p) for f, _ in EvacMlpPolicy._fields_[2:]]
+
+
 class EvacError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"libevac error {code}: {msg}")
@@ -93,6 +103,10 @@ SIGNATURES = {
     "evac_norm_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "evac_policy_rollout": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                       C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    "evac_gae": (C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
+    "evac_rpo_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
+    "evac_rpo_minibatch_grad": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacRpoLossConfig), C.c_int64, _P, _P, _P, _P, _P, _P,
+                                          C.c_int64, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(EvacMlpPolicyGrads), _P, _P, _P]),
 }
 
 _lib = None

@@ -17,6 +17,7 @@
 #include "evac_team.h"
 #include "evac_gather.h"
 #include "evac_policy.h"
+#include "evac_train.h"
 
 namespace {
 
@@ -1495,6 +1496,106 @@ int evac_policy_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_
     hipLaunchKernelGGL(fn, dim3((unsigned)((h->p.n_envs + per_block - 1) / per_block)), dim3(evac::PolicyFamily::kBlock), 0,
                        (hipStream_t)stream, h->p, (int)n_steps, a, na);
     return check_launch(h, "evac_policy_rollout");
+}
+
+// ---- The trainer's update (evac_train.h): no handle, so errors are reported through the return code alone ----
+namespace {
+int device_of(const void* p) {                     // (no handle: the kernels must run on the device that owns the buffers)
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) == hipSuccess) return attr.device;
+    (void)hipGetLastError();
+    return -1;
+}
+}  // namespace
+
+int evac_gae(int32_t n_steps, int64_t n_envs, const float* rewards, const float* values, const float* dones, const float* next_value,
+             const float* next_done, double gamma, double gae_lambda, float* advantages_out, float* returns_out, void* stream) {
+    if (n_steps < 1 || n_envs < 1 || n_envs >= (int64_t)1 << 38 || !rewards || !values || !dones || !next_value || !next_done ||
+        !advantages_out || !returns_out)
+        return EVAC_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(device_of(rewards));
+    // gamma meets a tensor as float32; gamma * gae_lambda is a product of Python floats, rounded once (rpo_agent.py:217-219)
+    hipLaunchKernelGGL(evac::k_gae, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)n_steps, n_envs,
+                       rewards, values, dones, next_value, next_done, (float)gamma, (float)(gamma * gae_lambda), advantages_out,
+                       returns_out);
+    return hipGetLastError() == hipSuccess ? EVAC_OK : EVAC_ERR_HIP;
+}
+
+int64_t evac_rpo_workspace_bytes(int32_t obs_dim, int64_t n_minibatch) {
+    if (obs_dim < 1 || obs_dim > evac::kTrainMaxObs || n_minibatch < 1 || n_minibatch >= (int64_t)1 << 31) return EVAC_ERR_INVALID_ARGUMENT;
+    return (int64_t)evac::kWsFixedBytes + 2 * n_minibatch * evac::kTrainHidden * (int64_t)sizeof(float) +
+           (int64_t)evac::rpo_w1_parts_floats(obs_dim, n_minibatch) * (int64_t)sizeof(float) +
+           2 * (int64_t)evac::rpo_parts_upper(n_minibatch) * evac::kPart * (int64_t)sizeof(float);
+}
+
+int evac_rpo_minibatch_grad(const evac_mlp_policy_t* policy, const evac_rpo_loss_config_t* cfg, int64_t batch_size, const float* b_obs,
+                            const float* b_actions, const float* b_logprobs, const float* b_advantages, const float* b_returns,
+                            const float* b_values, int64_t n_minibatch, const int64_t* mb_inds, const float* rpo_noise,
+                            uint64_t seed, uint64_t draw_counter, const evac_mlp_policy_grads_t* grads_out, float* stats_out,
+                            void* workspace, void* stream) {
+    if (!policy || !cfg || !b_obs || !b_actions || !b_logprobs || !b_advantages || !b_returns || !b_values || !mb_inds || !grads_out ||
+        !stats_out || !workspace)
+        return EVAC_ERR_INVALID_ARGUMENT;
+    const evac_mlp_policy_t& P = *policy;
+    const evac_mlp_policy_grads_t& G = *grads_out;
+    if (!P.actor_w1 || !P.actor_b1 || !P.actor_w2 || !P.actor_b2 || !P.actor_w3 || !P.actor_b3 || !P.actor_logstd || !P.critic_w1 ||
+        !P.critic_b1 || !P.critic_w2 || !P.critic_b2 || !P.critic_w3 || !P.critic_b3)
+        return EVAC_ERR_INVALID_ARGUMENT;
+    if (!G.actor_w1 || !G.actor_b1 || !G.actor_w2 || !G.actor_b2 || !G.actor_w3 || !G.actor_b3 || !G.actor_logstd || !G.critic_w1 ||
+        !G.critic_b1 || !G.critic_w2 || !G.critic_b2 || !G.critic_w3 || !G.critic_b3)
+        return EVAC_ERR_INVALID_ARGUMENT;
+    if (P.hidden != evac::kTrainHidden || P.obs_dim < 1 || P.obs_dim > evac::kTrainMaxObs)
+        return EVAC_ERR_INVALID_ARGUMENT;
+    if (batch_size < 1 || n_minibatch < 1 || n_minibatch >= (int64_t)1 << 31 || (cfg->norm_adv && n_minibatch < 2))
+        return EVAC_ERR_INVALID_ARGUMENT;              // (the unbiased std of one sample does not exist)
+    if (((uintptr_t)workspace & 15u) != 0) return EVAC_ERR_INVALID_ARGUMENT;
+    evac::RpoArgs a{};
+    a.net[0] = evac::RpoNet{P.actor_w1, P.actor_b1, P.actor_w2, P.actor_b2, P.actor_w3, P.actor_b3,
+                            G.actor_w1, G.actor_b1, G.actor_w2, G.actor_b2, G.actor_w3, G.actor_b3};
+    a.net[1] = evac::RpoNet{P.critic_w1, P.critic_b1, P.critic_w2, P.critic_b2, P.critic_w3, P.critic_b3,
+                            G.critic_w1, G.critic_b1, G.critic_w2, G.critic_b2, G.critic_w3, G.critic_b3};
+    a.logstd = P.actor_logstd;
+    a.glogstd = G.actor_logstd;
+    a.obs = b_obs; a.actions = b_actions; a.logprobs = b_logprobs; a.adv = b_advantages; a.ret = b_returns; a.val = b_values;
+    a.inds = mb_inds;
+    a.noise = rpo_noise;
+    a.stats = stats_out;
+    a.ws = (char*)workspace;
+    a.B = batch_size;
+    a.clip = cfg->clip_coef; a.ent = cfg->ent_coef; a.vf = cfg->vf_coef; a.alpha = cfg->rpo_alpha;
+    a.norm_adv = cfg->norm_adv != 0;
+    a.clip_vloss = cfg->clip_vloss != 0;
+    a.D = P.obs_dim;
+    a.M = (int)n_minibatch;
+    const int p0 = evac::rpo_parts_upper(n_minibatch);
+    a.chunk = (int)((n_minibatch + p0 - 1) / p0);
+    a.P = (int)((n_minibatch + a.chunk - 1) / a.chunk);            // every workgroup has samples (P <= p0: the workspace's bound)
+    a.S = evac::rpo_w1_segments(a.D, n_minibatch);
+    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
+    a.ctr_lo = (uint32_t)draw_counter; a.ctr_hi = (uint32_t)(draw_counter >> 32);
+    const int dev = device_of(workspace);
+    DeviceGuard g(dev);
+    hipStream_t S = (hipStream_t)stream;
+    const size_t lds = evac::rpo_grad_lds_floats(a.D) * sizeof(float);
+    if (lds > 64 * 1024) {                             // (wide observations: more dynamic LDS than the default limit; once per device)
+        static std::mutex mu;
+        static bool raised[64] = {};
+        std::lock_guard<std::mutex> lock(mu);
+        const int slot = dev >= 0 && dev < 64 ? dev : 0;
+        if (!raised[slot]) {
+            const size_t most = evac::rpo_grad_lds_floats(evac::kTrainMaxObs) * sizeof(float);
+            if (hipFuncSetAttribute((const void*)evac::k_rpo_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) != hipSuccess) {
+                (void)hipGetLastError();
+                return EVAC_ERR_HIP;
+            }
+            raised[slot] = true;
+        }
+    }
+    if (a.norm_adv) hipLaunchKernelGGL(evac::k_rpo_adv_stats, dim3(1), dim3(evac::kFinishBlock), 0, S, a);
+    hipLaunchKernelGGL(evac::k_rpo_grad, dim3((unsigned)a.P, 2u), dim3(evac::kGradBlock), lds, S, a);
+    const int tiles = (a.D + evac::kW1Tile - 1) / evac::kW1Tile;
+    hipLaunchKernelGGL(evac::k_rpo_finish, dim3((unsigned)(2 * evac::kFinishCombineWgs + 2 * tiles * a.S)), dim3(evac::kFinishBlock), 0, S, a);
+    return hipGetLastError() == hipSuccess ? EVAC_OK : EVAC_ERR_HIP;
 }
 
 }  // extern "C"

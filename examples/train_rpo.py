@@ -1,0 +1,182 @@
+#!/usr/bin/env python3
+"""The reference trainer's whole loop (src/agents/rpo_agent.py:172-299) on the device: ``RPOTrainer``.
+
+Collection (``policy_rollout``: one launch), advantages (``evac_gae``: one launch), and per minibatch step the gradient of the
+RPO loss (``evac_rpo_minibatch_grad``: three launches) followed by torch's ``clip_grad_norm_`` arithmetic and ``Adam`` on
+``.grad``.  Prints the reference's ``SPS`` line per update.
+
+    python examples/train_rpo.py [--envs 4096] [--steps 128] [--updates 5] [--pedestrians 60]
+
+``--compare`` measures, at the same sizes and with the reference's 32 minibatches x 10 epochs, one ``update()`` (a) with the
+kernels against (b) the same update with the loss written in torch (tests/trainer_ref.py, float32) and autograd, eager and with
+each minibatch step replayed from a ``torch.cuda.graph``, and the split collection / GAE / gradient / optimiser of each: hipEvent
+times after warm-up, the three forms alternated inside every repetition, median and spread of ``--reps`` repetitions.
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import evacuation_amd as ea  # noqa: E402
+from evacuation_amd.policy import LinearActorCritic, mlp_tensors  # noqa: E402
+from evacuation_amd.trainer import RPOTrainer, RPOTrainingConfig, flatten_batch  # noqa: E402
+
+DEV = torch.device("cuda:0")
+
+
+def make_trainer(args, **hooks):
+    cfg = RPOTrainingConfig(num_envs=args.envs, num_steps=args.steps, total_timesteps=args.envs * args.steps * max(args.updates, 1),
+                            num_minibatches=args.minibatches, update_epochs=args.epochs, seed=1)
+    env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=args.pedestrians, is_new_exiting_reward=True),
+                                      ea.EnvWrappersConfig(positions="grav", alpha=3), num_envs=args.envs, gamma=cfg.gamma, seed=1)
+    torch.manual_seed(0)
+    net = LinearActorCritic(env.obs_dim).to(DEV)
+    return RPOTrainer(env, net, cfg, **hooks)
+
+
+def eager_yardstick(R):
+    def fn(trainer, batch, mb_inds, rpo_noise, draw_counter, stats):
+        grads, s, _ = R.minibatch_grad(trainer.net, batch, mb_inds, trainer.cfg, rpo_noise)
+        for p, g in zip(trainer.params, grads):
+            p.grad.copy_(g)
+        stats.copy_(s)
+        return stats
+    return fn
+
+
+class GraphedYardstick:
+    """The same torch step (gather, forward, loss, autograd, copy into .grad) captured once and replayed per minibatch."""
+
+    def __init__(self, R):
+        self.R, self.graph = R, None
+
+    def _step(self, trainer, batch):
+        grads, s, _ = self.R.minibatch_grad(trainer.net, batch, self.inds, trainer.cfg, self.noise)
+        for p, g in zip(trainer.params, grads):
+            p.grad.copy_(g)
+        self.stats.copy_(s)
+
+    def __call__(self, trainer, batch, mb_inds, rpo_noise, draw_counter, stats):
+        if self.graph is None:
+            self.inds, self.noise, self.stats = mb_inds.clone(), rpo_noise.clone(), torch.zeros(8, device=DEV)
+            self.batch = batch                                   # (the storage is reused by every update: same addresses)
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(3):
+                    self._step(trainer, batch)
+            torch.cuda.current_stream().wait_stream(side)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self._step(trainer, batch)
+        assert all(batch[k].data_ptr() == self.batch[k].data_ptr() for k in batch)
+        self.inds.copy_(mb_inds)
+        self.noise.copy_(rpo_noise)
+        self.graph.replay()
+        stats.copy_(self.stats)
+        return stats
+
+
+def timed(fn, n):
+    """Milliseconds per call of ``fn`` over ``n`` calls between two events."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / n
+
+
+def compare(args):
+    from tests import trainer_ref as R
+    gen = torch.Generator(device=DEV).manual_seed(7)
+
+    def noise_fn(M):
+        return (torch.rand(M, 2, device=DEV, generator=gen) * 2 - 1) * 0.5
+    forms = {"kernels": make_trainer(args), "torch eager": make_trainer(args, grad_fn=eager_yardstick(R), rpo_noise_fn=noise_fn),
+             "torch graphed": make_trainer(args, grad_fn=GraphedYardstick(R), rpo_noise_fn=noise_fn)}
+    for tr in forms.values():                                    # warm-up: every shape, the capture, the allocator
+        tr.update()
+        tr.update()
+    torch.cuda.synchronize()
+    M = forms["kernels"].cfg.minibatch_size
+    steps = forms["kernels"].cfg.num_minibatches * forms["kernels"].cfg.update_epochs
+    n_upd = {}
+    for name, tr in forms.items():                               # updates per timed window: at least ~0.4 s
+        ms = timed(tr.update, 1)
+        n_upd[name] = max(1, min(50, int(400.0 / ms) + 1))
+    whole = {k: [] for k in forms}
+    split = {k: {"collection": [], "gae": [], "gradient": [], "optimiser": []} for k in forms}
+    for _ in range(args.reps):
+        for name, tr in forms.items():                           # alternated inside every repetition
+            whole[name].append(timed(tr.update, n_upd[name]))
+        for name, tr in forms.items():
+            cfg = tr.cfg
+            with torch.no_grad():
+                split[name]["collection"].append(timed(lambda: tr.env.policy_rollout(tr.net, cfg.num_steps, tr.next_obs, tr.next_done, out=tr.storage), 5))
+            if name == "kernels":
+                split[name]["gae"].append(timed(lambda: ea.trainer.gae(tr.storage, cfg.gamma, cfg.gae_lambda, out=(tr.advantages, tr.returns)), 20))
+            else:
+                st = tr.storage
+                with torch.no_grad():
+                    split[name]["gae"].append(timed(lambda: R.gae(st["rewards"], st["values"], st["dones"], st["next_value"], st["next_done"],
+                                                                  cfg.gamma, cfg.gae_lambda), 2))
+            batch = flatten_batch(tr.storage, tr.advantages, tr.returns)
+            perm = torch.randperm(cfg.batch_size, device=DEV)
+            z = noise_fn(M)
+            k = [0]
+
+            def grad():
+                i = k[0] % cfg.num_minibatches
+                k[0] += 1
+                tr.grad_fn(tr, batch, perm[i * M:(i + 1) * M], z if tr.rpo_noise_fn is not None else None, k[0], tr.stats)
+            grad()
+            split[name]["gradient"].append(timed(grad, 64 if name != "torch eager" else 16))
+            split[name]["optimiser"].append(timed(lambda: tr.apply_gradient(tr.stats), 64))
+
+    def show(v):
+        return f"{statistics.median(v):9.3f} ms  [{min(v):.3f} .. {max(v):.3f}]"
+    print(f"N = {args.pedestrians}, gravity observation, {args.envs} envs x {args.steps} steps, {steps} minibatch steps of {M} samples per update; "
+          f"median [min .. max] of {args.reps} repetitions")
+    for name in forms:
+        print(f"{name:14s} update()            {show(whole[name])}   ({n_upd[name]} updates per window)")
+        for part, per in (("collection", 1), ("gae", 1), ("gradient", steps), ("optimiser", steps)):
+            v = split[name][part]
+            print(f"{'':14s}   {part:10s} per call {show(v)}   x {per:3d} = {statistics.median(v) * per:9.3f} ms per update")
+    a, c = statistics.median(whole["kernels"]), statistics.median(whole["torch graphed"])
+    print(f"update(): kernels / torch graphed = {a / c:.3f}, kernels / torch eager = {a / statistics.median(whole['torch eager']):.3f}")
+    for tr in forms.values():
+        tr.env.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=128)
+    ap.add_argument("--updates", type=int, default=5)
+    ap.add_argument("--pedestrians", type=int, default=60)
+    ap.add_argument("--minibatches", type=int, default=32)
+    ap.add_argument("--epochs", type=int, default=10)
+    ap.add_argument("--compare", action="store_true", help="time update() with the kernels against the torch yardstick + autograd")
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    if args.compare:
+        return compare(args)
+    tr = make_trainer(args)
+
+    def line(log):
+        r = log["episodes"]["episode_reward"]
+        ret = f"{float(r.mean()):9.2f} over {r.numel():5d} episodes" if r.numel() else "   (no episode finished)"
+        print(f"update {log['update']:3d}  global_step={log['global_step']:9d}  value_loss={log['value_loss']:.4f}  policy_loss={log['policy_loss']:+.5f}  "
+              f"approx_kl={log['approx_kl']:.5f}  clipfrac={log['clipfrac']:.3f}  explained_variance={log['explained_variance']:+.3f}  episodic_return={ret}")
+        print("SPS:", log["SPS"])
+    tr.learn(callback=line)
+    tr.env.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -407,6 +407,59 @@ int evac_policy_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_
                         double* norm_state_or_null, float gamma, float obs_clip, float reward_clip, float epsilon,
                         void* stream);
 
+/* ---- The trainer's update: the other half of RPOAgent.learn() (rpo_agent.py:205-283) for the network above ----
+ * No handle: buffers, sizes and a stream; arguments are validated on the host before anything touches a device, and errors
+ * come back through the return code alone (evac_last_error keeps its meaning for handles).
+ *
+ * evac_gae: rpo_agent.py:205-220 in one launch, one lane per env, time walked backwards, in float32 and operation for operation
+ * as torch evaluates the reference's lines (every product and sum rounded, no fma):
+ *   nonterminal = 1 - done_next;  delta = (r + (gamma * v_next) * nonterminal) - v;
+ *   adv = delta + ((float)(gamma * gae_lambda) * nonterminal) * adv_next;  returns = adv + v
+ * gamma and gae_lambda are doubles because the reference's are Python floats: gamma is rounded to float32 where it meets a
+ * tensor, the product gamma * gae_lambda is formed in double and rounded once.  The result is bit-equal to the reference's loop
+ * under torch float32 on the CPU.  rewards / values / dones / advantages_out / returns_out [T][E], next_value / next_done [E]
+ * (the outputs must not overlap the inputs).  EVAC_ERR_INVALID_ARGUMENT: a NULL pointer, n_steps < 1, n_envs < 1. */
+int evac_gae(int32_t n_steps, int64_t n_envs, const float* rewards, const float* values, const float* dones,
+             const float* next_value, const float* next_done, double gamma, double gae_lambda, float* advantages_out,
+             float* returns_out, void* stream);
+
+/* evac_rpo_minibatch_grad: rpo_agent.py:239-277 for ONE minibatch, up to and including loss.backward(): the forward pass of
+ * actor and critic on b_obs[mb_inds] with the recorded actions, the RPO perturbation of the mean
+ * (rpo_linear_agent_network.py:55-59), the loss as the reference composes it, and its gradient with respect to all 13 tensors,
+ * WRITTEN (not accumulated: the reference calls zero_grad() first) into grads_out in the parameters' own layouts.
+ *   mean = actor_mean(x) + z: z = the row of rpo_noise, or, when it is NULL, rpo_alpha * (2 u - 1) with u the 24-bit uniform of
+ *   words 0 and 1 of Philox4x32-10 at counter (position in the minibatch, draw_counter low, draw_counter high, 'RPOZ') keyed by
+ *   seed -- statistically equivalent to torch's uniform_, not bit-identical (as the policy noise above).  z is a constant for
+ *   the gradient.
+ *   newlogprob, entropy of Normal(mean, exp(logstd)); ratio = exp(newlogprob - b_logprobs); with norm_adv the advantages are
+ *   normalised over THIS minibatch with the unbiased std and + 1e-8 (:250-251); pg_loss = mean(max(-A ratio, -A clamp(ratio,
+ *   1 - clip, 1 + clip))) (:254-256); v_loss clipped or not (:260-271); loss = pg_loss - ent_coef * entropy + vf_coef * v_loss.
+ *   Sub-gradients as torch takes them: clamp passes 1 on the closed interval, max splits a tie half and half.
+ *   stats_out [8] = loss, pg_loss, v_loss, entropy, old_approx_kl, approx_kl, clipfrac, sum of squares of all gradient entries
+ *   (what clip_grad_norm_ needs).
+ * b_obs [B][D], b_actions [B][2], b_logprobs / b_advantages / b_returns / b_values [B]; mb_inds int64 [M] in DEVICE memory, values
+ * in [0, B) (an index outside is clamped into the batch, never followed); rpo_noise [M][2] or NULL; workspace: 16-byte aligned,
+ * evac_rpo_workspace_bytes(obs_dim, M) bytes, contents irrelevant before and after.
+ * At most three launches on `stream`, no host synchronisation, capturable into a graph; the parameters are read when the kernels
+ * run.  DETERMINISTIC: every gradient and statistic is a fixed-order sum (no floating-point atomics), the same bits on every run
+ * and stream.  EVAC_ERR_INVALID_ARGUMENT: a NULL pointer (rpo_noise excepted), hidden != 64, obs_dim outside 1..396,
+ * batch_size < 1, n_minibatch < 1 (< 2 with norm_adv: the unbiased std of one sample does not exist), a misaligned workspace. */
+typedef struct evac_rpo_loss_config {
+    float clip_coef, ent_coef, vf_coef, rpo_alpha;
+    int32_t norm_adv, clip_vloss;
+} evac_rpo_loss_config_t;
+typedef struct evac_mlp_policy_grads {   /* the 13 tensors of evac_mlp_policy_t, writable, same layouts */
+    float *actor_w1, *actor_b1, *actor_w2, *actor_b2, *actor_w3, *actor_b3, *actor_logstd;
+    float *critic_w1, *critic_b1, *critic_w2, *critic_b2, *critic_w3, *critic_b3;
+} evac_mlp_policy_grads_t;
+/* bytes of workspace for a minibatch of M samples (EVAC_ERR_INVALID_ARGUMENT for obs_dim outside 1..396 or M outside 1..2^31-1) */
+int64_t evac_rpo_workspace_bytes(int32_t obs_dim, int64_t n_minibatch);
+int evac_rpo_minibatch_grad(const evac_mlp_policy_t* policy, const evac_rpo_loss_config_t* cfg, int64_t batch_size,
+                            const float* b_obs, const float* b_actions, const float* b_logprobs, const float* b_advantages,
+                            const float* b_returns, const float* b_values, int64_t n_minibatch, const int64_t* mb_inds,
+                            const float* rpo_noise_or_null, uint64_t seed, uint64_t draw_counter,
+                            const evac_mlp_policy_grads_t* grads_out, float* stats_out, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
