@@ -3,14 +3,15 @@
 Public surface = the reference's ``src.env`` exports (src/env/__init__.py:3-21):
 ``setup_env, EvacuationEnv, EnvConfig, EnvWrappersConfig, Status`` plus the batched form
 ``BatchedEvacuationEnv``, its SyncVectorEnv-shaped host face ``HostVectorEnv``, the sharded form ``ShardedEvacuationEnv`` (across GPUs) and ``SplitBatchEnv`` (across streams of one GPU), and the reference trainer's update on
-the device (``RPOTrainer``, ``RPOTrainingConfig``, ``gae``, ``rpo_minibatch_grad``: ``evacuation_amd.trainer``).  Importing the package does
+the device (``RPOTrainer``, ``RPOTrainingConfig``, ``gae``, ``rpo_minibatch_grad``, and the optimiser
+step ``DeviceAdam``, ``rpo_minibatch_step``, ``rpo_update``: ``evacuation_amd.trainer``).  Importing the package does
 not touch the GPU; constructing an env loads libevac.so and fails loudly without it."""
 from .config import EnvConfig, EnvWrappersConfig
 from .statuses import Status
 
 __all__ = ["EnvConfig", "EnvWrappersConfig", "Status", "setup_env", "EvacuationEnv", "BatchedEvacuationEnv",
            "ShardedEvacuationEnv", "SplitBatchEnv", "NormalizedVectorEnv", "HostVectorEnv", "RandomAgent", "KernelOptions", "kernel_options",
-           "RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad"]
+           "RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad", "DeviceAdam", "rpo_minibatch_step", "rpo_update"]
 
 
 def __getattr__(name):   # lazy: keeps `import evacuation_amd` light and torch-free for config users
@@ -38,7 +39,7 @@ def __getattr__(name):   # lazy: keeps `import evacuation_amd` light and torch-f
     if name == "RandomAgent":
         from .agents import RandomAgent
         return RandomAgent
-    if name in ("RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad"):   # the trainer's update on the device
+    if name in ("RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad", "DeviceAdam", "rpo_minibatch_step", "rpo_update"):   # the trainer's update on the device
         from . import trainer as _trainer
         return getattr(_trainer, name)
     raise AttributeError(name)

@@ -54,6 +54,16 @@ class EvacMlpPolicyGrads(C.Structure):
     _fields_ = [(f, C.c_void_p) for f, _ in EvacMlpPolicy._fields_[2:]]
 
 
+class EvacAdamConfig(C.Structure):
+    """evac_adam_config_t"""
+    _fields_ = [(f, C.c_double) for f in ("lr", "beta1", "beta2", "eps", "max_grad_norm")]
+
+
+class EvacAdamState(C.Structure):
+    """evac_adam_state_t: the optimiser's header and moments (caller-owned device memory; all zero = a fresh optimiser)"""
+    _fields_ = [("header", C.c_void_p), ("exp_avg", EvacMlpPolicyGrads), ("exp_avg_sq", EvacMlpPolicyGrads)]
+
+
 class EvacError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"libevac error {code}: {msg}")
@@ -107,6 +117,15 @@ SIGNATURES = {
     "evac_rpo_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
     "evac_rpo_minibatch_grad": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacRpoLossConfig), C.c_int64, _P, _P, _P, _P, _P, _P,
                                           C.c_int64, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(EvacMlpPolicyGrads), _P, _P, _P]),
+    "evac_adam_step": (C.c_int, [C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacAdamState),
+                                 C.POINTER(EvacAdamConfig), C.c_int32, _P, _P]),
+    "evac_rpo_minibatch_step": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacRpoLossConfig), C.c_int64, _P, _P, _P, _P, _P, _P,
+                                          C.c_int64, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(EvacMlpPolicyGrads), _P, _P, _P,
+                                          C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacAdamState), C.POINTER(EvacAdamConfig)]),
+    "evac_rpo_update": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacMlpPolicyGrads),
+                                  C.POINTER(EvacRpoLossConfig), C.POINTER(EvacAdamConfig), C.POINTER(EvacAdamState), C.c_int64,
+                                  _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, C.c_uint64, C.c_uint64, C.c_int32,
+                                  C.c_double, _P, _P, _P]),
 }
 
 _lib = None

@@ -1,7 +1,8 @@
 // Device code of libevac, part 6: the TRAINER'S UPDATE -- the other half of RPOAgent.learn() (rpo_agent.py:205-283) for the network
 // the policy rollout takes (RPOLinearNetwork, hidden width 64): generalised advantage estimation in one launch (k_gae) and the
 // gradient of the RPO / PPO loss of one minibatch with respect to all 13 parameter tensors (k_rpo_*), up to and including what
-// loss.backward() leaves in .grad.  No env handle: buffers, sizes and a stream.
+// loss.backward() leaves in .grad; then the optimiser step, clip_grad_norm_ and Adam (k_adam: one more launch), and the whole
+// update's epochs and minibatches from one host call (evac_rpo_update).  No env handle: buffers, sizes and a stream.
 //
 // evac_rpo_minibatch_grad is at most three launches:
 //   k_rpo_adv_stats  (norm_adv only) mean and unbiased std of the minibatch's advantages, one workgroup, fixed-order sums in f64
@@ -76,6 +77,20 @@ __host__ __device__ inline int rpo_grad_region_floats(int D) {
     const int w = (kTrainHidden + D) * kRowPad, r = kRedCols * kRowPad;
     return ((w > r ? w : r) + 3) & ~3;
 }
+
+// The optimiser's header (evac_adam_state_t.header; k_adam below).  It lives on the device so that a captured step counts when
+// it is replayed.  The k_rpo_* kernels are templates over an optional trailing argument: k_rpo_*<> (RpoArgs alone) are
+// evac_rpo_minibatch_grad's kernels; k_rpo_*<const AdamHeader*> are evac_rpo_update's, which return at once, touching nothing,
+// when the header's stop flag is set.
+struct AdamHeader {                             // 64 bytes (evac_adam_state_t.header)
+    int64_t t;                                  // steps taken
+    double P1, P2;                              // beta1 ** t, beta2 ** t as running products (read as 1 while t == 0)
+    int32_t stop, steps_run, epochs_run;        // evac_rpo_update's early exit and what ran
+    uint32_t ticket;                            // the launch's integer ticket: zero between launches
+    int32_t pad[6];
+};
+static_assert(sizeof(AdamHeader) == 64, "evac_adam_state_t.header is 64 bytes");
+__device__ __forceinline__ bool rpo_stopped(const AdamHeader* h) { return h->stop != 0; }
 
 struct RpoNet {
     const float *w1, *b1, *w2, *b2, *w3, *b3;
@@ -156,8 +171,12 @@ __device__ __forceinline__ double block_sum_1024(double v, double* buf) {
 }
 
 // rpo_agent.py:250-251: mean and torch's default (unbiased) std of b_advantages[mb_inds]; header = (mean, std + 1e-8)
-__global__ __launch_bounds__(kFinishBlock) void k_rpo_adv_stats(RpoArgs a) {
+template <class... Gate>
+__global__ __launch_bounds__(kFinishBlock) void k_rpo_adv_stats(RpoArgs a, Gate... gate) {
     __shared__ double buf[kFinishBlock];
+    if constexpr (sizeof...(Gate) != 0) {
+        if (rpo_stopped(gate...)) return;
+    }
     double s = 0.0, q = 0.0;                   // one pass: in f64 the sum of squares of f32 values loses nothing that matters
 #pragma unroll 8
     for (int m = (int)threadIdx.x; m < a.M; m += kFinishBlock) {
@@ -374,8 +393,12 @@ __device__ __forceinline__ void rpo_grad_body(const RpoArgs& a, float* lds) {
     }
 }
 
-__global__ __launch_bounds__(kGradBlock) void k_rpo_grad(RpoArgs a) {
+template <class... Gate>
+__global__ __launch_bounds__(kGradBlock) void k_rpo_grad(RpoArgs a, Gate... gate) {
     extern __shared__ __attribute__((aligned(16))) float rpo_lds[];
+    if constexpr (sizeof...(Gate) != 0) {
+        if (rpo_stopped(gate...)) return;
+    }
     if (blockIdx.x == 0 && blockIdx.y == 0) {  // (k_rpo_finish follows on the stream)
         if (threadIdx.x == 0) *ws_ticket(a.ws) = 0u;
         if (threadIdx.x < 2 * kMaxW1Tiles) ws_tile_tickets(a.ws)[threadIdx.x] = 0u;
@@ -405,8 +428,12 @@ __device__ __forceinline__ float block_sum_1024f(float v, float* buf) {
     return r;
 }
 
-__global__ __launch_bounds__(kFinishBlock) void k_rpo_finish(RpoArgs a) {
+template <class... Gate>
+__global__ __launch_bounds__(kFinishBlock) void k_rpo_finish(RpoArgs a, Gate... gate) {
     constexpr int H = kTrainHidden;
+    if constexpr (sizeof...(Gate) != 0) {
+        if (rpo_stopped(gate...)) return;
+    }
     __shared__ float red[16][kW1Tile][H];      // 32 KiB: the 16 waves' dW1 tiles; reused for the sums of squares
     __shared__ float fin[32];
     __shared__ int last;
@@ -526,6 +553,83 @@ __global__ __launch_bounds__(kFinishBlock) void k_rpo_finish(RpoArgs a) {
         a.stats[6] = fin[8] * inv_m;
         a.stats[7] = fin[16];
     }
+}
+
+// ---- rpo_agent.py:278-279: clip_grad_norm_ and Adam(eps = 1e-5).step(), one launch (include/evac.h: evac_adam_step) ----
+// A launch of its own behind k_rpo_finish, not a stage of that kernel's last workgroup: the 13 tensors are 9.4 k elements at
+// D = 6 and 59 k at D = 396, four arrays each (150 KB .. 950 KB read, all of it written back), which one workgroup
+// would walk as a chain of dependent loads of what other workgroups just wrote; a launch spreads them over 37 .. 232 workgroups
+// for the price of one kernel boundary, and evac_adam_step (gradients from elsewhere) is then the same kernel, not a twin of it.
+// DESIGN.md section 4.6 has the measured cost.
+constexpr int kAdamTensors = 13;
+constexpr int kAdamBlock = 256;
+struct AdamArgs {
+    float *p[kAdamTensors], *g[kAdamTensors], *m[kAdamTensors], *v[kAdamTensors];
+    int end[kAdamTensors];                      // running element counts: tensor i is [end[i - 1], end[i])
+    AdamHeader* hdr;
+    const float* sumsq;                         // the sum of squares of all gradient entries (device)
+    const float* stats;                         // the step's statistics (approx_kl at [5]) for the early exit, or NULL
+    double lr, beta1, beta2, target_kl;
+    float max_norm, w, b2, u, eps;              // f32(max_grad_norm), f32(1 - beta1), f32(beta2), f32(1 - beta2), f32(eps)
+    int gated, epoch_last, use_target_kl;
+};
+
+// Every workgroup forms the scalars from the same inputs (the header is read-only until the last workgroup has its ticket);
+// one element per thread; every operation rounded on its own (the sequence of include/evac.h, bit for bit).  sqrt goes through
+// double: correctly rounded for a float argument, which the f32 intrinsic of this toolchain is not.
+__device__ __forceinline__ void adam_stage(const AdamArgs& a) {
+    AdamHeader* h = a.hdr;
+    const int64_t t0 = h->t;
+    const double P1 = (t0 == 0 ? 1.0 : h->P1) * a.beta1, P2 = (t0 == 0 ? 1.0 : h->P2) * a.beta2;
+    const float s = *a.sumsq;
+    const float x = a.max_norm / __fadd_rn((float)sqrt((double)s), 1e-6f);
+    const float c = x > 1.0f ? 1.0f : x;        // (a NaN stays a NaN, as torch.clamp keeps it)
+    const float al = (float)(-(a.lr / (1.0 - P1)));
+    const float q = (float)sqrt(1.0 - P2);
+    const int e = (int)blockIdx.x * kAdamBlock + (int)threadIdx.x;
+    if (e < a.end[kAdamTensors - 1]) {
+        float *pp = a.p[0], *pg = a.g[0], *pm = a.m[0], *pv = a.v[0];
+        int base = 0;
+#pragma unroll
+        for (int i = 1; i < kAdamTensors; ++i) {
+            const bool in = e >= a.end[i - 1];
+            pp = in ? a.p[i] : pp;
+            pg = in ? a.g[i] : pg;
+            pm = in ? a.m[i] : pm;
+            pv = in ? a.v[i] : pv;
+            base = in ? a.end[i - 1] : base;
+        }
+        const int o = e - base;
+        const float g0 = pg[o], m0 = pm[o], v0 = pv[o], p0 = pp[o];
+        const float g = __fmul_rn(g0, c);
+        const float m = __fadd_rn(m0, __fmul_rn(a.w, __fsub_rn(g, m0)));
+        const float v = __fadd_rn(__fmul_rn(v0, a.b2), __fmul_rn(__fmul_rn(a.u, g), g));
+        const float den = __fadd_rn((float)sqrt((double)v) / q, a.eps);
+        pg[o] = g;
+        pm[o] = m;
+        pv[o] = v;
+        pp[o] = __fadd_rn(p0, __fmul_rn(al, m) / den);
+    }
+    // the last workgroup to finish (an integer ticket) is the one writer of the header: everybody has read it by then
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned ticket = __hip_atomic_fetch_add(&h->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (ticket == gridDim.x - 1u) {
+            h->t = t0 + 1;
+            h->P1 = P1;
+            h->P2 = P2;
+            h->steps_run += 1;
+            if (a.epoch_last) {                                               // rpo_agent.py:281-283
+                h->epochs_run += 1;
+                if (a.use_target_kl && (double)a.stats[5] > a.target_kl) h->stop = 1;
+            }
+            h->ticket = 0u;
+        }
+    }
+}
+__global__ __launch_bounds__(kAdamBlock) void k_adam(AdamArgs a) {
+    if (a.gated && a.hdr->stop) return;
+    adam_stage(a);
 }
 
 }  // namespace evac

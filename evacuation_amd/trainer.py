@@ -3,13 +3,16 @@
 ``policy_rollout`` fills the trainer's storage in one launch; this module does what the reference does with it afterwards:
 ``gae`` (rpo_agent.py:205-220, ``evac_gae``: one launch), ``rpo_minibatch_grad`` (rpo_agent.py:239-277 up to and including
 ``loss.backward()``, ``evac_rpo_minibatch_grad``: at most three launches, deterministic) and ``RPOTrainer``, one iteration of the
-reference's loop per ``update()``.  Gradient clipping and Adam stay torch (they work on ``.grad`` in place)."""
+reference's loop per ``update()``.  Gradient clipping and Adam are torch's by default (they work on ``.grad`` in place) or the
+library's own (``DeviceAdam``, ``evac_adam_step``: one launch), with which a minibatch step is one host call
+(``rpo_minibatch_step``) and a whole update's epochs and minibatches are one (``rpo_update``), ``target_kl`` included."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 import time
 from dataclasses import dataclass
-from typing import Callable, Dict, Optional
+from typing import Callable, Dict, Optional, Tuple
 
 import torch
 
@@ -144,12 +147,8 @@ def ensure_grads(net) -> "_lib.EvacMlpPolicyGrads":
     return st.grads_struct
 
 
-def rpo_minibatch_grad(net, batch: Dict[str, torch.Tensor], mb_inds: torch.Tensor, cfg, *, rpo_noise: Optional[torch.Tensor] = None,
-                       seed: int = 0, draw_counter: int = 0, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The gradient of the RPO loss of the minibatch ``mb_inds`` of ``batch`` (``flatten_batch``) into the parameters' ``.grad``
-    (written, not accumulated), by ``evac_rpo_minibatch_grad``; returns the 8 statistics (``STAT_NAMES``) as a device tensor.
-    ``cfg``: an ``RPOTrainingConfig`` (or anything with its loss fields).  ``rpo_noise`` [M, 2] injects the RPO perturbation;
-    None draws it on the device from (``seed``, ``draw_counter``).  No host synchronisation; capturable into a graph."""
+def _batch_args(net, batch: Dict[str, torch.Tensor]):
+    """The checks every gradient entry makes of ``batch``; returns (B, D, device, state, evac_mlp_policy_t, grads struct)."""
     b_obs = batch["b_obs"]
     B, D = b_obs.shape
     dev = b_obs.device
@@ -157,33 +156,266 @@ def rpo_minibatch_grad(net, batch: Dict[str, torch.Tensor], mb_inds: torch.Tenso
     _f32(batch["b_actions"], (B, 2), "b_actions")
     for k in BATCH_KEYS[2:]:
         _f32(batch[k], (B,), k)
-    if mb_inds.dtype != torch.int64 or mb_inds.device != dev or not mb_inds.is_contiguous() or mb_inds.dim() != 1:
-        raise ValueError("mb_inds: expected a contiguous int64 device vector")
-    M = int(mb_inds.shape[0])
-    if rpo_noise is not None:
-        _f32(rpo_noise, (M, 2), "rpo_noise")
     st = _grad_state(net)
     if st.binder is None or st.binder.obs_dim != D or st.binder.device != dev:
         st.binder = PolicyBinder(D, dev)
     pol = st.binder(net)
     grads = ensure_grads(net)
-    lib = _lib.load()
-    need = int(lib.evac_rpo_workspace_bytes(D, M))
+    return B, D, dev, st, pol, grads
+
+
+def _workspace(st: _GradState, D: int, M: int, dev) -> torch.Tensor:
+    need = int(_lib.load().evac_rpo_workspace_bytes(D, M))
     if need < 0:
         raise _lib.EvacError(need, f"evac_rpo_workspace_bytes({D}, {M})")
     if st.workspace is None or st.workspace.numel() < need or st.workspace.device != dev:
         st.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    return st.workspace
+
+
+def _loss_config(cfg) -> "_lib.EvacRpoLossConfig":
+    return cfg.loss_config() if hasattr(cfg, "loss_config") else RPOTrainingConfig.loss_config(cfg)
+
+
+def _u64(x: int) -> int:
+    return int(x) & (2 ** 64 - 1)
+
+
+def rpo_minibatch_grad(net, batch: Dict[str, torch.Tensor], mb_inds: torch.Tensor, cfg, *, rpo_noise: Optional[torch.Tensor] = None,
+                       seed: int = 0, draw_counter: int = 0, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of the RPO loss of the minibatch ``mb_inds`` of ``batch`` (``flatten_batch``) into the parameters' ``.grad``
+    (written, not accumulated), by ``evac_rpo_minibatch_grad``; returns the 8 statistics (``STAT_NAMES``) as a device tensor.
+    ``cfg``: an ``RPOTrainingConfig`` (or anything with its loss fields).  ``rpo_noise`` [M, 2] injects the RPO perturbation;
+    None draws it on the device from (``seed``, ``draw_counter``).  No host synchronisation; capturable into a graph."""
+    B, D, dev, st, pol, grads = _batch_args(net, batch)
+    if mb_inds.dtype != torch.int64 or mb_inds.device != dev or not mb_inds.is_contiguous() or mb_inds.dim() != 1:
+        raise ValueError("mb_inds: expected a contiguous int64 device vector")
+    M = int(mb_inds.shape[0])
+    if rpo_noise is not None:
+        _f32(rpo_noise, (M, 2), "rpo_noise")
+    ws = _workspace(st, D, M, dev)
     if stats is None:
         stats = torch.empty(8, dtype=torch.float32, device=dev)
     else:
         _f32(stats, (8,), "stats")
-    lc = cfg.loss_config() if hasattr(cfg, "loss_config") else RPOTrainingConfig.loss_config(cfg)
-    rc = lib.evac_rpo_minibatch_grad(C.byref(pol), C.byref(lc), B, _ptr(b_obs), _ptr(batch["b_actions"]), _ptr(batch["b_logprobs"]),
-                                     _ptr(batch["b_advantages"]), _ptr(batch["b_returns"]), _ptr(batch["b_values"]), M,
-                                     _ptr(mb_inds), _ptr(rpo_noise), int(seed) & (2 ** 64 - 1), int(draw_counter) & (2 ** 64 - 1),
-                                     C.byref(grads), _ptr(stats), _ptr(st.workspace), _stream(dev))
+    lc = _loss_config(cfg)
+    rc = _lib.load().evac_rpo_minibatch_grad(C.byref(pol), C.byref(lc), B, _ptr(batch["b_obs"]), _ptr(batch["b_actions"]),
+                                             _ptr(batch["b_logprobs"]), _ptr(batch["b_advantages"]), _ptr(batch["b_returns"]),
+                                             _ptr(batch["b_values"]), M, _ptr(mb_inds), _ptr(rpo_noise), _u64(seed),
+                                             _u64(draw_counter), C.byref(grads), _ptr(stats), _ptr(ws), _stream(dev))
     _lib.check(rc)
     return stats
+
+
+HEADER_FIELDS = ("t", "P1", "P2", "stop", "steps_run", "epochs_run")
+
+
+def decode_header(header: torch.Tensor) -> dict:
+    """The optimiser's 64-byte header (``evac_adam_state_t.header``) as a dict of ``HEADER_FIELDS``: one host transfer for a
+    device tensor, none for a host copy."""
+    h = header.detach().cpu().contiguous().view(torch.int64).numpy()
+    t = int(h[0])
+    P1, P2 = (float(x) for x in h[1:3].view("float64"))
+    stop, steps_run, epochs_run = (int(x) for x in h[3:5].view("int32")[:3])
+    return {"t": t, "P1": P1 if t else 1.0, "P2": P2 if t else 1.0, "stop": stop, "steps_run": steps_run, "epochs_run": epochs_run}
+
+
+class DeviceAdam:
+    """``clip_grad_norm_(max_grad_norm)`` and ``torch.optim.Adam(lr, betas, eps)`` (no weight decay, no amsgrad) for the 13
+    tensors of ``net`` in one launch (``evac_adam_step``; the arithmetic is specified in include/evac.h).  The step count and
+    the bias corrections' running products live on the device, so a captured step counts when it is replayed.
+    ``param_groups[0]`` is read at every call: ``opt.param_groups[0]["lr"] = lrnow`` works as with torch."""
+
+    def __init__(self, net, lr: float = 3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm: float = 0.5):
+        group = {"lr": float(lr), "betas": (float(betas[0]), float(betas[1])), "eps": float(eps), "max_grad_norm": float(max_grad_norm)}
+        self._check_group(group)
+        self.net = net
+        self.params = list(mlp_tensors(net))
+        self.device = self.params[0].device
+        for p in self.params:
+            if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous():
+                raise ValueError("DeviceAdam: the parameters must be contiguous float32 device tensors")
+        self.obs_dim = int(self.params[0].shape[1])
+        self.param_groups = [group]
+        self.header = torch.zeros(8, dtype=torch.int64, device=self.device)
+        self.exp_avg = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self.exp_avg_sq = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self._state = _lib.EvacAdamState(self.header.data_ptr(), _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in self.exp_avg)),
+                                         _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in self.exp_avg_sq)))
+        self._params_key = self._params_struct = None
+        ensure_grads(net)
+
+    @staticmethod
+    def _check_group(g: dict) -> None:
+        b1, b2 = g["betas"]
+        if not math.isfinite(g["lr"]):
+            raise ValueError(f"DeviceAdam: lr = {g['lr']} is not finite")
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"DeviceAdam: betas = {g['betas']} outside [0, 1)")
+        if not g["eps"] > 0.0:
+            raise ValueError(f"DeviceAdam: eps = {g['eps']} must be > 0")
+        if not g["max_grad_norm"] > 0.0:
+            raise ValueError(f"DeviceAdam: max_grad_norm = {g['max_grad_norm']} must be > 0")
+
+    def config(self) -> "_lib.EvacAdamConfig":
+        g = self.param_groups[0]
+        return _lib.EvacAdamConfig(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["max_grad_norm"]))
+
+    def params_struct(self) -> "_lib.EvacMlpPolicyGrads":
+        key = tuple(p.data_ptr() for p in self.params)
+        if key != self._params_key:
+            self._params_struct, self._params_key = _lib.EvacMlpPolicyGrads(*key), key
+        return self._params_struct
+
+    def state_struct(self) -> "_lib.EvacAdamState":
+        return self._state
+
+    def step(self, grad_sumsq: torch.Tensor) -> None:
+        """Clip the parameters' ``.grad`` by ``grad_sumsq`` (a float32 device scalar: the sum of squares of all gradient entries,
+        ``stats[7]`` of ``rpo_minibatch_grad``) and take one Adam step.  One launch, no host synchronisation."""
+        if not isinstance(grad_sumsq, torch.Tensor) or grad_sumsq.dtype != torch.float32 or grad_sumsq.device != self.device or grad_sumsq.numel() != 1:
+            raise ValueError("DeviceAdam.step: grad_sumsq must be a float32 scalar on the parameters' device")
+        grads = ensure_grads(self.net)
+        cfg = self.config()
+        rc = _lib.load().evac_adam_step(C.byref(self.params_struct()), C.byref(grads), C.byref(self._state), C.byref(cfg), self.obs_dim,
+                                        _ptr(grad_sumsq), _stream(self.device))
+        _lib.check(rc)
+
+    def zero_grad(self, set_to_none: bool = False) -> None:
+        """Nothing to do: the gradient kernels write ``.grad``, they do not accumulate (kept for torch's interface)."""
+
+    def read_header(self) -> dict:
+        return decode_header(self.header)
+
+    @property
+    def step_count(self) -> int:
+        return int(self.header[0].item())
+
+    def state_dict(self) -> dict:
+        """``torch.optim.Adam``'s format (``state[i]`` in ``mlp_tensors`` order), plus ``P1``, ``P2`` (the running products) and
+        ``max_grad_norm`` in the param group: torch's ``load_state_dict`` takes the dict once those three keys are dropped."""
+        h = self.read_header()
+        g = self.param_groups[0]
+        state = {i: {"step": torch.tensor(float(h["t"])), "exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()}
+                 for i, (m, v) in enumerate(zip(self.exp_avg, self.exp_avg_sq))}
+        group = {"lr": g["lr"], "betas": tuple(g["betas"]), "eps": g["eps"], "weight_decay": 0, "amsgrad": False,
+                 "max_grad_norm": g["max_grad_norm"], "P1": h["P1"], "P2": h["P2"], "params": list(range(len(self.params)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd: dict) -> None:
+        groups = sd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(self.params):
+            raise ValueError("DeviceAdam.load_state_dict: expected one param group of 13 tensors")
+        sg = groups[0]
+        if sg.get("weight_decay", 0) or sg.get("amsgrad", False):
+            raise ValueError("DeviceAdam.load_state_dict: weight decay and amsgrad are not supported")
+        g = dict(self.param_groups[0])
+        g.update({"lr": float(sg["lr"]), "betas": (float(sg["betas"][0]), float(sg["betas"][1])), "eps": float(sg["eps"])})
+        if "max_grad_norm" in sg:
+            g["max_grad_norm"] = float(sg["max_grad_norm"])
+        self._check_group(g)
+        state = sd["state"]
+        steps = {int(float(state[i]["step"])) for i in sg["params"]} if state else {0}
+        if len(steps) != 1:
+            raise ValueError("DeviceAdam.load_state_dict: the tensors' step counts differ")
+        t = steps.pop()
+        with torch.no_grad():
+            for k, i in enumerate(sg["params"]):
+                if state:
+                    self.exp_avg[k].copy_(state[i]["exp_avg"])
+                    self.exp_avg_sq[k].copy_(state[i]["exp_avg_sq"])
+                else:
+                    self.exp_avg[k].zero_()
+                    self.exp_avg_sq[k].zero_()
+        P1 = float(sg["P1"]) if "P1" in sg else g["betas"][0] ** t
+        P2 = float(sg["P2"]) if "P2" in sg else g["betas"][1] ** t
+        host = torch.zeros(8, dtype=torch.int64)
+        host[0] = t
+        host[1:3] = torch.tensor([P1, P2], dtype=torch.float64).view(torch.int64)
+        self.header.copy_(host)
+        self.param_groups[0] = g
+
+
+def _check_opt(opt, net) -> None:
+    if not isinstance(opt, DeviceAdam):
+        raise TypeError(f"expected a DeviceAdam, got {type(opt).__name__}")
+    if opt.net is not net:
+        raise ValueError("the DeviceAdam was made for another network")
+
+
+def rpo_minibatch_step(net, batch: Dict[str, torch.Tensor], mb_inds: torch.Tensor, cfg, opt: DeviceAdam, *,
+                       rpo_noise: Optional[torch.Tensor] = None, seed: int = 0, draw_counter: int = 0,
+                       stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``rpo_minibatch_grad`` with the same arguments, then ``opt.step(stats[7])``, in one host call
+    (``evac_rpo_minibatch_step``: one launch more than the gradient).  ``.grad`` is left clipped; ``stats`` are those of the
+    gradient at the parameters before the step.  No host synchronisation; capturable (``lr`` and ``draw_counter`` are frozen by
+    a capture, the step count is not)."""
+    _check_opt(opt, net)
+    B, D, dev, st, pol, grads = _batch_args(net, batch)
+    if mb_inds.dtype != torch.int64 or mb_inds.device != dev or not mb_inds.is_contiguous() or mb_inds.dim() != 1:
+        raise ValueError("mb_inds: expected a contiguous int64 device vector")
+    M = int(mb_inds.shape[0])
+    if rpo_noise is not None:
+        _f32(rpo_noise, (M, 2), "rpo_noise")
+    ws = _workspace(st, D, M, dev)
+    if stats is None:
+        stats = torch.empty(8, dtype=torch.float32, device=dev)
+    else:
+        _f32(stats, (8,), "stats")
+    lc, oc = _loss_config(cfg), opt.config()
+    rc = _lib.load().evac_rpo_minibatch_step(C.byref(pol), C.byref(lc), B, _ptr(batch["b_obs"]), _ptr(batch["b_actions"]),
+                                             _ptr(batch["b_logprobs"]), _ptr(batch["b_advantages"]), _ptr(batch["b_returns"]),
+                                             _ptr(batch["b_values"]), M, _ptr(mb_inds), _ptr(rpo_noise), _u64(seed),
+                                             _u64(draw_counter), C.byref(grads), _ptr(stats), _ptr(ws), _stream(dev),
+                                             C.byref(opt.params_struct()), C.byref(opt.state_struct()), C.byref(oc))
+    _lib.check(rc)
+    return stats
+
+
+def update_steps(batch_size: int, minibatch_size: int, norm_adv: bool) -> list:
+    """The sizes of the minibatches of one epoch, in order: ``range(0, B, M)`` with a tail of fewer than 2 samples (1 without
+    ``norm_adv``) left out, as the trainer's loop skips it."""
+    B, M, least = int(batch_size), int(minibatch_size), 2 if norm_adv else 1
+    return [min(M, B - s) for s in range(0, B, M) if min(M, B - s) >= least]
+
+
+def rpo_update(net, batch: Dict[str, torch.Tensor], perms: torch.Tensor, cfg, opt: DeviceAdam, *,
+               rpo_noise: Optional[torch.Tensor] = None, seed: int = 0, first_draw_counter: int = 0,
+               stats: Optional[torch.Tensor] = None, minibatch_size: Optional[int] = None):
+    """rpo_agent.py:233-283 in one host call (``evac_rpo_update``): for every row of ``perms`` (int64 [epochs, B], device) and
+    every ``start`` in ``range(0, B, M)`` one minibatch step on ``perms[epoch, start:start + M]``, ``M = minibatch_size``
+    (default ``cfg.minibatch_size``).  Step k of the call draws its perturbation at ``first_draw_counter + k`` or reads
+    ``rpo_noise[k]`` ([steps, M, 2]).  With ``cfg.target_kl`` set, the early exit is taken on the device.  Returns
+    (``stats`` [steps, 8], the optimiser's header: ``decode_header``); rows beyond ``steps_run`` keep what they held."""
+    _check_opt(opt, net)
+    B, D, dev, st, pol, grads = _batch_args(net, batch)
+    if not isinstance(perms, torch.Tensor) or perms.dtype != torch.int64 or perms.device != dev or not perms.is_contiguous() or \
+            perms.dim() != 2 or perms.shape[1] != B or perms.shape[0] < 1:
+        raise ValueError(f"perms: expected a contiguous int64 device tensor of shape [epochs, {B}]")
+    M = int(cfg.minibatch_size if minibatch_size is None else minibatch_size)
+    norm_adv = bool(getattr(cfg, "norm_adv", True))
+    if M < (2 if norm_adv else 1):
+        raise ValueError(f"rpo_update: minibatch_size = {M}")
+    M = min(M, B)
+    n_epochs = int(perms.shape[0])
+    steps = n_epochs * len(update_steps(B, M, norm_adv))
+    if rpo_noise is not None:
+        _f32(rpo_noise, (steps, M, 2), "rpo_noise")
+    ws = _workspace(st, D, M, dev)
+    if stats is None:
+        stats = torch.zeros(steps, 8, dtype=torch.float32, device=dev)
+    else:
+        _f32(stats, (steps, 8), "stats")
+    target_kl = getattr(cfg, "target_kl", None)
+    lc, oc = _loss_config(cfg), opt.config()
+    rc = _lib.load().evac_rpo_update(C.byref(pol), C.byref(opt.params_struct()), C.byref(grads), C.byref(lc), C.byref(oc),
+                                     C.byref(opt.state_struct()), B, _ptr(batch["b_obs"]), _ptr(batch["b_actions"]),
+                                     _ptr(batch["b_logprobs"]), _ptr(batch["b_advantages"]), _ptr(batch["b_returns"]),
+                                     _ptr(batch["b_values"]), M, n_epochs, _ptr(perms), _ptr(rpo_noise), _u64(seed),
+                                     _u64(first_draw_counter), int(target_kl is not None), float(target_kl or 0.0), _ptr(stats),
+                                     _ptr(ws), _stream(dev))
+    _lib.check(rc)
+    return stats, opt.header
 
 
 def _kernel_grad(trainer: "RPOTrainer", batch, mb_inds, rpo_noise, draw_counter: int, stats: torch.Tensor) -> torch.Tensor:
@@ -200,11 +432,22 @@ class RPOTrainer:
     The permutation of every epoch is drawn on the device from a generator seeded with ``cfg.seed`` (the reference shuffles on
     the host).  ``grad_fn(trainer, batch, mb_inds, rpo_noise, draw_counter, stats)`` computes the gradient of one minibatch into
     the parameters' ``.grad`` and returns the 8 statistics: the kernel by default.  ``rpo_noise_fn(M)`` -> [M, 2] injects the
-    RPO perturbation (default: drawn inside the kernel)."""
+    RPO perturbation (default: drawn inside the kernel).
+
+    ``optimizer="torch"`` (default): ``torch.optim.Adam`` and a ``foreach`` clip.  ``optimizer="device"``: ``DeviceAdam``.  The
+    permutations of all epochs are then drawn before the loop, so with ``target_kl`` the generator advances by
+    ``update_epochs`` draws per update whether or not the loop stops early.  With the default ``grad_fn`` and ``one_call=True``
+    the whole update is one ``rpo_update`` (the early exit on the device; an ``rpo_noise_fn`` is called once per step in step
+    order before the call and the results stacked, so both forms see the same perturbations -- for every epoch, stopped early
+    or not); ``one_call=False`` makes one ``rpo_minibatch_step`` per minibatch and reads ``approx_kl`` on the host after every
+    epoch; a custom ``grad_fn`` is followed by ``self.optimizer.step(stats[7])``."""
 
     def __init__(self, env, net, cfg: RPOTrainingConfig, *, grad_fn: Optional[Callable] = None,
-                 rpo_noise_fn: Optional[Callable[[int], torch.Tensor]] = None):
+                 rpo_noise_fn: Optional[Callable[[int], torch.Tensor]] = None, optimizer: str = "torch", one_call: bool = True):
         cfg.check()
+        if optimizer not in ("torch", "device"):
+            raise ValueError(f"RPOTrainer: optimizer = {optimizer!r}: expected \"torch\" or \"device\"")
+        self.optimizer_kind, self.one_call = optimizer, bool(one_call)
         if env.num_envs != cfg.num_envs:
             raise ValueError(f"RPOTrainer: the env has {env.num_envs} envs, cfg.num_envs = {cfg.num_envs}")
         self.env, self.net, self.cfg = env, net, cfg
@@ -213,7 +456,11 @@ class RPOTrainer:
         self.params = list(mlp_tensors(net))
         self.device = self.params[0].device
         ensure_grads(net)
-        self.optimizer = torch.optim.Adam(self.params, lr=cfg.learning_rate, eps=1e-5)
+        if optimizer == "device":
+            self.optimizer = DeviceAdam(net, lr=cfg.learning_rate, eps=1e-5, max_grad_norm=cfg.max_grad_norm)
+        else:
+            self.optimizer = torch.optim.Adam(self.params, lr=cfg.learning_rate, eps=1e-5)
+        self.stats_rows = None
         self.generator = torch.Generator(device=self.device)
         self.generator.manual_seed(int(cfg.seed))
         self.update_index = 0            # updates done
@@ -245,11 +492,15 @@ class RPOTrainer:
 
     def apply_gradient(self, stats: torch.Tensor):
         """``clip_grad_norm_`` (rpo_agent.py:279) from the sum of squares the gradient step left in ``stats[7]``, then Adam."""
+        if self.optimizer_kind == "device":
+            return self.optimizer.step(stats[7])
         coef = torch.clamp(self.cfg.max_grad_norm / (stats[7].sqrt() + 1e-6), max=1.0)
         torch._foreach_mul_([p.grad for p in self.params], coef)
         self.optimizer.step()
 
     def update(self) -> dict:
+        if self.optimizer_kind == "device":
+            return self._update_device()
         cfg = self.cfg
         if cfg.anneal_lr:                                                     # rpo_agent.py:174-177
             frac = 1.0 - self.update_index / max(1, cfg.num_updates)
@@ -287,6 +538,73 @@ class RPOTrainer:
         return {"update": self.update_index, "global_step": self.global_step, "learning_rate": self.optimizer.param_groups[0]["lr"],
                 "value_loss": host[2], "policy_loss": host[1], "entropy": host[3], "old_approx_kl": host[4], "approx_kl": host[5],
                 "clipfrac": host[8], "explained_variance": float("nan") if host[10] == 0 else host[9], "loss": host[0], "SPS": sps,
+                "episodes": {k: recs[:, i] for i, k in enumerate(STATS_FIELDS)}}
+
+    def _update_device(self) -> dict:
+        """``update()`` with the library's optimiser: one ``rpo_update`` per update, or one ``rpo_minibatch_step`` (or ``grad_fn``
+        and ``DeviceAdam.step``) per minibatch."""
+        cfg = self.cfg
+        if cfg.anneal_lr:                                                     # rpo_agent.py:174-177
+            frac = 1.0 - self.update_index / max(1, cfg.num_updates)
+            self.optimizer.param_groups[0]["lr"] = frac * cfg.learning_rate
+        storage = self.collect()
+        batch = flatten_batch(storage, self.advantages, self.returns)
+        B, M = cfg.batch_size, cfg.minibatch_size
+        perms = torch.stack([torch.randperm(B, device=self.device, generator=self.generator) for _ in range(cfg.update_epochs)])
+        self.last_permutations = list(perms)
+        sizes = update_steps(B, M, cfg.norm_adv)
+        y_pred, y_true = batch["b_values"], batch["b_returns"]
+        if self.grad_fn is _kernel_grad and self.one_call:
+            steps = cfg.update_epochs * len(sizes)
+            noise = None
+            if self.rpo_noise_fn is not None:
+                noise = torch.zeros(steps, M, 2, dtype=torch.float32, device=self.device)
+                for k in range(steps):
+                    m = sizes[k % len(sizes)]
+                    noise[k, :m] = self.rpo_noise_fn(m)
+            if self.stats_rows is None or self.stats_rows.shape[0] != steps:
+                self.stats_rows = torch.zeros(steps, 8, dtype=torch.float32, device=self.device)
+            rows, header = rpo_update(self.net, batch, perms, cfg, self.optimizer, rpo_noise=noise, seed=cfg.seed,
+                                      first_draw_counter=self.minibatch_steps, stats=self.stats_rows)
+            var_y = y_true.var(unbiased=False)
+            ev = 1 - (y_true - y_pred).var(unbiased=False) / var_y
+            host = torch.cat([header.view(torch.float32), rows.reshape(-1), ev.reshape(1), var_y.reshape(1)]).cpu()   # the one transfer
+            ran = decode_header(host[:16])["steps_run"]
+            rows_h = host[16:16 + 8 * steps].reshape(steps, 8)
+            self.minibatch_steps += ran
+            last = rows_h[ran - 1].tolist()
+            clipfrac, ev_h, var_h = float(rows_h[:ran, 6].mean()), float(host[-2]), float(host[-1])
+        else:
+            clipfracs = []
+            for e in range(cfg.update_epochs):
+                start = 0
+                for m in sizes:
+                    mb_inds = perms[e, start:start + m]
+                    start += M
+                    noise = self.rpo_noise_fn(m) if self.rpo_noise_fn is not None else None
+                    if self.grad_fn is _kernel_grad:
+                        stats = rpo_minibatch_step(self.net, batch, mb_inds, cfg, self.optimizer, rpo_noise=noise, seed=cfg.seed,
+                                                   draw_counter=self.minibatch_steps, stats=self.stats)
+                    else:
+                        stats = self.grad_fn(self, batch, mb_inds, noise, self.minibatch_steps, self.stats)
+                        self.optimizer.step(stats[7])
+                    self.minibatch_steps += 1
+                    clipfracs.append(stats[6].clone())
+                if cfg.target_kl is not None and float(stats[5]) > cfg.target_kl:   # rpo_agent.py:282-284 (the one host read)
+                    break
+            var_y = y_true.var(unbiased=False)
+            ev = 1 - (y_true - y_pred).var(unbiased=False) / var_y
+            host = torch.cat([stats, torch.stack(clipfracs).mean().reshape(1), ev.reshape(1), var_y.reshape(1)]).tolist()
+            last, clipfrac, ev_h, var_h = host[:8], host[8], host[9], host[10]
+        self.update_index += 1
+        es = storage["episode_stats"]
+        done = storage["dones"][1:].bool()                                    # (an episode that ended at step t shows in dones[t + 1])
+        ended = torch.cat([done, storage["next_done"].bool()[None]], dim=0)
+        recs = es[ended]
+        sps = int(self.global_step / max(time.time() - self.start_time, 1e-9))
+        return {"update": self.update_index, "global_step": self.global_step, "learning_rate": self.optimizer.param_groups[0]["lr"],
+                "value_loss": last[2], "policy_loss": last[1], "entropy": last[3], "old_approx_kl": last[4], "approx_kl": last[5],
+                "clipfrac": clipfrac, "explained_variance": float("nan") if var_h == 0 else ev_h, "loss": last[0], "SPS": sps,
                 "episodes": {k: recs[:, i] for i, k in enumerate(STATS_FIELDS)}}
 
     def learn(self, total_timesteps: Optional[int] = None, callback: Optional[Callable[[dict], None]] = None) -> list:

@@ -3,14 +3,17 @@
 
 Collection (``policy_rollout``: one launch), advantages (``evac_gae``: one launch), and per minibatch step the gradient of the
 RPO loss (``evac_rpo_minibatch_grad``: three launches) followed by torch's ``clip_grad_norm_`` arithmetic and ``Adam`` on
-``.grad``.  Prints the reference's ``SPS`` line per update.
+``.grad`` -- or, with ``--optimizer device``, by the library's own clip + Adam (one more launch), the whole update's epochs and
+minibatches in one host call (``evac_rpo_update``).  Prints the reference's ``SPS`` line per update.
 
-    python examples/train_rpo.py [--envs 4096] [--steps 128] [--updates 5] [--pedestrians 60]
+    python examples/train_rpo.py [--envs 4096] [--steps 128] [--updates 5] [--pedestrians 60] [--optimizer device]
 
 ``--compare`` measures, at the same sizes and with the reference's 32 minibatches x 10 epochs, one ``update()`` (a) with the
 kernels against (b) the same update with the loss written in torch (tests/trainer_ref.py, float32) and autograd, eager and with
-each minibatch step replayed from a ``torch.cuda.graph``, and the split collection / GAE / gradient / optimiser of each: hipEvent
-times after warm-up, the three forms alternated inside every repetition, median and spread of ``--reps`` repetitions.
+each minibatch step replayed from a ``torch.cuda.graph``, (c) the kernels with the device optimiser, one
+``rpo_minibatch_step`` per minibatch, and (d) the same with one ``rpo_update`` per update; and the split collection / GAE /
+gradient / optimiser of each (for the device forms the optimiser's line is the step call minus the gradient call): hipEvent
+times after warm-up, the forms alternated inside every repetition, median and spread of ``--reps`` repetitions.
 """
 import argparse
 import os
@@ -97,7 +100,8 @@ def compare(args):
 
     def noise_fn(M):
         return (torch.rand(M, 2, device=DEV, generator=gen) * 2 - 1) * 0.5
-    forms = {"kernels": make_trainer(args), "torch eager": make_trainer(args, grad_fn=eager_yardstick(R), rpo_noise_fn=noise_fn),
+    forms = {"kernels": make_trainer(args), "kernels + device optimiser, per-minibatch calls": make_trainer(args, optimizer="device", one_call=False),
+             "kernels, one call per update": make_trainer(args, optimizer="device", one_call=True), "torch eager": make_trainer(args, grad_fn=eager_yardstick(R), rpo_noise_fn=noise_fn),
              "torch graphed": make_trainer(args, grad_fn=GraphedYardstick(R), rpo_noise_fn=noise_fn)}
     for tr in forms.values():                                    # warm-up: every shape, the capture, the allocator
         tr.update()
@@ -118,7 +122,7 @@ def compare(args):
             cfg = tr.cfg
             with torch.no_grad():
                 split[name]["collection"].append(timed(lambda: tr.env.policy_rollout(tr.net, cfg.num_steps, tr.next_obs, tr.next_done, out=tr.storage), 5))
-            if name == "kernels":
+            if name.startswith("kernels"):
                 split[name]["gae"].append(timed(lambda: ea.trainer.gae(tr.storage, cfg.gamma, cfg.gae_lambda, out=(tr.advantages, tr.returns)), 20))
             else:
                 st = tr.storage
@@ -136,19 +140,31 @@ def compare(args):
                 tr.grad_fn(tr, batch, perm[i * M:(i + 1) * M], z if tr.rpo_noise_fn is not None else None, k[0], tr.stats)
             grad()
             split[name]["gradient"].append(timed(grad, 64 if name != "torch eager" else 16))
-            split[name]["optimiser"].append(timed(lambda: tr.apply_gradient(tr.stats), 64))
+            if tr.optimizer_kind == "device":                    # the Adam stage = step call - gradient call
+                def step():
+                    i = k[0] % cfg.num_minibatches
+                    k[0] += 1
+                    ea.trainer.rpo_minibatch_step(tr.net, batch, perm[i * M:(i + 1) * M], cfg, tr.optimizer, seed=cfg.seed, draw_counter=k[0],
+                                                  stats=tr.stats)
+                step()
+                split[name]["optimiser"].append(timed(step, 64) - split[name]["gradient"][-1])
+            else:
+                split[name]["optimiser"].append(timed(lambda: tr.apply_gradient(tr.stats), 64))
 
     def show(v):
         return f"{statistics.median(v):9.3f} ms  [{min(v):.3f} .. {max(v):.3f}]"
     print(f"N = {args.pedestrians}, gravity observation, {args.envs} envs x {args.steps} steps, {steps} minibatch steps of {M} samples per update; "
           f"median [min .. max] of {args.reps} repetitions")
     for name in forms:
-        print(f"{name:14s} update()            {show(whole[name])}   ({n_upd[name]} updates per window)")
+        print(f"{name}")
+        print(f"{'':14s} update()            {show(whole[name])}   ({n_upd[name]} updates per window)")
         for part, per in (("collection", 1), ("gae", 1), ("gradient", steps), ("optimiser", steps)):
             v = split[name][part]
             print(f"{'':14s}   {part:10s} per call {show(v)}   x {per:3d} = {statistics.median(v) * per:9.3f} ms per update")
     a, c = statistics.median(whole["kernels"]), statistics.median(whole["torch graphed"])
     print(f"update(): kernels / torch graphed = {a / c:.3f}, kernels / torch eager = {a / statistics.median(whole['torch eager']):.3f}")
+    for name in ("kernels + device optimiser, per-minibatch calls", "kernels, one call per update"):
+        print(f"update(): {name} / kernels = {statistics.median(whole[name]) / a:.3f}")
     for tr in forms.values():
         tr.env.close()
 
@@ -163,10 +179,11 @@ def main():
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--compare", action="store_true", help="time update() with the kernels against the torch yardstick + autograd")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--optimizer", choices=("torch", "device"), default="torch", help="torch.optim.Adam, or the library's clip + Adam")
     args = ap.parse_args()
     if args.compare:
         return compare(args)
-    tr = make_trainer(args)
+    tr = make_trainer(args, optimizer=args.optimizer)
 
     def line(log):
         r = log["episodes"]["episode_reward"]

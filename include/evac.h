@@ -460,6 +460,69 @@ int evac_rpo_minibatch_grad(const evac_mlp_policy_t* policy, const evac_rpo_loss
                             const float* rpo_noise_or_null, uint64_t seed, uint64_t draw_counter,
                             const evac_mlp_policy_grads_t* grads_out, float* stats_out, void* workspace, void* stream);
 
+/* ---- The optimiser step: rpo_agent.py:278-279, clip_grad_norm_(max_grad_norm) and Adam(lr, eps = 1e-5).step(), on the device ----
+ * Adam as torch.optim.Adam with betas, no weight decay, no amsgrad.  All in float32, EVERY OPERATION ROUNDED ON ITS OWN (no fused
+ * multiply-add, IEEE division, correctly rounded sqrt), except the three scalars marked double, formed in double and rounded
+ * once.  With s = the sum of squares of all gradient entries:
+ *   x  = f32(max_grad_norm) / (sqrt(s) + f32(1e-6));  c = x > 1 ? 1 : x        (a NaN stays a NaN, as torch.clamp keeps it)
+ *   t += 1;  P1 *= beta1;  P2 *= beta2                                         (int64 and two doubles; P1 = P2 = 1 at t = 0)
+ *   a  = f32(-(lr / (1 - P1)));  q = f32(sqrt(1 - P2))                         (double, rounded once)
+ *   w  = f32(1 - beta1);  b2 = f32(beta2);  u = f32(1 - beta2);  e = f32(eps)  ((1 - beta) formed in double)
+ *   per element:  g' = g * c;  m' = m + w * (g' - m);  v' = v * b2 + (u * g') * g';  p' = p + (a * m') / (sqrt(v') / q + e)
+ * The gradients are left holding g' (what clip_grad_norm_ leaves); m, v, p are updated in place.  This sequence in float64 is
+ * torch's Adam to 1e-15; in float32 it is as accurate as torch's float32 Adam but NOT bit-equal to it (torch's kernels fuse
+ * some of the products and differ between builds); the kernels are bit-equal to the sequence above.  P1, P2 are running
+ * products (beta ** t to a few 1e-16) so that the step count lives on the device: a captured step counts when it is replayed.
+ *
+ * The optimiser's state is caller-owned device memory; all zero = a fresh optimiser.  The header's last 28 bytes are the
+ * library's (an integer ticket of the running launch, zero between launches): keep them zero.  steps_run counts every step
+ * since evac_rpo_update last cleared it; stop and epochs_run are written by evac_rpo_update's launches alone. */
+typedef struct evac_adam_config { double lr, beta1, beta2, eps, max_grad_norm; } evac_adam_config_t;
+typedef struct evac_adam_state {
+    void* header;                         /* 64 bytes, 8-byte aligned: int64 t | double P1 | double P2 | int32 stop |
+                                             int32 steps_run | int32 epochs_run | pad  (P1, P2 read as 1 while t == 0) */
+    evac_mlp_policy_grads_t exp_avg, exp_avg_sq;     /* the 13 tensors' moments, the parameters' layouts */
+} evac_adam_state_t;
+/* evac_adam_step: the sequence above for gradients that are already in `grads` (a caller with its own backward pass).  `params`:
+ * the 13 parameter tensors, writable (the tensors evac_mlp_policy_t names); grad_sumsq: one float in DEVICE memory, read when
+ * the kernel runs.  ONE launch on `stream` (one element per thread; the last workgroup to finish, by an integer ticket, is the
+ * one writer of the header), no host synchronisation, capturable; cfg's values are frozen by a capture (the step count is not).
+ * EVAC_ERR_INVALID_ARGUMENT: a NULL pointer, obs_dim outside 1..396, a header that is not 8-byte aligned, lr not finite, a beta
+ * outside [0, 1), eps <= 0, max_grad_norm <= 0. */
+int evac_adam_step(const evac_mlp_policy_grads_t* params, const evac_mlp_policy_grads_t* grads, const evac_adam_state_t* state,
+                   const evac_adam_config_t* cfg, int32_t obs_dim, const float* grad_sumsq, void* stream);
+/* evac_rpo_minibatch_step: evac_rpo_minibatch_grad with the same arguments (same kernels, same bits in grads_out before the
+ * clip and in stats_out: its sum of squares is that of the UNCLIPPED gradient), then evac_adam_step on `params` (the tensors of
+ * `policy`, writable) from stats_out[7].  One launch more than evac_rpo_minibatch_grad, no host synchronisation, capturable:
+ * replaying the captured call n times equals n calls with the same arguments (by-value arguments -- lr, draw_counter, seed --
+ * are frozen by a capture, as for evac_rpo_minibatch_grad; mb_inds, rpo_noise and the step count are read on the device).
+ * EVAC_ERR_INVALID_ARGUMENT: as evac_rpo_minibatch_grad and evac_adam_step. */
+int evac_rpo_minibatch_step(const evac_mlp_policy_t* policy, const evac_rpo_loss_config_t* cfg, int64_t batch_size,
+                            const float* b_obs, const float* b_actions, const float* b_logprobs, const float* b_advantages,
+                            const float* b_returns, const float* b_values, int64_t n_minibatch, const int64_t* mb_inds,
+                            const float* rpo_noise_or_null, uint64_t seed, uint64_t draw_counter,
+                            const evac_mlp_policy_grads_t* grads_out, float* stats_out, void* workspace, void* stream,
+                            const evac_mlp_policy_grads_t* params, const evac_adam_state_t* state,
+                            const evac_adam_config_t* adam_cfg);
+/* evac_rpo_update: rpo_agent.py:233-283 in ONE host call: for every epoch, for start in range(0, B, M), a minibatch step on
+ * perms[epoch][start : start + M] (perms: int64 [n_epochs][B] in device memory).  Step k, counted over the whole call, draws its
+ * RPO perturbation at first_draw_counter + k (or reads rpo_noise[k], [steps][M][2], the tail's rows first) and writes
+ * stats_out[k] ([steps][8], steps = n_epochs * ceil(B / M) at most).  The tail minibatch of B mod M samples is run like the
+ * others and skipped when it has fewer than 2 samples (1 without norm_adv).  `grads`: where the gradients live (they hold the
+ * last step's clipped gradient afterwards).  target_kl WITHOUT THE HOST (use_target_kl != 0): the launch that finishes an
+ * epoch's last minibatch sets header.stop when that minibatch's approx_kl > target_kl (:281-283); every later kernel of the
+ * call returns at once when it sees the flag, touching nothing.  header.steps_run / epochs_run say what ran; rows of stats_out
+ * beyond steps_run are left as they were.  The call clears stop, steps_run, epochs_run on the stream before its first step.
+ * workspace: evac_rpo_workspace_bytes(obs_dim, M).  No host synchronisation; four launches per step.
+ * EVAC_ERR_INVALID_ARGUMENT: as evac_rpo_minibatch_step, and n_epochs < 1. */
+int evac_rpo_update(const evac_mlp_policy_t* policy, const evac_mlp_policy_grads_t* params, const evac_mlp_policy_grads_t* grads,
+                    const evac_rpo_loss_config_t* loss_cfg, const evac_adam_config_t* adam_cfg, const evac_adam_state_t* state,
+                    int64_t batch_size, const float* b_obs, const float* b_actions, const float* b_logprobs,
+                    const float* b_advantages, const float* b_returns, const float* b_values, int64_t n_minibatch,
+                    int32_t n_epochs, const int64_t* perms, const float* rpo_noise_or_null, uint64_t seed,
+                    uint64_t first_draw_counter, int32_t use_target_kl, double target_kl, float* stats_out, void* workspace,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
