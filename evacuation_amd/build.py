@@ -9,8 +9,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libevac.so")
-SOURCES = [os.path.join(CSRC, "evac_api.hip")]
-DEPENDS = SOURCES + [os.path.join(CSRC, f) for f in ("evac_common.h", "evac_families.h", "evac_device.h", "evac_subwave.h", "evac_team.h", "evac_gather.h", "evac_policy.h", "evac_train.h")] + [
+SOURCES = [os.path.join(CSRC, f) for f in ("evac_api.hip", "evac_train_api.hip")]      # the env | the trainer's update
+# what the library is built from: every source and header under csrc/, and the public header last
+DEPENDS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [
     os.path.join(os.path.dirname(HERE), "include", "evac.h")]
 ARCH = "gfx950"
 # -ffp-contract=off: fused multiply-adds are written explicitly in the kernels, so the f32 arithmetic

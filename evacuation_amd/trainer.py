@@ -114,14 +114,19 @@ def flatten_batch(storage: Dict[str, torch.Tensor], advantages: torch.Tensor, re
             "b_values": storage["values"].reshape(-1)}
 
 
+def _tensor_struct(cache: list, tensors) -> "_lib.EvacMlpPolicyGrads":
+    """The addresses of 13 tensors as ``evac_mlp_policy_grads_t``, rebuilt when one of them changes.  ``cache``: [key, struct]."""
+    key = tuple(t.data_ptr() for t in tensors)
+    if key != cache[0]:
+        cache[:] = key, _lib.EvacMlpPolicyGrads(*key)
+    return cache[1]
+
+
 class _GradState:
     """What ``rpo_minibatch_grad`` keeps per network: the binder, the ``.grad`` tensors' addresses and the workspace."""
 
     def __init__(self):
-        self.binder = None
-        self.grads_key = None
-        self.grads_struct = None
-        self.workspace = None
+        self.binder, self.grads, self.workspace = None, [None, None], None
 
 
 def _grad_state(net) -> _GradState:
@@ -135,20 +140,17 @@ def _grad_state(net) -> _GradState:
 def ensure_grads(net) -> "_lib.EvacMlpPolicyGrads":
     """Every parameter gets a contiguous float32 ``.grad`` on its device (allocated once, then reused: torch's optimisers update
     in place); their addresses as ``evac_mlp_policy_grads_t``."""
-    st = _grad_state(net)
     ts = mlp_tensors(net)
     for t in ts:
         g = t.grad
         if g is None or g.dtype != torch.float32 or g.device != t.device or not g.is_contiguous() or g.shape != t.shape:
             t.grad = torch.zeros_like(t, memory_format=torch.contiguous_format)
-    key = tuple(t.grad.data_ptr() for t in ts)
-    if key != st.grads_key:
-        st.grads_struct, st.grads_key = _lib.EvacMlpPolicyGrads(*key), key
-    return st.grads_struct
+    return _tensor_struct(_grad_state(net).grads, [t.grad for t in ts])
 
 
 def _batch_args(net, batch: Dict[str, torch.Tensor]):
-    """The checks every gradient entry makes of ``batch``; returns (B, D, device, state, evac_mlp_policy_t, grads struct)."""
+    """The checks every gradient entry makes of ``batch``; returns (B, D, device, state, evac_mlp_policy_t, grads struct, the
+    entries' arguments ``batch_size, b_obs .. b_values``)."""
     b_obs = batch["b_obs"]
     B, D = b_obs.shape
     dev = b_obs.device
@@ -161,16 +163,25 @@ def _batch_args(net, batch: Dict[str, torch.Tensor]):
         st.binder = PolicyBinder(D, dev)
     pol = st.binder(net)
     grads = ensure_grads(net)
-    return B, D, dev, st, pol, grads
+    return B, D, dev, st, pol, grads, [B] + [_ptr(batch[k]) for k in BATCH_KEYS]
 
 
-def _workspace(st: _GradState, D: int, M: int, dev) -> torch.Tensor:
+def _call_buffers(st: _GradState, D: int, M: int, dev, rpo_noise, stats, steps: Optional[int] = None):
+    """``rpo_noise`` and ``stats`` checked against the call's shape ([M, 2] and [8]; [steps, M, 2] and [steps, 8] for a whole
+    update), ``stats`` made if None, the workspace grown if too small; returns (stats, the workspace)."""
+    lead = () if steps is None else (steps,)
+    if rpo_noise is not None:
+        _f32(rpo_noise, lead + (M, 2), "rpo_noise")
     need = int(_lib.load().evac_rpo_workspace_bytes(D, M))
     if need < 0:
         raise _lib.EvacError(need, f"evac_rpo_workspace_bytes({D}, {M})")
     if st.workspace is None or st.workspace.numel() < need or st.workspace.device != dev:
         st.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    return st.workspace
+    if stats is None:
+        stats = (torch.empty if steps is None else torch.zeros)(lead + (8,), dtype=torch.float32, device=dev)
+    else:
+        _f32(stats, lead + (8,), "stats")
+    return stats, st.workspace
 
 
 def _loss_config(cfg) -> "_lib.EvacRpoLossConfig":
@@ -181,30 +192,32 @@ def _u64(x: int) -> int:
     return int(x) & (2 ** 64 - 1)
 
 
+def _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, opt: Optional["DeviceAdam"]) -> torch.Tensor:
+    """``evac_rpo_minibatch_grad``, or with ``opt`` ``evac_rpo_minibatch_step``: the same arguments and the optimiser's three."""
+    B, D, dev, st, pol, grads, b_args = _batch_args(net, batch)
+    if mb_inds.dtype != torch.int64 or mb_inds.device != dev or not mb_inds.is_contiguous() or mb_inds.dim() != 1:
+        raise ValueError("mb_inds: expected a contiguous int64 device vector")
+    M = int(mb_inds.shape[0])
+    stats, ws = _call_buffers(st, D, M, dev, rpo_noise, stats)
+    lc = _loss_config(cfg)
+    args = [C.byref(pol), C.byref(lc), *b_args, M, _ptr(mb_inds), _ptr(rpo_noise), _u64(seed), _u64(draw_counter), C.byref(grads),
+            _ptr(stats), _ptr(ws), _stream(dev)]
+    if opt is None:
+        rc = _lib.load().evac_rpo_minibatch_grad(*args)
+    else:
+        oc = opt.config()
+        rc = _lib.load().evac_rpo_minibatch_step(*args, C.byref(opt.params_struct()), C.byref(opt.state_struct()), C.byref(oc))
+    _lib.check(rc)
+    return stats
+
+
 def rpo_minibatch_grad(net, batch: Dict[str, torch.Tensor], mb_inds: torch.Tensor, cfg, *, rpo_noise: Optional[torch.Tensor] = None,
                        seed: int = 0, draw_counter: int = 0, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The gradient of the RPO loss of the minibatch ``mb_inds`` of ``batch`` (``flatten_batch``) into the parameters' ``.grad``
     (written, not accumulated), by ``evac_rpo_minibatch_grad``; returns the 8 statistics (``STAT_NAMES``) as a device tensor.
     ``cfg``: an ``RPOTrainingConfig`` (or anything with its loss fields).  ``rpo_noise`` [M, 2] injects the RPO perturbation;
     None draws it on the device from (``seed``, ``draw_counter``).  No host synchronisation; capturable into a graph."""
-    B, D, dev, st, pol, grads = _batch_args(net, batch)
-    if mb_inds.dtype != torch.int64 or mb_inds.device != dev or not mb_inds.is_contiguous() or mb_inds.dim() != 1:
-        raise ValueError("mb_inds: expected a contiguous int64 device vector")
-    M = int(mb_inds.shape[0])
-    if rpo_noise is not None:
-        _f32(rpo_noise, (M, 2), "rpo_noise")
-    ws = _workspace(st, D, M, dev)
-    if stats is None:
-        stats = torch.empty(8, dtype=torch.float32, device=dev)
-    else:
-        _f32(stats, (8,), "stats")
-    lc = _loss_config(cfg)
-    rc = _lib.load().evac_rpo_minibatch_grad(C.byref(pol), C.byref(lc), B, _ptr(batch["b_obs"]), _ptr(batch["b_actions"]),
-                                             _ptr(batch["b_logprobs"]), _ptr(batch["b_advantages"]), _ptr(batch["b_returns"]),
-                                             _ptr(batch["b_values"]), M, _ptr(mb_inds), _ptr(rpo_noise), _u64(seed),
-                                             _u64(draw_counter), C.byref(grads), _ptr(stats), _ptr(ws), _stream(dev))
-    _lib.check(rc)
-    return stats
+    return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, None)
 
 
 HEADER_FIELDS = ("t", "P1", "P2", "stop", "steps_run", "epochs_run")
@@ -242,7 +255,7 @@ class DeviceAdam:
         self.exp_avg_sq = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
         self._state = _lib.EvacAdamState(self.header.data_ptr(), _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in self.exp_avg)),
                                          _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in self.exp_avg_sq)))
-        self._params_key = self._params_struct = None
+        self._params = [None, None]
         ensure_grads(net)
 
     @staticmethod
@@ -262,10 +275,7 @@ class DeviceAdam:
         return _lib.EvacAdamConfig(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["max_grad_norm"]))
 
     def params_struct(self) -> "_lib.EvacMlpPolicyGrads":
-        key = tuple(p.data_ptr() for p in self.params)
-        if key != self._params_key:
-            self._params_struct, self._params_key = _lib.EvacMlpPolicyGrads(*key), key
-        return self._params_struct
+        return _tensor_struct(self._params, self.params)
 
     def state_struct(self) -> "_lib.EvacAdamState":
         return self._state
@@ -351,25 +361,7 @@ def rpo_minibatch_step(net, batch: Dict[str, torch.Tensor], mb_inds: torch.Tenso
     gradient at the parameters before the step.  No host synchronisation; capturable (``lr`` and ``draw_counter`` are frozen by
     a capture, the step count is not)."""
     _check_opt(opt, net)
-    B, D, dev, st, pol, grads = _batch_args(net, batch)
-    if mb_inds.dtype != torch.int64 or mb_inds.device != dev or not mb_inds.is_contiguous() or mb_inds.dim() != 1:
-        raise ValueError("mb_inds: expected a contiguous int64 device vector")
-    M = int(mb_inds.shape[0])
-    if rpo_noise is not None:
-        _f32(rpo_noise, (M, 2), "rpo_noise")
-    ws = _workspace(st, D, M, dev)
-    if stats is None:
-        stats = torch.empty(8, dtype=torch.float32, device=dev)
-    else:
-        _f32(stats, (8,), "stats")
-    lc, oc = _loss_config(cfg), opt.config()
-    rc = _lib.load().evac_rpo_minibatch_step(C.byref(pol), C.byref(lc), B, _ptr(batch["b_obs"]), _ptr(batch["b_actions"]),
-                                             _ptr(batch["b_logprobs"]), _ptr(batch["b_advantages"]), _ptr(batch["b_returns"]),
-                                             _ptr(batch["b_values"]), M, _ptr(mb_inds), _ptr(rpo_noise), _u64(seed),
-                                             _u64(draw_counter), C.byref(grads), _ptr(stats), _ptr(ws), _stream(dev),
-                                             C.byref(opt.params_struct()), C.byref(opt.state_struct()), C.byref(oc))
-    _lib.check(rc)
-    return stats
+    return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, opt)
 
 
 def update_steps(batch_size: int, minibatch_size: int, norm_adv: bool) -> list:
@@ -388,7 +380,7 @@ def rpo_update(net, batch: Dict[str, torch.Tensor], perms: torch.Tensor, cfg, op
     ``rpo_noise[k]`` ([steps, M, 2]).  With ``cfg.target_kl`` set, the early exit is taken on the device.  Returns
     (``stats`` [steps, 8], the optimiser's header: ``decode_header``); rows beyond ``steps_run`` keep what they held."""
     _check_opt(opt, net)
-    B, D, dev, st, pol, grads = _batch_args(net, batch)
+    B, D, dev, st, pol, grads, b_args = _batch_args(net, batch)
     if not isinstance(perms, torch.Tensor) or perms.dtype != torch.int64 or perms.device != dev or not perms.is_contiguous() or \
             perms.dim() != 2 or perms.shape[1] != B or perms.shape[0] < 1:
         raise ValueError(f"perms: expected a contiguous int64 device tensor of shape [epochs, {B}]")
@@ -399,19 +391,11 @@ def rpo_update(net, batch: Dict[str, torch.Tensor], perms: torch.Tensor, cfg, op
     M = min(M, B)
     n_epochs = int(perms.shape[0])
     steps = n_epochs * len(update_steps(B, M, norm_adv))
-    if rpo_noise is not None:
-        _f32(rpo_noise, (steps, M, 2), "rpo_noise")
-    ws = _workspace(st, D, M, dev)
-    if stats is None:
-        stats = torch.zeros(steps, 8, dtype=torch.float32, device=dev)
-    else:
-        _f32(stats, (steps, 8), "stats")
+    stats, ws = _call_buffers(st, D, M, dev, rpo_noise, stats, steps)
     target_kl = getattr(cfg, "target_kl", None)
     lc, oc = _loss_config(cfg), opt.config()
     rc = _lib.load().evac_rpo_update(C.byref(pol), C.byref(opt.params_struct()), C.byref(grads), C.byref(lc), C.byref(oc),
-                                     C.byref(opt.state_struct()), B, _ptr(batch["b_obs"]), _ptr(batch["b_actions"]),
-                                     _ptr(batch["b_logprobs"]), _ptr(batch["b_advantages"]), _ptr(batch["b_returns"]),
-                                     _ptr(batch["b_values"]), M, n_epochs, _ptr(perms), _ptr(rpo_noise), _u64(seed),
+                                     C.byref(opt.state_struct()), *b_args, M, n_epochs, _ptr(perms), _ptr(rpo_noise), _u64(seed),
                                      _u64(first_draw_counter), int(target_kl is not None), float(target_kl or 0.0), _ptr(stats),
                                      _ptr(ws), _stream(dev))
     _lib.check(rc)
@@ -498,105 +482,83 @@ class RPOTrainer:
         torch._foreach_mul_([p.grad for p in self.params], coef)
         self.optimizer.step()
 
+    def _randperm(self) -> torch.Tensor:
+        return torch.randperm(self.cfg.batch_size, device=self.device, generator=self.generator)
+
+    def _epochs_by_minibatch(self, batch, perms) -> list:
+        """One host call (or ``grad_fn`` and ``apply_gradient``) per minibatch, one read of ``approx_kl`` per epoch with
+        ``target_kl``; ``perms`` None: every epoch draws its permutation as it starts.  Returns what the log needs, on the device:
+        the last step's statistics and the mean ``clipfrac``."""
+        cfg = self.cfg
+        one_step = self.optimizer_kind == "device" and self.grad_fn is _kernel_grad
+        sizes = update_steps(cfg.batch_size, cfg.minibatch_size, cfg.norm_adv)
+        clipfracs = []
+        for e in range(cfg.update_epochs):
+            if perms is None:
+                perm = self._randperm()
+                self.last_permutations.append(perm)
+            else:
+                perm = perms[e]
+            start = 0
+            for m in sizes:
+                mb_inds = perm[start:start + m]
+                start += cfg.minibatch_size
+                noise = self.rpo_noise_fn(m) if self.rpo_noise_fn is not None else None
+                if one_step:
+                    stats = rpo_minibatch_step(self.net, batch, mb_inds, cfg, self.optimizer, rpo_noise=noise, seed=cfg.seed,
+                                               draw_counter=self.minibatch_steps, stats=self.stats)
+                else:
+                    stats = self.grad_fn(self, batch, mb_inds, noise, self.minibatch_steps, self.stats)
+                    self.apply_gradient(stats)
+                self.minibatch_steps += 1
+                clipfracs.append(stats[6].clone())
+            if cfg.target_kl is not None and float(stats[5]) > cfg.target_kl:   # rpo_agent.py:282-284 (the one host read)
+                break
+        return [stats, torch.stack(clipfracs).mean().reshape(1)]
+
+    def _epochs_one_call(self, batch, perms) -> list:
+        """The whole update as one ``rpo_update``.  Returns what the log needs, on the device: the optimiser's header (16 words)
+        and every step's statistics."""
+        cfg = self.cfg
+        sizes = update_steps(cfg.batch_size, cfg.minibatch_size, cfg.norm_adv)
+        steps = cfg.update_epochs * len(sizes)
+        noise = None
+        if self.rpo_noise_fn is not None:
+            noise = torch.zeros(steps, cfg.minibatch_size, 2, dtype=torch.float32, device=self.device)
+            for k in range(steps):
+                m = sizes[k % len(sizes)]
+                noise[k, :m] = self.rpo_noise_fn(m)
+        if self.stats_rows is None or self.stats_rows.shape[0] != steps:
+            self.stats_rows = torch.zeros(steps, 8, dtype=torch.float32, device=self.device)
+        rows, header = rpo_update(self.net, batch, perms, cfg, self.optimizer, rpo_noise=noise, seed=cfg.seed,
+                                  first_draw_counter=self.minibatch_steps, stats=self.stats_rows)
+        return [header.view(torch.float32), rows.reshape(-1)]
+
     def update(self) -> dict:
-        if self.optimizer_kind == "device":
-            return self._update_device()
         cfg = self.cfg
         if cfg.anneal_lr:                                                     # rpo_agent.py:174-177
             frac = 1.0 - self.update_index / max(1, cfg.num_updates)
             self.optimizer.param_groups[0]["lr"] = frac * cfg.learning_rate
         storage = self.collect()
         batch = flatten_batch(storage, self.advantages, self.returns)
-        B, M = cfg.batch_size, cfg.minibatch_size
-        clipfracs = []
-        self.last_permutations = []
-        for _ in range(cfg.update_epochs):
-            perm = torch.randperm(B, device=self.device, generator=self.generator)
-            self.last_permutations.append(perm)
-            for start in range(0, B, M):
-                mb_inds = perm[start:start + M]
-                if mb_inds.shape[0] < (2 if cfg.norm_adv else 1):
-                    continue
-                noise = self.rpo_noise_fn(int(mb_inds.shape[0])) if self.rpo_noise_fn is not None else None
-                stats = self.grad_fn(self, batch, mb_inds, noise, self.minibatch_steps, self.stats)
-                self.minibatch_steps += 1
-                self.apply_gradient(stats)
-                clipfracs.append(stats[6].clone())
-            if cfg.target_kl is not None and float(stats[5]) > cfg.target_kl:   # rpo_agent.py:282-284 (the one host read)
-                break
+        device = self.optimizer_kind == "device"
+        one_call = device and self.one_call and self.grad_fn is _kernel_grad
+        perms = torch.stack([self._randperm() for _ in range(cfg.update_epochs)]) if device else None
+        self.last_permutations = list(perms) if device else []
+        sent = self._epochs_one_call(batch, perms) if one_call else self._epochs_by_minibatch(batch, perms)
         self.update_index += 1
         # rpo_agent.py:286-299: the logged scalars (one transfer) and the finished episodes of this collection phase
         y_pred, y_true = batch["b_values"], batch["b_returns"]
         var_y = y_true.var(unbiased=False)
         ev = 1 - (y_true - y_pred).var(unbiased=False) / var_y
-        host = torch.cat([stats, torch.stack(clipfracs).mean().reshape(1), ev.reshape(1), var_y.reshape(1)]).tolist()
-        es = storage["episode_stats"]
-        done = storage["dones"][1:].bool()                                    # (an episode that ended at step t shows in dones[t + 1])
-        ended = torch.cat([done, storage["next_done"].bool()[None]], dim=0)
-        recs = es[ended]
-        sps = int(self.global_step / max(time.time() - self.start_time, 1e-9))
-        return {"update": self.update_index, "global_step": self.global_step, "learning_rate": self.optimizer.param_groups[0]["lr"],
-                "value_loss": host[2], "policy_loss": host[1], "entropy": host[3], "old_approx_kl": host[4], "approx_kl": host[5],
-                "clipfrac": host[8], "explained_variance": float("nan") if host[10] == 0 else host[9], "loss": host[0], "SPS": sps,
-                "episodes": {k: recs[:, i] for i, k in enumerate(STATS_FIELDS)}}
-
-    def _update_device(self) -> dict:
-        """``update()`` with the library's optimiser: one ``rpo_update`` per update, or one ``rpo_minibatch_step`` (or ``grad_fn``
-        and ``DeviceAdam.step``) per minibatch."""
-        cfg = self.cfg
-        if cfg.anneal_lr:                                                     # rpo_agent.py:174-177
-            frac = 1.0 - self.update_index / max(1, cfg.num_updates)
-            self.optimizer.param_groups[0]["lr"] = frac * cfg.learning_rate
-        storage = self.collect()
-        batch = flatten_batch(storage, self.advantages, self.returns)
-        B, M = cfg.batch_size, cfg.minibatch_size
-        perms = torch.stack([torch.randperm(B, device=self.device, generator=self.generator) for _ in range(cfg.update_epochs)])
-        self.last_permutations = list(perms)
-        sizes = update_steps(B, M, cfg.norm_adv)
-        y_pred, y_true = batch["b_values"], batch["b_returns"]
-        if self.grad_fn is _kernel_grad and self.one_call:
-            steps = cfg.update_epochs * len(sizes)
-            noise = None
-            if self.rpo_noise_fn is not None:
-                noise = torch.zeros(steps, M, 2, dtype=torch.float32, device=self.device)
-                for k in range(steps):
-                    m = sizes[k % len(sizes)]
-                    noise[k, :m] = self.rpo_noise_fn(m)
-            if self.stats_rows is None or self.stats_rows.shape[0] != steps:
-                self.stats_rows = torch.zeros(steps, 8, dtype=torch.float32, device=self.device)
-            rows, header = rpo_update(self.net, batch, perms, cfg, self.optimizer, rpo_noise=noise, seed=cfg.seed,
-                                      first_draw_counter=self.minibatch_steps, stats=self.stats_rows)
-            var_y = y_true.var(unbiased=False)
-            ev = 1 - (y_true - y_pred).var(unbiased=False) / var_y
-            host = torch.cat([header.view(torch.float32), rows.reshape(-1), ev.reshape(1), var_y.reshape(1)]).cpu()   # the one transfer
+        host = torch.cat(sent + [ev.reshape(1), var_y.reshape(1)]).cpu()
+        if one_call:
             ran = decode_header(host[:16])["steps_run"]
-            rows_h = host[16:16 + 8 * steps].reshape(steps, 8)
+            rows = host[16:-2].reshape(-1, 8)
             self.minibatch_steps += ran
-            last = rows_h[ran - 1].tolist()
-            clipfrac, ev_h, var_h = float(rows_h[:ran, 6].mean()), float(host[-2]), float(host[-1])
+            last, clipfrac = rows[ran - 1].tolist(), float(rows[:ran, 6].mean())
         else:
-            clipfracs = []
-            for e in range(cfg.update_epochs):
-                start = 0
-                for m in sizes:
-                    mb_inds = perms[e, start:start + m]
-                    start += M
-                    noise = self.rpo_noise_fn(m) if self.rpo_noise_fn is not None else None
-                    if self.grad_fn is _kernel_grad:
-                        stats = rpo_minibatch_step(self.net, batch, mb_inds, cfg, self.optimizer, rpo_noise=noise, seed=cfg.seed,
-                                                   draw_counter=self.minibatch_steps, stats=self.stats)
-                    else:
-                        stats = self.grad_fn(self, batch, mb_inds, noise, self.minibatch_steps, self.stats)
-                        self.optimizer.step(stats[7])
-                    self.minibatch_steps += 1
-                    clipfracs.append(stats[6].clone())
-                if cfg.target_kl is not None and float(stats[5]) > cfg.target_kl:   # rpo_agent.py:282-284 (the one host read)
-                    break
-            var_y = y_true.var(unbiased=False)
-            ev = 1 - (y_true - y_pred).var(unbiased=False) / var_y
-            host = torch.cat([stats, torch.stack(clipfracs).mean().reshape(1), ev.reshape(1), var_y.reshape(1)]).tolist()
-            last, clipfrac, ev_h, var_h = host[:8], host[8], host[9], host[10]
-        self.update_index += 1
+            last, clipfrac = host[:8].tolist(), float(host[8])
         es = storage["episode_stats"]
         done = storage["dones"][1:].bool()                                    # (an episode that ended at step t shows in dones[t + 1])
         ended = torch.cat([done, storage["next_done"].bool()[None]], dim=0)
@@ -604,8 +566,8 @@ class RPOTrainer:
         sps = int(self.global_step / max(time.time() - self.start_time, 1e-9))
         return {"update": self.update_index, "global_step": self.global_step, "learning_rate": self.optimizer.param_groups[0]["lr"],
                 "value_loss": last[2], "policy_loss": last[1], "entropy": last[3], "old_approx_kl": last[4], "approx_kl": last[5],
-                "clipfrac": clipfrac, "explained_variance": float("nan") if var_h == 0 else ev_h, "loss": last[0], "SPS": sps,
-                "episodes": {k: recs[:, i] for i, k in enumerate(STATS_FIELDS)}}
+                "clipfrac": clipfrac, "explained_variance": float("nan") if float(host[-1]) == 0 else float(host[-2]), "loss": last[0],
+                "SPS": sps, "episodes": {k: recs[:, i] for i, k in enumerate(STATS_FIELDS)}}
 
     def learn(self, total_timesteps: Optional[int] = None, callback: Optional[Callable[[dict], None]] = None) -> list:
         """``num_updates`` updates (``total_timesteps // batch_size``); returns the list of their logged scalars."""

@@ -17,6 +17,7 @@ import evacuation_amd as ea
 from evacuation_amd import _lib, build
 from evacuation_amd.config import obs_dim, to_c_config
 from tests import helpers as H
+from tests.kernel_meta import kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -175,23 +176,11 @@ def test_kernel_resource_budgets():
     """Compile the device code to gfx950 assembly and check the register budgets the design relies on:
     every step / rollout kernel fits 4 waves per SIMD (<= 128 VGPRs; C3 lost a quarter of its occupancy when one
     grew to 135), and the headline kernels (1 wave per env, sub-wave) neither spill VGPRs nor use scratch."""
-    import tempfile
-    src = os.path.join(ROOT, "evacuation_amd", "csrc", "evac_api.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "evac.s")
-        flags = [f for f in build.FLAGS if f not in ("-fPIC", "-shared")]       # the product's own flags
-        subprocess.run([build.hipcc_path()] + flags + ["-S", "--cuda-device-only", src, "-o", out], check=True, capture_output=True)
-        text = open(out).read()
-    meta = text[text.index("amdhsa.kernels:"):]
-    kernels = {}
-    for block in meta.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        kernels[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", block).group(1))
-                         for k in ("vgpr_count", "vgpr_spill_count", "sgpr_count", "private_segment_fixed_size")}
+    kernels = kernel_resources("evac_api.hip")
     assert len(kernels) >= 40
-    names = subprocess.run(["c++filt"], input="\n".join(kernels), capture_output=True, text=True).stdout.splitlines()
-    for mangled, name in zip(kernels, names):
-        k = kernels[mangled]
+    names = list(kernels)
+    assert not any(t in n for n in names for t in ("k_gae", "k_adam", "k_rpo"))      # the trainer's kernels are evac_train_api.hip's
+    for name, k in kernels.items():
         if any(t in name for t in ("k_step", "k_rollout", "k_reset", "k_observe")):
             assert k["vgpr_count"] <= 128, (name, k)
         # the default faces of the production families: one wave per env (4- and 16-wave workgroups), sub-wave, cell list, teams

@@ -12,10 +12,9 @@ import pytest
 
 from tests import trainer_ref as R
 from tests.optimizer_ref import AdamRef
-from tests.test_gpu_trainer import _yardstick_grad_fn, build_case, loss_cfg, make_initial_net, make_net
+from tests.trainer_cases import DEV, _yardstick_grad_fn, build_case, loss_cfg, make_initial_net, make_net, make_trainer, same_bits
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 SCALES = (10.0, 1.0, 1e-3, 1e-5)
 
 
@@ -26,17 +25,6 @@ def ea():
         pytest.skip("needs an MI355X")
     import evacuation_amd
     return evacuation_amd
-
-
-def bits(t):
-    import torch
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t.view(torch.int64)
-
-
-def same_bits(a, b):
-    import torch
-    return torch.equal(bits(a), bits(b))
 
 
 def twin(net_seed, D, like):
@@ -455,20 +443,6 @@ def test_state_dict_round_trip_and_torch_accepts_it(ea):
 
 
 # ------------------------------------------------------------------------------------------------ RPOTrainer(optimizer="device")
-def make_trainer(ea, n_ped, E, T, seed=1, net_seed=0, **kw):
-    import torch
-    from evacuation_amd.policy import LinearActorCritic
-    from evacuation_amd.trainer import RPOTrainer, RPOTrainingConfig
-    hooks = {k: kw.pop(k) for k in ("grad_fn", "rpo_noise_fn", "optimizer", "one_call") if k in kw}
-    env_kw = {k: kw.pop(k) for k in ("max_timesteps",) if k in kw}
-    cfg = RPOTrainingConfig(seed=seed, num_envs=E, num_steps=T, **kw)
-    env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=n_ped, **env_kw), ea.EnvWrappersConfig(positions="grav"), num_envs=E,
-                                      gamma=cfg.gamma, seed=seed)
-    torch.manual_seed(net_seed)
-    net = LinearActorCritic(env.obs_dim).to(DEV)
-    return RPOTrainer(env, net, cfg, **hooks)
-
-
 def _two_updates(ea, **kw):
     import torch
     tr = make_trainer(ea, 10, 64, 64, total_timesteps=64 * 64 * 2, num_minibatches=4, update_epochs=3, optimizer="device", **kw)

@@ -5,14 +5,13 @@ own float32 Adam; the new kernels use no scratch and spill nothing."""
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
 from evacuation_amd import _lib, build
+from tests.kernel_meta import kernel_resources
 from tests.optimizer_ref import AdamRef
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -229,20 +228,10 @@ def test_the_yardstick_keeps_a_nan_and_counts_without_the_host():
 def test_new_kernels_use_no_scratch_and_spill_nothing():
     """From the compiled device code, as test_kernel_resource_budgets reads it: k_adam and the stop-aware instantiations of the
     gradient kernels."""
-    src = os.path.join(ROOT, "evacuation_amd", "csrc", "evac_api.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "evac.s")
-        flags = [f for f in build.FLAGS if f not in ("-fPIC", "-shared")]
-        subprocess.run([build.hipcc_path()] + flags + ["-S", "--cuda-device-only", src, "-o", out], check=True, capture_output=True)
-        text = open(out).read()
-    meta = text[text.index("amdhsa.kernels:"):]
-    kernels = {}
-    for block in meta.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        kernels[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", block).group(1))
-                         for k in ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size")}
-    names = subprocess.run(["c++filt"], input="\n".join(kernels), capture_output=True, text=True).stdout.splitlines()
-    by_name = dict(zip(names, kernels.values()))
+    by_name = {n: {f: k[f] for f in ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size")}
+               for n, k in kernel_resources("evac_train_api.hip").items()}
+    stems = ["k_gae", "k_adam"] + [s + t for s in ("k_rpo_adv_stats", "k_rpo_grad", "k_rpo_finish") for t in ("<>", "<evac::AdamHeader const*>")]
+    assert len(by_name) == 8 and all(sum(s in n for n in by_name) == 1 for s in stems), list(by_name)      # these eight and no other
     adam = [k for n, k in by_name.items() if "k_adam" in n]
     assert len(adam) == 1
     assert adam[0]["private_segment_fixed_size"] == 0 and adam[0]["vgpr_spill_count"] == 0 and adam[0]["sgpr_spill_count"] == 0, adam

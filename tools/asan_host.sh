@@ -8,7 +8,7 @@ OUT=${TMPDIR:-/tmp}/evac_asan
 mkdir -p "$OUT"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 $HIPCC -O1 -g --offload-arch=gfx950 -ffp-contract=off -std=c++17 -fPIC -shared -fsanitize=address,undefined -fno-gpu-sanitize \
-  -fno-sanitize-recover=undefined "$ROOT/evacuation_amd/csrc/evac_api.hip" -o "$OUT/libevac_asan.so"
+  -fno-sanitize-recover=undefined "$ROOT/evacuation_amd/csrc/evac_api.hip" "$ROOT/evacuation_amd/csrc/evac_train_api.hip" -o "$OUT/libevac_asan.so"
 RT=$(dirname "$($HIPCC --print-file-name=libclang_rt.asan-x86_64.so 2>/dev/null || echo /opt/rocm/lib/llvm/lib/clang/22/lib/linux/libclang_rt.asan-x86_64.so)")
 [ -f "$RT/libclang_rt.asan-x86_64.so" ] || RT=$(dirname "$(find /opt/rocm/lib/llvm/lib/clang -name 'libclang_rt.asan-x86_64.so' | head -1)")
 /opt/rocm/lib/llvm/bin/clang -O1 -g -fsanitize=address,undefined -shared-libsan -I"$ROOT/include" "$ROOT/tools/asan/host_driver.c" \
