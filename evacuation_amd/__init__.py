@@ -4,14 +4,16 @@ Public surface = the reference's ``src.env`` exports (src/env/__init__.py:3-21):
 ``setup_env, EvacuationEnv, EnvConfig, EnvWrappersConfig, Status`` plus the batched form
 ``BatchedEvacuationEnv``, its SyncVectorEnv-shaped host face ``HostVectorEnv``, the sharded form ``ShardedEvacuationEnv`` (across GPUs) and ``SplitBatchEnv`` (across streams of one GPU), and the reference trainer's update on
 the device (``RPOTrainer``, ``RPOTrainingConfig``, ``gae``, ``rpo_minibatch_grad``, and the optimiser
-step ``DeviceAdam``, ``rpo_minibatch_step``, ``rpo_update``: ``evacuation_amd.trainer``).  Importing the package does
+step ``DeviceAdam``, ``rpo_minibatch_step``, ``rpo_update``: ``evacuation_amd.trainer``), and the evaluation of a fixed agent
+over whole episodes (``PolicyEvaluator``, ``EvaluationResult``, the scripted baseline ``WacuumCleaner``).  Importing the package does
 not touch the GPU; constructing an env loads libevac.so and fails loudly without it."""
 from .config import EnvConfig, EnvWrappersConfig
 from .statuses import Status
 
 __all__ = ["EnvConfig", "EnvWrappersConfig", "Status", "setup_env", "EvacuationEnv", "BatchedEvacuationEnv",
            "ShardedEvacuationEnv", "SplitBatchEnv", "NormalizedVectorEnv", "HostVectorEnv", "RandomAgent", "KernelOptions", "kernel_options",
-           "RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad", "DeviceAdam", "rpo_minibatch_step", "rpo_update"]
+           "RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad", "DeviceAdam", "rpo_minibatch_step", "rpo_update",
+           "WacuumCleaner", "PolicyEvaluator", "EvaluationResult"]
 
 
 def __getattr__(name):   # lazy: keeps `import evacuation_amd` light and torch-free for config users
@@ -36,9 +38,12 @@ def __getattr__(name):   # lazy: keeps `import evacuation_amd` light and torch-f
     if name in ("KernelOptions", "kernel_options"):
         from . import options as _options
         return getattr(_options, name)
-    if name == "RandomAgent":
-        from .agents import RandomAgent
-        return RandomAgent
+    if name in ("RandomAgent", "WacuumCleaner"):
+        from . import agents as _agents
+        return getattr(_agents, name)
+    if name in ("PolicyEvaluator", "EvaluationResult"):      # whole-episode evaluation of a fixed agent on the device
+        from . import evaluation as _evaluation
+        return getattr(_evaluation, name)
     if name in ("RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad", "DeviceAdam", "rpo_minibatch_step", "rpo_update"):   # the trainer's update on the device
         from . import trainer as _trainer
         return getattr(_trainer, name)

@@ -17,6 +17,7 @@ TYPE = {"Dict": 0, "Box": 1}
 MAX_PEDESTRIANS = 1024
 VERSION = 150
 EPISODE_STATS_WORDS = 10       # evac_episode_stats_t: 8 floats + 2 int32
+AGENT_POLICY_MEAN, AGENT_POLICY_SAMPLE, AGENT_VACUUM_CLEANER = 0, 1, 2   # evac_policy_evaluate's agents
 
 
 class EvacConfig(C.Structure):
@@ -113,6 +114,7 @@ SIGNATURES = {
     "evac_norm_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "evac_policy_rollout": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                       C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    "evac_policy_evaluate": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P]),
     "evac_gae": (C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
     "evac_rpo_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
     "evac_rpo_minibatch_grad": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacRpoLossConfig), C.c_int64, _P, _P, _P, _P, _P, _P,

@@ -18,6 +18,7 @@
 #include "evac_team.h"
 #include "evac_gather.h"
 #include "evac_policy.h"
+#include "evac_evaluate.h"
 #include "evac_host.h"
 
 namespace {
@@ -1481,6 +1482,74 @@ int evac_policy_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_
     hipLaunchKernelGGL(fn, dim3((unsigned)((h->p.n_envs + per_block - 1) / per_block)), dim3(evac::PolicyFamily::kBlock), 0,
                        (hipStream_t)stream, h->p, (int)n_steps, a, na);
     return check_launch(h, "evac_policy_rollout");
+}
+
+// The double a caller wrote for a setting that evac_config_t holds as float32: the shortest decimal that rounds to the float
+// (1.3f -> 1.3, as Python prints a float32).  The reference's scripted agent forms its thresholds from the Python floats of its
+// config; from the widened float32 values they can come out one float32 apart (0.7 x 1.3, step 0.03: 1.2299999 for 1.23).
+static double as_written(float v) {
+    char buf[40];
+    for (int digits = 1; digits <= 9; ++digits) {
+        snprintf(buf, sizeof buf, "%.*g", digits, (double)v);
+        if (strtof(buf, nullptr) == v) return strtod(buf, nullptr);
+    }
+    return (double)v;
+}
+
+// ---- evac_policy_evaluate: whole episodes under a fixed agent, one record per finished episode (evac_evaluate.h) ----
+int evac_policy_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy, int32_t n_episodes, int32_t max_steps,
+                         int32_t* progress, evac_episode_stats_t* episodes_out, const double* norm_state, float obs_clip,
+                         float epsilon, void* stream) {
+    EVAC_REQUIRE_BOUND(h, "evac_policy_evaluate");
+    const bool scripted = agent == EVAC_AGENT_VACUUM_CLEANER;
+    if (agent != EVAC_AGENT_POLICY_MEAN && agent != EVAC_AGENT_POLICY_SAMPLE && !scripted)
+        return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: unknown agent " + std::to_string(agent));
+    if (!progress || !episodes_out) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: progress / episodes_out is NULL");
+    if (n_episodes < 1 || max_steps < 1) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: n_episodes and max_steps must be >= 1");
+    if (scripted && norm_state)
+        return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: the scripted agent reads no observation: norm_state must be NULL");
+    if ((uintptr_t)progress & 15u) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: progress must be 16-byte aligned");
+    evac::PolicyArgs a{};
+    if (!scripted) {
+        if (!policy) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: a policy agent needs a policy");
+        const evac_mlp_policy_t& P = *policy;
+        if (!mlp_all_set(P)) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: a tensor pointer of the policy is NULL");
+        if (P.hidden != evac::kHidden) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: hidden must be 64");
+        if (P.obs_dim != h->p.obs_dim)
+            return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: policy obs_dim " + std::to_string(P.obs_dim) +
+                                                          " != evac_obs_dim " + std::to_string(h->p.obs_dim));
+        a = evac::PolicyArgs{P.actor_w1, P.actor_b1, P.actor_w2, P.actor_b2, P.actor_w3, P.actor_b3, P.actor_logstd,
+                             P.critic_w1, P.critic_b1, P.critic_w2, P.critic_b2, P.critic_w3, P.critic_b3};
+    }
+    if (h->p.n_ped > evac::kWave)
+        return fail(h, EVAC_ERR_UNSUPPORTED, "evac_policy_evaluate: rooms of more than 64 pedestrians are not supported (one wave per env)");
+    // (parts / chained / persistent handles: joined first, then ONE kernel on `stream` over the whole batch)
+    if (const int st = settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
+    DeviceGuard g(h->device);
+    // the sweep's turning points: extent - SWITCH_DISTANCE_TO_LEADER / 2 + step_size in double, rounded once
+    // (baseline_wacuum_cleaner.py:18-28, constants.py:35), from the settings as the caller wrote them (as_written)
+    const double step = as_written(h->cfg.step_size);
+    const float thr_x = (float)(as_written(h->cfg.width) - 0.2 / 2 + step);
+    const float thr_y = (float)(as_written(h->cfg.height) - 0.2 / 2 + step);
+    const evac::EvalArgs ev{(int4*)progress, episodes_out, norm_state, (int)n_episodes, (int)max_steps,
+                            agent == EVAC_AGENT_POLICY_SAMPLE ? 1 : 0, obs_clip, epsilon, thr_x, thr_y};
+    const int per_block = evac::PolicyFamily::kEnvsPerBlock;
+    const dim3 grid((unsigned)((h->p.n_envs + per_block - 1) / per_block)), block(evac::PolicyFamily::kBlock);
+    const bool grav = h->p.obs_pos == EVAC_POS_GRAV, norm = norm_state != nullptr, def = h->default_cfg;
+    if (scripted) {
+        using evac::k_policy_evaluate_scripted;
+        hipLaunchKernelGGL(def ? k_policy_evaluate_scripted<true> : k_policy_evaluate_scripted<false>, grid, block, 0,
+                           (hipStream_t)stream, h->p, ev);
+    } else {
+        using evac::k_policy_evaluate;
+        void (*fn)(evac::Params, evac::PolicyArgs, evac::EvalArgs) =
+            grav ? (norm ? (def ? k_policy_evaluate<true, true, true> : k_policy_evaluate<true, true, false>)
+                         : (def ? k_policy_evaluate<true, false, true> : k_policy_evaluate<true, false, false>))
+                 : (norm ? (def ? k_policy_evaluate<false, true, true> : k_policy_evaluate<false, true, false>)
+                         : (def ? k_policy_evaluate<false, false, true> : k_policy_evaluate<false, false, false>));
+        hipLaunchKernelGGL(fn, grid, block, 0, (hipStream_t)stream, h->p, a, ev);
+    }
+    return check_launch(h, "evac_policy_evaluate");
 }
 
 }  // extern "C"

@@ -75,8 +75,9 @@ __device__ __forceinline__ void stage_observation(const Params& p, typename F::C
 }
 
 // actor_mean(x) and critic(x) of the observation in the wave's LDS row (every lane computes unit `k` = its lane; results
-// wave-uniform, b3 not added).  ACTOR = false: the critic alone (the bootstrap value).
-template <bool GRAV, bool ACTOR>
+// wave-uniform, b3 not added).  ACTOR = false: the critic alone (the bootstrap value).  CRITIC = false: the actor alone (the
+// policy evaluation, which has no use for values; v comes back 0).
+template <bool GRAV, bool ACTOR, bool CRITIC = true>
 __device__ __forceinline__ void policy_eval(const PolicyArgs& a, PolicySmem<GRAV>& ps, int slot, int k, int D, float& m0, float& m1,
                                             float& v) {
     const float* xs = ps.x[slot];
@@ -85,26 +86,32 @@ __device__ __forceinline__ void policy_eval(const PolicyArgs& a, PolicySmem<GRAV
     if constexpr (GRAV) {
         const f4 x03 = *(const f4*)xs;
         const f2 x45 = *(const f2*)(xs + 4);
-        const f4 wc0 = ps.w1[1][0][k], wc1 = ps.w1[1][1][k];
+        f4 wc0{}, wc1{};
+        if constexpr (CRITIC) {
+            wc0 = ps.w1[1][0][k];
+            wc1 = ps.w1[1][1][k];
+        }
         if constexpr (ACTOR) {
             const f4 wa0 = ps.w1[0][0][k], wa1 = ps.w1[0][1][k];
             ha = fmaf(wa0.x, x03.x, ha); ha = fmaf(wa0.y, x03.y, ha); ha = fmaf(wa0.z, x03.z, ha); ha = fmaf(wa0.w, x03.w, ha);
             ha = fmaf(wa1.x, x45.x, ha); ha = fmaf(wa1.y, x45.y, ha);
         }
-        hc = fmaf(wc0.x, x03.x, hc); hc = fmaf(wc0.y, x03.y, hc); hc = fmaf(wc0.z, x03.z, hc); hc = fmaf(wc0.w, x03.w, hc);
-        hc = fmaf(wc1.x, x45.x, hc); hc = fmaf(wc1.y, x45.y, hc);
+        if constexpr (CRITIC) {
+            hc = fmaf(wc0.x, x03.x, hc); hc = fmaf(wc0.y, x03.y, hc); hc = fmaf(wc0.z, x03.z, hc); hc = fmaf(wc0.w, x03.w, hc);
+            hc = fmaf(wc1.x, x45.x, hc); hc = fmaf(wc1.y, x45.y, hc);
+        }
     } else {
         const float* __restrict__ ra = a.aw1 + (size_t)k * D;
         const float* __restrict__ rc = a.cw1 + (size_t)k * D;
         for (int j = 0; j < D; ++j) {
             const float xj = xs[j];
             if constexpr (ACTOR) ha = fmaf(ra[j], xj, ha);
-            hc = fmaf(rc[j], xj, hc);
+            if constexpr (CRITIC) hc = fmaf(rc[j], xj, hc);
         }
     }
     float* hrow = ps.h[slot][0];
     if constexpr (ACTOR) hrow[k] = tanhf(ha);
-    hrow[kHidden + k] = tanhf(hc);
+    if constexpr (CRITIC) hrow[kHidden + k] = tanhf(hc);
     PolicyFamily::sync();
     float ga = u0.z, gc = u0.w;
 #pragma unroll 1
@@ -113,12 +120,14 @@ __device__ __forceinline__ void policy_eval(const PolicyArgs& a, PolicySmem<GRAV
             const f4 w = ps.w2[0][g][k], hv = *(const f4*)(hrow + 4 * g);
             ga = fmaf(w.x, hv.x, ga); ga = fmaf(w.y, hv.y, ga); ga = fmaf(w.z, hv.z, ga); ga = fmaf(w.w, hv.w, ga);
         }
-        const f4 w = ps.w2[1][g][k], hv = *(const f4*)(hrow + kHidden + 4 * g);
-        gc = fmaf(w.x, hv.x, gc); gc = fmaf(w.y, hv.y, gc); gc = fmaf(w.z, hv.z, gc); gc = fmaf(w.w, hv.w, gc);
+        if constexpr (CRITIC) {
+            const f4 w = ps.w2[1][g][k], hv = *(const f4*)(hrow + kHidden + 4 * g);
+            gc = fmaf(w.x, hv.x, gc); gc = fmaf(w.y, hv.y, gc); gc = fmaf(w.z, hv.z, gc); gc = fmaf(w.w, hv.w, gc);
+        }
     }
     PolicyFamily::sync();       // (the next evaluation writes the activations again: in-order LDS, only the compiler is held)
     const f4 u1 = ps.unit[1][k];
-    float p0 = 0.0f, p1 = 0.0f, pv = u1.z * tanhf(gc);
+    float p0 = 0.0f, p1 = 0.0f, pv = CRITIC ? u1.z * tanhf(gc) : 0.0f;
     if constexpr (ACTOR) {
         const float t = tanhf(ga);
         p0 = u1.x * t;
@@ -141,17 +150,16 @@ __device__ __forceinline__ float2 policy_normal(const Params& p, uint32_t env_gi
     return make_float2(rad * c, rad * s);
 }
 
-template <bool GRAV, bool NORM>
-__device__ __forceinline__ void policy_rollout_body(PolicyFamily::Smem& sm, PolicySmem<GRAV>& ps, const Params& p, int n_steps,
-                                                    const PolicyArgs& ka, const NormArgs& kna) {
-    using F = PolicyFamily;
-    // the weights into LDS, by the whole workgroup (before any wave may leave)
-    for (int idx = (int)threadIdx.x; idx < 2 * (kHidden / 4) * kHidden; idx += F::kBlock) {
+// The weights, the launch's arguments and the policy's constants into LDS, by the whole workgroup (before any wave may leave);
+// the caller's __syncthreads() follows.  Shared by the policy rollout and the policy evaluation (evac_evaluate.h).
+template <bool GRAV>
+__device__ __forceinline__ void stage_policy(PolicySmem<GRAV>& ps, const PolicyArgs& ka, const NormArgs& kna) {
+    for (int idx = (int)threadIdx.x; idx < 2 * (kHidden / 4) * kHidden; idx += PolicyFamily::kBlock) {
         const int m = idx / ((kHidden / 4) * kHidden), g = (idx / kHidden) % (kHidden / 4), k = idx % kHidden;
         const float* src = (m == 0 ? ka.aw2 : ka.cw2) + k * kHidden + 4 * g;
         ps.w2[m][g][k] = f4{src[0], src[1], src[2], src[3]};
     }
-    for (int idx = (int)threadIdx.x; idx < 2 * kHidden; idx += F::kBlock) {
+    for (int idx = (int)threadIdx.x; idx < 2 * kHidden; idx += PolicyFamily::kBlock) {
         const int m = idx / kHidden, k = idx % kHidden;
         ps.unit[m][k] = m == 0 ? f4{ka.ab1[k], ka.cb1[k], ka.ab2[k], ka.cb2[k]} : f4{ka.aw3[k], ka.aw3[kHidden + k], ka.cw3[k], 0.0f};
         if constexpr (GRAV) {
@@ -168,6 +176,13 @@ __device__ __forceinline__ void policy_rollout_body(PolicyFamily::Smem& sm, Poli
         ps.c[1] = f4{sd0, sd1, sd0 * sd0, sd1 * sd1};
         ps.c[2] = f4{ls0, ls1, 0.0f, 0.0f};
     }
+}
+
+template <bool GRAV, bool NORM>
+__device__ __forceinline__ void policy_rollout_body(PolicyFamily::Smem& sm, PolicySmem<GRAV>& ps, const Params& p, int n_steps,
+                                                    const PolicyArgs& ka, const NormArgs& kna) {
+    using F = PolicyFamily;
+    stage_policy<GRAV>(ps, ka, kna);
     __syncthreads();
     typename F::Ctx w(sm);
     if (w.env >= p.n_envs) return;

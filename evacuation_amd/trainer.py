@@ -456,6 +456,7 @@ class RPOTrainer:
         self.stats = torch.zeros(8, dtype=torch.float32, device=self.device)
         self.next_obs = self.next_done = None
         self.last_permutations = []
+        self.evaluator = None            # evaluate(): built on first use
 
     def _start(self):
         obs, _ = self.env.reset(seed=self.cfg.seed)
@@ -569,12 +570,39 @@ class RPOTrainer:
                 "clipfrac": clipfrac, "explained_variance": float("nan") if float(host[-1]) == 0 else float(host[-2]), "loss": last[0],
                 "SPS": sps, "episodes": {k: recs[:, i] for i, k in enumerate(STATS_FIELDS)}}
 
-    def learn(self, total_timesteps: Optional[int] = None, callback: Optional[Callable[[dict], None]] = None) -> list:
-        """``num_updates`` updates (``total_timesteps // batch_size``); returns the list of their logged scalars."""
+    def make_evaluator(self, num_envs: Optional[int] = None):
+        """The ``PolicyEvaluator`` of ``evaluate``: the training env's configs, a handle and a batch of its own (``num_envs``:
+        the training batch's size by default).  Kept until a different ``num_envs`` is asked for."""
+        from .evaluation import PolicyEvaluator
+        base = getattr(self.env, "env", self.env)
+        n = base.num_envs if num_envs is None else int(num_envs)
+        if self.evaluator is None or self.evaluator.num_envs != n:
+            if self.evaluator is not None:
+                self.evaluator.close()
+            self.evaluator = PolicyEvaluator(base.env_config, base.wrap_config, num_envs=n, seed=base.seed_value, device=base.device)
+        return self.evaluator
+
+    def evaluate(self, n_episodes: int = 1, num_envs: Optional[int] = None, deterministic: bool = True):
+        """``n_episodes`` whole episodes per env of the current network on an evaluation batch of its own: the mean action
+        (``deterministic``), the training env's observation statistics frozen at a copy of what they are now (when the
+        training env normalises).  Nothing of the training env is touched.  Returns an ``EvaluationResult``."""
+        ev = self.make_evaluator(num_envs)
+        kw = {}
+        if hasattr(self.env, "norm_state"):
+            kw = {"norm_state": self.env.norm_state.clone(), "obs_clip": self.env.obs_clip, "epsilon": self.env.epsilon}
+        with torch.no_grad():
+            return ev.evaluate(self.net, n_episodes, deterministic=deterministic, **kw)
+
+    def learn(self, total_timesteps: Optional[int] = None, callback: Optional[Callable[[dict], None]] = None, *,
+              eval_every: Optional[int] = None, eval_episodes: int = 1) -> list:
+        """``num_updates`` updates (``total_timesteps // batch_size``); returns the list of their logged scalars.  Every
+        ``eval_every`` updates ``log["eval"]`` holds the ``summary()`` of ``evaluate(eval_episodes)``."""
         n = self.cfg.num_updates if total_timesteps is None else int(total_timesteps) // self.cfg.batch_size
         logs = []
         for _ in range(n):
             log = self.update()
+            if eval_every and self.update_index % int(eval_every) == 0:
+                log["eval"] = self.evaluate(eval_episodes).summary()
             logs.append(log)
             if callback is not None:
                 callback(log)

@@ -87,6 +87,24 @@ class StepInfos(dict):
             return default
 
 
+# evac_policy_evaluate's agents (include/evac.h)
+EVALUATE_AGENTS = {"vacuum_cleaner": _lib.AGENT_VACUUM_CLEANER}
+
+
+def check_evaluate_args(agent, n_episodes, max_steps, norm) -> None:
+    """The argument checks of ``policy_evaluate`` that need no device (``evac_policy_evaluate`` repeats them on the host side of
+    the C ABI): an unknown scripted agent, ``n_episodes`` / ``max_steps`` below 1, a normaliser given with a scripted agent."""
+    if isinstance(agent, str):
+        if agent not in EVALUATE_AGENTS:
+            raise ValueError(f"policy_evaluate: unknown scripted agent {agent!r} (known: {sorted(EVALUATE_AGENTS)})")
+        if norm is not None:
+            raise ValueError("policy_evaluate: a scripted agent reads no observation: no normaliser can be given")
+    elif agent is None:
+        raise ValueError("policy_evaluate: agent is None (a network or \"vacuum_cleaner\")")
+    if int(n_episodes) < 1 or int(max_steps) < 1:
+        raise ValueError(f"policy_evaluate: n_episodes and max_steps must be >= 1, got {n_episodes} and {max_steps}")
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -595,6 +613,47 @@ class BatchedEvacuationEnv:
             _ptr(state), gamma, obs_clip, reward_clip, eps, self._stream()), self._h)
         out["next_obs"], out["next_done"] = next_obs, next_done
         return out
+
+    def policy_evaluate(self, agent, n_episodes: int, max_steps: int, progress: Optional[torch.Tensor] = None,
+                        out: Optional[torch.Tensor] = None, *, deterministic: bool = True, _norm=None):
+        """Whole episodes per env under a FIXED agent, ONE kernel launch (``evac_policy_evaluate``): every env steps from its
+        current state until it has finished ``n_episodes`` episodes or taken ``max_steps`` steps in this call, and writes one
+        episode record per finished episode into ``out`` [n_episodes, E, 10] -- nothing else (no storage, no values).
+        ``agent``: a network with RPOLinearNetwork's attribute names -- its mean action (``deterministic=True``) or the policy
+        rollout's own sampled action (``False``: the same env, seed and network give ``policy_rollout``'s actions) -- or
+        ``"vacuum_cleaner"``, the reference's scripted sweep baseline (``agents.WacuumCleaner``, fresh for every episode).
+        ``progress`` int32 [E, 4] = (episodes finished, steps taken, two words of the scripted agent) is carried in and out:
+        pass the returned tensors again to continue where the call stopped (bit-identical to one long call); an env with
+        ``progress[e, 0] >= n_episodes`` does nothing.  Returns ``(progress, out)``; both are made (zeroed) when not given.
+        ``_norm = (norm_state, obs_clip, epsilon)``: the trainer's observation statistics applied FROZEN (read only) -- see
+        ``NormalizedVectorEnv.policy_evaluate``.  No host synchronisation; capturable; the weights are read when the kernel runs."""
+        from .policy import MAX_PEDESTRIANS, PolicyBinder
+        check_evaluate_args(agent, n_episodes, max_steps, _norm)
+        if self.n_ped > MAX_PEDESTRIANS:
+            raise NotImplementedError(f"policy_evaluate runs one wave per env: rooms of at most {MAX_PEDESTRIANS} pedestrians "
+                                      f"(this env has {self.n_ped})")
+        K, T, E, D = int(n_episodes), int(max_steps), self.num_envs, self.obs_dim
+        if isinstance(agent, str):
+            code, pol = EVALUATE_AGENTS[agent], None
+        else:
+            binder = getattr(self, "_policy_binder", None)
+            if binder is None:
+                binder = self._policy_binder = PolicyBinder(D, self.device)
+            code, pol = (_lib.AGENT_POLICY_MEAN if deterministic else _lib.AGENT_POLICY_SAMPLE), C.byref(binder(agent))
+        if progress is None:
+            progress = torch.zeros((E, 4), dtype=torch.int32, device=self.device)
+        else:
+            self._check_tensor(progress, (E, 4), torch.int32, "progress")
+        if out is None:
+            out = torch.zeros((K, E, STATS_WORDS), dtype=torch.float32, device=self.device)
+        else:
+            self._check_tensor(out, (K, E, STATS_WORDS), torch.float32, "out")
+        state, obs_clip, eps = (None, 0.0, 0.0) if _norm is None else _norm
+        if state is not None:
+            self._check_tensor(state, (E, 3 * D + 4), torch.float64, "norm_state")
+        _lib.check(self.lib.evac_policy_evaluate(self._h, code, pol, K, T, _ptr(progress), _ptr(out), _ptr(state), obs_clip, eps,
+                                                 self._stream()), self._h)
+        return progress, out
 
     def observe(self, out: Optional[torch.Tensor] = None):
         """Observation of the current state without stepping (env.py:98-104 through the wrappers)."""

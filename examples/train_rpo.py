@@ -7,6 +7,11 @@ RPO loss (``evac_rpo_minibatch_grad``: three launches) followed by torch's ``cli
 minibatches in one host call (``evac_rpo_update``).  Prints the reference's ``SPS`` line per update.
 
     python examples/train_rpo.py [--envs 4096] [--steps 128] [--updates 5] [--pedestrians 60] [--optimizer device]
+                                 [--eval-every 1] [--eval-episodes 1] [--baseline]
+
+``--eval-every K`` evaluates the leader every K updates (``RPOTrainer.evaluate``: whole episodes, the mean action, the observation
+statistics frozen) and prints the summary; ``--baseline`` prints the same line for the reference's scripted sweep baseline
+(baseline_wacuum_cleaner.py) on the same evaluator, i.e. on the same episodes.
 
 ``--compare`` measures, at the same sizes and with the reference's 32 minibatches x 10 epochs, one ``update()`` (a) with the
 kernels against (b) the same update with the loss written in torch (tests/trainer_ref.py, float32) and autograd, eager and with
@@ -180,10 +185,19 @@ def main():
     ap.add_argument("--compare", action="store_true", help="time update() with the kernels against the torch yardstick + autograd")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--optimizer", choices=("torch", "device"), default="torch", help="torch.optim.Adam, or the library's clip + Adam")
+    ap.add_argument("--eval-every", type=int, default=None, help="evaluate the leader every K updates (whole episodes, mean action, frozen normaliser)")
+    ap.add_argument("--eval-episodes", type=int, default=1, help="episodes per env of an evaluation")
+    ap.add_argument("--baseline", action="store_true", help="print the scripted sweep baseline's summary on the same evaluator")
     args = ap.parse_args()
     if args.compare:
         return compare(args)
     tr = make_trainer(args, optimizer=args.optimizer)
+
+    def eval_line(name, s):
+        print(f"eval {name:14s} episodic_return={s['episode_reward_mean']:9.2f} +- {s['episode_reward_std']:.2f}  length={s['episode_length_mean']:7.1f}  "
+              f"escaped={s['escaped_fraction_mean']:.3f}  all_escaped={s['all_escaped_share']:.3f}  over {s['episodes']} episodes")
+    if args.baseline:
+        eval_line("vacuum_cleaner", tr.make_evaluator().evaluate("vacuum_cleaner", args.eval_episodes).summary())
 
     def line(log):
         r = log["episodes"]["episode_reward"]
@@ -191,7 +205,9 @@ def main():
         print(f"update {log['update']:3d}  global_step={log['global_step']:9d}  value_loss={log['value_loss']:.4f}  policy_loss={log['policy_loss']:+.5f}  "
               f"approx_kl={log['approx_kl']:.5f}  clipfrac={log['clipfrac']:.3f}  explained_variance={log['explained_variance']:+.3f}  episodic_return={ret}")
         print("SPS:", log["SPS"])
-    tr.learn(callback=line)
+        if "eval" in log:
+            eval_line("policy (mean)", log["eval"])
+    tr.learn(callback=line, eval_every=args.eval_every, eval_episodes=args.eval_episodes)
     tr.env.close()
 
 

@@ -407,6 +407,52 @@ int evac_policy_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_
                         double* norm_state_or_null, float gamma, float obs_clip, float reward_clip, float epsilon,
                         void* stream);
 
+/* ---- Policy evaluation: whole episodes per env under a FIXED agent, one episode record per finished episode ----
+ * What a user of the reference writes around a trained network or a scripted agent and EvacuationEnv.step / reset
+ * (env.py:106-171): `obs = env.reset(); while not done: obs, r, term, trunc, _ = env.step(agent.act(obs))`, per env, with the
+ * episode dict of env.py:115-125 kept at every episode end.  ONE kernel (evac_evaluate.h), geometry and step body of
+ * evac_policy_rollout.  Per env e, with progress[e] = {episodes finished, steps taken so far, two words of the scripted agent's
+ * state} carried in and out (zero it to begin):
+ *   if progress[e][0] >= n_episodes at entry: nothing is read or written for this env;
+ *   x = the observation of the current state (as evac_observe), computed in the kernel;
+ *   at most max_steps times:
+ *     the action a, by `agent`:
+ *       EVAC_AGENT_POLICY_MEAN    a = actor_mean(x) (rpo_linear_agent_network.py:49-50: the mean of get_action_and_value); no
+ *                                 noise is drawn
+ *       EVAC_AGENT_POLICY_SAMPLE  a = mu + sigma z, z exactly evac_policy_rollout's draw (counter (env id, 0, total steps of the
+ *                                 env, 'POLI')): same env, seed and network give the same actions as evac_policy_rollout
+ *       EVAC_AGENT_VACUUM_CLEANER WacuumCleaner.act (baseline_wacuum_cleaner.py:36-82) on the leader's position: climb until
+ *                                 y >= T_y, sweep right / left between +-T_x with, at every turn, one step down and then up to 25
+ *                                 more as long as y > -T_y, and once a step of those finds y <= -T_y head for the exit with
+ *                                 a = exit - position.  T = extent - SWITCH_DISTANCE_TO_LEADER / 2 + step_size (:18-28) in double,
+ *                                 rounded to float32 once (NumPy 2 compares the float32 position with a Python float in float32);
+ *                                 extent and step_size are taken as the shortest decimals that round to the float32 values of
+ *                                 evac_config_t (1.3f -> 1.3: the Python floats of the caller's config).
+ *                                 It reads no observation.  The reference's object is never reset and would head for the exit for
+ *                                 ever after its first episode; here an agent is FRESH FOR EVERY EPISODE (the two state words are
+ *                                 cleared at every autoreset)
+ *     the env steps with a exactly as evac_step would (ClipAction, the pedestrians' Philox noise, autoreset); progress[e][1] += 1;
+ *     when the episode ended: episodes_out[progress[e][0]][e] = its record (as final_stats of evac_step); progress[e][0] += 1;
+ *     the env is reset with its next Philox reset draw; the scripted agent starts afresh; stop if progress[e][0] == n_episodes;
+ *     x = the new observation.
+ *   The state is stored back: the next call continues where this one stopped -- max_steps = 17 repeated until every env is done
+ *   equals one long call bit for bit.
+ * norm_state_or_null (policy agents): the trainer's observation statistics, FROZEN: x = clip((x - mean_j) / sqrt(var_j + epsilon),
+ * +-obs_clip) with the env's own row of norm_state ([E][evac_norm_state_doubles(h)]), which is only read; nothing is counted,
+ * rewards and records stay raw.
+ *   progress int32 [E][4], 16-byte aligned; episodes_out [n_episodes][E] (slots beyond an env's count are left untouched).
+ * One wave per env: EVAC_ERR_UNSUPPORTED for rooms of more than 64 pedestrians.  EVAC_ERR_INVALID_ARGUMENT, decided on the host
+ * before anything is launched: an unknown agent, a NULL or misaligned progress, a NULL episodes_out, n_episodes < 1,
+ * max_steps < 1, a policy agent with a NULL policy, a NULL tensor, hidden != 64 or obs_dim != evac_obs_dim(h), norm_state given
+ * with the scripted agent.  Handles with parts = 2 or chain = 1 / 2 are joined first; the call is ONE kernel on `stream`, no host
+ * synchronisation, capturable; the weights are read when the kernel runs. */
+enum { EVAC_AGENT_POLICY_MEAN = 0, EVAC_AGENT_POLICY_SAMPLE = 1, EVAC_AGENT_VACUUM_CLEANER = 2 };
+int evac_policy_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy_or_null,
+                         int32_t n_episodes, int32_t max_steps,
+                         int32_t* progress,                   /* [E][4] in/out; zero it to begin */
+                         evac_episode_stats_t* episodes_out,  /* [n_episodes][E] */
+                         const double* norm_state_or_null, float obs_clip, float epsilon, void* stream);
+
 /* ---- The trainer's update: the other half of RPOAgent.learn() (rpo_agent.py:205-283) for the network above ----
  * No handle: buffers, sizes and a stream; arguments are validated on the host before anything touches a device, and errors
  * come back through the return code alone (evac_last_error keeps its meaning for handles).

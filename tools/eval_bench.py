@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""Measure the policy evaluation kernel (evac_policy_evaluate) against the policy rollout.
+
+    python tools/eval_bench.py [--envs 4096] [--steps 128] [--reps 9] [--shape grav|wide|both] [--evaluate-only]
+
+Per shape -- N = 60 with the gravity observation (D = 6), and with the rel + ohe Box observation (D = 372), both with the frozen
+normaliser -- the time per env-step of ``policy_evaluate(mean, max_steps = T)`` and of ``policy_rollout(T)`` from the same start
+state: hipEvent times after warm-up, the two forms alternated inside every repetition, median and range.  Then one
+``PolicyEvaluator.evaluate(n_episodes = 1)`` at the default ``max_timesteps`` (host wall time and launches) and one launch of
+4096 steps, which is what the ``max_steps_per_launch`` default rests on.  ``--evaluate-only`` runs just the evaluate() part
+(for a kernel trace: ``rocprofv3 --kernel-trace --stats -- python tools/eval_bench.py --evaluate-only``)."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import evacuation_amd as ea  # noqa: E402
+from evacuation_amd.policy import LinearActorCritic  # noqa: E402
+
+DEV = torch.device("cuda:0")
+SHAPES = {"grav": dict(positions="grav", alpha=3), "wide": dict(positions="rel", statuses="ohe", type="Box")}
+STATE = ("ped", "status", "agent", "clock", "acc")
+
+
+def event_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def show(v, scale=1.0, unit="ms"):
+    return f"{statistics.median(v) * scale:10.3f} {unit}  [{min(v) * scale:.3f} .. {max(v) * scale:.3f}]"
+
+
+def kernel_against_rollout(shape, args):
+    E, T = args.envs, args.steps
+    env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=60, is_new_exiting_reward=True), ea.EnvWrappersConfig(**SHAPES[shape]),
+                                      num_envs=E, seed=1)
+    b = env.env
+    torch.manual_seed(0)
+    net = LinearActorCritic(env.obs_dim).to(DEV)
+    obs, _ = env.reset()
+    next_obs, next_done = obs.clone(), torch.zeros(E, dtype=torch.float32, device=DEV)
+    with torch.no_grad():
+        storage = env.policy_rollout(net, T, next_obs, next_done)             # the statistics move; allocates the storage
+        storage = env.policy_rollout(net, T, next_obs, next_done, out=storage)
+        keep = {k: getattr(b, k).clone() for k in STATE}
+        keep_ns, keep_obs, keep_done = env.norm_state.clone(), next_obs.clone(), next_done.clone()
+        progress, out = env.policy_evaluate(net, T, T)
+
+        def rewind():
+            for k in STATE:
+                getattr(b, k).copy_(keep[k])
+            env.norm_state.copy_(keep_ns)
+            next_obs.copy_(keep_obs)
+            next_done.copy_(keep_done)
+            progress.zero_()
+
+        def rollout():
+            env.policy_rollout(net, T, next_obs, next_done, out=storage)
+
+        def evaluate():
+            env.policy_evaluate(net, T, T, progress, out)
+        for _ in range(2):                                                     # warm-up of both forms from the start state
+            rewind(); rollout(); rewind(); evaluate()
+        torch.cuda.synchronize()
+        t_ro, t_ev = [], []
+        for rep in range(args.reps):                                           # alternated inside every repetition
+            for form in (("ro", "ev") if rep % 2 == 0 else ("ev", "ro")):
+                rewind()
+                torch.cuda.synchronize()
+                (t_ro if form == "ro" else t_ev).append(event_ms(rollout if form == "ro" else evaluate))
+    per = 1e6 / (E * T)                                                        # ms per launch -> ns per env-step
+    print(f"[{shape}] N = 60, D = {env.obs_dim}, {E} envs x {T} steps, frozen normaliser; median [min .. max] of {args.reps} repetitions")
+    print(f"    policy_rollout({T})              {show(t_ro)}   {show(t_ro, per, 'ns / env-step')}")
+    print(f"    policy_evaluate(mean, {T})       {show(t_ev)}   {show(t_ev, per, 'ns / env-step')}")
+    ok = statistics.median(t_ev) <= max(t_ro)
+    print(f"    evaluation median / rollout median = {statistics.median(t_ev) / statistics.median(t_ro):.3f}; "
+          f"evaluation median {'within or below' if ok else 'ABOVE'} the rollout's range")
+    env.close()
+    return ok
+
+
+def whole_evaluation(args):
+    E = args.envs
+    cfg = ea.EnvConfig(number_of_pedestrians=60, is_new_exiting_reward=True, clip_action=True)
+    ev = ea.PolicyEvaluator(cfg, ea.EnvWrappersConfig(**SHAPES["grav"]), num_envs=E, seed=1)
+    torch.manual_seed(0)
+    net = LinearActorCritic(6).to(DEV)
+    ns = torch.zeros((E, 22), dtype=torch.float64, device=DEV)
+    ns[:, 6:12] = 1.0
+    with torch.no_grad():
+        for name, agent, kw in (("policy (mean), frozen normaliser", net, dict(norm_state=ns)), ("vacuum_cleaner", "vacuum_cleaner", {})):
+            ev.evaluate(agent, 1, **kw)                                        # warm-up
+            torch.cuda.synchronize()
+            wall = []
+            for _ in range(args.eval_reps):
+                t0 = time.perf_counter()
+                res = ev.evaluate(agent, 1, **kw)
+                torch.cuda.synchronize()
+                wall.append((time.perf_counter() - t0) * 1e3)
+            s = res.summary()
+            steps = int(res.steps.sum())
+            print(f"evaluate(n_episodes=1), {E} envs, max_timesteps = {cfg.max_timesteps}, {name}: {show(wall)} host wall time, "
+                  f"{ev.launches} launch(es), {steps} env-steps ({statistics.median(wall) * 1e6 / steps:.2f} ns / env-step), "
+                  f"episodic_return {s['episode_reward_mean']:.2f}, length {s['episode_length_mean']:.1f}, escaped {s['escaped_fraction_mean']:.3f}")
+        if not args.evaluate_only:
+            # one launch of max_steps_per_launch = 4096 steps that no env finishes early (n_episodes = 8 at max_timesteps = 2000)
+            progress, out = ev.env.policy_evaluate(net, 8, 4096, _norm=(ns, 1.0, 1e-8))
+            torch.cuda.synchronize()
+            t = []
+            for _ in range(args.eval_reps):
+                ev.restore()
+                progress.zero_()
+                torch.cuda.synchronize()
+                t.append(event_ms(lambda: ev.env.policy_evaluate(net, 8, 4096, progress, out, _norm=(ns, 1.0, 1e-8))))
+            assert int(progress[:, 1].min()) == 4096
+            print(f"one launch of 4096 steps, {E} envs (policy, frozen normaliser): {show(t)}   {show(t, 1e6 / (E * 4096), 'ns / env-step')}")
+    ev.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=128)
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--eval-reps", type=int, default=3)
+    ap.add_argument("--shape", choices=("grav", "wide", "both"), default="both")
+    ap.add_argument("--evaluate-only", action="store_true")
+    args = ap.parse_args()
+    ok = True
+    if not args.evaluate_only:
+        for shape in (("grav", "wide") if args.shape == "both" else (args.shape,)):
+            ok = kernel_against_rollout(shape, args) and ok
+    whole_evaluation(args)
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
