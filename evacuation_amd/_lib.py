@@ -16,6 +16,7 @@ STAT = {"no": 0, "ohe": 1, "cat": 2}
 TYPE = {"Dict": 0, "Box": 1}
 MAX_PEDESTRIANS = 1024
 VERSION = 150
+MAX_LEARNERS = 64              # EVAC_MAX_LEARNERS
 EPISODE_STATS_WORDS = 10       # evac_episode_stats_t: 8 floats + 2 int32
 AGENT_POLICY_MEAN, AGENT_POLICY_SAMPLE, AGENT_VACUUM_CLEANER = 0, 1, 2   # evac_policy_evaluate's agents
 
@@ -53,6 +54,11 @@ class EvacRpoLossConfig(C.Structure):
 class EvacMlpPolicyGrads(C.Structure):
     """evac_mlp_policy_grads_t: where evac_rpo_minibatch_grad writes the gradients of the 13 tensors"""
     _fields_ = [(f, C.c_void_p) for f, _ in EvacMlpPolicy._fields_[2:]]
+
+
+class EvacMlpPolicyStrides(C.Structure):
+    """evac_mlp_policy_strides_t: floats from learner s to learner s + 1, per tensor of evac_mlp_policy_t"""
+    _fields_ = [(f, C.c_int64) for f, _ in EvacMlpPolicy._fields_[2:]]
 
 
 class EvacAdamConfig(C.Structure):
@@ -114,6 +120,8 @@ SIGNATURES = {
     "evac_norm_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "evac_policy_rollout": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                       C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    "evac_policy_rollout_population": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyStrides), C.c_int32,
+                                                 _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "evac_policy_evaluate": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P]),
     "evac_gae": (C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
     "evac_rpo_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
@@ -128,6 +136,13 @@ SIGNATURES = {
                                   C.POINTER(EvacRpoLossConfig), C.POINTER(EvacAdamConfig), C.POINTER(EvacAdamState), C.c_int64,
                                   _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, C.c_uint64, C.c_uint64, C.c_int32,
                                   C.c_double, _P, _P, _P]),
+    "evac_rpo_population_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32]),
+    "evac_rpo_update_population": (C.c_int, [C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacMlpPolicyGrads),
+                                             C.POINTER(EvacMlpPolicyStrides), C.POINTER(EvacMlpPolicyStrides),
+                                             C.POINTER(EvacMlpPolicyStrides), C.c_int64, C.POINTER(EvacRpoLossConfig),
+                                             C.POINTER(EvacAdamConfig), C.POINTER(EvacAdamState), C.c_int64, _P, _P, _P, _P, _P, _P,
+                                             C.c_int64, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                             C.c_int32, C.c_double, _P, _P, _P]),
 }
 
 _lib = None

@@ -1445,24 +1445,44 @@ int evac_norm_step(evac_handle_t h, float* obs, float* final_obs, float* reward,
 }
 
 // ---- evac_policy_rollout: the trainer's collection loop with the actor-critic inside the launch (evac_policy.h) ----
-int evac_policy_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_t* policy, float* next_obs, float* next_done,
-                        float* obs_out, float* actions_out, float* logprob_out, float* value_out, float* reward_out, float* done_out,
-                        float* next_value_out, evac_episode_stats_t* final_stats, double* norm_state, float gamma, float obs_clip,
-                        float reward_clip, float epsilon, void* stream) {
-    EVAC_REQUIRE_BOUND(h, "evac_policy_rollout");
+// ... and evac_policy_rollout_population (n_learners >= 1, strides set): the same checks, the learners' workgroups in one launch.
+static int policy_rollout(evac_handle_t h, const char* what, int32_t n_learners, const evac_mlp_policy_strides_t* strides,
+                          int32_t n_steps, const evac_mlp_policy_t* policy, float* next_obs, float* next_done, float* obs_out,
+                          float* actions_out, float* logprob_out, float* value_out, float* reward_out, float* done_out,
+                          float* next_value_out, evac_episode_stats_t* final_stats, double* norm_state, float gamma, float obs_clip,
+                          float reward_clip, float epsilon, void* stream) {
+    const std::string w = what;
     if (h->p.n_ped > evac::kWave)
-        return fail(h, EVAC_ERR_UNSUPPORTED, "evac_policy_rollout: rooms of more than 64 pedestrians are not supported (one wave per env)");
-    if (n_steps < 1) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout: n_steps must be >= 1");
+        return fail(h, EVAC_ERR_UNSUPPORTED, w + ": rooms of more than 64 pedestrians are not supported (one wave per env)");
+    if (n_steps < 1) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": n_steps must be >= 1");
     if (!policy || !next_obs || !next_done || !obs_out || !actions_out || !logprob_out || !value_out || !reward_out || !done_out ||
         !next_value_out)
-        return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout: policy and every output buffer but final_stats / norm_state must be non-NULL");
+        return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": policy and every output buffer but final_stats / norm_state must be non-NULL");
     const evac_mlp_policy_t& P = *policy;
-    if (!mlp_all_set(P)) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout: a tensor pointer of the policy is NULL");
-    if (P.hidden != evac::kHidden) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout: hidden must be 64");
+    if (!mlp_all_set(P)) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": a tensor pointer of the policy is NULL");
+    if (P.hidden != evac::kHidden) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": hidden must be 64");
     if (P.obs_dim != h->p.obs_dim)
-        return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout: policy obs_dim " + std::to_string(P.obs_dim) + " != evac_obs_dim " +
+        return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": policy obs_dim " + std::to_string(P.obs_dim) + " != evac_obs_dim " +
                                                       std::to_string(h->p.obs_dim));
-    if ((uintptr_t)actions_out & 7u) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout: actions_out must be 8-byte aligned");
+    if ((uintptr_t)actions_out & 7u) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": actions_out must be 8-byte aligned");
+    evac::PopulationArgs q{};
+    if (strides) {
+        if (n_learners < 1 || n_learners > EVAC_MAX_LEARNERS)
+            return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": n_learners must be in 1.." + std::to_string(EVAC_MAX_LEARNERS));
+        if (h->p.n_envs % n_learners != 0)
+            return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the handle's " + std::to_string(h->p.n_envs) + " envs are not " +
+                                                          std::to_string(n_learners) + " learners' equal shares");
+        // learner s + 1's tensor lies at least one tensor beyond learner s's (a stride of 0 would alias them)
+        const int64_t H = evac::kHidden, D = P.obs_dim;
+        const int64_t least[kMlpTensors] = {H * D, H, H * H, H, 2 * H, 2, 2, H * D, H, H * H, H, H, 1};
+        for (int i = 0; i < kMlpTensors; ++i) {
+            q.stride[i] = (&strides->actor_w1)[i];
+            if (n_learners > 1 && q.stride[i] < least[i])
+                return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": a learner stride is smaller than its tensor");
+        }
+        q.envs_per_learner = h->p.n_envs / n_learners;
+        q.wgs = (q.envs_per_learner + evac::PolicyFamily::kEnvsPerBlock - 1) / evac::PolicyFamily::kEnvsPerBlock;
+    }
     // (parts / chained / persistent handles: joined first, then ONE kernel on `stream` over the whole batch)
     if (const int st = settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
     DeviceGuard g(h->device);
@@ -1472,6 +1492,17 @@ int evac_policy_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_
                              final_stats};
     const evac::NormArgs na{norm_state, gamma, obs_clip, reward_clip, epsilon};
     const bool grav = h->p.obs_pos == EVAC_POS_GRAV, norm = norm_state != nullptr, def = h->default_cfg;
+    const dim3 block(evac::PolicyFamily::kBlock);
+    if (strides) {
+        using evac::k_collect_population;
+        void (*fn)(evac::Params, int, evac::PolicyArgs, evac::NormArgs, evac::PopulationArgs) =
+            grav ? (norm ? (def ? k_collect_population<true, true, true> : k_collect_population<true, true, false>)
+                         : (def ? k_collect_population<true, false, true> : k_collect_population<true, false, false>))
+                 : (norm ? (def ? k_collect_population<false, true, true> : k_collect_population<false, true, false>)
+                         : (def ? k_collect_population<false, false, true> : k_collect_population<false, false, false>));
+        hipLaunchKernelGGL(fn, dim3((unsigned)(n_learners * q.wgs)), block, 0, (hipStream_t)stream, h->p, (int)n_steps, a, na, q);
+        return check_launch(h, what);
+    }
     using evac::k_policy_rollout;
     void (*fn)(evac::Params, int, evac::PolicyArgs, evac::NormArgs) =
         grav ? (norm ? (def ? k_policy_rollout<true, true, true> : k_policy_rollout<true, true, false>)
@@ -1479,9 +1510,31 @@ int evac_policy_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_
              : (norm ? (def ? k_policy_rollout<false, true, true> : k_policy_rollout<false, true, false>)
                      : (def ? k_policy_rollout<false, false, true> : k_policy_rollout<false, false, false>));
     const int per_block = evac::PolicyFamily::kEnvsPerBlock;
-    hipLaunchKernelGGL(fn, dim3((unsigned)((h->p.n_envs + per_block - 1) / per_block)), dim3(evac::PolicyFamily::kBlock), 0,
-                       (hipStream_t)stream, h->p, (int)n_steps, a, na);
-    return check_launch(h, "evac_policy_rollout");
+    hipLaunchKernelGGL(fn, dim3((unsigned)((h->p.n_envs + per_block - 1) / per_block)), block, 0, (hipStream_t)stream, h->p,
+                       (int)n_steps, a, na);
+    return check_launch(h, what);
+}
+
+int evac_policy_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_t* policy, float* next_obs, float* next_done,
+                        float* obs_out, float* actions_out, float* logprob_out, float* value_out, float* reward_out, float* done_out,
+                        float* next_value_out, evac_episode_stats_t* final_stats, double* norm_state, float gamma, float obs_clip,
+                        float reward_clip, float epsilon, void* stream) {
+    EVAC_REQUIRE_BOUND(h, "evac_policy_rollout");
+    return policy_rollout(h, "evac_policy_rollout", 0, nullptr, n_steps, policy, next_obs, next_done, obs_out, actions_out, logprob_out,
+                          value_out, reward_out, done_out, next_value_out, final_stats, norm_state, gamma, obs_clip, reward_clip, epsilon,
+                          stream);
+}
+
+int evac_policy_rollout_population(evac_handle_t h, int32_t n_learners, const evac_mlp_policy_t* policy,
+                                   const evac_mlp_policy_strides_t* strides, int32_t n_steps, float* next_obs, float* next_done,
+                                   float* obs_out, float* actions_out, float* logprob_out, float* value_out, float* reward_out,
+                                   float* done_out, float* next_value_out, evac_episode_stats_t* final_stats, double* norm_state,
+                                   float gamma, float obs_clip, float reward_clip, float epsilon, void* stream) {
+    EVAC_REQUIRE_BOUND(h, "evac_policy_rollout_population");
+    if (!strides) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout_population: strides is NULL");
+    return policy_rollout(h, "evac_policy_rollout_population", n_learners, strides, n_steps, policy, next_obs, next_done, obs_out,
+                          actions_out, logprob_out, value_out, reward_out, done_out, next_value_out, final_stats, norm_state, gamma,
+                          obs_clip, reward_clip, epsilon, stream);
 }
 
 // The double a caller wrote for a setting that evac_config_t holds as float32: the shortest decimal that rounds to the float

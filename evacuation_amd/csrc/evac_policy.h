@@ -178,14 +178,21 @@ __device__ __forceinline__ void stage_policy(PolicySmem<GRAV>& ps, const PolicyA
     }
 }
 
-template <bool GRAV, bool NORM>
+// SHIFTED (the population form, k_collect_population): the wave's env is its place in the launch plus `env_shift`, and it has
+// work while that is below `env_end` -- each learner's workgroups get the learner's own envs.
+template <bool GRAV, bool NORM, bool SHIFTED = false>
 __device__ __forceinline__ void policy_rollout_body(PolicyFamily::Smem& sm, PolicySmem<GRAV>& ps, const Params& p, int n_steps,
-                                                    const PolicyArgs& ka, const NormArgs& kna) {
+                                                    const PolicyArgs& ka, const NormArgs& kna, int env_shift = 0, int env_end = 0) {
     using F = PolicyFamily;
     stage_policy<GRAV>(ps, ka, kna);
     __syncthreads();
     typename F::Ctx w(sm);
-    if (w.env >= p.n_envs) return;
+    if constexpr (SHIFTED) {
+        w.env += env_shift;
+        if (w.env >= env_end) return;
+    } else {
+        if (w.env >= p.n_envs) return;
+    }
     F::init(w);
     const int k = w.lane, D = GRAV ? 6 : p.obs_dim, env = w.env;
     const bool active = w.i < p.n_ped;
@@ -301,6 +308,34 @@ __global__ __launch_bounds__(PolicyFamily::kBlock, 4) void k_policy_rollout(Para
     __shared__ PolicySmem<GRAV> ps;
     if constexpr (DEF) p = default_config_constants<GRAV>(p);
     policy_rollout_body<GRAV, NORM>(sm, ps, p, n_steps, a, na);
+}
+
+// ---- The population form: S learners' collection phases in one launch (include/evac.h: evac_policy_rollout_population) ----
+// Learner s owns envs [s E_l, (s + 1) E_l) of the handle and `wgs` = ceil(E_l / 16) workgroups of the launch, so a workgroup
+// never mixes learners: it stages learner s's 13 tensors (base + s x the tensor's stride) and runs policy_rollout_body on the
+// learner's envs.  The waves past the learner's last env leave after the staging barrier, as the waves past the batch's end do.
+struct PopulationArgs {
+    int envs_per_learner, wgs;                  // E_l, ceil(E_l / 16)
+    int64_t stride[13];                         // floats from learner s to learner s + 1, in evac_mlp_policy_t order
+};
+__device__ __forceinline__ PolicyArgs learner_policy(PolicyArgs a, const PopulationArgs& q, int s) {
+    a.aw1 += s * q.stride[0]; a.ab1 += s * q.stride[1]; a.aw2 += s * q.stride[2]; a.ab2 += s * q.stride[3];
+    a.aw3 += s * q.stride[4]; a.ab3 += s * q.stride[5]; a.logstd += s * q.stride[6];
+    a.cw1 += s * q.stride[7]; a.cb1 += s * q.stride[8]; a.cw2 += s * q.stride[9]; a.cb2 += s * q.stride[10];
+    a.cw3 += s * q.stride[11]; a.cb3 += s * q.stride[12];
+    return a;
+}
+template <bool GRAV, bool NORM, bool DEF>
+__global__ __launch_bounds__(PolicyFamily::kBlock, 4) void k_collect_population(Params p, int n_steps, PolicyArgs a, NormArgs na,
+                                                                                PopulationArgs q) {
+    __shared__ PolicyFamily::Smem sm;
+    __shared__ PolicySmem<GRAV> ps;
+    if constexpr (DEF) p = default_config_constants<GRAV>(p);
+    const int s = (int)blockIdx.x / q.wgs;
+    const PolicyArgs la = learner_policy(a, q, s);
+    // (blockIdx.x x 16 + slot) + shift = s E_l + (blockIdx.x - s wgs) x 16 + slot
+    policy_rollout_body<GRAV, NORM, true>(sm, ps, p, n_steps, la, na, s * (q.envs_per_learner - q.wgs * PolicyFamily::kEnvsPerBlock),
+                                          (s + 1) * q.envs_per_learner);
 }
 
 }  // namespace evac

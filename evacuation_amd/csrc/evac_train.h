@@ -132,28 +132,8 @@ __host__ __device__ inline size_t rpo_w1_parts_floats(int D, int64_t M) {
 }
 __device__ __forceinline__ float* ws_parts(char* ws, int M, int D) { return ws_w1_parts(ws, M) + rpo_w1_parts_floats(D, M); }
 
-// ---- rpo_agent.py:205-220: advantages[t] = delta_t + gamma lambda nonterminal_{t+1} advantages[t+1], one lane per env ----
-// The reference's torch ops, operation for operation (every product and sum rounded: no fma), so the result is bit-equal to the
-// float32 loop on the CPU.  `gl` = (float)(gamma * gae_lambda), the product formed in double and rounded once (Python floats).
-__global__ __launch_bounds__(256) void k_gae(int T, int64_t E, const float* __restrict__ rewards, const float* __restrict__ values,
-                                             const float* __restrict__ dones, const float* __restrict__ next_value,
-                                             const float* __restrict__ next_done, float gamma, float gl, float* __restrict__ adv_out,
-                                             float* __restrict__ ret_out) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= E) return;
-    float vn = next_value[e], dn = next_done[e], last = 0.0f;
-    for (int t = T - 1; t >= 0; --t) {
-        const size_t i = (size_t)t * (size_t)E + (size_t)e;
-        const float r = rewards[i], v = values[i], d = dones[i];
-        const float nonterminal = __fsub_rn(1.0f, dn);
-        const float delta = __fsub_rn(__fadd_rn(r, __fmul_rn(__fmul_rn(gamma, vn), nonterminal)), v);
-        last = __fadd_rn(delta, __fmul_rn(__fmul_rn(gl, nonterminal), last));
-        adv_out[i] = last;
-        ret_out[i] = __fadd_rn(last, v);
-        vn = v;
-        dn = d;
-    }
-}
+// (k_gae and k_adam, the two kernels here that are not templates, are defined in evac_train_api.hip: this header is seen by
+// two translation units)
 
 // Sum of one double per thread over a 1024-thread workgroup: a fixed tree, the total in every thread.
 __device__ __forceinline__ double block_sum_1024(double v, double* buf) {
@@ -171,12 +151,7 @@ __device__ __forceinline__ double block_sum_1024(double v, double* buf) {
 }
 
 // rpo_agent.py:250-251: mean and torch's default (unbiased) std of b_advantages[mb_inds]; header = (mean, std + 1e-8)
-template <class... Gate>
-__global__ __launch_bounds__(kFinishBlock) void k_rpo_adv_stats(RpoArgs a, Gate... gate) {
-    __shared__ double buf[kFinishBlock];
-    if constexpr (sizeof...(Gate) != 0) {
-        if (rpo_stopped(gate...)) return;
-    }
+__device__ __forceinline__ void rpo_adv_stats_body(const RpoArgs& a, double* buf) {
     double s = 0.0, q = 0.0;                   // one pass: in f64 the sum of squares of f32 values loses nothing that matters
 #pragma unroll 8
     for (int m = (int)threadIdx.x; m < a.M; m += kFinishBlock) {
@@ -193,6 +168,14 @@ __global__ __launch_bounds__(kFinishBlock) void k_rpo_adv_stats(RpoArgs a, Gate.
         h[0] = (float)mean;
         h[1] = (float)sqrt(var) + 1e-8f;
     }
+}
+template <class... Gate>
+__global__ __launch_bounds__(kFinishBlock) void k_rpo_adv_stats(RpoArgs a, Gate... gate) {
+    __shared__ double buf[kFinishBlock];
+    if constexpr (sizeof...(Gate) != 0) {
+        if (rpo_stopped(gate...)) return;
+    }
+    rpo_adv_stats_body(a, buf);
 }
 
 template <bool ACTOR>
@@ -393,16 +376,20 @@ __device__ __forceinline__ void rpo_grad_body(const RpoArgs& a, float* lds) {
     }
 }
 
+// The first workgroup of the gradient launch clears the tickets of the finishing launch that follows on the stream.
+__device__ __forceinline__ void rpo_clear_tickets(char* ws) {
+    if (blockIdx.x == 0 && blockIdx.y == 0) {
+        if (threadIdx.x == 0) *ws_ticket(ws) = 0u;
+        if (threadIdx.x < 2 * kMaxW1Tiles) ws_tile_tickets(ws)[threadIdx.x] = 0u;
+    }
+}
 template <class... Gate>
 __global__ __launch_bounds__(kGradBlock) void k_rpo_grad(RpoArgs a, Gate... gate) {
     extern __shared__ __attribute__((aligned(16))) float rpo_lds[];
     if constexpr (sizeof...(Gate) != 0) {
         if (rpo_stopped(gate...)) return;
     }
-    if (blockIdx.x == 0 && blockIdx.y == 0) {  // (k_rpo_finish follows on the stream)
-        if (threadIdx.x == 0) *ws_ticket(a.ws) = 0u;
-        if (threadIdx.x < 2 * kMaxW1Tiles) ws_tile_tickets(a.ws)[threadIdx.x] = 0u;
-    }
+    rpo_clear_tickets(a.ws);
     if (blockIdx.y == 0) rpo_grad_body<true>(a, rpo_lds);
     else rpo_grad_body<false>(a, rpo_lds);
 }
@@ -428,12 +415,13 @@ __device__ __forceinline__ float block_sum_1024f(float v, float* buf) {
     return r;
 }
 
-template <class... Gate>
-__global__ __launch_bounds__(kFinishBlock) void k_rpo_finish(RpoArgs a, Gate... gate) {
+// The finishing launch's workgroup.  Args = const RpoArgs (BY VALUE) for k_rpo_finish: with a reference the compiler unrolls the
+// dW1 loop differently and the kernel no longer compiles to the instructions it had as one function.  The population form
+// (evac_population.h) passes a reference to its learner's arguments in LDS: a.net[net] is indexed at run time, which a
+// modified private copy could only serve from scratch memory.
+template <class Args>
+__device__ __forceinline__ void rpo_finish_body(Args a) {
     constexpr int H = kTrainHidden;
-    if constexpr (sizeof...(Gate) != 0) {
-        if (rpo_stopped(gate...)) return;
-    }
     __shared__ float red[16][kW1Tile][H];      // 32 KiB: the 16 waves' dW1 tiles; reused for the sums of squares
     __shared__ float fin[32];
     __shared__ int last;
@@ -554,6 +542,13 @@ __global__ __launch_bounds__(kFinishBlock) void k_rpo_finish(RpoArgs a, Gate... 
         a.stats[7] = fin[16];
     }
 }
+template <class... Gate>
+__global__ __launch_bounds__(kFinishBlock) void k_rpo_finish(RpoArgs a, Gate... gate) {
+    if constexpr (sizeof...(Gate) != 0) {
+        if (rpo_stopped(gate...)) return;
+    }
+    rpo_finish_body<const RpoArgs>(a);
+}
 
 // ---- rpo_agent.py:278-279: clip_grad_norm_ and Adam(eps = 1e-5).step(), one launch (include/evac.h: evac_adam_step) ----
 // A launch of its own behind k_rpo_finish, not a stage of that kernel's last workgroup: the 13 tensors are 9.4 k elements at
@@ -627,9 +622,4 @@ __device__ __forceinline__ void adam_stage(const AdamArgs& a) {
         }
     }
 }
-__global__ __launch_bounds__(kAdamBlock) void k_adam(AdamArgs a) {
-    if (a.gated && a.hdr->stop) return;
-    adam_stage(a);
-}
-
 }  // namespace evac

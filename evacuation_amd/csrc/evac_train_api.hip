@@ -3,13 +3,44 @@
 // first HIP call.  No device allocation, no synchronisation: every call only enqueues work on the caller's stream.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <mutex>
 
-#include "evac_host.h"
-#include "evac_train.h"
+#include "evac_train_host.h"
+
+// The two kernels of evac_train.h that are not templates: defined in this translation unit alone.
+namespace evac {
+
+// ---- rpo_agent.py:205-220: advantages[t] = delta_t + gamma lambda nonterminal_{t+1} advantages[t+1], one lane per env ----
+// The reference's torch ops, operation for operation (every product and sum rounded: no fma), so the result is bit-equal to the
+// float32 loop on the CPU.  `gl` = (float)(gamma * gae_lambda), the product formed in double and rounded once (Python floats).
+__global__ __launch_bounds__(256) void k_gae(int T, int64_t E, const float* __restrict__ rewards, const float* __restrict__ values,
+                                             const float* __restrict__ dones, const float* __restrict__ next_value,
+                                             const float* __restrict__ next_done, float gamma, float gl, float* __restrict__ adv_out,
+                                             float* __restrict__ ret_out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    float vn = next_value[e], dn = next_done[e], last = 0.0f;
+    for (int t = T - 1; t >= 0; --t) {
+        const size_t i = (size_t)t * (size_t)E + (size_t)e;
+        const float r = rewards[i], v = values[i], d = dones[i];
+        const float nonterminal = __fsub_rn(1.0f, dn);
+        const float delta = __fsub_rn(__fadd_rn(r, __fmul_rn(__fmul_rn(gamma, vn), nonterminal)), v);
+        last = __fadd_rn(delta, __fmul_rn(__fmul_rn(gl, nonterminal), last));
+        adv_out[i] = last;
+        ret_out[i] = __fadd_rn(last, v);
+        vn = v;
+        dn = d;
+    }
+}
+
+__global__ __launch_bounds__(kAdamBlock) void k_adam(AdamArgs a) {
+    if (a.gated && a.hdr->stop) return;
+    adam_stage(a);
+}
+
+}  // namespace evac
 
 extern "C" {
 
@@ -34,53 +65,6 @@ int64_t evac_rpo_workspace_bytes(int32_t obs_dim, int64_t n_minibatch) {
 }
 
 namespace {
-// What evac_rpo_minibatch_grad checks and sets up, for every entry that runs the gradient of a minibatch.
-int rpo_prepare(const evac_mlp_policy_t* policy, const evac_rpo_loss_config_t* cfg, int64_t batch_size, const float* b_obs,
-                const float* b_actions, const float* b_logprobs, const float* b_advantages, const float* b_returns,
-                const float* b_values, int64_t n_minibatch, const int64_t* mb_inds, const float* rpo_noise, uint64_t seed,
-                const evac_mlp_policy_grads_t* grads_out, float* stats_out, void* workspace, evac::RpoArgs& a) {
-    if (!policy || !cfg || !b_obs || !b_actions || !b_logprobs || !b_advantages || !b_returns || !b_values || !mb_inds || !grads_out ||
-        !stats_out || !workspace)
-        return EVAC_ERR_INVALID_ARGUMENT;
-    const evac_mlp_policy_t& P = *policy;
-    const evac_mlp_policy_grads_t& G = *grads_out;
-    if (!mlp_all_set(P) || !mlp_all_set(G)) return EVAC_ERR_INVALID_ARGUMENT;
-    if (P.hidden != evac::kTrainHidden || P.obs_dim < 1 || P.obs_dim > evac::kTrainMaxObs)
-        return EVAC_ERR_INVALID_ARGUMENT;
-    if (batch_size < 1 || n_minibatch < 1 || n_minibatch >= (int64_t)1 << 31 || (cfg->norm_adv && n_minibatch < 2))
-        return EVAC_ERR_INVALID_ARGUMENT;              // (the unbiased std of one sample does not exist)
-    if (((uintptr_t)workspace & 15u) != 0) return EVAC_ERR_INVALID_ARGUMENT;
-    a = evac::RpoArgs{};
-    const float* const* p = mlp_tensors(P);            // (w1 b1 w2 b2 w3 b3 of the actor, logstd, the same six of the critic)
-    float* const* g = mlp_tensors(G);
-    for (int n = 0; n < 2; ++n) {
-        const int o = 7 * n;
-        a.net[n] = evac::RpoNet{p[o], p[o + 1], p[o + 2], p[o + 3], p[o + 4], p[o + 5], g[o], g[o + 1], g[o + 2], g[o + 3], g[o + 4], g[o + 5]};
-    }
-    a.logstd = p[6];
-    a.glogstd = g[6];
-    a.obs = b_obs; a.actions = b_actions; a.logprobs = b_logprobs; a.adv = b_advantages; a.ret = b_returns; a.val = b_values;
-    a.inds = mb_inds;
-    a.noise = rpo_noise;
-    a.stats = stats_out;
-    a.ws = (char*)workspace;
-    a.B = batch_size;
-    a.clip = cfg->clip_coef; a.ent = cfg->ent_coef; a.vf = cfg->vf_coef; a.alpha = cfg->rpo_alpha;
-    a.norm_adv = cfg->norm_adv != 0;
-    a.clip_vloss = cfg->clip_vloss != 0;
-    a.D = P.obs_dim;
-    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
-    return EVAC_OK;
-}
-// the fields that depend on the minibatch's size and on the draw
-void rpo_shape(evac::RpoArgs& a, int64_t n_minibatch, uint64_t draw_counter) {
-    a.M = (int)n_minibatch;
-    const int p0 = evac::rpo_parts_upper(n_minibatch);
-    a.chunk = (int)((n_minibatch + p0 - 1) / p0);
-    a.P = (int)((n_minibatch + a.chunk - 1) / a.chunk);            // every workgroup has samples (P <= p0: the workspace's bound)
-    a.S = evac::rpo_w1_segments(a.D, n_minibatch);
-    a.ctr_lo = (uint32_t)draw_counter; a.ctr_hi = (uint32_t)(draw_counter >> 32);
-}
 // wide observations: more dynamic LDS than the default limit; once per device and kernel
 int rpo_raise_lds(const evac::RpoArgs& a, int dev, bool gated) {
     if (evac::rpo_grad_lds_floats(a.D) * sizeof(float) <= 64 * 1024) return EVAC_OK;
@@ -115,35 +99,6 @@ void rpo_launch(const evac::RpoArgs& a, hipStream_t S, const evac::AdamHeader* g
     }
 }
 
-// What evac_adam_step checks and sets up.  (!(x > 0) also refuses a NaN.)
-int adam_prepare(const evac_mlp_policy_grads_t* params, const evac_mlp_policy_grads_t* grads, const evac_adam_state_t* state,
-                 const evac_adam_config_t* cfg, int32_t obs_dim, evac::AdamArgs& a) {
-    if (!params || !grads || !state || !cfg || !state->header) return EVAC_ERR_INVALID_ARGUMENT;
-    if (obs_dim < 1 || obs_dim > evac::kTrainMaxObs) return EVAC_ERR_INVALID_ARGUMENT;
-    if (((uintptr_t)state->header & 7u) != 0) return EVAC_ERR_INVALID_ARGUMENT;
-    if (!std::isfinite(cfg->lr) || !(cfg->beta1 >= 0.0 && cfg->beta1 < 1.0) || !(cfg->beta2 >= 0.0 && cfg->beta2 < 1.0) ||
-        !(cfg->eps > 0.0) || !(cfg->max_grad_norm > 0.0))
-        return EVAC_ERR_INVALID_ARGUMENT;
-    const evac_mlp_policy_grads_t* sets[4] = {params, grads, &state->exp_avg, &state->exp_avg_sq};
-    float** dst[4] = {a.p, a.g, a.m, a.v};
-    for (int k = 0; k < 4; ++k) {
-        if (!mlp_all_set(*sets[k])) return EVAC_ERR_INVALID_ARGUMENT;
-        for (int i = 0; i < evac::kAdamTensors; ++i) dst[k][i] = mlp_tensors(*sets[k])[i];
-    }
-    const int H = evac::kTrainHidden, D = obs_dim;
-    const int n[evac::kAdamTensors] = {H * D, H, H * H, H, 2 * H, 2, 2, H * D, H, H * H, H, H, 1};
-    int end = 0;
-    for (int i = 0; i < evac::kAdamTensors; ++i) a.end[i] = (end += n[i]);
-    a.hdr = (evac::AdamHeader*)state->header;
-    a.sumsq = nullptr;
-    a.stats = nullptr;
-    a.lr = cfg->lr; a.beta1 = cfg->beta1; a.beta2 = cfg->beta2; a.target_kl = 0.0;
-    a.max_norm = (float)cfg->max_grad_norm;
-    a.w = (float)(1.0 - cfg->beta1); a.b2 = (float)cfg->beta2; a.u = (float)(1.0 - cfg->beta2); a.eps = (float)cfg->eps;
-    a.gated = a.epoch_last = a.use_target_kl = 0;
-    return EVAC_OK;
-}
-static_assert(evac::kAdamTensors == kMlpTensors, "the optimiser walks the 13 tensors of evac_mlp_policy_grads_t");
 void adam_launch(const evac::AdamArgs& a, hipStream_t S) {
     const int n = a.end[evac::kAdamTensors - 1];
     hipLaunchKernelGGL(evac::k_adam, dim3((unsigned)((n + evac::kAdamBlock - 1) / evac::kAdamBlock)), dim3(evac::kAdamBlock), 0, S, a);

@@ -1,0 +1,338 @@
+"""Population training: S independent RPO learners of ONE configuration in one set of launches.
+
+What the reference's users run is a sweep -- ``for sweep in 1 .. 10`` independent training processes per setting
+(run_scripts/run_article_sweeps-*.sh).  At the reference's shape (3 envs x 2048 steps, minibatches of 192) one learner's
+update is a chain of small launches on a nearly idle chip; here learner s rides in the same launches as learner 0:
+
+* ``PolicyPopulation``: the 13 tensors of the actor-critic stacked ``[S, ...]``; ``nets[s]`` is a ``LinearActorCritic`` whose
+  parameters (and ``.grad``) are views of row s, initialised exactly as ``torch.manual_seed(seeds[s]); LinearActorCritic(D)``.
+* ``PopulationAdam``: the optimiser's moments stacked the same way and ``[S]`` headers; ``learners[s]`` is a ``DeviceAdam`` over
+  row s.
+* ``BatchedEvacuationEnv.policy_rollout_population``: the collection phase of all learners in one launch; learner s owns envs
+  ``[s E_l, (s + 1) E_l)`` of one env of ``S E_l`` envs.
+* ``rpo_update_population``: every learner's epochs and minibatches in one host call, four launches per minibatch step as for
+  one learner (``evac_rpo_update_population``).
+* ``PopulationTrainer``: one iteration of the reference's loop for all learners per ``update()``.
+
+Learner s is BIT FOR BIT the ``RPOTrainer(optimizer="device", one_call=True)`` it would be alone on an env of ``E_l`` envs with the
+population env's seed and ``env_id_offset`` further by ``s E_l``, with ``cfg.seed = seeds[s]`` and the same reset state.  One
+configuration per population: no per-learner hyperparameters or env settings."""
+from __future__ import annotations
+
+import ctypes as C
+import time
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+import torch
+from torch import nn
+
+from . import _lib
+from .policy import HIDDEN, LinearActorCritic, _check_structure, mlp_tensors
+from .trainer import (BATCH_KEYS, DeviceAdam, RPOTrainingConfig, _f32, _loss_config, _stream, _u64, decode_header, flatten_batch, gae,
+                      update_steps)
+from .vector_env import STATS_FIELDS, _ptr
+
+MAX_LEARNERS = _lib.MAX_LEARNERS
+
+
+def population_rows(inds: torch.Tensor, learner, envs_per_learner: int, num_learners: int) -> torch.Tensor:
+    """Sample ``i`` of a learner's own batch ``[T, E_l]`` (flattened) -> its row of the common batch ``[T, S E_l]`` (flattened):
+    ``(i // E_l) (S E_l) + s E_l + i % E_l``.  ``learner``: an int, or a tensor that broadcasts against ``inds``."""
+    E_l, S = int(envs_per_learner), int(num_learners)
+    return torch.div(inds, E_l, rounding_mode="floor") * (S * E_l) + learner * E_l + inds % E_l
+
+
+class PolicyPopulation:
+    """S actor-critics of observation width ``obs_dim`` as 13 stacked tensors ``[S, ...]`` on ``device``; see the module's
+    docstring.  ``tensors`` / ``grads``: the stacks, in ``evac_mlp_policy_t`` order; ``strides``: a learner's distance in each."""
+
+    def __init__(self, obs_dim: int, seeds: Sequence[int], device="cuda:0"):
+        seeds = [int(s) for s in seeds]
+        if not 1 <= len(seeds) <= MAX_LEARNERS:
+            raise ValueError(f"PolicyPopulation: {len(seeds)} learners; expected 1..{MAX_LEARNERS}")
+        self.obs_dim, self.seeds, self.device = int(obs_dim), seeds, torch.device(device)
+        self.num_learners = len(seeds)
+        fresh = []
+        with torch.random.fork_rng(devices=[]):                # (the caller's generator is left where it was)
+            for seed in seeds:
+                torch.manual_seed(seed)
+                fresh.append(LinearActorCritic(self.obs_dim))
+        with torch.no_grad():
+            self.tensors = [torch.stack([mlp_tensors(n)[i].detach() for n in fresh]).to(self.device).contiguous() for i in range(13)]
+        self.grads = [torch.zeros_like(t) for t in self.tensors]
+        self.nets: List[LinearActorCritic] = []
+        for s, net in enumerate(fresh):
+            self._bind(net, s)
+            self.nets.append(net)
+            _check_structure(net, self.obs_dim, self.device)
+        self.strides = _lib.EvacMlpPolicyStrides(*(int(t[0].numel()) for t in self.tensors))
+        self._policy = _lib.EvacMlpPolicy(self.obs_dim, HIDDEN, *(t.data_ptr() for t in self.tensors))
+
+    def _bind(self, net: LinearActorCritic, s: int) -> None:
+        """The parameters of ``net`` become views of row s (and their ``.grad`` views of the gradients' row s)."""
+        a, c = net.actor_mean, net.critic
+        owners = [(a[0], "weight"), (a[0], "bias"), (a[2], "weight"), (a[2], "bias"), (a[4], "weight"), (a[4], "bias"),
+                  (net, "actor_logstd"), (c[0], "weight"), (c[0], "bias"), (c[2], "weight"), (c[2], "bias"), (c[4], "weight"), (c[4], "bias")]
+        for i, (mod, name) in enumerate(owners):
+            prm = nn.Parameter(self.tensors[i][s])
+            prm.grad = self.grads[i][s]
+            setattr(mod, name, prm)
+
+    def policy_struct(self) -> "_lib.EvacMlpPolicy":
+        """``evac_mlp_policy_t`` of learner 0, the base the strides count from (every learner's views were checked when made)."""
+        return self._policy
+
+
+class PopulationAdam:
+    """``DeviceAdam`` for every learner of ``population``: the moments stacked ``[S, ...]``, ``headers`` ``[S, 8]`` (64 bytes a
+    learner).  One ``param_groups[0]`` for all (one configuration per population).  ``learners[s]`` is a ``DeviceAdam`` whose
+    state is row s: ``state_dict(s)`` / ``load_state_dict(s, sd)`` are its, in ``DeviceAdam``'s format."""
+
+    def __init__(self, population: PolicyPopulation, lr: float = 3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5,
+                 max_grad_norm: float = 0.5):
+        self.population = population
+        S, dev = population.num_learners, population.device
+        self.headers = torch.zeros(S, 8, dtype=torch.int64, device=dev)
+        self.exp_avg = [torch.zeros_like(t) for t in population.tensors]
+        self.exp_avg_sq = [torch.zeros_like(t) for t in population.tensors]
+        self.learners = [DeviceAdam(net, lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm,
+                                    storage=(self.headers[s], [m[s] for m in self.exp_avg], [v[s] for v in self.exp_avg_sq]))
+                         for s, net in enumerate(population.nets)]
+        self.param_groups = self.learners[0].param_groups
+        for opt in self.learners[1:]:
+            opt.param_groups = self.param_groups
+        self.header_stride_bytes = 64
+        self.moment_strides = population.strides
+
+    def config(self) -> "_lib.EvacAdamConfig":
+        return self.learners[0].config()
+
+    def read_headers(self) -> List[dict]:
+        host = self.headers.cpu()
+        return [decode_header(h) for h in host]
+
+    def state_dict(self, learner: int) -> dict:
+        return self.learners[learner].state_dict()
+
+    def load_state_dict(self, learner: int, sd: dict) -> None:
+        self.learners[learner].load_state_dict(sd)
+
+
+def _batch_ptrs(batch: Dict[str, torch.Tensor]):
+    b_obs = batch["b_obs"]
+    B, D = b_obs.shape
+    _f32(b_obs, (B, D), "b_obs")
+    _f32(batch["b_actions"], (B, 2), "b_actions")
+    for k in BATCH_KEYS[2:]:
+        _f32(batch[k], (B,), k)
+    return int(B), int(D), [int(B)] + [_ptr(batch[k]) for k in BATCH_KEYS]
+
+
+def population_workspace_bytes(obs_dim: int, minibatch_size: int, num_learners: int) -> int:
+    need = int(_lib.load().evac_rpo_population_workspace_bytes(int(obs_dim), int(minibatch_size), int(num_learners)))
+    if need < 0:
+        raise _lib.EvacError(need, f"evac_rpo_population_workspace_bytes({obs_dim}, {minibatch_size}, {num_learners})")
+    return need
+
+
+def rpo_update_population(population: PolicyPopulation, batch: Dict[str, torch.Tensor], rows: torch.Tensor, cfg, opt: PopulationAdam, *,
+                          minibatch_size: Optional[int] = None, rpo_noise: Optional[torch.Tensor] = None,
+                          seeds: Optional[Sequence[int]] = None, first_draw_counters: Optional[Sequence[int]] = None,
+                          stats: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """``rpo_update`` for every learner in one host call (``evac_rpo_update_population``).  ``batch``: the COMMON flat arrays
+    (``flatten_batch`` of the population's storage); ``rows`` int64 ``[S, epochs, B_l]``: per learner and epoch the rows of the
+    common batch in the order the learner visits them (``population_rows`` of its permutation of ``[0, B_l)``).  Learner s draws
+    its RPO perturbation from Philox keyed ``seeds[s]`` (default ``population.seeds``) at ``first_draw_counters[s] + k`` for step
+    k, or reads ``rpo_noise[s, k]`` (``[S, steps, M, 2]``).  Returns (``stats`` ``[S, steps, 8]``, ``opt.headers``); rows beyond a
+    learner's ``steps_run`` keep what they held.  No host synchronisation; four launches per minibatch step."""
+    if opt.population is not population:
+        raise ValueError("the PopulationAdam was made for another population")
+    S, dev = population.num_learners, population.device
+    B, D, b_args = _batch_ptrs(batch)
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int64 or rows.device != batch["b_obs"].device or \
+            not rows.is_contiguous() or rows.dim() != 3 or rows.shape[0] != S or rows.shape[1] < 1 or rows.shape[2] < 1:
+        raise ValueError(f"rows: expected a contiguous int64 device tensor of shape [{S}, epochs, B_l]")
+    n_epochs, B_l = int(rows.shape[1]), int(rows.shape[2])
+    M = int(cfg.minibatch_size if minibatch_size is None else minibatch_size)
+    norm_adv = bool(getattr(cfg, "norm_adv", True))
+    if M < (2 if norm_adv else 1):
+        raise ValueError(f"rpo_update_population: minibatch_size = {M}")
+    M = min(M, B_l)
+    steps = n_epochs * len(update_steps(B_l, M, norm_adv))
+    if rpo_noise is not None:
+        _f32(rpo_noise, (S, steps, M, 2), "rpo_noise")
+    if stats is None:
+        stats = torch.zeros(S, steps, 8, dtype=torch.float32, device=dev)
+    else:
+        _f32(stats, (S, steps, 8), "stats")
+    need = population_workspace_bytes(D, M, S)
+    if workspace is None or workspace.numel() < need or workspace.device != dev:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    seeds = population.seeds if seeds is None else [int(x) for x in seeds]
+    counters = [0] * S if first_draw_counters is None else [int(x) for x in first_draw_counters]
+    if len(seeds) != S or len(counters) != S:
+        raise ValueError(f"rpo_update_population: seeds and first_draw_counters must have {S} entries")
+    u64 = C.c_uint64 * S
+    if D != population.obs_dim:
+        raise ValueError(f"rpo_update_population: b_obs has {D} columns, the population's observation has {population.obs_dim}")
+    pol = population.policy_struct()
+    params = _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in population.tensors))
+    grads = _lib.EvacMlpPolicyGrads(*(g.data_ptr() for g in population.grads))
+    target_kl = getattr(cfg, "target_kl", None)
+    lc, oc = _loss_config(cfg), opt.config()
+    rc = _lib.load().evac_rpo_update_population(
+        S, C.byref(pol), C.byref(params), C.byref(grads), C.byref(population.strides), C.byref(population.strides),
+        C.byref(opt.moment_strides), opt.header_stride_bytes, C.byref(lc), C.byref(oc), C.byref(opt.learners[0].state_struct()), *b_args,
+        B_l, M, n_epochs, _ptr(rows), _ptr(rpo_noise), u64(*(_u64(x) for x in seeds)), u64(*(_u64(x) for x in counters)),
+        int(target_kl is not None), float(target_kl or 0.0), _ptr(stats), _ptr(workspace), _stream(dev))
+    _lib.check(rc)
+    return stats, opt.headers
+
+
+class PopulationTrainer:
+    """``RPOTrainer(optimizer="device", one_call=True)`` for every learner of ``population`` at once.  ``env``: a
+    ``NormalizedVectorEnv`` or ``BatchedEvacuationEnv`` of ``S x cfg.num_envs`` envs (learner s owns the s-th share); ``cfg``: ONE
+    configuration for all, ``cfg.seed`` unused -- learner s's permutations come from a generator seeded ``population.seeds[s]`` and
+    its RPO perturbation from Philox keyed with the same seed.  ``update()``: anneal, one collection launch, one ``gae``, the
+    permutations, one ``rpo_update_population``, ONE host transfer; returns a list of S logs with ``RPOTrainer.update()``'s keys."""
+
+    def __init__(self, env, population: PolicyPopulation, cfg: RPOTrainingConfig):
+        cfg.check()
+        S = population.num_learners
+        if env.num_envs != S * cfg.num_envs:
+            raise ValueError(f"PopulationTrainer: the env has {env.num_envs} envs; {S} learners x cfg.num_envs = {S * cfg.num_envs}")
+        self.env, self.population, self.cfg = env, population, cfg
+        self.nets, self.device = population.nets, population.device
+        self.num_learners, self.envs_per_learner = S, int(cfg.num_envs)
+        self.optimizer = PopulationAdam(population, lr=cfg.learning_rate, eps=1e-5, max_grad_norm=cfg.max_grad_norm)
+        self.generators = []
+        for seed in population.seeds:
+            g = torch.Generator(device=self.device)
+            g.manual_seed(int(seed))
+            self.generators.append(g)
+        self.learner_index = torch.arange(S, device=self.device).reshape(S, 1, 1)
+        self.update_index = 0
+        self.global_step = 0                      # of ONE learner, as RPOTrainer counts
+        self.minibatch_steps = [0] * S            # every learner's draw counter of the RPO perturbation
+        self.start_time = None
+        self.storage = self.advantages = self.returns = None
+        self.next_obs = self.next_done = None
+        self.stats_rows = self.workspace = None
+        self.last_permutations = None             # [S, epochs, B_l]: the learners' own permutations of the last update
+        self.evaluator = None
+
+    def _start(self):
+        obs, _ = self.env.reset()
+        self.next_obs = obs.clone()
+        self.next_done = torch.zeros(self.env.num_envs, dtype=torch.float32, device=self.device)
+        self.start_time = time.time()
+
+    def collect(self):
+        """Every learner's collection phase (one launch) and advantages (one launch)."""
+        if self.next_obs is None:
+            self._start()
+        if self.start_time is None:
+            self.start_time = time.time()
+        with torch.no_grad():
+            self.storage = self.env.policy_rollout_population(self.population, self.cfg.num_steps, self.next_obs, self.next_done,
+                                                              out=self.storage)
+            out = None if self.advantages is None else (self.advantages, self.returns)
+            self.advantages, self.returns = gae(self.storage, self.cfg.gamma, self.cfg.gae_lambda, out=out)
+        self.global_step += self.cfg.batch_size
+        return self.storage
+
+    def update(self) -> List[dict]:
+        cfg, S, E_l = self.cfg, self.num_learners, self.envs_per_learner
+        if cfg.anneal_lr:
+            frac = 1.0 - self.update_index / max(1, cfg.num_updates)
+            self.optimizer.param_groups[0]["lr"] = frac * cfg.learning_rate
+        storage = self.collect()
+        batch = flatten_batch(storage, self.advantages, self.returns)
+        B_l, T = cfg.batch_size, cfg.num_steps
+        perms = torch.stack([torch.stack([torch.randperm(B_l, device=self.device, generator=g) for _ in range(cfg.update_epochs)])
+                             for g in self.generators])
+        self.last_permutations = perms
+        rows = population_rows(perms, self.learner_index, E_l, S)
+        steps = cfg.update_epochs * len(update_steps(B_l, cfg.minibatch_size, cfg.norm_adv))
+        if self.stats_rows is None or self.stats_rows.shape[1] != steps:
+            self.stats_rows = torch.zeros(S, steps, 8, dtype=torch.float32, device=self.device)
+        need = population_workspace_bytes(self.population.obs_dim, min(cfg.minibatch_size, B_l), S)
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        stats, headers = rpo_update_population(self.population, batch, rows, cfg, self.optimizer,
+                                               first_draw_counters=self.minibatch_steps, stats=self.stats_rows,
+                                               workspace=self.workspace)
+        self.update_index += 1
+        # the logged scalars of every learner, over its own columns (contiguous copies: the arrays RPOTrainer reduces), ONE transfer
+        ret, val = self.returns.view(T, S, E_l), storage["values"].view(T, S, E_l)
+        evs, var_ys = [], []
+        for s in range(S):
+            y_true, y_pred = ret[:, s].reshape(-1), val[:, s].reshape(-1)
+            var_y = y_true.var(unbiased=False)
+            evs.append((1 - (y_true - y_pred).var(unbiased=False) / var_y).reshape(1))
+            var_ys.append(var_y.reshape(1))
+        host = torch.cat([headers.view(torch.float32).reshape(-1), stats.reshape(-1)] + evs + var_ys).cpu()
+        hdr, rows_h = host[:16 * S].reshape(S, 16), host[16 * S:16 * S + S * steps * 8].reshape(S, steps, 8)
+        tail = host[16 * S + S * steps * 8:]
+        es = storage["episode_stats"]
+        done = storage["dones"][1:].bool()
+        ended = torch.cat([done, storage["next_done"].bool()[None]], dim=0)
+        sps = int(self.global_step / max(time.time() - self.start_time, 1e-9))
+        lr = self.optimizer.param_groups[0]["lr"]
+        logs = []
+        for s in range(S):
+            h = decode_header(hdr[s])
+            ran = h["steps_run"]
+            self.minibatch_steps[s] += ran
+            last, clipfrac = rows_h[s, ran - 1].tolist(), float(rows_h[s, :ran, 6].mean())
+            cols = slice(s * E_l, (s + 1) * E_l)
+            recs = es[:, cols][ended[:, cols]]
+            ev, var_y = float(tail[s]), float(tail[S + s])
+            logs.append({"update": self.update_index, "global_step": self.global_step, "learning_rate": lr, "value_loss": last[2],
+                         "policy_loss": last[1], "entropy": last[3], "old_approx_kl": last[4], "approx_kl": last[5],
+                         "clipfrac": clipfrac, "explained_variance": float("nan") if var_y == 0 else ev, "loss": last[0], "SPS": sps,
+                         "episodes": {k: recs[:, i] for i, k in enumerate(STATS_FIELDS)}, "learner": s,
+                         "seed": self.population.seeds[s], "steps_run": ran, "epochs_run": h["epochs_run"]})
+        return logs
+
+    def make_evaluator(self, num_envs: Optional[int] = None):
+        """One ``PolicyEvaluator`` for all learners: the training env's configs, a handle and a batch of its own (``num_envs``: a
+        learner's share of the training batch by default)."""
+        from .evaluation import PolicyEvaluator
+        base = getattr(self.env, "env", self.env)
+        n = self.envs_per_learner if num_envs is None else int(num_envs)
+        if self.evaluator is None or self.evaluator.num_envs != n:
+            if self.evaluator is not None:
+                self.evaluator.close()
+            self.evaluator = PolicyEvaluator(base.env_config, base.wrap_config, num_envs=n, seed=base.seed_value, device=base.device)
+        return self.evaluator
+
+    def evaluate(self, n_episodes: int = 1, num_envs: Optional[int] = None, deterministic: bool = True) -> list:
+        """``RPOTrainer.evaluate`` for every learner in turn on the shared evaluator, each with its own rows of the training
+        env's observation statistics (frozen copies).  Returns S ``EvaluationResult``s."""
+        ev, E_l = self.make_evaluator(num_envs), self.envs_per_learner
+        out = []
+        with torch.no_grad():
+            for s, net in enumerate(self.nets):
+                kw = {}
+                if hasattr(self.env, "norm_state"):
+                    kw = {"norm_state": self.env.norm_state[s * E_l:(s + 1) * E_l].clone(), "obs_clip": self.env.obs_clip,
+                          "epsilon": self.env.epsilon}
+                out.append(ev.evaluate(net, n_episodes, deterministic=deterministic, **kw))
+        return out
+
+    def learn(self, total_timesteps: Optional[int] = None, callback: Optional[Callable[[List[dict]], None]] = None, *,
+              eval_every: Optional[int] = None, eval_episodes: int = 1) -> list:
+        """``num_updates`` updates (``total_timesteps // batch_size``, per learner); returns the list of ``update()``'s results.
+        Every ``eval_every`` updates each learner's ``log["eval"]`` holds the ``summary()`` of its ``evaluate(eval_episodes)``."""
+        n = self.cfg.num_updates if total_timesteps is None else int(total_timesteps) // self.cfg.batch_size
+        all_logs = []
+        for _ in range(n):
+            logs = self.update()
+            if eval_every and self.update_index % int(eval_every) == 0:
+                for log, res in zip(logs, self.evaluate(eval_episodes)):
+                    log["eval"] = res.summary()
+            all_logs.append(logs)
+            if callback is not None:
+                callback(logs)
+        return all_logs

@@ -239,7 +239,9 @@ class DeviceAdam:
     the bias corrections' running products live on the device, so a captured step counts when it is replayed.
     ``param_groups[0]`` is read at every call: ``opt.param_groups[0]["lr"] = lrnow`` works as with torch."""
 
-    def __init__(self, net, lr: float = 3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm: float = 0.5):
+    def __init__(self, net, lr: float = 3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm: float = 0.5,
+                 *, storage=None):
+        """``storage`` = (header, exp_avg, exp_avg_sq): the state lives in the caller's tensors (``PopulationAdam``'s rows)."""
         group = {"lr": float(lr), "betas": (float(betas[0]), float(betas[1])), "eps": float(eps), "max_grad_norm": float(max_grad_norm)}
         self._check_group(group)
         self.net = net
@@ -250,9 +252,12 @@ class DeviceAdam:
                 raise ValueError("DeviceAdam: the parameters must be contiguous float32 device tensors")
         self.obs_dim = int(self.params[0].shape[1])
         self.param_groups = [group]
-        self.header = torch.zeros(8, dtype=torch.int64, device=self.device)
-        self.exp_avg = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
-        self.exp_avg_sq = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        if storage is None:
+            self.header = torch.zeros(8, dtype=torch.int64, device=self.device)
+            self.exp_avg = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+            self.exp_avg_sq = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        else:
+            self.header, self.exp_avg, self.exp_avg_sq = storage[0], list(storage[1]), list(storage[2])
         self._state = _lib.EvacAdamState(self.header.data_ptr(), _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in self.exp_avg)),
                                          _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in self.exp_avg_sq)))
         self._params = [None, None]

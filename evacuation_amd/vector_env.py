@@ -585,6 +585,20 @@ class BatchedEvacuationEnv:
         ``next_done``.  Pass a previous result as ``out`` to reuse it.  Raw observations and rewards here;
         ``NormalizedVectorEnv.policy_rollout`` runs the trainer's normalisation chain.  No host synchronisation: the call can
         be captured into a graph, and the kernel reads the parameters in place at every replay."""
+        return self._policy_rollout(net, None, n_steps, next_obs, next_done, out, _norm)
+
+    def policy_rollout_population(self, population, n_steps: int, next_obs: torch.Tensor, next_done: torch.Tensor,
+                                  out: Optional[TDict] = None, _norm=None):
+        """``policy_rollout`` for the S learners of ``population`` (a ``PolicyPopulation``) in ONE launch
+        (``evac_policy_rollout_population``): learner s acts in envs ``[s E_l, (s + 1) E_l)`` of this env, ``E_l = num_envs / S``.
+        Arguments and storage are ``policy_rollout``'s, over the whole batch; learner s's columns hold, bit for bit, what
+        ``policy_rollout(population.nets[s], ...)`` writes on an env of ``E_l`` envs with the same seed, ``env_id_offset`` further
+        by ``s E_l`` and the same start state."""
+        if self.num_envs % population.num_learners:
+            raise ValueError(f"policy_rollout_population: {self.num_envs} envs are not {population.num_learners} learners' equal shares")
+        return self._policy_rollout(population.nets[0], population, n_steps, next_obs, next_done, out, _norm)
+
+    def _policy_rollout(self, net, population, n_steps, next_obs, next_done, out, _norm):
         from .policy import MAX_PEDESTRIANS, PolicyBinder
         if self.n_ped > MAX_PEDESTRIANS:
             raise NotImplementedError(f"policy_rollout runs one wave per env: rooms of at most {MAX_PEDESTRIANS} pedestrians "
@@ -607,10 +621,15 @@ class BatchedEvacuationEnv:
             for k, s in shapes.items():
                 self._check_tensor(out[k], s, f32, k)
         state, gamma, obs_clip, reward_clip, eps = _norm if _norm is not None else (None, 0.0, 0.0, 0.0, 0.0)
-        _lib.check(self.lib.evac_policy_rollout(
-            self._h, T, C.byref(pol), _ptr(next_obs), _ptr(next_done), _ptr(out["obs"]), _ptr(out["actions"]), _ptr(out["logprobs"]),
-            _ptr(out["values"]), _ptr(out["rewards"]), _ptr(out["dones"]), _ptr(out["next_value"]), _ptr(out["episode_stats"]),
-            _ptr(state), gamma, obs_clip, reward_clip, eps, self._stream()), self._h)
+        args = [_ptr(next_obs), _ptr(next_done), _ptr(out["obs"]), _ptr(out["actions"]), _ptr(out["logprobs"]), _ptr(out["values"]),
+                _ptr(out["rewards"]), _ptr(out["dones"]), _ptr(out["next_value"]), _ptr(out["episode_stats"]), _ptr(state), gamma,
+                obs_clip, reward_clip, eps, self._stream()]
+        if population is None:
+            rc = self.lib.evac_policy_rollout(self._h, T, C.byref(pol), *args)
+        else:
+            rc = self.lib.evac_policy_rollout_population(self._h, population.num_learners, C.byref(pol), C.byref(population.strides),
+                                                         T, *args)
+        _lib.check(rc, self._h)
         out["next_obs"], out["next_done"] = next_obs, next_done
         return out
 

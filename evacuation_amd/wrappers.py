@@ -68,6 +68,11 @@ class NormalizedVectorEnv:
         return self.env.policy_rollout(net, n_steps, next_obs, next_done, out=out,
                                        _norm=(self.norm_state, self.gamma, self.obs_clip, self.reward_clip, self.epsilon))
 
+    def policy_rollout_population(self, population, n_steps: int, next_obs, next_done, out=None):
+        """``BatchedEvacuationEnv.policy_rollout_population`` through the trainer's chain (as ``policy_rollout``)."""
+        return self.env.policy_rollout_population(population, n_steps, next_obs, next_done, out=out,
+                                                  _norm=(self.norm_state, self.gamma, self.obs_clip, self.reward_clip, self.epsilon))
+
     def policy_evaluate(self, agent, n_episodes: int, max_steps: int, progress=None, out=None, *, deterministic: bool = True):
         """``BatchedEvacuationEnv.policy_evaluate`` with this env's observation statistics applied FROZEN: the policy reads
         ``clip((x - mean) / sqrt(var + epsilon), +-obs_clip)`` of ``norm_state``, which is only read -- nothing is counted, and

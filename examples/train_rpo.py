@@ -7,11 +7,16 @@ RPO loss (``evac_rpo_minibatch_grad``: three launches) followed by torch's ``cli
 minibatches in one host call (``evac_rpo_update``).  Prints the reference's ``SPS`` line per update.
 
     python examples/train_rpo.py [--envs 4096] [--steps 128] [--updates 5] [--pedestrians 60] [--optimizer device]
-                                 [--eval-every 1] [--eval-episodes 1] [--baseline]
+                                 [--eval-every 1] [--eval-episodes 1] [--baseline] [--seeds 1,2,3]
 
 ``--eval-every K`` evaluates the leader every K updates (``RPOTrainer.evaluate``: whole episodes, the mean action, the observation
 statistics frozen) and prints the summary; ``--baseline`` prints the same line for the reference's scripted sweep baseline
 (baseline_wacuum_cleaner.py) on the same evaluator, i.e. on the same episodes.
+
+``--seeds a,b,c`` trains one learner per seed as a POPULATION (``PopulationTrainer``): ``--envs`` envs per learner in one env of
+``len(seeds) x --envs``, every learner's collection in one launch and every learner's minibatch step in the four launches of one
+(``evac_rpo_update_population``); each learner is bit for bit the ``--optimizer device`` run it would be alone.  One line per
+learner and update.
 
 ``--compare`` measures, at the same sizes and with the reference's 32 minibatches x 10 epochs, one ``update()`` (a) with the
 kernels against (b) the same update with the loss written in torch (tests/trainer_ref.py, float32) and autograd, eager and with
@@ -43,6 +48,16 @@ def make_trainer(args, **hooks):
     torch.manual_seed(0)
     net = LinearActorCritic(env.obs_dim).to(DEV)
     return RPOTrainer(env, net, cfg, **hooks)
+
+
+def make_population_trainer(args, seeds):
+    from evacuation_amd.population import PolicyPopulation, PopulationTrainer
+    cfg = RPOTrainingConfig(num_envs=args.envs, num_steps=args.steps, total_timesteps=args.envs * args.steps * max(args.updates, 1),
+                            num_minibatches=args.minibatches, update_epochs=args.epochs)
+    env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=args.pedestrians, is_new_exiting_reward=True),
+                                      ea.EnvWrappersConfig(positions="grav", alpha=3), num_envs=args.envs * len(seeds), gamma=cfg.gamma,
+                                      seed=1)
+    return PopulationTrainer(env, PolicyPopulation(env.obs_dim, seeds, DEV), cfg)
 
 
 def eager_yardstick(R):
@@ -188,10 +203,12 @@ def main():
     ap.add_argument("--eval-every", type=int, default=None, help="evaluate the leader every K updates (whole episodes, mean action, frozen normaliser)")
     ap.add_argument("--eval-episodes", type=int, default=1, help="episodes per env of an evaluation")
     ap.add_argument("--baseline", action="store_true", help="print the scripted sweep baseline's summary on the same evaluator")
+    ap.add_argument("--seeds", type=str, default=None, help="comma-separated seeds: one learner per seed, trained as a population")
     args = ap.parse_args()
     if args.compare:
         return compare(args)
-    tr = make_trainer(args, optimizer=args.optimizer)
+    seeds = [int(x) for x in args.seeds.split(",")] if args.seeds else None
+    tr = make_population_trainer(args, seeds) if seeds else make_trainer(args, optimizer=args.optimizer)
 
     def eval_line(name, s):
         print(f"eval {name:14s} episodic_return={s['episode_reward_mean']:9.2f} +- {s['episode_reward_std']:.2f}  length={s['episode_length_mean']:7.1f}  "
@@ -200,9 +217,14 @@ def main():
         eval_line("vacuum_cleaner", tr.make_evaluator().evaluate("vacuum_cleaner", args.eval_episodes).summary())
 
     def line(log):
+        if isinstance(log, list):                                # a population's update: one line per learner
+            for one in log:
+                line(one)
+            return
         r = log["episodes"]["episode_reward"]
         ret = f"{float(r.mean()):9.2f} over {r.numel():5d} episodes" if r.numel() else "   (no episode finished)"
-        print(f"update {log['update']:3d}  global_step={log['global_step']:9d}  value_loss={log['value_loss']:.4f}  policy_loss={log['policy_loss']:+.5f}  "
+        who = f"seed {log['seed']:<6d} " if "seed" in log else ""
+        print(f"{who}update {log['update']:3d}  global_step={log['global_step']:9d}  value_loss={log['value_loss']:.4f}  policy_loss={log['policy_loss']:+.5f}  "
               f"approx_kl={log['approx_kl']:.5f}  clipfrac={log['clipfrac']:.3f}  explained_variance={log['explained_variance']:+.3f}  episodic_return={ret}")
         print("SPS:", log["SPS"])
         if "eval" in log:

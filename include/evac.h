@@ -407,6 +407,34 @@ int evac_policy_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_
                         double* norm_state_or_null, float gamma, float obs_clip, float reward_clip, float epsilon,
                         void* stream);
 
+/* ---- Population: S independent learners of ONE configuration in one set of launches ----
+ * What the reference's users run is a sweep: `for sweep in 1 .. 10` independent training processes per setting.  A population
+ * is S learners whose 13 tensors are stacked (learner s's tensor = the base pointer + s x that tensor's stride, in floats) and
+ * whose envs are the consecutive shares of ONE handle of S x E_l envs: learner s owns envs [s E_l, (s + 1) E_l).
+ * EVAC_MAX_LEARNERS is set by the kernel-argument segment: evac_rpo_update_population passes every learner's seed and draw
+ * counter by value (16 bytes a learner: 1 KiB of the 4 KiB a HIP launch takes, beside ~0.9 KiB of pointers and strides). */
+#define EVAC_MAX_LEARNERS 64
+typedef struct evac_mlp_policy_strides {   /* floats from learner s to learner s + 1, per tensor of evac_mlp_policy_t */
+    int64_t actor_w1, actor_b1, actor_w2, actor_b2, actor_w3, actor_b3, actor_logstd;
+    int64_t critic_w1, critic_b1, critic_w2, critic_b2, critic_w3, critic_b3;
+} evac_mlp_policy_strides_t;
+/* evac_policy_rollout_population: evac_policy_rollout for n_learners learners in ONE launch.  `policy` holds learner 0's
+ * tensors; the storage is that of one evac_policy_rollout over the whole handle (time-major, E = S x E_l: obs_out [T][E][D] ...),
+ * norm_state and the env state likewise.  EQUIVALENCE: the call writes, bit for bit, what S calls of evac_policy_rollout write
+ * -- call s with learner s's tensors on a handle of E_l envs with the same seed, env_id_offset = this handle's + s E_l and
+ * learner s's share of the state -- into the learner's columns [s E_l, (s + 1) E_l) of every array (envs are independent of
+ * their neighbours in a batch).  ceil(E_l / 16) CU-wide workgroups per learner; a workgroup never mixes learners.
+ * EVAC_ERR_INVALID_ARGUMENT: as evac_policy_rollout, and a NULL strides, n_learners outside 1..EVAC_MAX_LEARNERS, a number of
+ * envs that n_learners does not divide, and with n_learners > 1 a stride smaller than its tensor (0 included). */
+int evac_policy_rollout_population(evac_handle_t h, int32_t n_learners, const evac_mlp_policy_t* policy,
+                                   const evac_mlp_policy_strides_t* strides, int32_t n_steps,
+                                   float* next_obs, float* next_done,
+                                   float* obs_out, float* actions_out, float* logprob_out,
+                                   float* value_out, float* reward_out, float* done_out,
+                                   float* next_value_out, evac_episode_stats_t* final_stats_or_null,
+                                   double* norm_state_or_null, float gamma, float obs_clip, float reward_clip, float epsilon,
+                                   void* stream);
+
 /* ---- Policy evaluation: whole episodes per env under a FIXED agent, one episode record per finished episode ----
  * What a user of the reference writes around a trained network or a scripted agent and EvacuationEnv.step / reset
  * (env.py:106-171): `obs = env.reset(); while not done: obs, r, term, trunc, _ = env.step(agent.act(obs))`, per env, with the
@@ -568,6 +596,42 @@ int evac_rpo_update(const evac_mlp_policy_t* policy, const evac_mlp_policy_grads
                     int32_t n_epochs, const int64_t* perms, const float* rpo_noise_or_null, uint64_t seed,
                     uint64_t first_draw_counter, int32_t use_target_kl, double target_kl, float* stats_out, void* workspace,
                     void* stream);
+
+/* evac_rpo_update_population: evac_rpo_update for n_learners learners in one set of launches: the learner is one more grid
+ * dimension of each of the four kernels of a step, so the launch count per minibatch step is that of one learner.
+ *   policy / params / grads / state: learner 0's tensors; learner s's are s x the strides further (param_strides for policy and
+ *   params, grad_strides, moment_strides for exp_avg and exp_avg_sq, in floats) and its 64-byte header s x header_stride_bytes.
+ *   The batch arrays are COMMON: batch_size rows, of which each learner reads its own through its index list.
+ *   perms int64 [S][n_epochs][learner_batch_size] in device memory: learner s's minibatches are consecutive n_minibatch-long
+ *   pieces of perms[s][epoch], exactly as evac_rpo_update cuts perms[epoch]; the VALUES are rows of the common arrays (an index
+ *   outside [0, batch_size) is clamped into the batch, never followed).  For the storage of evac_policy_rollout_population,
+ *   flattened, sample i of learner s is row (i / E_l) x (S x E_l) + s x E_l + i % E_l.
+ *   rpo_noise_or_null [S][steps][M][2];  stats_out [S][steps][8];  seeds [S] and first_draw_counters [S]: HOST arrays, read
+ *   during the call (learners that stopped early have run fewer steps, so their counters differ).
+ *   workspace: evac_rpo_population_workspace_bytes(obs_dim, M, S) bytes, 16-byte aligned: S slices of
+ *   evac_rpo_workspace_bytes(obs_dim, M) rounded up to 128 bytes each.
+ * Every learner has its own workspace slice, ticket words, header and statistics rows: no learner reads another's and nothing
+ * waits across learners.  A learner whose stop flag is set (target_kl) returns at once in every later kernel while the others go
+ * on; header s says what learner s ran.  The call clears every learner's stop / steps_run / epochs_run on the stream before
+ * its first step.  EQUIVALENCE: learner s's parameters, moments, header, gradients and statistics rows are, bit for bit, those
+ * of evac_rpo_update called with learner s's tensors, perms[s], seeds[s], first_draw_counters[s] and the same common batch
+ * (equivalently: with the learner's own rows gathered into a batch of learner_batch_size and its own positions as indices).
+ * No host synchronisation, capturable (seeds and counters are frozen by a capture, as evac_rpo_update's).
+ * EVAC_ERR_INVALID_ARGUMENT, decided on the host before anything touches a device: as evac_rpo_update (a NULL pointer, hidden
+ * != 64, obs_dim outside 1..396, n_minibatch < 1 or < 2 with norm_adv, a misaligned workspace, ...), and n_learners outside
+ * 1..EVAC_MAX_LEARNERS, a NULL strides / seeds / first_draw_counters, learner_batch_size < 1, and with n_learners > 1 a stride
+ * smaller than its tensor (0 included) or a header stride that is below 64 or not a multiple of 8. */
+int64_t evac_rpo_population_workspace_bytes(int32_t obs_dim, int64_t n_minibatch, int32_t n_learners);
+int evac_rpo_update_population(int32_t n_learners, const evac_mlp_policy_t* policy, const evac_mlp_policy_grads_t* params,
+                               const evac_mlp_policy_grads_t* grads, const evac_mlp_policy_strides_t* param_strides,
+                               const evac_mlp_policy_strides_t* grad_strides, const evac_mlp_policy_strides_t* moment_strides,
+                               int64_t header_stride_bytes, const evac_rpo_loss_config_t* loss_cfg,
+                               const evac_adam_config_t* adam_cfg, const evac_adam_state_t* state, int64_t batch_size,
+                               const float* b_obs, const float* b_actions, const float* b_logprobs, const float* b_advantages,
+                               const float* b_returns, const float* b_values, int64_t learner_batch_size, int64_t n_minibatch,
+                               int32_t n_epochs, const int64_t* perms, const float* rpo_noise_or_null, const uint64_t* seeds,
+                               const uint64_t* first_draw_counters, int32_t use_target_kl, double target_kl, float* stats_out,
+                               void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
