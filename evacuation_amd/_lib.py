@@ -71,6 +71,40 @@ class EvacAdamState(C.Structure):
     _fields_ = [("header", C.c_void_p), ("exp_avg", EvacMlpPolicyGrads), ("exp_avg_sq", EvacMlpPolicyGrads)]
 
 
+class EvacLearnerHyper(C.Structure):
+    """evac_learner_hyper_t: one learner's float-valued hyperparameters (a host array [S] for the sweep entries)"""
+    _fields_ = [(f, C.c_double) for f in ("learning_rate", "target_kl", "gamma", "gae_lambda")] + [
+        (f, C.c_float) for f in ("clip_coef", "ent_coef", "vf_coef", "rpo_alpha", "max_grad_norm")] + [("use_target_kl", C.c_int32)]
+
+
+HYPER_DEFAULTS = {"learning_rate": 3e-4, "target_kl": None, "gamma": 0.99, "gae_lambda": 0.95, "clip_coef": 0.2, "ent_coef": 0.0,
+                  "vf_coef": 0.5, "rpo_alpha": 0.5, "max_grad_norm": 0.5}   # RPOTrainingConfig's
+
+
+def learner_hypers(n_learners: int, **columns):
+    """``evac_learner_hyper_t[n_learners]`` (a host array) from columns named as ``HYPER_DEFAULTS``: each one value for all
+    learners or a sequence of ``n_learners``; a ``target_kl`` of None means no target.  What is not given takes the default."""
+    n = int(n_learners)
+    unknown = set(columns) - set(HYPER_DEFAULTS)
+    if unknown:
+        raise ValueError(f"learner_hypers: unknown fields {sorted(unknown)}")
+    if not 1 <= n <= MAX_LEARNERS:
+        raise ValueError(f"learner_hypers: {n} learners; expected 1..{MAX_LEARNERS}")
+    out = (EvacLearnerHyper * n)()
+    for name, default in HYPER_DEFAULTS.items():
+        col = columns.get(name, default)
+        col = list(col) if isinstance(col, (list, tuple)) else [col] * n
+        if len(col) != n:
+            raise ValueError(f"learner_hypers: {name} has {len(col)} entries for {n} learners")
+        for s, v in enumerate(col):
+            if name == "target_kl":
+                out[s].use_target_kl = int(v is not None)
+                out[s].target_kl = float(v or 0.0)
+            else:
+                setattr(out[s], name, float(v))
+    return out
+
+
 class EvacError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"libevac error {code}: {msg}")
@@ -143,6 +177,17 @@ SIGNATURES = {
                                              C.POINTER(EvacAdamConfig), C.POINTER(EvacAdamState), C.c_int64, _P, _P, _P, _P, _P, _P,
                                              C.c_int64, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                              C.c_int32, C.c_double, _P, _P, _P]),
+    "evac_gae_learners": (C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.POINTER(EvacLearnerHyper),
+                                    _P, _P, _P]),
+    "evac_policy_rollout_sweep": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyStrides), C.c_int32,
+                                            _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float,
+                                            C.POINTER(EvacLearnerHyper), _P]),
+    "evac_rpo_update_sweep": (C.c_int, [C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacMlpPolicyGrads),
+                                        C.POINTER(EvacMlpPolicyStrides), C.POINTER(EvacMlpPolicyStrides),
+                                        C.POINTER(EvacMlpPolicyStrides), C.c_int64, C.POINTER(EvacRpoLossConfig),
+                                        C.POINTER(EvacAdamConfig), C.POINTER(EvacAdamState), C.c_int64, _P, _P, _P, _P, _P, _P,
+                                        C.c_int64, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                        C.POINTER(EvacLearnerHyper), _P, _P, _P]),
 }
 
 _lib = None

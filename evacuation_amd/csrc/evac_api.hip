@@ -1450,7 +1450,7 @@ static int policy_rollout(evac_handle_t h, const char* what, int32_t n_learners,
                           int32_t n_steps, const evac_mlp_policy_t* policy, float* next_obs, float* next_done, float* obs_out,
                           float* actions_out, float* logprob_out, float* value_out, float* reward_out, float* done_out,
                           float* next_value_out, evac_episode_stats_t* final_stats, double* norm_state, float gamma, float obs_clip,
-                          float reward_clip, float epsilon, void* stream) {
+                          float reward_clip, float epsilon, void* stream, const evac_learner_hyper_t* hypers = nullptr) {
     const std::string w = what;
     if (h->p.n_ped > evac::kWave)
         return fail(h, EVAC_ERR_UNSUPPORTED, w + ": rooms of more than 64 pedestrians are not supported (one wave per env)");
@@ -1483,6 +1483,9 @@ static int policy_rollout(evac_handle_t h, const char* what, int32_t n_learners,
         q.envs_per_learner = h->p.n_envs / n_learners;
         q.wgs = (q.envs_per_learner + evac::PolicyFamily::kEnvsPerBlock - 1) / evac::PolicyFamily::kEnvsPerBlock;
     }
+    evac::LearnerGammas lg{};
+    if (hypers)
+        for (int s = 0; s < n_learners; ++s) lg.gamma[s] = (float)hypers[s].gamma;
     // (parts / chained / persistent handles: joined first, then ONE kernel on `stream` over the whole batch)
     if (const int st = settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
     DeviceGuard g(h->device);
@@ -1493,6 +1496,14 @@ static int policy_rollout(evac_handle_t h, const char* what, int32_t n_learners,
     const evac::NormArgs na{norm_state, gamma, obs_clip, reward_clip, epsilon};
     const bool grav = h->p.obs_pos == EVAC_POS_GRAV, norm = norm_state != nullptr, def = h->default_cfg;
     const dim3 block(evac::PolicyFamily::kBlock);
+    if (strides && hypers && norm) {                   // (without the chain gamma does not enter collection)
+        using evac::k_collect_sweep;
+        void (*fn)(evac::Params, int, evac::PolicyArgs, evac::NormArgs, evac::PopulationArgs, evac::LearnerGammas) =
+            grav ? (def ? k_collect_sweep<true, true> : k_collect_sweep<true, false>)
+                 : (def ? k_collect_sweep<false, true> : k_collect_sweep<false, false>);
+        hipLaunchKernelGGL(fn, dim3((unsigned)(n_learners * q.wgs)), block, 0, (hipStream_t)stream, h->p, (int)n_steps, a, na, q, lg);
+        return check_launch(h, what);
+    }
     if (strides) {
         using evac::k_collect_population;
         void (*fn)(evac::Params, int, evac::PolicyArgs, evac::NormArgs, evac::PopulationArgs) =
@@ -1535,6 +1546,28 @@ int evac_policy_rollout_population(evac_handle_t h, int32_t n_learners, const ev
     return policy_rollout(h, "evac_policy_rollout_population", n_learners, strides, n_steps, policy, next_obs, next_done, obs_out,
                           actions_out, logprob_out, value_out, reward_out, done_out, next_value_out, final_stats, norm_state, gamma,
                           obs_clip, reward_clip, epsilon, stream);
+}
+
+static_assert(sizeof(evac::LearnerGammas) == EVAC_MAX_LEARNERS * sizeof(float), "evac::LearnerGammas holds EVAC_MAX_LEARNERS values");
+static_assert(sizeof(evac::Params) + 8 + sizeof(evac::PolicyArgs) + sizeof(evac::NormArgs) + sizeof(evac::PopulationArgs) +
+                      sizeof(evac::LearnerGammas) <= 4096, "k_collect_sweep: arguments beyond the kernel-argument segment");
+
+int evac_policy_rollout_sweep(evac_handle_t h, int32_t n_learners, const evac_mlp_policy_t* policy,
+                              const evac_mlp_policy_strides_t* strides, int32_t n_steps, float* next_obs, float* next_done,
+                              float* obs_out, float* actions_out, float* logprob_out, float* value_out, float* reward_out,
+                              float* done_out, float* next_value_out, evac_episode_stats_t* final_stats, double* norm_state,
+                              float gamma, float obs_clip, float reward_clip, float epsilon, const evac_learner_hyper_t* hypers,
+                              void* stream) {
+    EVAC_REQUIRE_BOUND(h, "evac_policy_rollout_sweep");
+    if (!strides) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout_sweep: strides is NULL");
+    if (n_learners < 1 || n_learners > EVAC_MAX_LEARNERS)
+        return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout_sweep: n_learners must be in 1.." + std::to_string(EVAC_MAX_LEARNERS));
+    if (!learner_hypers_ok(hypers, n_learners))
+        return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_rollout_sweep: hypers is NULL or a learner's values are refused "
+                                                  "(see evac_learner_hyper_t)");
+    return policy_rollout(h, "evac_policy_rollout_sweep", n_learners, strides, n_steps, policy, next_obs, next_done, obs_out,
+                          actions_out, logprob_out, value_out, reward_out, done_out, next_value_out, final_stats, norm_state, gamma,
+                          obs_clip, reward_clip, epsilon, stream, hypers);
 }
 
 // The double a caller wrote for a setting that evac_config_t holds as float32: the shortest decimal that rounds to the float

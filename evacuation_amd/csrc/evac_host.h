@@ -44,4 +44,18 @@ inline bool mlp_all_set(const T& set) {
     return true;
 }
 
+// evac_learner_hyper_t [n_learners] (include/evac.h), for every entry that takes one: what the lone entries refuse of the same
+// values, for every learner.  (!(x > 0) also refuses a NaN.)
+inline bool learner_hypers_ok(const evac_learner_hyper_t* hypers, int32_t n_learners) {
+    if (!hypers || n_learners < 1 || n_learners > EVAC_MAX_LEARNERS) return false;
+    const auto finite = [](double x) { return x - x == 0.0; };
+    for (int s = 0; s < n_learners; ++s) {
+        const evac_learner_hyper_t& y = hypers[s];
+        if (!finite(y.learning_rate) || !finite(y.gamma) || !finite(y.gae_lambda)) return false;
+        if (!(y.max_grad_norm > 0.0f) || !(y.clip_coef >= 0.0f) || !(y.rpo_alpha >= 0.0f)) return false;
+        if (y.use_target_kl && y.target_kl != y.target_kl) return false;
+    }
+    return true;
+}
+
 }  // namespace

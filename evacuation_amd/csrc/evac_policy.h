@@ -338,4 +338,24 @@ __global__ __launch_bounds__(PolicyFamily::kBlock, 4) void k_collect_population(
                                           (s + 1) * q.envs_per_learner);
 }
 
+// ---- ... with a NormalizeReward gamma per learner (include/evac.h: evac_policy_rollout_sweep) ----
+// The reference wraps a learner's env with its training gamma, so in a gamma sweep every learner's chain has its own.  The
+// values travel by value, indexed by the workgroup's learner (a scalar load from the kernel-argument segment); the body is
+// k_collect_population's.  Only with the chain does gamma enter collection, hence NORM = true alone.
+struct LearnerGammas {
+    float gamma[64];                            // (float)evac_learner_hyper_t.gamma of learner s; 64 = EVAC_MAX_LEARNERS
+};
+template <bool GRAV, bool DEF>
+__global__ __launch_bounds__(PolicyFamily::kBlock, 4) void k_collect_sweep(Params p, int n_steps, PolicyArgs a, NormArgs na,
+                                                                           PopulationArgs q, LearnerGammas lg) {
+    __shared__ PolicyFamily::Smem sm;
+    __shared__ PolicySmem<GRAV> ps;
+    if constexpr (DEF) p = default_config_constants<GRAV>(p);
+    const int s = (int)blockIdx.x / q.wgs;
+    const PolicyArgs la = learner_policy(a, q, s);
+    na.gamma = lg.gamma[s];
+    policy_rollout_body<GRAV, true, true>(sm, ps, p, n_steps, la, na, s * (q.envs_per_learner - q.wgs * PolicyFamily::kEnvsPerBlock),
+                                          (s + 1) * q.envs_per_learner);
+}
+
 }  // namespace evac

@@ -8,19 +8,13 @@
 #include <mutex>
 
 #include "evac_population.h"
-#include "evac_train_host.h"
+#include "evac_population_host.h"
 
 static_assert(evac::kMaxLearners == EVAC_MAX_LEARNERS, "evac::LearnerDraws holds EVAC_MAX_LEARNERS seeds and counters");
 static_assert(sizeof(evac::RpoArgs) + sizeof(evac::LearnerStrides) + sizeof(evac::LearnerDraws) + sizeof(void*) <= 4096,
               "the gradient kernels' arguments must fit the kernel-argument segment");
 
 namespace {
-constexpr int64_t kSliceAlign = 128;            // a learner's workspace slice starts on a cache line of its own
-
-int64_t slice_bytes(int32_t obs_dim, int64_t n_minibatch) {
-    const int64_t one = evac_rpo_workspace_bytes(obs_dim, n_minibatch);
-    return one < 0 ? one : (one + kSliceAlign - 1) / kSliceAlign * kSliceAlign;
-}
 // wide observations: more dynamic LDS than the default limit; once per device (as rpo_raise_lds)
 int raise_lds(int D, int dev) {
     if (evac::rpo_grad_lds_floats(D) * sizeof(float) <= 64 * 1024) return EVAC_OK;
@@ -38,17 +32,17 @@ int raise_lds(int D, int dev) {
     }
     return EVAC_OK;
 }
-// learner s + 1's tensor lies at least one tensor beyond learner s's (a stride of 0 would make the learners share it)
-bool strides_ok(const evac_mlp_policy_strides_t* st, int32_t obs_dim, int32_t n_learners, int64_t* out) {
-    const int64_t H = evac::kTrainHidden, D = obs_dim;
-    const int64_t least[kMlpTensors] = {H * D, H, H * H, H, 2 * H, 2, 2, H * D, H, H * H, H, H, 1};
-    for (int i = 0; i < kMlpTensors; ++i) {
-        out[i] = (&st->actor_w1)[i];
-        if (n_learners > 1 && out[i] < least[i]) return false;
-    }
-    return true;
-}
 }  // namespace
+
+namespace evac {
+void population_launch_begin(AdamHeader* hdr, int64_t header_stride_bytes, int n_learners, hipStream_t stream) {
+    hipLaunchKernelGGL(k_population_begin, dim3(1), dim3(kMaxLearners), 0, stream, hdr, header_stride_bytes, n_learners);
+}
+void population_launch_adv_stats(const RpoArgs& a, const LearnerStrides& q, const LearnerDraws& d, const AdamHeader* gate,
+                                 int n_learners, hipStream_t stream) {
+    hipLaunchKernelGGL(k_population_adv_stats, dim3(1, (unsigned)n_learners), dim3(kFinishBlock), 0, stream, a, q, d, gate);
+}
+}  // namespace evac
 
 extern "C" {
 
@@ -67,36 +61,16 @@ int evac_rpo_update_population(int32_t n_learners, const evac_mlp_policy_t* poli
                                int64_t learner_batch_size, int64_t n_minibatch, int32_t n_epochs, const int64_t* perms,
                                const float* rpo_noise, const uint64_t* seeds, const uint64_t* first_draw_counters,
                                int32_t use_target_kl, double target_kl, float* stats_out, void* workspace, void* stream) {
-    if (n_learners < 1 || n_learners > EVAC_MAX_LEARNERS || n_epochs < 1 || learner_batch_size < 1) return EVAC_ERR_INVALID_ARGUMENT;
-    if (!param_strides || !grad_strides || !moment_strides || !seeds || !first_draw_counters) return EVAC_ERR_INVALID_ARGUMENT;
     evac::RpoArgs a;
-    int rc = rpo_prepare(policy, loss_cfg, batch_size, b_obs, b_actions, b_logprobs, b_advantages, b_returns, b_values, n_minibatch,
-                         perms, rpo_noise, 0, grads, stats_out, workspace, a);
-    if (rc != EVAC_OK) return rc;
     evac::AdamArgs o;
-    rc = adam_prepare(params, grads, state, adam_cfg, policy->obs_dim, o);
+    evac::LearnerStrides q;
+    evac::LearnerDraws d;
+    const int rc = population_prepare(n_learners, policy, params, grads, param_strides, grad_strides, moment_strides, header_stride_bytes,
+                                      loss_cfg, adam_cfg, state, batch_size, b_obs, b_actions, b_logprobs, b_advantages, b_returns,
+                                      b_values, learner_batch_size, n_minibatch, n_epochs, perms, rpo_noise, seeds, first_draw_counters,
+                                      stats_out, workspace, a, o, q, d);
     if (rc != EVAC_OK) return rc;
-    evac::LearnerStrides q{};
-    if (!strides_ok(param_strides, a.D, n_learners, q.p) || !strides_ok(grad_strides, a.D, n_learners, q.g) ||
-        !strides_ok(moment_strides, a.D, n_learners, q.m))
-        return EVAC_ERR_INVALID_ARGUMENT;
-    if (n_learners > 1 && (header_stride_bytes < (int64_t)sizeof(evac::AdamHeader) || (header_stride_bytes & 7) != 0))
-        return EVAC_ERR_INVALID_ARGUMENT;
     const int64_t B = learner_batch_size, M = n_minibatch, least = a.norm_adv ? 2 : 1;
-    int64_t steps = 0;                                 // of one learner, in the whole call
-    for (int64_t start = 0; start < B; start += M) steps += (B - start < M ? B - start : M) >= least;
-    steps *= n_epochs;
-    q.hdr = header_stride_bytes;
-    q.ws = slice_bytes(a.D, M);
-    q.inds = (int64_t)n_epochs * B;
-    q.stats = steps * 8;
-    q.noise = steps * M * 2;
-    evac::LearnerDraws d{};
-    for (int s = 0; s < n_learners; ++s) {
-        d.seed[s] = seeds[s];
-        d.first_counter[s] = first_draw_counters[s];
-    }
-    o.gated = 1;
     o.use_target_kl = use_target_kl != 0;
     o.target_kl = target_kl;
     const int dev = device_of(workspace);
@@ -104,7 +78,7 @@ int evac_rpo_update_population(int32_t n_learners, const evac_mlp_policy_t* poli
     if (raise_lds(a.D, dev) != EVAC_OK) return EVAC_ERR_HIP;
     hipStream_t S = (hipStream_t)stream;
     const unsigned L = (unsigned)n_learners;
-    hipLaunchKernelGGL(evac::k_population_begin, dim3(1), dim3(evac::kMaxLearners), 0, S, o.hdr, header_stride_bytes, n_learners);
+    evac::population_launch_begin(o.hdr, header_stride_bytes, n_learners, S);
     const size_t lds = evac::rpo_grad_lds_floats(a.D) * sizeof(float);
     const int tiles = (a.D + evac::kW1Tile - 1) / evac::kW1Tile;
     uint64_t k = 0;
@@ -121,7 +95,7 @@ int evac_rpo_update_population(int32_t n_learners, const evac_mlp_policy_t* poli
             o.stats = a.stats;
             o.epoch_last = m_next < least;
             const evac::AdamHeader* gate = o.hdr;
-            if (a.norm_adv) hipLaunchKernelGGL(evac::k_population_adv_stats, dim3(1, L), dim3(evac::kFinishBlock), 0, S, a, q, d, gate);
+            if (a.norm_adv) evac::population_launch_adv_stats(a, q, d, gate, n_learners, S);
             hipLaunchKernelGGL(evac::k_population_grad, dim3((unsigned)a.P, 2u, L), dim3(evac::kGradBlock), lds, S, a, q, d, gate);
             hipLaunchKernelGGL(evac::k_population_finish, dim3((unsigned)(2 * evac::kFinishCombineWgs + 2 * tiles * a.S), L),
                                dim3(evac::kFinishBlock), 0, S, a, q, d, gate);

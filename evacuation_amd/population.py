@@ -1,4 +1,4 @@
-"""Population training: S independent RPO learners of ONE configuration in one set of launches.
+"""Population training: S independent RPO learners in one set of launches, of one configuration or one each.
 
 What the reference's users run is a sweep -- ``for sweep in 1 .. 10`` independent training processes per setting
 (run_scripts/run_article_sweeps-*.sh).  At the reference's shape (3 envs x 2048 steps, minibatches of 192) one learner's
@@ -13,13 +13,20 @@ update is a chain of small launches on a nearly idle chip; here learner s rides 
 * ``rpo_update_population``: every learner's epochs and minibatches in one host call, four launches per minibatch step as for
   one learner (``evac_rpo_update_population``).
 * ``PopulationTrainer``: one iteration of the reference's loop for all learners per ``update()``.
+* Sweeps: every float-valued hyperparameter (``SWEEP_FIELDS``) may differ per learner -- ``PopulationTrainer(env, population,
+  [cfg_0, .., cfg_S-1])``, ``rpo_update_population(cfg=[...])``, ``gae(gamma=[...])``, ``policy_rollout_population(gammas=[...])``;
+  ``sweep_configs`` makes the cartesian product.  The learners' values ride in the kernel arguments beside their seeds
+  (``evac_rpo_update_sweep``, ``evac_gae_learners``, ``evac_policy_rollout_sweep``).  What fixes launch geometry, step counts
+  or storage shape (``STRUCTURAL_FIELDS``) stays one value for all.
 
 Learner s is BIT FOR BIT the ``RPOTrainer(optimizer="device", one_call=True)`` it would be alone on an env of ``E_l`` envs with the
-population env's seed and ``env_id_offset`` further by ``s E_l``, with ``cfg.seed = seeds[s]`` and the same reset state.  One
-configuration per population: no per-learner hyperparameters or env settings."""
+population env's seed and ``env_id_offset`` further by ``s E_l``, with its own configuration, ``cfg.seed = seeds[s]`` and the
+same reset state (wrapped, for a gamma sweep, with its own gamma).  Env settings are per population."""
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
+import itertools
 import time
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
@@ -33,6 +40,51 @@ from .trainer import (BATCH_KEYS, DeviceAdam, RPOTrainingConfig, _f32, _loss_con
 from .vector_env import STATS_FIELDS, _ptr
 
 MAX_LEARNERS = _lib.MAX_LEARNERS
+# what may differ between the learners of one population, and what may not (launch geometry, step counts, storage shape)
+SWEEP_FIELDS = ("learning_rate", "anneal_lr", "gamma", "gae_lambda", "clip_coef", "ent_coef", "vf_coef", "rpo_alpha", "max_grad_norm",
+                "target_kl")
+STRUCTURAL_FIELDS = ("num_envs", "num_steps", "total_timesteps", "num_minibatches", "update_epochs", "norm_adv", "clip_vloss")
+
+
+def _per_learner(value, n: int, name: str) -> list:
+    """One value for all learners, or a sequence of ``n``."""
+    if isinstance(value, (list, tuple)):
+        if len(value) != n:
+            raise ValueError(f"{name}: {len(value)} entries for {n} learners")
+        return list(value)
+    return [value] * n
+
+
+def check_structure(cfgs: Sequence, what: str = "configuration") -> None:
+    """Every learner's structural fields are learner 0's, or a ``ValueError`` naming the field and the learner."""
+    for s, c in enumerate(cfgs):
+        for f in STRUCTURAL_FIELDS:
+            if getattr(c, f, None) != getattr(cfgs[0], f, None):
+                raise ValueError(f"{what}: {f} = {getattr(c, f, None)!r} of learner {s} differs from learner 0's "
+                                 f"{getattr(cfgs[0], f, None)!r}; {f} fixes the launches' shape and is one value per population")
+
+
+def sweep_configs(base: RPOTrainingConfig, grid: Dict[str, Sequence], seeds: Optional[Sequence[int]] = None) -> list:
+    """The cartesian product of ``grid`` (field of ``RPOTrainingConfig`` -> its values) over ``seeds`` (default: ``base.seed``)
+    as a list of ``(seed, cfg)``, ``cfg = replace(base, seed=seed, **setting)``: the first field varies slowest, the seeds
+    fastest (a setting's seeds are neighbours).  ``ValueError`` for an unknown field or more than ``MAX_LEARNERS`` learners."""
+    names = {f.name for f in dataclasses.fields(base)}
+    for f, values in grid.items():
+        if f not in names or f == "seed":
+            raise ValueError(f"sweep_configs: {f!r} is not a field of {type(base).__name__} to sweep")
+        if len(values) < 1:
+            raise ValueError(f"sweep_configs: no values for {f!r}")
+    seeds = [int(base.seed)] if seeds is None else [int(s) for s in seeds]
+    n = len(seeds)
+    for values in grid.values():
+        n *= len(values)
+    if not 1 <= n <= MAX_LEARNERS:
+        raise ValueError(f"sweep_configs: {n} learners; a population holds 1..{MAX_LEARNERS}")
+    out = []
+    for setting in itertools.product(*grid.values()):
+        for seed in seeds:
+            out.append((seed, dataclasses.replace(base, seed=seed, **dict(zip(grid, setting)))))
+    return out
 
 
 def population_rows(inds: torch.Tensor, learner, envs_per_learner: int, num_learners: int) -> torch.Tensor:
@@ -85,27 +137,49 @@ class PolicyPopulation:
 
 class PopulationAdam:
     """``DeviceAdam`` for every learner of ``population``: the moments stacked ``[S, ...]``, ``headers`` ``[S, 8]`` (64 bytes a
-    learner).  One ``param_groups[0]`` for all (one configuration per population).  ``learners[s]`` is a ``DeviceAdam`` whose
-    state is row s: ``state_dict(s)`` / ``load_state_dict(s, sd)`` are its, in ``DeviceAdam``'s format."""
+    learner).  ``learners[s]`` is a ``DeviceAdam`` whose state is row s and whose ``param_groups`` are its own: ``lr`` and
+    ``max_grad_norm`` (one value or a sequence of S) may differ per learner, the betas and eps are one value for all.
+    ``param_groups[s]`` is learner s's group; ``state_dict(s)`` / ``load_state_dict(s, sd)`` are its, in ``DeviceAdam``'s
+    format, and touch no other learner."""
 
-    def __init__(self, population: PolicyPopulation, lr: float = 3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5,
-                 max_grad_norm: float = 0.5):
+    def __init__(self, population: PolicyPopulation, lr=3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5,
+                 max_grad_norm=0.5):
         self.population = population
         S, dev = population.num_learners, population.device
+        lrs, norms = _per_learner(lr, S, "lr"), _per_learner(max_grad_norm, S, "max_grad_norm")
         self.headers = torch.zeros(S, 8, dtype=torch.int64, device=dev)
         self.exp_avg = [torch.zeros_like(t) for t in population.tensors]
         self.exp_avg_sq = [torch.zeros_like(t) for t in population.tensors]
-        self.learners = [DeviceAdam(net, lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm,
+        self.learners = [DeviceAdam(net, lr=lrs[s], betas=betas, eps=eps, max_grad_norm=norms[s],
                                     storage=(self.headers[s], [m[s] for m in self.exp_avg], [v[s] for v in self.exp_avg_sq]))
                          for s, net in enumerate(population.nets)]
-        self.param_groups = self.learners[0].param_groups
-        for opt in self.learners[1:]:
-            opt.param_groups = self.param_groups
         self.header_stride_bytes = 64
         self.moment_strides = population.strides
 
-    def config(self) -> "_lib.EvacAdamConfig":
-        return self.learners[0].config()
+    @property
+    def param_groups(self) -> List[dict]:
+        """Learner s's group at index s (read at every call, as ``DeviceAdam.param_groups[0]``)."""
+        return [opt.param_groups[0] for opt in self.learners]
+
+    def set_lr(self, lr) -> None:
+        """``lr``: one value for all learners or a sequence of S."""
+        for opt, x in zip(self.learners, _per_learner(lr, len(self.learners), "lr")):
+            opt.param_groups[0]["lr"] = float(x)
+
+    def uniform(self) -> bool:
+        """Every learner's ``lr`` and ``max_grad_norm`` are learner 0's."""
+        g0 = self.learners[0].param_groups[0]
+        return all(o.param_groups[0]["lr"] == g0["lr"] and o.param_groups[0]["max_grad_norm"] == g0["max_grad_norm"]
+                   for o in self.learners)
+
+    def config(self, learner: int = 0) -> "_lib.EvacAdamConfig":
+        """``evac_adam_config_t`` of one learner.  The betas and eps are shared by all: a learner whose differ is an error."""
+        g0 = self.learners[0].param_groups[0]
+        for s, opt in enumerate(self.learners):
+            g = opt.param_groups[0]
+            if tuple(g["betas"]) != tuple(g0["betas"]) or g["eps"] != g0["eps"]:
+                raise ValueError(f"PopulationAdam: betas / eps of learner {s} differ from learner 0's; they are one value per population")
+        return self.learners[learner].config()
 
     def read_headers(self) -> List[dict]:
         host = self.headers.cpu()
@@ -135,6 +209,19 @@ def population_workspace_bytes(obs_dim: int, minibatch_size: int, num_learners: 
     return need
 
 
+def learner_hypers(cfgs: Sequence, opt: Optional[PopulationAdam] = None):
+    """``evac_learner_hyper_t[S]`` of the configurations; with ``opt`` the learning rate and ``max_grad_norm`` are the
+    optimiser's (``opt.learners[s].param_groups[0]``: the annealed rate), as ``rpo_update`` takes them from its ``DeviceAdam``."""
+    S = len(cfgs)
+    col = lambda f, default: [getattr(c, f, default) for c in cfgs]
+    groups = None if opt is None else opt.param_groups
+    return _lib.learner_hypers(
+        S, learning_rate=col("learning_rate", 3e-4) if groups is None else [g["lr"] for g in groups],
+        max_grad_norm=col("max_grad_norm", 0.5) if groups is None else [g["max_grad_norm"] for g in groups],
+        target_kl=col("target_kl", None), gamma=col("gamma", 0.99), gae_lambda=col("gae_lambda", 0.95), clip_coef=col("clip_coef", 0.2),
+        ent_coef=col("ent_coef", 0.0), vf_coef=col("vf_coef", 0.5), rpo_alpha=col("rpo_alpha", 0.5))
+
+
 def rpo_update_population(population: PolicyPopulation, batch: Dict[str, torch.Tensor], rows: torch.Tensor, cfg, opt: PopulationAdam, *,
                           minibatch_size: Optional[int] = None, rpo_noise: Optional[torch.Tensor] = None,
                           seeds: Optional[Sequence[int]] = None, first_draw_counters: Optional[Sequence[int]] = None,
@@ -144,10 +231,27 @@ def rpo_update_population(population: PolicyPopulation, batch: Dict[str, torch.T
     common batch in the order the learner visits them (``population_rows`` of its permutation of ``[0, B_l)``).  Learner s draws
     its RPO perturbation from Philox keyed ``seeds[s]`` (default ``population.seeds``) at ``first_draw_counters[s] + k`` for step
     k, or reads ``rpo_noise[s, k]`` (``[S, steps, M, 2]``).  Returns (``stats`` ``[S, steps, 8]``, ``opt.headers``); rows beyond a
-    learner's ``steps_run`` keep what they held.  No host synchronisation; four launches per minibatch step."""
+    learner's ``steps_run`` keep what they held.  No host synchronisation; four launches per minibatch step.
+    ``cfg``: one configuration, or a sequence of S (``evac_rpo_update_sweep``): learner s's loss runs with ``cfg[s]``'s
+    ``clip_coef`` / ``ent_coef`` / ``vf_coef`` / ``rpo_alpha`` / ``target_kl`` and its optimiser with
+    ``opt.learners[s].param_groups[0]``'s ``lr`` / ``max_grad_norm``, bit for bit ``rpo_update(..., cfg[s], DeviceAdam(lr, ...))``
+    alone; ``norm_adv``, ``clip_vloss`` and the minibatch size are learner 0's and must be everybody's.  With one ``cfg`` the
+    optimiser's per-learner values are honoured in the same way."""
     if opt.population is not population:
         raise ValueError("the PopulationAdam was made for another population")
     S, dev = population.num_learners, population.device
+    cfgs = None
+    if isinstance(cfg, (list, tuple)):
+        cfgs = list(cfg)
+        if len(cfgs) != S:
+            raise ValueError(f"rpo_update_population: {len(cfgs)} configurations for {S} learners")
+        for s, c in enumerate(cfgs):
+            for f in ("norm_adv", "clip_vloss") + (("minibatch_size",) if minibatch_size is None else ()):
+                if getattr(c, f, True) != getattr(cfgs[0], f, True):
+                    raise ValueError(f"rpo_update_population: {f} of learner {s} differs from learner 0's")
+        cfg = cfgs[0]
+    elif not opt.uniform():
+        cfgs = [cfg] * S
     B, D, b_args = _batch_ptrs(batch)
     if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int64 or rows.device != batch["b_obs"].device or \
             not rows.is_contiguous() or rows.dim() != 3 or rows.shape[0] != S or rows.shape[1] < 1 or rows.shape[2] < 1:
@@ -180,31 +284,50 @@ def rpo_update_population(population: PolicyPopulation, batch: Dict[str, torch.T
     grads = _lib.EvacMlpPolicyGrads(*(g.data_ptr() for g in population.grads))
     target_kl = getattr(cfg, "target_kl", None)
     lc, oc = _loss_config(cfg), opt.config()
-    rc = _lib.load().evac_rpo_update_population(
-        S, C.byref(pol), C.byref(params), C.byref(grads), C.byref(population.strides), C.byref(population.strides),
-        C.byref(opt.moment_strides), opt.header_stride_bytes, C.byref(lc), C.byref(oc), C.byref(opt.learners[0].state_struct()), *b_args,
-        B_l, M, n_epochs, _ptr(rows), _ptr(rpo_noise), u64(*(_u64(x) for x in seeds)), u64(*(_u64(x) for x in counters)),
-        int(target_kl is not None), float(target_kl or 0.0), _ptr(stats), _ptr(workspace), _stream(dev))
+    head = [S, C.byref(pol), C.byref(params), C.byref(grads), C.byref(population.strides), C.byref(population.strides),
+            C.byref(opt.moment_strides), opt.header_stride_bytes, C.byref(lc), C.byref(oc), C.byref(opt.learners[0].state_struct()), *b_args,
+            B_l, M, n_epochs, _ptr(rows), _ptr(rpo_noise), u64(*(_u64(x) for x in seeds)), u64(*(_u64(x) for x in counters))]
+    tail = [_ptr(stats), _ptr(workspace), _stream(dev)]
+    if cfgs is None:
+        rc = _lib.load().evac_rpo_update_population(*head, int(target_kl is not None), float(target_kl or 0.0), *tail)
+    else:
+        rc = _lib.load().evac_rpo_update_sweep(*head, learner_hypers(cfgs, opt), *tail)
     _lib.check(rc)
     return stats, opt.headers
 
 
 class PopulationTrainer:
     """``RPOTrainer(optimizer="device", one_call=True)`` for every learner of ``population`` at once.  ``env``: a
-    ``NormalizedVectorEnv`` or ``BatchedEvacuationEnv`` of ``S x cfg.num_envs`` envs (learner s owns the s-th share); ``cfg``: ONE
-    configuration for all, ``cfg.seed`` unused -- learner s's permutations come from a generator seeded ``population.seeds[s]`` and
-    its RPO perturbation from Philox keyed with the same seed.  ``update()``: anneal, one collection launch, one ``gae``, the
-    permutations, one ``rpo_update_population``, ONE host transfer; returns a list of S logs with ``RPOTrainer.update()``'s keys."""
+    ``NormalizedVectorEnv`` or ``BatchedEvacuationEnv`` of ``S x cfg.num_envs`` envs (learner s owns the s-th share); ``cfgs``: ONE
+    configuration for all, or a sequence of S that may differ in ``SWEEP_FIELDS`` (a differing ``STRUCTURAL_FIELDS`` entry is a
+    ``ValueError``); ``seed`` unused -- learner s's permutations come from a generator seeded ``population.seeds[s]`` and
+    its RPO perturbation from Philox keyed with the same seed.  With a sequence learner s anneals its own rate, its reward
+    normaliser runs with its own gamma (whatever the env was wrapped with) and its advantages, loss, clip and ``target_kl`` are
+    its own.  ``update()``: anneal, one collection launch, one ``gae``, the permutations, one ``rpo_update_population``, ONE host
+    transfer; returns a list of S logs with ``RPOTrainer.update()``'s keys, ``learning_rate`` the learner's own and ``config``
+    its fields that differ from learner 0's."""
 
-    def __init__(self, env, population: PolicyPopulation, cfg: RPOTrainingConfig):
-        cfg.check()
+    def __init__(self, env, population: PolicyPopulation, cfgs):
         S = population.num_learners
+        self.sweep = isinstance(cfgs, (list, tuple))
+        if self.sweep:
+            self.cfgs = list(cfgs)
+            if len(self.cfgs) != S:
+                raise ValueError(f"PopulationTrainer: {len(self.cfgs)} configurations for {S} learners")
+            for c in self.cfgs:
+                c.check()
+            check_structure(self.cfgs, "PopulationTrainer")
+        else:
+            cfgs.check()
+            self.cfgs = [cfgs] * S
+        cfg = self.cfgs[0]
         if env.num_envs != S * cfg.num_envs:
             raise ValueError(f"PopulationTrainer: the env has {env.num_envs} envs; {S} learners x cfg.num_envs = {S * cfg.num_envs}")
         self.env, self.population, self.cfg = env, population, cfg
         self.nets, self.device = population.nets, population.device
         self.num_learners, self.envs_per_learner = S, int(cfg.num_envs)
-        self.optimizer = PopulationAdam(population, lr=cfg.learning_rate, eps=1e-5, max_grad_norm=cfg.max_grad_norm)
+        self.optimizer = PopulationAdam(population, lr=[c.learning_rate for c in self.cfgs], eps=1e-5,
+                                        max_grad_norm=[c.max_grad_norm for c in self.cfgs])
         self.generators = []
         for seed in population.seeds:
             g = torch.Generator(device=self.device)
@@ -234,18 +357,24 @@ class PopulationTrainer:
         if self.start_time is None:
             self.start_time = time.time()
         with torch.no_grad():
+            kw = {"gammas": [c.gamma for c in self.cfgs]} if self.sweep else {}
             self.storage = self.env.policy_rollout_population(self.population, self.cfg.num_steps, self.next_obs, self.next_done,
-                                                              out=self.storage)
+                                                              out=self.storage, **kw)
             out = None if self.advantages is None else (self.advantages, self.returns)
-            self.advantages, self.returns = gae(self.storage, self.cfg.gamma, self.cfg.gae_lambda, out=out)
+            if self.sweep:
+                self.advantages, self.returns = gae(self.storage, [c.gamma for c in self.cfgs], [c.gae_lambda for c in self.cfgs],
+                                                    out=out, envs_per_learner=self.envs_per_learner)
+            else:
+                self.advantages, self.returns = gae(self.storage, self.cfg.gamma, self.cfg.gae_lambda, out=out)
         self.global_step += self.cfg.batch_size
         return self.storage
 
     def update(self) -> List[dict]:
         cfg, S, E_l = self.cfg, self.num_learners, self.envs_per_learner
-        if cfg.anneal_lr:
-            frac = 1.0 - self.update_index / max(1, cfg.num_updates)
-            self.optimizer.param_groups[0]["lr"] = frac * cfg.learning_rate
+        frac = 1.0 - self.update_index / max(1, cfg.num_updates)
+        for c, opt in zip(self.cfgs, self.optimizer.learners):        # (every learner anneals its own rate, or does not)
+            if c.anneal_lr:
+                opt.param_groups[0]["lr"] = frac * c.learning_rate
         storage = self.collect()
         batch = flatten_batch(storage, self.advantages, self.returns)
         B_l, T = cfg.batch_size, cfg.num_steps
@@ -259,7 +388,7 @@ class PopulationTrainer:
         need = population_workspace_bytes(self.population.obs_dim, min(cfg.minibatch_size, B_l), S)
         if self.workspace is None or self.workspace.numel() < need:
             self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        stats, headers = rpo_update_population(self.population, batch, rows, cfg, self.optimizer,
+        stats, headers = rpo_update_population(self.population, batch, rows, self.cfgs if self.sweep else cfg, self.optimizer,
                                                first_draw_counters=self.minibatch_steps, stats=self.stats_rows,
                                                workspace=self.workspace)
         self.update_index += 1
@@ -278,7 +407,8 @@ class PopulationTrainer:
         done = storage["dones"][1:].bool()
         ended = torch.cat([done, storage["next_done"].bool()[None]], dim=0)
         sps = int(self.global_step / max(time.time() - self.start_time, 1e-9))
-        lr = self.optimizer.param_groups[0]["lr"]
+        lrs = [g["lr"] for g in self.optimizer.param_groups]
+        differs = [{f: getattr(c, f) for f in SWEEP_FIELDS if getattr(c, f) != getattr(cfg, f)} for c in self.cfgs]
         logs = []
         for s in range(S):
             h = decode_header(hdr[s])
@@ -288,11 +418,11 @@ class PopulationTrainer:
             cols = slice(s * E_l, (s + 1) * E_l)
             recs = es[:, cols][ended[:, cols]]
             ev, var_y = float(tail[s]), float(tail[S + s])
-            logs.append({"update": self.update_index, "global_step": self.global_step, "learning_rate": lr, "value_loss": last[2],
+            logs.append({"update": self.update_index, "global_step": self.global_step, "learning_rate": lrs[s], "value_loss": last[2],
                          "policy_loss": last[1], "entropy": last[3], "old_approx_kl": last[4], "approx_kl": last[5],
                          "clipfrac": clipfrac, "explained_variance": float("nan") if var_y == 0 else ev, "loss": last[0], "SPS": sps,
                          "episodes": {k: recs[:, i] for i, k in enumerate(STATS_FIELDS)}, "learner": s,
-                         "seed": self.population.seeds[s], "steps_run": ran, "epochs_run": h["epochs_run"]})
+                         "seed": self.population.seeds[s], "steps_run": ran, "epochs_run": h["epochs_run"], "config": differs[s]})
         return logs
 
     def make_evaluator(self, num_envs: Optional[int] = None):

@@ -89,9 +89,11 @@ def _f32(t: torch.Tensor, shape, name: str) -> torch.Tensor:
     return t
 
 
-def gae(storage: Dict[str, torch.Tensor], gamma: float, gae_lambda: float, out=None):
+def gae(storage: Dict[str, torch.Tensor], gamma, gae_lambda, out=None, *, envs_per_learner: Optional[int] = None):
     """Advantages and returns [T, E] of the storage ``policy_rollout`` returns (rpo_agent.py:205-220), one launch, bit-equal to
-    the reference's loop in float32.  ``out`` = (advantages, returns) to reuse."""
+    the reference's loop in float32.  ``out`` = (advantages, returns) to reuse.  For a population's storage ``gamma`` and
+    ``gae_lambda`` may be sequences of S with ``envs_per_learner = E / S``: learner s's columns take its own pair
+    (``evac_gae_learners``), bit-equal to ``gae`` on those columns alone."""
     rewards = storage["rewards"]
     T, E = rewards.shape
     rewards = _f32(rewards, (T, E), "rewards")
@@ -100,8 +102,17 @@ def gae(storage: Dict[str, torch.Tensor], gamma: float, gae_lambda: float, out=N
     if out is None:
         out = (torch.empty_like(rewards), torch.empty_like(rewards))
     adv, ret = _f32(out[0], (T, E), "advantages"), _f32(out[1], (T, E), "returns")
-    rc = _lib.load().evac_gae(T, E, _ptr(rewards), _ptr(values), _ptr(dones), _ptr(next_value), _ptr(next_done), float(gamma),
-                              float(gae_lambda), _ptr(adv), _ptr(ret), _stream(rewards.device))
+    per_learner = isinstance(gamma, (list, tuple)) or isinstance(gae_lambda, (list, tuple))
+    if per_learner or envs_per_learner is not None:
+        if envs_per_learner is None or int(envs_per_learner) < 1 or E % int(envs_per_learner):
+            raise ValueError(f"gae: per-learner gamma / gae_lambda need envs_per_learner, a divisor of the storage's {E} envs")
+        S = E // int(envs_per_learner)
+        hypers = _lib.learner_hypers(S, gamma=gamma, gae_lambda=gae_lambda)
+        rc = _lib.load().evac_gae_learners(T, E, _ptr(rewards), _ptr(values), _ptr(dones), _ptr(next_value), _ptr(next_done),
+                                           int(envs_per_learner), S, hypers, _ptr(adv), _ptr(ret), _stream(rewards.device))
+    else:
+        rc = _lib.load().evac_gae(T, E, _ptr(rewards), _ptr(values), _ptr(dones), _ptr(next_value), _ptr(next_done), float(gamma),
+                                  float(gae_lambda), _ptr(adv), _ptr(ret), _stream(rewards.device))
     _lib.check(rc)
     return adv, ret
 

@@ -588,17 +588,20 @@ class BatchedEvacuationEnv:
         return self._policy_rollout(net, None, n_steps, next_obs, next_done, out, _norm)
 
     def policy_rollout_population(self, population, n_steps: int, next_obs: torch.Tensor, next_done: torch.Tensor,
-                                  out: Optional[TDict] = None, _norm=None):
+                                  out: Optional[TDict] = None, _norm=None, gammas=None):
         """``policy_rollout`` for the S learners of ``population`` (a ``PolicyPopulation``) in ONE launch
         (``evac_policy_rollout_population``): learner s acts in envs ``[s E_l, (s + 1) E_l)`` of this env, ``E_l = num_envs / S``.
         Arguments and storage are ``policy_rollout``'s, over the whole batch; learner s's columns hold, bit for bit, what
         ``policy_rollout(population.nets[s], ...)`` writes on an env of ``E_l`` envs with the same seed, ``env_id_offset`` further
-        by ``s E_l`` and the same start state."""
+        by ``s E_l`` and the same start state.  ``gammas``: the learners' training gammas (a sequence of S).  Gamma enters
+        collection through the reward normaliser alone, so on this raw env ``gammas`` is accepted (and checked) and has no effect;
+        ``NormalizedVectorEnv.policy_rollout_population`` runs learner s's chain with ``gammas[s]``."""
         if self.num_envs % population.num_learners:
             raise ValueError(f"policy_rollout_population: {self.num_envs} envs are not {population.num_learners} learners' equal shares")
-        return self._policy_rollout(population.nets[0], population, n_steps, next_obs, next_done, out, _norm)
+        hypers = None if gammas is None else _lib.learner_hypers(population.num_learners, gamma=[float(g) for g in gammas])
+        return self._policy_rollout(population.nets[0], population, n_steps, next_obs, next_done, out, _norm, hypers)
 
-    def _policy_rollout(self, net, population, n_steps, next_obs, next_done, out, _norm):
+    def _policy_rollout(self, net, population, n_steps, next_obs, next_done, out, _norm, hypers=None):
         from .policy import MAX_PEDESTRIANS, PolicyBinder
         if self.n_ped > MAX_PEDESTRIANS:
             raise NotImplementedError(f"policy_rollout runs one wave per env: rooms of at most {MAX_PEDESTRIANS} pedestrians "
@@ -626,6 +629,9 @@ class BatchedEvacuationEnv:
                 obs_clip, reward_clip, eps, self._stream()]
         if population is None:
             rc = self.lib.evac_policy_rollout(self._h, T, C.byref(pol), *args)
+        elif hypers is not None:
+            rc = self.lib.evac_policy_rollout_sweep(self._h, population.num_learners, C.byref(pol), C.byref(population.strides), T,
+                                                    *args[:-1], hypers, args[-1])
         else:
             rc = self.lib.evac_policy_rollout_population(self._h, population.num_learners, C.byref(pol), C.byref(population.strides),
                                                          T, *args)

@@ -68,9 +68,11 @@ class NormalizedVectorEnv:
         return self.env.policy_rollout(net, n_steps, next_obs, next_done, out=out,
                                        _norm=(self.norm_state, self.gamma, self.obs_clip, self.reward_clip, self.epsilon))
 
-    def policy_rollout_population(self, population, n_steps: int, next_obs, next_done, out=None):
-        """``BatchedEvacuationEnv.policy_rollout_population`` through the trainer's chain (as ``policy_rollout``)."""
-        return self.env.policy_rollout_population(population, n_steps, next_obs, next_done, out=out,
+    def policy_rollout_population(self, population, n_steps: int, next_obs, next_done, out=None, gammas=None):
+        """``BatchedEvacuationEnv.policy_rollout_population`` through the trainer's chain (as ``policy_rollout``).  ``gammas``: a
+        sequence of S -- learner s's reward normaliser runs with ``gammas[s]`` in place of this env's ``gamma``, as the
+        reference's ``wrapping(env, gamma)`` gives every learner of a gamma sweep its own (``evac_policy_rollout_sweep``)."""
+        return self.env.policy_rollout_population(population, n_steps, next_obs, next_done, out=out, gammas=gammas,
                                                   _norm=(self.norm_state, self.gamma, self.obs_clip, self.reward_clip, self.epsilon))
 
     def policy_evaluate(self, agent, n_episodes: int, max_steps: int, progress=None, out=None, *, deterministic: bool = True):

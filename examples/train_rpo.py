@@ -8,6 +8,7 @@ minibatches in one host call (``evac_rpo_update``).  Prints the reference's ``SP
 
     python examples/train_rpo.py [--envs 4096] [--steps 128] [--updates 5] [--pedestrians 60] [--optimizer device]
                                  [--eval-every 1] [--eval-episodes 1] [--baseline] [--seeds 1,2,3]
+                                 [--sweep learning_rate=1e-4,3e-4,1e-3 --sweep ent_coef=0,0.01]
 
 ``--eval-every K`` evaluates the leader every K updates (``RPOTrainer.evaluate``: whole episodes, the mean action, the observation
 statistics frozen) and prints the summary; ``--baseline`` prints the same line for the reference's scripted sweep baseline
@@ -17,6 +18,13 @@ statistics frozen) and prints the summary; ``--baseline`` prints the same line f
 ``len(seeds) x --envs``, every learner's collection in one launch and every learner's minibatch step in the four launches of one
 (``evac_rpo_update_population``); each learner is bit for bit the ``--optimizer device`` run it would be alone.  One line per
 learner and update.
+
+``--sweep field=v1,v2,..`` (repeatable; with ``--seeds``: every setting over every seed) trains the cartesian product of the
+settings as ONE population (``sweep_configs``, ``PopulationTrainer(env, population, cfgs)``): the learners' learning rates, loss
+coefficients, gammas, ``max_grad_norm`` and ``target_kl`` ride in the kernel arguments of the same launches
+(``evac_rpo_update_sweep``), each learner bit for bit the run it would be alone with its configuration.  Fields:
+``population.SWEEP_FIELDS``; ``target_kl=none`` is no target.  Every line is led by the learner's own values of the swept fields
+(``log["config"]`` holds those that differ from learner 0's).
 
 ``--compare`` measures, at the same sizes and with the reference's 32 minibatches x 10 epochs, one ``update()`` (a) with the
 kernels against (b) the same update with the loss written in torch (tests/trainer_ref.py, float32) and autograd, eager and with
@@ -50,14 +58,33 @@ def make_trainer(args, **hooks):
     return RPOTrainer(env, net, cfg, **hooks)
 
 
-def make_population_trainer(args, seeds):
-    from evacuation_amd.population import PolicyPopulation, PopulationTrainer
+def parse_sweep(specs):
+    """``["learning_rate=1e-4,3e-4", "anneal_lr=0,1", "target_kl=none,0.01"]`` -> the grid of ``sweep_configs``."""
+    from evacuation_amd.population import SWEEP_FIELDS
+    grid = {}
+    for spec in specs:
+        field, _, values = spec.partition("=")
+        if field not in SWEEP_FIELDS or not values:
+            raise SystemExit(f"--sweep {spec}: expected field=v1,v2,.. with a field of {', '.join(SWEEP_FIELDS)}")
+        if field == "anneal_lr":
+            grid[field] = [v.lower() in ("1", "true", "yes") for v in values.split(",")]
+        else:
+            grid[field] = [None if v.lower() == "none" else float(v) for v in values.split(",")]
+    return grid
+
+
+def make_population_trainer(args, seeds, grid=None):
+    from evacuation_amd.population import PolicyPopulation, PopulationTrainer, sweep_configs
     cfg = RPOTrainingConfig(num_envs=args.envs, num_steps=args.steps, total_timesteps=args.envs * args.steps * max(args.updates, 1),
                             num_minibatches=args.minibatches, update_epochs=args.epochs)
+    cfgs = cfg
+    if grid is not None:                                         # one learner per (setting, seed)
+        pairs = sweep_configs(cfg, grid, seeds)
+        seeds, cfgs = [s for s, _ in pairs], [c for _, c in pairs]
     env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=args.pedestrians, is_new_exiting_reward=True),
                                       ea.EnvWrappersConfig(positions="grav", alpha=3), num_envs=args.envs * len(seeds), gamma=cfg.gamma,
                                       seed=1)
-    return PopulationTrainer(env, PolicyPopulation(env.obs_dim, seeds, DEV), cfg)
+    return PopulationTrainer(env, PolicyPopulation(env.obs_dim, seeds, DEV), cfgs)
 
 
 def eager_yardstick(R):
@@ -204,11 +231,17 @@ def main():
     ap.add_argument("--eval-episodes", type=int, default=1, help="episodes per env of an evaluation")
     ap.add_argument("--baseline", action="store_true", help="print the scripted sweep baseline's summary on the same evaluator")
     ap.add_argument("--seeds", type=str, default=None, help="comma-separated seeds: one learner per seed, trained as a population")
+    ap.add_argument("--sweep", action="append", default=None, metavar="FIELD=V1,V2,..",
+                    help="per-learner values of a hyperparameter; repeat for a grid: the product trains as one population")
     args = ap.parse_args()
     if args.compare:
         return compare(args)
     seeds = [int(x) for x in args.seeds.split(",")] if args.seeds else None
-    tr = make_population_trainer(args, seeds) if seeds else make_trainer(args, optimizer=args.optimizer)
+    grid = parse_sweep(args.sweep) if args.sweep else None
+    if grid:
+        tr = make_population_trainer(args, seeds or [1], grid)
+    else:
+        tr = make_population_trainer(args, seeds) if seeds else make_trainer(args, optimizer=args.optimizer)
 
     def eval_line(name, s):
         print(f"eval {name:14s} episodic_return={s['episode_reward_mean']:9.2f} +- {s['episode_reward_std']:.2f}  length={s['episode_length_mean']:7.1f}  "
@@ -224,6 +257,8 @@ def main():
         r = log["episodes"]["episode_reward"]
         ret = f"{float(r.mean()):9.2f} over {r.numel():5d} episodes" if r.numel() else "   (no episode finished)"
         who = f"seed {log['seed']:<6d} " if "seed" in log else ""
+        if grid:                                                 # led by the learner's own values of the swept fields
+            who = " ".join(f"{k}={getattr(tr.cfgs[log['learner']], k)}" for k in grid) + "  " + who
         print(f"{who}update {log['update']:3d}  global_step={log['global_step']:9d}  value_loss={log['value_loss']:.4f}  policy_loss={log['policy_loss']:+.5f}  "
               f"approx_kl={log['approx_kl']:.5f}  clipfrac={log['clipfrac']:.3f}  explained_variance={log['explained_variance']:+.3f}  episodic_return={ret}")
         print("SPS:", log["SPS"])

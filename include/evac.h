@@ -633,6 +633,61 @@ int evac_rpo_update_population(int32_t n_learners, const evac_mlp_policy_t* poli
                                const uint64_t* first_draw_counters, int32_t use_target_kl, double target_kl, float* stats_out,
                                void* workspace, void* stream);
 
+/* ---- Sweeps: a population whose learners differ in their float-valued hyperparameters ----
+ * evac_learner_hyper_t: one learner's values.  Callers pass a HOST array [n_learners], read during the call; the values travel
+ * to the kernels by value in the kernel-argument segment (as the seeds and draw counters do), so the calls stay free of host
+ * synchronisation and capturable, and a capture freezes them.  Number types are the lone trainer's: learning_rate and target_kl
+ * are used as doubles, the loss coefficients and max_grad_norm as float32, and gamma / gae_lambda as evac_gae uses them
+ * ((float)gamma, (float)(gamma * gae_lambda) with the product formed in double).  What fixes launch geometry or storage shape
+ * (n_minibatch, n_epochs, norm_adv, clip_vloss, Adam's betas and eps) stays one value for all learners.
+ * Every entry below refuses (EVAC_ERR_INVALID_ARGUMENT, on the host, before anything touches a device) a NULL hypers and, for
+ * any learner: a non-finite learning_rate, gamma or gae_lambda; max_grad_norm <= 0 (or NaN); clip_coef < 0 or rpo_alpha < 0 (or
+ * NaN); with use_target_kl, a NaN target_kl. */
+typedef struct evac_learner_hyper {
+    double learning_rate, target_kl, gamma, gae_lambda;
+    float clip_coef, ent_coef, vf_coef, rpo_alpha, max_grad_norm;
+    int32_t use_target_kl;                 /* 0: target_kl is ignored and the learner never stops early */
+} evac_learner_hyper_t;
+
+/* evac_gae_learners: evac_gae over the storage of a population: env e belongs to learner e / envs_per_learner and uses
+ * hypers[that learner].gamma / gae_lambda.  EQUIVALENCE: learner s's columns are, bit for bit, evac_gae on those columns alone
+ * with hypers[s].gamma and hypers[s].gae_lambda.  Refused as evac_gae, and envs_per_learner < 1, n_learners outside
+ * 1..EVAC_MAX_LEARNERS, n_envs != n_learners x envs_per_learner, and the hypers as above. */
+int evac_gae_learners(int32_t n_steps, int64_t n_envs, const float* rewards, const float* values, const float* dones,
+                      const float* next_value, const float* next_done, int64_t envs_per_learner, int32_t n_learners,
+                      const evac_learner_hyper_t* hypers, float* advantages_out, float* returns_out, void* stream);
+
+/* evac_policy_rollout_sweep: evac_policy_rollout_population with a per-learner gamma of the reward normaliser (the reference
+ * wraps a learner's env with its training gamma).  Of hypers only gamma is read: learner s's chain runs with (float)hypers[s].gamma;
+ * the `gamma` argument is not used.  Without the chain (norm_state NULL) gamma does not enter collection and the call is
+ * evac_policy_rollout_population.  EQUIVALENCE: learner s's columns are, bit for bit, evac_policy_rollout on a handle of its
+ * envs with gamma = (float)hypers[s].gamma.  Refused as evac_policy_rollout_population, and the hypers as above. */
+int evac_policy_rollout_sweep(evac_handle_t h, int32_t n_learners, const evac_mlp_policy_t* policy,
+                              const evac_mlp_policy_strides_t* strides, int32_t n_steps, float* next_obs, float* next_done,
+                              float* obs_out, float* actions_out, float* logprob_out, float* value_out, float* reward_out,
+                              float* done_out, float* next_value_out, evac_episode_stats_t* final_stats_or_null,
+                              double* norm_state_or_null, float gamma, float obs_clip, float reward_clip, float epsilon,
+                              const evac_learner_hyper_t* hypers, void* stream);
+
+/* evac_rpo_update_sweep: evac_rpo_update_population with hypers[s] in place of the one configuration: learner s's loss runs
+ * with hypers[s].clip_coef / ent_coef / vf_coef / rpo_alpha and its optimiser with learning_rate / max_grad_norm / use_target_kl
+ * / target_kl.  loss_cfg gives norm_adv and clip_vloss (its four coefficients are not used), adam_cfg the betas and eps (its lr
+ * and max_grad_norm are not used, but must be valid).  A learner with use_target_kl == 0 never sets its stop flag, whatever its
+ * neighbours do.  EQUIVALENCE: learner s is, bit for bit, evac_rpo_update with learner s's tensors, perms[s], seeds[s],
+ * first_draw_counters[s], a loss_cfg and adam_cfg holding hypers[s]'s values, and hypers[s].use_target_kl / target_kl.  The
+ * same number of launches as evac_rpo_update_population; no host synchronisation, capturable.  Refused as
+ * evac_rpo_update_population, and the hypers as above. */
+int evac_rpo_update_sweep(int32_t n_learners, const evac_mlp_policy_t* policy, const evac_mlp_policy_grads_t* params,
+                          const evac_mlp_policy_grads_t* grads, const evac_mlp_policy_strides_t* param_strides,
+                          const evac_mlp_policy_strides_t* grad_strides, const evac_mlp_policy_strides_t* moment_strides,
+                          int64_t header_stride_bytes, const evac_rpo_loss_config_t* loss_cfg,
+                          const evac_adam_config_t* adam_cfg, const evac_adam_state_t* state, int64_t batch_size,
+                          const float* b_obs, const float* b_actions, const float* b_logprobs, const float* b_advantages,
+                          const float* b_returns, const float* b_values, int64_t learner_batch_size, int64_t n_minibatch,
+                          int32_t n_epochs, const int64_t* perms, const float* rpo_noise_or_null, const uint64_t* seeds,
+                          const uint64_t* first_draw_counters, const evac_learner_hyper_t* hypers, float* stats_out,
+                          void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,9 @@
 `--tree`: the checkout whose package and libevac.so are timed (a built checkout of another commit for an A/B run; the two
 builds run as separate processes, alternated by the caller inside every repetition).  `--form standalone`: S
 ``RPOTrainer(optimizer="device")`` on handles of E_l envs, updated one after another; `--form population`: one
-``PopulationTrainer`` of S learners.  The reference's 32 minibatches x 10 epochs, N = 60, gravity observation.  hipEvent times
+``PopulationTrainer`` of S learners; `--form sweep_equal` / `sweep_differ`: the same population given S configurations (the
+per-learner path), all equal or differing in learning rate, annealing, gamma, lambda, the loss
+coefficients, max_grad_norm and target_kl (none of them reached, so every form runs the same steps).  The reference's 32 minibatches x 10 epochs, N = 60, gravity observation.  hipEvent times
 after two warm-up windows; one JSON line per shape: the milliseconds of each window of S learner-updates."""
 import argparse
 import json
@@ -16,7 +18,7 @@ import sys
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--tree", required=True)
-ap.add_argument("--form", required=True, choices=("standalone", "population"))
+ap.add_argument("--form", required=True, choices=("standalone", "population", "sweep_equal", "sweep_differ"))
 ap.add_argument("--shapes", required=True, help="E_l:T:S,E_l:T:S,...")
 ap.add_argument("--windows", type=int, default=3)
 args = ap.parse_args()
@@ -60,9 +62,18 @@ for shape in args.shapes.split(","):
         close = lambda: [tr.env.close() for tr in trs]
     else:
         from evacuation_amd.population import PolicyPopulation, PopulationTrainer
+        import dataclasses
         cfg = cfg_of(E_l, T, 0)
         env = env_of(S * E_l, cfg)
-        ptr = PopulationTrainer(env, PolicyPopulation(env.obs_dim, seeds, DEV), cfg)
+        cfgs = cfg
+        if args.form == "sweep_equal":
+            cfgs = [dataclasses.replace(cfg) for _ in range(S)]
+        elif args.form == "sweep_differ":
+            cfgs = [dataclasses.replace(cfg, learning_rate=3e-4 * (1 + s), anneal_lr=bool(s % 2), gamma=0.99 - 0.01 * s,
+                                        gae_lambda=0.95 - 0.02 * s, clip_coef=0.2 + 0.01 * s, ent_coef=0.001 * s, vf_coef=0.5 + 0.05 * s,
+                                        rpo_alpha=0.5 - 0.03 * s, max_grad_norm=0.5 + 0.1 * s, target_kl=None if s % 3 == 0 else 1e9)
+                    for s in range(S)]
+        ptr = PopulationTrainer(env, PolicyPopulation(env.obs_dim, seeds, DEV), cfgs)
         window = ptr.update
         close = env.close
     window(); window()
