@@ -46,6 +46,12 @@ class EvacMlpPolicy(C.Structure):
                                   "critic_w1", "critic_b1", "critic_w2", "critic_b2", "critic_w3", "critic_b3")]
 
 
+class EvacDeepSets(C.Structure):
+    """evac_deepsets_t: the set encoder's tensors (torch layouts) for evac_policy_rollout_deepsets / evac_policy_evaluate_deepsets"""
+    _fields_ = [("set_elem_dim", C.c_int32), ("hidden", C.c_int32)] + [
+        (f, C.c_void_p) for f in ("phi_w1", "phi_b1", "phi_w2", "phi_b2", "rho_w", "rho_b")]
+
+
 class EvacRpoLossConfig(C.Structure):
     """evac_rpo_loss_config_t"""
     _fields_ = [(f, C.c_float) for f in ("clip_coef", "ent_coef", "vf_coef", "rpo_alpha")] + [("norm_adv", C.c_int32), ("clip_vloss", C.c_int32)]
@@ -157,6 +163,10 @@ SIGNATURES = {
     "evac_policy_rollout_population": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyStrides), C.c_int32,
                                                  _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "evac_policy_evaluate": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P]),
+    "evac_policy_rollout_deepsets": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                               C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(EvacDeepSets), _P]),
+    "evac_policy_evaluate_deepsets": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float,
+                                                C.c_float, C.POINTER(EvacDeepSets), _P]),
     "evac_gae": (C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
     "evac_rpo_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
     "evac_rpo_minibatch_grad": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacRpoLossConfig), C.c_int64, _P, _P, _P, _P, _P, _P,

@@ -20,6 +20,7 @@
 #include "evac_policy.h"
 #include "evac_evaluate.h"
 #include "evac_host.h"
+#include "evac_handle_host.h"
 
 namespace {
 
@@ -1639,3 +1640,19 @@ int evac_policy_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t
 }
 
 }  // extern "C"
+
+// ---- evac_handle_host.h: the handle for the entries of other translation units (evac_deepsets_api.hip) ----
+namespace evac_host {
+
+int handle_begin(evac_handle_t h, const char* what, HandleView* out) {
+    if (!h) return EVAC_ERR_INVALID_ARGUMENT;
+    if (!h->bound) return fail(h, EVAC_ERR_NOT_BOUND, std::string(what) + ": call evac_bind_state first");
+    if (const int ta = team_aborted(h, what); ta != EVAC_OK) return ta;
+    *out = HandleView{h->p, h->device, h->default_cfg};
+    return EVAC_OK;
+}
+int handle_settle(evac_handle_t h, hipStream_t stream) { return settle(h, stream); }
+int handle_fail(evac_handle_t h, int code, const std::string& msg) { return fail(h, code, msg); }
+int handle_check_launch(evac_handle_t h, const char* what) { return check_launch(h, what); }
+
+}  // namespace evac_host

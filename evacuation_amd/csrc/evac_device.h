@@ -974,6 +974,9 @@ __global__ __launch_bounds__(F::kBlock, 4) void k_rollout_persist_default_config
 // (re)start of a chain: every env's generation word (device-scope stores, like the launches' own), and one permutation copied to
 // the three other buffers of the four-deep rotation
 // one wave per env: the caller's state arrays -> the env's exchange record at generation `gen` (a chain starts) ...
+// (The kernels that are no templates are evac_api.hip's alone: a translation unit that includes this file beside it -- for the
+// templates -- defines EVAC_TEMPLATE_KERNELS_ONLY, or the library would hold them twice.)
+#ifndef EVAC_TEMPLATE_KERNELS_ONLY
 __global__ __launch_bounds__(256) void k_chain_import(Params p, char* __restrict__ xchg, int gen, unsigned* __restrict__ abort_word,
                                                       unsigned long long started_so_far, int wpe) {
     // (one wave per 64 pedestrians of an env: wave `part` of env `env`; T = 64 wpe lanes per env)
@@ -1038,6 +1041,7 @@ __global__ __launch_bounds__(1024) void k_schedule(int n_envs, const int* __rest
         for (int e = threadIdx.x; e < n_envs; e += 1024) perm_other[e] = perm[e];
     }
 }
+#endif
 template <class F, bool GRAV>
 __global__ __launch_bounds__(F::kBlock, 4) void k_rollout_diag(
     Params p, int n_steps, const float2* __restrict__ actions, float2* __restrict__ actions_out,
@@ -1079,6 +1083,7 @@ __global__ __launch_bounds__(F::kBlock, 4) void k_observe(Params p, float* __res
 }
 
 // state exchange in the reference's shapes
+#ifndef EVAC_TEMPLATE_KERNELS_ONLY
 __global__ void k_get_state(Params p, float2* pos, float2* dir, uint8_t* status, float2* apos, float2* adir, int32_t* now) {
     const size_t n = (size_t)p.n_envs * p.n_ped;
     for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x * blockDim.x) {
@@ -1116,12 +1121,14 @@ __global__ void k_set_state(Params p, const float2* pos, const float2* dir, cons
         }
     }
 }
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // The trainer's per-env wrapper chain as a SEPARATE epilogue (rpo_agent.py:24-33): used for resets (evac_norm_reset) and
 // kept as the unfused reference of evac_step_normalized (tests/test_gpu_wrappers.py); the statistics themselves are in
 // evac_common.h (rms_update1, norm_clip).
 // ------------------------------------------------------------------------------------------------
+#ifndef EVAC_TEMPLATE_KERNELS_ONLY
 __global__ void k_norm_init(int n_envs, int D, double* __restrict__ st) {
     const int W = 3 * D + 4;
     const size_t n = (size_t)n_envs * W;
@@ -1173,6 +1180,7 @@ __global__ void k_norm_step(int n_envs, int D, float* __restrict__ obs, float* _
         }
     }
 }
+#endif
 
 // layout guards: the tile and the staging rows are accessed with 16-byte LDS instructions
 static_assert(offsetof(Wave<1>::Smem, stage) % 16 == 0 && offsetof(Wave<2>::Smem, stage) % 16 == 0 &&

@@ -94,11 +94,13 @@ __device__ __forceinline__ void eval_observation(const Params& p, PolicyFamily::
 }
 
 // POLICY: the network is the agent (ps: its weights in LDS); else the scripted baseline, which reads e.ax / e.ay and nothing else.
-template <bool POLICY, bool GRAV, bool NORM>
+// ENC: an encoder in front of the actor (evac_policy.h: NoEncoder; evac_deepsets.h).
+template <bool POLICY, bool GRAV, bool NORM, class ENC = NoEncoder>
 __device__ __forceinline__ void policy_evaluate_body(PolicyFamily::Smem& sm, PolicySmem<GRAV>* psp, EvalSmem& es, const Params& p,
-                                                     const PolicyArgs& ka, const EvalArgs& kev) {
+                                                     const PolicyArgs& ka, const EvalArgs& kev, const ENC& enc = ENC{}) {
     using F = PolicyFamily;
     if constexpr (POLICY) stage_policy<GRAV>(*psp, ka, NormArgs{nullptr, 0.f, 0.f, 0.f, 0.f});
+    if constexpr (ENC::kOn) enc.stage();
     if (threadIdx.x == 0) es.a = kev;
     __syncthreads();
     typename F::Ctx w(sm);
@@ -146,7 +148,12 @@ __device__ __forceinline__ void policy_evaluate_body(PolicyFamily::Smem& sm, Pol
             if (sample && (t & 63) == 0) ps.z[w.slot][k] = policy_normal(p, gid, e.total + (uint32_t)k);   // as policy_rollout_body
             F::sync();
             float m0, m1, v;
-            policy_eval<GRAV, true, false>(ps.args, ps, w.slot, k, D, m0, m1, v);
+            if constexpr (ENC::kOn) {
+                enc.encode(xs, w.slot, k, D, p.n_ped + 2);
+                policy_eval<GRAV, true, false>(ps.args, ps, w.slot, k, D, m0, m1, v, enc.row(w.slot));
+            } else {
+                policy_eval<GRAV, true, false>(ps.args, ps, w.slot, k, D, m0, m1, v);
+            }
             const f4 c0 = ps.c[0];
             m0 += c0.x;
             m1 += c0.y;

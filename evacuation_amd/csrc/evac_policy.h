@@ -76,11 +76,12 @@ __device__ __forceinline__ void stage_observation(const Params& p, typename F::C
 
 // actor_mean(x) and critic(x) of the observation in the wave's LDS row (every lane computes unit `k` = its lane; results
 // wave-uniform, b3 not added).  ACTOR = false: the critic alone (the bootstrap value).  CRITIC = false: the actor alone (the
-// policy evaluation, which has no use for values; v comes back 0).
+// policy evaluation, which has no use for values; v comes back 0).  `row`: the LDS row the first layer reads instead of the
+// observation's (an encoder's output: evac_deepsets.h).
 template <bool GRAV, bool ACTOR, bool CRITIC = true>
 __device__ __forceinline__ void policy_eval(const PolicyArgs& a, PolicySmem<GRAV>& ps, int slot, int k, int D, float& m0, float& m1,
-                                            float& v) {
-    const float* xs = ps.x[slot];
+                                            float& v, const float* row = nullptr) {
+    const float* xs = row ? row : ps.x[slot];
     const f4 u0 = ps.unit[0][k];
     float ha = u0.x, hc = u0.y;
     if constexpr (GRAV) {
@@ -178,13 +179,22 @@ __device__ __forceinline__ void stage_policy(PolicySmem<GRAV>& ps, const PolicyA
     }
 }
 
+// An encoder between the observation and the actor-critic (ENC of the bodies below and of policy_evaluate_body): staged with
+// the weights, run on the wave's observation row before every forward pass, and the actor-critic reads its row.  None here;
+// evac_deepsets.h has one.
+struct NoEncoder {
+    static constexpr bool kOn = false;
+};
+
 // SHIFTED (the population form, k_collect_population): the wave's env is its place in the launch plus `env_shift`, and it has
 // work while that is below `env_end` -- each learner's workgroups get the learner's own envs.
-template <bool GRAV, bool NORM, bool SHIFTED = false>
+template <bool GRAV, bool NORM, bool SHIFTED = false, class ENC = NoEncoder>
 __device__ __forceinline__ void policy_rollout_body(PolicyFamily::Smem& sm, PolicySmem<GRAV>& ps, const Params& p, int n_steps,
-                                                    const PolicyArgs& ka, const NormArgs& kna, int env_shift = 0, int env_end = 0) {
+                                                    const PolicyArgs& ka, const NormArgs& kna, int env_shift = 0, int env_end = 0,
+                                                    const ENC& enc = ENC{}) {
     using F = PolicyFamily;
     stage_policy<GRAV>(ps, ka, kna);
+    if constexpr (ENC::kOn) enc.stage();
     __syncthreads();
     typename F::Ctx w(sm);
     if constexpr (SHIFTED) {
@@ -217,7 +227,12 @@ __device__ __forceinline__ void policy_rollout_body(PolicyFamily::Smem& sm, Poli
         if ((t & 63) == 0) ps.z[w.slot][k] = policy_normal(p, gid, e.total + (uint32_t)k);   // the noise of the next 64 steps, one per lane
         F::sync();
         float m0, m1, v;
-        policy_eval<GRAV, true>(a, ps, w.slot, k, D, m0, m1, v);
+        if constexpr (ENC::kOn) {
+            enc.encode(xs, w.slot, k, D, p.n_ped + 2);
+            policy_eval<GRAV, true>(a, ps, w.slot, k, D, m0, m1, v, enc.row(w.slot));
+        } else {
+            policy_eval<GRAV, true>(a, ps, w.slot, k, D, m0, m1, v);
+        }
         const f4 c0 = ps.c[0], c1 = ps.c[1], c2 = ps.c[2];
         m0 += c0.x;
         m1 += c0.y;
@@ -296,7 +311,12 @@ __device__ __forceinline__ void policy_rollout_body(PolicyFamily::Smem& sm, Poli
     }
     F::sync();
     float m0, m1, v;
-    policy_eval<GRAV, false>(a, ps, w.slot, k, D, m0, m1, v);   // the trainer's bootstrap get_value(next_obs)
+    if constexpr (ENC::kOn) {
+        enc.encode(xs, w.slot, k, D, p.n_ped + 2);
+        policy_eval<GRAV, false>(a, ps, w.slot, k, D, m0, m1, v, enc.row(w.slot));
+    } else {
+        policy_eval<GRAV, false>(a, ps, w.slot, k, D, m0, m1, v);   // the trainer's bootstrap get_value(next_obs)
+    }
     if (w.owner) a.next_value_out[env] = v + ps.c[0].z;
     store_env(p, env, w.i, active, w.owner, q, e);
 }

@@ -34,7 +34,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .policy import HIDDEN, LinearActorCritic, _check_structure, mlp_tensors
+from .policy import HIDDEN, LinearActorCritic, _check_structure, mlp_tensors, refuse_deepsets
 from .trainer import (BATCH_KEYS, DeviceAdam, RPOTrainingConfig, _f32, _loss_config, _stream, _u64, decode_header, flatten_batch, gae,
                       update_steps)
 from .vector_env import STATS_FIELDS, _ptr
@@ -64,10 +64,12 @@ def check_structure(cfgs: Sequence, what: str = "configuration") -> None:
                                  f"{getattr(cfgs[0], f, None)!r}; {f} fixes the launches' shape and is one value per population")
 
 
-def sweep_configs(base: RPOTrainingConfig, grid: Dict[str, Sequence], seeds: Optional[Sequence[int]] = None) -> list:
+def sweep_configs(base: RPOTrainingConfig, grid: Dict[str, Sequence], seeds: Optional[Sequence[int]] = None, net=None) -> list:
     """The cartesian product of ``grid`` (field of ``RPOTrainingConfig`` -> its values) over ``seeds`` (default: ``base.seed``)
     as a list of ``(seed, cfg)``, ``cfg = replace(base, seed=seed, **setting)``: the first field varies slowest, the seeds
-    fastest (a setting's seeds are neighbours).  ``ValueError`` for an unknown field or more than ``MAX_LEARNERS`` learners."""
+    fastest (a setting's seeds are neighbours).  ``ValueError`` for an unknown field or more than ``MAX_LEARNERS`` learners, and
+    for a ``net`` (the network the sweep is meant for, optional) with a set encoder: populations are the linear network's."""
+    refuse_deepsets(net, "sweep_configs")
     names = {f.name for f in dataclasses.fields(base)}
     for f, values in grid.items():
         if f not in names or f == "seed":
@@ -98,7 +100,10 @@ class PolicyPopulation:
     """S actor-critics of observation width ``obs_dim`` as 13 stacked tensors ``[S, ...]`` on ``device``; see the module's
     docstring.  ``tensors`` / ``grads``: the stacks, in ``evac_mlp_policy_t`` order; ``strides``: a learner's distance in each."""
 
-    def __init__(self, obs_dim: int, seeds: Sequence[int], device="cuda:0"):
+    def __init__(self, obs_dim: int, seeds: Sequence[int], device="cuda:0", net=None):
+        """``net``: the network the learners are meant to copy, optional and only checked -- the learners are
+        ``LinearActorCritic``s; one with a set encoder is a ``ValueError``."""
+        refuse_deepsets(net, "PolicyPopulation")
         seeds = [int(s) for s in seeds]
         if not 1 <= len(seeds) <= MAX_LEARNERS:
             raise ValueError(f"PolicyPopulation: {len(seeds)} learners; expected 1..{MAX_LEARNERS}")
@@ -308,6 +313,9 @@ class PopulationTrainer:
     its fields that differ from learner 0's."""
 
     def __init__(self, env, population: PolicyPopulation, cfgs):
+        refuse_deepsets(population, "PopulationTrainer")       # (a network where the population goes)
+        for net in getattr(population, "nets", ()):
+            refuse_deepsets(net, "PopulationTrainer")
         S = population.num_learners
         self.sweep = isinstance(cfgs, (list, tuple))
         if self.sweep:

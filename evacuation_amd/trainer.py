@@ -17,7 +17,7 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from .policy import PolicyBinder, mlp_tensors
+from .policy import PolicyBinder, all_tensors, encode_observation, is_deepsets, mlp_tensors, refuse_deepsets
 from .vector_env import STATS_FIELDS, _ptr
 
 STAT_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "grad_sumsq")
@@ -152,7 +152,7 @@ def ensure_grads(net) -> "_lib.EvacMlpPolicyGrads":
     """Every parameter gets a contiguous float32 ``.grad`` on its device (allocated once, then reused: torch's optimisers update
     in place); their addresses as ``evac_mlp_policy_grads_t``."""
     ts = mlp_tensors(net)
-    for t in ts:
+    for t in all_tensors(net):               # (a set encoder's six as well: autograd_minibatch_grad writes them)
         g = t.grad
         if g is None or g.dtype != torch.float32 or g.device != t.device or not g.is_contiguous() or g.shape != t.shape:
             t.grad = torch.zeros_like(t, memory_format=torch.contiguous_format)
@@ -162,6 +162,7 @@ def ensure_grads(net) -> "_lib.EvacMlpPolicyGrads":
 def _batch_args(net, batch: Dict[str, torch.Tensor]):
     """The checks every gradient entry makes of ``batch``; returns (B, D, device, state, evac_mlp_policy_t, grads struct, the
     entries' arguments ``batch_size, b_obs .. b_values``)."""
+    refuse_deepsets(net, "the device gradient")
     b_obs = batch["b_obs"]
     B, D = b_obs.shape
     dev = b_obs.device
@@ -423,10 +424,73 @@ def _kernel_grad(trainer: "RPOTrainer", batch, mb_inds, rpo_noise, draw_counter:
                               draw_counter=draw_counter, stats=stats)
 
 
+def _draw_seed(seed: int, draw_counter: int) -> int:
+    return ((int(seed) & 0xffffffff) << 31) ^ (int(draw_counter) & 0x7fffffff)
+
+
+def autograd_minibatch_grad(trainer, batch, mb_inds, rpo_noise, draw_counter: int, stats: torch.Tensor) -> torch.Tensor:
+    """A ``grad_fn`` of ``RPOTrainer`` for ANY network it takes: the reference's minibatch loss (rpo_agent.py:239-274 with
+    get_action_and_value of rpo_linear_agent_network.py:48-61 / rpo_deep_sets_agent_network.py:83-90) through torch autograd on
+    the module itself -- the gradient of a network with a set encoder, whose 19 tensors the gradient kernels do not know.
+    Writes the parameters' ``.grad`` (not accumulated) and the 8 statistics (``STAT_NAMES``; ``stats[7]`` the gradient's sum of
+    squares, in double).  ``rpo_noise`` [M, 2]: the perturbation of the mean; None draws U(-rpo_alpha, rpo_alpha) from a torch
+    generator seeded with (``cfg.seed``, ``draw_counter``).  ``trainer``: anything with ``net`` and ``cfg``."""
+    net, cfg = trainer.net, trainer.cfg
+    params = list(all_tensors(net))
+    dev = params[0].device
+    M = int(mb_inds.shape[0])
+    if rpo_noise is None:
+        gen = getattr(trainer, "_autograd_generator", None)
+        if gen is None or gen.device != dev:
+            gen = trainer._autograd_generator = torch.Generator(device=dev)
+        gen.manual_seed(_draw_seed(cfg.seed, draw_counter))
+        alpha = float(cfg.rpo_alpha)
+        rpo_noise = (torch.rand(M, 2, device=dev, dtype=torch.float32, generator=gen) * 2.0 - 1.0) * alpha
+    with torch.enable_grad():
+        y = encode_observation(net, batch["b_obs"][mb_inds])
+        mean = net.actor_mean(y) + rpo_noise
+        probs = torch.distributions.normal.Normal(mean, torch.exp(net.actor_logstd.expand_as(mean)))
+        newlogprob, entropy = probs.log_prob(batch["b_actions"][mb_inds]).sum(1), probs.entropy().sum(1)
+        newvalue = net.critic(y).view(-1)
+        logratio = newlogprob - batch["b_logprobs"][mb_inds]
+        ratio = logratio.exp()
+        with torch.no_grad():
+            old_approx_kl = (-logratio).mean()
+            approx_kl = ((ratio - 1) - logratio).mean()
+            clipfrac = ((ratio - 1.0).abs() > cfg.clip_coef).float().mean()
+        adv = batch["b_advantages"][mb_inds]
+        if cfg.norm_adv:
+            adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+        pg_loss = torch.max(-adv * ratio, -adv * torch.clamp(ratio, 1 - cfg.clip_coef, 1 + cfg.clip_coef)).mean()
+        ret, old_v = batch["b_returns"][mb_inds], batch["b_values"][mb_inds]
+        if cfg.clip_vloss:
+            v_clipped = old_v + torch.clamp(newvalue - old_v, -cfg.clip_coef, cfg.clip_coef)
+            v_loss = 0.5 * torch.max((newvalue - ret) ** 2, (v_clipped - ret) ** 2).mean()
+        else:
+            v_loss = 0.5 * ((newvalue - ret) ** 2).mean()
+        ent = entropy.mean()
+        loss = pg_loss - cfg.ent_coef * ent + v_loss * cfg.vf_coef
+        grads = torch.autograd.grad(loss, params)
+    with torch.no_grad():
+        for p, g in zip(params, grads):
+            if p.grad is None or p.grad.shape != g.shape:
+                p.grad = g.contiguous().clone()
+            else:
+                p.grad.copy_(g)
+        sumsq = torch.stack([(g.double() ** 2).sum() for g in grads]).sum().float()
+        stats.copy_(torch.stack([loss.detach(), pg_loss.detach(), v_loss.detach(), ent.detach(), old_approx_kl, approx_kl, clipfrac,
+                                 sumsq]))
+    return stats
+
+
 class RPOTrainer:
     """One iteration of the reference's training loop (rpo_agent.py:172-299) per ``update()``: learning-rate annealing, the
     collection phase (``policy_rollout``), ``gae``, ``update_epochs`` x ``num_minibatches`` steps of gradient (kernel),
     ``clip_grad_norm_`` (from the kernel's sum of squares) and ``Adam(eps=1e-5)``, the ``target_kl`` early exit.
+
+    ``net``: the linear network, or one with the reference's set encoder (``policy.DeepSetsActorCritic``): its collection and
+    evaluation run on the device too, its gradient is ``autograd_minibatch_grad`` (the default ``grad_fn`` then) and its
+    optimiser torch's -- ``optimizer="device"`` is a ``ValueError``: the gradient and optimiser kernels are the linear network's.
 
     ``env``: a ``NormalizedVectorEnv`` (the trainer's wrapper chain) or a ``BatchedEvacuationEnv`` with ``cfg.num_envs`` envs.
     The permutation of every epoch is drawn on the device from a generator seeded with ``cfg.seed`` (the reference shuffles on
@@ -451,9 +515,12 @@ class RPOTrainer:
         if env.num_envs != cfg.num_envs:
             raise ValueError(f"RPOTrainer: the env has {env.num_envs} envs, cfg.num_envs = {cfg.num_envs}")
         self.env, self.net, self.cfg = env, net, cfg
-        self.grad_fn = grad_fn or _kernel_grad
+        if is_deepsets(net) and optimizer == "device":
+            refuse_deepsets(net, "RPOTrainer(optimizer=\"device\")")
+        # (a set encoder: collection and evaluation on the device, the gradient of all 19 tensors by autograd)
+        self.grad_fn = grad_fn or (autograd_minibatch_grad if is_deepsets(net) else _kernel_grad)
         self.rpo_noise_fn = rpo_noise_fn
-        self.params = list(mlp_tensors(net))
+        self.params = list(all_tensors(net))
         self.device = self.params[0].device
         ensure_grads(net)
         if optimizer == "device":

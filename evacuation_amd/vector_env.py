@@ -584,7 +584,9 @@ class BatchedEvacuationEnv:
         ``get_value(next_obs)``), ``episode_stats`` [T,E,10] (rows valid where an episode ended), and ``next_obs`` /
         ``next_done``.  Pass a previous result as ``out`` to reuse it.  Raw observations and rewards here;
         ``NormalizedVectorEnv.policy_rollout`` runs the trainer's normalisation chain.  No host synchronisation: the call can
-        be captured into a graph, and the kernel reads the parameters in place at every replay."""
+        be captured into a graph, and the kernel reads the parameters in place at every replay.  A ``net`` with the reference's
+        set encoder (``deep_sets``: ``evacuation_amd.policy.DeepSetsActorCritic``, Box observations) runs the encoder inside the
+        same launch (``evac_policy_rollout_deepsets``); the storage is the same, ``obs`` the observation before the encoder."""
         return self._policy_rollout(net, None, n_steps, next_obs, next_done, out, _norm)
 
     def policy_rollout_population(self, population, n_steps: int, next_obs: torch.Tensor, next_done: torch.Tensor,
@@ -602,7 +604,7 @@ class BatchedEvacuationEnv:
         return self._policy_rollout(population.nets[0], population, n_steps, next_obs, next_done, out, _norm, hypers)
 
     def _policy_rollout(self, net, population, n_steps, next_obs, next_done, out, _norm, hypers=None):
-        from .policy import MAX_PEDESTRIANS, PolicyBinder
+        from .policy import MAX_PEDESTRIANS, PolicyBinder, is_deepsets, refuse_deepsets
         if self.n_ped > MAX_PEDESTRIANS:
             raise NotImplementedError(f"policy_rollout runs one wave per env: rooms of at most {MAX_PEDESTRIANS} pedestrians "
                                       f"(this env has {self.n_ped})")
@@ -611,8 +613,13 @@ class BatchedEvacuationEnv:
             raise ValueError("policy_rollout: n_steps must be >= 1")
         binder = getattr(self, "_policy_binder", None)
         if binder is None:
-            binder = self._policy_binder = PolicyBinder(D, self.device)
+            binder = self._policy_binder = PolicyBinder(D, self.device, self.n_ped)
         pol = binder(net)
+        enc = None
+        if is_deepsets(net):                  # the set encoder in front of the actor-critic: evac_policy_rollout_deepsets
+            if population is not None:
+                refuse_deepsets(net, "policy_rollout_population")
+            enc = binder.encoder(net)
         next_obs = self._check_tensor(next_obs, (E, D), torch.float32, "next_obs")
         next_done = self._check_tensor(next_done, (E,), torch.float32, "next_done")
         dev, f32 = self.device, torch.float32
@@ -627,7 +634,9 @@ class BatchedEvacuationEnv:
         args = [_ptr(next_obs), _ptr(next_done), _ptr(out["obs"]), _ptr(out["actions"]), _ptr(out["logprobs"]), _ptr(out["values"]),
                 _ptr(out["rewards"]), _ptr(out["dones"]), _ptr(out["next_value"]), _ptr(out["episode_stats"]), _ptr(state), gamma,
                 obs_clip, reward_clip, eps, self._stream()]
-        if population is None:
+        if enc is not None:
+            rc = self.lib.evac_policy_rollout_deepsets(self._h, T, C.byref(pol), *args[:-1], C.byref(enc), args[-1])
+        elif population is None:
             rc = self.lib.evac_policy_rollout(self._h, T, C.byref(pol), *args)
         elif hypers is not None:
             rc = self.lib.evac_policy_rollout_sweep(self._h, population.num_learners, C.byref(pol), C.byref(population.strides), T,
@@ -651,20 +660,24 @@ class BatchedEvacuationEnv:
         pass the returned tensors again to continue where the call stopped (bit-identical to one long call); an env with
         ``progress[e, 0] >= n_episodes`` does nothing.  Returns ``(progress, out)``; both are made (zeroed) when not given.
         ``_norm = (norm_state, obs_clip, epsilon)``: the trainer's observation statistics applied FROZEN (read only) -- see
-        ``NormalizedVectorEnv.policy_evaluate``.  No host synchronisation; capturable; the weights are read when the kernel runs."""
-        from .policy import MAX_PEDESTRIANS, PolicyBinder
+        ``NormalizedVectorEnv.policy_evaluate``.  No host synchronisation; capturable; the weights are read when the kernel runs.
+        A network with a set encoder (``deep_sets``) goes to ``evac_policy_evaluate_deepsets``."""
+        from .policy import MAX_PEDESTRIANS, PolicyBinder, is_deepsets
         check_evaluate_args(agent, n_episodes, max_steps, _norm)
         if self.n_ped > MAX_PEDESTRIANS:
             raise NotImplementedError(f"policy_evaluate runs one wave per env: rooms of at most {MAX_PEDESTRIANS} pedestrians "
                                       f"(this env has {self.n_ped})")
         K, T, E, D = int(n_episodes), int(max_steps), self.num_envs, self.obs_dim
+        enc = None
         if isinstance(agent, str):
             code, pol = EVALUATE_AGENTS[agent], None
         else:
             binder = getattr(self, "_policy_binder", None)
             if binder is None:
-                binder = self._policy_binder = PolicyBinder(D, self.device)
+                binder = self._policy_binder = PolicyBinder(D, self.device, self.n_ped)
             code, pol = (_lib.AGENT_POLICY_MEAN if deterministic else _lib.AGENT_POLICY_SAMPLE), C.byref(binder(agent))
+            if is_deepsets(agent):
+                enc = binder.encoder(agent)
         if progress is None:
             progress = torch.zeros((E, 4), dtype=torch.int32, device=self.device)
         else:
@@ -676,8 +689,13 @@ class BatchedEvacuationEnv:
         state, obs_clip, eps = (None, 0.0, 0.0) if _norm is None else _norm
         if state is not None:
             self._check_tensor(state, (E, 3 * D + 4), torch.float64, "norm_state")
-        _lib.check(self.lib.evac_policy_evaluate(self._h, code, pol, K, T, _ptr(progress), _ptr(out), _ptr(state), obs_clip, eps,
-                                                 self._stream()), self._h)
+        if enc is not None:
+            rc = self.lib.evac_policy_evaluate_deepsets(self._h, code, pol, K, T, _ptr(progress), _ptr(out), _ptr(state), obs_clip, eps,
+                                                        C.byref(enc), self._stream())
+        else:
+            rc = self.lib.evac_policy_evaluate(self._h, code, pol, K, T, _ptr(progress), _ptr(out), _ptr(state), obs_clip, eps,
+                                               self._stream())
+        _lib.check(rc, self._h)
         return progress, out
 
     def observe(self, out: Optional[torch.Tensor] = None):

@@ -481,6 +481,40 @@ int evac_policy_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t
                          evac_episode_stats_t* episodes_out,  /* [n_episodes][E] */
                          const double* norm_state_or_null, float obs_clip, float epsilon, void* stream);
 
+/* ---- The deep-sets leader: the reference's set encoder in front of the actor-critic (rpo_deep_sets_agent_network.py:25-90) ----
+ * RPODeepSetsEmbedding reads the Box observation x [D] as a set of S = N + 2 rows (pedestrians, leader, exit) of
+ * set_elem_dim = D / S floats (6: positions + one-hot status, 3: positions + categorical status, 2: positions only):
+ *   phi(x_i) = phi_w2 . relu(phi_w1 x_i + phi_b1) + phi_b2     phi_w1 [24][set_elem_dim], phi_b1 [24], phi_w2 [24][24], phi_b2 [24]
+ *   y = rho_w . sum_i phi(x_i) + rho_b                          rho_w [D][24], rho_b [D]
+ * and actor_mean(y) / critic(y) of evac_mlp_policy_t.  One encoder serves actor and critic.  x is what evac_policy_rollout's
+ * network reads -- after the normalisation chain when norm_state is given -- and what goes into obs_out: y is never stored.
+ * The kernels pool above the relu, sum_i phi(x_i) = phi_w2 . (sum_i relu(phi_w1 x_i + phi_b1)) + S phi_b2: the same function,
+ * rounded elsewhere; every sum has a fixed order (evac_deepsets.h), so results do not depend on the batch, the launch or the run.
+ * Tensors in torch layouts, float32, read in place when the kernel runs; rho_w 16-byte aligned (its rows are read as vectors). */
+typedef struct evac_deepsets {
+    int32_t set_elem_dim;      /* set_elem_dim x (N + 2) == evac_obs_dim(h): a Box observation */
+    int32_t hidden;            /* 24 (RPODeepSetsEmbeddingConfig.dim_hidden, the only width taken) */
+    const float *phi_w1, *phi_b1, *phi_w2, *phi_b2;
+    const float *rho_w, *rho_b;
+} evac_deepsets_t;
+/* evac_policy_rollout with the encoder run on x before every step's forward pass and before the bootstrap value: arguments,
+ * storage, env side (bit for bit) and refusals are evac_policy_rollout's.  Further EVAC_ERR_INVALID_ARGUMENT: a NULL encoder or
+ * tensor of it, hidden != 24, set_elem_dim x (N + 2) != evac_obs_dim(h) (the gravity observation included), a misaligned rho_w. */
+int evac_policy_rollout_deepsets(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_t* policy,
+                                 float* next_obs, float* next_done,
+                                 float* obs_out, float* actions_out, float* logprob_out,
+                                 float* value_out, float* reward_out, float* done_out,
+                                 float* next_value_out, evac_episode_stats_t* final_stats_or_null,
+                                 double* norm_state_or_null, float gamma, float obs_clip, float reward_clip, float epsilon,
+                                 const evac_deepsets_t* encoder, void* stream);
+/* evac_policy_evaluate for the policy agents with the encoder run before the actor: a = actor_mean(y) (+ sigma z).  Sample mode
+ * is evac_policy_rollout_deepsets bit for bit.  EVAC_ERR_INVALID_ARGUMENT as evac_policy_evaluate and as above, and for
+ * EVAC_AGENT_VACUUM_CLEANER (no network: evac_policy_evaluate runs it). */
+int evac_policy_evaluate_deepsets(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy,
+                                  int32_t n_episodes, int32_t max_steps, int32_t* progress, evac_episode_stats_t* episodes_out,
+                                  const double* norm_state_or_null, float obs_clip, float epsilon,
+                                  const evac_deepsets_t* encoder, void* stream);
+
 /* ---- The trainer's update: the other half of RPOAgent.learn() (rpo_agent.py:205-283) for the network above ----
  * No handle: buffers, sizes and a stream; arguments are validated on the host before anything touches a device, and errors
  * come back through the return code alone (evac_last_error keeps its meaning for handles).
