@@ -1459,12 +1459,8 @@ static int policy_rollout(evac_handle_t h, const char* what, int32_t n_learners,
     if (!policy || !next_obs || !next_done || !obs_out || !actions_out || !logprob_out || !value_out || !reward_out || !done_out ||
         !next_value_out)
         return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": policy and every output buffer but final_stats / norm_state must be non-NULL");
-    const evac_mlp_policy_t& P = *policy;
-    if (!mlp_all_set(P)) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": a tensor pointer of the policy is NULL");
-    if (P.hidden != evac::kHidden) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": hidden must be 64");
-    if (P.obs_dim != h->p.obs_dim)
-        return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": policy obs_dim " + std::to_string(P.obs_dim) + " != evac_obs_dim " +
-                                                      std::to_string(h->p.obs_dim));
+    evac::PolicyArgs a{};
+    if (const std::string why = mlp_policy_check(*policy, h->p.obs_dim, a); !why.empty()) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
     if ((uintptr_t)actions_out & 7u) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": actions_out must be 8-byte aligned");
     evac::PopulationArgs q{};
     if (strides) {
@@ -1473,14 +1469,8 @@ static int policy_rollout(evac_handle_t h, const char* what, int32_t n_learners,
         if (h->p.n_envs % n_learners != 0)
             return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the handle's " + std::to_string(h->p.n_envs) + " envs are not " +
                                                           std::to_string(n_learners) + " learners' equal shares");
-        // learner s + 1's tensor lies at least one tensor beyond learner s's (a stride of 0 would alias them)
-        const int64_t H = evac::kHidden, D = P.obs_dim;
-        const int64_t least[kMlpTensors] = {H * D, H, H * H, H, 2 * H, 2, 2, H * D, H, H * H, H, H, 1};
-        for (int i = 0; i < kMlpTensors; ++i) {
-            q.stride[i] = (&strides->actor_w1)[i];
-            if (n_learners > 1 && q.stride[i] < least[i])
-                return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": a learner stride is smaller than its tensor");
-        }
+        if (!mlp_strides_ok(strides, policy->obs_dim, n_learners, q.stride))
+            return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": a learner stride is smaller than its tensor");
         q.envs_per_learner = h->p.n_envs / n_learners;
         q.wgs = (q.envs_per_learner + evac::PolicyFamily::kEnvsPerBlock - 1) / evac::PolicyFamily::kEnvsPerBlock;
     }
@@ -1490,37 +1480,23 @@ static int policy_rollout(evac_handle_t h, const char* what, int32_t n_learners,
     // (parts / chained / persistent handles: joined first, then ONE kernel on `stream` over the whole batch)
     if (const int st = settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
     DeviceGuard g(h->device);
-    const evac::PolicyArgs a{P.actor_w1, P.actor_b1, P.actor_w2, P.actor_b2, P.actor_w3, P.actor_b3, P.actor_logstd,
-                             P.critic_w1, P.critic_b1, P.critic_w2, P.critic_b2, P.critic_w3, P.critic_b3,
-                             next_obs, next_done, obs_out, actions_out, logprob_out, value_out, reward_out, done_out, next_value_out,
-                             final_stats};
+    a.next_obs = next_obs; a.next_done = next_done; a.obs_out = obs_out; a.actions_out = actions_out; a.logprob_out = logprob_out;
+    a.value_out = value_out; a.reward_out = reward_out; a.done_out = done_out; a.next_value_out = next_value_out;
+    a.final_stats = final_stats;
     const evac::NormArgs na{norm_state, gamma, obs_clip, reward_clip, epsilon};
     const bool grav = h->p.obs_pos == EVAC_POS_GRAV, norm = norm_state != nullptr, def = h->default_cfg;
     const dim3 block(evac::PolicyFamily::kBlock);
     if (strides && hypers && norm) {                   // (without the chain gamma does not enter collection)
-        using evac::k_collect_sweep;
-        void (*fn)(evac::Params, int, evac::PolicyArgs, evac::NormArgs, evac::PopulationArgs, evac::LearnerGammas) =
-            grav ? (def ? k_collect_sweep<true, true> : k_collect_sweep<true, false>)
-                 : (def ? k_collect_sweep<false, true> : k_collect_sweep<false, false>);
+        const auto fn = EVAC_PICK_BOOL2(evac::k_collect_sweep, grav, def);
         hipLaunchKernelGGL(fn, dim3((unsigned)(n_learners * q.wgs)), block, 0, (hipStream_t)stream, h->p, (int)n_steps, a, na, q, lg);
         return check_launch(h, what);
     }
     if (strides) {
-        using evac::k_collect_population;
-        void (*fn)(evac::Params, int, evac::PolicyArgs, evac::NormArgs, evac::PopulationArgs) =
-            grav ? (norm ? (def ? k_collect_population<true, true, true> : k_collect_population<true, true, false>)
-                         : (def ? k_collect_population<true, false, true> : k_collect_population<true, false, false>))
-                 : (norm ? (def ? k_collect_population<false, true, true> : k_collect_population<false, true, false>)
-                         : (def ? k_collect_population<false, false, true> : k_collect_population<false, false, false>));
+        const auto fn = EVAC_PICK_BOOL3(evac::k_collect_population, grav, norm, def);
         hipLaunchKernelGGL(fn, dim3((unsigned)(n_learners * q.wgs)), block, 0, (hipStream_t)stream, h->p, (int)n_steps, a, na, q);
         return check_launch(h, what);
     }
-    using evac::k_policy_rollout;
-    void (*fn)(evac::Params, int, evac::PolicyArgs, evac::NormArgs) =
-        grav ? (norm ? (def ? k_policy_rollout<true, true, true> : k_policy_rollout<true, true, false>)
-                     : (def ? k_policy_rollout<true, false, true> : k_policy_rollout<true, false, false>))
-             : (norm ? (def ? k_policy_rollout<false, true, true> : k_policy_rollout<false, true, false>)
-                     : (def ? k_policy_rollout<false, false, true> : k_policy_rollout<false, false, false>));
+    const auto fn = EVAC_PICK_BOOL3(evac::k_policy_rollout, grav, norm, def);
     const int per_block = evac::PolicyFamily::kEnvsPerBlock;
     hipLaunchKernelGGL(fn, dim3((unsigned)((h->p.n_envs + per_block - 1) / per_block)), block, 0, (hipStream_t)stream, h->p,
                        (int)n_steps, a, na);
@@ -1550,6 +1526,7 @@ int evac_policy_rollout_population(evac_handle_t h, int32_t n_learners, const ev
 }
 
 static_assert(sizeof(evac::LearnerGammas) == EVAC_MAX_LEARNERS * sizeof(float), "evac::LearnerGammas holds EVAC_MAX_LEARNERS values");
+static_assert(evac::kHidden == kMlpHidden, "mlp_policy_check and mlp_sizes: the width the policy kernels take");
 static_assert(sizeof(evac::Params) + 8 + sizeof(evac::PolicyArgs) + sizeof(evac::NormArgs) + sizeof(evac::PopulationArgs) +
                       sizeof(evac::LearnerGammas) <= 4096, "k_collect_sweep: arguments beyond the kernel-argument segment");
 
@@ -1599,14 +1576,8 @@ int evac_policy_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t
     evac::PolicyArgs a{};
     if (!scripted) {
         if (!policy) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: a policy agent needs a policy");
-        const evac_mlp_policy_t& P = *policy;
-        if (!mlp_all_set(P)) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: a tensor pointer of the policy is NULL");
-        if (P.hidden != evac::kHidden) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: hidden must be 64");
-        if (P.obs_dim != h->p.obs_dim)
-            return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: policy obs_dim " + std::to_string(P.obs_dim) +
-                                                          " != evac_obs_dim " + std::to_string(h->p.obs_dim));
-        a = evac::PolicyArgs{P.actor_w1, P.actor_b1, P.actor_w2, P.actor_b2, P.actor_w3, P.actor_b3, P.actor_logstd,
-                             P.critic_w1, P.critic_b1, P.critic_w2, P.critic_b2, P.critic_w3, P.critic_b3};
+        if (const std::string why = mlp_policy_check(*policy, h->p.obs_dim, a); !why.empty())
+            return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate" + why);
     }
     if (h->p.n_ped > evac::kWave)
         return fail(h, EVAC_ERR_UNSUPPORTED, "evac_policy_evaluate: rooms of more than 64 pedestrians are not supported (one wave per env)");
@@ -1628,12 +1599,7 @@ int evac_policy_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t
         hipLaunchKernelGGL(def ? k_policy_evaluate_scripted<true> : k_policy_evaluate_scripted<false>, grid, block, 0,
                            (hipStream_t)stream, h->p, ev);
     } else {
-        using evac::k_policy_evaluate;
-        void (*fn)(evac::Params, evac::PolicyArgs, evac::EvalArgs) =
-            grav ? (norm ? (def ? k_policy_evaluate<true, true, true> : k_policy_evaluate<true, true, false>)
-                         : (def ? k_policy_evaluate<true, false, true> : k_policy_evaluate<true, false, false>))
-                 : (norm ? (def ? k_policy_evaluate<false, true, true> : k_policy_evaluate<false, true, false>)
-                         : (def ? k_policy_evaluate<false, false, true> : k_policy_evaluate<false, false, false>));
+        const auto fn = EVAC_PICK_BOOL3(evac::k_policy_evaluate, grav, norm, def);
         hipLaunchKernelGGL(fn, grid, block, 0, (hipStream_t)stream, h->p, a, ev);
     }
     return check_launch(h, "evac_policy_evaluate");

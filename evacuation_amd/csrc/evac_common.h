@@ -31,6 +31,8 @@ constexpr float kRPed2Big = kRPed2 * 0x1.0p80f;        // r_ped^2 * 2^80, exact:
 constexpr uint32_t kFlagNewExitingReward = 1u, kFlagNewFollowersReward = 2u, kFlagTermOnWall = 4u, kFlagNanGuard = 8u,
                    kFlagClipAction = 16u;
 constexpr int kWave = 64;
+constexpr int kMaxLearners = 64;                // EVAC_MAX_LEARNERS: a population's per-learner values travel by value in the kernel arguments
+static_assert(kMaxLearners == EVAC_MAX_LEARNERS, "every per-learner array of the kernels' arguments holds EVAC_MAX_LEARNERS values");
 constexpr int kStageSteps = 7, kGravRow = 9;   // 7 steps x (6 obs + reward + terminated + truncated) = 63 words <= 64 lanes
 // Cell list of the workgroup-per-env kernels (evac_families.h, Cells): kCellsX x kCellsY cells over the room.
 // A cell is at least 0.125 wide (host: evac_create), i.e. wider than the pedestrian radius 0.1 by far more than any

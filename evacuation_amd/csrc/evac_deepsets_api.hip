@@ -27,12 +27,9 @@ int check_networks(evac_handle_t h, const std::string& w, const evac_host::Handl
                    const evac_deepsets_t* encoder, evac::PolicyArgs& a, evac::DeepSetsArgs& da) {
     if (!policy) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": policy is NULL");
     if (!encoder) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": encoder is NULL");
-    const evac_mlp_policy_t& P = *policy;
-    if (!mlp_all_set(P)) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": a tensor pointer of the policy is NULL");
-    if (P.hidden != evac::kHidden) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": hidden must be 64");
-    if (P.obs_dim != v.p.obs_dim)
-        return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": policy obs_dim " + std::to_string(P.obs_dim) + " != evac_obs_dim " +
-                                                             std::to_string(v.p.obs_dim));
+    evac::PolicyArgs pa{};                             // (`a` and `da` are written only once every check has passed)
+    if (const std::string why = mlp_policy_check(*policy, v.p.obs_dim, pa); !why.empty())
+        return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
     const evac_deepsets_t& S = *encoder;
     if (!S.phi_w1 || !S.phi_b1 || !S.phi_w2 || !S.phi_b2 || !S.rho_w || !S.rho_b)
         return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": a tensor pointer of the encoder is NULL");
@@ -45,8 +42,7 @@ int check_networks(evac_handle_t h, const std::string& w, const evac_host::Handl
                                                              std::to_string(v.p.n_ped) + " + 2) elements is not the observation's " +
                                                              std::to_string(v.p.obs_dim) + " floats (a Box observation is needed)");
     if ((uintptr_t)S.rho_w & 15u) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": rho_w must be 16-byte aligned");
-    a = evac::PolicyArgs{P.actor_w1, P.actor_b1, P.actor_w2, P.actor_b2, P.actor_w3, P.actor_b3, P.actor_logstd,
-                         P.critic_w1, P.critic_b1, P.critic_w2, P.critic_b2, P.critic_w3, P.critic_b3};
+    a = pa;
     da = evac::DeepSetsArgs{S.phi_w1, S.phi_b1, S.phi_w2, S.phi_b2, S.rho_w, S.rho_b, (int)S.set_elem_dim};
     return EVAC_OK;
 }
@@ -79,10 +75,7 @@ int evac_policy_rollout_deepsets(evac_handle_t h, int32_t n_steps, const evac_ml
     a.final_stats = final_stats;
     const evac::NormArgs na{norm_state, gamma, obs_clip, reward_clip, epsilon};
     const bool norm = norm_state != nullptr, def = v.default_cfg;
-    using evac::k_policy_rollout_deepsets;
-    void (*fn)(evac::Params, int, evac::PolicyArgs, evac::NormArgs, evac::DeepSetsArgs) =
-        norm ? (def ? k_policy_rollout_deepsets<true, true> : k_policy_rollout_deepsets<true, false>)
-             : (def ? k_policy_rollout_deepsets<false, true> : k_policy_rollout_deepsets<false, false>);
+    const auto fn = EVAC_PICK_BOOL2(evac::k_policy_rollout_deepsets, norm, def);
     const int per_block = evac::PolicyFamily::kEnvsPerBlock;
     hipLaunchKernelGGL(fn, dim3((unsigned)((v.p.n_envs + per_block - 1) / per_block)), dim3(evac::PolicyFamily::kBlock), 0,
                        (hipStream_t)stream, v.p, (int)n_steps, a, na, da);
@@ -112,10 +105,7 @@ int evac_policy_evaluate_deepsets(evac_handle_t h, int32_t agent, const evac_mlp
     const evac::EvalArgs ev{(int4*)progress, episodes_out, norm_state, (int)n_episodes, (int)max_steps,
                             agent == EVAC_AGENT_POLICY_SAMPLE ? 1 : 0, obs_clip, epsilon, 0.0f, 0.0f};
     const bool norm = norm_state != nullptr, def = v.default_cfg;
-    using evac::k_policy_evaluate_deepsets;
-    void (*fn)(evac::Params, evac::PolicyArgs, evac::EvalArgs, evac::DeepSetsArgs) =
-        norm ? (def ? k_policy_evaluate_deepsets<true, true> : k_policy_evaluate_deepsets<true, false>)
-             : (def ? k_policy_evaluate_deepsets<false, true> : k_policy_evaluate_deepsets<false, false>);
+    const auto fn = EVAC_PICK_BOOL2(evac::k_policy_evaluate_deepsets, norm, def);
     const int per_block = evac::PolicyFamily::kEnvsPerBlock;
     hipLaunchKernelGGL(fn, dim3((unsigned)((v.p.n_envs + per_block - 1) / per_block)), dim3(evac::PolicyFamily::kBlock), 0,
                        (hipStream_t)stream, v.p, a, ev, da);

@@ -1,9 +1,12 @@
-// Host-only helpers shared by the translation units of libevac (evac_api.hip: the env; evac_train_api.hip: the trainer's
-// update): which device a call runs on, and the 13 tensors of the actor-critic as an array.
+// Host-only helpers shared by the five translation units of libevac: which device a call runs on; the 13 tensors of the
+// actor-critic as an array, their sizes, the check of a population's strides and of a policy against a handle; the picker of a
+// kernel template's instantiation over bools; what every entry refuses of evac_learner_hyper_t.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+
+#include <string>
 
 #include "../../include/evac.h"
 
@@ -43,6 +46,44 @@ inline bool mlp_all_set(const T& set) {
         if (!mlp_tensors(set)[i]) return false;
     return true;
 }
+
+// Their element counts at observation width D (hidden width 64, the only one the kernels take), in the same order.
+constexpr int kMlpHidden = 64;
+struct MlpSizes {
+    int64_t n[kMlpTensors];
+};
+inline MlpSizes mlp_sizes(int64_t D) {
+    const int64_t H = kMlpHidden;
+    return {{H * D, H, H * H, H, 2 * H, 2, 2, H * D, H, H * H, H, H, 1}};
+}
+// A population's strides into `out`: learner s + 1's tensor lies at least one tensor beyond learner s's (a stride of 0 would
+// make the learners share it).
+inline bool mlp_strides_ok(const evac_mlp_policy_strides_t* st, int32_t obs_dim, int32_t n_learners, int64_t* out) {
+    const MlpSizes least = mlp_sizes(obs_dim);
+    for (int i = 0; i < kMlpTensors; ++i) {
+        out[i] = (&st->actor_w1)[i];
+        if (n_learners > 1 && out[i] < least.n[i]) return false;
+    }
+    return true;
+}
+// A policy against a handle's observation width, for the entries that run it on a handle's envs (Args: evac::PolicyArgs, which
+// starts with the 13 pointers).  Empty and the pointers in `a` (the rest of it zero), or what is refused: the text that follows
+// the entry's name in its message.  The entry reports it through its own fail.
+template <class Args>
+inline std::string mlp_policy_check(const evac_mlp_policy_t& P, int32_t obs_dim, Args& a) {
+    if (!mlp_all_set(P)) return ": a tensor pointer of the policy is NULL";
+    if (P.hidden != kMlpHidden) return ": hidden must be 64";
+    if (P.obs_dim != obs_dim) return ": policy obs_dim " + std::to_string(P.obs_dim) + " != evac_obs_dim " + std::to_string(obs_dim);
+    a = Args{P.actor_w1, P.actor_b1, P.actor_w2, P.actor_b2, P.actor_w3, P.actor_b3, P.actor_logstd,
+             P.critic_w1, P.critic_b1, P.critic_w2, P.critic_b2, P.critic_w3, P.critic_b3};
+    return {};
+}
+
+// The instantiation of kernel template K over two or three bools that are known at run time (grav, norm, def of the callers).
+#define EVAC_PICK_BOOL2(K, b0, b1) ((b0) ? ((b1) ? K<true, true> : K<true, false>) : ((b1) ? K<false, true> : K<false, false>))
+#define EVAC_PICK_BOOL3(K, b0, b1, b2)                                                                                            \
+    ((b0) ? ((b1) ? ((b2) ? K<true, true, true> : K<true, true, false>) : ((b2) ? K<true, false, true> : K<true, false, false>)) \
+          : ((b1) ? ((b2) ? K<false, true, true> : K<false, true, false>) : ((b2) ? K<false, false, true> : K<false, false, false>)))
 
 // evac_learner_hyper_t [n_learners] (include/evac.h), for every entry that takes one: what the lone entries refuse of the same
 // values, for every learner.  (!(x > 0) also refuses a NaN.)

@@ -7,14 +7,12 @@
 
 namespace evac {
 
-constexpr int kMaxLearners = 64;                // EVAC_MAX_LEARNERS: seeds and counters travel by value (1 KiB of kernel arguments)
-
 struct LearnerStrides {
     int64_t p[kAdamTensors], g[kAdamTensors], m[kAdamTensors];   // floats: parameters, gradients, moments (both of them)
     int64_t hdr, ws;                            // bytes
     int64_t inds, stats, noise;                 // elements of perms / stats_out / rpo_noise per learner
 };
-struct LearnerDraws {
+struct LearnerDraws {                           // by value: 1 KiB of kernel arguments
     uint64_t seed[kMaxLearners], first_counter[kMaxLearners];
 };
 

@@ -362,8 +362,9 @@ __global__ __launch_bounds__(PolicyFamily::kBlock, 4) void k_collect_population(
 // The reference wraps a learner's env with its training gamma, so in a gamma sweep every learner's chain has its own.  The
 // values travel by value, indexed by the workgroup's learner (a scalar load from the kernel-argument segment); the body is
 // k_collect_population's.  Only with the chain does gamma enter collection, hence NORM = true alone.
+// TWIN: k_collect_sweep repeats k_collect_population's lines; change one, change the other.
 struct LearnerGammas {
-    float gamma[64];                            // (float)evac_learner_hyper_t.gamma of learner s; 64 = EVAC_MAX_LEARNERS
+    float gamma[kMaxLearners];                  // (float)evac_learner_hyper_t.gamma of learner s
 };
 template <bool GRAV, bool DEF>
 __global__ __launch_bounds__(PolicyFamily::kBlock, 4) void k_collect_sweep(Params p, int n_steps, PolicyArgs a, NormArgs na,

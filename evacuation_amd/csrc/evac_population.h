@@ -29,7 +29,7 @@ __global__ __launch_bounds__(kFinishBlock) void k_population_adv_stats(RpoArgs a
     if (rpo_stopped(learner_header(gate, q, s))) return;
     rpo_adv_stats_body(learner_rpo_args(a, q, d, s), buf);
 }
-// grid (P, 2, S)
+// grid (P, 2, S).  TWIN: k_sweep_grad (evac_sweep.h) repeats these lines; change one, change the other
 __global__ __launch_bounds__(kGradBlock) void k_population_grad(RpoArgs a, LearnerStrides q, LearnerDraws d, const AdamHeader* gate) {
     extern __shared__ __attribute__((aligned(16))) float population_lds[];
     const int s = (int)blockIdx.z;
@@ -41,6 +41,7 @@ __global__ __launch_bounds__(kGradBlock) void k_population_grad(RpoArgs a, Learn
 }
 // grid (10 + 2 x tiles x segments, S).  The finishing body picks its net's pointers at run time (a.net[net]): the learner's
 // arguments are formed once, by thread 0, and lie in LDS -- registers cannot be indexed, and a private copy would be scratch.
+// TWIN: k_sweep_finish (evac_sweep.h); change one, change the other.
 __global__ __launch_bounds__(kFinishBlock) void k_population_finish(RpoArgs a, LearnerStrides q, LearnerDraws d, const AdamHeader* gate) {
     __shared__ RpoArgs mine;
     const int s = (int)blockIdx.y;
@@ -52,6 +53,7 @@ __global__ __launch_bounds__(kFinishBlock) void k_population_finish(RpoArgs a, L
 // grid (ceil(elements / 256), S); `a` as evac_rpo_update sets it (gated), sumsq / stats pointing into learner 0's statistics row.
 // The learner's 4 x 13 pointers are formed by 13 threads and lie in LDS: adam_stage picks a thread's tensor with per-lane
 // selects, so they end in vector registers either way, and 52 shifted pointers at once would not fit the scalar registers.
+// TWIN: k_sweep_optimizer (evac_sweep.h); change one, change the other.
 __global__ __launch_bounds__(kAdamBlock) void k_population_optimizer(AdamArgs a, LearnerStrides q) {
     __shared__ AdamArgs mine;
     const int s = (int)blockIdx.y, t = (int)threadIdx.x;

@@ -1,5 +1,5 @@
 // Host side of the population's update, the part its two translation units share (evac_population_api.hip: one configuration;
-// evac_sweep_api.hip: a configuration per learner): the checks and the learners' strides, and the two launches of
+// evac_sweep_api.hip: a configuration per learner): the checks and the learners' strides, a step's grids, and the two launches of
 // evac_population_api.hip that the sweep reuses (no hyperparameter enters them), reached through plain host functions so that
 // evac_population.h's kernels are defined in one translation unit alone.
 #pragma once
@@ -21,15 +21,16 @@ inline int64_t slice_bytes(int32_t obs_dim, int64_t n_minibatch) {
     const int64_t one = evac_rpo_workspace_bytes(obs_dim, n_minibatch);
     return one < 0 ? one : (one + kSliceAlign - 1) / kSliceAlign * kSliceAlign;
 }
-// learner s + 1's tensor lies at least one tensor beyond learner s's (a stride of 0 would make the learners share it)
-inline bool strides_ok(const evac_mlp_policy_strides_t* st, int32_t obs_dim, int32_t n_learners, int64_t* out) {
-    const int64_t H = evac::kTrainHidden, D = obs_dim;
-    const int64_t least[kMlpTensors] = {H * D, H, H * H, H, 2 * H, 2, 2, H * D, H, H * H, H, H, 1};
-    for (int i = 0; i < kMlpTensors; ++i) {
-        out[i] = (&st->actor_w1)[i];
-        if (n_learners > 1 && out[i] < least[i]) return false;
-    }
-    return true;
+// The grids of a step's gradient, finishing and optimiser launches for L learners (the one-learner kernels' with the learner as
+// one more dimension) and the gradient kernel's dynamic LDS
+struct LearnerGrids {
+    dim3 grad, finish, optimizer;
+    size_t lds;
+};
+inline LearnerGrids learner_grids(const evac::RpoArgs& a, const evac::AdamArgs& o, unsigned L) {
+    const int tiles = (a.D + evac::kW1Tile - 1) / evac::kW1Tile, n = o.end[evac::kAdamTensors - 1];
+    return {dim3((unsigned)a.P, 2u, L), dim3((unsigned)(2 * evac::kFinishCombineWgs + 2 * tiles * a.S), L),
+            dim3((unsigned)((n + evac::kAdamBlock - 1) / evac::kAdamBlock), L), evac::rpo_grad_lds_floats(a.D) * sizeof(float)};
 }
 // What evac_rpo_update_population checks and sets up: learner 0's argument structs, the learners' strides and draws.
 inline int population_prepare(int32_t n_learners, const evac_mlp_policy_t* policy, const evac_mlp_policy_grads_t* params,
@@ -49,15 +50,13 @@ inline int population_prepare(int32_t n_learners, const evac_mlp_policy_t* polic
     rc = adam_prepare(params, grads, state, adam_cfg, policy->obs_dim, o);
     if (rc != EVAC_OK) return rc;
     q = evac::LearnerStrides{};
-    if (!strides_ok(param_strides, a.D, n_learners, q.p) || !strides_ok(grad_strides, a.D, n_learners, q.g) ||
-        !strides_ok(moment_strides, a.D, n_learners, q.m))
+    if (!mlp_strides_ok(param_strides, a.D, n_learners, q.p) || !mlp_strides_ok(grad_strides, a.D, n_learners, q.g) ||
+        !mlp_strides_ok(moment_strides, a.D, n_learners, q.m))
         return EVAC_ERR_INVALID_ARGUMENT;
     if (n_learners > 1 && (header_stride_bytes < (int64_t)sizeof(evac::AdamHeader) || (header_stride_bytes & 7) != 0))
         return EVAC_ERR_INVALID_ARGUMENT;
-    const int64_t B = learner_batch_size, M = n_minibatch, least = a.norm_adv ? 2 : 1;
-    int64_t steps = 0;                                 // of one learner, in the whole call
-    for (int64_t start = 0; start < B; start += M) steps += (B - start < M ? B - start : M) >= least;
-    steps *= n_epochs;
+    const int64_t B = learner_batch_size, M = n_minibatch;
+    const int64_t steps = rpo_steps_per_epoch(B, M, a.norm_adv ? 2 : 1) * n_epochs;     // of one learner, in the whole call
     q.hdr = header_stride_bytes;
     q.ws = slice_bytes(a.D, M);
     q.inds = (int64_t)n_epochs * B;

@@ -29,7 +29,8 @@ __device__ __forceinline__ RpoArgs learner_loss_args(RpoArgs a, const LearnerLos
 }
 
 // k_gae (evac_train_api.hip) with the learner's pair: env e is learner e / E_l's.  A learner's boundary may fall inside a wave,
-// so the pair is read per lane.  The arithmetic is k_gae's, operation for operation.
+// so the pair is read per lane.  The arithmetic is k_gae's, operation for operation.  TWIN: change one, change the other (a shared
+// body changes both kernels' instructions: DESIGN.md section 4.11); likewise the three kernels below and evac_population.h's.
 __global__ __launch_bounds__(256) void k_sweep_advantages(int T, int64_t E, const float* __restrict__ rewards,
                                                           const float* __restrict__ values, const float* __restrict__ dones,
                                                           const float* __restrict__ next_value, const float* __restrict__ next_done,
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(256) void k_sweep_advantages(int T, int64_t E, cons
     }
 }
 
-// grid (P, 2, S): k_population_grad with the learner's clip / ent / vf / alpha
+// grid (P, 2, S): k_population_grad with the learner's clip / ent / vf / alpha (TWIN of it)
 __global__ __launch_bounds__(kGradBlock) void k_sweep_grad(RpoArgs a, LearnerStrides q, LearnerDraws d, LearnerLoss h,
                                                            const AdamHeader* gate) {
     extern __shared__ __attribute__((aligned(16))) float sweep_lds[];
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(kGradBlock) void k_sweep_grad(RpoArgs a, LearnerStr
     else rpo_grad_body<false>(la, sweep_lds);
 }
 // grid (10 + 2 x tiles x segments, S): k_population_finish with the learner's coefficients (the body reads ent and vf: the
-// entropy's gradient of logstd and the logged loss)
+// entropy's gradient of logstd and the logged loss).  TWIN of k_population_finish.
 __global__ __launch_bounds__(kFinishBlock) void k_sweep_finish(RpoArgs a, LearnerStrides q, LearnerDraws d, LearnerLoss h,
                                                                const AdamHeader* gate) {
     __shared__ RpoArgs mine;
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(kFinishBlock) void k_sweep_finish(RpoArgs a, Learne
     __syncthreads();
     rpo_finish_body<const RpoArgs&>(mine);
 }
-// grid (ceil(elements / 256), S): k_population_optimizer with the learner's lr, max_norm and target
+// grid (ceil(elements / 256), S): k_population_optimizer with the learner's lr, max_norm and target (TWIN of it)
 __global__ __launch_bounds__(kAdamBlock) void k_sweep_optimizer(AdamArgs a, LearnerStrides q, LearnerSteps h) {
     __shared__ AdamArgs mine;
     const int s = (int)blockIdx.y, t = (int)threadIdx.x;

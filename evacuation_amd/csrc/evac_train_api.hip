@@ -5,7 +5,6 @@
 
 #include <cstddef>
 #include <cstdint>
-#include <mutex>
 
 #include "evac_train_host.h"
 
@@ -15,6 +14,7 @@ namespace evac {
 // ---- rpo_agent.py:205-220: advantages[t] = delta_t + gamma lambda nonterminal_{t+1} advantages[t+1], one lane per env ----
 // The reference's torch ops, operation for operation (every product and sum rounded: no fma), so the result is bit-equal to the
 // float32 loop on the CPU.  `gl` = (float)(gamma * gae_lambda), the product formed in double and rounded once (Python floats).
+// TWIN: k_sweep_advantages (evac_sweep.h) repeats the loop; change one, change the other.
 __global__ __launch_bounds__(256) void k_gae(int T, int64_t E, const float* __restrict__ rewards, const float* __restrict__ values,
                                              const float* __restrict__ dones, const float* __restrict__ next_value,
                                              const float* __restrict__ next_done, float gamma, float gl, float* __restrict__ adv_out,
@@ -65,24 +65,6 @@ int64_t evac_rpo_workspace_bytes(int32_t obs_dim, int64_t n_minibatch) {
 }
 
 namespace {
-// wide observations: more dynamic LDS than the default limit; once per device and kernel
-int rpo_raise_lds(const evac::RpoArgs& a, int dev, bool gated) {
-    if (evac::rpo_grad_lds_floats(a.D) * sizeof(float) <= 64 * 1024) return EVAC_OK;
-    static std::mutex mu;
-    static bool raised[2][64] = {};
-    std::lock_guard<std::mutex> lock(mu);
-    const int slot = dev >= 0 && dev < 64 ? dev : 0;
-    if (!raised[gated][slot]) {
-        const size_t most = evac::rpo_grad_lds_floats(evac::kTrainMaxObs) * sizeof(float);
-        const void* fn = gated ? (const void*)evac::k_rpo_grad<const evac::AdamHeader*> : (const void*)evac::k_rpo_grad<>;
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) != hipSuccess) {
-            (void)hipGetLastError();
-            return EVAC_ERR_HIP;
-        }
-        raised[gated][slot] = true;
-    }
-    return EVAC_OK;
-}
 // the launches of one minibatch's gradient; `gate` = the optimiser's header whose stop flag the kernels honour, or NULL
 void rpo_launch(const evac::RpoArgs& a, hipStream_t S, const evac::AdamHeader* gate) {
     const size_t lds = evac::rpo_grad_lds_floats(a.D) * sizeof(float);
@@ -122,7 +104,7 @@ int rpo_minibatch(const evac_mlp_policy_t* policy, const evac_rpo_loss_config_t*
     rpo_shape(a, n_minibatch, draw_counter);
     const int dev = device_of(workspace);
     DeviceGuard g(dev);
-    if (rpo_raise_lds(a, dev, false) != EVAC_OK) return EVAC_ERR_HIP;
+    if (rpo_raise_lds<evac::k_rpo_grad<>>(a.D, dev) != EVAC_OK) return EVAC_ERR_HIP;
     rpo_launch(a, (hipStream_t)stream, nullptr);
     if (adam) adam_launch(o, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? EVAC_OK : EVAC_ERR_HIP;
@@ -179,32 +161,18 @@ int evac_rpo_update(const evac_mlp_policy_t* policy, const evac_mlp_policy_grads
     o.target_kl = target_kl;
     const int dev = device_of(workspace);
     DeviceGuard g(dev);
-    if (rpo_raise_lds(a, dev, true) != EVAC_OK) return EVAC_ERR_HIP;
+    if (rpo_raise_lds<evac::k_rpo_grad<const evac::AdamHeader*>>(a.D, dev) != EVAC_OK) return EVAC_ERR_HIP;
     hipStream_t S = (hipStream_t)stream;
     // stop, steps_run, epochs_run (and the ticket, zero anyway)
     if (hipMemsetAsync((char*)state->header + offsetof(evac::AdamHeader, stop), 0, 16, S) != hipSuccess) {
         (void)hipGetLastError();
         return EVAC_ERR_HIP;
     }
-    const int64_t B = batch_size, M = n_minibatch, least = a.norm_adv ? 2 : 1;
-    uint64_t k = 0;
-    for (int32_t ep = 0; ep < n_epochs; ++ep) {
-        for (int64_t start = 0; start < B; start += M) {
-            const int64_t m = B - start < M ? B - start : M;
-            if (m < least) continue;                   // (the tail: as RPOTrainer.update() skips it)
-            const int64_t next = start + M, m_next = next >= B ? 0 : (B - next < M ? B - next : M);
-            a.inds = perms + (int64_t)ep * B + start;
-            a.noise = rpo_noise ? rpo_noise + k * (uint64_t)M * 2u : nullptr;
-            a.stats = stats_out + k * 8u;
-            rpo_shape(a, m, first_draw_counter + k);
-            o.sumsq = a.stats + 7;
-            o.stats = a.stats;
-            o.epoch_last = m_next < least;
-            rpo_launch(a, S, o.hdr);
-            adam_launch(o, S);
-            ++k;
-        }
-    }
+    rpo_update_steps(a, o, batch_size, n_minibatch, n_epochs, perms, rpo_noise, stats_out, first_draw_counter,
+                     [S](const evac::RpoArgs& step, const evac::AdamArgs& adam, uint64_t) {
+                         rpo_launch(step, S, adam.hdr);
+                         adam_launch(adam, S);
+                     });
     return hipGetLastError() == hipSuccess ? EVAC_OK : EVAC_ERR_HIP;
 }
 

@@ -1,5 +1,7 @@
-// Host side of the trainer's update, the part its two translation units share (evac_train_api.hip: one learner;
-// evac_population_api.hip: a population): what the entries check of their arguments and the kernels' argument structs.
+// Host side of the trainer's update, the part its three translation units share (evac_train_api.hip: one learner;
+// evac_population_api.hip: a population; evac_sweep_api.hip: ... with a configuration per learner): what the entries check of
+// their arguments, the kernels' argument structs, the walk over an update call's minibatch steps, and the raising of a gradient
+// kernel's dynamic-LDS limit.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,6 +9,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <mutex>
 
 #include "evac_host.h"
 #include "evac_train.h"
@@ -75,10 +78,9 @@ inline int adam_prepare(const evac_mlp_policy_grads_t* params, const evac_mlp_po
         if (!mlp_all_set(*sets[k])) return EVAC_ERR_INVALID_ARGUMENT;
         for (int i = 0; i < evac::kAdamTensors; ++i) dst[k][i] = mlp_tensors(*sets[k])[i];
     }
-    const int H = evac::kTrainHidden, D = obs_dim;
-    const int n[evac::kAdamTensors] = {H * D, H, H * H, H, 2 * H, 2, 2, H * D, H, H * H, H, H, 1};
+    const MlpSizes sizes = mlp_sizes(obs_dim);
     int end = 0;
-    for (int i = 0; i < evac::kAdamTensors; ++i) a.end[i] = (end += n[i]);
+    for (int i = 0; i < evac::kAdamTensors; ++i) a.end[i] = (end += (int)sizes.n[i]);
     a.hdr = (evac::AdamHeader*)state->header;
     a.sumsq = nullptr;
     a.stats = nullptr;
@@ -89,4 +91,64 @@ inline int adam_prepare(const evac_mlp_policy_grads_t* params, const evac_mlp_po
     return EVAC_OK;
 }
 static_assert(evac::kAdamTensors == kMlpTensors, "the optimiser walks the 13 tensors of evac_mlp_policy_grads_t");
+static_assert(evac::kTrainHidden == kMlpHidden, "mlp_sizes: the tensors of the width the trainer's kernels take");
+
+// The minibatch steps of an update call over a (learner's) batch of B samples: for every epoch the starts 0, M, 2M .., without a
+// tail shorter than `least` (as RPOTrainer.update() skips it).  step(epoch, start, m, epoch_last, k): m samples from `start`,
+// `epoch_last` when no step of this epoch follows, k the step's number in the call.  Returns the number of steps.
+template <class Step>
+inline uint64_t rpo_walk_steps(int64_t B, int64_t M, int32_t n_epochs, int64_t least, Step&& step) {
+    uint64_t k = 0;
+    for (int32_t ep = 0; ep < n_epochs; ++ep) {
+        for (int64_t start = 0; start < B; start += M) {
+            const int64_t m = B - start < M ? B - start : M;
+            if (m < least) continue;
+            const int64_t next = start + M, m_next = next >= B ? 0 : (B - next < M ? B - next : M);
+            step(ep, start, m, m_next < least, k);
+            ++k;
+        }
+    }
+    return k;
+}
+// ... of one epoch, counted alone (population_prepare: the stride of a learner's statistics and noise rows)
+inline int64_t rpo_steps_per_epoch(int64_t B, int64_t M, int64_t least) {
+    return (int64_t)rpo_walk_steps(B, M, 1, least, [](int32_t, int64_t, int64_t, bool, uint64_t) {});
+}
+// The step loop of evac_rpo_update and of the population's two entries: `a` and `o` as the prepare functions left them, set for
+// step k (its index list, noise row, statistics row, shape, draw counter `counter_base` + k, and whether it ends an epoch), then
+// launch(step k's RpoArgs, its AdamArgs, k), which enqueues the step's kernels.  Nothing here calls HIP or allocates.
+template <class Launch>
+inline void rpo_update_steps(evac::RpoArgs& a, evac::AdamArgs& o, int64_t B, int64_t M, int32_t n_epochs, const int64_t* perms,
+                             const float* rpo_noise, float* stats_out, uint64_t counter_base, Launch&& launch) {
+    rpo_walk_steps(B, M, n_epochs, a.norm_adv ? 2 : 1, [&](int32_t ep, int64_t start, int64_t m, bool epoch_last, uint64_t k) {
+        a.inds = perms + (int64_t)ep * B + start;
+        a.noise = rpo_noise ? rpo_noise + k * (uint64_t)M * 2u : nullptr;
+        a.stats = stats_out + k * 8u;
+        rpo_shape(a, m, counter_base + k);
+        o.sumsq = a.stats + 7;
+        o.stats = a.stats;
+        o.epoch_last = epoch_last;
+        launch(a, o, k);
+    });
+}
+
+// Wide observations: a gradient kernel needs more dynamic LDS than the default limit.  Once per device and kernel: the flags
+// belong to the instantiation, that is to `Kernel`'s address.
+template <auto Kernel>
+inline int rpo_raise_lds(int D, int dev) {
+    if (evac::rpo_grad_lds_floats(D) * sizeof(float) <= 64 * 1024) return EVAC_OK;
+    static std::mutex mu;
+    static bool raised[64] = {};
+    std::lock_guard<std::mutex> lock(mu);
+    const int slot = dev >= 0 && dev < 64 ? dev : 0;
+    if (!raised[slot]) {
+        const size_t most = evac::rpo_grad_lds_floats(evac::kTrainMaxObs) * sizeof(float);
+        if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) != hipSuccess) {
+            (void)hipGetLastError();
+            return EVAC_ERR_HIP;
+        }
+        raised[slot] = true;
+    }
+    return EVAC_OK;
+}
 }  // namespace

@@ -232,6 +232,60 @@ def test_update_equals_standalone_updates(ea, D, B_l, E_l, M, norm_adv, clip_vlo
         assert not same_bits(stats[0], stats[1])
 
 
+@pytest.mark.parametrize("B_l,norm_adv,target_kl,per_epoch", [
+    (37, 1, None, 5),                           # B_l mod M = 5: the tail runs
+    (33, 1, None, 4),                           # B_l mod M = 1 with norm_adv: the tail is skipped
+    (33, 0, None, 5),                           # ... and runs without it
+    (37, 1, 1e-6, 5),                           # every learner stops at its first epoch's end
+])
+def test_the_three_update_entries_walk_the_same_steps(ea, B_l, norm_adv, target_kl, per_epoch):
+    """evac_rpo_update, evac_rpo_update_population and evac_rpo_update_sweep share one step loop: from the same weights every
+    learner ends with the same bits whichever entry ran it.  The perturbation is drawn on the device at non-zero draw counters
+    that differ between the learners (the lone entry adds the counter on the host, the others in the kernel), and the shapes are
+    the smallest with a tail, an epoch boundary and a stop."""
+    import torch
+    from evacuation_amd import population, trainer
+    D, S, M, E_l, n_epochs, lr = 6, 2, 8, 1, 2, 1e-3
+    cfg = loss_cfg(norm_adv, 1, 0.01, 0.5)
+    cfg.target_kl = target_kl
+    seeds, firsts = [21, 34], [3, 11]
+    steps = n_epochs * per_epoch
+    assert steps == n_epochs * len(trainer.update_steps(B_l, M, bool(norm_adv)))
+    nets, batches = [], []
+    for s in range(S):
+        net, batch, *_ = build_case(D, B_l, "repeat", cfg, seed=400 + B_l + s)
+        nets.append(net)
+        batches.append(batch)
+    common = interleave(batches, E_l)
+    gen = torch.Generator().manual_seed(B_l)
+    perms = torch.stack([torch.stack([torch.randperm(B_l, generator=gen) for _ in range(n_epochs)]) for _ in range(S)]).to(DEV)
+    rows = population.population_rows(perms, torch.arange(S, device=DEV).reshape(S, 1, 1), E_l, S)
+    runs = []
+    for form in (cfg, [cfg] * S):                                    # one configuration: the population entry; a list: the sweep's
+        pop = load_population(ea, D, seeds, nets)
+        popt = population.PopulationAdam(pop, lr=lr)
+        stats = torch.full((S, steps, 8), -7.0, device=DEV)
+        population.rpo_update_population(pop, common, rows, form, popt, minibatch_size=M, seeds=seeds, first_draw_counters=firsts,
+                                         stats=stats)
+        runs.append((pop, popt, stats))
+    torch.cuda.synchronize()
+    ran = per_epoch if target_kl is not None else steps
+    for s in range(S):
+        opt = trainer.DeviceAdam(nets[s], lr=lr)
+        alone = torch.full((steps, 8), -7.0, device=DEV)
+        _, header = trainer.rpo_update(nets[s], batches[s], perms[s].contiguous(), cfg, opt, seed=seeds[s], first_draw_counter=firsts[s],
+                                       stats=alone, minibatch_size=M)
+        h = trainer.decode_header(header)
+        assert (h["steps_run"], h["epochs_run"], h["t"]) == (ran, ran // per_epoch, ran), h
+        assert not bool((alone[:ran] == -7.0).any()) and bool((alone[ran:] == -7.0).all())          # rows beyond steps_run: untouched
+        for (pop, popt, stats), entry in zip(runs, ("population", "sweep")):
+            hp = popt.learners[s].read_header()
+            assert (hp["steps_run"], hp["epochs_run"], hp["t"]) == (h["steps_run"], h["epochs_run"], h["t"]), (entry, s, hp, h)
+            assert_learner_equals(pop, popt, s, nets[s], opt, (entry, B_l, norm_adv, target_kl))
+            assert same_bits(stats[s], alone), (entry, B_l, norm_adv, target_kl, s)
+    assert not same_bits(runs[0][2][0, :ran], runs[0][2][1, :ran])
+
+
 # ------------------------------------------------------------------------------------------------ 3. target_kl
 def test_learners_stop_at_different_epochs(ea):
     """The inputs are chosen from the standalone runs: old log-probabilities that are the network's own and no perturbation, so
