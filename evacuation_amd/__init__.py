@@ -5,7 +5,7 @@ Public surface = the reference's ``src.env`` exports (src/env/__init__.py:3-21):
 ``BatchedEvacuationEnv``, its SyncVectorEnv-shaped host face ``HostVectorEnv``, the sharded form ``ShardedEvacuationEnv`` (across GPUs) and ``SplitBatchEnv`` (across streams of one GPU), and the reference trainer's update on
 the device (``RPOTrainer``, ``RPOTrainingConfig``, ``gae``, ``rpo_minibatch_grad``, and the optimiser
 step ``DeviceAdam``, ``rpo_minibatch_step``, ``rpo_update``: ``evacuation_amd.trainer``), and the evaluation of a fixed agent
-over whole episodes (``PolicyEvaluator``, ``EvaluationResult``, the scripted baseline ``WacuumCleaner``), and S independent
+over whole episodes (``PolicyEvaluator``, ``PopulationEvaluator``, ``EvaluationResult``, the scripted baseline ``WacuumCleaner``), and S independent
 learners of one configuration in one set of launches (``PolicyPopulation``, ``PopulationAdam``, ``PopulationTrainer``,
 ``rpo_update_population``: ``evacuation_amd.population``).  Importing the package does
 not touch the GPU; constructing an env loads libevac.so and fails loudly without it."""
@@ -15,7 +15,7 @@ from .statuses import Status
 __all__ = ["EnvConfig", "EnvWrappersConfig", "Status", "setup_env", "EvacuationEnv", "BatchedEvacuationEnv",
            "ShardedEvacuationEnv", "SplitBatchEnv", "NormalizedVectorEnv", "HostVectorEnv", "RandomAgent", "KernelOptions", "kernel_options",
            "RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad", "DeviceAdam", "rpo_minibatch_step", "rpo_update",
-           "WacuumCleaner", "PolicyEvaluator", "EvaluationResult",
+           "WacuumCleaner", "PolicyEvaluator", "PopulationEvaluator", "EvaluationResult",
            "PolicyPopulation", "PopulationAdam", "PopulationTrainer", "rpo_update_population"]
 
 
@@ -44,7 +44,7 @@ def __getattr__(name):   # lazy: keeps `import evacuation_amd` light and torch-f
     if name in ("RandomAgent", "WacuumCleaner"):
         from . import agents as _agents
         return getattr(_agents, name)
-    if name in ("PolicyEvaluator", "EvaluationResult"):      # whole-episode evaluation of a fixed agent on the device
+    if name in ("PolicyEvaluator", "PopulationEvaluator", "EvaluationResult"):      # whole-episode evaluation of a fixed agent on the device
         from . import evaluation as _evaluation
         return getattr(_evaluation, name)
     if name in ("RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad", "DeviceAdam", "rpo_minibatch_step", "rpo_update"):   # the trainer's update on the device

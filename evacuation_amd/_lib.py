@@ -163,6 +163,8 @@ SIGNATURES = {
     "evac_policy_rollout_population": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyStrides), C.c_int32,
                                                  _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "evac_policy_evaluate": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P]),
+    "evac_policy_evaluate_population": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyStrides), C.c_int32,
+                                                  C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P]),
     "evac_policy_rollout_deepsets": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                                C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(EvacDeepSets), _P]),
     "evac_policy_evaluate_deepsets": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float,

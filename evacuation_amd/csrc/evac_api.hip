@@ -1561,26 +1561,42 @@ static double as_written(float v) {
 }
 
 // ---- evac_policy_evaluate: whole episodes under a fixed agent, one record per finished episode (evac_evaluate.h) ----
-int evac_policy_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy, int32_t n_episodes, int32_t max_steps,
-                         int32_t* progress, evac_episode_stats_t* episodes_out, const double* norm_state, float obs_clip,
-                         float epsilon, void* stream) {
-    EVAC_REQUIRE_BOUND(h, "evac_policy_evaluate");
+// ... and evac_policy_evaluate_population (strides set, n_learners >= 1): the same checks, the learners' workgroups in one launch.
+static int policy_evaluate(evac_handle_t h, const char* what, int32_t n_learners, const evac_mlp_policy_strides_t* strides,
+                           int32_t shared_episodes, int32_t agent, const evac_mlp_policy_t* policy, int32_t n_episodes,
+                           int32_t max_steps, int32_t* progress, evac_episode_stats_t* episodes_out, const double* norm_state,
+                           float obs_clip, float epsilon, void* stream) {
+    const std::string w = what;
     const bool scripted = agent == EVAC_AGENT_VACUUM_CLEANER;
     if (agent != EVAC_AGENT_POLICY_MEAN && agent != EVAC_AGENT_POLICY_SAMPLE && !scripted)
-        return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: unknown agent " + std::to_string(agent));
-    if (!progress || !episodes_out) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: progress / episodes_out is NULL");
-    if (n_episodes < 1 || max_steps < 1) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: n_episodes and max_steps must be >= 1");
+        return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": unknown agent " + std::to_string(agent));
+    if (scripted && strides)
+        return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the scripted agent has no learners: evac_policy_evaluate runs it");
+    if (!progress || !episodes_out) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": progress / episodes_out is NULL");
+    if (n_episodes < 1 || max_steps < 1) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": n_episodes and max_steps must be >= 1");
     if (scripted && norm_state)
-        return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: the scripted agent reads no observation: norm_state must be NULL");
-    if ((uintptr_t)progress & 15u) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: progress must be 16-byte aligned");
+        return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the scripted agent reads no observation: norm_state must be NULL");
+    if ((uintptr_t)progress & 15u) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": progress must be 16-byte aligned");
     evac::PolicyArgs a{};
     if (!scripted) {
-        if (!policy) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate: a policy agent needs a policy");
+        if (!policy) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": a policy agent needs a policy");
         if (const std::string why = mlp_policy_check(*policy, h->p.obs_dim, a); !why.empty())
-            return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate" + why);
+            return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
+    }
+    evac::PopulationArgs q{};
+    if (strides) {
+        if (n_learners < 1 || n_learners > EVAC_MAX_LEARNERS)
+            return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": n_learners must be in 1.." + std::to_string(EVAC_MAX_LEARNERS));
+        if (h->p.n_envs % n_learners != 0)
+            return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the handle's " + std::to_string(h->p.n_envs) + " envs are not " +
+                                                          std::to_string(n_learners) + " learners' equal shares");
+        if (!mlp_strides_ok(strides, policy->obs_dim, n_learners, q.stride))
+            return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": a learner stride is smaller than its tensor");
+        q.envs_per_learner = h->p.n_envs / n_learners;
+        q.wgs = (q.envs_per_learner + evac::PolicyFamily::kEnvsPerBlock - 1) / evac::PolicyFamily::kEnvsPerBlock;
     }
     if (h->p.n_ped > evac::kWave)
-        return fail(h, EVAC_ERR_UNSUPPORTED, "evac_policy_evaluate: rooms of more than 64 pedestrians are not supported (one wave per env)");
+        return fail(h, EVAC_ERR_UNSUPPORTED, w + ": rooms of more than 64 pedestrians are not supported (one wave per env)");
     // (parts / chained / persistent handles: joined first, then ONE kernel on `stream` over the whole batch)
     if (const int st = settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
     DeviceGuard g(h->device);
@@ -1594,7 +1610,11 @@ int evac_policy_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t
     const int per_block = evac::PolicyFamily::kEnvsPerBlock;
     const dim3 grid((unsigned)((h->p.n_envs + per_block - 1) / per_block)), block(evac::PolicyFamily::kBlock);
     const bool grav = h->p.obs_pos == EVAC_POS_GRAV, norm = norm_state != nullptr, def = h->default_cfg;
-    if (scripted) {
+    if (strides) {
+        const auto fn = EVAC_PICK_BOOL3(evac::k_evaluate_population, grav, norm, def);
+        hipLaunchKernelGGL(fn, dim3((unsigned)(n_learners * q.wgs)), block, 0, (hipStream_t)stream, h->p, a, ev, q,
+                           (int)(shared_episodes != 0));
+    } else if (scripted) {
         using evac::k_policy_evaluate_scripted;
         hipLaunchKernelGGL(def ? k_policy_evaluate_scripted<true> : k_policy_evaluate_scripted<false>, grid, block, 0,
                            (hipStream_t)stream, h->p, ev);
@@ -1602,7 +1622,25 @@ int evac_policy_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t
         const auto fn = EVAC_PICK_BOOL3(evac::k_policy_evaluate, grav, norm, def);
         hipLaunchKernelGGL(fn, grid, block, 0, (hipStream_t)stream, h->p, a, ev);
     }
-    return check_launch(h, "evac_policy_evaluate");
+    return check_launch(h, what);
+}
+
+int evac_policy_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy, int32_t n_episodes, int32_t max_steps,
+                         int32_t* progress, evac_episode_stats_t* episodes_out, const double* norm_state, float obs_clip,
+                         float epsilon, void* stream) {
+    EVAC_REQUIRE_BOUND(h, "evac_policy_evaluate");
+    return policy_evaluate(h, "evac_policy_evaluate", 0, nullptr, 0, agent, policy, n_episodes, max_steps, progress, episodes_out,
+                           norm_state, obs_clip, epsilon, stream);
+}
+
+int evac_policy_evaluate_population(evac_handle_t h, int32_t n_learners, const evac_mlp_policy_t* policy,
+                                    const evac_mlp_policy_strides_t* strides, int32_t agent, int32_t shared_episodes,
+                                    int32_t n_episodes, int32_t max_steps, int32_t* progress, evac_episode_stats_t* episodes_out,
+                                    const double* norm_state, float obs_clip, float epsilon, void* stream) {
+    EVAC_REQUIRE_BOUND(h, "evac_policy_evaluate_population");
+    if (!strides) return fail(h, EVAC_ERR_INVALID_ARGUMENT, "evac_policy_evaluate_population: strides is NULL");
+    return policy_evaluate(h, "evac_policy_evaluate_population", n_learners, strides, shared_episodes, agent, policy, n_episodes,
+                           max_steps, progress, episodes_out, norm_state, obs_clip, epsilon, stream);
 }
 
 }  // extern "C"

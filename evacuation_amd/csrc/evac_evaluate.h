@@ -95,16 +95,25 @@ __device__ __forceinline__ void eval_observation(const Params& p, PolicyFamily::
 
 // POLICY: the network is the agent (ps: its weights in LDS); else the scripted baseline, which reads e.ax / e.ay and nothing else.
 // ENC: an encoder in front of the actor (evac_policy.h: NoEncoder; evac_deepsets.h).
-template <bool POLICY, bool GRAV, bool NORM, class ENC = NoEncoder>
+// SHIFTED (the population form, k_evaluate_population): as policy_rollout_body's -- the wave's env is its place in the launch plus
+// `env_shift`, and it has work while that is below `env_end`; the env's global id, which keys every Philox stream of the body, is
+// further back by `id_shift` (a learner's share with the ids of learner 0's: the same episodes for every learner).
+template <bool POLICY, bool GRAV, bool NORM, class ENC = NoEncoder, bool SHIFTED = false>
 __device__ __forceinline__ void policy_evaluate_body(PolicyFamily::Smem& sm, PolicySmem<GRAV>* psp, EvalSmem& es, const Params& p,
-                                                     const PolicyArgs& ka, const EvalArgs& kev, const ENC& enc = ENC{}) {
+                                                     const PolicyArgs& ka, const EvalArgs& kev, const ENC& enc = ENC{},
+                                                     int env_shift = 0, int env_end = 0, int id_shift = 0) {
     using F = PolicyFamily;
     if constexpr (POLICY) stage_policy<GRAV>(*psp, ka, NormArgs{nullptr, 0.f, 0.f, 0.f, 0.f});
     if constexpr (ENC::kOn) enc.stage();
     if (threadIdx.x == 0) es.a = kev;
     __syncthreads();
     typename F::Ctx w(sm);
-    if (w.env >= p.n_envs) return;
+    if constexpr (SHIFTED) {
+        w.env += env_shift;
+        if (w.env >= env_end) return;
+    } else {
+        if (w.env >= p.n_envs) return;
+    }
     const EvalArgs& ev = es.a;
     const int env = w.env;
     // The env's progress words stay out of the registers (the step takes them all, as in policy_rollout_body): the episode count
@@ -126,7 +135,8 @@ __device__ __forceinline__ void policy_evaluate_body(PolicyFamily::Smem& sm, Pol
     Ped q;
     Env e;
     load_env(p, env, w.i, active, q, e);
-    const uint32_t gid = p.env_id_offset + (uint32_t)env;
+    uint32_t gid = p.env_id_offset + (uint32_t)env;
+    if constexpr (SHIFTED) gid = p.env_id_offset + (uint32_t)(env - id_shift);
     float* xs = nullptr;
     float o6[6] = {};
     if constexpr (POLICY) xs = psp->x[w.slot];
@@ -223,6 +233,25 @@ __global__ __launch_bounds__(PolicyFamily::kBlock, 4) void k_policy_evaluate_scr
     __shared__ EvalSmem es;
     if constexpr (DEF) p = default_config_constants<false>(p);
     policy_evaluate_body<false, false, false>(sm, (PolicySmem<false>*)nullptr, es, p, PolicyArgs{}, ev);
+}
+
+// ---- The population form: S learners' evaluations in one launch (include/evac.h: evac_policy_evaluate_population) ----
+// k_collect_population's geometry (evac_policy.h): learner s owns envs [s E_l, (s + 1) E_l) of the handle and `wgs` workgroups of
+// the launch, stages its own 13 tensors and runs policy_evaluate_body on its envs.  progress, episodes_out and norm_state are
+// indexed by the handle's env.  shared != 0: learner s's env i draws with the id of env i, whoever the learner is.
+template <bool GRAV, bool NORM, bool DEF>
+__global__ __launch_bounds__(PolicyFamily::kBlock, 4) void k_evaluate_population(Params p, PolicyArgs a, EvalArgs ev, PopulationArgs q,
+                                                                                 int shared) {
+    __shared__ PolicyFamily::Smem sm;
+    __shared__ PolicySmem<GRAV> ps;
+    __shared__ EvalSmem es;
+    if constexpr (DEF) p = default_config_constants<GRAV>(p);
+    const int s = (int)blockIdx.x / q.wgs;
+    const PolicyArgs la = learner_policy(a, q, s);
+    // (blockIdx.x x 16 + slot) + shift = s E_l + (blockIdx.x - s wgs) x 16 + slot
+    policy_evaluate_body<true, GRAV, NORM, NoEncoder, true>(sm, &ps, es, p, la, ev, NoEncoder{},
+                                                            s * (q.envs_per_learner - q.wgs * PolicyFamily::kEnvsPerBlock),
+                                                            (s + 1) * q.envs_per_learner, shared ? s * q.envs_per_learner : 0);
 }
 
 }  // namespace evac

@@ -4,11 +4,12 @@ The episode records that fall out of the trainer's collection phase carry the ex
 and episodes cut at the ``num_steps`` window.  ``PolicyEvaluator`` answers "how good is this leader?" instead: every env runs
 whole episodes under the network's MEAN action (or its sampled one) with the observation statistics FROZEN, or under the
 reference's scripted sweep baseline (src/agents/baseline_wacuum_cleaner.py) -- from the same start states, reset draws and
-pedestrian-noise streams for every agent, so two agents are compared on the same episodes."""
+pedestrian-noise streams for every agent, so two agents are compared on the same episodes.  ``PopulationEvaluator`` does the
+same for the S learners of a ``PolicyPopulation`` in one set of launches (``evac_policy_evaluate_population``)."""
 from __future__ import annotations
 
 import dataclasses
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -16,6 +17,7 @@ from .config import EnvConfig, EnvWrappersConfig
 from .vector_env import STATS_FIELDS, STATS_INT_FIELDS, BatchedEvacuationEnv, stats_int_view
 
 _STATE = ("ped", "status", "agent", "clock", "acc")
+_SUMMARY_KEYS = ("episode_reward_mean", "episode_reward_std", "episode_length_mean", "escaped_fraction_mean", "all_escaped_share")
 
 
 @dataclasses.dataclass
@@ -38,13 +40,31 @@ class EvaluationResult:
     def summary(self) -> Dict[str, float]:
         """Python floats over all episodes of all envs: mean and (population) std of ``episode_reward``, mean
         ``episode_length``, mean share of the pedestrians that escaped, and the share of episodes in which everybody did."""
+        out = dict(zip(_SUMMARY_KEYS, self._summary_scalars().cpu().tolist()))
+        out["episodes"] = int(self.episodes["episode_reward"].numel())
+        return out
+
+    def _summary_scalars(self) -> torch.Tensor:
+        """The five reductions of ``summary()`` as one float64 [5] tensor on the episodes' device (no host transfer)."""
         r = self.episodes["episode_reward"].double()
         esc = self.episodes["escaped_pedestrians"].double()
-        host = torch.stack([r.mean(), r.std(unbiased=False), self.episodes["episode_length"].double().mean(),
-                            (esc / self.n_pedestrians).mean(), (esc == self.n_pedestrians).double().mean()]).cpu().tolist()
-        keys = ("episode_reward_mean", "episode_reward_std", "episode_length_mean", "escaped_fraction_mean", "all_escaped_share")
-        out = dict(zip(keys, host))
-        out["episodes"] = int(r.numel())
+        return torch.stack([r.mean(), r.std(unbiased=False), self.episodes["episode_length"].double().mean(),
+                            (esc / self.n_pedestrians).mean(), (esc == self.n_pedestrians).double().mean()])
+
+    @staticmethod
+    def summaries(results: Sequence["EvaluationResult"]) -> List[Dict[str, float]]:
+        """``[r.summary() for r in results]`` with ONE host transfer for all of them (the S learners of
+        ``PopulationEvaluator.evaluate``): every result's reductions are ``summary()``'s own, so the values are its bits, and
+        they are gathered on the device and read once -- the S synchronising reads are what the per-result loop costs."""
+        results = list(results)
+        if not results:
+            return []
+        host = torch.stack([res._summary_scalars() for res in results]).cpu().tolist()
+        out = []
+        for res, row in zip(results, host):
+            d = dict(zip(_SUMMARY_KEYS, row))
+            d["episodes"] = int(res.episodes["episode_reward"].numel())
+            out.append(d)
         return out
 
 
@@ -96,6 +116,90 @@ class PolicyEvaluator:
             if int(progress[:, 0].min()) >= int(n_episodes):
                 break
         return EvaluationResult.from_records(out, progress[:, 1].clone(), env.n_ped)
+
+    def close(self) -> None:
+        self.env.close()
+
+
+def check_population_norm_state(norm_state, num_learners: int, obs_dim: int):
+    """``PopulationEvaluator.evaluate``'s ``norm_state``: float64 [S, rows, 3 D + 4], or a sequence of S float64 [rows_s, 3 D + 4]
+    (rows >= 1).  Returns the S tensors; ``ValueError`` otherwise."""
+    S, W = int(num_learners), 3 * int(obs_dim) + 4
+    parts = list(norm_state.unbind(0)) if isinstance(norm_state, torch.Tensor) and norm_state.dim() == 3 else norm_state
+    if isinstance(parts, torch.Tensor) or not isinstance(parts, (list, tuple)) or len(parts) != S:
+        if isinstance(parts, torch.Tensor):
+            got = f"a tensor {tuple(parts.shape)}"
+        else:
+            got = f"{type(parts).__name__} of {len(parts)}" if hasattr(parts, "__len__") else type(parts).__name__
+        raise ValueError(f"evaluate: norm_state must be float64 [{S}, rows, {W}] or a sequence of {S} tensors [rows, {W}], got {got}")
+    for s, t in enumerate(parts):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != W or t.dtype != torch.float64 or t.shape[0] < 1:
+            what = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"evaluate: norm_state of learner {s} must be float64 [rows, {W}], got {what}")
+    return parts
+
+
+class PopulationEvaluator:
+    """``PolicyEvaluator`` for the S learners of a ``PolicyPopulation`` in one set of launches
+    (``evac_policy_evaluate_population``): ONE handle of ``num_learners x num_envs`` envs, reset once; learner s evaluates in
+    envs ``[s E_l, (s + 1) E_l)`` with the global ids of envs ``[0, E_l)``, so every learner's result is, bit for bit, what
+    ``PolicyEvaluator(num_envs=E_l, seed=seed).evaluate(nets[s], ...)`` gives -- the learners are compared on the same episodes.
+    The snapshot is the reset state of envs ``[0, E_l)`` tiled S times: envs of one seed and the same global ids are identical,
+    so no second handle is needed to take it from."""
+
+    def __init__(self, env_config: EnvConfig, wrap_config: Optional[EnvWrappersConfig] = None, num_learners: int = 1,
+                 num_envs: int = 1, seed: int = 0, device="cuda:0", options=None):
+        from .population import MAX_LEARNERS
+        S, E_l = int(num_learners), int(num_envs)
+        if not 1 <= S <= MAX_LEARNERS:
+            raise ValueError(f"PopulationEvaluator: {S} learners; expected 1..{MAX_LEARNERS}")
+        if E_l < 1:
+            raise ValueError(f"PopulationEvaluator: num_envs must be >= 1, got {E_l}")
+        self.num_learners, self.num_envs = S, E_l
+        self.env = BatchedEvacuationEnv(env_config, wrap_config, num_envs=S * E_l, device=device, seed=seed, autoreset=True,
+                                        options=options)
+        self.env.reset()
+        self.snapshot = {}
+        for k in _STATE:
+            t = getattr(self.env, k)
+            self.snapshot[k] = t[:E_l].repeat((S,) + (1,) * (t.dim() - 1))
+        self.launches = 0                      # launches of the last evaluate()
+
+    def restore(self) -> None:
+        for k in _STATE:
+            getattr(self.env, k).copy_(self.snapshot[k])
+
+    def evaluate(self, population, n_episodes: int = 1, *, deterministic: bool = True, norm_state=None, obs_clip: float = 1.0,
+                 epsilon: float = 1e-8, max_steps_per_launch: int = 4096) -> List[EvaluationResult]:
+        """``n_episodes`` whole episodes per env under every learner of ``population``: S ``EvaluationResult``s whose tensors are
+        views of ONE records tensor [n_episodes, S, E_l, 10].  ``norm_state``: float64 [S, rows, 3 D + 4] or a list of S tensors
+        [rows_s, 3 D + 4]; row ``i mod rows`` of learner s serves its env i, applied frozen.  Launches of at most
+        ``max_steps_per_launch`` steps until every env of every learner has finished; the one host read per launch is
+        ``progress[:, 0].min()`` over all learners."""
+        env, S, E_l = self.env, self.num_learners, self.num_envs
+        if int(getattr(population, "num_learners", -1)) != S:
+            raise ValueError(f"evaluate: the population has {getattr(population, 'num_learners', None)} learners, the evaluator {S}")
+        norm = None
+        if norm_state is not None:
+            parts = check_population_norm_state(norm_state, S, env.obs_dim)
+            rows = torch.arange(E_l, device=env.device)
+            state = torch.cat([t.to(env.device)[rows % t.shape[0]] for t in parts]).contiguous()
+            norm = (state, float(obs_clip), float(epsilon))
+        self.restore()
+        progress = out = None
+        self.launches = 0
+        # (the launch bound of PolicyEvaluator.evaluate: a launch that made no progress is an error, not a hang)
+        bound = -(-int(n_episodes) * int(env.env_config.max_timesteps) // int(max_steps_per_launch)) + 1
+        while True:
+            if self.launches >= bound:
+                raise RuntimeError(f"evaluate: {self.launches} launches of {max_steps_per_launch} steps did not finish {n_episodes} episodes")
+            progress, out = env.policy_evaluate_population(population, n_episodes, max_steps_per_launch, progress, out,
+                                                           deterministic=deterministic, shared_episodes=True, _norm=norm)
+            self.launches += 1
+            if int(progress[:, 0].min()) >= int(n_episodes):
+                break
+        records, steps = out.view(int(n_episodes), S, E_l, out.shape[-1]), progress[:, 1].clone().view(S, E_l)
+        return [EvaluationResult.from_records(records[:, s], steps[s], env.n_ped) for s in range(S)]
 
     def close(self) -> None:
         self.env.close()

@@ -12,7 +12,8 @@ update is a chain of small launches on a nearly idle chip; here learner s rides 
   ``[s E_l, (s + 1) E_l)`` of one env of ``S E_l`` envs.
 * ``rpo_update_population``: every learner's epochs and minibatches in one host call, four launches per minibatch step as for
   one learner (``evac_rpo_update_population``).
-* ``PopulationTrainer``: one iteration of the reference's loop for all learners per ``update()``.
+* ``PopulationTrainer``: one iteration of the reference's loop for all learners per ``update()``; ``evaluate()`` runs every
+  learner's whole episodes in one set of launches (``evaluation.PopulationEvaluator``, ``evac_policy_evaluate_population``).
 * Sweeps: every float-valued hyperparameter (``SWEEP_FIELDS``) may differ per learner -- ``PopulationTrainer(env, population,
   [cfg_0, .., cfg_S-1])``, ``rpo_update_population(cfg=[...])``, ``gae(gamma=[...])``, ``policy_rollout_population(gammas=[...])``;
   ``sweep_configs`` makes the cartesian product.  The learners' values ride in the kernel arguments beside their seeds
@@ -351,6 +352,7 @@ class PopulationTrainer:
         self.stats_rows = self.workspace = None
         self.last_permutations = None             # [S, epochs, B_l]: the learners' own permutations of the last update
         self.evaluator = None
+        self.population_evaluator = None          # evaluate()'s: every learner in one set of launches
 
     def _start(self):
         obs, _ = self.env.reset()
@@ -445,31 +447,44 @@ class PopulationTrainer:
             self.evaluator = PolicyEvaluator(base.env_config, base.wrap_config, num_envs=n, seed=base.seed_value, device=base.device)
         return self.evaluator
 
+    def make_population_evaluator(self, num_envs: Optional[int] = None):
+        """One ``PopulationEvaluator`` for all learners: the training env's configs and seed, a handle of its own with
+        ``num_envs`` envs per learner (a learner's share of the training batch by default)."""
+        from .evaluation import PopulationEvaluator
+        base = getattr(self.env, "env", self.env)
+        n = self.envs_per_learner if num_envs is None else int(num_envs)
+        if self.population_evaluator is None or self.population_evaluator.num_envs != n:
+            if self.population_evaluator is not None:
+                self.population_evaluator.close()
+            self.population_evaluator = PopulationEvaluator(base.env_config, base.wrap_config, num_learners=self.num_learners,
+                                                            num_envs=n, seed=base.seed_value, device=base.device)
+        return self.population_evaluator
+
     def evaluate(self, n_episodes: int = 1, num_envs: Optional[int] = None, deterministic: bool = True) -> list:
-        """``RPOTrainer.evaluate`` for every learner in turn on the shared evaluator, each with its own rows of the training
-        env's observation statistics (frozen copies).  Returns S ``EvaluationResult``s."""
-        ev, E_l = self.make_evaluator(num_envs), self.envs_per_learner
-        out = []
+        """``RPOTrainer.evaluate`` for every learner in ONE set of launches on the population evaluator, each with its own rows
+        of the training env's observation statistics (frozen copies).  Returns S ``EvaluationResult``s, bit for bit those of
+        ``make_evaluator().evaluate(nets[s], ...)`` learner by learner."""
+        ev, S, E_l = self.make_population_evaluator(num_envs), self.num_learners, self.envs_per_learner
+        kw = {}
+        if hasattr(self.env, "norm_state"):
+            kw = {"norm_state": self.env.norm_state.view(S, E_l, -1).clone(), "obs_clip": self.env.obs_clip,
+                  "epsilon": self.env.epsilon}
         with torch.no_grad():
-            for s, net in enumerate(self.nets):
-                kw = {}
-                if hasattr(self.env, "norm_state"):
-                    kw = {"norm_state": self.env.norm_state[s * E_l:(s + 1) * E_l].clone(), "obs_clip": self.env.obs_clip,
-                          "epsilon": self.env.epsilon}
-                out.append(ev.evaluate(net, n_episodes, deterministic=deterministic, **kw))
-        return out
+            return ev.evaluate(self.population, n_episodes, deterministic=deterministic, **kw)
 
     def learn(self, total_timesteps: Optional[int] = None, callback: Optional[Callable[[List[dict]], None]] = None, *,
               eval_every: Optional[int] = None, eval_episodes: int = 1) -> list:
         """``num_updates`` updates (``total_timesteps // batch_size``, per learner); returns the list of ``update()``'s results.
-        Every ``eval_every`` updates each learner's ``log["eval"]`` holds the ``summary()`` of its ``evaluate(eval_episodes)``."""
+        Every ``eval_every`` updates each learner's ``log["eval"]`` holds the ``summary()`` of its ``evaluate(eval_episodes)``
+        (``EvaluationResult.summaries``: one host transfer for all learners)."""
+        from .evaluation import EvaluationResult
         n = self.cfg.num_updates if total_timesteps is None else int(total_timesteps) // self.cfg.batch_size
         all_logs = []
         for _ in range(n):
             logs = self.update()
             if eval_every and self.update_index % int(eval_every) == 0:
-                for log, res in zip(logs, self.evaluate(eval_episodes)):
-                    log["eval"] = res.summary()
+                for log, summary in zip(logs, EvaluationResult.summaries(self.evaluate(eval_episodes))):
+                    log["eval"] = summary
             all_logs.append(logs)
             if callback is not None:
                 callback(logs)

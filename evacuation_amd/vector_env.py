@@ -698,6 +698,55 @@ class BatchedEvacuationEnv:
         _lib.check(rc, self._h)
         return progress, out
 
+    def policy_evaluate_population(self, population, n_episodes: int, max_steps: int, progress: Optional[torch.Tensor] = None,
+                                   out: Optional[torch.Tensor] = None, *, deterministic: bool = True, shared_episodes: bool = True,
+                                   _norm=None):
+        """``policy_evaluate`` for the S learners of ``population`` (a ``PolicyPopulation``) in ONE launch
+        (``evac_policy_evaluate_population``): learner s acts in envs ``[s E_l, (s + 1) E_l)`` of this env, ``E_l = num_envs / S``.
+        Arguments and results are ``policy_evaluate``'s over the whole batch -- ``progress`` [S E_l, 4], ``out`` [n_episodes,
+        S E_l, 10], ``_norm``'s state [S E_l, 3 D + 4] -- and learner s's columns hold, bit for bit, what
+        ``policy_evaluate(population.nets[s], ...)`` writes on an env of ``E_l`` envs with the same seed and the same start state.
+        ``shared_episodes=True``: that env has this env's ``env_id_offset``, so env i of every learner sees the same reset draws
+        and pedestrian noise (the learners are compared on the same episodes); ``False``: its offset is further by ``s E_l``,
+        the ids of ``policy_rollout_population``.  The networks alone: a scripted agent has no learners (``policy_evaluate``),
+        and a population or net with a set encoder is a ``ValueError``."""
+        from .policy import MAX_PEDESTRIANS, PolicyBinder, refuse_deepsets
+        refuse_deepsets(population, "policy_evaluate_population")
+        for net in getattr(population, "nets", ()):
+            refuse_deepsets(net, "policy_evaluate_population")
+        if isinstance(population, str) or not hasattr(population, "strides"):
+            raise ValueError("policy_evaluate_population: a PolicyPopulation is expected (a scripted agent has no learners: "
+                             "policy_evaluate runs it)")
+        check_evaluate_args(population, n_episodes, max_steps, _norm)
+        if self.n_ped > MAX_PEDESTRIANS:
+            raise NotImplementedError(f"policy_evaluate_population runs one wave per env: rooms of at most {MAX_PEDESTRIANS} "
+                                      f"pedestrians (this env has {self.n_ped})")
+        S = int(population.num_learners)
+        if self.num_envs % S:
+            raise ValueError(f"policy_evaluate_population: {self.num_envs} envs are not {S} learners' equal shares")
+        K, T, E, D = int(n_episodes), int(max_steps), self.num_envs, self.obs_dim
+        binder = getattr(self, "_policy_binder", None)
+        if binder is None:
+            binder = self._policy_binder = PolicyBinder(D, self.device, self.n_ped)
+        pol = binder(population.nets[0])
+        code = _lib.AGENT_POLICY_MEAN if deterministic else _lib.AGENT_POLICY_SAMPLE
+        if progress is None:
+            progress = torch.zeros((E, 4), dtype=torch.int32, device=self.device)
+        else:
+            self._check_tensor(progress, (E, 4), torch.int32, "progress")
+        if out is None:
+            out = torch.zeros((K, E, STATS_WORDS), dtype=torch.float32, device=self.device)
+        else:
+            self._check_tensor(out, (K, E, STATS_WORDS), torch.float32, "out")
+        state, obs_clip, eps = (None, 0.0, 0.0) if _norm is None else _norm
+        if state is not None:
+            self._check_tensor(state, (E, 3 * D + 4), torch.float64, "norm_state")
+        rc = self.lib.evac_policy_evaluate_population(self._h, S, C.byref(pol), C.byref(population.strides), code,
+                                                      int(bool(shared_episodes)), K, T, _ptr(progress), _ptr(out), _ptr(state),
+                                                      obs_clip, eps, self._stream())
+        _lib.check(rc, self._h)
+        return progress, out
+
     def observe(self, out: Optional[torch.Tensor] = None):
         """Observation of the current state without stepping (env.py:98-104 through the wrappers)."""
         out = self.obs if out is None else self._check_tensor(out, (self.num_envs, self.obs_dim), torch.float32, "out")

@@ -480,6 +480,26 @@ int evac_policy_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t
                          int32_t* progress,                   /* [E][4] in/out; zero it to begin */
                          evac_episode_stats_t* episodes_out,  /* [n_episodes][E] */
                          const double* norm_state_or_null, float obs_clip, float epsilon, void* stream);
+/* evac_policy_evaluate_population: evac_policy_evaluate under the policy agents for n_learners learners in ONE launch.  `policy`
+ * holds learner 0's tensors (the actor alone is read); learner s evaluates in envs [s E_l, (s + 1) E_l) of the handle, and
+ * progress [S E_l][4], episodes_out [n_episodes][S E_l] and norm_state [S E_l][evac_norm_state_doubles(h)] are indexed by the
+ * handle's env.  EQUIVALENCE: the call writes, bit for bit, what S calls of evac_policy_evaluate write -- call s with learner s's
+ * tensors on a handle of E_l envs with the same seed, learner s's share of the state and its rows of norm_state -- into learner
+ * s's columns of progress and episodes_out and its share of the state.  With shared_episodes != 0 that handle's env_id_offset is
+ * this handle's: env i of EVERY learner has the global id of env i, so all learners meet the same reset draws and pedestrian noise
+ * (and, in sample mode, the same z).  With shared_episodes == 0 it is this handle's + s E_l, the id convention of
+ * evac_policy_rollout_population: sample mode with max_steps = T is then that call's env side bit for bit.
+ * ceil(E_l / 16) CU-wide workgroups per learner; a workgroup never mixes learners; the launch lasts as long as its longest env.
+ * EVAC_ERR_UNSUPPORTED / EVAC_ERR_INVALID_ARGUMENT, decided on the host before anything is launched: as evac_policy_evaluate, and
+ * EVAC_AGENT_VACUUM_CLEANER (no learners: evac_policy_evaluate runs it), a NULL strides, n_learners outside
+ * 1..EVAC_MAX_LEARNERS, a number of envs that n_learners does not divide, and with n_learners > 1 a stride smaller than its
+ * tensor (0 included).  The handle is joined first; ONE kernel on `stream`, no host synchronisation, capturable. */
+int evac_policy_evaluate_population(evac_handle_t h, int32_t n_learners, const evac_mlp_policy_t* policy,
+                                    const evac_mlp_policy_strides_t* strides, int32_t agent, int32_t shared_episodes,
+                                    int32_t n_episodes, int32_t max_steps,
+                                    int32_t* progress,                   /* [S E_l][4] in/out; zero it to begin */
+                                    evac_episode_stats_t* episodes_out,  /* [n_episodes][S E_l] */
+                                    const double* norm_state_or_null, float obs_clip, float epsilon, void* stream);
 
 /* ---- The deep-sets leader: the reference's set encoder in front of the actor-critic (rpo_deep_sets_agent_network.py:25-90) ----
  * RPODeepSetsEmbedding reads the Box observation x [D] as a set of S = N + 2 rows (pedestrians, leader, exit) of

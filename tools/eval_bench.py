@@ -2,13 +2,20 @@
 """Measure the policy evaluation kernel (evac_policy_evaluate) against the policy rollout.
 
     python tools/eval_bench.py [--envs 4096] [--steps 128] [--reps 9] [--shape grav|wide|both] [--evaluate-only]
+    python tools/eval_bench.py --learners S [--learner-envs 256] [--pairs 9]
 
 Per shape -- N = 60 with the gravity observation (D = 6), and with the rel + ohe Box observation (D = 372), both with the frozen
 normaliser -- the time per env-step of ``policy_evaluate(mean, max_steps = T)`` and of ``policy_rollout(T)`` from the same start
 state: hipEvent times after warm-up, the two forms alternated inside every repetition, median and range.  Then one
 ``PolicyEvaluator.evaluate(n_episodes = 1)`` at the default ``max_timesteps`` (host wall time and launches) and one launch of
 4096 steps, which is what the ``max_steps_per_launch`` default rests on.  ``--evaluate-only`` runs just the evaluate() part
-(for a kernel trace: ``rocprofv3 --kernel-trace --stats -- python tools/eval_bench.py --evaluate-only``)."""
+(for a kernel trace: ``rocprofv3 --kernel-trace --stats -- python tools/eval_bench.py --evaluate-only``).
+
+``--learners S`` measures the population evaluation instead: S learners of ``--learner-envs`` envs each, N = 60 with the gravity
+observation and the frozen normaliser, one episode per env at the default ``max_timesteps`` -- a loop of S
+``PolicyEvaluator.evaluate`` calls (one learner after another) against ONE ``PopulationEvaluator.evaluate``, the same nets and
+statistics, one warm-up of each, then interleaved pairs whose order alternates: hipEvent time and host wall time, median and
+range, and the S ``summary()`` reads against one ``EvaluationResult.summaries``."""
 import argparse
 import os
 import statistics
@@ -126,6 +133,81 @@ def whole_evaluation(args):
     ev.close()
 
 
+def population_against_loop(args):
+    from evacuation_amd.evaluation import EvaluationResult, PopulationEvaluator
+    S, E_l = args.learners, args.learner_envs
+    cfg = ea.EnvConfig(number_of_pedestrians=60, is_new_exiting_reward=True, clip_action=True)
+    wrap = ea.EnvWrappersConfig(**SHAPES["grav"])
+    one = ea.PolicyEvaluator(cfg, wrap, num_envs=E_l, seed=1)
+    every = PopulationEvaluator(cfg, wrap, num_learners=S, num_envs=E_l, seed=1)
+    pop = ea.PolicyPopulation(6, list(range(1, S + 1)), DEV)
+    g = torch.Generator().manual_seed(0)
+    ns = torch.zeros((S, E_l, 22), dtype=torch.float64)
+    ns[..., :6] = torch.randn((S, E_l, 6), generator=g, dtype=torch.float64) * 0.1
+    ns[..., 6:12] = torch.rand((S, E_l, 6), generator=g, dtype=torch.float64) + 0.5
+    ns = ns.to(DEV)
+    launches = {}
+
+    def loop():
+        launches["loop"] = 0
+        res = []
+        for s in range(S):
+            res.append(one.evaluate(pop.nets[s], 1, norm_state=ns[s]))
+            launches["loop"] += one.launches
+        return res
+
+    def together():
+        res = every.evaluate(pop, 1, norm_state=ns)
+        launches["population"] = every.launches
+        return res
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        res = fn()
+        b.record()
+        b.synchronize()
+        return res, a.elapsed_time(b), (time.perf_counter() - t0) * 1e3
+
+    def host_ms(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+    with torch.no_grad():
+        r_loop, r_pop = loop(), together()                                     # one warm-up of each
+        for s in range(S):                                                     # the two paths give the same records
+            for k in r_loop[s].episodes:
+                assert r_loop[s].episodes[k].contiguous().view(torch.int32).equal(r_pop[s].episodes[k].contiguous().view(torch.int32)), (s, k)
+        ev = {"loop": [], "population": []}
+        wall = {"loop": [], "population": []}
+        summ = {"loop": [], "population": []}
+        for pair in range(args.pairs):
+            for form in (("loop", "population") if pair % 2 == 0 else ("population", "loop")):
+                res, e_ms, w_ms = timed(loop if form == "loop" else together)
+                ev[form].append(e_ms)
+                wall[form].append(w_ms)
+                if form == "loop":
+                    summ[form].append(host_ms(lambda: [r.summary() for r in res]))
+                else:
+                    summ[form].append(host_ms(lambda: EvaluationResult.summaries(res)))
+    steps = int(sum(int(r.steps.sum()) for r in r_pop))
+    print(f"[population] S = {S} learners x {E_l} envs, N = 60, D = 6, frozen normaliser, 1 episode per env, max_timesteps = "
+          f"{cfg.max_timesteps}, {steps} env-steps; median [min .. max] of {args.pairs} interleaved pairs")
+    for form, name in (("loop", f"{S} x PolicyEvaluator.evaluate     "), ("population", "1 x PopulationEvaluator.evaluate")):
+        print(f"    {name}  events {show(ev[form])}   host {show(wall[form])}   {launches[form]} launch(es)   summaries {show(summ[form])}")
+    r_ev = statistics.median(ev["loop"]) / statistics.median(ev["population"])
+    r_wall = statistics.median(wall["loop"]) / statistics.median(wall["population"])
+    r_all = (statistics.median(wall["loop"]) + statistics.median(summ["loop"])) / \
+        (statistics.median(wall["population"]) + statistics.median(summ["population"]))
+    print(f"    loop / population: events {r_ev:.2f} x, host {r_wall:.2f} x, host with the summaries {r_all:.2f} x")
+    one.close()
+    every.close()
+    return r_wall >= 1.0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
@@ -134,7 +216,12 @@ def main():
     ap.add_argument("--eval-reps", type=int, default=3)
     ap.add_argument("--shape", choices=("grav", "wide", "both"), default="both")
     ap.add_argument("--evaluate-only", action="store_true")
+    ap.add_argument("--learners", type=int, default=0, help="measure the population evaluation with this many learners instead")
+    ap.add_argument("--learner-envs", type=int, default=256)
+    ap.add_argument("--pairs", type=int, default=9)
     args = ap.parse_args()
+    if args.learners:
+        return 0 if population_against_loop(args) else 1
     ok = True
     if not args.evaluate_only:
         for shape in (("grav", "wide") if args.shape == "both" else (args.shape,)):
