@@ -4,7 +4,8 @@ Public surface = the reference's ``src.env`` exports (src/env/__init__.py:3-21):
 ``setup_env, EvacuationEnv, EnvConfig, EnvWrappersConfig, Status`` plus the batched form
 ``BatchedEvacuationEnv``, its SyncVectorEnv-shaped host face ``HostVectorEnv``, the sharded form ``ShardedEvacuationEnv`` (across GPUs) and ``SplitBatchEnv`` (across streams of one GPU), and the reference trainer's update on
 the device (``RPOTrainer``, ``RPOTrainingConfig``, ``gae``, ``rpo_minibatch_grad``, and the optimiser
-step ``DeviceAdam``, ``rpo_minibatch_step``, ``rpo_update``: ``evacuation_amd.trainer``), and the evaluation of a fixed agent
+step ``DeviceAdam``, ``rpo_minibatch_step``, ``rpo_update``, and the deep-sets leader's gradient ``deepsets_minibatch_grad`` /
+``deepsets_kernel_grad``: ``evacuation_amd.trainer``), and the evaluation of a fixed agent
 over whole episodes (``PolicyEvaluator``, ``PopulationEvaluator``, ``EvaluationResult``, the scripted baseline ``WacuumCleaner``), and S independent
 learners of one configuration in one set of launches (``PolicyPopulation``, ``PopulationAdam``, ``PopulationTrainer``,
 ``rpo_update_population``: ``evacuation_amd.population``).  Importing the package does
@@ -15,7 +16,7 @@ from .statuses import Status
 __all__ = ["EnvConfig", "EnvWrappersConfig", "Status", "setup_env", "EvacuationEnv", "BatchedEvacuationEnv",
            "ShardedEvacuationEnv", "SplitBatchEnv", "NormalizedVectorEnv", "HostVectorEnv", "RandomAgent", "KernelOptions", "kernel_options",
            "RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad", "DeviceAdam", "rpo_minibatch_step", "rpo_update",
-           "WacuumCleaner", "PolicyEvaluator", "PopulationEvaluator", "EvaluationResult",
+           "deepsets_minibatch_grad", "deepsets_kernel_grad", "WacuumCleaner", "PolicyEvaluator", "PopulationEvaluator", "EvaluationResult",
            "PolicyPopulation", "PopulationAdam", "PopulationTrainer", "rpo_update_population"]
 
 
@@ -47,7 +48,8 @@ def __getattr__(name):   # lazy: keeps `import evacuation_amd` light and torch-f
     if name in ("PolicyEvaluator", "PopulationEvaluator", "EvaluationResult"):      # whole-episode evaluation of a fixed agent on the device
         from . import evaluation as _evaluation
         return getattr(_evaluation, name)
-    if name in ("RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad", "DeviceAdam", "rpo_minibatch_step", "rpo_update"):   # the trainer's update on the device
+    if name in ("RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad", "DeviceAdam", "rpo_minibatch_step", "rpo_update",
+                "deepsets_minibatch_grad", "deepsets_kernel_grad"):   # the trainer's update on the device
         from . import trainer as _trainer
         return getattr(_trainer, name)
     if name in ("PolicyPopulation", "PopulationAdam", "PopulationTrainer", "rpo_update_population"):   # S learners in one set of launches

@@ -52,6 +52,11 @@ class EvacDeepSets(C.Structure):
         (f, C.c_void_p) for f in ("phi_w1", "phi_b1", "phi_w2", "phi_b2", "rho_w", "rho_b")]
 
 
+class EvacDeepSetsGrads(C.Structure):
+    """evac_deepsets_grads_t: where evac_deepsets_minibatch_grad writes the gradients of the encoder's six tensors"""
+    _fields_ = [(f, C.c_void_p) for f, _ in EvacDeepSets._fields_[2:]]
+
+
 class EvacRpoLossConfig(C.Structure):
     """evac_rpo_loss_config_t"""
     _fields_ = [(f, C.c_float) for f in ("clip_coef", "ent_coef", "vf_coef", "rpo_alpha")] + [("norm_adv", C.c_int32), ("clip_vloss", C.c_int32)]
@@ -173,6 +178,10 @@ SIGNATURES = {
     "evac_rpo_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
     "evac_rpo_minibatch_grad": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacRpoLossConfig), C.c_int64, _P, _P, _P, _P, _P, _P,
                                           C.c_int64, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(EvacMlpPolicyGrads), _P, _P, _P]),
+    "evac_deepsets_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
+    "evac_deepsets_minibatch_grad": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacDeepSets), C.POINTER(EvacRpoLossConfig), C.c_int64,
+                                               _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_uint64,
+                                               C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads), _P, _P, _P]),
     "evac_adam_step": (C.c_int, [C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacAdamState),
                                  C.POINTER(EvacAdamConfig), C.c_int32, _P, _P]),
     "evac_rpo_minibatch_step": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacRpoLossConfig), C.c_int64, _P, _P, _P, _P, _P, _P,

@@ -1,4 +1,4 @@
-// Host-only helpers shared by the five translation units of libevac: which device a call runs on; the 13 tensors of the
+// Host-only helpers shared by the six translation units of libevac: which device a call runs on; the 13 tensors of the
 // actor-critic as an array, their sizes, the check of a population's strides and of a policy against a handle; the picker of a
 // kernel template's instantiation over bools; what every entry refuses of evac_learner_hyper_t.
 #pragma once

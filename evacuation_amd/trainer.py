@@ -17,7 +17,7 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from .policy import PolicyBinder, all_tensors, encode_observation, is_deepsets, mlp_tensors, refuse_deepsets
+from .policy import PolicyBinder, all_tensors, deepsets_tensors, encode_observation, is_deepsets, mlp_tensors, refuse_deepsets
 from .vector_env import STATS_FIELDS, _ptr
 
 STAT_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "grad_sumsq")
@@ -138,6 +138,7 @@ class _GradState:
 
     def __init__(self):
         self.binder, self.grads, self.workspace = None, [None, None], None
+        self.encoder_grads, self.deepsets_workspace = [None, None], None     # deepsets_minibatch_grad's
 
 
 def _grad_state(net) -> _GradState:
@@ -159,10 +160,21 @@ def ensure_grads(net) -> "_lib.EvacMlpPolicyGrads":
     return _tensor_struct(_grad_state(net).grads, [t.grad for t in ts])
 
 
-def _batch_args(net, batch: Dict[str, torch.Tensor]):
+def ensure_encoder_grads(net) -> "_lib.EvacDeepSetsGrads":
+    """``ensure_grads`` for the set encoder's six tensors: the addresses of their ``.grad`` as ``evac_deepsets_grads_t``."""
+    ensure_grads(net)
+    cache = _grad_state(net).encoder_grads
+    key = tuple(t.grad.data_ptr() for t in deepsets_tensors(net))
+    if key != cache[0]:
+        cache[:] = key, _lib.EvacDeepSetsGrads(*key)
+    return cache[1]
+
+
+def _batch_args(net, batch: Dict[str, torch.Tensor], deepsets: bool = False):
     """The checks every gradient entry makes of ``batch``; returns (B, D, device, state, evac_mlp_policy_t, grads struct, the
-    entries' arguments ``batch_size, b_obs .. b_values``)."""
-    refuse_deepsets(net, "the device gradient")
+    entries' arguments ``batch_size, b_obs .. b_values``).  ``deepsets``: the caller is the set encoder's own entry."""
+    if not deepsets:
+        refuse_deepsets(net, "the device gradient")
     b_obs = batch["b_obs"]
     B, D = b_obs.shape
     dev = b_obs.device
@@ -230,6 +242,39 @@ def rpo_minibatch_grad(net, batch: Dict[str, torch.Tensor], mb_inds: torch.Tenso
     ``cfg``: an ``RPOTrainingConfig`` (or anything with its loss fields).  ``rpo_noise`` [M, 2] injects the RPO perturbation;
     None draws it on the device from (``seed``, ``draw_counter``).  No host synchronisation; capturable into a graph."""
     return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, None)
+
+
+def deepsets_minibatch_grad(net, batch: Dict[str, torch.Tensor], mb_inds: torch.Tensor, cfg, *, rpo_noise: Optional[torch.Tensor] = None,
+                            seed: int = 0, draw_counter: int = 0, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``rpo_minibatch_grad`` for a network with the reference's set encoder (``policy.DeepSetsActorCritic``): the gradient of the
+    RPO loss of the minibatch into the ``.grad`` of all 19 tensors (written, not accumulated) by ``evac_deepsets_minibatch_grad``
+    -- the encoder forwards, the linear network's three gradient launches on the encoded observations, the encoder backwards.
+    Same arguments, same 8 statistics (``stats[7]``: the sum of squares over the 19 tensors), deterministic, no host
+    synchronisation, capturable.  The optimiser stays torch's (``RPOTrainer(grad_fn=deepsets_kernel_grad)``)."""
+    if not is_deepsets(net):
+        raise ValueError("deepsets_minibatch_grad: the network has no set encoder (`deep_sets`); its gradient is rpo_minibatch_grad's")
+    B, D, dev, st, pol, grads, b_args = _batch_args(net, batch, deepsets=True)
+    enc, enc_grads = st.binder.encoder(net), ensure_encoder_grads(net)
+    if mb_inds.dtype != torch.int64 or mb_inds.device != dev or not mb_inds.is_contiguous() or mb_inds.dim() != 1:
+        raise ValueError("mb_inds: expected a contiguous int64 device vector")
+    M = int(mb_inds.shape[0])
+    if rpo_noise is not None:
+        _f32(rpo_noise, (M, 2), "rpo_noise")
+    need = int(_lib.load().evac_deepsets_workspace_bytes(D, M))
+    if need < 0:
+        raise _lib.EvacError(need, f"evac_deepsets_workspace_bytes({D}, {M})")
+    if st.deepsets_workspace is None or st.deepsets_workspace.numel() < need or st.deepsets_workspace.device != dev:
+        st.deepsets_workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    if stats is None:
+        stats = torch.empty(8, dtype=torch.float32, device=dev)
+    else:
+        _f32(stats, (8,), "stats")
+    lc = _loss_config(cfg)
+    rc = _lib.load().evac_deepsets_minibatch_grad(C.byref(pol), C.byref(enc), C.byref(lc), *b_args, M, _ptr(mb_inds), _ptr(rpo_noise),
+                                                  _u64(seed), _u64(draw_counter), C.byref(grads), C.byref(enc_grads), _ptr(stats),
+                                                  _ptr(st.deepsets_workspace), _stream(dev))
+    _lib.check(rc)
+    return stats
 
 
 HEADER_FIELDS = ("t", "P1", "P2", "stop", "steps_run", "epochs_run")
@@ -424,6 +469,13 @@ def _kernel_grad(trainer: "RPOTrainer", batch, mb_inds, rpo_noise, draw_counter:
                               draw_counter=draw_counter, stats=stats)
 
 
+def deepsets_kernel_grad(trainer: "RPOTrainer", batch, mb_inds, rpo_noise, draw_counter: int, stats: torch.Tensor) -> torch.Tensor:
+    """A ``grad_fn`` of ``RPOTrainer`` for a network with a set encoder: ``deepsets_minibatch_grad`` (collection and gradient on
+    the device, torch's clip and Adam).  Opt-in: the default for such a network stays ``autograd_minibatch_grad``."""
+    return deepsets_minibatch_grad(trainer.net, batch, mb_inds, trainer.cfg, rpo_noise=rpo_noise, seed=trainer.cfg.seed,
+                                   draw_counter=draw_counter, stats=stats)
+
+
 def _draw_seed(seed: int, draw_counter: int) -> int:
     return ((int(seed) & 0xffffffff) << 31) ^ (int(draw_counter) & 0x7fffffff)
 
@@ -489,8 +541,9 @@ class RPOTrainer:
     ``clip_grad_norm_`` (from the kernel's sum of squares) and ``Adam(eps=1e-5)``, the ``target_kl`` early exit.
 
     ``net``: the linear network, or one with the reference's set encoder (``policy.DeepSetsActorCritic``): its collection and
-    evaluation run on the device too, its gradient is ``autograd_minibatch_grad`` (the default ``grad_fn`` then) and its
-    optimiser torch's -- ``optimizer="device"`` is a ``ValueError``: the gradient and optimiser kernels are the linear network's.
+    evaluation run on the device too, its gradient is ``autograd_minibatch_grad`` (the default ``grad_fn`` then) or, with
+    ``grad_fn=deepsets_kernel_grad``, the device's (``evac_deepsets_minibatch_grad``), and its optimiser torch's --
+    ``optimizer="device"`` is a ``ValueError``: the optimiser kernel is the linear network's.
 
     ``env``: a ``NormalizedVectorEnv`` (the trainer's wrapper chain) or a ``BatchedEvacuationEnv`` with ``cfg.num_envs`` envs.
     The permutation of every epoch is drawn on the device from a generator seeded with ``cfg.seed`` (the reference shuffles on

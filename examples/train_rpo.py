@@ -7,14 +7,15 @@ RPO loss (``evac_rpo_minibatch_grad``: three launches) followed by torch's ``cli
 minibatches in one host call (``evac_rpo_update``).  Prints the reference's ``SPS`` line per update.
 
     python examples/train_rpo.py [--envs 4096] [--steps 128] [--updates 5] [--pedestrians 60] [--optimizer device]
-                                 [--network linear|deep_sets]
+                                 [--network linear|deep_sets] [--gradient autograd|device]
                                  [--eval-every 1] [--eval-episodes 1] [--baseline] [--seeds 1,2,3]
                                  [--sweep learning_rate=1e-4,3e-4,1e-3 --sweep ent_coef=0,0.01]
 
 ``--network deep_sets`` trains the reference's set-encoder network (``policy.DeepSetsActorCritic``, RPODeepSetsEmbedding) on the
 rel + ohe Box observation: collection and evaluation on the device (``evac_policy_rollout_deepsets`` /
-``evac_policy_evaluate_deepsets``), the gradient of its 19 tensors by torch autograd (``trainer.autograd_minibatch_grad``) and
-torch's Adam.  Not with ``--optimizer device``, ``--seeds``, ``--sweep`` or ``--compare``: those kernels are the linear network's.
+``evac_policy_evaluate_deepsets``), the gradient of its 19 tensors by torch autograd (``trainer.autograd_minibatch_grad``) or,
+with ``--gradient device``, by ``evac_deepsets_minibatch_grad`` (``trainer.deepsets_kernel_grad``: six launches), and torch's
+Adam.  Not with ``--optimizer device``, ``--seeds``, ``--sweep`` or ``--compare``: those kernels are the linear network's.
 
 ``--eval-every K`` evaluates the leader every K updates (``RPOTrainer.evaluate``: whole episodes, the mean action, the observation
 statistics frozen) and prints the summary; ``--baseline`` prints the same line for the reference's scripted sweep baseline
@@ -49,7 +50,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import evacuation_amd as ea  # noqa: E402
 from evacuation_amd.policy import DeepSetsActorCritic, LinearActorCritic, mlp_tensors  # noqa: E402
-from evacuation_amd.trainer import RPOTrainer, RPOTrainingConfig, flatten_batch  # noqa: E402
+from evacuation_amd.trainer import RPOTrainer, RPOTrainingConfig, deepsets_kernel_grad, flatten_batch  # noqa: E402
 
 DEV = torch.device("cuda:0")
 
@@ -63,6 +64,8 @@ def make_trainer(args, **hooks):
                                       num_envs=args.envs, gamma=cfg.gamma, seed=1)
     torch.manual_seed(0)
     net = (DeepSetsActorCritic(env.obs_dim, args.pedestrians) if deep_sets else LinearActorCritic(env.obs_dim)).to(DEV)
+    if deep_sets and getattr(args, "gradient", "autograd") == "device":
+        hooks.setdefault("grad_fn", deepsets_kernel_grad)
     return RPOTrainer(env, net, cfg, **hooks)
 
 
@@ -243,10 +246,14 @@ def main():
                     help="per-learner values of a hyperparameter; repeat for a grid: the product trains as one population")
     ap.add_argument("--network", choices=("linear", "deep_sets"), default="linear",
                     help="the reference's linear network on the gravity observation, or its set-encoder network on the rel + ohe Box observation")
+    ap.add_argument("--gradient", choices=("autograd", "device"), default="autograd",
+                    help="with --network deep_sets: the gradient of its 19 tensors by torch autograd or by evac_deepsets_minibatch_grad")
     args = ap.parse_args()
+    if args.gradient == "device" and args.network != "deep_sets":
+        raise SystemExit("--gradient device goes with --network deep_sets (the linear network's gradient is the device's anyway)")
     if args.network == "deep_sets" and (args.compare or args.seeds or args.sweep or args.optimizer == "device"):
         raise SystemExit("--network deep_sets: the gradient and optimiser kernels (--optimizer device, --seeds, --sweep, --compare) are "
-                         "the linear network's; its gradient is autograd's")
+                         "the linear network's; its gradient is autograd's or --gradient device")
     if args.compare:
         return compare(args)
     seeds = [int(x) for x in args.seeds.split(",")] if args.seeds else None

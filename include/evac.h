@@ -588,6 +588,32 @@ int evac_rpo_minibatch_grad(const evac_mlp_policy_t* policy, const evac_rpo_loss
                             const float* rpo_noise_or_null, uint64_t seed, uint64_t draw_counter,
                             const evac_mlp_policy_grads_t* grads_out, float* stats_out, void* workspace, void* stream);
 
+/* The same gradient for the deep-sets leader, all 19 tensors: the contract above word for word (the loss, the sub-gradients, the
+ * clamped indices, the Philox draw of z when rpo_noise is NULL, written not accumulated), with the network reading y = encode(x)
+ * of evac_deepsets_t where the linear one reads x = b_obs[mb_inds[m]].  The 13 gradients go to grads_out, the encoder's six to
+ * encoder_grads_out; stats_out[0..6] keep their meaning and stats_out[7] is the sum of squares of the gradient over all 19
+ * tensors.  relu' is 1 where the pre-activation is > 0 and 0 otherwise (torch's convention).  The forward pass is the pooled
+ * form of the kernels above, the same order of sums.  Six launches on `stream` (five without norm_adv): the encoder forwards, the
+ * three of the call above on the encoded observations, the encoder backwards, its finish.  No host synchronisation, capturable;
+ * the parameters are read when the kernels run.  DETERMINISTIC: every sum has a fixed order, no floating-point atomics, the same
+ * bits on every run and stream.  workspace: 16-byte aligned, evac_deepsets_workspace_bytes(obs_dim, M) bytes (that is an error
+ * code for the arguments the other size function refuses), contents irrelevant before and after.
+ * EVAC_ERR_INVALID_ARGUMENT, before anything touches a device: everything the call above refuses; a NULL encoder, a NULL
+ * encoder-gradient struct or a NULL tensor in either; hidden != 24; set_elem_dim outside 1..6; obs_dim not a multiple of
+ * set_elem_dim or fewer than 3 rows; a rho_w that is not 16-byte aligned; a misaligned workspace. */
+typedef struct evac_deepsets_grads {      /* the six tensors of evac_deepsets_t, writable, same layouts */
+    float *phi_w1, *phi_b1, *phi_w2, *phi_b2, *rho_w, *rho_b;
+} evac_deepsets_grads_t;
+int64_t evac_deepsets_workspace_bytes(int32_t obs_dim, int64_t n_minibatch);
+int evac_deepsets_minibatch_grad(const evac_mlp_policy_t* policy, const evac_deepsets_t* encoder,
+                                 const evac_rpo_loss_config_t* cfg, int64_t batch_size,
+                                 const float* b_obs, const float* b_actions, const float* b_logprobs,
+                                 const float* b_advantages, const float* b_returns, const float* b_values,
+                                 int64_t n_minibatch, const int64_t* mb_inds, const float* rpo_noise_or_null,
+                                 uint64_t seed, uint64_t draw_counter,
+                                 const evac_mlp_policy_grads_t* grads_out, const evac_deepsets_grads_t* encoder_grads_out,
+                                 float* stats_out, void* workspace, void* stream);
+
 /* ---- The optimiser step: rpo_agent.py:278-279, clip_grad_norm_(max_grad_norm) and Adam(lr, eps = 1e-5).step(), on the device ----
  * Adam as torch.optim.Adam with betas, no weight decay, no amsgrad.  All in float32, EVERY OPERATION ROUNDED ON ITS OWN (no fused
  * multiply-add, IEEE division, correctly rounded sqrt), except the three scalars marked double, formed in double and rounded

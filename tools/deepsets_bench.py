@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Measure the deep-sets leader's collection phase (evac_policy_rollout_deepsets) against what it stands beside and what it
-replaces.
+replaces, and its minibatch gradient on the device (evac_deepsets_minibatch_grad) against autograd's.
 
-    python tools/deepsets_bench.py --part a|b|c|c-eager [--envs 4096] [--steps 128] [--reps 7]
+    python tools/deepsets_bench.py --part a|b|c|c-eager|grad-autograd|grad-device [--envs 4096] [--steps 128] [--reps 7]
 
 N = 60, the rel + ohe Box observation (D = 372), the trainer's normalisation chain, E envs, T steps per call; hipEvent times of
 whole calls after two warm-up calls, median and range of ``--reps`` calls, one JSON line:
@@ -11,6 +11,9 @@ whole calls after two warm-up calls, median and range of ``--reps`` calls, one J
   c        what b replaces: per step the module's torch forward (``get_action_and_value``, written out) and ``step(out_*=)`` into the
            trainer's storage, the T steps captured into a graph once and replayed (as examples/rollout_with_policy.py)
   c-eager  the same loop launched step by step
+  grad-autograd  one minibatch gradient of ``DeepSetsActorCritic`` by ``trainer.autograd_minibatch_grad`` at the trainer's shape: a
+           batch of E x T rows, a minibatch of ``--minibatch`` (16 384) of them from a permutation, injected noise
+  grad-device    the same by ``trainer.deepsets_minibatch_grad`` (six launches)
 One part per process, so that a job script can give each its own time limit."""
 import argparse
 import json
@@ -38,13 +41,50 @@ def event_ms(fn):
     return a.elapsed_time(b)
 
 
+def grad_part(args):
+    """One minibatch gradient of all 19 tensors: whole calls between two events after two warm-up calls."""
+    from types import SimpleNamespace
+
+    from evacuation_amd import trainer
+    E, T, M = args.envs, args.steps, args.minibatch
+    D, B = (N_PED + 2) * 6, E * T
+    torch.manual_seed(0)
+    net = DeepSetsActorCritic(D, N_PED).to(DEV)
+    cfg = trainer.RPOTrainingConfig(num_envs=E, num_steps=T)
+    g = torch.Generator(device=DEV).manual_seed(1)
+    rnd = lambda *shape: torch.randn(*shape, device=DEV, generator=g)
+    batch = {"b_obs": rnd(B, D).clamp(-5, 5), "b_actions": rnd(B, 2), "b_logprobs": -2.0 + 0.1 * rnd(B), "b_advantages": rnd(B),
+             "b_returns": rnd(B), "b_values": rnd(B)}
+    inds = torch.randperm(B, device=DEV, generator=g)[:M].contiguous()
+    z = ((torch.rand(M, 2, device=DEV, generator=g) * 2 - 1) * cfg.rpo_alpha).contiguous()
+    stats = torch.zeros(8, device=DEV)
+    holder = SimpleNamespace(net=net, cfg=cfg)
+    trainer.ensure_grads(net)
+    if args.part == "grad-device":
+        def run():
+            trainer.deepsets_minibatch_grad(net, batch, inds, cfg, rpo_noise=z, stats=stats)
+    else:
+        def run():
+            trainer.autograd_minibatch_grad(holder, batch, inds, z, 0, stats)
+    for _ in range(2):
+        run()
+    torch.cuda.synchronize()
+    ms = [event_ms(run) for _ in range(max(5, args.reps))]
+    med = statistics.median(ms)
+    print(json.dumps({"part": args.part, "envs": E, "steps": T, "batch": B, "minibatch": M, "obs_dim": D, "ms_per_call_median": round(med, 4),
+                      "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "grad_sumsq": float(stats[7]), "calls": len(ms)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", required=True, choices=["a", "b", "c", "c-eager"])
+    ap.add_argument("--part", required=True, choices=["a", "b", "c", "c-eager", "grad-autograd", "grad-device"])
+    ap.add_argument("--minibatch", type=int, default=16384)
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--reps", type=int, default=7)
     args = ap.parse_args()
+    if args.part.startswith("grad-"):
+        return grad_part(args)
     E, T = args.envs, args.steps
     env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=N_PED), ea.EnvWrappersConfig(positions="rel", statuses="ohe", type="Box"),
                                       num_envs=E, gamma=0.99, seed=1)

@@ -3,7 +3,8 @@
 
     python tools/kernel_asm_diff.py <checkout A> <checkout B> [--units evac_sweep_api.hip,...]
 
-For every translation unit of B's ``evacuation_amd.build.SOURCES`` (A's must be the same list) the device code is compiled with
+For every translation unit that both checkouts list in ``evacuation_amd.build.SOURCES`` (one that only one side has is named
+and left out) the device code is compiled with
 ``build.FLAGS`` and ``-S --cuda-device-only``, as tests/kernel_meta.py does, and split per kernel: its code, its kernel
 descriptor (.amdhsa_kernel .. .end_amdhsa_kernel) and its entry in the amdhsa.kernels metadata (the argument layout and the
 resource figures).  Comments are dropped, the function number of block labels (.LBB<f>_<n> -> .LBB_<n>) and every mangled
@@ -103,10 +104,11 @@ def main():
     args = ap.parse_args()
     builds = [load_build(os.path.abspath(c)) for c in (args.a, args.b)]
     units = [[os.path.basename(s) for s in b.SOURCES] for b in builds]
-    if units[0] != units[1]:
-        print(f"the translation units differ: {units[0]} against {units[1]}")
-        return 1
-    chosen = args.units.split(",") if args.units else units[1]
+    for side, other in ((0, 1), (1, 0)):                         # (a unit that one side adds or drops has nothing to be compared with)
+        for u in units[side]:
+            if u not in units[other]:
+                print(f"only in {'AB'[side]}: {u}")
+    chosen = args.units.split(",") if args.units else [u for u in units[1] if u in units[0]]
     with concurrent.futures.ThreadPoolExecutor(args.jobs) as pool:
         jobs = {(u, side): pool.submit(device_asm, builds[side], os.path.join(builds[side].CSRC, u)) for u in chosen for side in (0, 1)}
         asm = {key: split_kernels(job.result()) for key, job in jobs.items()}
