@@ -1453,36 +1453,22 @@ static int policy_rollout(evac_handle_t h, const char* what, int32_t n_learners,
                           float* next_value_out, evac_episode_stats_t* final_stats, double* norm_state, float gamma, float obs_clip,
                           float reward_clip, float epsilon, void* stream, const evac_learner_hyper_t* hypers = nullptr) {
     const std::string w = what;
-    if (h->p.n_ped > evac::kWave)
-        return fail(h, EVAC_ERR_UNSUPPORTED, w + ": rooms of more than 64 pedestrians are not supported (one wave per env)");
-    if (n_steps < 1) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": n_steps must be >= 1");
-    if (!policy || !next_obs || !next_done || !obs_out || !actions_out || !logprob_out || !value_out || !reward_out || !done_out ||
-        !next_value_out)
-        return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": policy and every output buffer but final_stats / norm_state must be non-NULL");
-    evac::PolicyArgs a{};
-    if (const std::string why = mlp_policy_check(*policy, h->p.obs_dim, a); !why.empty()) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
-    if ((uintptr_t)actions_out & 7u) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": actions_out must be 8-byte aligned");
+    std::string why = one_wave_check(h->p);
+    if (!why.empty()) return fail(h, EVAC_ERR_UNSUPPORTED, w + why);
+    evac::PolicyArgs a = collect_outputs(next_obs, next_done, obs_out, actions_out, logprob_out, value_out, reward_out, done_out,
+                                         next_value_out, final_stats);
     evac::PopulationArgs q{};
-    if (strides) {
-        if (n_learners < 1 || n_learners > EVAC_MAX_LEARNERS)
-            return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": n_learners must be in 1.." + std::to_string(EVAC_MAX_LEARNERS));
-        if (h->p.n_envs % n_learners != 0)
-            return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the handle's " + std::to_string(h->p.n_envs) + " envs are not " +
-                                                          std::to_string(n_learners) + " learners' equal shares");
-        if (!mlp_strides_ok(strides, policy->obs_dim, n_learners, q.stride))
-            return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": a learner stride is smaller than its tensor");
-        q.envs_per_learner = h->p.n_envs / n_learners;
-        q.wgs = (q.envs_per_learner + evac::PolicyFamily::kEnvsPerBlock - 1) / evac::PolicyFamily::kEnvsPerBlock;
-    }
+    why = collect_check(n_steps, a, true, policy);     // (the first refusal in the entry's order of checks)
+    if (why.empty()) why = mlp_policy_check(*policy, h->p.obs_dim, a);
+    if (why.empty()) why = collect_aligned(a);
+    if (why.empty() && strides) why = learner_shares(h->p.n_envs, n_learners, strides, policy->obs_dim, q);
+    if (!why.empty()) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
     evac::LearnerGammas lg{};
     if (hypers)
         for (int s = 0; s < n_learners; ++s) lg.gamma[s] = (float)hypers[s].gamma;
     // (parts / chained / persistent handles: joined first, then ONE kernel on `stream` over the whole batch)
     if (const int st = settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
     DeviceGuard g(h->device);
-    a.next_obs = next_obs; a.next_done = next_done; a.obs_out = obs_out; a.actions_out = actions_out; a.logprob_out = logprob_out;
-    a.value_out = value_out; a.reward_out = reward_out; a.done_out = done_out; a.next_value_out = next_value_out;
-    a.final_stats = final_stats;
     const evac::NormArgs na{norm_state, gamma, obs_clip, reward_clip, epsilon};
     const bool grav = h->p.obs_pos == EVAC_POS_GRAV, norm = norm_state != nullptr, def = h->default_cfg;
     const dim3 block(evac::PolicyFamily::kBlock);
@@ -1497,9 +1483,7 @@ static int policy_rollout(evac_handle_t h, const char* what, int32_t n_learners,
         return check_launch(h, what);
     }
     const auto fn = EVAC_PICK_BOOL3(evac::k_policy_rollout, grav, norm, def);
-    const int per_block = evac::PolicyFamily::kEnvsPerBlock;
-    hipLaunchKernelGGL(fn, dim3((unsigned)((h->p.n_envs + per_block - 1) / per_block)), block, 0, (hipStream_t)stream, h->p,
-                       (int)n_steps, a, na);
+    hipLaunchKernelGGL(fn, dim3((unsigned)policy_wgs(h->p.n_envs)), block, 0, (hipStream_t)stream, h->p, (int)n_steps, a, na);
     return check_launch(h, what);
 }
 
@@ -1572,43 +1556,23 @@ static int policy_evaluate(evac_handle_t h, const char* what, int32_t n_learners
         return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": unknown agent " + std::to_string(agent));
     if (scripted && strides)
         return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the scripted agent has no learners: evac_policy_evaluate runs it");
-    if (!progress || !episodes_out) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": progress / episodes_out is NULL");
-    if (n_episodes < 1 || max_steps < 1) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": n_episodes and max_steps must be >= 1");
-    if (scripted && norm_state)
-        return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the scripted agent reads no observation: norm_state must be NULL");
-    if ((uintptr_t)progress & 15u) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": progress must be 16-byte aligned");
+    evac::EvalArgs ev{};
     evac::PolicyArgs a{};
-    if (!scripted) {
-        if (!policy) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": a policy agent needs a policy");
-        if (const std::string why = mlp_policy_check(*policy, h->p.obs_dim, a); !why.empty())
-            return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
-    }
-    evac::PopulationArgs q{};
-    if (strides) {
-        if (n_learners < 1 || n_learners > EVAC_MAX_LEARNERS)
-            return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": n_learners must be in 1.." + std::to_string(EVAC_MAX_LEARNERS));
-        if (h->p.n_envs % n_learners != 0)
-            return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the handle's " + std::to_string(h->p.n_envs) + " envs are not " +
-                                                          std::to_string(n_learners) + " learners' equal shares");
-        if (!mlp_strides_ok(strides, policy->obs_dim, n_learners, q.stride))
-            return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": a learner stride is smaller than its tensor");
-        q.envs_per_learner = h->p.n_envs / n_learners;
-        q.wgs = (q.envs_per_learner + evac::PolicyFamily::kEnvsPerBlock - 1) / evac::PolicyFamily::kEnvsPerBlock;
-    }
-    if (h->p.n_ped > evac::kWave)
-        return fail(h, EVAC_ERR_UNSUPPORTED, w + ": rooms of more than 64 pedestrians are not supported (one wave per env)");
+    evac::PopulationArgs q{};                          // (below: the first refusal in the entry's order of checks)
+    std::string why = evaluate_check(agent, n_episodes, max_steps, progress, episodes_out, norm_state, obs_clip, epsilon, ev);
+    if (why.empty() && !scripted) why = policy ? mlp_policy_check(*policy, h->p.obs_dim, a) : ": a policy agent needs a policy";
+    if (why.empty() && strides) why = learner_shares(h->p.n_envs, n_learners, strides, policy->obs_dim, q);
+    if (!why.empty()) return fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
+    if (!(why = one_wave_check(h->p)).empty()) return fail(h, EVAC_ERR_UNSUPPORTED, w + why);
     // (parts / chained / persistent handles: joined first, then ONE kernel on `stream` over the whole batch)
     if (const int st = settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
     DeviceGuard g(h->device);
     // the sweep's turning points: extent - SWITCH_DISTANCE_TO_LEADER / 2 + step_size in double, rounded once
     // (baseline_wacuum_cleaner.py:18-28, constants.py:35), from the settings as the caller wrote them (as_written)
     const double step = as_written(h->cfg.step_size);
-    const float thr_x = (float)(as_written(h->cfg.width) - 0.2 / 2 + step);
-    const float thr_y = (float)(as_written(h->cfg.height) - 0.2 / 2 + step);
-    const evac::EvalArgs ev{(int4*)progress, episodes_out, norm_state, (int)n_episodes, (int)max_steps,
-                            agent == EVAC_AGENT_POLICY_SAMPLE ? 1 : 0, obs_clip, epsilon, thr_x, thr_y};
-    const int per_block = evac::PolicyFamily::kEnvsPerBlock;
-    const dim3 grid((unsigned)((h->p.n_envs + per_block - 1) / per_block)), block(evac::PolicyFamily::kBlock);
+    ev.thr_x = (float)(as_written(h->cfg.width) - 0.2 / 2 + step);
+    ev.thr_y = (float)(as_written(h->cfg.height) - 0.2 / 2 + step);
+    const dim3 grid((unsigned)policy_wgs(h->p.n_envs)), block(evac::PolicyFamily::kBlock);
     const bool grav = h->p.obs_pos == EVAC_POS_GRAV, norm = norm_state != nullptr, def = h->default_cfg;
     if (strides) {
         const auto fn = EVAC_PICK_BOOL3(evac::k_evaluate_population, grav, norm, def);

@@ -18,33 +18,25 @@ static_assert(sizeof(evac::Params) + 8 + sizeof(evac::PolicyArgs) + sizeof(evac:
 static_assert(sizeof(evac::PolicyFamily::Smem) + sizeof(evac::PolicySmem<false>) + sizeof(evac::EvalSmem) + sizeof(evac::DeepSetsSmem) <=
                   160 * 1024, "the deep-sets kernels' LDS beyond a CU's 160 KiB");
 
+static_assert(evac::kSetHidden == kSetEncoderHidden && evac::kSetMaxElemDim == kSetEncoderMaxElemDim,
+              "deepsets_check: the widths the deep-sets kernels take");
+
 namespace {
 
 using evac_host::handle_fail;
 
-// The checks the two entries share: the thirteen tensors as evac_policy_rollout makes them, then the encoder's.
-int check_networks(evac_handle_t h, const std::string& w, const evac_host::HandleView& v, const evac_mlp_policy_t* policy,
-                   const evac_deepsets_t* encoder, evac::PolicyArgs& a, evac::DeepSetsArgs& da) {
-    if (!policy) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": policy is NULL");
-    if (!encoder) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": encoder is NULL");
-    evac::PolicyArgs pa{};                             // (`a` and `da` are written only once every check has passed)
-    if (const std::string why = mlp_policy_check(*policy, v.p.obs_dim, pa); !why.empty())
-        return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
+// The checks the two entries share: the thirteen tensors as evac_policy_rollout makes them (into `a`), then the encoder's.
+// The text that follows the entry's name, or empty.
+std::string check_networks(const evac::Params& p, const evac_mlp_policy_t* policy, const evac_deepsets_t* encoder, evac::PolicyArgs& a,
+                           evac::DeepSetsArgs& da) {
+    if (!policy) return ": policy is NULL";
+    if (!encoder) return ": encoder is NULL";
+    if (const std::string why = mlp_policy_check(*policy, p.obs_dim, a); !why.empty()) return why;
     const evac_deepsets_t& S = *encoder;
-    if (!S.phi_w1 || !S.phi_b1 || !S.phi_w2 || !S.phi_b2 || !S.rho_w || !S.rho_b)
-        return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": a tensor pointer of the encoder is NULL");
-    if (S.hidden != evac::kSetHidden)
-        return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the encoder's hidden must be " + std::to_string(evac::kSetHidden));
     // (the gravity observation's 6 floats are no whole number of rows for any N >= 5, and no set for the others)
-    if (v.p.obs_pos == EVAC_POS_GRAV || S.set_elem_dim < 1 || S.set_elem_dim > evac::kSetMaxElemDim ||
-        (int64_t)S.set_elem_dim * (v.p.n_ped + 2) != (int64_t)v.p.obs_dim)
-        return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": set_elem_dim " + std::to_string(S.set_elem_dim) + " x (" +
-                                                             std::to_string(v.p.n_ped) + " + 2) elements is not the observation's " +
-                                                             std::to_string(v.p.obs_dim) + " floats (a Box observation is needed)");
-    if ((uintptr_t)S.rho_w & 15u) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": rho_w must be 16-byte aligned");
-    a = pa;
+    const bool rows_fit = p.obs_pos != EVAC_POS_GRAV && (int64_t)S.set_elem_dim * (p.n_ped + 2) == (int64_t)p.obs_dim;
     da = evac::DeepSetsArgs{S.phi_w1, S.phi_b1, S.phi_w2, S.phi_b2, S.rho_w, S.rho_b, (int)S.set_elem_dim};
-    return EVAC_OK;
+    return deepsets_check(S, p.obs_dim, p.n_ped, rows_fit);
 }
 
 }  // namespace
@@ -59,26 +51,22 @@ int evac_policy_rollout_deepsets(evac_handle_t h, int32_t n_steps, const evac_ml
     const std::string w = "evac_policy_rollout_deepsets";
     evac_host::HandleView v;
     if (const int rc = evac_host::handle_begin(h, w.c_str(), &v); rc != EVAC_OK) return rc;
-    if (v.p.n_ped > evac::kWave)
-        return handle_fail(h, EVAC_ERR_UNSUPPORTED, w + ": rooms of more than 64 pedestrians are not supported (one wave per env)");
-    if (n_steps < 1) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": n_steps must be >= 1");
-    if (!next_obs || !next_done || !obs_out || !actions_out || !logprob_out || !value_out || !reward_out || !done_out || !next_value_out)
-        return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": every output buffer but final_stats / norm_state must be non-NULL");
-    evac::PolicyArgs a{};
+    std::string why = one_wave_check(v.p);
+    if (!why.empty()) return handle_fail(h, EVAC_ERR_UNSUPPORTED, w + why);
+    evac::PolicyArgs a = collect_outputs(next_obs, next_done, obs_out, actions_out, logprob_out, value_out, reward_out, done_out,
+                                         next_value_out, final_stats);
     evac::DeepSetsArgs da{};
-    if (const int rc = check_networks(h, w, v, policy, encoder, a, da); rc != EVAC_OK) return rc;
-    if ((uintptr_t)actions_out & 7u) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": actions_out must be 8-byte aligned");
+    why = collect_check(n_steps, a, false, policy);    // (the first refusal in the entry's order of checks)
+    if (why.empty()) why = check_networks(v.p, policy, encoder, a, da);
+    if (why.empty()) why = collect_aligned(a);
+    if (!why.empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
     if (const int st = evac_host::handle_settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
     DeviceGuard g(v.device);
-    a.next_obs = next_obs; a.next_done = next_done; a.obs_out = obs_out; a.actions_out = actions_out; a.logprob_out = logprob_out;
-    a.value_out = value_out; a.reward_out = reward_out; a.done_out = done_out; a.next_value_out = next_value_out;
-    a.final_stats = final_stats;
     const evac::NormArgs na{norm_state, gamma, obs_clip, reward_clip, epsilon};
     const bool norm = norm_state != nullptr, def = v.default_cfg;
     const auto fn = EVAC_PICK_BOOL2(evac::k_policy_rollout_deepsets, norm, def);
-    const int per_block = evac::PolicyFamily::kEnvsPerBlock;
-    hipLaunchKernelGGL(fn, dim3((unsigned)((v.p.n_envs + per_block - 1) / per_block)), dim3(evac::PolicyFamily::kBlock), 0,
-                       (hipStream_t)stream, v.p, (int)n_steps, a, na, da);
+    hipLaunchKernelGGL(fn, dim3((unsigned)policy_wgs(v.p.n_envs)), dim3(evac::PolicyFamily::kBlock), 0, (hipStream_t)stream, v.p,
+                       (int)n_steps, a, na, da);
     return evac_host::handle_check_launch(h, w.c_str());
 }
 
@@ -92,23 +80,19 @@ int evac_policy_evaluate_deepsets(evac_handle_t h, int32_t agent, const evac_mlp
         return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the scripted agent has no network (use evac_policy_evaluate)");
     if (agent != EVAC_AGENT_POLICY_MEAN && agent != EVAC_AGENT_POLICY_SAMPLE)
         return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": unknown agent " + std::to_string(agent));
-    if (!progress || !episodes_out) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": progress / episodes_out is NULL");
-    if (n_episodes < 1 || max_steps < 1) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": n_episodes and max_steps must be >= 1");
-    if ((uintptr_t)progress & 15u) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": progress must be 16-byte aligned");
+    evac::EvalArgs ev{};
     evac::PolicyArgs a{};
     evac::DeepSetsArgs da{};
-    if (const int rc = check_networks(h, w, v, policy, encoder, a, da); rc != EVAC_OK) return rc;
-    if (v.p.n_ped > evac::kWave)
-        return handle_fail(h, EVAC_ERR_UNSUPPORTED, w + ": rooms of more than 64 pedestrians are not supported (one wave per env)");
+    std::string why = evaluate_check(agent, n_episodes, max_steps, progress, episodes_out, norm_state, obs_clip, epsilon, ev);
+    if (why.empty()) why = check_networks(v.p, policy, encoder, a, da);
+    if (!why.empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
+    if (!(why = one_wave_check(v.p)).empty()) return handle_fail(h, EVAC_ERR_UNSUPPORTED, w + why);
     if (const int st = evac_host::handle_settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
     DeviceGuard g(v.device);
-    const evac::EvalArgs ev{(int4*)progress, episodes_out, norm_state, (int)n_episodes, (int)max_steps,
-                            agent == EVAC_AGENT_POLICY_SAMPLE ? 1 : 0, obs_clip, epsilon, 0.0f, 0.0f};
     const bool norm = norm_state != nullptr, def = v.default_cfg;
     const auto fn = EVAC_PICK_BOOL2(evac::k_policy_evaluate_deepsets, norm, def);
-    const int per_block = evac::PolicyFamily::kEnvsPerBlock;
-    hipLaunchKernelGGL(fn, dim3((unsigned)((v.p.n_envs + per_block - 1) / per_block)), dim3(evac::PolicyFamily::kBlock), 0,
-                       (hipStream_t)stream, v.p, a, ev, da);
+    hipLaunchKernelGGL(fn, dim3((unsigned)policy_wgs(v.p.n_envs)), dim3(evac::PolicyFamily::kBlock), 0, (hipStream_t)stream, v.p, a, ev,
+                       da);
     return evac_host::handle_check_launch(h, w.c_str());
 }
 

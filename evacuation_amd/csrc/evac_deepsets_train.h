@@ -24,7 +24,7 @@
 
 namespace evac {
 
-constexpr int kSetTrainHidden = 24;             // (evac_deepsets.h: kSetHidden)
+constexpr int kSetTrainHidden = 24;             // (kSetHidden's: both asserted against evac_host.h's)
 constexpr int kSetTrainMaxElemDim = 6;
 constexpr int kSetBlock = 256;                  // 4 waves
 constexpr int kSetWaves = kSetBlock / 64;

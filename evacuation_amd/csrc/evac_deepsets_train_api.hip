@@ -10,6 +10,9 @@
 #include "evac_deepsets_train.h"
 #include "evac_train_host.h"
 
+static_assert(evac::kSetTrainHidden == kSetEncoderHidden && evac::kSetTrainMaxElemDim == kSetEncoderMaxElemDim,
+              "deepsets_check: the widths the gradient's kernels take, which are the rollout's (evac_deepsets_api.hip asserts its own)");
+
 namespace {
 
 constexpr int64_t kAlign = 256;
@@ -71,14 +74,10 @@ int evac_deepsets_minibatch_grad(const evac_mlp_policy_t* policy, const evac_dee
     if (!encoder || !encoder_grads_out) return EVAC_ERR_INVALID_ARGUMENT;
     const evac_deepsets_t& E = *encoder;
     const evac_deepsets_grads_t& G = *encoder_grads_out;
-    if (!E.phi_w1 || !E.phi_b1 || !E.phi_w2 || !E.phi_b2 || !E.rho_w || !E.rho_b || !G.phi_w1 || !G.phi_b1 || !G.phi_w2 || !G.phi_b2 ||
-        !G.rho_w || !G.rho_b)
-        return EVAC_ERR_INVALID_ARGUMENT;
-    if (E.hidden != evac::kSetTrainHidden || E.set_elem_dim < 1 || E.set_elem_dim > evac::kSetTrainMaxElemDim)
-        return EVAC_ERR_INVALID_ARGUMENT;
+    if (!G.phi_w1 || !G.phi_b1 || !G.phi_w2 || !G.phi_b2 || !G.rho_w || !G.rho_b) return EVAC_ERR_INVALID_ARGUMENT;
     const int D = a.D, ed = E.set_elem_dim;
-    if (D % ed != 0 || D / ed < 3) return EVAC_ERR_INVALID_ARGUMENT;        // (N + 2 rows, N >= 1)
-    if (((uintptr_t)E.rho_w & 15u) != 0) return EVAC_ERR_INVALID_ARGUMENT;
+    const bool rows_fit = ed > 0 && D % ed == 0 && D / ed >= 3;             // (N + 2 rows, N >= 1)
+    if (!deepsets_check(E, D, 0, rows_fit).empty()) return EVAC_ERR_INVALID_ARGUMENT;
 
     const int64_t M = n_minibatch;
     const SetLayout L = set_layout(D, M);
@@ -120,11 +119,7 @@ int evac_deepsets_minibatch_grad(const evac_mlp_policy_t* policy, const evac_dee
     const int64_t enc_wgs = (M + evac::kSetWaves - 1) / evac::kSetWaves;
     hipLaunchKernelGGL(evac::k_set_encode, dim3((unsigned)(enc_wgs > evac::kSetEncodeMaxWgs ? evac::kSetEncodeMaxWgs : enc_wgs)),
                        dim3(evac::kSetBlock), 0, S, s);
-    const size_t lds = evac::rpo_grad_lds_floats(D) * sizeof(float);
-    const int tiles = (D + evac::kW1Tile - 1) / evac::kW1Tile;
-    if (a.norm_adv) hipLaunchKernelGGL(evac::k_rpo_adv_stats<>, dim3(1), dim3(evac::kFinishBlock), 0, S, a);
-    hipLaunchKernelGGL(evac::k_rpo_grad<>, dim3((unsigned)a.P, 2u), dim3(evac::kGradBlock), lds, S, a);
-    hipLaunchKernelGGL(evac::k_rpo_finish<>, dim3((unsigned)(2 * evac::kFinishCombineWgs + 2 * tiles * a.S)), dim3(evac::kFinishBlock), 0, S, a);
+    rpo_launch(a, S);
     hipLaunchKernelGGL(evac::k_set_backward, dim3((unsigned)s.P), dim3(evac::kSetBlock), 0, S, s);
     const int rtiles = (D + evac::kSetRTile - 1) / evac::kSetRTile;
     hipLaunchKernelGGL(evac::k_set_finish, dim3((unsigned)(rtiles * s.Sr + 1)), dim3(evac::kSetBlock), 0, S, s);

@@ -1,5 +1,9 @@
-// What a translation unit beside evac_api.hip needs of a handle (evac_deepsets_api.hip: entries that take one).  The handle's
-// struct stays evac_api.hip's own; these four functions are defined there and are not exported from the library.
+// What the entries that run a network on a handle's envs share (evac_api.hip: evac_policy_rollout*, evac_policy_evaluate*;
+// evac_deepsets_api.hip: their deep-sets forms).  The handle's struct stays evac_api.hip's own: the four handle_* functions are
+// defined there and are not exported from the library.  Below them, host-only and inline: what every collection entry and every
+// evaluation entry refuses, the one-wave limit, a population's shares of the envs, and the grid.  Each returns the text that
+// follows the entry's name in its message (empty: accepted), as mlp_policy_check does; the entry reports it through its own fail,
+// at its own place in its order of checks.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,7 +11,8 @@
 #include <string>
 
 #include "../../include/evac.h"
-#include "evac_common.h"
+#include "evac_evaluate.h"
+#include "evac_host.h"
 
 namespace evac_host {
 
@@ -28,3 +33,67 @@ EVAC_HOST_LOCAL int handle_check_launch(evac_handle_t h, const char* what);
 #undef EVAC_HOST_LOCAL
 
 }  // namespace evac_host
+
+namespace {
+
+// One wave per env (EVAC_ERR_UNSUPPORTED): the collection entries refuse it first, the evaluation entries last.
+inline std::string one_wave_check(const evac::Params& p) {
+    if (p.n_ped > evac::kWave) return ": rooms of more than 64 pedestrians are not supported (one wave per env)";
+    return {};
+}
+// One workgroup per kEnvsPerBlock envs (of the handle, or of a learner's share).
+inline int policy_wgs(int n_envs) { return (n_envs + evac::PolicyFamily::kEnvsPerBlock - 1) / evac::PolicyFamily::kEnvsPerBlock; }
+
+// The outputs of a collection launch; the 13 pointers in front of them are mlp_policy_check's.
+inline evac::PolicyArgs collect_outputs(float* next_obs, float* next_done, float* obs_out, float* actions_out, float* logprob_out,
+                                        float* value_out, float* reward_out, float* done_out, float* next_value_out,
+                                        evac_episode_stats_t* final_stats) {
+    evac::PolicyArgs a{};
+    a.next_obs = next_obs; a.next_done = next_done; a.obs_out = obs_out; a.actions_out = actions_out; a.logprob_out = logprob_out;
+    a.value_out = value_out; a.reward_out = reward_out; a.done_out = done_out; a.next_value_out = next_value_out;
+    a.final_stats = final_stats;
+    return a;
+}
+// What every collection entry refuses of its step count and buffers (`a`: collect_outputs), before it looks at the networks.
+// `policy_named`: the linear entries refuse a NULL policy with the same message, the deep-sets entry with its networks.
+inline std::string collect_check(int32_t n_steps, const evac::PolicyArgs& a, bool policy_named, const evac_mlp_policy_t* policy) {
+    if (n_steps < 1) return ": n_steps must be >= 1";
+    const bool buffers = a.next_obs && a.next_done && a.obs_out && a.actions_out && a.logprob_out && a.value_out && a.reward_out &&
+                         a.done_out && a.next_value_out;
+    if (!buffers || (policy_named && !policy))
+        return std::string(policy_named ? ": policy and every" : ": every") + " output buffer but final_stats / norm_state must be non-NULL";
+    return {};
+}
+// ... and after the networks (the kernels store an action as one float2)
+inline std::string collect_aligned(const evac::PolicyArgs& a) {
+    if ((uintptr_t)a.actions_out & 7u) return ": actions_out must be 8-byte aligned";
+    return {};
+}
+
+// What every evaluation entry refuses of its counts and buffers, after the agent code and before the networks, and the
+// arguments it launches with (the scripted agent's turning points left 0).
+inline std::string evaluate_check(int32_t agent, int32_t n_episodes, int32_t max_steps, int32_t* progress, evac_episode_stats_t* episodes_out,
+                                  const double* norm_state, float obs_clip, float epsilon, evac::EvalArgs& ev) {
+    if (!progress || !episodes_out) return ": progress / episodes_out is NULL";
+    if (n_episodes < 1 || max_steps < 1) return ": n_episodes and max_steps must be >= 1";
+    if (agent == EVAC_AGENT_VACUUM_CLEANER && norm_state) return ": the scripted agent reads no observation: norm_state must be NULL";
+    if ((uintptr_t)progress & 15u) return ": progress must be 16-byte aligned";
+    ev = evac::EvalArgs{(int4*)progress, episodes_out, norm_state, (int)n_episodes, (int)max_steps,
+                        agent == EVAC_AGENT_POLICY_SAMPLE ? 1 : 0, obs_clip, epsilon, 0.0f, 0.0f};
+    return {};
+}
+
+// A population's equal shares of a handle's envs into `q`: the learners' number, the envs divisible by it, every stride at least
+// its tensor.
+inline std::string learner_shares(int n_envs, int32_t n_learners, const evac_mlp_policy_strides_t* strides, int32_t obs_dim,
+                                  evac::PopulationArgs& q) {
+    if (n_learners < 1 || n_learners > EVAC_MAX_LEARNERS) return ": n_learners must be in 1.." + std::to_string(EVAC_MAX_LEARNERS);
+    if (n_envs % n_learners != 0)
+        return ": the handle's " + std::to_string(n_envs) + " envs are not " + std::to_string(n_learners) + " learners' equal shares";
+    if (!mlp_strides_ok(strides, obs_dim, n_learners, q.stride)) return ": a learner stride is smaller than its tensor";
+    q.envs_per_learner = n_envs / n_learners;
+    q.wgs = policy_wgs(q.envs_per_learner);
+    return {};
+}
+
+}  // namespace

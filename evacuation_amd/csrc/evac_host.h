@@ -1,6 +1,6 @@
 // Host-only helpers shared by the six translation units of libevac: which device a call runs on; the 13 tensors of the
-// actor-critic as an array, their sizes, the check of a population's strides and of a policy against a handle; the picker of a
-// kernel template's instantiation over bools; what every entry refuses of evac_learner_hyper_t.
+// actor-critic as an array, their sizes, the check of a population's strides, of a policy against a handle and of a set encoder's
+// struct; the picker of a kernel template's instantiation over bools; what every entry refuses of evac_learner_hyper_t.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -67,15 +67,30 @@ inline bool mlp_strides_ok(const evac_mlp_policy_strides_t* st, int32_t obs_dim,
     return true;
 }
 // A policy against a handle's observation width, for the entries that run it on a handle's envs (Args: evac::PolicyArgs, which
-// starts with the 13 pointers).  Empty and the pointers in `a` (the rest of it zero), or what is refused: the text that follows
-// the entry's name in its message.  The entry reports it through its own fail.
+// starts with the 13 pointers).  Empty and the pointers in `a` (the rest of it as it was), or what is refused: the text that
+// follows the entry's name in its message.  The entry reports it through its own fail.
 template <class Args>
 inline std::string mlp_policy_check(const evac_mlp_policy_t& P, int32_t obs_dim, Args& a) {
     if (!mlp_all_set(P)) return ": a tensor pointer of the policy is NULL";
     if (P.hidden != kMlpHidden) return ": hidden must be 64";
     if (P.obs_dim != obs_dim) return ": policy obs_dim " + std::to_string(P.obs_dim) + " != evac_obs_dim " + std::to_string(obs_dim);
-    a = Args{P.actor_w1, P.actor_b1, P.actor_w2, P.actor_b2, P.actor_w3, P.actor_b3, P.actor_logstd,
-             P.critic_w1, P.critic_b1, P.critic_w2, P.critic_b2, P.critic_w3, P.critic_b3};
+    a.aw1 = P.actor_w1; a.ab1 = P.actor_b1; a.aw2 = P.actor_w2; a.ab2 = P.actor_b2; a.aw3 = P.actor_w3; a.ab3 = P.actor_b3;
+    a.logstd = P.actor_logstd;
+    a.cw1 = P.critic_w1; a.cb1 = P.critic_b1; a.cw2 = P.critic_w2; a.cb2 = P.critic_b2; a.cw3 = P.critic_w3; a.cb3 = P.critic_b3;
+    return {};
+}
+
+// evac_deepsets_t for every entry that takes one: six pointers, the hidden width and the element width the kernels take
+// (evac_deepsets.h and evac_deepsets_train.h assert theirs against these), rho_w's alignment.  `rows_fit` is the entry's own
+// condition on set_elem_dim x rows = the observation (a handle has its N; the gradient has none); `n_ped` serves the message.
+constexpr int kSetEncoderHidden = 24, kSetEncoderMaxElemDim = 6;
+inline std::string deepsets_check(const evac_deepsets_t& S, int32_t obs_dim, int32_t n_ped, bool rows_fit) {
+    if (!S.phi_w1 || !S.phi_b1 || !S.phi_w2 || !S.phi_b2 || !S.rho_w || !S.rho_b) return ": a tensor pointer of the encoder is NULL";
+    if (S.hidden != kSetEncoderHidden) return ": the encoder's hidden must be " + std::to_string(kSetEncoderHidden);
+    if (S.set_elem_dim < 1 || S.set_elem_dim > kSetEncoderMaxElemDim || !rows_fit)
+        return ": set_elem_dim " + std::to_string(S.set_elem_dim) + " x (" + std::to_string(n_ped) + " + 2) elements is not the observation's " +
+               std::to_string(obs_dim) + " floats (a Box observation is needed)";
+    if ((uintptr_t)S.rho_w & 15u) return ": rho_w must be 16-byte aligned";
     return {};
 }
 

@@ -65,22 +65,6 @@ int64_t evac_rpo_workspace_bytes(int32_t obs_dim, int64_t n_minibatch) {
 }
 
 namespace {
-// the launches of one minibatch's gradient; `gate` = the optimiser's header whose stop flag the kernels honour, or NULL
-void rpo_launch(const evac::RpoArgs& a, hipStream_t S, const evac::AdamHeader* gate) {
-    const size_t lds = evac::rpo_grad_lds_floats(a.D) * sizeof(float);
-    const int tiles = (a.D + evac::kW1Tile - 1) / evac::kW1Tile;
-    const dim3 fin((unsigned)(2 * evac::kFinishCombineWgs + 2 * tiles * a.S));
-    if (!gate) {
-        if (a.norm_adv) hipLaunchKernelGGL(evac::k_rpo_adv_stats<>, dim3(1), dim3(evac::kFinishBlock), 0, S, a);
-        hipLaunchKernelGGL(evac::k_rpo_grad<>, dim3((unsigned)a.P, 2u), dim3(evac::kGradBlock), lds, S, a);
-        hipLaunchKernelGGL(evac::k_rpo_finish<>, fin, dim3(evac::kFinishBlock), 0, S, a);
-    } else {
-        if (a.norm_adv) hipLaunchKernelGGL(evac::k_rpo_adv_stats<const evac::AdamHeader*>, dim3(1), dim3(evac::kFinishBlock), 0, S, a, gate);
-        hipLaunchKernelGGL(evac::k_rpo_grad<const evac::AdamHeader*>, dim3((unsigned)a.P, 2u), dim3(evac::kGradBlock), lds, S, a, gate);
-        hipLaunchKernelGGL(evac::k_rpo_finish<const evac::AdamHeader*>, fin, dim3(evac::kFinishBlock), 0, S, a, gate);
-    }
-}
-
 void adam_launch(const evac::AdamArgs& a, hipStream_t S) {
     const int n = a.end[evac::kAdamTensors - 1];
     hipLaunchKernelGGL(evac::k_adam, dim3((unsigned)((n + evac::kAdamBlock - 1) / evac::kAdamBlock)), dim3(evac::kAdamBlock), 0, S, a);
@@ -105,7 +89,7 @@ int rpo_minibatch(const evac_mlp_policy_t* policy, const evac_rpo_loss_config_t*
     const int dev = device_of(workspace);
     DeviceGuard g(dev);
     if (rpo_raise_lds<evac::k_rpo_grad<>>(a.D, dev) != EVAC_OK) return EVAC_ERR_HIP;
-    rpo_launch(a, (hipStream_t)stream, nullptr);
+    rpo_launch(a, (hipStream_t)stream);
     if (adam) adam_launch(o, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? EVAC_OK : EVAC_ERR_HIP;
 }
@@ -170,7 +154,7 @@ int evac_rpo_update(const evac_mlp_policy_t* policy, const evac_mlp_policy_grads
     }
     rpo_update_steps(a, o, batch_size, n_minibatch, n_epochs, perms, rpo_noise, stats_out, first_draw_counter,
                      [S](const evac::RpoArgs& step, const evac::AdamArgs& adam, uint64_t) {
-                         rpo_launch(step, S, adam.hdr);
+                         rpo_launch(step, S, (const evac::AdamHeader*)adam.hdr);
                          adam_launch(adam, S);
                      });
     return hipGetLastError() == hipSuccess ? EVAC_OK : EVAC_ERR_HIP;

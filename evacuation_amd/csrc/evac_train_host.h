@@ -1,8 +1,8 @@
 // Host side of the trainer's update, the part its translation units share (evac_train_api.hip: one learner;
 // evac_population_api.hip: a population; evac_sweep_api.hip: ... with a configuration per learner; evac_deepsets_train_api.hip:
 // the gradient behind a set encoder): what the entries check of
-// their arguments, the kernels' argument structs, the walk over an update call's minibatch steps, and the raising of a gradient
-// kernel's dynamic-LDS limit.
+// their arguments, the kernels' argument structs, the walk over an update call's minibatch steps, the raising of a gradient
+// kernel's dynamic-LDS limit, and the launches of one minibatch's gradient.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -151,5 +151,17 @@ inline int rpo_raise_lds(int D, int dev) {
         raised[slot] = true;
     }
     return EVAC_OK;
+}
+
+// The launches of one minibatch's gradient.  `gate`: nothing, or the optimiser's header (const evac::AdamHeader*) whose stop flag
+// the kernels honour.  A unit instantiates the kernels of the forms it calls alone.
+template <class... Gate>
+inline void rpo_launch(const evac::RpoArgs& a, hipStream_t S, Gate... gate) {
+    const size_t lds = evac::rpo_grad_lds_floats(a.D) * sizeof(float);
+    const int tiles = (a.D + evac::kW1Tile - 1) / evac::kW1Tile;
+    const dim3 fin((unsigned)(2 * evac::kFinishCombineWgs + 2 * tiles * a.S));
+    if (a.norm_adv) hipLaunchKernelGGL(evac::k_rpo_adv_stats<Gate...>, dim3(1), dim3(evac::kFinishBlock), 0, S, a, gate...);
+    hipLaunchKernelGGL(evac::k_rpo_grad<Gate...>, dim3((unsigned)a.P, 2u), dim3(evac::kGradBlock), lds, S, a, gate...);
+    hipLaunchKernelGGL(evac::k_rpo_finish<Gate...>, fin, dim3(evac::kFinishBlock), 0, S, a, gate...);
 }
 }  // namespace

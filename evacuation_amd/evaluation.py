@@ -68,7 +68,38 @@ class EvaluationResult:
         return out
 
 
-class PolicyEvaluator:
+class _Evaluator:
+    """What the two evaluators share: ``env`` (reset once), ``snapshot`` (the state every evaluation starts from) and the launch
+    loop."""
+
+    launches = 0                               # launches of the last evaluate()
+
+    def restore(self) -> None:
+        for k in _STATE:
+            getattr(self.env, k).copy_(self.snapshot[k])
+
+    def _run(self, n_episodes: int, max_steps_per_launch: int, launch):
+        """``restore()``, then ``progress, out = launch(progress, out)`` until every env has finished ``n_episodes`` episodes;
+        returns the two.  The one host read per launch is ``progress[:, 0].min()``."""
+        self.restore()
+        progress = out = None
+        self.launches = 0
+        # (every step either ends an episode or brings it one step nearer to max_timesteps: the loop below ends by itself;
+        # the bound turns a launch that made no progress into an error instead of a hang)
+        bound = -(-int(n_episodes) * int(self.env.env_config.max_timesteps) // int(max_steps_per_launch)) + 1
+        while True:
+            if self.launches >= bound:
+                raise RuntimeError(f"evaluate: {self.launches} launches of {max_steps_per_launch} steps did not finish {n_episodes} episodes")
+            progress, out = launch(progress, out)
+            self.launches += 1
+            if int(progress[:, 0].min()) >= int(n_episodes):
+                return progress, out
+
+    def close(self) -> None:
+        self.env.close()
+
+
+class PolicyEvaluator(_Evaluator):
     """An evaluation batch of ``num_envs`` envs with a handle of its own, reset ONCE; the state of that reset is kept, and every
     ``evaluate`` restores it first: all evaluations see the same start states, and -- because the Philox counters of the reset
     draws and of the pedestrians' noise come from ``clock`` -- the same reset draws and noise streams."""
@@ -80,11 +111,6 @@ class PolicyEvaluator:
         self.env.reset()
         self.snapshot = {k: getattr(self.env, k).clone() for k in _STATE}
         self.num_envs = self.env.num_envs
-        self.launches = 0                      # launches of the last evaluate()
-
-    def restore(self) -> None:
-        for k in _STATE:
-            getattr(self.env, k).copy_(self.snapshot[k])
 
     def evaluate(self, agent, n_episodes: int = 1, *, deterministic: bool = True, norm_state: Optional[torch.Tensor] = None,
                  obs_clip: float = 1.0, epsilon: float = 1e-8, max_steps_per_launch: int = 4096) -> EvaluationResult:
@@ -101,24 +127,9 @@ class PolicyEvaluator:
                 raise ValueError(f"evaluate: norm_state must be float64 [rows, {W}], got {norm_state.dtype} {tuple(norm_state.shape)}")
             rows = torch.arange(E, device=env.device) % norm_state.shape[0]
             norm = (norm_state.to(env.device)[rows].contiguous(), float(obs_clip), float(epsilon))
-        self.restore()
-        progress = out = None
-        self.launches = 0
-        # (every step either ends an episode or brings it one step nearer to max_timesteps: the loop below ends by itself;
-        # the bound turns a launch that made no progress into an error instead of a hang)
-        bound = -(-int(n_episodes) * int(env.env_config.max_timesteps) // int(max_steps_per_launch)) + 1
-        while True:
-            if self.launches >= bound:
-                raise RuntimeError(f"evaluate: {self.launches} launches of {max_steps_per_launch} steps did not finish {n_episodes} episodes")
-            progress, out = env.policy_evaluate(agent, n_episodes, max_steps_per_launch, progress, out, deterministic=deterministic,
-                                                _norm=norm)
-            self.launches += 1
-            if int(progress[:, 0].min()) >= int(n_episodes):
-                break
+        progress, out = self._run(n_episodes, max_steps_per_launch, lambda progress, out: env.policy_evaluate(
+            agent, n_episodes, max_steps_per_launch, progress, out, deterministic=deterministic, _norm=norm))
         return EvaluationResult.from_records(out, progress[:, 1].clone(), env.n_ped)
-
-    def close(self) -> None:
-        self.env.close()
 
 
 def check_population_norm_state(norm_state, num_learners: int, obs_dim: int):
@@ -139,7 +150,7 @@ def check_population_norm_state(norm_state, num_learners: int, obs_dim: int):
     return parts
 
 
-class PopulationEvaluator:
+class PopulationEvaluator(_Evaluator):
     """``PolicyEvaluator`` for the S learners of a ``PolicyPopulation`` in one set of launches
     (``evac_policy_evaluate_population``): ONE handle of ``num_learners x num_envs`` envs, reset once; learner s evaluates in
     envs ``[s E_l, (s + 1) E_l)`` with the global ids of envs ``[0, E_l)``, so every learner's result is, bit for bit, what
@@ -163,11 +174,6 @@ class PopulationEvaluator:
         for k in _STATE:
             t = getattr(self.env, k)
             self.snapshot[k] = t[:E_l].repeat((S,) + (1,) * (t.dim() - 1))
-        self.launches = 0                      # launches of the last evaluate()
-
-    def restore(self) -> None:
-        for k in _STATE:
-            getattr(self.env, k).copy_(self.snapshot[k])
 
     def evaluate(self, population, n_episodes: int = 1, *, deterministic: bool = True, norm_state=None, obs_clip: float = 1.0,
                  epsilon: float = 1e-8, max_steps_per_launch: int = 4096) -> List[EvaluationResult]:
@@ -185,21 +191,7 @@ class PopulationEvaluator:
             rows = torch.arange(E_l, device=env.device)
             state = torch.cat([t.to(env.device)[rows % t.shape[0]] for t in parts]).contiguous()
             norm = (state, float(obs_clip), float(epsilon))
-        self.restore()
-        progress = out = None
-        self.launches = 0
-        # (the launch bound of PolicyEvaluator.evaluate: a launch that made no progress is an error, not a hang)
-        bound = -(-int(n_episodes) * int(env.env_config.max_timesteps) // int(max_steps_per_launch)) + 1
-        while True:
-            if self.launches >= bound:
-                raise RuntimeError(f"evaluate: {self.launches} launches of {max_steps_per_launch} steps did not finish {n_episodes} episodes")
-            progress, out = env.policy_evaluate_population(population, n_episodes, max_steps_per_launch, progress, out,
-                                                           deterministic=deterministic, shared_episodes=True, _norm=norm)
-            self.launches += 1
-            if int(progress[:, 0].min()) >= int(n_episodes):
-                break
+        progress, out = self._run(n_episodes, max_steps_per_launch, lambda progress, out: env.policy_evaluate_population(
+            population, n_episodes, max_steps_per_launch, progress, out, deterministic=deterministic, shared_episodes=True, _norm=norm))
         records, steps = out.view(int(n_episodes), S, E_l, out.shape[-1]), progress[:, 1].clone().view(S, E_l)
         return [EvaluationResult.from_records(records[:, s], steps[s], env.n_ped) for s in range(S)]
-
-    def close(self) -> None:
-        self.env.close()

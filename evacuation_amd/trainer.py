@@ -125,11 +125,12 @@ def flatten_batch(storage: Dict[str, torch.Tensor], advantages: torch.Tensor, re
             "b_values": storage["values"].reshape(-1)}
 
 
-def _tensor_struct(cache: list, tensors) -> "_lib.EvacMlpPolicyGrads":
-    """The addresses of 13 tensors as ``evac_mlp_policy_grads_t``, rebuilt when one of them changes.  ``cache``: [key, struct]."""
+def _tensor_struct(cache: list, tensors, struct=_lib.EvacMlpPolicyGrads):
+    """The addresses of the tensors as ``struct`` (``evac_mlp_policy_grads_t``: 13; ``evac_deepsets_grads_t``: the encoder's 6),
+    rebuilt when one of them changes.  ``cache``: [key, struct]."""
     key = tuple(t.data_ptr() for t in tensors)
     if key != cache[0]:
-        cache[:] = key, _lib.EvacMlpPolicyGrads(*key)
+        cache[:] = key, struct(*key)
     return cache[1]
 
 
@@ -138,7 +139,7 @@ class _GradState:
 
     def __init__(self):
         self.binder, self.grads, self.workspace = None, [None, None], None
-        self.encoder_grads, self.deepsets_workspace = [None, None], None     # deepsets_minibatch_grad's
+        self.encoder_grads = [None, None]                                    # deepsets_minibatch_grad's
 
 
 def _grad_state(net) -> _GradState:
@@ -163,11 +164,7 @@ def ensure_grads(net) -> "_lib.EvacMlpPolicyGrads":
 def ensure_encoder_grads(net) -> "_lib.EvacDeepSetsGrads":
     """``ensure_grads`` for the set encoder's six tensors: the addresses of their ``.grad`` as ``evac_deepsets_grads_t``."""
     ensure_grads(net)
-    cache = _grad_state(net).encoder_grads
-    key = tuple(t.grad.data_ptr() for t in deepsets_tensors(net))
-    if key != cache[0]:
-        cache[:] = key, _lib.EvacDeepSetsGrads(*key)
-    return cache[1]
+    return _tensor_struct(_grad_state(net).encoder_grads, [t.grad for t in deepsets_tensors(net)], _lib.EvacDeepSetsGrads)
 
 
 def _batch_args(net, batch: Dict[str, torch.Tensor], deepsets: bool = False):
@@ -190,15 +187,16 @@ def _batch_args(net, batch: Dict[str, torch.Tensor], deepsets: bool = False):
     return B, D, dev, st, pol, grads, [B] + [_ptr(batch[k]) for k in BATCH_KEYS]
 
 
-def _call_buffers(st: _GradState, D: int, M: int, dev, rpo_noise, stats, steps: Optional[int] = None):
+def _call_buffers(st: _GradState, D: int, M: int, dev, rpo_noise, stats, steps: Optional[int] = None,
+                  sizer: str = "evac_rpo_workspace_bytes"):
     """``rpo_noise`` and ``stats`` checked against the call's shape ([M, 2] and [8]; [steps, M, 2] and [steps, 8] for a whole
-    update), ``stats`` made if None, the workspace grown if too small; returns (stats, the workspace)."""
+    update), ``stats`` made if None, the workspace grown if too small for ``sizer``'s figure; returns (stats, the workspace)."""
     lead = () if steps is None else (steps,)
     if rpo_noise is not None:
         _f32(rpo_noise, lead + (M, 2), "rpo_noise")
-    need = int(_lib.load().evac_rpo_workspace_bytes(D, M))
+    need = int(getattr(_lib.load(), sizer)(D, M))
     if need < 0:
-        raise _lib.EvacError(need, f"evac_rpo_workspace_bytes({D}, {M})")
+        raise _lib.EvacError(need, f"{sizer}({D}, {M})")
     if st.workspace is None or st.workspace.numel() < need or st.workspace.device != dev:
         st.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
     if stats is None:
@@ -216,17 +214,24 @@ def _u64(x: int) -> int:
     return int(x) & (2 ** 64 - 1)
 
 
-def _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, opt: Optional["DeviceAdam"]) -> torch.Tensor:
-    """``evac_rpo_minibatch_grad``, or with ``opt`` ``evac_rpo_minibatch_step``: the same arguments and the optimiser's three."""
-    B, D, dev, st, pol, grads, b_args = _batch_args(net, batch)
+def _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, opt: Optional["DeviceAdam"],
+                    deepsets: bool = False) -> torch.Tensor:
+    """``evac_rpo_minibatch_grad``, or with ``opt`` ``evac_rpo_minibatch_step``: the same arguments and the optimiser's three;
+    or with ``deepsets`` ``evac_deepsets_minibatch_grad``: the same arguments, the encoder after the policy and its gradients
+    after the policy's, and a workspace of its own size."""
+    B, D, dev, st, pol, grads, b_args = _batch_args(net, batch, deepsets)
+    if deepsets:
+        enc, enc_grads = st.binder.encoder(net), ensure_encoder_grads(net)
     if mb_inds.dtype != torch.int64 or mb_inds.device != dev or not mb_inds.is_contiguous() or mb_inds.dim() != 1:
         raise ValueError("mb_inds: expected a contiguous int64 device vector")
     M = int(mb_inds.shape[0])
-    stats, ws = _call_buffers(st, D, M, dev, rpo_noise, stats)
+    stats, ws = _call_buffers(st, D, M, dev, rpo_noise, stats, sizer=f"evac_{'deepsets' if deepsets else 'rpo'}_workspace_bytes")
     lc = _loss_config(cfg)
     args = [C.byref(pol), C.byref(lc), *b_args, M, _ptr(mb_inds), _ptr(rpo_noise), _u64(seed), _u64(draw_counter), C.byref(grads),
             _ptr(stats), _ptr(ws), _stream(dev)]
-    if opt is None:
+    if deepsets:
+        rc = _lib.load().evac_deepsets_minibatch_grad(args[0], C.byref(enc), *args[1:-3], C.byref(enc_grads), *args[-3:])
+    elif opt is None:
         rc = _lib.load().evac_rpo_minibatch_grad(*args)
     else:
         oc = opt.config()
@@ -253,28 +258,7 @@ def deepsets_minibatch_grad(net, batch: Dict[str, torch.Tensor], mb_inds: torch.
     synchronisation, capturable.  The optimiser stays torch's (``RPOTrainer(grad_fn=deepsets_kernel_grad)``)."""
     if not is_deepsets(net):
         raise ValueError("deepsets_minibatch_grad: the network has no set encoder (`deep_sets`); its gradient is rpo_minibatch_grad's")
-    B, D, dev, st, pol, grads, b_args = _batch_args(net, batch, deepsets=True)
-    enc, enc_grads = st.binder.encoder(net), ensure_encoder_grads(net)
-    if mb_inds.dtype != torch.int64 or mb_inds.device != dev or not mb_inds.is_contiguous() or mb_inds.dim() != 1:
-        raise ValueError("mb_inds: expected a contiguous int64 device vector")
-    M = int(mb_inds.shape[0])
-    if rpo_noise is not None:
-        _f32(rpo_noise, (M, 2), "rpo_noise")
-    need = int(_lib.load().evac_deepsets_workspace_bytes(D, M))
-    if need < 0:
-        raise _lib.EvacError(need, f"evac_deepsets_workspace_bytes({D}, {M})")
-    if st.deepsets_workspace is None or st.deepsets_workspace.numel() < need or st.deepsets_workspace.device != dev:
-        st.deepsets_workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    if stats is None:
-        stats = torch.empty(8, dtype=torch.float32, device=dev)
-    else:
-        _f32(stats, (8,), "stats")
-    lc = _loss_config(cfg)
-    rc = _lib.load().evac_deepsets_minibatch_grad(C.byref(pol), C.byref(enc), C.byref(lc), *b_args, M, _ptr(mb_inds), _ptr(rpo_noise),
-                                                  _u64(seed), _u64(draw_counter), C.byref(grads), C.byref(enc_grads), _ptr(stats),
-                                                  _ptr(st.deepsets_workspace), _stream(dev))
-    _lib.check(rc)
-    return stats
+    return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, None, deepsets=True)
 
 
 HEADER_FIELDS = ("t", "P1", "P2", "stop", "steps_run", "epochs_run")

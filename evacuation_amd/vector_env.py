@@ -603,17 +603,27 @@ class BatchedEvacuationEnv:
         hypers = None if gammas is None else _lib.learner_hypers(population.num_learners, gamma=[float(g) for g in gammas])
         return self._policy_rollout(population.nets[0], population, n_steps, next_obs, next_done, out, _norm, hypers)
 
-    def _policy_rollout(self, net, population, n_steps, next_obs, next_done, out, _norm, hypers=None):
-        from .policy import MAX_PEDESTRIANS, PolicyBinder, is_deepsets, refuse_deepsets
+    def _one_wave(self, what: str) -> None:
+        from .policy import MAX_PEDESTRIANS
         if self.n_ped > MAX_PEDESTRIANS:
-            raise NotImplementedError(f"policy_rollout runs one wave per env: rooms of at most {MAX_PEDESTRIANS} pedestrians "
+            raise NotImplementedError(f"{what} runs one wave per env: rooms of at most {MAX_PEDESTRIANS} pedestrians "
                                       f"(this env has {self.n_ped})")
+
+    def _binder(self):
+        """The env's ``PolicyBinder`` (a network's tensors as ``evac_mlp_policy_t`` / ``evac_deepsets_t``), made at first use."""
+        binder = getattr(self, "_policy_binder", None)
+        if binder is None:
+            from .policy import PolicyBinder
+            binder = self._policy_binder = PolicyBinder(self.obs_dim, self.device, self.n_ped)
+        return binder
+
+    def _policy_rollout(self, net, population, n_steps, next_obs, next_done, out, _norm, hypers=None):
+        from .policy import is_deepsets, refuse_deepsets
+        self._one_wave("policy_rollout")
         T, E, D = int(n_steps), self.num_envs, self.obs_dim
         if T < 1:
             raise ValueError("policy_rollout: n_steps must be >= 1")
-        binder = getattr(self, "_policy_binder", None)
-        if binder is None:
-            binder = self._policy_binder = PolicyBinder(D, self.device, self.n_ped)
+        binder = self._binder()
         pol = binder(net)
         enc = None
         if is_deepsets(net):                  # the set encoder in front of the actor-critic: evac_policy_rollout_deepsets
@@ -662,19 +672,22 @@ class BatchedEvacuationEnv:
         ``_norm = (norm_state, obs_clip, epsilon)``: the trainer's observation statistics applied FROZEN (read only) -- see
         ``NormalizedVectorEnv.policy_evaluate``.  No host synchronisation; capturable; the weights are read when the kernel runs.
         A network with a set encoder (``deep_sets``) goes to ``evac_policy_evaluate_deepsets``."""
-        from .policy import MAX_PEDESTRIANS, PolicyBinder, is_deepsets
         check_evaluate_args(agent, n_episodes, max_steps, _norm)
-        if self.n_ped > MAX_PEDESTRIANS:
-            raise NotImplementedError(f"policy_evaluate runs one wave per env: rooms of at most {MAX_PEDESTRIANS} pedestrians "
-                                      f"(this env has {self.n_ped})")
+        return self._policy_evaluate("policy_evaluate", agent, None, n_episodes, max_steps, progress, out, deterministic, 0, _norm)
+
+    def _policy_evaluate(self, what, agent, population, n_episodes, max_steps, progress, out, deterministic, shared_episodes, _norm):
+        """What ``policy_evaluate`` and ``policy_evaluate_population`` share, after their own checks of the agent: the one-wave
+        limit, the learners' shares, the agent's code and structs, ``progress`` / ``out`` / the frozen statistics made or checked, and the call."""
+        from .policy import is_deepsets
+        self._one_wave(what)
         K, T, E, D = int(n_episodes), int(max_steps), self.num_envs, self.obs_dim
-        enc = None
+        if population is not None and E % int(population.num_learners):
+            raise ValueError(f"{what}: {E} envs are not {int(population.num_learners)} learners' equal shares")
+        pol = enc = None
         if isinstance(agent, str):
-            code, pol = EVALUATE_AGENTS[agent], None
+            code = EVALUATE_AGENTS[agent]
         else:
-            binder = getattr(self, "_policy_binder", None)
-            if binder is None:
-                binder = self._policy_binder = PolicyBinder(D, self.device, self.n_ped)
+            binder = self._binder()
             code, pol = (_lib.AGENT_POLICY_MEAN if deterministic else _lib.AGENT_POLICY_SAMPLE), C.byref(binder(agent))
             if is_deepsets(agent):
                 enc = binder.encoder(agent)
@@ -689,12 +702,14 @@ class BatchedEvacuationEnv:
         state, obs_clip, eps = (None, 0.0, 0.0) if _norm is None else _norm
         if state is not None:
             self._check_tensor(state, (E, 3 * D + 4), torch.float64, "norm_state")
-        if enc is not None:
-            rc = self.lib.evac_policy_evaluate_deepsets(self._h, code, pol, K, T, _ptr(progress), _ptr(out), _ptr(state), obs_clip, eps,
-                                                        C.byref(enc), self._stream())
+        args = [K, T, _ptr(progress), _ptr(out), _ptr(state), obs_clip, eps]
+        if population is not None:
+            rc = self.lib.evac_policy_evaluate_population(self._h, int(population.num_learners), pol, C.byref(population.strides), code,
+                                                          int(bool(shared_episodes)), *args, self._stream())
+        elif enc is not None:
+            rc = self.lib.evac_policy_evaluate_deepsets(self._h, code, pol, *args, C.byref(enc), self._stream())
         else:
-            rc = self.lib.evac_policy_evaluate(self._h, code, pol, K, T, _ptr(progress), _ptr(out), _ptr(state), obs_clip, eps,
-                                               self._stream())
+            rc = self.lib.evac_policy_evaluate(self._h, code, pol, *args, self._stream())
         _lib.check(rc, self._h)
         return progress, out
 
@@ -710,7 +725,7 @@ class BatchedEvacuationEnv:
         and pedestrian noise (the learners are compared on the same episodes); ``False``: its offset is further by ``s E_l``,
         the ids of ``policy_rollout_population``.  The networks alone: a scripted agent has no learners (``policy_evaluate``),
         and a population or net with a set encoder is a ``ValueError``."""
-        from .policy import MAX_PEDESTRIANS, PolicyBinder, refuse_deepsets
+        from .policy import refuse_deepsets
         refuse_deepsets(population, "policy_evaluate_population")
         for net in getattr(population, "nets", ()):
             refuse_deepsets(net, "policy_evaluate_population")
@@ -718,34 +733,8 @@ class BatchedEvacuationEnv:
             raise ValueError("policy_evaluate_population: a PolicyPopulation is expected (a scripted agent has no learners: "
                              "policy_evaluate runs it)")
         check_evaluate_args(population, n_episodes, max_steps, _norm)
-        if self.n_ped > MAX_PEDESTRIANS:
-            raise NotImplementedError(f"policy_evaluate_population runs one wave per env: rooms of at most {MAX_PEDESTRIANS} "
-                                      f"pedestrians (this env has {self.n_ped})")
-        S = int(population.num_learners)
-        if self.num_envs % S:
-            raise ValueError(f"policy_evaluate_population: {self.num_envs} envs are not {S} learners' equal shares")
-        K, T, E, D = int(n_episodes), int(max_steps), self.num_envs, self.obs_dim
-        binder = getattr(self, "_policy_binder", None)
-        if binder is None:
-            binder = self._policy_binder = PolicyBinder(D, self.device, self.n_ped)
-        pol = binder(population.nets[0])
-        code = _lib.AGENT_POLICY_MEAN if deterministic else _lib.AGENT_POLICY_SAMPLE
-        if progress is None:
-            progress = torch.zeros((E, 4), dtype=torch.int32, device=self.device)
-        else:
-            self._check_tensor(progress, (E, 4), torch.int32, "progress")
-        if out is None:
-            out = torch.zeros((K, E, STATS_WORDS), dtype=torch.float32, device=self.device)
-        else:
-            self._check_tensor(out, (K, E, STATS_WORDS), torch.float32, "out")
-        state, obs_clip, eps = (None, 0.0, 0.0) if _norm is None else _norm
-        if state is not None:
-            self._check_tensor(state, (E, 3 * D + 4), torch.float64, "norm_state")
-        rc = self.lib.evac_policy_evaluate_population(self._h, S, C.byref(pol), C.byref(population.strides), code,
-                                                      int(bool(shared_episodes)), K, T, _ptr(progress), _ptr(out), _ptr(state),
-                                                      obs_clip, eps, self._stream())
-        _lib.check(rc, self._h)
-        return progress, out
+        return self._policy_evaluate("policy_evaluate_population", population.nets[0], population, n_episodes, max_steps, progress, out,
+                                     deterministic, shared_episodes, _norm)
 
     def observe(self, out: Optional[torch.Tensor] = None):
         """Observation of the current state without stepping (env.py:98-104 through the wrappers)."""

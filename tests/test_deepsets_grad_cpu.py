@@ -94,7 +94,9 @@ def test_every_refusal_comes_before_a_device_is_touched(lib):
         setattr(add(f"NULL encoder.{f}").enc, f, None)
         setattr(add(f"NULL encoder_grads.{f}").enc_grads, f, None)
     add("hidden != 24").enc.hidden = 23
+    add("hidden 16").enc.hidden = 16
     add("set_elem_dim 0").enc.set_elem_dim = 0
+    add("set_elem_dim 5, which does not divide obs_dim", D=36, ed=5)
     add("set_elem_dim 7", D=42, ed=7)
     add("obs_dim no multiple of set_elem_dim", D=37, ed=3)
     add("fewer than 3 rows", D=12, ed=6)
