@@ -82,6 +82,11 @@ class EvacAdamState(C.Structure):
     _fields_ = [("header", C.c_void_p), ("exp_avg", EvacMlpPolicyGrads), ("exp_avg_sq", EvacMlpPolicyGrads)]
 
 
+class EvacDeepSetsAdamState(C.Structure):
+    """evac_deepsets_adam_state_t: evac_adam_state_t with the set encoder's moments after the 13 tensors'"""
+    _fields_ = EvacAdamState._fields_ + [("enc_exp_avg", EvacDeepSetsGrads), ("enc_exp_avg_sq", EvacDeepSetsGrads)]
+
+
 class EvacLearnerHyper(C.Structure):
     """evac_learner_hyper_t: one learner's float-valued hyperparameters (a host array [S] for the sweep entries)"""
     _fields_ = [(f, C.c_double) for f in ("learning_rate", "target_kl", "gamma", "gae_lambda")] + [
@@ -191,6 +196,19 @@ SIGNATURES = {
                                   C.POINTER(EvacRpoLossConfig), C.POINTER(EvacAdamConfig), C.POINTER(EvacAdamState), C.c_int64,
                                   _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, C.c_uint64, C.c_uint64, C.c_int32,
                                   C.c_double, _P, _P, _P]),
+    "evac_deepsets_adam_step": (C.c_int, [C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads), C.POINTER(EvacMlpPolicyGrads),
+                                          C.POINTER(EvacDeepSetsGrads), C.POINTER(EvacDeepSetsAdamState), C.POINTER(EvacAdamConfig),
+                                          C.c_int32, C.c_int32, _P, _P]),
+    "evac_deepsets_minibatch_step": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacDeepSets), C.POINTER(EvacRpoLossConfig), C.c_int64,
+                                               _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_uint64,
+                                               C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads), _P, _P, _P,
+                                               C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads),
+                                               C.POINTER(EvacDeepSetsAdamState), C.POINTER(EvacAdamConfig)]),
+    "evac_deepsets_update": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacDeepSets), C.POINTER(EvacMlpPolicyGrads),
+                                       C.POINTER(EvacDeepSetsGrads), C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads),
+                                       C.POINTER(EvacRpoLossConfig), C.POINTER(EvacAdamConfig), C.POINTER(EvacDeepSetsAdamState),
+                                       C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, C.c_uint64, C.c_uint64,
+                                       C.c_int32, C.c_double, _P, _P, _P]),
     "evac_rpo_population_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32]),
     "evac_rpo_update_population": (C.c_int, [C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacMlpPolicyGrads),
                                              C.POINTER(EvacMlpPolicyStrides), C.POINTER(EvacMlpPolicyStrides),

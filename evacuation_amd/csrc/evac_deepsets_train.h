@@ -16,6 +16,7 @@
 //   k_set_finish     dW_r = dY^T s and db_r = sum_m dY in tiles of 64 columns over segments of the minibatch; the last workgroup
 //                    of a tile (an INTEGER ticket) adds the segments in order.  One more workgroup adds the partials of the four
 //                    small tensors in workgroup order.  The last workgroup of all adds the slots' sums of squares to stats[7].
+// (templates over an optional stop gate: see above k_set_encode.)
 // Every sum has a fixed order, no floating-point atomics: the same bits on every run and stream.  f32 fmaf chains on the VALU
 // (no MFMA: contractions of M x 24 are far below where it pays).
 #pragma once
@@ -98,7 +99,17 @@ __device__ __forceinline__ float set_preact(const f4 w0, const f4 w1, const floa
     return v;
 }
 
-__global__ __launch_bounds__(kSetBlock) void k_set_encode(SetArgs a) {
+// The three kernels are templates over an optional trailing argument, as k_rpo_* of evac_train.h: k_set_*<> (SetArgs alone) are
+// evac_deepsets_minibatch_grad's and evac_deepsets_minibatch_step's; k_set_*<const AdamHeader*> are evac_deepsets_update's, which
+// return at once, touching nothing, when the header's stop flag is set (a gated k_set_encode then leaves k_set_finish's tickets
+// as they are: every later kernel of the call returns too).  The bodies stay inside the kernels: moved into __device__
+// functions (SetArgs by reference, by value, const or not) all three compiled to other instructions than as plain kernels, and
+// k_set_backward began to keep scalars in VGPR lanes; as written, k_set_*<> are instruction for instruction what they were.
+template <class... Gate>
+__global__ __launch_bounds__(kSetBlock) void k_set_encode(SetArgs a, Gate... gate) {
+    if constexpr (sizeof...(Gate) != 0) {
+        if (rpo_stopped(gate...)) return;
+    }
     constexpr int H = kSetTrainHidden;
     __shared__ f4 wa[H][2];
     __shared__ float wb[H][H];                  // [j][k] = W_b[k][j]
@@ -183,7 +194,11 @@ __global__ __launch_bounds__(kSetBlock) void k_set_encode(SetArgs a) {
     }
 }
 
-__global__ __launch_bounds__(kSetBlock) void k_set_backward(SetArgs a) {
+template <class... Gate>
+__global__ __launch_bounds__(kSetBlock) void k_set_backward(SetArgs a, Gate... gate) {
+    if constexpr (sizeof...(Gate) != 0) {
+        if (rpo_stopped(gate...)) return;
+    }
     constexpr int H = kSetTrainHidden, H1 = kTrainHidden;
     __shared__ f4 wa[H][2];
     __shared__ float wb[H][H];                  // [k][j] = W_b[k][j]
@@ -346,7 +361,11 @@ __device__ __forceinline__ float set_block_sum(float v, float* buf) {
     return r;
 }
 
-__global__ __launch_bounds__(kSetBlock) void k_set_finish(SetArgs a) {
+template <class... Gate>
+__global__ __launch_bounds__(kSetBlock) void k_set_finish(SetArgs a, Gate... gate) {
+    if constexpr (sizeof...(Gate) != 0) {
+        if (rpo_stopped(gate...)) return;
+    }
     constexpr int H = kSetTrainHidden;
     __shared__ float buf[kSetBlock];
     __shared__ float fin[8];

@@ -572,15 +572,61 @@ struct AdamArgs {
 // Every workgroup forms the scalars from the same inputs (the header is read-only until the last workgroup has its ticket);
 // one element per thread; every operation rounded on its own (the sequence of include/evac.h, bit for bit).  sqrt goes through
 // double: correctly rounded for a float argument, which the f32 intrinsic of this toolchain is not.
-__device__ __forceinline__ void adam_stage(const AdamArgs& a) {
-    AdamHeader* h = a.hdr;
-    const int64_t t0 = h->t;
-    const double P1 = (t0 == 0 ? 1.0 : h->P1) * a.beta1, P2 = (t0 == 0 ? 1.0 : h->P2) * a.beta2;
+// The three pieces are templates over the argument struct (AdamArgs here; SetAdamArgs of evac_deepsets_adam.h, 19 tensors), which
+// names its header, its scalars and its flags alike: k_adam_set shares them, adam_stage is their sequence as it always was.
+struct AdamScalars {
+    int64_t t0;
+    double P1, P2;                              // the header's products after this step
+    float c, al, q;                             // the clip coefficient, f32(-(lr / (1 - P1))), f32(sqrt(1 - P2))
+};
+template <class Args>
+__device__ __forceinline__ AdamScalars adam_scalars(const Args& a) {
+    const AdamHeader* h = a.hdr;
+    AdamScalars k;
+    k.t0 = h->t;
+    k.P1 = (k.t0 == 0 ? 1.0 : h->P1) * a.beta1;
+    k.P2 = (k.t0 == 0 ? 1.0 : h->P2) * a.beta2;
     const float s = *a.sumsq;
     const float x = a.max_norm / __fadd_rn((float)sqrt((double)s), 1e-6f);
-    const float c = x > 1.0f ? 1.0f : x;        // (a NaN stays a NaN, as torch.clamp keeps it)
-    const float al = (float)(-(a.lr / (1.0 - P1)));
-    const float q = (float)sqrt(1.0 - P2);
+    k.c = x > 1.0f ? 1.0f : x;                  // (a NaN stays a NaN, as torch.clamp keeps it)
+    k.al = (float)(-(a.lr / (1.0 - k.P1)));
+    k.q = (float)sqrt(1.0 - k.P2);
+    return k;
+}
+template <class Args>
+__device__ __forceinline__ void adam_element(const Args& a, const AdamScalars& k, float* pp, float* pg, float* pm, float* pv, int o) {
+    const float g0 = pg[o], m0 = pm[o], v0 = pv[o], p0 = pp[o];
+    const float g = __fmul_rn(g0, k.c);
+    const float m = __fadd_rn(m0, __fmul_rn(a.w, __fsub_rn(g, m0)));
+    const float v = __fadd_rn(__fmul_rn(v0, a.b2), __fmul_rn(__fmul_rn(a.u, g), g));
+    const float den = __fadd_rn((float)sqrt((double)v) / k.q, a.eps);
+    pg[o] = g;
+    pm[o] = m;
+    pv[o] = v;
+    pp[o] = __fadd_rn(p0, __fmul_rn(k.al, m) / den);
+}
+// the last workgroup to finish (an integer ticket) is the one writer of the header: everybody has read it by then
+template <class Args>
+__device__ __forceinline__ void adam_close(const Args& a, const AdamScalars& k) {
+    AdamHeader* h = a.hdr;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned ticket = __hip_atomic_fetch_add(&h->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (ticket == gridDim.x - 1u) {
+            h->t = k.t0 + 1;
+            h->P1 = k.P1;
+            h->P2 = k.P2;
+            h->steps_run += 1;
+            if (a.epoch_last) {                                               // rpo_agent.py:281-283
+                h->epochs_run += 1;
+                if (a.use_target_kl && (double)a.stats[5] > a.target_kl) h->stop = 1;
+            }
+            h->ticket = 0u;
+        }
+    }
+}
+__device__ __forceinline__ void adam_stage(const AdamArgs& a) {
+    const AdamScalars k = adam_scalars(a);
     const int e = (int)blockIdx.x * kAdamBlock + (int)threadIdx.x;
     if (e < a.end[kAdamTensors - 1]) {
         float *pp = a.p[0], *pg = a.g[0], *pm = a.m[0], *pv = a.v[0];
@@ -594,32 +640,8 @@ __device__ __forceinline__ void adam_stage(const AdamArgs& a) {
             pv = in ? a.v[i] : pv;
             base = in ? a.end[i - 1] : base;
         }
-        const int o = e - base;
-        const float g0 = pg[o], m0 = pm[o], v0 = pv[o], p0 = pp[o];
-        const float g = __fmul_rn(g0, c);
-        const float m = __fadd_rn(m0, __fmul_rn(a.w, __fsub_rn(g, m0)));
-        const float v = __fadd_rn(__fmul_rn(v0, a.b2), __fmul_rn(__fmul_rn(a.u, g), g));
-        const float den = __fadd_rn((float)sqrt((double)v) / q, a.eps);
-        pg[o] = g;
-        pm[o] = m;
-        pv[o] = v;
-        pp[o] = __fadd_rn(p0, __fmul_rn(al, m) / den);
+        adam_element(a, k, pp, pg, pm, pv, e - base);
     }
-    // the last workgroup to finish (an integer ticket) is the one writer of the header: everybody has read it by then
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned ticket = __hip_atomic_fetch_add(&h->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (ticket == gridDim.x - 1u) {
-            h->t = t0 + 1;
-            h->P1 = P1;
-            h->P2 = P2;
-            h->steps_run += 1;
-            if (a.epoch_last) {                                               // rpo_agent.py:281-283
-                h->epochs_run += 1;
-                if (a.use_target_kl && (double)a.stats[5] > a.target_kl) h->stop = 1;
-            }
-            h->ticket = 0u;
-        }
-    }
+    adam_close(a, k);
 }
 }  // namespace evac

@@ -118,7 +118,10 @@ def all_tensors(net) -> tuple:
 
 
 def refuse_deepsets(net, what: str) -> None:
-    """``ValueError`` where only the linear network can go: the gradient and optimiser kernels are the linear network's."""
+    """``ValueError`` where only the linear network can go: the linear entries (``rpo_minibatch_grad`` .. ``rpo_update``),
+    populations, sweeps, and ``RPOTrainer(optimizer="device")`` with the gradient left at its default, which for such a network
+    is autograd's.  (Its own device entries are ``trainer.deepsets_minibatch_grad`` / ``deepsets_minibatch_step`` /
+    ``deepsets_update`` and ``DeviceAdam``: ``RPOTrainer(grad_fn=deepsets_kernel_grad, optimizer="device")``.)"""
     if net is not None and is_deepsets(net):
         raise ValueError(f"{what}: the network has a set encoder (`deep_sets`); the gradient and optimiser kernels are the linear "
                          "network's -- train it with RPOTrainer(optimizer=\"torch\"), whose gradient is autograd's")

@@ -218,7 +218,8 @@ def _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, sta
                     deepsets: bool = False) -> torch.Tensor:
     """``evac_rpo_minibatch_grad``, or with ``opt`` ``evac_rpo_minibatch_step``: the same arguments and the optimiser's three;
     or with ``deepsets`` ``evac_deepsets_minibatch_grad``: the same arguments, the encoder after the policy and its gradients
-    after the policy's, and a workspace of its own size."""
+    after the policy's, and a workspace of its own size -- and with ``opt`` ``evac_deepsets_minibatch_step``: the optimiser's
+    three, the encoder's parameters after the policy's."""
     B, D, dev, st, pol, grads, b_args = _batch_args(net, batch, deepsets)
     if deepsets:
         enc, enc_grads = st.binder.encoder(net), ensure_encoder_grads(net)
@@ -230,7 +231,13 @@ def _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, sta
     args = [C.byref(pol), C.byref(lc), *b_args, M, _ptr(mb_inds), _ptr(rpo_noise), _u64(seed), _u64(draw_counter), C.byref(grads),
             _ptr(stats), _ptr(ws), _stream(dev)]
     if deepsets:
-        rc = _lib.load().evac_deepsets_minibatch_grad(args[0], C.byref(enc), *args[1:-3], C.byref(enc_grads), *args[-3:])
+        args = [args[0], C.byref(enc), *args[1:-3], C.byref(enc_grads), *args[-3:]]
+        if opt is None:
+            rc = _lib.load().evac_deepsets_minibatch_grad(*args)
+        else:
+            oc = opt.config()
+            rc = _lib.load().evac_deepsets_minibatch_step(*args, C.byref(opt.params_struct()), C.byref(opt.encoder_params_struct()),
+                                                          C.byref(opt.state_struct()), C.byref(oc))
     elif opt is None:
         rc = _lib.load().evac_rpo_minibatch_grad(*args)
     else:
@@ -276,22 +283,29 @@ def decode_header(header: torch.Tensor) -> dict:
 
 class DeviceAdam:
     """``clip_grad_norm_(max_grad_norm)`` and ``torch.optim.Adam(lr, betas, eps)`` (no weight decay, no amsgrad) for the 13
-    tensors of ``net`` in one launch (``evac_adam_step``; the arithmetic is specified in include/evac.h).  The step count and
-    the bias corrections' running products live on the device, so a captured step counts when it is replayed.
-    ``param_groups[0]`` is read at every call: ``opt.param_groups[0]["lr"] = lrnow`` works as with torch."""
+    tensors of ``net`` in one launch (``evac_adam_step``; the arithmetic is specified in include/evac.h) -- or, for a network
+    with a set encoder, for all 19 in ``all_tensors`` order (``evac_deepsets_adam_step``: one launch, one clip coefficient, one
+    step count).  The step count and the bias corrections' running products live on the device, so a captured step counts when
+    it is replayed.  ``param_groups[0]`` is read at every call: ``opt.param_groups[0]["lr"] = lrnow`` works as with torch."""
 
     def __init__(self, net, lr: float = 3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm: float = 0.5,
                  *, storage=None):
-        """``storage`` = (header, exp_avg, exp_avg_sq): the state lives in the caller's tensors (``PopulationAdam``'s rows)."""
+        """``storage`` = (header, exp_avg, exp_avg_sq): the state lives in the caller's tensors (``PopulationAdam``'s rows: 13
+        tensors, so a ``ValueError`` for a network with a set encoder)."""
+        self.deepsets = is_deepsets(net)
+        if self.deepsets and storage is not None:
+            raise ValueError("DeviceAdam: `storage` holds the 13 tensors of a population's row; a network with a set encoder "
+                             "(`deep_sets`) has 19")
         group = {"lr": float(lr), "betas": (float(betas[0]), float(betas[1])), "eps": float(eps), "max_grad_norm": float(max_grad_norm)}
         self._check_group(group)
         self.net = net
-        self.params = list(mlp_tensors(net))
+        self.params = list(all_tensors(net))        # (13, or 19 with a set encoder)
         self.device = self.params[0].device
         for p in self.params:
             if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous():
                 raise ValueError("DeviceAdam: the parameters must be contiguous float32 device tensors")
         self.obs_dim = int(self.params[0].shape[1])
+        self.set_elem_dim = int(self.params[13].shape[1]) if self.deepsets else None
         self.param_groups = [group]
         if storage is None:
             self.header = torch.zeros(8, dtype=torch.int64, device=self.device)
@@ -299,9 +313,13 @@ class DeviceAdam:
             self.exp_avg_sq = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
         else:
             self.header, self.exp_avg, self.exp_avg_sq = storage[0], list(storage[1]), list(storage[2])
-        self._state = _lib.EvacAdamState(self.header.data_ptr(), _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in self.exp_avg)),
-                                         _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in self.exp_avg_sq)))
-        self._params = [None, None]
+        self._state = _lib.EvacAdamState(self.header.data_ptr(), _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in self.exp_avg[:13])),
+                                         _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in self.exp_avg_sq[:13])))
+        if self.deepsets:
+            self._state = _lib.EvacDeepSetsAdamState(self._state.header, self._state.exp_avg, self._state.exp_avg_sq,
+                                                     _lib.EvacDeepSetsGrads(*(t.data_ptr() for t in self.exp_avg[13:])),
+                                                     _lib.EvacDeepSetsGrads(*(t.data_ptr() for t in self.exp_avg_sq[13:])))
+        self._params, self._encoder_params = [None, None], [None, None]
         ensure_grads(net)
 
     @staticmethod
@@ -321,9 +339,14 @@ class DeviceAdam:
         return _lib.EvacAdamConfig(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["max_grad_norm"]))
 
     def params_struct(self) -> "_lib.EvacMlpPolicyGrads":
-        return _tensor_struct(self._params, self.params)
+        return _tensor_struct(self._params, self.params[:13])
 
-    def state_struct(self) -> "_lib.EvacAdamState":
+    def encoder_params_struct(self) -> "_lib.EvacDeepSetsGrads":
+        """The set encoder's six parameter tensors (a network with a set encoder only)."""
+        return _tensor_struct(self._encoder_params, self.params[13:], _lib.EvacDeepSetsGrads)
+
+    def state_struct(self):
+        """``evac_adam_state_t``, or ``evac_deepsets_adam_state_t`` for a network with a set encoder."""
         return self._state
 
     def step(self, grad_sumsq: torch.Tensor) -> None:
@@ -333,8 +356,13 @@ class DeviceAdam:
             raise ValueError("DeviceAdam.step: grad_sumsq must be a float32 scalar on the parameters' device")
         grads = ensure_grads(self.net)
         cfg = self.config()
-        rc = _lib.load().evac_adam_step(C.byref(self.params_struct()), C.byref(grads), C.byref(self._state), C.byref(cfg), self.obs_dim,
-                                        _ptr(grad_sumsq), _stream(self.device))
+        if self.deepsets:
+            rc = _lib.load().evac_deepsets_adam_step(C.byref(self.params_struct()), C.byref(self.encoder_params_struct()), C.byref(grads),
+                                                     C.byref(ensure_encoder_grads(self.net)), C.byref(self._state), C.byref(cfg),
+                                                     self.obs_dim, self.set_elem_dim, _ptr(grad_sumsq), _stream(self.device))
+        else:
+            rc = _lib.load().evac_adam_step(C.byref(self.params_struct()), C.byref(grads), C.byref(self._state), C.byref(cfg),
+                                            self.obs_dim, _ptr(grad_sumsq), _stream(self.device))
         _lib.check(rc)
 
     def zero_grad(self, set_to_none: bool = False) -> None:
@@ -348,7 +376,7 @@ class DeviceAdam:
         return int(self.header[0].item())
 
     def state_dict(self) -> dict:
-        """``torch.optim.Adam``'s format (``state[i]`` in ``mlp_tensors`` order), plus ``P1``, ``P2`` (the running products) and
+        """``torch.optim.Adam``'s format (``state[i]`` in ``all_tensors`` order: 13 entries, 19 with a set encoder), plus ``P1``, ``P2`` (the running products) and
         ``max_grad_norm`` in the param group: torch's ``load_state_dict`` takes the dict once those three keys are dropped."""
         h = self.read_header()
         g = self.param_groups[0]
@@ -361,7 +389,7 @@ class DeviceAdam:
     def load_state_dict(self, sd: dict) -> None:
         groups = sd["param_groups"]
         if len(groups) != 1 or len(groups[0]["params"]) != len(self.params):
-            raise ValueError("DeviceAdam.load_state_dict: expected one param group of 13 tensors")
+            raise ValueError(f"DeviceAdam.load_state_dict: expected one param group of {len(self.params)} tensors")
         sg = groups[0]
         if sg.get("weight_decay", 0) or sg.get("amsgrad", False):
             raise ValueError("DeviceAdam.load_state_dict: weight decay and amsgrad are not supported")
@@ -417,6 +445,38 @@ def update_steps(batch_size: int, minibatch_size: int, norm_adv: bool) -> list:
     return [min(M, B - s) for s in range(0, B, M) if min(M, B - s) >= least]
 
 
+def _update_call(net, batch, perms, cfg, opt, rpo_noise, seed, first_draw_counter, stats, minibatch_size, deepsets: bool = False):
+    """``evac_rpo_update``, or with ``deepsets`` ``evac_deepsets_update``: the same arguments with the encoder after the policy,
+    its parameters after the policy's and its gradients after the policy's, and a workspace of its own size."""
+    _check_opt(opt, net)
+    B, D, dev, st, pol, grads, b_args = _batch_args(net, batch, deepsets)
+    if not isinstance(perms, torch.Tensor) or perms.dtype != torch.int64 or perms.device != dev or not perms.is_contiguous() or \
+            perms.dim() != 2 or perms.shape[1] != B or perms.shape[0] < 1:
+        raise ValueError(f"perms: expected a contiguous int64 device tensor of shape [epochs, {B}]")
+    M = int(cfg.minibatch_size if minibatch_size is None else minibatch_size)
+    norm_adv = bool(getattr(cfg, "norm_adv", True))
+    if M < (2 if norm_adv else 1):
+        raise ValueError(f"{'deepsets' if deepsets else 'rpo'}_update: minibatch_size = {M}")
+    M = min(M, B)
+    n_epochs = int(perms.shape[0])
+    steps = n_epochs * len(update_steps(B, M, norm_adv))
+    stats, ws = _call_buffers(st, D, M, dev, rpo_noise, stats, steps, sizer=f"evac_{'deepsets' if deepsets else 'rpo'}_workspace_bytes")
+    target_kl = getattr(cfg, "target_kl", None)
+    lc, oc = _loss_config(cfg), opt.config()
+    tail = [*b_args, M, n_epochs, _ptr(perms), _ptr(rpo_noise), _u64(seed), _u64(first_draw_counter), int(target_kl is not None),
+            float(target_kl or 0.0), _ptr(stats), _ptr(ws), _stream(dev)]
+    if deepsets:
+        enc, enc_grads = st.binder.encoder(net), ensure_encoder_grads(net)
+        rc = _lib.load().evac_deepsets_update(C.byref(pol), C.byref(enc), C.byref(opt.params_struct()), C.byref(opt.encoder_params_struct()),
+                                              C.byref(grads), C.byref(enc_grads), C.byref(lc), C.byref(oc), C.byref(opt.state_struct()),
+                                              *tail)
+    else:
+        rc = _lib.load().evac_rpo_update(C.byref(pol), C.byref(opt.params_struct()), C.byref(grads), C.byref(lc), C.byref(oc),
+                                         C.byref(opt.state_struct()), *tail)
+    _lib.check(rc)
+    return stats, opt.header
+
+
 def rpo_update(net, batch: Dict[str, torch.Tensor], perms: torch.Tensor, cfg, opt: DeviceAdam, *,
                rpo_noise: Optional[torch.Tensor] = None, seed: int = 0, first_draw_counter: int = 0,
                stats: Optional[torch.Tensor] = None, minibatch_size: Optional[int] = None):
@@ -425,27 +485,31 @@ def rpo_update(net, batch: Dict[str, torch.Tensor], perms: torch.Tensor, cfg, op
     (default ``cfg.minibatch_size``).  Step k of the call draws its perturbation at ``first_draw_counter + k`` or reads
     ``rpo_noise[k]`` ([steps, M, 2]).  With ``cfg.target_kl`` set, the early exit is taken on the device.  Returns
     (``stats`` [steps, 8], the optimiser's header: ``decode_header``); rows beyond ``steps_run`` keep what they held."""
+    return _update_call(net, batch, perms, cfg, opt, rpo_noise, seed, first_draw_counter, stats, minibatch_size)
+
+
+def deepsets_minibatch_step(net, batch: Dict[str, torch.Tensor], mb_inds: torch.Tensor, cfg, opt: DeviceAdam, *,
+                            rpo_noise: Optional[torch.Tensor] = None, seed: int = 0, draw_counter: int = 0,
+                            stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``rpo_minibatch_step`` for a network with a set encoder: ``deepsets_minibatch_grad`` with the same arguments, then
+    ``opt.step(stats[7])`` over all 19 tensors, in one host call (``evac_deepsets_minibatch_step``: one launch more than the
+    gradient).  ``.grad`` is left clipped; ``stats`` are those of the gradient at the parameters before the step.  No host
+    synchronisation; capturable (``lr`` and ``draw_counter`` are frozen by a capture, the step count is not)."""
+    if not is_deepsets(net):
+        raise ValueError("deepsets_minibatch_step: the network has no set encoder (`deep_sets`); its step is rpo_minibatch_step's")
     _check_opt(opt, net)
-    B, D, dev, st, pol, grads, b_args = _batch_args(net, batch)
-    if not isinstance(perms, torch.Tensor) or perms.dtype != torch.int64 or perms.device != dev or not perms.is_contiguous() or \
-            perms.dim() != 2 or perms.shape[1] != B or perms.shape[0] < 1:
-        raise ValueError(f"perms: expected a contiguous int64 device tensor of shape [epochs, {B}]")
-    M = int(cfg.minibatch_size if minibatch_size is None else minibatch_size)
-    norm_adv = bool(getattr(cfg, "norm_adv", True))
-    if M < (2 if norm_adv else 1):
-        raise ValueError(f"rpo_update: minibatch_size = {M}")
-    M = min(M, B)
-    n_epochs = int(perms.shape[0])
-    steps = n_epochs * len(update_steps(B, M, norm_adv))
-    stats, ws = _call_buffers(st, D, M, dev, rpo_noise, stats, steps)
-    target_kl = getattr(cfg, "target_kl", None)
-    lc, oc = _loss_config(cfg), opt.config()
-    rc = _lib.load().evac_rpo_update(C.byref(pol), C.byref(opt.params_struct()), C.byref(grads), C.byref(lc), C.byref(oc),
-                                     C.byref(opt.state_struct()), *b_args, M, n_epochs, _ptr(perms), _ptr(rpo_noise), _u64(seed),
-                                     _u64(first_draw_counter), int(target_kl is not None), float(target_kl or 0.0), _ptr(stats),
-                                     _ptr(ws), _stream(dev))
-    _lib.check(rc)
-    return stats, opt.header
+    return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, opt, deepsets=True)
+
+
+def deepsets_update(net, batch: Dict[str, torch.Tensor], perms: torch.Tensor, cfg, opt: DeviceAdam, *,
+                    rpo_noise: Optional[torch.Tensor] = None, seed: int = 0, first_draw_counter: int = 0,
+                    stats: Optional[torch.Tensor] = None, minibatch_size: Optional[int] = None):
+    """``rpo_update`` for a network with a set encoder (``evac_deepsets_update``): the same arguments, the same returns
+    (``stats`` [steps, 8], the optimiser's header), the ``target_kl`` exit taken on the device; bit for bit the host loop of
+    ``deepsets_minibatch_step``."""
+    if not is_deepsets(net):
+        raise ValueError("deepsets_update: the network has no set encoder (`deep_sets`); its update is rpo_update's")
+    return _update_call(net, batch, perms, cfg, opt, rpo_noise, seed, first_draw_counter, stats, minibatch_size, deepsets=True)
 
 
 def _kernel_grad(trainer: "RPOTrainer", batch, mb_inds, rpo_noise, draw_counter: int, stats: torch.Tensor) -> torch.Tensor:
@@ -458,6 +522,16 @@ def deepsets_kernel_grad(trainer: "RPOTrainer", batch, mb_inds, rpo_noise, draw_
     the device, torch's clip and Adam).  Opt-in: the default for such a network stays ``autograd_minibatch_grad``."""
     return deepsets_minibatch_grad(trainer.net, batch, mb_inds, trainer.cfg, rpo_noise=rpo_noise, seed=trainer.cfg.seed,
                                    draw_counter=draw_counter, stats=stats)
+
+
+# The gradient functions whose step and whole update exist as one host call (RPOTrainer with optimizer="device")
+_STEP_OF = ((_kernel_grad, rpo_minibatch_step), (deepsets_kernel_grad, deepsets_minibatch_step))
+_UPDATE_OF = ((_kernel_grad, rpo_update), (deepsets_kernel_grad, deepsets_update))
+
+
+def _one_call_form(grad_fn, table):
+    """The entry of ``table`` for ``grad_fn`` (compared by identity), or None."""
+    return next((form for fn, form in table if grad_fn is fn), None)
 
 
 def _draw_seed(seed: int, draw_counter: int) -> int:
@@ -526,8 +600,11 @@ class RPOTrainer:
 
     ``net``: the linear network, or one with the reference's set encoder (``policy.DeepSetsActorCritic``): its collection and
     evaluation run on the device too, its gradient is ``autograd_minibatch_grad`` (the default ``grad_fn`` then) or, with
-    ``grad_fn=deepsets_kernel_grad``, the device's (``evac_deepsets_minibatch_grad``), and its optimiser torch's --
-    ``optimizer="device"`` is a ``ValueError``: the optimiser kernel is the linear network's.
+    ``grad_fn=deepsets_kernel_grad``, the device's (``evac_deepsets_minibatch_grad``).  Its optimiser is torch's by default;
+    ``optimizer="device"`` takes an explicit ``grad_fn`` (``DeviceAdam`` over all 19 tensors: with ``deepsets_kernel_grad`` the
+    whole update is one ``deepsets_update``, or one ``deepsets_minibatch_step`` per minibatch with ``one_call=False``; any other
+    ``grad_fn`` is followed by ``self.optimizer.step(stats[7])``) and stays a ``ValueError`` with ``grad_fn`` left at its
+    default, which for such a network is autograd's.
 
     ``env``: a ``NormalizedVectorEnv`` (the trainer's wrapper chain) or a ``BatchedEvacuationEnv`` with ``cfg.num_envs`` envs.
     The permutation of every epoch is drawn on the device from a generator seeded with ``cfg.seed`` (the reference shuffles on
@@ -552,7 +629,7 @@ class RPOTrainer:
         if env.num_envs != cfg.num_envs:
             raise ValueError(f"RPOTrainer: the env has {env.num_envs} envs, cfg.num_envs = {cfg.num_envs}")
         self.env, self.net, self.cfg = env, net, cfg
-        if is_deepsets(net) and optimizer == "device":
+        if is_deepsets(net) and optimizer == "device" and grad_fn is None:     # (the default gradient of such a net is autograd's)
             refuse_deepsets(net, "RPOTrainer(optimizer=\"device\")")
         # (a set encoder: collection and evaluation on the device, the gradient of all 19 tensors by autograd)
         self.grad_fn = grad_fn or (autograd_minibatch_grad if is_deepsets(net) else _kernel_grad)
@@ -611,7 +688,7 @@ class RPOTrainer:
         ``target_kl``; ``perms`` None: every epoch draws its permutation as it starts.  Returns what the log needs, on the device:
         the last step's statistics and the mean ``clipfrac``."""
         cfg = self.cfg
-        one_step = self.optimizer_kind == "device" and self.grad_fn is _kernel_grad
+        one_step = _one_call_form(self.grad_fn, _STEP_OF) if self.optimizer_kind == "device" else None
         sizes = update_steps(cfg.batch_size, cfg.minibatch_size, cfg.norm_adv)
         clipfracs = []
         for e in range(cfg.update_epochs):
@@ -625,9 +702,9 @@ class RPOTrainer:
                 mb_inds = perm[start:start + m]
                 start += cfg.minibatch_size
                 noise = self.rpo_noise_fn(m) if self.rpo_noise_fn is not None else None
-                if one_step:
-                    stats = rpo_minibatch_step(self.net, batch, mb_inds, cfg, self.optimizer, rpo_noise=noise, seed=cfg.seed,
-                                               draw_counter=self.minibatch_steps, stats=self.stats)
+                if one_step is not None:
+                    stats = one_step(self.net, batch, mb_inds, cfg, self.optimizer, rpo_noise=noise, seed=cfg.seed,
+                                     draw_counter=self.minibatch_steps, stats=self.stats)
                 else:
                     stats = self.grad_fn(self, batch, mb_inds, noise, self.minibatch_steps, self.stats)
                     self.apply_gradient(stats)
@@ -638,7 +715,7 @@ class RPOTrainer:
         return [stats, torch.stack(clipfracs).mean().reshape(1)]
 
     def _epochs_one_call(self, batch, perms) -> list:
-        """The whole update as one ``rpo_update``.  Returns what the log needs, on the device: the optimiser's header (16 words)
+        """The whole update as one ``rpo_update`` (``deepsets_update`` for ``deepsets_kernel_grad``).  Returns what the log needs, on the device: the optimiser's header (16 words)
         and every step's statistics."""
         cfg = self.cfg
         sizes = update_steps(cfg.batch_size, cfg.minibatch_size, cfg.norm_adv)
@@ -651,8 +728,9 @@ class RPOTrainer:
                 noise[k, :m] = self.rpo_noise_fn(m)
         if self.stats_rows is None or self.stats_rows.shape[0] != steps:
             self.stats_rows = torch.zeros(steps, 8, dtype=torch.float32, device=self.device)
-        rows, header = rpo_update(self.net, batch, perms, cfg, self.optimizer, rpo_noise=noise, seed=cfg.seed,
-                                  first_draw_counter=self.minibatch_steps, stats=self.stats_rows)
+        update = _one_call_form(self.grad_fn, _UPDATE_OF)
+        rows, header = update(self.net, batch, perms, cfg, self.optimizer, rpo_noise=noise, seed=cfg.seed,
+                              first_draw_counter=self.minibatch_steps, stats=self.stats_rows)
         return [header.view(torch.float32), rows.reshape(-1)]
 
     def update(self) -> dict:
@@ -663,7 +741,7 @@ class RPOTrainer:
         storage = self.collect()
         batch = flatten_batch(storage, self.advantages, self.returns)
         device = self.optimizer_kind == "device"
-        one_call = device and self.one_call and self.grad_fn is _kernel_grad
+        one_call = device and self.one_call and _one_call_form(self.grad_fn, _UPDATE_OF) is not None
         perms = torch.stack([self._randperm() for _ in range(cfg.update_epochs)]) if device else None
         self.last_permutations = list(perms) if device else []
         sent = self._epochs_one_call(batch, perms) if one_call else self._epochs_by_minibatch(batch, perms)

@@ -15,7 +15,9 @@ minibatches in one host call (``evac_rpo_update``).  Prints the reference's ``SP
 rel + ohe Box observation: collection and evaluation on the device (``evac_policy_rollout_deepsets`` /
 ``evac_policy_evaluate_deepsets``), the gradient of its 19 tensors by torch autograd (``trainer.autograd_minibatch_grad``) or,
 with ``--gradient device``, by ``evac_deepsets_minibatch_grad`` (``trainer.deepsets_kernel_grad``: six launches), and torch's
-Adam.  Not with ``--optimizer device``, ``--seeds``, ``--sweep`` or ``--compare``: those kernels are the linear network's.
+Adam -- or, with ``--gradient device --optimizer device``, the library's clip + Adam over all 19 tensors, the whole update in one
+host call (``evac_deepsets_update``: seven launches per step).  Not with ``--seeds``, ``--sweep`` or ``--compare``, nor with
+``--optimizer device`` under the autograd gradient: those kernels are the linear network's.
 
 ``--eval-every K`` evaluates the leader every K updates (``RPOTrainer.evaluate``: whole episodes, the mean action, the observation
 statistics frozen) and prints the summary; ``--baseline`` prints the same line for the reference's scripted sweep baseline
@@ -251,9 +253,11 @@ def main():
     args = ap.parse_args()
     if args.gradient == "device" and args.network != "deep_sets":
         raise SystemExit("--gradient device goes with --network deep_sets (the linear network's gradient is the device's anyway)")
-    if args.network == "deep_sets" and (args.compare or args.seeds or args.sweep or args.optimizer == "device"):
+    if args.network == "deep_sets" and (args.compare or args.seeds or args.sweep or
+                                        (args.optimizer == "device" and args.gradient != "device")):
         raise SystemExit("--network deep_sets: the gradient and optimiser kernels (--optimizer device, --seeds, --sweep, --compare) are "
-                         "the linear network's; its gradient is autograd's or --gradient device")
+                         "the linear network's; its gradient is autograd's or --gradient device, and --optimizer device goes with "
+                         "--gradient device")
     if args.compare:
         return compare(args)
     seeds = [int(x) for x in args.seeds.split(",")] if args.seeds else None

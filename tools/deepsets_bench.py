@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Measure the deep-sets leader's collection phase (evac_policy_rollout_deepsets) against what it stands beside and what it
-replaces, and its minibatch gradient on the device (evac_deepsets_minibatch_grad) against autograd's.
+replaces, its minibatch gradient on the device (evac_deepsets_minibatch_grad) against autograd's, and one whole update's epochs
+with torch's optimiser against the device's (evac_deepsets_minibatch_step, evac_deepsets_update).
 
-    python tools/deepsets_bench.py --part a|b|c|c-eager|grad-autograd|grad-device [--envs 4096] [--steps 128] [--reps 7]
+    python tools/deepsets_bench.py --part a|b|c|c-eager|grad-autograd|grad-device|step-device|update-torch|update-step|update-one-call
+                                   [--envs 4096] [--steps 128] [--minibatch 16384] [--epochs 10] [--reps 7]
 
 N = 60, the rel + ohe Box observation (D = 372), the trainer's normalisation chain, E envs, T steps per call; hipEvent times of
 whole calls after two warm-up calls, median and range of ``--reps`` calls, one JSON line:
@@ -14,6 +16,13 @@ whole calls after two warm-up calls, median and range of ``--reps`` calls, one J
   grad-autograd  one minibatch gradient of ``DeepSetsActorCritic`` by ``trainer.autograd_minibatch_grad`` at the trainer's shape: a
            batch of E x T rows, a minibatch of ``--minibatch`` (16 384) of them from a permutation, injected noise
   grad-device    the same by ``trainer.deepsets_minibatch_grad`` (six launches)
+  step-device    the same followed by clip + Adam over the 19 tensors, one call (``trainer.deepsets_minibatch_step``: seven launches);
+           minus grad-device it is the Adam stage alone
+  update-torch   one whole update's epochs (``--epochs`` x B / minibatch steps over the E x T batch, the perturbation drawn on the
+           device): per minibatch ``deepsets_minibatch_grad``, the ``foreach`` clip and ``torch.optim.Adam.step()``, as
+           ``RPOTrainer(grad_fn=deepsets_kernel_grad)`` does; events around the whole loop after one warm-up update
+  update-step    the same with one ``deepsets_minibatch_step`` per minibatch (``DeviceAdam``)
+  update-one-call  the same as one ``deepsets_update``
 One part per process, so that a job script can give each its own time limit."""
 import argparse
 import json
@@ -41,12 +50,10 @@ def event_ms(fn):
     return a.elapsed_time(b)
 
 
-def grad_part(args):
-    """One minibatch gradient of all 19 tensors: whole calls between two events after two warm-up calls."""
-    from types import SimpleNamespace
-
+def make_batch(args):
+    """The network, the configuration and a random batch of E x T rows at the trainer's shape."""
     from evacuation_amd import trainer
-    E, T, M = args.envs, args.steps, args.minibatch
+    E, T = args.envs, args.steps
     D, B = (N_PED + 2) * 6, E * T
     torch.manual_seed(0)
     net = DeepSetsActorCritic(D, N_PED).to(DEV)
@@ -55,6 +62,64 @@ def grad_part(args):
     rnd = lambda *shape: torch.randn(*shape, device=DEV, generator=g)
     batch = {"b_obs": rnd(B, D).clamp(-5, 5), "b_actions": rnd(B, 2), "b_logprobs": -2.0 + 0.1 * rnd(B), "b_advantages": rnd(B),
              "b_returns": rnd(B), "b_values": rnd(B)}
+    return net, cfg, batch, g
+
+
+def update_part(args):
+    """One whole update's epochs, three ways: whole updates between two events after one warm-up update."""
+    from evacuation_amd import trainer
+    net, cfg, batch, g = make_batch(args)
+    B, M = args.envs * args.steps, args.minibatch
+    perms = torch.stack([torch.randperm(B, device=DEV, generator=g) for _ in range(args.epochs)]).contiguous()
+    sizes = trainer.update_steps(B, M, cfg.norm_adv)
+    steps = args.epochs * len(sizes)
+    params = list(trainer.all_tensors(net))
+    trainer.ensure_grads(net)
+    stats, rows = torch.zeros(8, device=DEV), torch.zeros(steps, 8, device=DEV)
+    if args.part == "update-torch":
+        opt = torch.optim.Adam(params, lr=cfg.learning_rate, eps=1e-5)
+
+        def step(inds, k):
+            trainer.deepsets_minibatch_grad(net, batch, inds, cfg, seed=1, draw_counter=k, stats=stats)
+            coef = torch.clamp(cfg.max_grad_norm / (stats[7].sqrt() + 1e-6), max=1.0)       # RPOTrainer.apply_gradient
+            torch._foreach_mul_([p.grad for p in params], coef)
+            opt.step()
+    else:
+        opt = trainer.DeviceAdam(net, lr=cfg.learning_rate, eps=1e-5, max_grad_norm=cfg.max_grad_norm)
+
+        def step(inds, k):
+            trainer.deepsets_minibatch_step(net, batch, inds, cfg, opt, seed=1, draw_counter=k, stats=stats)
+
+    def run():
+        if args.part == "update-one-call":
+            trainer.deepsets_update(net, batch, perms, cfg, opt, seed=1, first_draw_counter=0, stats=rows, minibatch_size=M)
+            return
+        k = 0
+        for e in range(args.epochs):
+            start = 0
+            for m in sizes:
+                step(perms[e, start:start + m], k)
+                start += M
+                k += 1
+    run()
+    torch.cuda.synchronize()
+    ms = [event_ms(run) for _ in range(max(3, args.reps))]
+    med = statistics.median(ms)
+    print(json.dumps({"part": args.part, "envs": args.envs, "steps": args.steps, "batch": B, "minibatch": M, "epochs": args.epochs,
+                      "minibatch_steps": steps, "ms_per_update_median": round(med, 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
+                      "us_per_minibatch_step": round(med / steps * 1e3, 2), "updates": len(ms),
+                      "finite": bool(all(torch.isfinite(p).all() for p in params))}))
+
+
+def grad_part(args):
+    """One minibatch gradient of all 19 tensors (step-device: and the optimiser's step): whole calls between two events after two
+    warm-up calls."""
+    from types import SimpleNamespace
+
+    from evacuation_amd import trainer
+    E, T, M = args.envs, args.steps, args.minibatch
+    D, B = (N_PED + 2) * 6, E * T
+    net, cfg, batch, g = make_batch(args)
     inds = torch.randperm(B, device=DEV, generator=g)[:M].contiguous()
     z = ((torch.rand(M, 2, device=DEV, generator=g) * 2 - 1) * cfg.rpo_alpha).contiguous()
     stats = torch.zeros(8, device=DEV)
@@ -63,6 +128,11 @@ def grad_part(args):
     if args.part == "grad-device":
         def run():
             trainer.deepsets_minibatch_grad(net, batch, inds, cfg, rpo_noise=z, stats=stats)
+    elif args.part == "step-device":
+        opt = trainer.DeviceAdam(net, lr=cfg.learning_rate, eps=1e-5, max_grad_norm=cfg.max_grad_norm)
+
+        def run():
+            trainer.deepsets_minibatch_step(net, batch, inds, cfg, opt, rpo_noise=z, stats=stats)
     else:
         def run():
             trainer.autograd_minibatch_grad(holder, batch, inds, z, 0, stats)
@@ -77,13 +147,17 @@ def grad_part(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", required=True, choices=["a", "b", "c", "c-eager", "grad-autograd", "grad-device"])
+    ap.add_argument("--part", required=True, choices=["a", "b", "c", "c-eager", "grad-autograd", "grad-device", "step-device", "update-torch",
+                                                     "update-step", "update-one-call"])
     ap.add_argument("--minibatch", type=int, default=16384)
+    ap.add_argument("--epochs", type=int, default=10, help="update-*: the epochs of one update")
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--reps", type=int, default=7)
     args = ap.parse_args()
-    if args.part.startswith("grad-"):
+    if args.part.startswith("update-"):
+        return update_part(args)
+    if args.part.startswith("grad-") or args.part == "step-device":
         return grad_part(args)
     E, T = args.envs, args.steps
     env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=N_PED), ea.EnvWrappersConfig(positions="rel", statuses="ohe", type="Box"),

@@ -12,7 +12,8 @@ symbol and section name are replaced by placeholders numbered in order of appear
 in its file, or whose LDS variable now belongs to another function, still compares equal, and nothing else does.
 
 Prints ``N of N identical`` per unit and in all, the names of kernels that only one side has, and a unified diff of every kernel
-that differs; exits 1 on any difference.  Pure text comparison: no instruction is looked for.
+that differs; exits 1 on any difference.  A kernel that one side has as ``k(Args)`` and the other as the template instantiation
+``k<>(Args)`` is named as renamed and compared like any other.  Pure text comparison: no instruction is looked for.
 """
 import argparse
 import concurrent.futures
@@ -117,6 +118,15 @@ def main():
     for u in chosen:
         ka, kb = asm[(u, 0)], asm[(u, 1)]
         names = demangle(sorted(set(ka) | set(kb)))
+        # a kernel that became a template whose plain instantiation is the old kernel (k<>(Args) for k(Args)) is the same kernel
+        # under another mangled name: B's is compared under A's name
+        plain = lambda n: re.sub(r"^void ", "", names[n]).replace("<>", "")
+        for nb in [n for n in kb if n not in ka]:
+            for na in [n for n in ka if n not in kb]:
+                if plain(na) == plain(nb) and names[na] != names[nb]:
+                    print(f"  renamed: {names[na]} -> {names[nb]}")
+                    kb[na] = kb.pop(nb)
+                    break
         both = [n for n in ka if n in kb]
         same = [n for n in both if ka[n] == kb[n]]
         total = len(set(ka) | set(kb))
