@@ -8,7 +8,8 @@ step ``DeviceAdam``, ``rpo_minibatch_step``, ``rpo_update``, and the deep-sets l
 ``deepsets_kernel_grad``: ``evacuation_amd.trainer``), and the evaluation of a fixed agent
 over whole episodes (``PolicyEvaluator``, ``PopulationEvaluator``, ``EvaluationResult``, the scripted baseline ``WacuumCleaner``), and S independent
 learners of one configuration in one set of launches (``PolicyPopulation``, ``PopulationAdam``, ``PopulationTrainer``,
-``rpo_update_population``: ``evacuation_amd.population``).  Importing the package does
+``rpo_update_population``: ``evacuation_amd.population``).  The reference's three networks live in ``evacuation_amd.policy``
+(``LinearActorCritic``, ``DeepSetsActorCritic``, ``TransformerActorCritic``): each collects and evaluates on the device.  Importing the package does
 not touch the GPU; constructing an env loads libevac.so and fails loudly without it."""
 from .config import EnvConfig, EnvWrappersConfig
 from .statuses import Status

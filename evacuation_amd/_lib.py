@@ -52,6 +52,18 @@ class EvacDeepSets(C.Structure):
         (f, C.c_void_p) for f in ("phi_w1", "phi_b1", "phi_w2", "phi_b2", "rho_w", "rho_b")]
 
 
+class EvacTransformerBlock(C.Structure):
+    """evac_transformer_block_t: one block's 16 tensors (torch layouts)"""
+    _fields_ = [(f, C.c_void_p) for f in ("wq", "bq", "wk", "bk", "wv", "bv", "dense_w", "dense_b", "ff1_w", "ff1_b", "ff2_w", "ff2_b",
+                                          "norm1_w", "norm1_b", "norm2_w", "norm2_b")]
+
+
+class EvacTransformer(C.Structure):
+    """evac_transformer_t: the attention encoder for evac_policy_rollout_transformer / evac_policy_evaluate_transformer"""
+    _fields_ = [(f, C.c_int32) for f in ("elem_dim", "num_blocks", "num_heads", "dim_feedforward", "use_resid")] + [
+        ("ln_eps", C.c_float), ("blocks", EvacTransformerBlock * 2)]
+
+
 class EvacDeepSetsGrads(C.Structure):
     """evac_deepsets_grads_t: where evac_deepsets_minibatch_grad writes the gradients of the encoder's six tensors"""
     _fields_ = [(f, C.c_void_p) for f, _ in EvacDeepSets._fields_[2:]]
@@ -179,6 +191,10 @@ SIGNATURES = {
                                                C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(EvacDeepSets), _P]),
     "evac_policy_evaluate_deepsets": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float,
                                                 C.c_float, C.POINTER(EvacDeepSets), _P]),
+    "evac_policy_rollout_transformer": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                  C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(EvacTransformer), _P]),
+    "evac_policy_evaluate_transformer": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float,
+                                                   C.c_float, C.POINTER(EvacTransformer), _P]),
     "evac_gae": (C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
     "evac_rpo_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
     "evac_rpo_minibatch_grad": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacRpoLossConfig), C.c_int64, _P, _P, _P, _P, _P, _P,

@@ -114,7 +114,8 @@ class PolicyEvaluator(_Evaluator):
 
     def evaluate(self, agent, n_episodes: int = 1, *, deterministic: bool = True, norm_state: Optional[torch.Tensor] = None,
                  obs_clip: float = 1.0, epsilon: float = 1e-8, max_steps_per_launch: int = 4096) -> EvaluationResult:
-        """``n_episodes`` whole episodes per env under ``agent`` (a network with RPOLinearNetwork's attribute names, or
+        """``n_episodes`` whole episodes per env under ``agent`` (a network with RPOLinearNetwork's attribute names -- with the
+        reference's set encoder ``deep_sets`` or attention encoder ``embedding`` in front, if it has one -- or
         ``"vacuum_cleaner"``).  ``norm_state``: the trainer's statistics ([rows, 3 D + 4] float64, any number of rows: row
         ``e mod rows`` serves env ``e`` -- the trainer's normaliser is per env and the evaluation batch need not have its
         size), applied frozen.  Launches of at most ``max_steps_per_launch`` steps until every env has finished; the one host
@@ -182,6 +183,8 @@ class PopulationEvaluator(_Evaluator):
         [rows_s, 3 D + 4]; row ``i mod rows`` of learner s serves its env i, applied frozen.  Launches of at most
         ``max_steps_per_launch`` steps until every env of every learner has finished; the one host read per launch is
         ``progress[:, 0].min()`` over all learners."""
+        from .policy import refuse_deepsets
+        refuse_deepsets(population, "PopulationEvaluator.evaluate")      # (a network where the population goes)
         env, S, E_l = self.env, self.num_learners, self.num_envs
         if int(getattr(population, "num_learners", -1)) != S:
             raise ValueError(f"evaluate: the population has {getattr(population, 'num_learners', None)} learners, the evaluator {S}")

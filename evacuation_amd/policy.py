@@ -7,7 +7,12 @@ reference's own network included -- can drive the device rollout; its parameters
 
 ``DeepSetsActorCritic`` is RPODeepSetsEmbedding (/root/reference/src/agents/networks/rpo_deep_sets_agent_network.py:25-90): the
 same actor-critic behind a set encoder ``deep_sets`` (``transform_phi``, ``transform_rho``) that reads the Box observation as
-``N + 2`` rows.  A module with those names routes to ``evac_policy_rollout_deepsets`` / ``evac_policy_evaluate_deepsets``."""
+``N + 2`` rows.  A module with those names routes to ``evac_policy_rollout_deepsets`` / ``evac_policy_evaluate_deepsets``.
+
+``TransformerActorCritic`` is RPOTransformerEmbedding (src/agents/networks/rpo_transformer_agent_network.py): the same
+actor-critic behind ``embedding``, a ``Sequential`` of attention blocks over the ``N + 2`` tokens of the Box observation.  A
+module with that attribute routes to ``evac_policy_rollout_transformer`` / ``evac_policy_evaluate_transformer``, which compute
+its EVAL-MODE function (dropout the identity): collection and training refuse a dropout probability other than 0."""
 from __future__ import annotations
 
 from typing import Optional
@@ -23,6 +28,11 @@ HIDDEN = 64           # the only hidden width the kernel takes (RPOLinearNetwork
 SET_HIDDEN = 24       # ... and the only width of the set encoder (RPODeepSetsEmbeddingConfig.dim_hidden default)
 SET_MAX_ELEM_DIM = 6  # positions + one-hot status
 MAX_PEDESTRIANS = 64  # one wave per env
+TF_HEADS = 3          # the only head count, feed-forward width and LayerNorm eps of the attention encoder the kernels take
+TF_FEEDFORWARD = 96   # (RPOTransformerEmbeddingConfig's defaults, nn.LayerNorm's default)
+TF_LN_EPS = 1e-5
+TF_MAX_BLOCKS = 2
+TF_MAX_PEDESTRIANS = 62   # one wave holds the N + 2 tokens
 
 
 def layer_init(layer: nn.Linear, std: float = float(np.sqrt(2)), bias_const: float = 0.0) -> nn.Linear:
@@ -93,13 +103,97 @@ class DeepSetsActorCritic(LinearActorCritic):
         return super().get_action_and_value(self.encode(x), action)
 
 
+class MultiHeadAttention(nn.Module):
+    """The reference's attention over x [batch, tokens, d_model]: ``Wq``, ``Wk``, ``Wv`` map a token to ``num_heads * d_model``
+    values, read as [heads, d_model] and permuted to [batch, d_model, tokens, heads] -- so the scores are taken per CHANNEL and
+    contracted over the heads, and ``dense`` reads the result flattened as channel * heads + head.  Restated as it is."""
+
+    def __init__(self, d_model: int, num_heads: int = TF_HEADS):
+        super().__init__()
+        self.d_model, self.num_heads, self.scale = int(d_model), int(num_heads), float(np.sqrt(d_model))
+        self.Wq = nn.Linear(self.d_model, self.d_model * self.num_heads)
+        self.Wk = nn.Linear(self.d_model, self.d_model * self.num_heads)
+        self.Wv = nn.Linear(self.d_model, self.d_model * self.num_heads)
+        self.dense = nn.Linear(self.d_model * self.num_heads, self.d_model)
+
+    def _by_channel(self, t):
+        return t.view(t.shape[0], -1, self.num_heads, self.d_model).permute(0, 3, 1, 2)      # [batch, d_model, tokens, heads]
+
+    def forward(self, x):
+        if x.dim() != 3:
+            raise ValueError(f"MultiHeadAttention: expected [batch, tokens, d_model], got {tuple(x.shape)}")
+        q, k, v = self._by_channel(self.Wq(x)), self._by_channel(self.Wk(x)), self._by_channel(self.Wv(x))
+        weights = torch.softmax(torch.matmul(q, k.transpose(-2, -1)) / self.scale, dim=-1)   # [batch, d_model, tokens, tokens]
+        out = torch.matmul(weights, v).transpose(1, 2).contiguous().flatten(-2, -1)           # [batch, tokens, d_model * heads]
+        return self.dense(out)
+
+
+class TransformerBlock(nn.Module):
+    """One block of the reference's encoder: attention, ``norm1``, the feed-forward ``ff`` (Linear, Dropout, ReLU, Linear),
+    ``norm2``; with ``use_resid`` each norm reads its input plus the sublayer's output, otherwise the output alone.  Takes the
+    observation flat [batch, tokens * d_model] or as tokens, and returns the shape it was given."""
+
+    def __init__(self, d_model: int, num_heads: int = TF_HEADS, d_ff: int = TF_FEEDFORWARD, dropout: float = 0.0, use_resid: bool = False):
+        super().__init__()
+        self.d_model, self.num_heads, self.use_resid = int(d_model), int(num_heads), bool(use_resid)
+        self.attention = MultiHeadAttention(self.d_model, self.num_heads)
+        self.ff = nn.Sequential(nn.Linear(self.d_model, int(d_ff)), nn.Dropout(dropout), nn.ReLU(), nn.Linear(int(d_ff), self.d_model))
+        self.norm1 = nn.LayerNorm(self.d_model)
+        self.norm2 = nn.LayerNorm(self.d_model)
+        self.dropout = nn.Dropout(dropout)
+
+    def forward(self, x):
+        shape = x.shape
+        if x.dim() == 2:
+            x = x.view(shape[0], -1, self.d_model)
+        a = self.dropout(self.attention(x))
+        x = self.norm1(x + a if self.use_resid else a)
+        f = self.dropout(self.ff(x))
+        x = self.norm2(x + f if self.use_resid else f)
+        return x.view(shape)
+
+
+class TransformerActorCritic(LinearActorCritic):
+    """RPOTransformerEmbedding without the env argument.  ``dropout`` defaults to 0 (the reference's 0.1 is drawn from torch's
+    generator in its collection and its update alike; the device computes the eval-mode function, so collection and training
+    take p = 0 only).  One encoder serves actor and critic; ``encode(x)`` is what they read."""
+
+    def __init__(self, obs_dim: int, number_of_pedestrians: int, num_blocks: int = 2, num_heads: int = TF_HEADS,
+                 dim_feedforward: int = TF_FEEDFORWARD, dropout: float = 0.0, use_resid: bool = False, hidden: int = HIDDEN,
+                 action_dim: int = 2):
+        super().__init__(obs_dim, hidden, action_dim)
+        tokens = int(number_of_pedestrians) + 2
+        if int(obs_dim) % tokens:
+            raise ValueError(f"TransformerActorCritic: an observation of {obs_dim} floats is not a whole number of floats for each of "
+                             f"the {tokens} tokens ({number_of_pedestrians} pedestrians, the leader, the exit): a Box observation is needed")
+        self.token_dim = int(obs_dim) // tokens
+        self.embedding = nn.Sequential(*[TransformerBlock(self.token_dim, num_heads, dim_feedforward, dropout, use_resid)
+                                         for _ in range(int(num_blocks))])
+
+    def encode(self, x):
+        return encode_observation(self, x)
+
+    def get_value(self, x):
+        return super().get_value(self.encode(x))
+
+    def get_action_and_value(self, x, action=None):
+        return super().get_action_and_value(self.encode(x), action)
+
+
 def is_deepsets(net) -> bool:
     return hasattr(net, "deep_sets")
 
 
+def is_transformer(net) -> bool:
+    return hasattr(net, "embedding")
+
+
 def encode_observation(net, x):
     """What ``actor_mean`` / ``critic`` of ``net`` read for the observations x [B, D]: x itself, or -- with a set encoder --
-    ``deep_sets`` of x as [B, D / set_elem_dim, set_elem_dim] (rpo_deep_sets_agent_network.py:76-90)."""
+    ``deep_sets`` of x as [B, D / set_elem_dim, set_elem_dim] (rpo_deep_sets_agent_network.py:76-90); with an attention encoder
+    ``embedding`` of x (its blocks take the flat observation)."""
+    if is_transformer(net):
+        return net.embedding(x)
     if not is_deepsets(net):
         return x
     ed = net.deep_sets.transform_phi[0].in_features
@@ -112,16 +206,61 @@ def deepsets_tensors(net) -> tuple:
     return (phi[0].weight, phi[0].bias, phi[2].weight, phi[2].bias, rho[0].weight, rho[0].bias)
 
 
+_BLOCK_TENSORS = ("attention.Wq.weight", "attention.Wq.bias", "attention.Wk.weight", "attention.Wk.bias", "attention.Wv.weight",
+                  "attention.Wv.bias", "attention.dense.weight", "attention.dense.bias", "ff[0].weight", "ff[0].bias", "ff[3].weight",
+                  "ff[3].bias", "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias")
+
+
+def _block_tensors(blk) -> tuple:
+    at = blk.attention
+    return (at.Wq.weight, at.Wq.bias, at.Wk.weight, at.Wk.bias, at.Wv.weight, at.Wv.bias, at.dense.weight, at.dense.bias,
+            blk.ff[0].weight, blk.ff[0].bias, blk.ff[3].weight, blk.ff[3].bias, blk.norm1.weight, blk.norm1.bias, blk.norm2.weight,
+            blk.norm2.bias)
+
+
+def transformer_tensors(net) -> tuple:
+    """The parameter tensors of the attention encoder of ``net``: 16 per block in ``evac_transformer_block_t`` order, block by
+    block."""
+    return tuple(t for blk in net.embedding for t in _block_tensors(blk))
+
+
 def all_tensors(net) -> tuple:
-    """Every parameter tensor the device reads: the actor-critic's 13, then the set encoder's 6 if ``net`` has one."""
+    """Every parameter tensor the device reads: the actor-critic's 13, then the set encoder's 6 or the attention encoder's 16 per
+    block if ``net`` has one."""
+    if is_transformer(net):
+        return mlp_tensors(net) + transformer_tensors(net)
     return mlp_tensors(net) + (deepsets_tensors(net) if is_deepsets(net) else ())
+
+
+def transformer_dropouts(net) -> list:
+    """The probabilities of every ``nn.Dropout`` inside ``embedding``."""
+    return [float(m.p) for m in net.embedding.modules() if isinstance(m, nn.Dropout)]
+
+
+def refuse_transformer(net, what: str) -> None:
+    """``ValueError`` where a network with an attention encoder cannot go: every gradient and optimiser kernel (the linear
+    network's and the set encoder's), ``DeviceAdam``, populations and sweeps.  It trains with ``RPOTrainer(optimizer="torch")``,
+    whose gradient for such a network is autograd's."""
+    if net is not None and is_transformer(net):
+        raise ValueError(f"{what}: the network has an attention encoder (`embedding`); the gradient and optimiser kernels do not know "
+                         "its tensors -- train it with RPOTrainer(optimizer=\"torch\"), whose gradient is autograd's")
+
+
+def refuse_dropout(net, what: str) -> None:
+    """``ValueError`` for an attention encoder with a dropout probability other than 0 where the device's eval-mode forward pass
+    would disagree with the module's own (collection against the autograd update)."""
+    if net is not None and is_transformer(net) and any(p != 0.0 for p in transformer_dropouts(net)):
+        raise ValueError(f"{what}: `embedding` has dropout p = {max(transformer_dropouts(net))}; the device computes the eval-mode "
+                         "function (no dropout masks), so collection and training take p = 0 only (evaluation takes any p)")
 
 
 def refuse_deepsets(net, what: str) -> None:
     """``ValueError`` where only the linear network can go: the linear entries (``rpo_minibatch_grad`` .. ``rpo_update``),
     populations, sweeps, and ``RPOTrainer(optimizer="device")`` with the gradient left at its default, which for such a network
     is autograd's.  (Its own device entries are ``trainer.deepsets_minibatch_grad`` / ``deepsets_minibatch_step`` /
-    ``deepsets_update`` and ``DeviceAdam``: ``RPOTrainer(grad_fn=deepsets_kernel_grad, optimizer="device")``.)"""
+    ``deepsets_update`` and ``DeviceAdam``: ``RPOTrainer(grad_fn=deepsets_kernel_grad, optimizer="device")``.)  A network with
+    an attention encoder (`embedding`) is refused in all the same places (``refuse_transformer``)."""
+    refuse_transformer(net, what)
     if net is not None and is_deepsets(net):
         raise ValueError(f"{what}: the network has a set encoder (`deep_sets`); the gradient and optimiser kernels are the linear "
                          "network's -- train it with RPOTrainer(optimizer=\"torch\"), whose gradient is autograd's")
@@ -194,6 +333,56 @@ def _check_encoder(net, obs_dim: int, device: torch.device, n_ped: Optional[int]
     return ed
 
 
+def _check_transformer(net, obs_dim: int, device: torch.device, n_ped: Optional[int] = None) -> tuple:
+    """The attention encoder of ``net`` against the observation and what the kernels take; returns (token width, blocks,
+    use_resid)."""
+    emb = net.embedding
+    if not isinstance(emb, (nn.Sequential, nn.ModuleList)) or len(emb) < 1:
+        raise ValueError("policy: `embedding` must be a Sequential of transformer blocks")
+    if len(emb) > TF_MAX_BLOCKS:
+        raise ValueError(f"policy: `embedding` has num_blocks {len(emb)}; the device kernels take 1 to {TF_MAX_BLOCKS}")
+    if n_ped is not None and n_ped > TF_MAX_PEDESTRIANS:
+        raise ValueError(f"policy: `embedding` over N = {n_ped} pedestrians: one wave holds the N + 2 tokens, so the device kernels take "
+                         f"N <= {TF_MAX_PEDESTRIANS}")
+    dm, resid = None, None
+    for b, blk in enumerate(emb):
+        where = f"embedding[{b}]"
+        try:
+            ts = _block_tensors(blk)
+            at, norms = blk.attention, (blk.norm1, blk.norm2)
+        except (AttributeError, IndexError, TypeError):
+            raise ValueError(f"policy: `{where}` must have the reference's `attention.Wq/Wk/Wv/dense`, `ff[0]`, `ff[3]`, `norm1`, "
+                             "`norm2`") from None
+        d = int(at.Wq.in_features)
+        heads = int(getattr(at, "num_heads", at.Wq.out_features // max(d, 1)))
+        if heads != TF_HEADS or at.Wq.out_features != TF_HEADS * d:
+            raise ValueError(f"policy: `{where}.attention` has num_heads {heads}; the device kernels take {TF_HEADS}")
+        if blk.ff[0].out_features != TF_FEEDFORWARD:
+            raise ValueError(f"policy: `{where}.ff` has dim_feedforward {blk.ff[0].out_features}; the device kernels take {TF_FEEDFORWARD}")
+        for name, nm in zip(("norm1", "norm2"), norms):
+            if not isinstance(nm, nn.LayerNorm) or not nm.elementwise_affine or nm.weight is None or nm.bias is None:
+                raise ValueError(f"policy: `{where}.{name}` must be an affine LayerNorm")
+            if np.float32(nm.eps) != np.float32(TF_LN_EPS):
+                raise ValueError(f"policy: `{where}.{name}` has eps {nm.eps}; the device kernels take {TF_LN_EPS}")
+        if dm is None:
+            dm, resid = d, bool(getattr(blk, "use_resid", False))
+        if d != dm or bool(getattr(blk, "use_resid", False)) != resid:
+            raise ValueError(f"policy: `{where}` has d_model {d}, use_resid {bool(getattr(blk, 'use_resid', False))}; "
+                             f"`embedding[0]` has {dm}, {resid}")
+        if d < 1 or d > SET_MAX_ELEM_DIM or obs_dim % d or (n_ped is not None and d * (n_ped + 2) != obs_dim):
+            rows = "" if n_ped is None else f" of {n_ped} + 2 tokens"
+            raise ValueError(f"policy: the observation's {obs_dim} floats are not a whole number of rows of `embedding`'s {d} floats per "
+                             f"token{rows} (a Box observation is needed)")
+        shapes = ((3 * d, d), (3 * d,)) * 3 + ((d, 3 * d), (d,), (TF_FEEDFORWARD, d), (TF_FEEDFORWARD,), (d, TF_FEEDFORWARD), (d,)) + ((d,),) * 4
+        for name, t, shape in zip(_BLOCK_TENSORS, ts, shapes):
+            if t is None or tuple(t.shape) != shape:
+                raise ValueError(f"policy: `{where}.{name}` of shape {None if t is None else tuple(t.shape)}, expected {shape}")
+            if t.dtype != torch.float32 or t.device != device or not t.is_contiguous():
+                raise ValueError(f"policy: `{where}.{name}` must be a contiguous float32 tensor on {device}, got {t.dtype} on {t.device}"
+                                 f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+    return dm, len(emb), resid
+
+
 class PolicyBinder:
     """``evac_mlp_policy_t`` of a network, validated once per distinct set of parameter tensors (keyed by the tensor objects and
     their addresses: parameters updated in place keep their entry; new tensors are checked again)."""
@@ -235,6 +424,27 @@ class PolicyBinder:
             return ent[0]
         ed = _check_encoder(net, self.obs_dim, self.device, self.n_ped)
         st = _lib.EvacDeepSets(ed, SET_HIDDEN, *[t.data_ptr() for t in ts])
+        if len(self._encoders) >= self._ENTRIES:
+            self._encoders.pop(next(iter(self._encoders)))
+        self._encoders[key] = (st, ts)
+        return st
+
+    def transformer(self, net) -> _lib.EvacTransformer:
+        """``evac_transformer_t`` of the attention encoder of ``net`` (``is_transformer``): cached and validated as the 13
+        tensors are (``use_resid`` is read at every call: it is no tensor)."""
+        try:
+            ts = transformer_tensors(net)
+        except (AttributeError, IndexError, TypeError):
+            _check_transformer(net, self.obs_dim, self.device, self.n_ped)
+            raise
+        key = tuple((id(t), t.data_ptr()) for t in ts) + (tuple(bool(getattr(b, "use_resid", False)) for b in net.embedding),)
+        ent = self._encoders.get(key)
+        if ent is not None:
+            return ent[0]
+        dm, blocks, resid = _check_transformer(net, self.obs_dim, self.device, self.n_ped)
+        st = _lib.EvacTransformer(dm, blocks, TF_HEADS, TF_FEEDFORWARD, int(resid), TF_LN_EPS)
+        for b in range(blocks):
+            st.blocks[b] = _lib.EvacTransformerBlock(*[t.data_ptr() for t in ts[16 * b:16 * b + 16]])
         if len(self._encoders) >= self._ENTRIES:
             self._encoders.pop(next(iter(self._encoders)))
         self._encoders[key] = (st, ts)

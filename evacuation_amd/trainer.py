@@ -17,7 +17,8 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from .policy import PolicyBinder, all_tensors, deepsets_tensors, encode_observation, is_deepsets, mlp_tensors, refuse_deepsets
+from .policy import (PolicyBinder, all_tensors, deepsets_tensors, encode_observation, is_deepsets, is_transformer, mlp_tensors,
+                     refuse_deepsets, refuse_dropout, refuse_transformer)
 from .vector_env import STATS_FIELDS, _ptr
 
 STAT_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "grad_sumsq")
@@ -263,6 +264,7 @@ def deepsets_minibatch_grad(net, batch: Dict[str, torch.Tensor], mb_inds: torch.
     -- the encoder forwards, the linear network's three gradient launches on the encoded observations, the encoder backwards.
     Same arguments, same 8 statistics (``stats[7]``: the sum of squares over the 19 tensors), deterministic, no host
     synchronisation, capturable.  The optimiser stays torch's (``RPOTrainer(grad_fn=deepsets_kernel_grad)``)."""
+    refuse_transformer(net, "deepsets_minibatch_grad")
     if not is_deepsets(net):
         raise ValueError("deepsets_minibatch_grad: the network has no set encoder (`deep_sets`); its gradient is rpo_minibatch_grad's")
     return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, None, deepsets=True)
@@ -292,6 +294,7 @@ class DeviceAdam:
                  *, storage=None):
         """``storage`` = (header, exp_avg, exp_avg_sq): the state lives in the caller's tensors (``PopulationAdam``'s rows: 13
         tensors, so a ``ValueError`` for a network with a set encoder)."""
+        refuse_transformer(net, "DeviceAdam")
         self.deepsets = is_deepsets(net)
         if self.deepsets and storage is not None:
             raise ValueError("DeviceAdam: `storage` holds the 13 tensors of a population's row; a network with a set encoder "
@@ -421,6 +424,7 @@ class DeviceAdam:
 
 
 def _check_opt(opt, net) -> None:
+    refuse_transformer(net, "the device optimiser step")      # (no DeviceAdam exists for such a network: say why, not "no DeviceAdam")
     if not isinstance(opt, DeviceAdam):
         raise TypeError(f"expected a DeviceAdam, got {type(opt).__name__}")
     if opt.net is not net:
@@ -495,6 +499,7 @@ def deepsets_minibatch_step(net, batch: Dict[str, torch.Tensor], mb_inds: torch.
     ``opt.step(stats[7])`` over all 19 tensors, in one host call (``evac_deepsets_minibatch_step``: one launch more than the
     gradient).  ``.grad`` is left clipped; ``stats`` are those of the gradient at the parameters before the step.  No host
     synchronisation; capturable (``lr`` and ``draw_counter`` are frozen by a capture, the step count is not)."""
+    refuse_transformer(net, "deepsets_minibatch_step")
     if not is_deepsets(net):
         raise ValueError("deepsets_minibatch_step: the network has no set encoder (`deep_sets`); its step is rpo_minibatch_step's")
     _check_opt(opt, net)
@@ -507,6 +512,7 @@ def deepsets_update(net, batch: Dict[str, torch.Tensor], perms: torch.Tensor, cf
     """``rpo_update`` for a network with a set encoder (``evac_deepsets_update``): the same arguments, the same returns
     (``stats`` [steps, 8], the optimiser's header), the ``target_kl`` exit taken on the device; bit for bit the host loop of
     ``deepsets_minibatch_step``."""
+    refuse_transformer(net, "deepsets_update")
     if not is_deepsets(net):
         raise ValueError("deepsets_update: the network has no set encoder (`deep_sets`); its update is rpo_update's")
     return _update_call(net, batch, perms, cfg, opt, rpo_noise, seed, first_draw_counter, stats, minibatch_size, deepsets=True)
@@ -541,7 +547,8 @@ def _draw_seed(seed: int, draw_counter: int) -> int:
 def autograd_minibatch_grad(trainer, batch, mb_inds, rpo_noise, draw_counter: int, stats: torch.Tensor) -> torch.Tensor:
     """A ``grad_fn`` of ``RPOTrainer`` for ANY network it takes: the reference's minibatch loss (rpo_agent.py:239-274 with
     get_action_and_value of rpo_linear_agent_network.py:48-61 / rpo_deep_sets_agent_network.py:83-90) through torch autograd on
-    the module itself -- the gradient of a network with a set encoder, whose 19 tensors the gradient kernels do not know.
+    the module itself -- the gradient of a network with a set encoder, whose 19 tensors the linear gradient kernels do not know,
+    and of one with an attention encoder (rpo_transformer_agent_network.py), whose 45 no kernel does.
     Writes the parameters' ``.grad`` (not accumulated) and the 8 statistics (``STAT_NAMES``; ``stats[7]`` the gradient's sum of
     squares, in double).  ``rpo_noise`` [M, 2]: the perturbation of the mean; None draws U(-rpo_alpha, rpo_alpha) from a torch
     generator seeded with (``cfg.seed``, ``draw_counter``).  ``trainer``: anything with ``net`` and ``cfg``."""
@@ -604,7 +611,10 @@ class RPOTrainer:
     ``optimizer="device"`` takes an explicit ``grad_fn`` (``DeviceAdam`` over all 19 tensors: with ``deepsets_kernel_grad`` the
     whole update is one ``deepsets_update``, or one ``deepsets_minibatch_step`` per minibatch with ``one_call=False``; any other
     ``grad_fn`` is followed by ``self.optimizer.step(stats[7])``) and stays a ``ValueError`` with ``grad_fn`` left at its
-    default, which for such a network is autograd's.
+    default, which for such a network is autograd's.  Or one with the reference's attention encoder
+    (``policy.TransformerActorCritic``): collection and evaluation on the device, the gradient of its 13 + 16 per block tensors
+    by ``autograd_minibatch_grad`` and torch's Adam; ``optimizer="device"`` and a dropout probability other than 0 (the device
+    collects with the eval-mode function) are ``ValueError``s.
 
     ``env``: a ``NormalizedVectorEnv`` (the trainer's wrapper chain) or a ``BatchedEvacuationEnv`` with ``cfg.num_envs`` envs.
     The permutation of every epoch is drawn on the device from a generator seeded with ``cfg.seed`` (the reference shuffles on
@@ -629,10 +639,13 @@ class RPOTrainer:
         if env.num_envs != cfg.num_envs:
             raise ValueError(f"RPOTrainer: the env has {env.num_envs} envs, cfg.num_envs = {cfg.num_envs}")
         self.env, self.net, self.cfg = env, net, cfg
+        if optimizer == "device":                                               # (no optimiser kernel knows an attention encoder's tensors)
+            refuse_transformer(net, "RPOTrainer(optimizer=\"device\")")
+        refuse_dropout(net, "RPOTrainer")                                       # (collection is the eval-mode function)
         if is_deepsets(net) and optimizer == "device" and grad_fn is None:     # (the default gradient of such a net is autograd's)
             refuse_deepsets(net, "RPOTrainer(optimizer=\"device\")")
-        # (a set encoder: collection and evaluation on the device, the gradient of all 19 tensors by autograd)
-        self.grad_fn = grad_fn or (autograd_minibatch_grad if is_deepsets(net) else _kernel_grad)
+        # (an encoder: collection and evaluation on the device, the gradient of all 19 / 13 + 16 per block tensors by autograd)
+        self.grad_fn = grad_fn or (autograd_minibatch_grad if is_deepsets(net) or is_transformer(net) else _kernel_grad)
         self.rpo_noise_fn = rpo_noise_fn
         self.params = list(all_tensors(net))
         self.device = self.params[0].device

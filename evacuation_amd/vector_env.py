@@ -586,7 +586,10 @@ class BatchedEvacuationEnv:
         ``NormalizedVectorEnv.policy_rollout`` runs the trainer's normalisation chain.  No host synchronisation: the call can
         be captured into a graph, and the kernel reads the parameters in place at every replay.  A ``net`` with the reference's
         set encoder (``deep_sets``: ``evacuation_amd.policy.DeepSetsActorCritic``, Box observations) runs the encoder inside the
-        same launch (``evac_policy_rollout_deepsets``); the storage is the same, ``obs`` the observation before the encoder."""
+        same launch (``evac_policy_rollout_deepsets``); the storage is the same, ``obs`` the observation before the encoder.
+        A ``net`` with the reference's attention encoder (``embedding``: ``evacuation_amd.policy.TransformerActorCritic``, Box
+        observations, at most 62 pedestrians) likewise (``evac_policy_rollout_transformer``): the device computes its eval-mode
+        function, so a dropout probability other than 0 is a ``ValueError``."""
         return self._policy_rollout(net, None, n_steps, next_obs, next_done, out, _norm)
 
     def policy_rollout_population(self, population, n_steps: int, next_obs: torch.Tensor, next_done: torch.Tensor,
@@ -610,7 +613,7 @@ class BatchedEvacuationEnv:
                                       f"(this env has {self.n_ped})")
 
     def _binder(self):
-        """The env's ``PolicyBinder`` (a network's tensors as ``evac_mlp_policy_t`` / ``evac_deepsets_t``), made at first use."""
+        """The env's ``PolicyBinder`` (a network's tensors as ``evac_mlp_policy_t`` / ``evac_deepsets_t`` / ``evac_transformer_t``), made at first use."""
         binder = getattr(self, "_policy_binder", None)
         if binder is None:
             from .policy import PolicyBinder
@@ -618,15 +621,20 @@ class BatchedEvacuationEnv:
         return binder
 
     def _policy_rollout(self, net, population, n_steps, next_obs, next_done, out, _norm, hypers=None):
-        from .policy import is_deepsets, refuse_deepsets
+        from .policy import is_deepsets, is_transformer, refuse_deepsets, refuse_dropout, refuse_transformer
+        if population is not None:
+            refuse_transformer(net, "policy_rollout_population")
+        refuse_dropout(net, "policy_rollout")
         self._one_wave("policy_rollout")
         T, E, D = int(n_steps), self.num_envs, self.obs_dim
         if T < 1:
             raise ValueError("policy_rollout: n_steps must be >= 1")
         binder = self._binder()
         pol = binder(net)
-        enc = None
-        if is_deepsets(net):                  # the set encoder in front of the actor-critic: evac_policy_rollout_deepsets
+        enc = tf = None
+        if is_transformer(net):               # the attention encoder in front of the actor-critic: evac_policy_rollout_transformer
+            tf = binder.transformer(net)
+        elif is_deepsets(net):                # the set encoder in front of the actor-critic: evac_policy_rollout_deepsets
             if population is not None:
                 refuse_deepsets(net, "policy_rollout_population")
             enc = binder.encoder(net)
@@ -644,7 +652,9 @@ class BatchedEvacuationEnv:
         args = [_ptr(next_obs), _ptr(next_done), _ptr(out["obs"]), _ptr(out["actions"]), _ptr(out["logprobs"]), _ptr(out["values"]),
                 _ptr(out["rewards"]), _ptr(out["dones"]), _ptr(out["next_value"]), _ptr(out["episode_stats"]), _ptr(state), gamma,
                 obs_clip, reward_clip, eps, self._stream()]
-        if enc is not None:
+        if tf is not None:
+            rc = self.lib.evac_policy_rollout_transformer(self._h, T, C.byref(pol), *args[:-1], C.byref(tf), args[-1])
+        elif enc is not None:
             rc = self.lib.evac_policy_rollout_deepsets(self._h, T, C.byref(pol), *args[:-1], C.byref(enc), args[-1])
         elif population is None:
             rc = self.lib.evac_policy_rollout(self._h, T, C.byref(pol), *args)
@@ -671,25 +681,28 @@ class BatchedEvacuationEnv:
         ``progress[e, 0] >= n_episodes`` does nothing.  Returns ``(progress, out)``; both are made (zeroed) when not given.
         ``_norm = (norm_state, obs_clip, epsilon)``: the trainer's observation statistics applied FROZEN (read only) -- see
         ``NormalizedVectorEnv.policy_evaluate``.  No host synchronisation; capturable; the weights are read when the kernel runs.
-        A network with a set encoder (``deep_sets``) goes to ``evac_policy_evaluate_deepsets``."""
+        A network with a set encoder (``deep_sets``) goes to ``evac_policy_evaluate_deepsets``, one with an attention encoder
+        (``embedding``) to ``evac_policy_evaluate_transformer`` (evaluation is eval mode: any dropout probability is taken)."""
         check_evaluate_args(agent, n_episodes, max_steps, _norm)
         return self._policy_evaluate("policy_evaluate", agent, None, n_episodes, max_steps, progress, out, deterministic, 0, _norm)
 
     def _policy_evaluate(self, what, agent, population, n_episodes, max_steps, progress, out, deterministic, shared_episodes, _norm):
         """What ``policy_evaluate`` and ``policy_evaluate_population`` share, after their own checks of the agent: the one-wave
         limit, the learners' shares, the agent's code and structs, ``progress`` / ``out`` / the frozen statistics made or checked, and the call."""
-        from .policy import is_deepsets
+        from .policy import is_deepsets, is_transformer
         self._one_wave(what)
         K, T, E, D = int(n_episodes), int(max_steps), self.num_envs, self.obs_dim
         if population is not None and E % int(population.num_learners):
             raise ValueError(f"{what}: {E} envs are not {int(population.num_learners)} learners' equal shares")
-        pol = enc = None
+        pol = enc = tf = None
         if isinstance(agent, str):
             code = EVALUATE_AGENTS[agent]
         else:
             binder = self._binder()
             code, pol = (_lib.AGENT_POLICY_MEAN if deterministic else _lib.AGENT_POLICY_SAMPLE), C.byref(binder(agent))
-            if is_deepsets(agent):
+            if is_transformer(agent):
+                tf = binder.transformer(agent)
+            elif is_deepsets(agent):
                 enc = binder.encoder(agent)
         if progress is None:
             progress = torch.zeros((E, 4), dtype=torch.int32, device=self.device)
@@ -706,6 +719,8 @@ class BatchedEvacuationEnv:
         if population is not None:
             rc = self.lib.evac_policy_evaluate_population(self._h, int(population.num_learners), pol, C.byref(population.strides), code,
                                                           int(bool(shared_episodes)), *args, self._stream())
+        elif tf is not None:
+            rc = self.lib.evac_policy_evaluate_transformer(self._h, code, pol, *args, C.byref(tf), self._stream())
         elif enc is not None:
             rc = self.lib.evac_policy_evaluate_deepsets(self._h, code, pol, *args, C.byref(enc), self._stream())
         else:
@@ -724,7 +739,7 @@ class BatchedEvacuationEnv:
         ``shared_episodes=True``: that env has this env's ``env_id_offset``, so env i of every learner sees the same reset draws
         and pedestrian noise (the learners are compared on the same episodes); ``False``: its offset is further by ``s E_l``,
         the ids of ``policy_rollout_population``.  The networks alone: a scripted agent has no learners (``policy_evaluate``),
-        and a population or net with a set encoder is a ``ValueError``."""
+        and a population or net with a set encoder or an attention encoder is a ``ValueError``."""
         from .policy import refuse_deepsets
         refuse_deepsets(population, "policy_evaluate_population")
         for net in getattr(population, "nets", ()):

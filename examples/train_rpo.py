@@ -7,7 +7,8 @@ RPO loss (``evac_rpo_minibatch_grad``: three launches) followed by torch's ``cli
 minibatches in one host call (``evac_rpo_update``).  Prints the reference's ``SPS`` line per update.
 
     python examples/train_rpo.py [--envs 4096] [--steps 128] [--updates 5] [--pedestrians 60] [--optimizer device]
-                                 [--network linear|deep_sets] [--gradient autograd|device]
+                                 [--network linear|deep_sets|transformer] [--gradient autograd|device]
+                                 [--blocks 2] [--use-resid]
                                  [--eval-every 1] [--eval-episodes 1] [--baseline] [--seeds 1,2,3]
                                  [--sweep learning_rate=1e-4,3e-4,1e-3 --sweep ent_coef=0,0.01]
 
@@ -18,6 +19,13 @@ with ``--gradient device``, by ``evac_deepsets_minibatch_grad`` (``trainer.deeps
 Adam -- or, with ``--gradient device --optimizer device``, the library's clip + Adam over all 19 tensors, the whole update in one
 host call (``evac_deepsets_update``: seven launches per step).  Not with ``--seeds``, ``--sweep`` or ``--compare``, nor with
 ``--optimizer device`` under the autograd gradient: those kernels are the linear network's.
+
+``--network transformer`` trains the reference's attention-encoder network (``policy.TransformerActorCritic``,
+RPOTransformerEmbedding; ``--blocks`` 1 or 2, ``--use-resid``) on the rel + ohe Box observation, at most 62 pedestrians:
+collection and evaluation on the device (``evac_policy_rollout_transformer`` / ``evac_policy_evaluate_transformer``, the
+eval-mode function: dropout 0), the gradient of its 13 + 16 per block tensors by torch autograd and torch's Adam.  Not with
+``--gradient device``, ``--optimizer device``, ``--seeds``, ``--sweep`` or ``--compare``: no gradient or optimiser kernel knows
+its tensors.
 
 ``--eval-every K`` evaluates the leader every K updates (``RPOTrainer.evaluate``: whole episodes, the mean action, the observation
 statistics frozen) and prints the summary; ``--baseline`` prints the same line for the reference's scripted sweep baseline
@@ -51,7 +59,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import evacuation_amd as ea  # noqa: E402
-from evacuation_amd.policy import DeepSetsActorCritic, LinearActorCritic, mlp_tensors  # noqa: E402
+from evacuation_amd.policy import DeepSetsActorCritic, LinearActorCritic, TransformerActorCritic, mlp_tensors  # noqa: E402
 from evacuation_amd.trainer import RPOTrainer, RPOTrainingConfig, deepsets_kernel_grad, flatten_batch  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -60,12 +68,16 @@ DEV = torch.device("cuda:0")
 def make_trainer(args, **hooks):
     cfg = RPOTrainingConfig(num_envs=args.envs, num_steps=args.steps, total_timesteps=args.envs * args.steps * max(args.updates, 1),
                             num_minibatches=args.minibatches, update_epochs=args.epochs, seed=1)
-    deep_sets = getattr(args, "network", "linear") == "deep_sets"
-    wrap = ea.EnvWrappersConfig(positions="rel", statuses="ohe", type="Box") if deep_sets else ea.EnvWrappersConfig(positions="grav", alpha=3)
+    network = getattr(args, "network", "linear")
+    deep_sets, box = network == "deep_sets", network in ("deep_sets", "transformer")
+    wrap = ea.EnvWrappersConfig(positions="rel", statuses="ohe", type="Box") if box else ea.EnvWrappersConfig(positions="grav", alpha=3)
     env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=args.pedestrians, is_new_exiting_reward=True), wrap,
                                       num_envs=args.envs, gamma=cfg.gamma, seed=1)
     torch.manual_seed(0)
-    net = (DeepSetsActorCritic(env.obs_dim, args.pedestrians) if deep_sets else LinearActorCritic(env.obs_dim)).to(DEV)
+    if network == "transformer":
+        net = TransformerActorCritic(env.obs_dim, args.pedestrians, num_blocks=args.blocks, use_resid=args.use_resid).to(DEV)
+    else:
+        net = (DeepSetsActorCritic(env.obs_dim, args.pedestrians) if deep_sets else LinearActorCritic(env.obs_dim)).to(DEV)
     if deep_sets and getattr(args, "gradient", "autograd") == "device":
         hooks.setdefault("grad_fn", deepsets_kernel_grad)
     return RPOTrainer(env, net, cfg, **hooks)
@@ -246,8 +258,11 @@ def main():
     ap.add_argument("--seeds", type=str, default=None, help="comma-separated seeds: one learner per seed, trained as a population")
     ap.add_argument("--sweep", action="append", default=None, metavar="FIELD=V1,V2,..",
                     help="per-learner values of a hyperparameter; repeat for a grid: the product trains as one population")
-    ap.add_argument("--network", choices=("linear", "deep_sets"), default="linear",
-                    help="the reference's linear network on the gravity observation, or its set-encoder network on the rel + ohe Box observation")
+    ap.add_argument("--network", choices=("linear", "deep_sets", "transformer"), default="linear",
+                    help="the reference's linear network on the gravity observation, or its set-encoder or attention-encoder network on the "
+                         "rel + ohe Box observation")
+    ap.add_argument("--blocks", type=int, default=2, help="with --network transformer: the encoder's blocks (1 or 2)")
+    ap.add_argument("--use-resid", action="store_true", help="with --network transformer: residual connections in the blocks")
     ap.add_argument("--gradient", choices=("autograd", "device"), default="autograd",
                     help="with --network deep_sets: the gradient of its 19 tensors by torch autograd or by evac_deepsets_minibatch_grad")
     args = ap.parse_args()
@@ -258,6 +273,9 @@ def main():
         raise SystemExit("--network deep_sets: the gradient and optimiser kernels (--optimizer device, --seeds, --sweep, --compare) are "
                          "the linear network's; its gradient is autograd's or --gradient device, and --optimizer device goes with "
                          "--gradient device")
+    if args.network == "transformer" and (args.compare or args.seeds or args.sweep or args.optimizer == "device" or args.gradient == "device"):
+        raise SystemExit("--network transformer: no gradient or optimiser kernel knows its tensors (--gradient device, --optimizer device, "
+                         "--seeds, --sweep, --compare); it trains with autograd's gradient and torch's Adam")
     if args.compare:
         return compare(args)
     seeds = [int(x) for x in args.seeds.split(",")] if args.seeds else None

@@ -535,6 +535,53 @@ int evac_policy_evaluate_deepsets(evac_handle_t h, int32_t agent, const evac_mlp
                                   const double* norm_state_or_null, float obs_clip, float epsilon,
                                   const evac_deepsets_t* encoder, void* stream);
 
+/* ---- The transformer leader: the reference's attention encoder in front of the actor-critic (rpo_transformer_agent_network.py) ----
+ * RPOTransformerEmbedding reads the Box observation x [D] as S = N + 2 tokens of elem_dim = D / S floats (6, 3 or 2) and runs
+ * num_blocks blocks [S][dm] -> [S][dm] (dm = elem_dim, H = num_heads = 3):
+ *   Q = x wq^T + bq, K, V likewise                       wq, wk, wv [H dm][dm], output index h dm + c
+ *   score[c][i][j] = sum_h Q[i][h dm + c] K[j][h dm + c] / sqrt(dm),  w = softmax_j(score)      per channel c, contracted over heads
+ *   o[i][c][h] = sum_j w[c][i][j] V[j][h dm + c],  a_i = dense_w . o[i] (flattened as c H + h) + dense_b      dense_w [dm][H dm]
+ *   u = LayerNorm1(use_resid ? x + a : a)                over the dm values of a token, biased variance, eps ln_eps, affine
+ *   f = ff2_w relu(ff1_w u + ff1_b) + ff2_b              ff1_w [96][dm], ff2_w [dm][96]
+ *   block output = LayerNorm2(use_resid ? u + f : f)
+ * with every dropout the identity (the module's eval-mode function), and actor_mean / critic of evac_mlp_policy_t read the last
+ * block's output flattened back to [D].  One encoder serves actor and critic; x is what goes into obs_out.  Every sum has a
+ * fixed order (evac_transformer.h): results do not depend on the batch, the launch or the run.  Tensors in torch layouts,
+ * float32, read in place when the kernel runs. */
+typedef struct evac_transformer_block {
+    const float *wq, *bq, *wk, *bk, *wv, *bv;
+    const float *dense_w, *dense_b;
+    const float *ff1_w, *ff1_b, *ff2_w, *ff2_b;
+    const float *norm1_w, *norm1_b, *norm2_w, *norm2_b;
+} evac_transformer_block_t;
+typedef struct evac_transformer {
+    int32_t elem_dim;          /* elem_dim x (N + 2) == evac_obs_dim(h): a Box observation */
+    int32_t num_blocks;        /* 1 or 2; blocks[num_blocks ..] are not read */
+    int32_t num_heads;         /* 3 (RPOTransformerEmbeddingConfig.num_heads, the only count taken) */
+    int32_t dim_feedforward;   /* 96 (likewise) */
+    int32_t use_resid;         /* 0 / 1 */
+    float ln_eps;              /* 1e-5f (nn.LayerNorm's default, the only value taken) */
+    evac_transformer_block_t blocks[2];
+} evac_transformer_t;
+/* evac_policy_rollout with the encoder run on x before every step's forward pass and before the bootstrap value: arguments,
+ * storage, env side (bit for bit) and refusals are evac_policy_rollout's.  Further EVAC_ERR_INVALID_ARGUMENT: a NULL encoder or
+ * tensor of a block in use, elem_dim outside 1..6 or elem_dim x (N + 2) != evac_obs_dim(h).  EVAC_ERR_UNSUPPORTED, with the
+ * field named by evac_last_error: num_heads != 3, dim_feedforward != 96, num_blocks outside 1..2, ln_eps != 1e-5f, N > 62 (one
+ * wave holds the N + 2 tokens), the gravity observation (no Box of tokens). */
+int evac_policy_rollout_transformer(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_t* policy,
+                                    float* next_obs, float* next_done,
+                                    float* obs_out, float* actions_out, float* logprob_out,
+                                    float* value_out, float* reward_out, float* done_out,
+                                    float* next_value_out, evac_episode_stats_t* final_stats_or_null,
+                                    double* norm_state_or_null, float gamma, float obs_clip, float reward_clip, float epsilon,
+                                    const evac_transformer_t* encoder, void* stream);
+/* evac_policy_evaluate for the policy agents with the encoder run before the actor.  Sample mode is
+ * evac_policy_rollout_transformer bit for bit.  Refusals as evac_policy_evaluate_deepsets and as above. */
+int evac_policy_evaluate_transformer(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy,
+                                     int32_t n_episodes, int32_t max_steps, int32_t* progress, evac_episode_stats_t* episodes_out,
+                                     const double* norm_state_or_null, float obs_clip, float epsilon,
+                                     const evac_transformer_t* encoder, void* stream);
+
 /* ---- The trainer's update: the other half of RPOAgent.learn() (rpo_agent.py:205-283) for the network above ----
  * No handle: buffers, sizes and a stream; arguments are validated on the host before anything touches a device, and errors
  * come back through the return code alone (evac_last_error keeps its meaning for handles).

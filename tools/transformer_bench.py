@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Measure the transformer leader's collection phase (evac_policy_rollout_transformer) against what it stands beside and what it
+replaces.
+
+    python tools/transformer_bench.py --part a|b|c|c-eager [--envs 4096] [--steps 128] [--blocks 2] [--use-resid] [--reps 7]
+
+N = 60, the rel + ohe Box observation (D = 372, 62 tokens of 6), the trainer's normalisation chain, E envs, T steps per call;
+hipEvent times of whole calls after two warm-up calls, median and range of ``--reps`` calls, one JSON line:
+  a        ``policy_rollout`` of the linear network (``LinearActorCritic``): one launch
+  b        ``policy_rollout`` of ``TransformerActorCritic``: one launch
+  c        what b replaces: per step the module's torch forward (``get_action_and_value``, written out) and ``step(out_*=)`` into the
+           trainer's storage, the T steps captured into a graph once and replayed (as examples/rollout_with_policy.py)
+  c-eager  the same loop launched step by step
+One part per process, so that a job script can give each its own time limit."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import evacuation_amd as ea  # noqa: E402
+from evacuation_amd.policy import LinearActorCritic, TransformerActorCritic  # noqa: E402
+
+DEV = torch.device("cuda:0")
+N_PED = 60
+LOG_SQRT_2PI = 0.9189385332046727
+
+
+def event_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--part", required=True, choices=["a", "b", "c", "c-eager"])
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=128)
+    ap.add_argument("--blocks", type=int, default=2)
+    ap.add_argument("--use-resid", action="store_true")
+    ap.add_argument("--reps", type=int, default=7)
+    args = ap.parse_args()
+    E, T = args.envs, args.steps
+    env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=N_PED), ea.EnvWrappersConfig(positions="rel", statuses="ohe", type="Box"),
+                                      num_envs=E, gamma=0.99, seed=1)
+    D = env.obs_dim
+    torch.manual_seed(0)
+    net = (LinearActorCritic(D) if args.part == "a" else
+           TransformerActorCritic(D, N_PED, num_blocks=args.blocks, use_resid=args.use_resid)).to(DEV)
+    first, _ = env.reset()
+    if args.part in ("a", "b"):
+        next_obs, next_done = first.clone(), torch.zeros(E, dtype=torch.float32, device=DEV)
+        with torch.no_grad():
+            out = env.policy_rollout(net, T, next_obs, next_done)
+
+        def run():
+            env.policy_rollout(net, T, next_obs, next_done, out=out)
+    else:
+        net.eval()
+        obs = torch.zeros((T + 1, E, D), device=DEV)
+        actions, logprobs = torch.zeros((T, E, 2), device=DEV), torch.zeros((T, E), device=DEV)
+        values, rewards = torch.zeros((T, E), device=DEV), torch.zeros((T, E), device=DEV)
+        terminated, truncated = torch.zeros((T, E), dtype=torch.uint8, device=DEV), torch.zeros((T, E), dtype=torch.uint8, device=DEV)
+        obs[0].copy_(first)
+
+        with torch.no_grad():
+            std = torch.exp(net.actor_logstd)
+
+        def loop():
+            with torch.no_grad():
+                for t in range(T):
+                    # get_action_and_value(obs[t]) written out (torch's Normal checks its arguments on the host, which a
+                    # capture does not allow): the encoder, both heads, the sample and its log-probability
+                    y = net.encode(obs[t])
+                    mean = net.actor_mean(y)
+                    torch.addcmul(mean, std, torch.randn_like(mean), out=actions[t])
+                    torch.sum(-((actions[t] - mean) ** 2) / (2 * std * std) - net.actor_logstd - LOG_SQRT_2PI, dim=1, out=logprobs[t])
+                    values[t].copy_(net.critic(y).view(-1))
+                    env.step(actions[t], out_obs=obs[t + 1], out_reward=rewards[t], out_terminated=terminated[t], out_truncated=truncated[t])
+                obs[0].copy_(obs[T])
+        loop()
+        torch.cuda.synchronize()
+        run = loop
+        if args.part == "c":
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.stream(side):
+                with torch.cuda.graph(g, stream=side):
+                    loop()
+            torch.cuda.current_stream().wait_stream(side)
+            run = g.replay
+    for _ in range(2):
+        run()
+    torch.cuda.synchronize()
+    ms = [event_ms(run) for _ in range(max(5, args.reps))]
+    med = statistics.median(ms)
+    print(json.dumps({"part": args.part, "envs": E, "steps": T, "obs_dim": D, "blocks": args.blocks, "use_resid": bool(args.use_resid),
+                      "ms_per_call_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
+                      "us_per_vector_step": round(med / T * 1e3, 3), "env_steps_per_s": round(E * T / (med * 1e-3), 1), "calls": len(ms)}))
+    env.close()
+
+
+if __name__ == "__main__":
+    main()
