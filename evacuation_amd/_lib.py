@@ -187,14 +187,11 @@ SIGNATURES = {
     "evac_policy_evaluate": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P]),
     "evac_policy_evaluate_population": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyStrides), C.c_int32,
                                                   C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P]),
-    "evac_policy_rollout_deepsets": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                               C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(EvacDeepSets), _P]),
-    "evac_policy_evaluate_deepsets": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float,
-                                                C.c_float, C.POINTER(EvacDeepSets), _P]),
-    "evac_policy_rollout_transformer": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                                  C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(EvacTransformer), _P]),
-    "evac_policy_evaluate_transformer": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float,
-                                                   C.c_float, C.POINTER(EvacTransformer), _P]),
+    # the encoder entries: evac_policy_rollout's / evac_policy_evaluate's arguments with the encoder's struct in front of the stream
+    **{f"evac_policy_{what}{suffix}": (C.c_int, front + [C.POINTER(struct), _P])
+       for suffix, struct in (("_deepsets", EvacDeepSets), ("_transformer", EvacTransformer))
+       for what, front in (("rollout", [_P, C.c_int32, C.POINTER(EvacMlpPolicy)] + [_P] * 11 + [C.c_float] * 4),
+                           ("evaluate", [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float]))},
     "evac_gae": (C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
     "evac_rpo_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
     "evac_rpo_minibatch_grad": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacRpoLossConfig), C.c_int64, _P, _P, _P, _P, _P, _P,

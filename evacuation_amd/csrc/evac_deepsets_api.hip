@@ -1,7 +1,7 @@
 // Host side of the deep-sets leader (include/evac.h: evac_policy_rollout_deepsets, evac_policy_evaluate_deepsets; kernels in
-// evac_deepsets.h): evac_policy_rollout's / evac_policy_evaluate's checks and launch with the encoder's six tensors beside the
-// actor-critic's thirteen.  The handle is reached through evac_handle_host.h.  Every refusal before the first HIP call, no device
-// allocation, no synchronisation: one kernel on the caller's stream, capturable.
+// evac_deepsets.h): the encoder's six tensors beside the actor-critic's thirteen.  The two entries' bodies -- the checks in their
+// order, the handle, the launch -- are evac_handle_host.h's encoder_rollout / encoder_evaluate, which evac_transformer_api.hip
+// shares; this unit holds what is the set encoder's own: its limits, its check, its kernels.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -23,21 +23,23 @@ static_assert(evac::kSetHidden == kSetEncoderHidden && evac::kSetMaxElemDim == k
 
 namespace {
 
-using evac_host::handle_fail;
-
-// The checks the two entries share: the thirteen tensors as evac_policy_rollout makes them (into `a`), then the encoder's.
-// The text that follows the entry's name, or empty.
-std::string check_networks(const evac::Params& p, const evac_mlp_policy_t* policy, const evac_deepsets_t* encoder, evac::PolicyArgs& a,
-                           evac::DeepSetsArgs& da) {
-    if (!policy) return ": policy is NULL";
-    if (!encoder) return ": encoder is NULL";
-    if (const std::string why = mlp_policy_check(*policy, p.obs_dim, a); !why.empty()) return why;
-    const evac_deepsets_t& S = *encoder;
-    // (the gravity observation's 6 floats are no whole number of rows for any N >= 5, and no set for the others)
-    const bool rows_fit = p.obs_pos != EVAC_POS_GRAV && (int64_t)S.set_elem_dim * (p.n_ped + 2) == (int64_t)p.obs_dim;
-    da = evac::DeepSetsArgs{S.phi_w1, S.phi_b1, S.phi_w2, S.phi_b2, S.rho_w, S.rho_b, (int)S.set_elem_dim};
-    return deepsets_check(S, p.obs_dim, p.n_ped, rows_fit);
-}
+// evac_handle_host.h's trait of an encoder.  `check` comes after the policy's thirteen tensors; every refusal of a set encoder
+// is EVAC_ERR_INVALID_ARGUMENT.
+struct DeepSetsEncoder {
+    using Struct = evac_deepsets_t;
+    using Args = evac::DeepSetsArgs;
+    static constexpr const char* kRollout = "evac_policy_rollout_deepsets";
+    static constexpr const char* kEvaluate = "evac_policy_evaluate_deepsets";
+    static int check(const evac::Params& p, const evac_deepsets_t& S, evac::DeepSetsArgs& da, std::string& why) {
+        // (the gravity observation's 6 floats are no whole number of rows for any N >= 5, and no set for the others)
+        const bool rows_fit = p.obs_pos != EVAC_POS_GRAV && (int64_t)S.set_elem_dim * (p.n_ped + 2) == (int64_t)p.obs_dim;
+        da = evac::DeepSetsArgs{S.phi_w1, S.phi_b1, S.phi_w2, S.phi_b2, S.rho_w, S.rho_b, (int)S.set_elem_dim};
+        why = deepsets_check(S, p.obs_dim, p.n_ped, rows_fit);
+        return why.empty() ? EVAC_OK : EVAC_ERR_INVALID_ARGUMENT;
+    }
+    static auto rollout_kernel(bool norm, bool def) { return EVAC_PICK_BOOL2(evac::k_policy_rollout_deepsets, norm, def); }
+    static auto evaluate_kernel(bool norm, bool def) { return EVAC_PICK_BOOL2(evac::k_policy_evaluate_deepsets, norm, def); }
+};
 
 }  // namespace
 
@@ -48,52 +50,17 @@ int evac_policy_rollout_deepsets(evac_handle_t h, int32_t n_steps, const evac_ml
                                  float* done_out, float* next_value_out, evac_episode_stats_t* final_stats, double* norm_state,
                                  float gamma, float obs_clip, float reward_clip, float epsilon, const evac_deepsets_t* encoder,
                                  void* stream) {
-    const std::string w = "evac_policy_rollout_deepsets";
-    evac_host::HandleView v;
-    if (const int rc = evac_host::handle_begin(h, w.c_str(), &v); rc != EVAC_OK) return rc;
-    std::string why = one_wave_check(v.p);
-    if (!why.empty()) return handle_fail(h, EVAC_ERR_UNSUPPORTED, w + why);
-    evac::PolicyArgs a = collect_outputs(next_obs, next_done, obs_out, actions_out, logprob_out, value_out, reward_out, done_out,
-                                         next_value_out, final_stats);
-    evac::DeepSetsArgs da{};
-    why = collect_check(n_steps, a, false, policy);    // (the first refusal in the entry's order of checks)
-    if (why.empty()) why = check_networks(v.p, policy, encoder, a, da);
-    if (why.empty()) why = collect_aligned(a);
-    if (!why.empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
-    if (const int st = evac_host::handle_settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
-    DeviceGuard g(v.device);
-    const evac::NormArgs na{norm_state, gamma, obs_clip, reward_clip, epsilon};
-    const bool norm = norm_state != nullptr, def = v.default_cfg;
-    const auto fn = EVAC_PICK_BOOL2(evac::k_policy_rollout_deepsets, norm, def);
-    hipLaunchKernelGGL(fn, dim3((unsigned)policy_wgs(v.p.n_envs)), dim3(evac::PolicyFamily::kBlock), 0, (hipStream_t)stream, v.p,
-                       (int)n_steps, a, na, da);
-    return evac_host::handle_check_launch(h, w.c_str());
+    return encoder_rollout<DeepSetsEncoder>(h, n_steps, policy,
+                                            collect_outputs(next_obs, next_done, obs_out, actions_out, logprob_out, value_out, reward_out,
+                                                            done_out, next_value_out, final_stats),
+                                            evac::NormArgs{norm_state, gamma, obs_clip, reward_clip, epsilon}, encoder, stream);
 }
 
 int evac_policy_evaluate_deepsets(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy, int32_t n_episodes, int32_t max_steps,
                                   int32_t* progress, evac_episode_stats_t* episodes_out, const double* norm_state, float obs_clip,
                                   float epsilon, const evac_deepsets_t* encoder, void* stream) {
-    const std::string w = "evac_policy_evaluate_deepsets";
-    evac_host::HandleView v;
-    if (const int rc = evac_host::handle_begin(h, w.c_str(), &v); rc != EVAC_OK) return rc;
-    if (agent == EVAC_AGENT_VACUUM_CLEANER)
-        return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the scripted agent has no network (use evac_policy_evaluate)");
-    if (agent != EVAC_AGENT_POLICY_MEAN && agent != EVAC_AGENT_POLICY_SAMPLE)
-        return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": unknown agent " + std::to_string(agent));
-    evac::EvalArgs ev{};
-    evac::PolicyArgs a{};
-    evac::DeepSetsArgs da{};
-    std::string why = evaluate_check(agent, n_episodes, max_steps, progress, episodes_out, norm_state, obs_clip, epsilon, ev);
-    if (why.empty()) why = check_networks(v.p, policy, encoder, a, da);
-    if (!why.empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
-    if (!(why = one_wave_check(v.p)).empty()) return handle_fail(h, EVAC_ERR_UNSUPPORTED, w + why);
-    if (const int st = evac_host::handle_settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
-    DeviceGuard g(v.device);
-    const bool norm = norm_state != nullptr, def = v.default_cfg;
-    const auto fn = EVAC_PICK_BOOL2(evac::k_policy_evaluate_deepsets, norm, def);
-    hipLaunchKernelGGL(fn, dim3((unsigned)policy_wgs(v.p.n_envs)), dim3(evac::PolicyFamily::kBlock), 0, (hipStream_t)stream, v.p, a, ev,
-                       da);
-    return evac_host::handle_check_launch(h, w.c_str());
+    return encoder_evaluate<DeepSetsEncoder>(h, agent, policy, n_episodes, max_steps, progress, episodes_out, norm_state, obs_clip, epsilon,
+                                             encoder, stream);
 }
 
 }  // extern "C"

@@ -1,9 +1,10 @@
 // What the entries that run a network on a handle's envs share (evac_api.hip: evac_policy_rollout*, evac_policy_evaluate*;
-// evac_deepsets_api.hip: their deep-sets forms).  The handle's struct stays evac_api.hip's own: the four handle_* functions are
-// defined there and are not exported from the library.  Below them, host-only and inline: what every collection entry and every
-// evaluation entry refuses, the one-wave limit, a population's shares of the envs, and the grid.  Each returns the text that
-// follows the entry's name in its message (empty: accepted), as mlp_policy_check does; the entry reports it through its own fail,
-// at its own place in its order of checks.
+// evac_deepsets_api.hip, evac_transformer_api.hip: their forms with an encoder).  The handle's struct stays evac_api.hip's own:
+// the four handle_* functions are defined there and are not exported from the library.  Below them, host-only and inline: what
+// every collection entry and every evaluation entry refuses, the one-wave limit, a population's shares of the envs, and the grid.
+// Each returns the text that follows the entry's name in its message (empty: accepted), as mlp_policy_check does; the entry
+// reports it through its own fail, at its own place in its order of checks.  Last, the whole bodies of the encoder entries as two
+// templates over the unit's encoder (encoder_rollout, encoder_evaluate): those entries differ in nothing else.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -55,7 +56,7 @@ inline evac::PolicyArgs collect_outputs(float* next_obs, float* next_done, float
     return a;
 }
 // What every collection entry refuses of its step count and buffers (`a`: collect_outputs), before it looks at the networks.
-// `policy_named`: the linear entries refuse a NULL policy with the same message, the deep-sets entry with its networks.
+// `policy_named`: the linear entries refuse a NULL policy with the same message, the encoder entries with their networks.
 inline std::string collect_check(int32_t n_steps, const evac::PolicyArgs& a, bool policy_named, const evac_mlp_policy_t* policy) {
     if (n_steps < 1) return ": n_steps must be >= 1";
     const bool buffers = a.next_obs && a.next_done && a.obs_out && a.actions_out && a.logprob_out && a.value_out && a.reward_out &&
@@ -94,6 +95,73 @@ inline std::string learner_shares(int n_envs, int32_t n_learners, const evac_mlp
     q.envs_per_learner = n_envs / n_learners;
     q.wgs = policy_wgs(q.envs_per_learner);
     return {};
+}
+
+// The entries of a network with an encoder in front of the actor-critic (evac_deepsets_api.hip, evac_transformer_api.hip), over
+// the unit's trait Enc:
+//   Struct, Args                     the encoder as include/evac.h has it and as the kernels take it
+//   kRollout, kEvaluate              the entries' names
+//   check(p, S, args, why)           the encoder against the handle, after the policy's own check: EVAC_OK and `args` filled, or
+//                                    the code with the text that follows the entry's name in `why`
+//   rollout_kernel(norm, def), evaluate_kernel(norm, def)      the instantiations of the unit's two kernel templates
+// What both entries refuse of the two networks, in this order: no policy, no encoder, the thirteen tensors (into `a`), Enc's own.
+template <class Enc>
+inline int encoder_networks_check(const evac::Params& p, const evac_mlp_policy_t* policy, const typename Enc::Struct* encoder,
+                                  evac::PolicyArgs& a, typename Enc::Args& ea, std::string& why) {
+    if (!policy) return why = ": policy is NULL", EVAC_ERR_INVALID_ARGUMENT;
+    if (!encoder) return why = ": encoder is NULL", EVAC_ERR_INVALID_ARGUMENT;
+    if (!(why = mlp_policy_check(*policy, p.obs_dim, a)).empty()) return EVAC_ERR_INVALID_ARGUMENT;
+    return Enc::check(p, *encoder, ea, why);
+}
+
+// evac_policy_rollout_<encoder> (`a`: collect_outputs).  Every refusal before the first HIP call; one kernel on `stream`.
+template <class Enc>
+inline int encoder_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_t* policy, evac::PolicyArgs a, const evac::NormArgs& na,
+                           const typename Enc::Struct* encoder, void* stream) {
+    using evac_host::handle_fail;
+    const std::string w = Enc::kRollout;
+    evac_host::HandleView v;
+    if (const int rc = evac_host::handle_begin(h, w.c_str(), &v); rc != EVAC_OK) return rc;
+    std::string why = one_wave_check(v.p);
+    if (!why.empty()) return handle_fail(h, EVAC_ERR_UNSUPPORTED, w + why);
+    typename Enc::Args ea{};
+    why = collect_check(n_steps, a, false, policy);    // (the first refusal in the entry's order of checks)
+    if (!why.empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
+    if (const int rc = encoder_networks_check<Enc>(v.p, policy, encoder, a, ea, why); rc != EVAC_OK) return handle_fail(h, rc, w + why);
+    why = collect_aligned(a);
+    if (!why.empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
+    if (const int st = evac_host::handle_settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
+    DeviceGuard g(v.device);
+    hipLaunchKernelGGL(Enc::rollout_kernel(na.state != nullptr, v.default_cfg), dim3((unsigned)policy_wgs(v.p.n_envs)),
+                       dim3(evac::PolicyFamily::kBlock), 0, (hipStream_t)stream, v.p, (int)n_steps, a, na, ea);
+    return evac_host::handle_check_launch(h, w.c_str());
+}
+
+// evac_policy_evaluate_<encoder>: the agent's code first, the one-wave limit last.
+template <class Enc>
+inline int encoder_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy, int32_t n_episodes, int32_t max_steps,
+                            int32_t* progress, evac_episode_stats_t* episodes_out, const double* norm_state, float obs_clip, float epsilon,
+                            const typename Enc::Struct* encoder, void* stream) {
+    using evac_host::handle_fail;
+    const std::string w = Enc::kEvaluate;
+    evac_host::HandleView v;
+    if (const int rc = evac_host::handle_begin(h, w.c_str(), &v); rc != EVAC_OK) return rc;
+    if (agent == EVAC_AGENT_VACUUM_CLEANER)
+        return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the scripted agent has no network (use evac_policy_evaluate)");
+    if (agent != EVAC_AGENT_POLICY_MEAN && agent != EVAC_AGENT_POLICY_SAMPLE)
+        return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": unknown agent " + std::to_string(agent));
+    evac::EvalArgs ev{};
+    evac::PolicyArgs a{};
+    typename Enc::Args ea{};
+    std::string why = evaluate_check(agent, n_episodes, max_steps, progress, episodes_out, norm_state, obs_clip, epsilon, ev);
+    if (!why.empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
+    if (const int rc = encoder_networks_check<Enc>(v.p, policy, encoder, a, ea, why); rc != EVAC_OK) return handle_fail(h, rc, w + why);
+    if (!(why = one_wave_check(v.p)).empty()) return handle_fail(h, EVAC_ERR_UNSUPPORTED, w + why);
+    if (const int st = evac_host::handle_settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
+    DeviceGuard g(v.device);
+    hipLaunchKernelGGL(Enc::evaluate_kernel(norm_state != nullptr, v.default_cfg), dim3((unsigned)policy_wgs(v.p.n_envs)),
+                       dim3(evac::PolicyFamily::kBlock), 0, (hipStream_t)stream, v.p, a, ev, ea);
+    return evac_host::handle_check_launch(h, w.c_str());
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 // Host side of the transformer leader (include/evac.h: evac_policy_rollout_transformer, evac_policy_evaluate_transformer; kernels
-// in evac_transformer.h): evac_policy_rollout's / evac_policy_evaluate's checks and launch with the encoder's blocks beside the
-// actor-critic's thirteen tensors.  The handle is reached through evac_handle_host.h.  Every refusal before the first HIP call,
-// no device allocation, no synchronisation: one kernel on the caller's stream, capturable.
+// in evac_transformer.h): the encoder's blocks beside the actor-critic's thirteen tensors.  The two entries' bodies -- the checks
+// in their order, the handle, the launch -- are evac_handle_host.h's encoder_rollout / encoder_evaluate, which
+// evac_deepsets_api.hip shares; this unit holds what is the attention encoder's own: its limits, its check, its kernels.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -22,47 +22,48 @@ static_assert(sizeof(evac_transformer_block_t) == sizeof(evac::TransformerBlockA
 
 namespace {
 
-using evac_host::handle_fail;
-
-// The checks the two entries share: the thirteen tensors as evac_policy_rollout makes them (into `a`), then the encoder's.
-// Returns EVAC_OK, or the code with the text that follows the entry's name in `why`.
-int check_networks(const evac::Params& p, const evac_mlp_policy_t* policy, const evac_transformer_t* encoder, evac::PolicyArgs& a,
-                   evac::TransformerArgs& ta, std::string& why) {
-    if (!policy) return why = ": policy is NULL", EVAC_ERR_INVALID_ARGUMENT;
-    if (!encoder) return why = ": encoder is NULL", EVAC_ERR_INVALID_ARGUMENT;
-    if (!(why = mlp_policy_check(*policy, p.obs_dim, a)).empty()) return EVAC_ERR_INVALID_ARGUMENT;
-    const evac_transformer_t& T = *encoder;
-    if (T.num_heads != evac::kTfHeads)
-        return why = ": num_heads " + std::to_string(T.num_heads) + " is not supported (the kernels take 3)", EVAC_ERR_UNSUPPORTED;
-    if (T.dim_feedforward != evac::kTfFeedForward)
-        return why = ": dim_feedforward " + std::to_string(T.dim_feedforward) + " is not supported (the kernels take 96)", EVAC_ERR_UNSUPPORTED;
-    if (T.num_blocks < 1 || T.num_blocks > evac::kTfMaxBlocks)
-        return why = ": num_blocks " + std::to_string(T.num_blocks) + " is not supported (1 or 2)", EVAC_ERR_UNSUPPORTED;
-    if (T.ln_eps != evac::kTfLnEps) return why = ": ln_eps other than 1e-5 is not supported", EVAC_ERR_UNSUPPORTED;
-    if (p.n_ped + 2 > evac::kWave)
-        return why = ": N = " + std::to_string(p.n_ped) + " pedestrians is not supported (one wave holds the N + 2 tokens: N <= 62)",
-               EVAC_ERR_UNSUPPORTED;
-    if (p.obs_pos == EVAC_POS_GRAV) return why = ": the gravity observation is not supported (a Box observation of tokens is needed)", EVAC_ERR_UNSUPPORTED;
-    for (int b = 0; b < T.num_blocks; ++b) {
-        const evac_transformer_block_t& B = T.blocks[b];
-        if (!B.wq || !B.bq || !B.wk || !B.bk || !B.wv || !B.bv || !B.dense_w || !B.dense_b || !B.ff1_w || !B.ff1_b || !B.ff2_w ||
-            !B.ff2_b || !B.norm1_w || !B.norm1_b || !B.norm2_w || !B.norm2_b)
-            return why = ": a tensor pointer of the encoder's block " + std::to_string(b) + " is NULL", EVAC_ERR_INVALID_ARGUMENT;
+// evac_handle_host.h's trait of an encoder.  `check` comes after the policy's thirteen tensors: what the kernels take of the
+// encoder's sizes, then the handle's tokens, then the blocks' pointers and the token width.
+struct TransformerEncoder {
+    using Struct = evac_transformer_t;
+    using Args = evac::TransformerArgs;
+    static constexpr const char* kRollout = "evac_policy_rollout_transformer";
+    static constexpr const char* kEvaluate = "evac_policy_evaluate_transformer";
+    static int check(const evac::Params& p, const evac_transformer_t& T, evac::TransformerArgs& ta, std::string& why) {
+        if (T.num_heads != evac::kTfHeads)
+            return why = ": num_heads " + std::to_string(T.num_heads) + " is not supported (the kernels take 3)", EVAC_ERR_UNSUPPORTED;
+        if (T.dim_feedforward != evac::kTfFeedForward)
+            return why = ": dim_feedforward " + std::to_string(T.dim_feedforward) + " is not supported (the kernels take 96)", EVAC_ERR_UNSUPPORTED;
+        if (T.num_blocks < 1 || T.num_blocks > evac::kTfMaxBlocks)
+            return why = ": num_blocks " + std::to_string(T.num_blocks) + " is not supported (1 or 2)", EVAC_ERR_UNSUPPORTED;
+        if (T.ln_eps != evac::kTfLnEps) return why = ": ln_eps other than 1e-5 is not supported", EVAC_ERR_UNSUPPORTED;
+        if (p.n_ped + 2 > evac::kWave)
+            return why = ": N = " + std::to_string(p.n_ped) + " pedestrians is not supported (one wave holds the N + 2 tokens: N <= 62)",
+                   EVAC_ERR_UNSUPPORTED;
+        if (p.obs_pos == EVAC_POS_GRAV) return why = ": the gravity observation is not supported (a Box observation of tokens is needed)", EVAC_ERR_UNSUPPORTED;
+        for (int b = 0; b < T.num_blocks; ++b) {
+            const evac_transformer_block_t& B = T.blocks[b];
+            if (!B.wq || !B.bq || !B.wk || !B.bk || !B.wv || !B.bv || !B.dense_w || !B.dense_b || !B.ff1_w || !B.ff1_b || !B.ff2_w ||
+                !B.ff2_b || !B.norm1_w || !B.norm1_b || !B.norm2_w || !B.norm2_b)
+                return why = ": a tensor pointer of the encoder's block " + std::to_string(b) + " is NULL", EVAC_ERR_INVALID_ARGUMENT;
+        }
+        if (T.elem_dim < 1 || T.elem_dim > evac::kTfMaxModelDim || (int64_t)T.elem_dim * (p.n_ped + 2) != (int64_t)p.obs_dim)
+            return why = ": elem_dim " + std::to_string(T.elem_dim) + " x (" + std::to_string(p.n_ped) + " + 2) tokens is not the observation's " +
+                         std::to_string(p.obs_dim) + " floats (a Box observation is needed)", EVAC_ERR_INVALID_ARGUMENT;
+        ta = evac::TransformerArgs{};
+        for (int b = 0; b < T.num_blocks; ++b) {
+            const evac_transformer_block_t& B = T.blocks[b];
+            ta.blk[b] = evac::TransformerBlockArgs{B.wq, B.bq, B.wk, B.bk, B.wv, B.bv, B.dense_w, B.dense_b, B.ff1_w, B.ff1_b, B.ff2_w, B.ff2_b,
+                                                   B.norm1_w, B.norm1_b, B.norm2_w, B.norm2_b};
+        }
+        ta.elem_dim = (int)T.elem_dim;
+        ta.num_blocks = (int)T.num_blocks;
+        ta.use_resid = T.use_resid != 0;
+        return EVAC_OK;
     }
-    if (T.elem_dim < 1 || T.elem_dim > evac::kTfMaxModelDim || (int64_t)T.elem_dim * (p.n_ped + 2) != (int64_t)p.obs_dim)
-        return why = ": elem_dim " + std::to_string(T.elem_dim) + " x (" + std::to_string(p.n_ped) + " + 2) tokens is not the observation's " +
-                     std::to_string(p.obs_dim) + " floats (a Box observation is needed)", EVAC_ERR_INVALID_ARGUMENT;
-    ta = evac::TransformerArgs{};
-    for (int b = 0; b < T.num_blocks; ++b) {
-        const evac_transformer_block_t& B = T.blocks[b];
-        ta.blk[b] = evac::TransformerBlockArgs{B.wq, B.bq, B.wk, B.bk, B.wv, B.bv, B.dense_w, B.dense_b, B.ff1_w, B.ff1_b, B.ff2_w, B.ff2_b,
-                                               B.norm1_w, B.norm1_b, B.norm2_w, B.norm2_b};
-    }
-    ta.elem_dim = (int)T.elem_dim;
-    ta.num_blocks = (int)T.num_blocks;
-    ta.use_resid = T.use_resid != 0;
-    return EVAC_OK;
-}
+    static auto rollout_kernel(bool norm, bool def) { return EVAC_PICK_BOOL2(evac::k_policy_rollout_transformer, norm, def); }
+    static auto evaluate_kernel(bool norm, bool def) { return EVAC_PICK_BOOL2(evac::k_policy_evaluate_transformer, norm, def); }
+};
 
 }  // namespace
 
@@ -73,53 +74,17 @@ int evac_policy_rollout_transformer(evac_handle_t h, int32_t n_steps, const evac
                                     float* done_out, float* next_value_out, evac_episode_stats_t* final_stats, double* norm_state,
                                     float gamma, float obs_clip, float reward_clip, float epsilon, const evac_transformer_t* encoder,
                                     void* stream) {
-    const std::string w = "evac_policy_rollout_transformer";
-    evac_host::HandleView v;
-    if (const int rc = evac_host::handle_begin(h, w.c_str(), &v); rc != EVAC_OK) return rc;
-    std::string why = one_wave_check(v.p);
-    if (!why.empty()) return handle_fail(h, EVAC_ERR_UNSUPPORTED, w + why);
-    evac::PolicyArgs a = collect_outputs(next_obs, next_done, obs_out, actions_out, logprob_out, value_out, reward_out, done_out,
-                                         next_value_out, final_stats);
-    evac::TransformerArgs ta{};
-    why = collect_check(n_steps, a, false, policy);    // (the first refusal in the entry's order of checks)
-    if (!why.empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
-    if (const int rc = check_networks(v.p, policy, encoder, a, ta, why); rc != EVAC_OK) return handle_fail(h, rc, w + why);
-    why = collect_aligned(a);
-    if (!why.empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
-    if (const int st = evac_host::handle_settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
-    DeviceGuard g(v.device);
-    const evac::NormArgs na{norm_state, gamma, obs_clip, reward_clip, epsilon};
-    const bool norm = norm_state != nullptr, def = v.default_cfg;
-    const auto fn = EVAC_PICK_BOOL2(evac::k_policy_rollout_transformer, norm, def);
-    hipLaunchKernelGGL(fn, dim3((unsigned)policy_wgs(v.p.n_envs)), dim3(evac::PolicyFamily::kBlock), 0, (hipStream_t)stream, v.p,
-                       (int)n_steps, a, na, ta);
-    return evac_host::handle_check_launch(h, w.c_str());
+    return encoder_rollout<TransformerEncoder>(h, n_steps, policy,
+                                               collect_outputs(next_obs, next_done, obs_out, actions_out, logprob_out, value_out,
+                                                               reward_out, done_out, next_value_out, final_stats),
+                                               evac::NormArgs{norm_state, gamma, obs_clip, reward_clip, epsilon}, encoder, stream);
 }
 
 int evac_policy_evaluate_transformer(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy, int32_t n_episodes,
                                      int32_t max_steps, int32_t* progress, evac_episode_stats_t* episodes_out, const double* norm_state,
                                      float obs_clip, float epsilon, const evac_transformer_t* encoder, void* stream) {
-    const std::string w = "evac_policy_evaluate_transformer";
-    evac_host::HandleView v;
-    if (const int rc = evac_host::handle_begin(h, w.c_str(), &v); rc != EVAC_OK) return rc;
-    if (agent == EVAC_AGENT_VACUUM_CLEANER)
-        return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the scripted agent has no network (use evac_policy_evaluate)");
-    if (agent != EVAC_AGENT_POLICY_MEAN && agent != EVAC_AGENT_POLICY_SAMPLE)
-        return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": unknown agent " + std::to_string(agent));
-    evac::EvalArgs ev{};
-    evac::PolicyArgs a{};
-    evac::TransformerArgs ta{};
-    std::string why = evaluate_check(agent, n_episodes, max_steps, progress, episodes_out, norm_state, obs_clip, epsilon, ev);
-    if (!why.empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
-    if (const int rc = check_networks(v.p, policy, encoder, a, ta, why); rc != EVAC_OK) return handle_fail(h, rc, w + why);
-    if (!(why = one_wave_check(v.p)).empty()) return handle_fail(h, EVAC_ERR_UNSUPPORTED, w + why);
-    if (const int st = evac_host::handle_settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
-    DeviceGuard g(v.device);
-    const bool norm = norm_state != nullptr, def = v.default_cfg;
-    const auto fn = EVAC_PICK_BOOL2(evac::k_policy_evaluate_transformer, norm, def);
-    hipLaunchKernelGGL(fn, dim3((unsigned)policy_wgs(v.p.n_envs)), dim3(evac::PolicyFamily::kBlock), 0, (hipStream_t)stream, v.p, a, ev,
-                       ta);
-    return evac_host::handle_check_launch(h, w.c_str());
+    return encoder_evaluate<TransformerEncoder>(h, agent, policy, n_episodes, max_steps, progress, episodes_out, norm_state, obs_clip,
+                                                epsilon, encoder, stream);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@ module with that attribute routes to ``evac_policy_rollout_transformer`` / ``eva
 its EVAL-MODE function (dropout the identity): collection and training refuse a dropout probability other than 0."""
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Optional
 
 import numpy as np
@@ -188,14 +189,21 @@ def is_transformer(net) -> bool:
     return hasattr(net, "embedding")
 
 
+def encoder_kind(net):
+    """The row of ``ENCODER_KINDS`` (below, with what its rows name) of the encoder in front of ``net``'s actor-critic, or None
+    for the linear network.  The table's order is the precedence: a module with both attributes is read by ``embedding``."""
+    return next((kind for kind in ENCODER_KINDS if hasattr(net, kind.attr)), None)
+
+
 def encode_observation(net, x):
     """What ``actor_mean`` / ``critic`` of ``net`` read for the observations x [B, D]: x itself, or -- with a set encoder --
     ``deep_sets`` of x as [B, D / set_elem_dim, set_elem_dim] (rpo_deep_sets_agent_network.py:76-90); with an attention encoder
     ``embedding`` of x (its blocks take the flat observation)."""
-    if is_transformer(net):
-        return net.embedding(x)
-    if not is_deepsets(net):
+    kind = encoder_kind(net)
+    if kind is None:
         return x
+    if kind is _TRANSFORMER:
+        return net.embedding(x)
     ed = net.deep_sets.transform_phi[0].in_features
     return net.deep_sets(x.view(x.shape[0], -1, ed)).view(x.shape)
 
@@ -227,9 +235,8 @@ def transformer_tensors(net) -> tuple:
 def all_tensors(net) -> tuple:
     """Every parameter tensor the device reads: the actor-critic's 13, then the set encoder's 6 or the attention encoder's 16 per
     block if ``net`` has one."""
-    if is_transformer(net):
-        return mlp_tensors(net) + transformer_tensors(net)
-    return mlp_tensors(net) + (deepsets_tensors(net) if is_deepsets(net) else ())
+    kind = encoder_kind(net)
+    return mlp_tensors(net) + (() if kind is None else kind.tensors(net))
 
 
 def transformer_dropouts(net) -> list:
@@ -303,6 +310,16 @@ _ENCODER_NAMES = ("deep_sets.transform_phi[0].weight", "deep_sets.transform_phi[
                   "deep_sets.transform_phi[2].bias", "deep_sets.transform_rho[0].weight", "deep_sets.transform_rho[0].bias")
 
 
+def _check_tensors(names, tensors, shapes, device: torch.device, shape_note: str = "") -> None:
+    """``shape_note`` ends the message of a wrong shape (the set encoder's names the observation)."""
+    for name, t, shape in zip(names, tensors, shapes):
+        if t is None or tuple(t.shape) != shape:
+            raise ValueError(f"policy: `{name}` of shape {None if t is None else tuple(t.shape)}, expected {shape}{shape_note}")
+        if t.dtype != torch.float32 or t.device != device or not t.is_contiguous():
+            raise ValueError(f"policy: `{name}` must be a contiguous float32 tensor on {device}, got {t.dtype} on {t.device}"
+                             f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+
+
 def _check_encoder(net, obs_dim: int, device: torch.device, n_ped: Optional[int] = None) -> int:
     """The set encoder of ``net`` against the observation; returns ``set_elem_dim``."""
     ds = net.deep_sets
@@ -321,13 +338,7 @@ def _check_encoder(net, obs_dim: int, device: torch.device, n_ped: Optional[int]
         raise ValueError(f"policy: the observation's {obs_dim} floats are not a whole number of rows of `deep_sets`' {ed} floats per "
                          f"element{rows} (a Box observation is needed)")
     shapes = ((width, ed), (width,), (width, width), (width,), (obs_dim, width), (obs_dim,))
-    for name, t, shape in zip(_ENCODER_NAMES, deepsets_tensors(net), shapes):
-        if t is None or tuple(t.shape) != shape:
-            raise ValueError(f"policy: `{name}` of shape {None if t is None else tuple(t.shape)}, expected {shape} "
-                             f"(observation dim {obs_dim})")
-        if t.dtype != torch.float32 or t.device != device or not t.is_contiguous():
-            raise ValueError(f"policy: `{name}` must be a contiguous float32 tensor on {device}, got {t.dtype} on {t.device}"
-                             f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+    _check_tensors(_ENCODER_NAMES, deepsets_tensors(net), shapes, device, f" (observation dim {obs_dim})")
     if deepsets_tensors(net)[4].data_ptr() % 16:
         raise ValueError(f"policy: `{_ENCODER_NAMES[4]}` must be 16-byte aligned (its rows are read as vectors)")
     return ed
@@ -374,18 +385,35 @@ def _check_transformer(net, obs_dim: int, device: torch.device, n_ped: Optional[
             raise ValueError(f"policy: the observation's {obs_dim} floats are not a whole number of rows of `embedding`'s {d} floats per "
                              f"token{rows} (a Box observation is needed)")
         shapes = ((3 * d, d), (3 * d,)) * 3 + ((d, 3 * d), (d,), (TF_FEEDFORWARD, d), (TF_FEEDFORWARD,), (d, TF_FEEDFORWARD), (d,)) + ((d,),) * 4
-        for name, t, shape in zip(_BLOCK_TENSORS, ts, shapes):
-            if t is None or tuple(t.shape) != shape:
-                raise ValueError(f"policy: `{where}.{name}` of shape {None if t is None else tuple(t.shape)}, expected {shape}")
-            if t.dtype != torch.float32 or t.device != device or not t.is_contiguous():
-                raise ValueError(f"policy: `{where}.{name}` must be a contiguous float32 tensor on {device}, got {t.dtype} on {t.device}"
-                                 f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+        _check_tensors([f"{where}.{name}" for name in _BLOCK_TENSORS], ts, shapes, device)
     return dm, len(emb), resid
+
+
+def _transformer_struct(found, ts) -> _lib.EvacTransformer:
+    dm, blocks, resid = found
+    st = _lib.EvacTransformer(dm, blocks, TF_HEADS, TF_FEEDFORWARD, int(resid), TF_LN_EPS)
+    for b in range(blocks):
+        st.blocks[b] = _lib.EvacTransformerBlock(*[t.data_ptr() for t in ts[16 * b:16 * b + 16]])
+    return st
+
+
+# One kind of encoder in front of the actor-critic: the attribute that marks such a network, the suffix of its C entries
+# (evac_policy_rollout + suffix, evac_policy_evaluate + suffix), its parameter tensors in its struct's order,
+# check(net, obs_dim, device, n_ped) -> what struct(found, tensors) builds the C struct from, and what a binder's key holds beside
+# the tensors (None: nothing; `use_resid` is no tensor, so it is read at every call).  The kinds in order of precedence.
+EncoderKind = namedtuple("EncoderKind", "attr suffix tensors check struct key")
+ENCODER_KINDS = (
+    EncoderKind("embedding", "_transformer", transformer_tensors, _check_transformer, _transformer_struct,
+                lambda net: tuple(bool(getattr(b, "use_resid", False)) for b in net.embedding)),
+    EncoderKind("deep_sets", "_deepsets", deepsets_tensors, _check_encoder,
+                lambda ed, ts: _lib.EvacDeepSets(ed, SET_HIDDEN, *[t.data_ptr() for t in ts]), None))
+_TRANSFORMER, _DEEP_SETS = ENCODER_KINDS
 
 
 class PolicyBinder:
     """``evac_mlp_policy_t`` of a network, validated once per distinct set of parameter tensors (keyed by the tensor objects and
-    their addresses: parameters updated in place keep their entry; new tensors are checked again)."""
+    their addresses: parameters updated in place keep their entry; new tensors are checked again), and its encoder's struct
+    likewise: the policies' dictionary, and one for the encoders of every kind (6 pairs, or 16 per block and a tuple of bools)."""
 
     _ENTRIES = 8
 
@@ -394,58 +422,41 @@ class PolicyBinder:
         self._cache = {}
         self._encoders = {}
 
-    def __call__(self, net) -> _lib.EvacMlpPolicy:
+    def _bound(self, cache, net, tensors, check, struct, key=None):
+        """The cached struct of ``tensors(net)``, or after ``check()`` a new one, in place of the oldest of ``_ENTRIES``."""
         try:
-            ts = mlp_tensors(net)
+            ts = tensors(net)
         except (AttributeError, IndexError, TypeError):
-            _check_structure(net, self.obs_dim, self.device)
+            check()             # (the check's own message, where it has one)
             raise
-        key = tuple((id(t), t.data_ptr()) for t in ts)
-        ent = self._cache.get(key)
+        k = tuple((id(t), t.data_ptr()) for t in ts) + (() if key is None else (key(net),))
+        ent = cache.get(k)
         if ent is not None:
             return ent[0]
-        _check_structure(net, self.obs_dim, self.device)
-        st = _lib.EvacMlpPolicy(self.obs_dim, HIDDEN, *[t.data_ptr() for t in ts])
-        if len(self._cache) >= self._ENTRIES:
-            self._cache.pop(next(iter(self._cache)))
-        self._cache[key] = (st, ts)      # (the tensors stay referenced: their ids cannot be reused while the entry exists)
+        st = struct(check(), ts)
+        if len(cache) >= self._ENTRIES:
+            cache.pop(next(iter(cache)))
+        cache[k] = (st, ts)      # (the tensors stay referenced: their ids cannot be reused while the entry exists)
         return st
+
+    def __call__(self, net) -> _lib.EvacMlpPolicy:
+        return self._bound(self._cache, net, mlp_tensors, lambda: _check_structure(net, self.obs_dim, self.device),
+                           lambda _, ts: _lib.EvacMlpPolicy(self.obs_dim, HIDDEN, *[t.data_ptr() for t in ts]))
+
+    def _bind(self, kind: EncoderKind, net):
+        return self._bound(self._encoders, net, kind.tensors, lambda: kind.check(net, self.obs_dim, self.device, self.n_ped),
+                           kind.struct, kind.key)
 
     def encoder(self, net) -> _lib.EvacDeepSets:
         """``evac_deepsets_t`` of the set encoder of ``net`` (``is_deepsets``): cached and validated as the 13 tensors are."""
-        try:
-            ts = deepsets_tensors(net)
-        except (AttributeError, IndexError, TypeError):
-            _check_encoder(net, self.obs_dim, self.device, self.n_ped)
-            raise
-        key = tuple((id(t), t.data_ptr()) for t in ts)
-        ent = self._encoders.get(key)
-        if ent is not None:
-            return ent[0]
-        ed = _check_encoder(net, self.obs_dim, self.device, self.n_ped)
-        st = _lib.EvacDeepSets(ed, SET_HIDDEN, *[t.data_ptr() for t in ts])
-        if len(self._encoders) >= self._ENTRIES:
-            self._encoders.pop(next(iter(self._encoders)))
-        self._encoders[key] = (st, ts)
-        return st
+        return self._bind(_DEEP_SETS, net)
 
     def transformer(self, net) -> _lib.EvacTransformer:
         """``evac_transformer_t`` of the attention encoder of ``net`` (``is_transformer``): cached and validated as the 13
         tensors are (``use_resid`` is read at every call: it is no tensor)."""
-        try:
-            ts = transformer_tensors(net)
-        except (AttributeError, IndexError, TypeError):
-            _check_transformer(net, self.obs_dim, self.device, self.n_ped)
-            raise
-        key = tuple((id(t), t.data_ptr()) for t in ts) + (tuple(bool(getattr(b, "use_resid", False)) for b in net.embedding),)
-        ent = self._encoders.get(key)
-        if ent is not None:
-            return ent[0]
-        dm, blocks, resid = _check_transformer(net, self.obs_dim, self.device, self.n_ped)
-        st = _lib.EvacTransformer(dm, blocks, TF_HEADS, TF_FEEDFORWARD, int(resid), TF_LN_EPS)
-        for b in range(blocks):
-            st.blocks[b] = _lib.EvacTransformerBlock(*[t.data_ptr() for t in ts[16 * b:16 * b + 16]])
-        if len(self._encoders) >= self._ENTRIES:
-            self._encoders.pop(next(iter(self._encoders)))
-        self._encoders[key] = (st, ts)
-        return st
+        return self._bind(_TRANSFORMER, net)
+
+    def bind_encoder(self, net) -> Optional[tuple]:
+        """(the C entries' suffix, the encoder's struct) for ``encoder_kind(net)``, or None for the linear network."""
+        kind = encoder_kind(net)
+        return None if kind is None else (kind.suffix, self._bind(kind, net))

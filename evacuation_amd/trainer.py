@@ -17,7 +17,7 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from .policy import (PolicyBinder, all_tensors, deepsets_tensors, encode_observation, is_deepsets, is_transformer, mlp_tensors,
+from .policy import (PolicyBinder, all_tensors, deepsets_tensors, encode_observation, encoder_kind, is_deepsets, mlp_tensors,
                      refuse_deepsets, refuse_dropout, refuse_transformer)
 from .vector_env import STATS_FIELDS, _ptr
 
@@ -645,7 +645,7 @@ class RPOTrainer:
         if is_deepsets(net) and optimizer == "device" and grad_fn is None:     # (the default gradient of such a net is autograd's)
             refuse_deepsets(net, "RPOTrainer(optimizer=\"device\")")
         # (an encoder: collection and evaluation on the device, the gradient of all 19 / 13 + 16 per block tensors by autograd)
-        self.grad_fn = grad_fn or (autograd_minibatch_grad if is_deepsets(net) or is_transformer(net) else _kernel_grad)
+        self.grad_fn = grad_fn or (autograd_minibatch_grad if encoder_kind(net) is not None else _kernel_grad)
         self.rpo_noise_fn = rpo_noise_fn
         self.params = list(all_tensors(net))
         self.device = self.params[0].device

@@ -621,7 +621,7 @@ class BatchedEvacuationEnv:
         return binder
 
     def _policy_rollout(self, net, population, n_steps, next_obs, next_done, out, _norm, hypers=None):
-        from .policy import is_deepsets, is_transformer, refuse_deepsets, refuse_dropout, refuse_transformer
+        from .policy import refuse_deepsets, refuse_dropout, refuse_transformer
         if population is not None:
             refuse_transformer(net, "policy_rollout_population")
         refuse_dropout(net, "policy_rollout")
@@ -631,13 +631,9 @@ class BatchedEvacuationEnv:
             raise ValueError("policy_rollout: n_steps must be >= 1")
         binder = self._binder()
         pol = binder(net)
-        enc = tf = None
-        if is_transformer(net):               # the attention encoder in front of the actor-critic: evac_policy_rollout_transformer
-            tf = binder.transformer(net)
-        elif is_deepsets(net):                # the set encoder in front of the actor-critic: evac_policy_rollout_deepsets
-            if population is not None:
-                refuse_deepsets(net, "policy_rollout_population")
-            enc = binder.encoder(net)
+        if population is not None:
+            refuse_deepsets(net, "policy_rollout_population")
+        enc = binder.bind_encoder(net)        # an encoder in front of the actor-critic: evac_policy_rollout_deepsets / _transformer
         next_obs = self._check_tensor(next_obs, (E, D), torch.float32, "next_obs")
         next_done = self._check_tensor(next_done, (E,), torch.float32, "next_done")
         dev, f32 = self.device, torch.float32
@@ -652,10 +648,8 @@ class BatchedEvacuationEnv:
         args = [_ptr(next_obs), _ptr(next_done), _ptr(out["obs"]), _ptr(out["actions"]), _ptr(out["logprobs"]), _ptr(out["values"]),
                 _ptr(out["rewards"]), _ptr(out["dones"]), _ptr(out["next_value"]), _ptr(out["episode_stats"]), _ptr(state), gamma,
                 obs_clip, reward_clip, eps, self._stream()]
-        if tf is not None:
-            rc = self.lib.evac_policy_rollout_transformer(self._h, T, C.byref(pol), *args[:-1], C.byref(tf), args[-1])
-        elif enc is not None:
-            rc = self.lib.evac_policy_rollout_deepsets(self._h, T, C.byref(pol), *args[:-1], C.byref(enc), args[-1])
+        if enc is not None:
+            rc = getattr(self.lib, "evac_policy_rollout" + enc[0])(self._h, T, C.byref(pol), *args[:-1], C.byref(enc[1]), args[-1])
         elif population is None:
             rc = self.lib.evac_policy_rollout(self._h, T, C.byref(pol), *args)
         elif hypers is not None:
@@ -689,21 +683,17 @@ class BatchedEvacuationEnv:
     def _policy_evaluate(self, what, agent, population, n_episodes, max_steps, progress, out, deterministic, shared_episodes, _norm):
         """What ``policy_evaluate`` and ``policy_evaluate_population`` share, after their own checks of the agent: the one-wave
         limit, the learners' shares, the agent's code and structs, ``progress`` / ``out`` / the frozen statistics made or checked, and the call."""
-        from .policy import is_deepsets, is_transformer
         self._one_wave(what)
         K, T, E, D = int(n_episodes), int(max_steps), self.num_envs, self.obs_dim
         if population is not None and E % int(population.num_learners):
             raise ValueError(f"{what}: {E} envs are not {int(population.num_learners)} learners' equal shares")
-        pol = enc = tf = None
+        pol = enc = None
         if isinstance(agent, str):
             code = EVALUATE_AGENTS[agent]
         else:
             binder = self._binder()
             code, pol = (_lib.AGENT_POLICY_MEAN if deterministic else _lib.AGENT_POLICY_SAMPLE), C.byref(binder(agent))
-            if is_transformer(agent):
-                tf = binder.transformer(agent)
-            elif is_deepsets(agent):
-                enc = binder.encoder(agent)
+            enc = binder.bind_encoder(agent)
         if progress is None:
             progress = torch.zeros((E, 4), dtype=torch.int32, device=self.device)
         else:
@@ -719,10 +709,8 @@ class BatchedEvacuationEnv:
         if population is not None:
             rc = self.lib.evac_policy_evaluate_population(self._h, int(population.num_learners), pol, C.byref(population.strides), code,
                                                           int(bool(shared_episodes)), *args, self._stream())
-        elif tf is not None:
-            rc = self.lib.evac_policy_evaluate_transformer(self._h, code, pol, *args, C.byref(tf), self._stream())
         elif enc is not None:
-            rc = self.lib.evac_policy_evaluate_deepsets(self._h, code, pol, *args, C.byref(enc), self._stream())
+            rc = getattr(self.lib, "evac_policy_evaluate" + enc[0])(self._h, code, pol, *args, C.byref(enc[1]), self._stream())
         else:
             rc = self.lib.evac_policy_evaluate(self._h, code, pol, *args, self._stream())
         _lib.check(rc, self._h)

@@ -24,6 +24,7 @@ import sys
 import numpy as np
 import pytest
 
+from tests.encoder_cases import EncoderCases, _frozen, ea, rel_err  # noqa: F401 (ea: the fixture)
 from tests.test_gpu_policy_rollout import OFFSET, SEED, base, i32, raw, replay_env_side, snapshot, start
 
 pytestmark = pytest.mark.gpu
@@ -48,26 +49,6 @@ NET_SEEDS = {"n62_rel_ohe_box_norm_clip": 0, "n60_rel_ohe_box_raw_resid": 0, "n6
              "n10_abs_cat_box_raw": 1, "n31_rel_no_box_norm": 1}
 MIN_NORM_VARIANCE = 1e-4
 T_STEPS = 40
-
-
-@pytest.fixture(scope="module")
-def ea():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import evacuation_amd
-    from evacuation_amd import build
-    build.build_library()
-    return evacuation_amd
-
-
-def make_env(ea, case, E, raw_env=False, **options):
-    from evacuation_amd.options import KernelOptions
-    cfg_kw, wrap_kw, norm, opts = CASES[case][:4]
-    opts = {**opts, **options}
-    env = ea.BatchedEvacuationEnv(ea.EnvConfig(**cfg_kw), ea.EnvWrappersConfig(**wrap_kw), num_envs=E, seed=SEED, env_id_offset=OFFSET,
-                                  options=KernelOptions().replace(**opts) if opts else None)
-    return ea.NormalizedVectorEnv(env) if norm and not raw_env else env
 
 
 def token_dim(case):
@@ -95,31 +76,8 @@ def make_net(case, seed=None, device="cuda:0"):
     return net.to(device)
 
 
-def rel_err(got, want):
-    return float(np.max(np.abs(got - want) / np.maximum(1.0, np.abs(want))))
-
-
-_RUNS = {}
-
-
-def rollout_of(ea, case, E):
-    """One rollout of T_STEPS per (case, E), shared by the tests and left unchanged: (net, storage, start observation,
-    the envs' step counts at the start, final snapshot, norm_state at the start or None)."""
-    key = (case, E)
-    if key not in _RUNS:
-        import torch
-        env = make_env(ea, case, E)
-        net = make_net(case)
-        obs, done = start(env)
-        ns0 = env.norm_state.clone() if hasattr(env, "norm_state") else None
-        total0 = base(env).clock[:, 2].cpu().numpy().astype(np.int64)
-        obs0 = obs.clone()
-        ro = env.policy_rollout(net, T_STEPS, obs, done)
-        torch.cuda.synchronize()
-        assert ro["next_obs"] is obs and ro["next_done"] is done
-        _RUNS[key] = (net, {k: v.clone() for k, v in ro.items()}, obs0, total0, snapshot(env), ns0)
-        env.close()
-    return _RUNS[key]
+_cases = EncoderCases(CASES, make_net, T_STEPS)
+make_env, rollout_of, _run, _twins = _cases.make_env, _cases.rollout_of, _cases.run, _cases.twins
 
 
 @pytest.mark.parametrize("E", [64, 20])
@@ -190,15 +148,6 @@ def test_env_side_bit_for_bit(ea, case, E):
     twin.close()
 
 
-def _run(ea, case, E, T_split, net):
-    env = make_env(ea, case, E)
-    obs, done = start(env)
-    outs = [{k: v.clone() for k, v in env.policy_rollout(net, T, obs, done).items()} for T in T_split]
-    fin = snapshot(env)
-    env.close()
-    return outs, fin
-
-
 PER_STEP = ("obs", "actions", "logprobs", "values", "rewards", "dones", "episode_stats")
 
 
@@ -221,30 +170,7 @@ def test_invariance(ea, case):
         assert raw(f1[k]).equal(raw(f2[k])) and raw(f1[k]).equal(raw(f3[k])), (case, k)
 
 
-def _twins(ea, case, E):
-    a, b = make_env(ea, case, E, raw_env=True, subwave=0), make_env(ea, case, E, raw_env=True, subwave=0)
-    a.reset()
-    b.reset()
-    for env in (a, b):
-        st = env.get_state()
-        now = st["now"].clone()
-        now[::5] = env.env_config.max_timesteps - 1
-        now[1::5] = env.env_config.max_timesteps - 2
-        env.set_state(now=now)
-    return a, b
-
-
 STATE = ("ped", "status", "agent", "clock", "acc")
-
-
-def _frozen(env, E):
-    import torch
-    g = torch.Generator().manual_seed(5)
-    D = env.obs_dim
-    ns = torch.zeros((E, 3 * D + 4), dtype=torch.float64)
-    ns[:, :D] = torch.randn((E, D), generator=g, dtype=torch.float64) * 0.1
-    ns[:, D:2 * D] = torch.rand((E, D), generator=g, dtype=torch.float64) + 0.05
-    return ns.to(env.device)
 
 
 @pytest.mark.parametrize("mode", ["sample", "mean"])
