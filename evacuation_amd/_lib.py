@@ -69,6 +69,16 @@ class EvacDeepSetsGrads(C.Structure):
     _fields_ = [(f, C.c_void_p) for f, _ in EvacDeepSets._fields_[2:]]
 
 
+class EvacTransformerBlockGrads(C.Structure):
+    """evac_transformer_block_grads_t: where evac_transformer_minibatch_grad writes the gradients of one block's 16 tensors"""
+    _fields_ = list(EvacTransformerBlock._fields_)
+
+
+class EvacTransformerGrads(C.Structure):
+    """evac_transformer_grads_t: the blocks' gradients (blocks at index num_blocks and above are never followed)"""
+    _fields_ = [("blocks", EvacTransformerBlockGrads * 2)]
+
+
 class EvacRpoLossConfig(C.Structure):
     """evac_rpo_loss_config_t"""
     _fields_ = [(f, C.c_float) for f in ("clip_coef", "ent_coef", "vf_coef", "rpo_alpha")] + [("norm_adv", C.c_int32), ("clip_vloss", C.c_int32)]
@@ -200,6 +210,10 @@ SIGNATURES = {
     "evac_deepsets_minibatch_grad": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacDeepSets), C.POINTER(EvacRpoLossConfig), C.c_int64,
                                                _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_uint64,
                                                C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads), _P, _P, _P]),
+    "evac_transformer_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
+    "evac_transformer_minibatch_grad": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacTransformer), C.POINTER(EvacRpoLossConfig), C.c_int64,
+                                                  _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_uint64,
+                                                  C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacTransformerGrads), _P, _P, _P]),
     "evac_adam_step": (C.c_int, [C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacAdamState),
                                  C.POINTER(EvacAdamConfig), C.c_int32, _P, _P]),
     "evac_rpo_minibatch_step": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacRpoLossConfig), C.c_int64, _P, _P, _P, _P, _P, _P,

@@ -12,6 +12,7 @@
 #include "evac_transformer.h"
 #include "evac_handle_host.h"
 #include "evac_host.h"
+#include "evac_transformer_host.h"
 
 static_assert(sizeof(evac::Params) + 8 + sizeof(evac::PolicyArgs) + sizeof(evac::NormArgs) + sizeof(evac::TransformerArgs) <= 4096,
               "k_policy_rollout_transformer: arguments beyond the kernel-argument segment");
@@ -19,34 +20,28 @@ static_assert(sizeof(evac::PolicyFamily::Smem) + sizeof(evac::PolicySmem<false>)
                   sizeof(evac::TransformerSmem) <= 160 * 1024, "the transformer kernels' LDS beyond a CU's 160 KiB");
 static_assert(sizeof(evac_transformer_block_t) == sizeof(evac::TransformerBlockArgs) && evac::kTfMaxBlocks == 2,
               "evac_transformer_block_t and the kernels' block arguments: the same 16 pointers in the same order");
+static_assert(evac::kTfHeads == kTransformerHeads && evac::kTfFeedForward == kTransformerFeedForward &&
+                  evac::kTfMaxModelDim == kTransformerMaxModelDim && evac::kTfMaxBlocks == kTransformerMaxBlocks &&
+                  evac::kWave == kTransformerMaxTokens && evac::kTfLnEps == kTransformerLnEps,
+              "evac_transformer_host.h's limits are the kernels'");
 
 namespace {
 
 // evac_handle_host.h's trait of an encoder.  `check` comes after the policy's thirteen tensors: what the kernels take of the
-// encoder's sizes, then the handle's tokens, then the blocks' pointers and the token width.
+// encoder's sizes, then the handle's tokens, then the blocks' pointers and the token width (the first and the third are
+// evac_transformer_host.h's, shared with the gradient's unit).
 struct TransformerEncoder {
     using Struct = evac_transformer_t;
     using Args = evac::TransformerArgs;
     static constexpr const char* kRollout = "evac_policy_rollout_transformer";
     static constexpr const char* kEvaluate = "evac_policy_evaluate_transformer";
     static int check(const evac::Params& p, const evac_transformer_t& T, evac::TransformerArgs& ta, std::string& why) {
-        if (T.num_heads != evac::kTfHeads)
-            return why = ": num_heads " + std::to_string(T.num_heads) + " is not supported (the kernels take 3)", EVAC_ERR_UNSUPPORTED;
-        if (T.dim_feedforward != evac::kTfFeedForward)
-            return why = ": dim_feedforward " + std::to_string(T.dim_feedforward) + " is not supported (the kernels take 96)", EVAC_ERR_UNSUPPORTED;
-        if (T.num_blocks < 1 || T.num_blocks > evac::kTfMaxBlocks)
-            return why = ": num_blocks " + std::to_string(T.num_blocks) + " is not supported (1 or 2)", EVAC_ERR_UNSUPPORTED;
-        if (T.ln_eps != evac::kTfLnEps) return why = ": ln_eps other than 1e-5 is not supported", EVAC_ERR_UNSUPPORTED;
+        if (const int rc = transformer_check_sizes(T, why); rc != EVAC_OK) return rc;
         if (p.n_ped + 2 > evac::kWave)
             return why = ": N = " + std::to_string(p.n_ped) + " pedestrians is not supported (one wave holds the N + 2 tokens: N <= 62)",
                    EVAC_ERR_UNSUPPORTED;
         if (p.obs_pos == EVAC_POS_GRAV) return why = ": the gravity observation is not supported (a Box observation of tokens is needed)", EVAC_ERR_UNSUPPORTED;
-        for (int b = 0; b < T.num_blocks; ++b) {
-            const evac_transformer_block_t& B = T.blocks[b];
-            if (!B.wq || !B.bq || !B.wk || !B.bk || !B.wv || !B.bv || !B.dense_w || !B.dense_b || !B.ff1_w || !B.ff1_b || !B.ff2_w ||
-                !B.ff2_b || !B.norm1_w || !B.norm1_b || !B.norm2_w || !B.norm2_b)
-                return why = ": a tensor pointer of the encoder's block " + std::to_string(b) + " is NULL", EVAC_ERR_INVALID_ARGUMENT;
-        }
+        if (const int rc = transformer_check_blocks(T, why); rc != EVAC_OK) return rc;
         if (T.elem_dim < 1 || T.elem_dim > evac::kTfMaxModelDim || (int64_t)T.elem_dim * (p.n_ped + 2) != (int64_t)p.obs_dim)
             return why = ": elem_dim " + std::to_string(T.elem_dim) + " x (" + std::to_string(p.n_ped) + " + 2) tokens is not the observation's " +
                          std::to_string(p.obs_dim) + " floats (a Box observation is needed)", EVAC_ERR_INVALID_ARGUMENT;

@@ -17,8 +17,8 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from .policy import (PolicyBinder, all_tensors, deepsets_tensors, encode_observation, encoder_kind, is_deepsets, mlp_tensors,
-                     refuse_deepsets, refuse_dropout, refuse_transformer)
+from .policy import (PolicyBinder, all_tensors, deepsets_tensors, encode_observation, encoder_kind, is_deepsets, is_transformer,
+                     mlp_tensors, refuse_deepsets, refuse_dropout, refuse_transformer, transformer_tensors)
 from .vector_env import STATS_FIELDS, _ptr
 
 STAT_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "grad_sumsq")
@@ -141,6 +141,7 @@ class _GradState:
     def __init__(self):
         self.binder, self.grads, self.workspace = None, [None, None], None
         self.encoder_grads = [None, None]                                    # deepsets_minibatch_grad's
+        self.transformer_grads = [None, None]                                # transformer_minibatch_grad's
 
 
 def _grad_state(net) -> _GradState:
@@ -168,9 +169,23 @@ def ensure_encoder_grads(net) -> "_lib.EvacDeepSetsGrads":
     return _tensor_struct(_grad_state(net).encoder_grads, [t.grad for t in deepsets_tensors(net)], _lib.EvacDeepSetsGrads)
 
 
+def ensure_transformer_grads(net) -> "_lib.EvacTransformerGrads":
+    """``ensure_grads`` for the attention encoder's 16 tensors per block: the addresses of their ``.grad`` as
+    ``evac_transformer_grads_t`` (the blocks the network does not have stay NULL: they are never followed)."""
+    ensure_grads(net)
+
+    def struct(*ptrs):
+        st = _lib.EvacTransformerGrads()
+        for b in range(len(ptrs) // 16):
+            st.blocks[b] = _lib.EvacTransformerBlockGrads(*ptrs[16 * b:16 * b + 16])
+        return st
+    return _tensor_struct(_grad_state(net).transformer_grads, [t.grad for t in transformer_tensors(net)], struct)
+
+
 def _batch_args(net, batch: Dict[str, torch.Tensor], deepsets: bool = False):
     """The checks every gradient entry makes of ``batch``; returns (B, D, device, state, evac_mlp_policy_t, grads struct, the
-    entries' arguments ``batch_size, b_obs .. b_values``).  ``deepsets``: the caller is the set encoder's own entry."""
+    entries' arguments ``batch_size, b_obs .. b_values``).  ``deepsets``: the caller is an encoder's own entry (the set encoder's,
+    or the attention encoder's)."""
     if not deepsets:
         refuse_deepsets(net, "the device gradient")
     b_obs = batch["b_obs"]
@@ -216,24 +231,30 @@ def _u64(x: int) -> int:
 
 
 def _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, opt: Optional["DeviceAdam"],
-                    deepsets: bool = False) -> torch.Tensor:
+                    deepsets: bool = False, transformer: bool = False) -> torch.Tensor:
     """``evac_rpo_minibatch_grad``, or with ``opt`` ``evac_rpo_minibatch_step``: the same arguments and the optimiser's three;
     or with ``deepsets`` ``evac_deepsets_minibatch_grad``: the same arguments, the encoder after the policy and its gradients
     after the policy's, and a workspace of its own size -- and with ``opt`` ``evac_deepsets_minibatch_step``: the optimiser's
-    three, the encoder's parameters after the policy's."""
-    B, D, dev, st, pol, grads, b_args = _batch_args(net, batch, deepsets)
-    if deepsets:
+    three, the encoder's parameters after the policy's; or with ``transformer`` ``evac_transformer_minibatch_grad``, whose
+    arguments are the set encoder's with the attention encoder's two structs (no optimiser form exists)."""
+    B, D, dev, st, pol, grads, b_args = _batch_args(net, batch, deepsets or transformer)
+    kind = "transformer" if transformer else ("deepsets" if deepsets else "rpo")
+    if transformer:
+        enc, enc_grads = st.binder.transformer(net), ensure_transformer_grads(net)
+    elif deepsets:
         enc, enc_grads = st.binder.encoder(net), ensure_encoder_grads(net)
     if mb_inds.dtype != torch.int64 or mb_inds.device != dev or not mb_inds.is_contiguous() or mb_inds.dim() != 1:
         raise ValueError("mb_inds: expected a contiguous int64 device vector")
     M = int(mb_inds.shape[0])
-    stats, ws = _call_buffers(st, D, M, dev, rpo_noise, stats, sizer=f"evac_{'deepsets' if deepsets else 'rpo'}_workspace_bytes")
+    stats, ws = _call_buffers(st, D, M, dev, rpo_noise, stats, sizer=f"evac_{kind}_workspace_bytes")
     lc = _loss_config(cfg)
     args = [C.byref(pol), C.byref(lc), *b_args, M, _ptr(mb_inds), _ptr(rpo_noise), _u64(seed), _u64(draw_counter), C.byref(grads),
             _ptr(stats), _ptr(ws), _stream(dev)]
-    if deepsets:
+    if deepsets or transformer:
         args = [args[0], C.byref(enc), *args[1:-3], C.byref(enc_grads), *args[-3:]]
-        if opt is None:
+        if transformer:
+            rc = _lib.load().evac_transformer_minibatch_grad(*args)
+        elif opt is None:
             rc = _lib.load().evac_deepsets_minibatch_grad(*args)
         else:
             oc = opt.config()
@@ -268,6 +289,22 @@ def deepsets_minibatch_grad(net, batch: Dict[str, torch.Tensor], mb_inds: torch.
     if not is_deepsets(net):
         raise ValueError("deepsets_minibatch_grad: the network has no set encoder (`deep_sets`); its gradient is rpo_minibatch_grad's")
     return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, None, deepsets=True)
+
+
+def transformer_minibatch_grad(net, batch: Dict[str, torch.Tensor], mb_inds: torch.Tensor, cfg, *,
+                               rpo_noise: Optional[torch.Tensor] = None, seed: int = 0, draw_counter: int = 0,
+                               stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``rpo_minibatch_grad`` for a network with the reference's attention encoder (``policy.TransformerActorCritic``): the
+    gradient of the RPO loss of the minibatch into the ``.grad`` of all 13 + 16 per block tensors (written, not accumulated) by
+    ``evac_transformer_minibatch_grad`` -- the encoder forwards, the linear network's three gradient launches on the encoded
+    observations, one launch per block backwards.  Same arguments, same 8 statistics (``stats[7]``: the sum of squares over all
+    the tensors), deterministic, no host synchronisation, capturable.  The encoder is the eval-mode function: a dropout
+    probability other than 0 is refused.  The optimiser stays torch's (``RPOTrainer(grad_fn=transformer_kernel_grad)``)."""
+    if not is_transformer(net):
+        raise ValueError("transformer_minibatch_grad: the network has no attention encoder (`embedding`); its gradient is "
+                         "rpo_minibatch_grad's or deepsets_minibatch_grad's")
+    refuse_dropout(net, "transformer_minibatch_grad")
+    return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, None, transformer=True)
 
 
 HEADER_FIELDS = ("t", "P1", "P2", "stop", "steps_run", "epochs_run")
@@ -530,6 +567,14 @@ def deepsets_kernel_grad(trainer: "RPOTrainer", batch, mb_inds, rpo_noise, draw_
                                    draw_counter=draw_counter, stats=stats)
 
 
+def transformer_kernel_grad(trainer: "RPOTrainer", batch, mb_inds, rpo_noise, draw_counter: int, stats: torch.Tensor) -> torch.Tensor:
+    """A ``grad_fn`` of ``RPOTrainer`` for a network with an attention encoder: ``transformer_minibatch_grad`` (collection and
+    gradient on the device, torch's clip and Adam).  Opt-in: the default for such a network stays ``autograd_minibatch_grad``,
+    and ``optimizer="device"`` stays refused with any ``grad_fn``."""
+    return transformer_minibatch_grad(trainer.net, batch, mb_inds, trainer.cfg, rpo_noise=rpo_noise, seed=trainer.cfg.seed,
+                                      draw_counter=draw_counter, stats=stats)
+
+
 # The gradient functions whose step and whole update exist as one host call (RPOTrainer with optimizer="device")
 _STEP_OF = ((_kernel_grad, rpo_minibatch_step), (deepsets_kernel_grad, deepsets_minibatch_step))
 _UPDATE_OF = ((_kernel_grad, rpo_update), (deepsets_kernel_grad, deepsets_update))
@@ -548,7 +593,7 @@ def autograd_minibatch_grad(trainer, batch, mb_inds, rpo_noise, draw_counter: in
     """A ``grad_fn`` of ``RPOTrainer`` for ANY network it takes: the reference's minibatch loss (rpo_agent.py:239-274 with
     get_action_and_value of rpo_linear_agent_network.py:48-61 / rpo_deep_sets_agent_network.py:83-90) through torch autograd on
     the module itself -- the gradient of a network with a set encoder, whose 19 tensors the linear gradient kernels do not know,
-    and of one with an attention encoder (rpo_transformer_agent_network.py), whose 45 no kernel does.
+    and of one with an attention encoder (rpo_transformer_agent_network.py), whose 45 ``transformer_kernel_grad`` does on opt-in.
     Writes the parameters' ``.grad`` (not accumulated) and the 8 statistics (``STAT_NAMES``; ``stats[7]`` the gradient's sum of
     squares, in double).  ``rpo_noise`` [M, 2]: the perturbation of the mean; None draws U(-rpo_alpha, rpo_alpha) from a torch
     generator seeded with (``cfg.seed``, ``draw_counter``).  ``trainer``: anything with ``net`` and ``cfg``."""
@@ -613,8 +658,9 @@ class RPOTrainer:
     ``grad_fn`` is followed by ``self.optimizer.step(stats[7])``) and stays a ``ValueError`` with ``grad_fn`` left at its
     default, which for such a network is autograd's.  Or one with the reference's attention encoder
     (``policy.TransformerActorCritic``): collection and evaluation on the device, the gradient of its 13 + 16 per block tensors
-    by ``autograd_minibatch_grad`` and torch's Adam; ``optimizer="device"`` and a dropout probability other than 0 (the device
-    collects with the eval-mode function) are ``ValueError``s.
+    by ``autograd_minibatch_grad`` or, with ``grad_fn=transformer_kernel_grad``, the device's
+    (``evac_transformer_minibatch_grad``), and torch's Adam; ``optimizer="device"`` (with any ``grad_fn``) and a dropout
+    probability other than 0 (the device collects with the eval-mode function) are ``ValueError``s.
 
     ``env``: a ``NormalizedVectorEnv`` (the trainer's wrapper chain) or a ``BatchedEvacuationEnv`` with ``cfg.num_envs`` envs.
     The permutation of every epoch is drawn on the device from a generator seeded with ``cfg.seed`` (the reference shuffles on

@@ -23,9 +23,9 @@ host call (``evac_deepsets_update``: seven launches per step).  Not with ``--see
 ``--network transformer`` trains the reference's attention-encoder network (``policy.TransformerActorCritic``,
 RPOTransformerEmbedding; ``--blocks`` 1 or 2, ``--use-resid``) on the rel + ohe Box observation, at most 62 pedestrians:
 collection and evaluation on the device (``evac_policy_rollout_transformer`` / ``evac_policy_evaluate_transformer``, the
-eval-mode function: dropout 0), the gradient of its 13 + 16 per block tensors by torch autograd and torch's Adam.  Not with
-``--gradient device``, ``--optimizer device``, ``--seeds``, ``--sweep`` or ``--compare``: no gradient or optimiser kernel knows
-its tensors.
+eval-mode function: dropout 0), the gradient of its 13 + 16 per block tensors by torch autograd or, with ``--gradient device``,
+by ``evac_transformer_minibatch_grad`` (``trainer.transformer_kernel_grad``), and torch's Adam.  Not with ``--optimizer device``,
+``--seeds``, ``--sweep`` or ``--compare``: no optimiser kernel knows its tensors.
 
 ``--eval-every K`` evaluates the leader every K updates (``RPOTrainer.evaluate``: whole episodes, the mean action, the observation
 statistics frozen) and prints the summary; ``--baseline`` prints the same line for the reference's scripted sweep baseline
@@ -60,7 +60,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import evacuation_amd as ea  # noqa: E402
 from evacuation_amd.policy import DeepSetsActorCritic, LinearActorCritic, TransformerActorCritic, mlp_tensors  # noqa: E402
-from evacuation_amd.trainer import RPOTrainer, RPOTrainingConfig, deepsets_kernel_grad, flatten_batch  # noqa: E402
+from evacuation_amd.trainer import (RPOTrainer, RPOTrainingConfig, deepsets_kernel_grad, flatten_batch,  # noqa: E402
+                                    transformer_kernel_grad)
 
 DEV = torch.device("cuda:0")
 
@@ -80,6 +81,8 @@ def make_trainer(args, **hooks):
         net = (DeepSetsActorCritic(env.obs_dim, args.pedestrians) if deep_sets else LinearActorCritic(env.obs_dim)).to(DEV)
     if deep_sets and getattr(args, "gradient", "autograd") == "device":
         hooks.setdefault("grad_fn", deepsets_kernel_grad)
+    if network == "transformer" and getattr(args, "gradient", "autograd") == "device":
+        hooks.setdefault("grad_fn", transformer_kernel_grad)
     return RPOTrainer(env, net, cfg, **hooks)
 
 
@@ -264,18 +267,20 @@ def main():
     ap.add_argument("--blocks", type=int, default=2, help="with --network transformer: the encoder's blocks (1 or 2)")
     ap.add_argument("--use-resid", action="store_true", help="with --network transformer: residual connections in the blocks")
     ap.add_argument("--gradient", choices=("autograd", "device"), default="autograd",
-                    help="with --network deep_sets: the gradient of its 19 tensors by torch autograd or by evac_deepsets_minibatch_grad")
+                    help="with --network deep_sets / transformer: the gradient of its 19 / 13 + 16 per block tensors by torch autograd or "
+                         "by evac_deepsets_minibatch_grad / evac_transformer_minibatch_grad")
     args = ap.parse_args()
-    if args.gradient == "device" and args.network != "deep_sets":
-        raise SystemExit("--gradient device goes with --network deep_sets (the linear network's gradient is the device's anyway)")
+    if args.gradient == "device" and args.network == "linear":
+        raise SystemExit("--gradient device goes with --network deep_sets or transformer (the linear network's gradient is the device's "
+                         "anyway)")
     if args.network == "deep_sets" and (args.compare or args.seeds or args.sweep or
                                         (args.optimizer == "device" and args.gradient != "device")):
         raise SystemExit("--network deep_sets: the gradient and optimiser kernels (--optimizer device, --seeds, --sweep, --compare) are "
                          "the linear network's; its gradient is autograd's or --gradient device, and --optimizer device goes with "
                          "--gradient device")
-    if args.network == "transformer" and (args.compare or args.seeds or args.sweep or args.optimizer == "device" or args.gradient == "device"):
-        raise SystemExit("--network transformer: no gradient or optimiser kernel knows its tensors (--gradient device, --optimizer device, "
-                         "--seeds, --sweep, --compare); it trains with autograd's gradient and torch's Adam")
+    if args.network == "transformer" and (args.compare or args.seeds or args.sweep or args.optimizer == "device"):
+        raise SystemExit("--network transformer: no optimiser kernel knows its tensors (--optimizer device, --seeds, --sweep, --compare); "
+                         "it trains with autograd's gradient or --gradient device, and torch's Adam")
     if args.compare:
         return compare(args)
     seeds = [int(x) for x in args.seeds.split(",")] if args.seeds else None

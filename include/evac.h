@@ -661,6 +661,39 @@ int evac_deepsets_minibatch_grad(const evac_mlp_policy_t* policy, const evac_dee
                                  const evac_mlp_policy_grads_t* grads_out, const evac_deepsets_grads_t* encoder_grads_out,
                                  float* stats_out, void* workspace, void* stream);
 
+/* The same gradient for the transformer leader, all 13 + 16 num_blocks tensors (45 with two blocks): evac_rpo_minibatch_grad's
+ * contract word for word (the loss, the sub-gradients, the clamped indices, the Philox draw of z when rpo_noise is NULL, written
+ * not accumulated), with the network reading y = encode(x) of evac_transformer_t -- the eval-mode function the entries above
+ * compute, the same formulas in the same order of sums -- where the linear one reads x = b_obs[mb_inds[m]].  The 13 gradients go
+ * to grads_out, a block's 16 to encoder_grads_out->blocks[b]; blocks at index num_blocks and above are neither read nor written
+ * (their pointers may be NULL).  stats_out[0..6] keep their meaning and stats_out[7] is the sum of squares of the gradient over
+ * all 13 + 16 num_blocks tensors.  relu' is 1 where the pre-activation is > 0 and 0 otherwise (torch's convention).  wk's bias has
+ * the exact gradient zero (a shift of every score of a row); it is computed like every other tensor and holds rounding.
+ * 5 + num_blocks + norm_adv launches on `stream`: the encoder forwards, the three of evac_rpo_minibatch_grad on the encoded
+ * observations, the gradient of the encoder's output, one launch per block backwards (the last block first), the finish.  No
+ * host synchronisation, capturable; the parameters are read when the kernels run.  DETERMINISTIC: every sum has a fixed order, no
+ * floating-point atomics, the same bits on every run and stream.  workspace: 16-byte aligned,
+ * evac_transformer_workspace_bytes(obs_dim, M) bytes (sized for two blocks; an error code for the arguments
+ * evac_rpo_workspace_bytes refuses), contents irrelevant before and after.
+ * Refusals, before anything touches a device and through the return code alone; the encoder's sizes are looked at before its
+ * pointers.  EVAC_ERR_INVALID_ARGUMENT: everything evac_rpo_minibatch_grad refuses; a NULL encoder or encoder-gradient struct; a
+ * NULL tensor of a block in use, in either; elem_dim outside 1..6; obs_dim not a multiple of elem_dim or fewer than 3 tokens; a
+ * misaligned workspace.  EVAC_ERR_UNSUPPORTED: num_heads != 3, dim_feedforward != 96, num_blocks outside 1..2, ln_eps != 1e-5f,
+ * more than 64 tokens (N > 62). */
+typedef struct evac_transformer_block_grads {   /* the 16 tensors of evac_transformer_block_t, writable, same order and layouts */
+    float *wq, *bq, *wk, *bk, *wv, *bv, *dense_w, *dense_b, *ff1_w, *ff1_b, *ff2_w, *ff2_b, *norm1_w, *norm1_b, *norm2_w, *norm2_b;
+} evac_transformer_block_grads_t;
+typedef struct evac_transformer_grads { evac_transformer_block_grads_t blocks[2]; } evac_transformer_grads_t;
+int64_t evac_transformer_workspace_bytes(int32_t obs_dim, int64_t n_minibatch);
+int evac_transformer_minibatch_grad(const evac_mlp_policy_t* policy, const evac_transformer_t* encoder,
+                                    const evac_rpo_loss_config_t* cfg, int64_t batch_size,
+                                    const float* b_obs, const float* b_actions, const float* b_logprobs,
+                                    const float* b_advantages, const float* b_returns, const float* b_values,
+                                    int64_t n_minibatch, const int64_t* mb_inds, const float* rpo_noise_or_null,
+                                    uint64_t seed, uint64_t draw_counter,
+                                    const evac_mlp_policy_grads_t* grads_out, const evac_transformer_grads_t* encoder_grads_out,
+                                    float* stats_out, void* workspace, void* stream);
+
 /* ---- The optimiser step: rpo_agent.py:278-279, clip_grad_norm_(max_grad_norm) and Adam(lr, eps = 1e-5).step(), on the device ----
  * Adam as torch.optim.Adam with betas, no weight decay, no amsgrad.  All in float32, EVERY OPERATION ROUNDED ON ITS OWN (no fused
  * multiply-add, IEEE division, correctly rounded sqrt), except the three scalars marked double, formed in double and rounded

@@ -1,0 +1,249 @@
+"""What the tests of the transformer leader's gradient (tests/test_transformer_grad_cpu.py, tests/test_gpu_transformer_grad.py)
+build: the yardstick and the branch-covering minibatch case.
+
+The yardstick is the reference's minibatch loss on the module in a given dtype through torch autograd: tests/trainer_ref.py's
+``loss_terms`` fed y = ``net.embedding(x)`` of a copy of the network in that dtype, the encoder run over chunks of rows (its
+score tensors are [rows, d_model, tokens, tokens]) and differentiated in two stages: the loss with respect to y, then every
+chunk's y with respect to the encoder's tensors.  It runs in float64 (the truth) and in float32 (whose error against float64
+sets every bound), on the device the batch is on."""
+import copy
+from types import SimpleNamespace
+
+from tests import trainer_ref as R
+
+DEV = "cuda:0"
+BLOCK_NAMES = ("wq", "bq", "wk", "bk", "wv", "bv", "dense_w", "dense_b", "ff1_w", "ff1_b", "ff2_w", "ff2_b", "norm1_w", "norm1_b",
+               "norm2_w", "norm2_b")
+RELU_MARGIN = 1e-5
+VARIANCE_FLOOR = 1e-4
+ROWS = 1024
+
+
+def names(blocks):
+    return R.NAMES + tuple(f"blocks[{b}].{n}" for b in range(blocks) for n in BLOCK_NAMES)
+
+
+def key_biases(blocks):
+    """The indices of `attention.Wk.bias` among the tensors: their exact gradient is zero."""
+    return [13 + 16 * b + 3 for b in range(blocks)]
+
+
+VANISHING = 1e-12
+
+
+def gradient_scales(g64, blocks):
+    """Per tensor the scale its error is divided by: its own largest float64 gradient; for a key bias (exact gradient zero) its
+    weight's.  A scale below ``VANISHING`` = 1e-12 of the case's largest gradient is no scale: float64 itself (2.2e-16 per
+    operation, sums of 1e4 to 1e6 terms that are themselves differences) does not resolve a gradient twelve orders below the
+    quantities it is computed from, so what float64 holds there is the rounding of a zero -- with two channels LayerNorm's output
+    is +-1 whatever its input and everything behind two of them vanishes.  Such a tensor is held against the case's largest
+    gradient instead, like the key biases against their weights.  Returns (scales, the case's largest gradient)."""
+    own = [float(g.abs().max()) for g in g64]
+    top = max(own)
+    scales = [own[i - 1] if i in key_biases(blocks) else own[i] for i in range(len(own))]
+    return [s if s >= VANISHING * top else top for s in scales], top
+
+
+def assert_key_biases_are_zero(g64, blocks):
+    """Float64 finds the zero of `attention.Wk.bias`: what it leaves is the rounding of a sum of M x tokens cancelling terms, each
+    up to 1 / |x| times a term of the weight's gradient -- 2.2e-16 times the terms' scale times the square root of their number
+    (at most 2048 x 64 here), so 1e-9 of the weight's largest gradient holds with three orders to spare, and is seven orders
+    below what float32 leaves.  Where the weight's own gradient vanishes (``gradient_scales``) the bias's vanishes with it."""
+    own = [float(g.abs().max()) for g in g64]
+    top = max(own)
+    for i in key_biases(blocks):
+        limit = 1e-9 * own[i - 1] if own[i - 1] >= VANISHING * top else VANISHING * top
+        assert own[i] <= limit, (i, own[i], limit)
+
+
+def all_tensors(net):
+    from evacuation_amd.policy import all_tensors as f
+    return f(net)
+
+
+def twin_of(net, dtype, device=None):
+    """A copy of the network in ``dtype`` (without what the trainer's entries keep on the module: addresses and a workspace)."""
+    state = getattr(net, "_evac_grad_state", None)
+    twin = copy.deepcopy(net, {} if state is None else {id(state): None})
+    return twin.to(dtype=dtype, device=device)
+
+
+def minibatch_grad(net, batch, mb_inds, cfg, z, dtype=None, rows=ROWS):
+    """Gradients of the 13 + 16 per block tensors (list, ``names`` order) and the 8 statistics of one minibatch, everything cast to
+    ``dtype`` (float32 by default) first, by autograd."""
+    import torch
+    dtype = dtype or torch.float32
+    twin = twin_of(net, dtype)
+    P = list(all_tensors(twin))
+    for p in P:
+        p.grad = None
+    gathered = {k: v[mb_inds].to(dtype) for k, v in batch.items()}
+    x = gathered["b_obs"]
+    M = x.shape[0]
+    with torch.no_grad():
+        y = torch.cat([twin.embedding(x[i:i + rows]) for i in range(0, M, rows)])
+    y.requires_grad_(True)
+    gathered["b_obs"] = y
+    head = [p.detach().clone().requires_grad_(True) for p in P[:13]]
+    t = R.loss_terms(head, gathered, torch.arange(M, device=mb_inds.device), cfg, z.to(dtype))
+    g_head = torch.autograd.grad(t.loss, head + [y])
+    dy = g_head[13]
+    g_enc = [torch.zeros_like(p) for p in P[13:]]
+    for i in range(0, M, rows):
+        part = torch.autograd.grad(twin.embedding(x[i:i + rows]), P[13:], dy[i:i + rows])
+        for g, p in zip(g_enc, part):
+            g += p
+    grads = list(g_head[:13]) + g_enc
+    sumsq = sum((g.double() ** 2).sum() for g in grads).to(dtype)
+    stats = torch.stack([t.loss.detach(), t.pg_loss.detach(), t.v_loss.detach(), t.entropy.detach(), t.old_approx_kl, t.approx_kl,
+                         t.clipfrac, sumsq])
+    return grads, stats, t
+
+
+def make_net(N, ed, blocks, use_resid, seed=0, device=DEV):
+    """A transformer leader with visible means and values (tests/trainer_cases.make_net): the actor's head x 40, two different
+    sigmas, non-zero biases, and LayerNorm weights and biases away from 1 and 0 as tests/test_transformer_cpu.py draws them."""
+    import torch
+    from evacuation_amd.policy import TransformerActorCritic
+    torch.manual_seed(seed)
+    net = TransformerActorCritic((N + 2) * ed, N, num_blocks=blocks, use_resid=use_resid)
+    with torch.no_grad():
+        net.actor_mean[4].weight.mul_(40.0)
+        net.actor_logstd.copy_(torch.tensor([[-0.4, 0.2]]))
+        for seq in (net.actor_mean, net.critic):
+            for i in (0, 2, 4):
+                seq[i].bias.uniform_(-0.2, 0.2)
+        for m in net.embedding.modules():
+            if isinstance(m, torch.nn.LayerNorm):
+                m.weight.uniform_(0.5, 1.5)
+                m.bias.normal_(0.0, 0.3)
+    return net.to(device)
+
+
+def internals(net64, obs, rows=ROWS):
+    """Of the float64 copy ``net64`` on observations obs [B, D], over all blocks: per row the smallest |feed-forward
+    pre-activation| and the smallest LayerNorm input variance, and the encoded rows y."""
+    import torch
+    pre_min, var_min, ys = [], [], []
+    with torch.no_grad():
+        for i in range(0, obs.shape[0], rows):
+            x = obs[i:i + rows]
+            x = x.view(x.shape[0], -1, net64.token_dim)
+            pm = torch.full((x.shape[0],), float("inf"), dtype=x.dtype, device=x.device)
+            vm = pm.clone()
+            for blk in net64.embedding:
+                a = blk.attention(x)
+                r1 = x + a if blk.use_resid else a
+                u = blk.norm1(r1)
+                pre = blk.ff[0](u)
+                f = blk.ff[3](torch.relu(pre))
+                r2 = u + f if blk.use_resid else f
+                x = blk.norm2(r2)
+                pm = torch.minimum(pm, pre.abs().flatten(1).min(dim=1).values)
+                for r in (r1, r2):
+                    vm = torch.minimum(vm, r.var(dim=-1, unbiased=False).min(dim=1).values)
+            pre_min.append(pm)
+            var_min.append(vm)
+            ys.append(x.flatten(1))
+    return torch.cat(pre_min), torch.cat(var_min), torch.cat(ys)
+
+
+_CASES = {}
+
+
+def build_case(N, ed, M, blocks, use_resid, mode, cfg, seed, device=DEV, cache=True):
+    """tests/deepsets_grad_cases.build_case's recipe behind the attention encoder: a batch whose minibatch takes every branch of the
+    loss by a known share of its samples -- old log-probabilities and values set FROM the float64 forward pass (half of the rows
+    inside each clip range, a quarter above, a quarter below), no sample within 1e-6 of a branch point of max / clamp -- and
+
+    * no batch row with a feed-forward pre-activation within 1e-5 of 0 in float64, in any block;
+    * every LayerNorm input variance >= 1e-4 in float64 (the kernels' own precondition: below it eps = 1e-5 stops being small
+      against the variance and float32 rounding is amplified by 1 / sqrt(variance)).
+
+    Rows that miss either are redrawn, at most 8 rounds, then both are asserted: change the seed, never the bound.  (Redrawing
+    for the variance as well is for the batch of 33 795 rows, 1.6 million LayerNorm inputs of 3 values: a handful of its rows
+    fall under the floor with every seed tried; the cases of up to 2 048 rows clear it as drawn.  The counts are returned.)
+    Returns (net, batch, inds, z, the float64 gradients, the 8 float64 statistics, the yardstick's terms with ``pre_min`` and
+    ``var_min`` -- the batch's smallest |pre-activation| and variance -- and ``rows``, ``redrawn_relu``, ``redrawn_variance``:
+    the batch's rows and how many were redrawn for either cause, over all rounds).
+    ``cache``: the case is built once per process and shared (nobody changes it)."""
+    import torch
+    key = (N, ed, M, blocks, use_resid, mode, cfg.norm_adv, cfg.clip_vloss, cfg.ent_coef, cfg.rpo_alpha, cfg.clip_coef, cfg.vf_coef,
+           seed, str(device))
+    if cache and key in _CASES:
+        return _CASES[key]
+    c = cfg.clip_coef
+    D = (N + 2) * ed
+    for attempt in range(8):
+        g = torch.Generator().manual_seed(seed + 1000 * attempt)
+        net = make_net(N, ed, blocks, use_resid, seed=seed, device=device)
+        net64 = twin_of(net, torch.float64, "cpu")
+        B = max(M, 4) if mode == "repeat" else 2 * M + 3
+        inds = torch.randint(0, B, (M,), generator=g) if mode == "repeat" else torch.arange(M) * 2 + 1
+        obs = (0.6 * torch.randn(B, D, generator=g)).clamp(-1, 1)
+        redrawn_relu = redrawn_variance = 0
+        for _ in range(8):                                                # the relu's branch point, the variance floor
+            pre_min, var_min, _ = internals(net64, obs.double())
+            near = (pre_min < RELU_MARGIN) | (var_min < VARIANCE_FLOOR)
+            n = int(near.sum())
+            redrawn_relu += int((pre_min < RELU_MARGIN).sum())
+            redrawn_variance += int((var_min < VARIANCE_FLOOR).sum())
+            if n == 0:
+                break
+            obs[near] = (0.6 * torch.randn(n, D, generator=g)).clamp(-1, 1)
+        pre_min, var_min, y64 = internals(net64, obs.double())
+        assert float(pre_min.min()) >= RELU_MARGIN, "rows at the relu's branch point after 8 rounds"
+        assert float(var_min.min()) >= VARIANCE_FLOOR, f"a LayerNorm input variance of {float(var_min.min()):.3g}"
+        P = [p.detach() for p in all_tensors(net64)]
+        act = torch.randn(B, 2, generator=g)
+        z = (torch.rand(M, 2, generator=g) * 2 - 1) * cfg.rpo_alpha
+        # the float64 forward pass of every batch row, with the perturbation of the LAST minibatch position that reads the row
+        zrow = torch.zeros(B, 2)
+        zrow[inds] = z
+        lp, _, val = R.logprob_entropy_value(P[:13], y64, act.double(), zrow.double())
+        u = torch.rand(B, generator=g)
+        mag = 0.25 + 0.35 * torch.rand(B, generator=g)                                    # |log ratio| in [0.25, 0.6]: ratio <= 0.78 or >= 1.28
+        inside = (0.05 * torch.randn(B, generator=g)).clamp(-0.12, 0.12)
+        target = torch.where(u < 0.5, inside, torch.where(u < 0.75, mag, -mag))
+        logprobs = (lp - target.double()).float()
+        u2 = torch.rand(B, generator=g)
+        mag2 = c * (1.25 + torch.rand(B, generator=g))
+        inside2 = c * (0.3 * torch.randn(B, generator=g)).clamp(-0.8, 0.8)
+        dv = torch.where(u2 < 0.5, inside2, torch.where(u2 < 0.75, mag2, -mag2))
+        values = (val.view(-1) - dv.double()).float()
+        returns = (val.view(-1) + 0.7 * torch.randn(B, generator=g).double()).float()
+        adv = torch.randn(B, generator=g) + 0.3
+        batch = {"b_obs": obs, "b_actions": act, "b_logprobs": logprobs, "b_advantages": adv, "b_returns": returns, "b_values": values}
+        batch = {k: v.to(device).contiguous() for k, v in batch.items()}
+        inds, z = inds.to(device), z.to(device).contiguous()
+        g64, s64, t = minibatch_grad(net, batch, inds, cfg, z, torch.float64)
+        near = ((t.ratio - (1 - c)).abs() < 1e-6) | ((t.ratio - (1 + c)).abs() < 1e-6) | (t.adv.abs() < 1e-6)
+        near |= ((t.dv.abs() - c).abs() < 1e-6)
+        if cfg.clip_vloss:
+            near |= ((t.dv.abs() > c) & ((t.v_unclipped - t.v_clipped).abs() < 1e-6))
+        if not bool(near.any()):
+            t.pre_min, t.var_min = float(pre_min.min()), float(var_min.min())
+            t.rows, t.redrawn_relu, t.redrawn_variance = B, redrawn_relu, redrawn_variance
+            out = (net, batch, inds, z, g64, s64, t)
+            if cache:
+                _CASES[key] = out
+            return out
+    raise AssertionError("could not build a case without samples at a branch point")
+
+
+def kernel_grad(net, batch, inds, cfg, z, **kw):
+    import torch
+    from evacuation_amd import trainer
+    stats = trainer.transformer_minibatch_grad(net, batch, inds, cfg, rpo_noise=z, **kw)
+    torch.cuda.synchronize()
+    return [p.grad.clone() for p in all_tensors(net)], stats.clone()
+
+
+def fake_trainer(net, cfg):
+    return SimpleNamespace(net=net, cfg=cfg)
+
+
+def tensor_errors(got, g64, blocks):
+    """Per tensor max|g - g64| / scale, the scales of ``gradient_scales``."""
+    scales, _ = gradient_scales(g64, blocks)
+    return [float((g.double() - r).abs().max()) / s for g, r, s in zip(got, g64, scales)]

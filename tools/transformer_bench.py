@@ -3,6 +3,7 @@
 replaces.
 
     python tools/transformer_bench.py --part a|b|c|c-eager [--envs 4096] [--steps 128] [--blocks 2] [--use-resid] [--reps 7]
+    python tools/transformer_bench.py --part grad-autograd|grad-device [--minibatch 16384] [--blocks 2] [--use-resid] [--reps 7]
 
 N = 60, the rel + ohe Box observation (D = 372, 62 tokens of 6), the trainer's normalisation chain, E envs, T steps per call;
 hipEvent times of whole calls after two warm-up calls, median and range of ``--reps`` calls, one JSON line:
@@ -11,6 +12,10 @@ hipEvent times of whole calls after two warm-up calls, median and range of ``--r
   c        what b replaces: per step the module's torch forward (``get_action_and_value``, written out) and ``step(out_*=)`` into the
            trainer's storage, the T steps captured into a graph once and replayed (as examples/rollout_with_policy.py)
   c-eager  the same loop launched step by step
+  grad-autograd  one minibatch gradient of the 13 + 16 per block tensors by ``trainer.autograd_minibatch_grad`` (torch autograd on
+           the module): M = ``--minibatch`` samples of a batch of 2 M observations drawn as 0.6 randn clamped to +-1, no env
+  grad-device    the same gradient by ``trainer.transformer_minibatch_grad`` (``evac_transformer_minibatch_grad``: 5 + blocks +
+           norm_adv launches)
 One part per process, so that a job script can give each its own time limit."""
 import argparse
 import json
@@ -38,15 +43,54 @@ def event_ms(fn):
     return a.elapsed_time(b)
 
 
+def grad_part(args):
+    """One minibatch gradient at N = 60, rel + ohe Box (D = 372): hipEvent median and range after warm-up, one JSON line."""
+    from types import SimpleNamespace
+    from evacuation_amd import trainer
+    D, M = (N_PED + 2) * 6, args.minibatch
+    B = 2 * M
+    torch.manual_seed(0)
+    net = TransformerActorCritic(D, N_PED, num_blocks=args.blocks, use_resid=args.use_resid).to(DEV)
+    g = torch.Generator(device=DEV).manual_seed(1)
+    rand = lambda *shape: torch.randn(*shape, device=DEV, generator=g)
+    batch = {"b_obs": (0.6 * rand(B, D)).clamp(-1, 1), "b_actions": rand(B, 2), "b_logprobs": -2.0 + 0.3 * rand(B),
+             "b_advantages": rand(B), "b_returns": rand(B), "b_values": rand(B)}
+    inds = torch.randperm(B, device=DEV, generator=g)[:M].contiguous()
+    z = (torch.rand(M, 2, device=DEV, generator=g) * 2 - 1) * 0.5
+    cfg = trainer.RPOTrainingConfig()
+    stats = torch.zeros(8, device=DEV)
+    if args.part == "grad-device":
+        def run():
+            trainer.transformer_minibatch_grad(net, batch, inds, cfg, rpo_noise=z, stats=stats)
+        launches = 5 + args.blocks + int(cfg.norm_adv)
+    else:
+        fake = SimpleNamespace(net=net, cfg=cfg)
+
+        def run():
+            trainer.autograd_minibatch_grad(fake, batch, inds, z, 0, stats)
+        launches = None
+    for _ in range(3):
+        run()
+    torch.cuda.synchronize()
+    ms = [event_ms(run) for _ in range(max(5, args.reps))]
+    med = statistics.median(ms)
+    print(json.dumps({"part": args.part, "minibatch": M, "obs_dim": D, "blocks": args.blocks, "use_resid": bool(args.use_resid),
+                      "ms_per_call_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
+                      "launches": launches, "loss": round(float(stats[0]), 6), "grad_sumsq": float(stats[7]), "calls": len(ms)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", required=True, choices=["a", "b", "c", "c-eager"])
+    ap.add_argument("--part", required=True, choices=["a", "b", "c", "c-eager", "grad-autograd", "grad-device"])
+    ap.add_argument("--minibatch", type=int, default=16384)
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--blocks", type=int, default=2)
     ap.add_argument("--use-resid", action="store_true")
     ap.add_argument("--reps", type=int, default=7)
     args = ap.parse_args()
+    if args.part.startswith("grad-"):
+        return grad_part(args)
     E, T = args.envs, args.steps
     env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=N_PED), ea.EnvWrappersConfig(positions="rel", statuses="ohe", type="Box"),
                                       num_envs=E, gamma=0.99, seed=1)
