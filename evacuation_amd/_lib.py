@@ -151,6 +151,15 @@ class EvacError(RuntimeError):
 
 # Every symbol include/evac.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
+
+
+def _grad_args(*encoder) -> list:
+    """evac_rpo_minibatch_grad's arguments; with ``encoder`` = (its struct, its gradients' struct) an encoder's entry's."""
+    enc, enc_grads = ([C.POINTER(s)] for s in encoder) if encoder else ([], [])
+    return [C.POINTER(EvacMlpPolicy), *enc, C.POINTER(EvacRpoLossConfig), C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_uint64,
+            C.c_uint64, C.POINTER(EvacMlpPolicyGrads), *enc_grads, _P, _P, _P]
+
+
 SIGNATURES = {
     "evac_version": (C.c_int, []),
     "evac_status_string": (C.c_char_p, [C.c_int]),
@@ -203,22 +212,17 @@ SIGNATURES = {
        for what, front in (("rollout", [_P, C.c_int32, C.POINTER(EvacMlpPolicy)] + [_P] * 11 + [C.c_float] * 4),
                            ("evaluate", [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float]))},
     "evac_gae": (C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
-    "evac_rpo_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
-    "evac_rpo_minibatch_grad": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacRpoLossConfig), C.c_int64, _P, _P, _P, _P, _P, _P,
-                                          C.c_int64, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(EvacMlpPolicyGrads), _P, _P, _P]),
-    "evac_deepsets_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
-    "evac_deepsets_minibatch_grad": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacDeepSets), C.POINTER(EvacRpoLossConfig), C.c_int64,
-                                               _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_uint64,
-                                               C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads), _P, _P, _P]),
-    "evac_transformer_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
-    "evac_transformer_minibatch_grad": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacTransformer), C.POINTER(EvacRpoLossConfig), C.c_int64,
-                                                  _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_uint64,
-                                                  C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacTransformerGrads), _P, _P, _P]),
+    # the gradient entries: the linear network's, and an encoder's with its struct after the policy and its gradients' after the
+    # policy's; a step has the optimiser's arguments behind the gradient's
+    **{f"evac_{kind}_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]) for kind in ("rpo", "deepsets", "transformer")},
+    "evac_rpo_minibatch_grad": (C.c_int, _grad_args()),
+    "evac_deepsets_minibatch_grad": (C.c_int, _grad_args(EvacDeepSets, EvacDeepSetsGrads)),
+    "evac_transformer_minibatch_grad": (C.c_int, _grad_args(EvacTransformer, EvacTransformerGrads)),
+    "evac_rpo_minibatch_step": (C.c_int, _grad_args() + [C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacAdamState), C.POINTER(EvacAdamConfig)]),
+    "evac_deepsets_minibatch_step": (C.c_int, _grad_args(EvacDeepSets, EvacDeepSetsGrads) + [
+        C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads), C.POINTER(EvacDeepSetsAdamState), C.POINTER(EvacAdamConfig)]),
     "evac_adam_step": (C.c_int, [C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacAdamState),
                                  C.POINTER(EvacAdamConfig), C.c_int32, _P, _P]),
-    "evac_rpo_minibatch_step": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacRpoLossConfig), C.c_int64, _P, _P, _P, _P, _P, _P,
-                                          C.c_int64, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(EvacMlpPolicyGrads), _P, _P, _P,
-                                          C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacAdamState), C.POINTER(EvacAdamConfig)]),
     "evac_rpo_update": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacMlpPolicyGrads),
                                   C.POINTER(EvacRpoLossConfig), C.POINTER(EvacAdamConfig), C.POINTER(EvacAdamState), C.c_int64,
                                   _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, C.c_uint64, C.c_uint64, C.c_int32,
@@ -226,11 +230,6 @@ SIGNATURES = {
     "evac_deepsets_adam_step": (C.c_int, [C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads), C.POINTER(EvacMlpPolicyGrads),
                                           C.POINTER(EvacDeepSetsGrads), C.POINTER(EvacDeepSetsAdamState), C.POINTER(EvacAdamConfig),
                                           C.c_int32, C.c_int32, _P, _P]),
-    "evac_deepsets_minibatch_step": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacDeepSets), C.POINTER(EvacRpoLossConfig), C.c_int64,
-                                               _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_uint64,
-                                               C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads), _P, _P, _P,
-                                               C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads),
-                                               C.POINTER(EvacDeepSetsAdamState), C.POINTER(EvacAdamConfig)]),
     "evac_deepsets_update": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacDeepSets), C.POINTER(EvacMlpPolicyGrads),
                                        C.POINTER(EvacDeepSetsGrads), C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads),
                                        C.POINTER(EvacRpoLossConfig), C.POINTER(EvacAdamConfig), C.POINTER(EvacDeepSetsAdamState),

@@ -1,8 +1,8 @@
 // Host side of the deep-sets leader's gradient (include/evac.h: evac_deepsets_workspace_bytes, evac_deepsets_minibatch_grad;
 // kernels in evac_deepsets_train.h and, launched as they are, evac_train.h's k_rpo_*<>; the checks, the workspace's layout and the
-// launches in evac_deepsets_train_host.h): six launches.  No handle: errors come back through the return code alone and every
-// refusal comes before the first HIP call.  No device allocation, no synchronisation: the call only enqueues work on the
-// caller's stream.
+// launches in evac_deepsets_train_host.h's SetGrad, the entry's body in evac_encoder_train_host.h): six launches.  No handle:
+// errors come back through the return code alone and every refusal comes before the first HIP call.  No device allocation, no
+// synchronisation: the call only enqueues work on the caller's stream.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -13,8 +13,7 @@
 extern "C" {
 
 int64_t evac_deepsets_workspace_bytes(int32_t obs_dim, int64_t n_minibatch) {
-    if (evac_rpo_workspace_bytes(obs_dim, n_minibatch) < 0) return EVAC_ERR_INVALID_ARGUMENT;
-    return set_layout(obs_dim, n_minibatch).total;
+    return encoder_workspace_bytes<SetGrad>(obs_dim, n_minibatch);
 }
 
 int evac_deepsets_minibatch_grad(const evac_mlp_policy_t* policy, const evac_deepsets_t* encoder, const evac_rpo_loss_config_t* cfg,
@@ -23,19 +22,9 @@ int evac_deepsets_minibatch_grad(const evac_mlp_policy_t* policy, const evac_dee
                                  const int64_t* mb_inds, const float* rpo_noise, uint64_t seed, uint64_t draw_counter,
                                  const evac_mlp_policy_grads_t* grads_out, const evac_deepsets_grads_t* encoder_grads_out,
                                  float* stats_out, void* workspace, void* stream) {
-    evac::RpoArgs a;
-    evac::SetArgs s;
-    if (const int rc = deepsets_prepare(policy, encoder, cfg, batch_size, b_obs, b_actions, b_logprobs, b_advantages, b_returns, b_values,
-                                        n_minibatch, mb_inds, rpo_noise, seed, grads_out, encoder_grads_out, stats_out, workspace, a, s);
-        rc != EVAC_OK)
-        return rc;
-    rpo_shape(a, n_minibatch, draw_counter);
-    const evac::RpoArgs inner = deepsets_step(a, s);
-    const int dev = device_of(workspace);
-    DeviceGuard g(dev);
-    if (rpo_raise_lds<evac::k_rpo_grad<>>(a.D, dev) != EVAC_OK) return EVAC_ERR_HIP;
-    deepsets_launch(inner, s, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? EVAC_OK : EVAC_ERR_HIP;
+    return encoder_minibatch_grad<SetGrad>(policy, encoder, cfg, batch_size, b_obs, b_actions, b_logprobs, b_advantages, b_returns,
+                                           b_values, n_minibatch, mb_inds, rpo_noise, seed, draw_counter, grads_out, encoder_grads_out,
+                                           stats_out, workspace, stream);
 }
 
 }  // extern "C"

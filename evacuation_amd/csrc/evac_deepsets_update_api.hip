@@ -1,7 +1,8 @@
 // Host side of the deep-sets leader's optimiser step and whole update (include/evac.h: evac_deepsets_adam_step,
 // evac_deepsets_minibatch_step, evac_deepsets_update; k_adam_set in evac_deepsets_adam.h, the gradient's kernels in
 // evac_deepsets_train.h and evac_train.h, plain for the step and gated by the optimiser's header for the update).  The checks are
-// rpo_prepare's, deepsets_prepare's and adam_prepare's, the walk over an update's steps is rpo_update_steps.  No handle: errors
+// rpo_prepare's, SetGrad's and adam_prepare's, the step's body is encoder_minibatch_grad's with the optimiser behind it, the walk
+// over an update's steps is rpo_update_steps.  No handle: errors
 // come back through the return code alone and every refusal comes before the first HIP call.  No device allocation, no
 // synchronisation: every call only enqueues work on the caller's stream.
 #include <hip/hip_runtime.h>
@@ -90,28 +91,18 @@ int evac_deepsets_minibatch_step(const evac_mlp_policy_t* policy, const evac_dee
                                  float* stats_out, void* workspace, void* stream, const evac_mlp_policy_grads_t* params,
                                  const evac_deepsets_grads_t* enc_params, const evac_deepsets_adam_state_t* state,
                                  const evac_adam_config_t* adam_cfg) {
-    evac::RpoArgs a;
-    evac::SetArgs s;
-    if (const int rc = deepsets_prepare(policy, encoder, cfg, batch_size, b_obs, b_actions, b_logprobs, b_advantages, b_returns, b_values,
-                                        n_minibatch, mb_inds, rpo_noise, seed, grads_out, encoder_grads_out, stats_out, workspace, a, s);
-        rc != EVAC_OK)
-        return rc;
     evac::AdamArgs o;
     evac::SetAdamArgs q;
-    if (const int rc = set_adam_prepare(params, enc_params, grads_out, encoder_grads_out, state, adam_cfg, policy->obs_dim,
-                                        encoder->set_elem_dim, o, q);
-        rc != EVAC_OK)
-        return rc;
-    q.sumsq = stats_out + 7;
-    rpo_shape(a, n_minibatch, draw_counter);
-    const evac::RpoArgs inner = deepsets_step(a, s);
-    const int dev = device_of(workspace);
-    DeviceGuard g(dev);
-    if (rpo_raise_lds<evac::k_rpo_grad<>>(a.D, dev) != EVAC_OK) return EVAC_ERR_HIP;
-    hipStream_t S = (hipStream_t)stream;
-    deepsets_launch(inner, s, S);
-    set_adam_launch(q, S);
-    return hipGetLastError() == hipSuccess ? EVAC_OK : EVAC_ERR_HIP;
+    return encoder_minibatch_grad<SetGrad>(
+        policy, encoder, cfg, batch_size, b_obs, b_actions, b_logprobs, b_advantages, b_returns, b_values, n_minibatch, mb_inds, rpo_noise,
+        seed, draw_counter, grads_out, encoder_grads_out, stats_out, workspace, stream,
+        [&] {                                                                  // (behind the gradient's checks: policy and encoder are set)
+            const int rc = set_adam_prepare(params, enc_params, grads_out, encoder_grads_out, state, adam_cfg, policy->obs_dim,
+                                            encoder->set_elem_dim, o, q);
+            if (rc == EVAC_OK) q.sumsq = stats_out + 7;
+            return rc;
+        },
+        [&q](hipStream_t S) { set_adam_launch(q, S); });
 }
 
 int evac_deepsets_update(const evac_mlp_policy_t* policy, const evac_deepsets_t* encoder, const evac_mlp_policy_grads_t* params,
@@ -125,8 +116,9 @@ int evac_deepsets_update(const evac_mlp_policy_t* policy, const evac_deepsets_t*
     if (n_epochs < 1) return EVAC_ERR_INVALID_ARGUMENT;
     evac::RpoArgs a;
     evac::SetArgs s;
-    if (const int rc = deepsets_prepare(policy, encoder, loss_cfg, batch_size, b_obs, b_actions, b_logprobs, b_advantages, b_returns,
-                                        b_values, n_minibatch, perms, rpo_noise, seed, grads, enc_grads, stats_out, workspace, a, s);
+    if (const int rc = encoder_grad_prepare<SetGrad>(policy, encoder, loss_cfg, batch_size, b_obs, b_actions, b_logprobs, b_advantages,
+                                                     b_returns, b_values, n_minibatch, perms, rpo_noise, seed, grads, enc_grads, stats_out,
+                                                     workspace, a, s);
         rc != EVAC_OK)
         return rc;
     evac::AdamArgs o;
@@ -148,9 +140,9 @@ int evac_deepsets_update(const evac_mlp_policy_t* policy, const evac_deepsets_t*
     }
     rpo_update_steps(a, o, batch_size, n_minibatch, n_epochs, perms, rpo_noise, stats_out, first_draw_counter,
                      [&s, &q, S](const evac::RpoArgs& step, const evac::AdamArgs& adam, uint64_t) {
-                         const evac::RpoArgs inner = deepsets_step(step, s);
+                         const evac::RpoArgs inner = encoder_grad_step<SetGrad>(step, s);
                          set_adam_scalars(adam, q);
-                         deepsets_launch(inner, s, S, (const evac::AdamHeader*)adam.hdr);
+                         SetGrad::launch(inner, s, S, (const evac::AdamHeader*)adam.hdr);
                          set_adam_launch(q, S);
                      });
     return hipGetLastError() == hipSuccess ? EVAC_OK : EVAC_ERR_HIP;

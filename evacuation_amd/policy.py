@@ -397,16 +397,26 @@ def _transformer_struct(found, ts) -> _lib.EvacTransformer:
     return st
 
 
+def _transformer_grads(*ptrs) -> _lib.EvacTransformerGrads:
+    """``evac_transformer_grads_t`` of 16 addresses per block (the blocks the network does not have stay NULL: they are never
+    followed)."""
+    st = _lib.EvacTransformerGrads()
+    for b in range(len(ptrs) // 16):
+        st.blocks[b] = _lib.EvacTransformerBlockGrads(*ptrs[16 * b:16 * b + 16])
+    return st
+
+
 # One kind of encoder in front of the actor-critic: the attribute that marks such a network, the suffix of its C entries
-# (evac_policy_rollout + suffix, evac_policy_evaluate + suffix), its parameter tensors in its struct's order,
-# check(net, obs_dim, device, n_ped) -> what struct(found, tensors) builds the C struct from, and what a binder's key holds beside
-# the tensors (None: nothing; `use_resid` is no tensor, so it is read at every call).  The kinds in order of precedence.
-EncoderKind = namedtuple("EncoderKind", "attr suffix tensors check struct key")
+# (evac_policy_rollout + suffix, evac_policy_evaluate + suffix; "evac" + suffix + _workspace_bytes, _minibatch_grad), its
+# parameter tensors in its struct's order, check(net, obs_dim, device, n_ped) -> what struct(found, tensors) builds the C struct
+# from, what a binder's key holds beside the tensors (None: nothing; `use_resid` is no tensor, so it is read at every call), and
+# grads(*addresses of the tensors' .grad) -> the C struct of its gradients.  The kinds in order of precedence.
+EncoderKind = namedtuple("EncoderKind", "attr suffix tensors check struct key grads")
 ENCODER_KINDS = (
     EncoderKind("embedding", "_transformer", transformer_tensors, _check_transformer, _transformer_struct,
-                lambda net: tuple(bool(getattr(b, "use_resid", False)) for b in net.embedding)),
+                lambda net: tuple(bool(getattr(b, "use_resid", False)) for b in net.embedding), _transformer_grads),
     EncoderKind("deep_sets", "_deepsets", deepsets_tensors, _check_encoder,
-                lambda ed, ts: _lib.EvacDeepSets(ed, SET_HIDDEN, *[t.data_ptr() for t in ts]), None))
+                lambda ed, ts: _lib.EvacDeepSets(ed, SET_HIDDEN, *[t.data_ptr() for t in ts]), None, _lib.EvacDeepSetsGrads))
 _TRANSFORMER, _DEEP_SETS = ENCODER_KINDS
 
 

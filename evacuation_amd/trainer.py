@@ -17,8 +17,8 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from .policy import (PolicyBinder, all_tensors, deepsets_tensors, encode_observation, encoder_kind, is_deepsets, is_transformer,
-                     mlp_tensors, refuse_deepsets, refuse_dropout, refuse_transformer, transformer_tensors)
+from .policy import (PolicyBinder, all_tensors, encode_observation, encoder_kind, is_deepsets, is_transformer, mlp_tensors,
+                     refuse_deepsets, refuse_dropout, refuse_transformer)
 from .vector_env import STATS_FIELDS, _ptr
 
 STAT_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "grad_sumsq")
@@ -140,8 +140,7 @@ class _GradState:
 
     def __init__(self):
         self.binder, self.grads, self.workspace = None, [None, None], None
-        self.encoder_grads = [None, None]                                    # deepsets_minibatch_grad's
-        self.transformer_grads = [None, None]                                # transformer_minibatch_grad's
+        self.encoder_grads = [None, None]                                    # the encoder's own entries' (ensure_encoder_grads)
 
 
 def _grad_state(net) -> _GradState:
@@ -163,30 +162,25 @@ def ensure_grads(net) -> "_lib.EvacMlpPolicyGrads":
     return _tensor_struct(_grad_state(net).grads, [t.grad for t in ts])
 
 
-def ensure_encoder_grads(net) -> "_lib.EvacDeepSetsGrads":
-    """``ensure_grads`` for the set encoder's six tensors: the addresses of their ``.grad`` as ``evac_deepsets_grads_t``."""
+def ensure_encoder_grads(net):
+    """``ensure_grads`` for the tensors of the encoder of ``net`` (``encoder_kind``): the addresses of their ``.grad`` as
+    ``evac_deepsets_grads_t`` (the set encoder's six) or ``evac_transformer_grads_t`` (the attention encoder's 16 per block; the
+    blocks the network does not have stay NULL: they are never followed)."""
     ensure_grads(net)
-    return _tensor_struct(_grad_state(net).encoder_grads, [t.grad for t in deepsets_tensors(net)], _lib.EvacDeepSetsGrads)
+    kind = encoder_kind(net)
+    return _tensor_struct(_grad_state(net).encoder_grads, [t.grad for t in kind.tensors(net)], kind.grads)
 
 
-def ensure_transformer_grads(net) -> "_lib.EvacTransformerGrads":
-    """``ensure_grads`` for the attention encoder's 16 tensors per block: the addresses of their ``.grad`` as
-    ``evac_transformer_grads_t`` (the blocks the network does not have stay NULL: they are never followed)."""
-    ensure_grads(net)
-
-    def struct(*ptrs):
-        st = _lib.EvacTransformerGrads()
-        for b in range(len(ptrs) // 16):
-            st.blocks[b] = _lib.EvacTransformerBlockGrads(*ptrs[16 * b:16 * b + 16])
-        return st
-    return _tensor_struct(_grad_state(net).transformer_grads, [t.grad for t in transformer_tensors(net)], struct)
+def _entry_name(kind, what: str) -> str:
+    """``evac_rpo_<what>``, or for a row of ``ENCODER_KINDS`` ``evac_deepsets_<what>`` / ``evac_transformer_<what>``."""
+    return f"evac{'_rpo' if kind is None else kind.suffix}_{what}"
 
 
-def _batch_args(net, batch: Dict[str, torch.Tensor], deepsets: bool = False):
+def _batch_args(net, batch: Dict[str, torch.Tensor], own_encoder_entry: bool = False):
     """The checks every gradient entry makes of ``batch``; returns (B, D, device, state, evac_mlp_policy_t, grads struct, the
-    entries' arguments ``batch_size, b_obs .. b_values``).  ``deepsets``: the caller is an encoder's own entry (the set encoder's,
-    or the attention encoder's)."""
-    if not deepsets:
+    entries' arguments ``batch_size, b_obs .. b_values``).  ``own_encoder_entry``: the caller is an encoder's own entry (the set
+    encoder's, or the attention encoder's), not the linear network's, which refuses a network with either."""
+    if not own_encoder_entry:
         refuse_deepsets(net, "the device gradient")
     b_obs = batch["b_obs"]
     B, D = b_obs.shape
@@ -230,42 +224,29 @@ def _u64(x: int) -> int:
     return int(x) & (2 ** 64 - 1)
 
 
-def _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, opt: Optional["DeviceAdam"],
-                    deepsets: bool = False, transformer: bool = False) -> torch.Tensor:
+def _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, opt: Optional["DeviceAdam"], kind=None) -> torch.Tensor:
     """``evac_rpo_minibatch_grad``, or with ``opt`` ``evac_rpo_minibatch_step``: the same arguments and the optimiser's three;
-    or with ``deepsets`` ``evac_deepsets_minibatch_grad``: the same arguments, the encoder after the policy and its gradients
-    after the policy's, and a workspace of its own size -- and with ``opt`` ``evac_deepsets_minibatch_step``: the optimiser's
-    three, the encoder's parameters after the policy's; or with ``transformer`` ``evac_transformer_minibatch_grad``, whose
-    arguments are the set encoder's with the attention encoder's two structs (no optimiser form exists)."""
-    B, D, dev, st, pol, grads, b_args = _batch_args(net, batch, deepsets or transformer)
-    kind = "transformer" if transformer else ("deepsets" if deepsets else "rpo")
-    if transformer:
-        enc, enc_grads = st.binder.transformer(net), ensure_transformer_grads(net)
-    elif deepsets:
-        enc, enc_grads = st.binder.encoder(net), ensure_encoder_grads(net)
+    or with ``kind`` (the network's own row of ``ENCODER_KINDS``) ``evac_deepsets_minibatch_grad`` /
+    ``evac_transformer_minibatch_grad``: the same arguments, the encoder after the policy and its gradients after the policy's,
+    and a workspace of its own size -- and with ``opt`` ``evac_deepsets_minibatch_step``: the optimiser's three, the encoder's
+    parameters after the policy's (the attention encoder has no optimiser form: a missing symbol)."""
+    B, D, dev, st, pol, grads, b_args = _batch_args(net, batch, kind is not None)
+    if kind is not None:
+        enc, enc_grads = st.binder.bind_encoder(net)[1], ensure_encoder_grads(net)
     if mb_inds.dtype != torch.int64 or mb_inds.device != dev or not mb_inds.is_contiguous() or mb_inds.dim() != 1:
         raise ValueError("mb_inds: expected a contiguous int64 device vector")
     M = int(mb_inds.shape[0])
-    stats, ws = _call_buffers(st, D, M, dev, rpo_noise, stats, sizer=f"evac_{kind}_workspace_bytes")
+    stats, ws = _call_buffers(st, D, M, dev, rpo_noise, stats, sizer=_entry_name(kind, "workspace_bytes"))
     lc = _loss_config(cfg)
     args = [C.byref(pol), C.byref(lc), *b_args, M, _ptr(mb_inds), _ptr(rpo_noise), _u64(seed), _u64(draw_counter), C.byref(grads),
             _ptr(stats), _ptr(ws), _stream(dev)]
-    if deepsets or transformer:
+    if kind is not None:
         args = [args[0], C.byref(enc), *args[1:-3], C.byref(enc_grads), *args[-3:]]
-        if transformer:
-            rc = _lib.load().evac_transformer_minibatch_grad(*args)
-        elif opt is None:
-            rc = _lib.load().evac_deepsets_minibatch_grad(*args)
-        else:
-            oc = opt.config()
-            rc = _lib.load().evac_deepsets_minibatch_step(*args, C.byref(opt.params_struct()), C.byref(opt.encoder_params_struct()),
-                                                          C.byref(opt.state_struct()), C.byref(oc))
-    elif opt is None:
-        rc = _lib.load().evac_rpo_minibatch_grad(*args)
-    else:
+    if opt is not None:
         oc = opt.config()
-        rc = _lib.load().evac_rpo_minibatch_step(*args, C.byref(opt.params_struct()), C.byref(opt.state_struct()), C.byref(oc))
-    _lib.check(rc)
+        args += [C.byref(opt.params_struct()), *([] if kind is None else [C.byref(opt.encoder_params_struct())]),
+                 C.byref(opt.state_struct()), C.byref(oc)]
+    _lib.check(getattr(_lib.load(), _entry_name(kind, "minibatch_grad" if opt is None else "minibatch_step"))(*args))
     return stats
 
 
@@ -288,7 +269,7 @@ def deepsets_minibatch_grad(net, batch: Dict[str, torch.Tensor], mb_inds: torch.
     refuse_transformer(net, "deepsets_minibatch_grad")
     if not is_deepsets(net):
         raise ValueError("deepsets_minibatch_grad: the network has no set encoder (`deep_sets`); its gradient is rpo_minibatch_grad's")
-    return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, None, deepsets=True)
+    return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, None, encoder_kind(net))
 
 
 def transformer_minibatch_grad(net, batch: Dict[str, torch.Tensor], mb_inds: torch.Tensor, cfg, *,
@@ -304,7 +285,7 @@ def transformer_minibatch_grad(net, batch: Dict[str, torch.Tensor], mb_inds: tor
         raise ValueError("transformer_minibatch_grad: the network has no attention encoder (`embedding`); its gradient is "
                          "rpo_minibatch_grad's or deepsets_minibatch_grad's")
     refuse_dropout(net, "transformer_minibatch_grad")
-    return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, None, transformer=True)
+    return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, None, encoder_kind(net))
 
 
 HEADER_FIELDS = ("t", "P1", "P2", "stop", "steps_run", "epochs_run")
@@ -486,34 +467,33 @@ def update_steps(batch_size: int, minibatch_size: int, norm_adv: bool) -> list:
     return [min(M, B - s) for s in range(0, B, M) if min(M, B - s) >= least]
 
 
-def _update_call(net, batch, perms, cfg, opt, rpo_noise, seed, first_draw_counter, stats, minibatch_size, deepsets: bool = False):
-    """``evac_rpo_update``, or with ``deepsets`` ``evac_deepsets_update``: the same arguments with the encoder after the policy,
-    its parameters after the policy's and its gradients after the policy's, and a workspace of its own size."""
+def _update_call(net, batch, perms, cfg, opt, rpo_noise, seed, first_draw_counter, stats, minibatch_size, kind=None):
+    """``evac_rpo_update``, or with ``kind`` (the network's own row of ``ENCODER_KINDS``: the set encoder's) ``evac_deepsets_update``:
+    the same arguments with the encoder after the policy, its parameters after the policy's and its gradients after the policy's,
+    and a workspace of its own size."""
     _check_opt(opt, net)
-    B, D, dev, st, pol, grads, b_args = _batch_args(net, batch, deepsets)
+    B, D, dev, st, pol, grads, b_args = _batch_args(net, batch, kind is not None)
+    name = _entry_name(kind, "update")
     if not isinstance(perms, torch.Tensor) or perms.dtype != torch.int64 or perms.device != dev or not perms.is_contiguous() or \
             perms.dim() != 2 or perms.shape[1] != B or perms.shape[0] < 1:
         raise ValueError(f"perms: expected a contiguous int64 device tensor of shape [epochs, {B}]")
     M = int(cfg.minibatch_size if minibatch_size is None else minibatch_size)
     norm_adv = bool(getattr(cfg, "norm_adv", True))
     if M < (2 if norm_adv else 1):
-        raise ValueError(f"{'deepsets' if deepsets else 'rpo'}_update: minibatch_size = {M}")
+        raise ValueError(f"{name[len('evac_'):]}: minibatch_size = {M}")
     M = min(M, B)
     n_epochs = int(perms.shape[0])
     steps = n_epochs * len(update_steps(B, M, norm_adv))
-    stats, ws = _call_buffers(st, D, M, dev, rpo_noise, stats, steps, sizer=f"evac_{'deepsets' if deepsets else 'rpo'}_workspace_bytes")
+    stats, ws = _call_buffers(st, D, M, dev, rpo_noise, stats, steps, sizer=_entry_name(kind, "workspace_bytes"))
     target_kl = getattr(cfg, "target_kl", None)
     lc, oc = _loss_config(cfg), opt.config()
-    tail = [*b_args, M, n_epochs, _ptr(perms), _ptr(rpo_noise), _u64(seed), _u64(first_draw_counter), int(target_kl is not None),
-            float(target_kl or 0.0), _ptr(stats), _ptr(ws), _stream(dev)]
-    if deepsets:
-        enc, enc_grads = st.binder.encoder(net), ensure_encoder_grads(net)
-        rc = _lib.load().evac_deepsets_update(C.byref(pol), C.byref(enc), C.byref(opt.params_struct()), C.byref(opt.encoder_params_struct()),
-                                              C.byref(grads), C.byref(enc_grads), C.byref(lc), C.byref(oc), C.byref(opt.state_struct()),
-                                              *tail)
-    else:
-        rc = _lib.load().evac_rpo_update(C.byref(pol), C.byref(opt.params_struct()), C.byref(grads), C.byref(lc), C.byref(oc),
-                                         C.byref(opt.state_struct()), *tail)
+    front = [C.byref(pol), C.byref(opt.params_struct()), C.byref(grads)]
+    if kind is not None:                                                      # ... each followed by the encoder's
+        enc, enc_grads = st.binder.bind_encoder(net)[1], ensure_encoder_grads(net)
+        front = [x for pair in zip(front, map(C.byref, (enc, opt.encoder_params_struct(), enc_grads))) for x in pair]
+    rc = getattr(_lib.load(), name)(*front, C.byref(lc), C.byref(oc), C.byref(opt.state_struct()), *b_args, M, n_epochs,
+                                    _ptr(perms), _ptr(rpo_noise), _u64(seed), _u64(first_draw_counter), int(target_kl is not None),
+                                    float(target_kl or 0.0), _ptr(stats), _ptr(ws), _stream(dev))
     _lib.check(rc)
     return stats, opt.header
 
@@ -540,7 +520,7 @@ def deepsets_minibatch_step(net, batch: Dict[str, torch.Tensor], mb_inds: torch.
     if not is_deepsets(net):
         raise ValueError("deepsets_minibatch_step: the network has no set encoder (`deep_sets`); its step is rpo_minibatch_step's")
     _check_opt(opt, net)
-    return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, opt, deepsets=True)
+    return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, opt, encoder_kind(net))
 
 
 def deepsets_update(net, batch: Dict[str, torch.Tensor], perms: torch.Tensor, cfg, opt: DeviceAdam, *,
@@ -552,7 +532,7 @@ def deepsets_update(net, batch: Dict[str, torch.Tensor], perms: torch.Tensor, cf
     refuse_transformer(net, "deepsets_update")
     if not is_deepsets(net):
         raise ValueError("deepsets_update: the network has no set encoder (`deep_sets`); its update is rpo_update's")
-    return _update_call(net, batch, perms, cfg, opt, rpo_noise, seed, first_draw_counter, stats, minibatch_size, deepsets=True)
+    return _update_call(net, batch, perms, cfg, opt, rpo_noise, seed, first_draw_counter, stats, minibatch_size, encoder_kind(net))
 
 
 def _kernel_grad(trainer: "RPOTrainer", batch, mb_inds, rpo_noise, draw_counter: int, stats: torch.Tensor) -> torch.Tensor:

@@ -5,19 +5,14 @@ The yardstick is the reference's minibatch loss on the module in a given dtype t
 ``loss_terms`` fed y = encode(x), the encoder element by element as tests/deepsets_ref.py states it (phi per element, then the
 sum, then rho).  It runs in float64 (the truth) and in float32 (whose error against float64 sets every bound), on the device
 the batch is on."""
-from types import SimpleNamespace
-
+from tests import encoder_grad_cases as G
 from tests import trainer_ref as R
+from tests.encoder_grad_cases import all_tensors, fake_trainer  # noqa: F401  (the test files reach them here)
 
 DEV = "cuda:0"
 ENCODER_NAMES = ("phi_w1", "phi_b1", "phi_w2", "phi_b2", "rho_w", "rho_b")
 NAMES = R.NAMES + ENCODER_NAMES
 RELU_MARGIN = 1e-5
-
-
-def all_tensors(net):
-    from evacuation_amd.policy import all_tensors as f
-    return f(net)
 
 
 def params_of(net, dtype=None, device=None):
@@ -94,9 +89,6 @@ def _near_relu(P, obs, rows=4096):
         return torch.cat([(preact(P, obs[i:i + rows]).abs() < RELU_MARGIN).flatten(1).any(dim=1) for i in range(0, obs.shape[0], rows)])
 
 
-_CASES = {}
-
-
 def build_case(N, ed, M, mode, cfg, seed, device=DEV, cache=True):
     """tests/trainer_cases.build_case's recipe behind the encoder: a batch whose minibatch takes every branch of the loss by a
     known share of its samples -- old log-probabilities and values set FROM the float64 forward pass (half of the rows inside
@@ -106,69 +98,20 @@ def build_case(N, ed, M, mode, cfg, seed, device=DEV, cache=True):
     float64 gradients, the 8 float64 statistics, the yardstick's terms with ``relu_on``: the share of relu masks that are 1).
     ``cache``: the case is built once per process and shared (nobody changes it)."""
     import torch
-    key = (N, ed, M, mode, cfg.norm_adv, cfg.clip_vloss, cfg.ent_coef, cfg.rpo_alpha, cfg.clip_coef, cfg.vf_coef, seed, str(device))
-    if cache and key in _CASES:
-        return _CASES[key]
-    c = cfg.clip_coef
     D = (N + 2) * ed
-    for attempt in range(8):
-        g = torch.Generator().manual_seed(seed + 1000 * attempt)
-        net = make_net(N, ed, seed=seed, device=device)
-        B = max(M, 4) if mode == "repeat" else 2 * M + 3
-        inds = torch.randint(0, B, (M,), generator=g) if mode == "repeat" else torch.arange(M) * 2 + 1
-        obs = (0.6 * torch.randn(B, D, generator=g)).clamp(-1, 1)
+
+    def encode64(net, obs, g):
         P = [p.detach().cpu().double() for p in all_tensors(net)]
-        for _ in range(8):                                                # the relu's branch point
-            near = _near_relu(P, obs.double())
-            n = int(near.sum())
-            if n == 0:
-                break
-            obs[near] = (0.6 * torch.randn(n, D, generator=g)).clamp(-1, 1)
+        G.redraw_rows(obs, g, lambda o: _near_relu(P, o.double()))          # the relu's branch point
         assert not bool(_near_relu(P, obs.double()).any()), "rows at the relu's branch point after 8 rounds"
-        act = torch.randn(B, 2, generator=g)
-        z = (torch.rand(M, 2, generator=g) * 2 - 1) * cfg.rpo_alpha
-        # the float64 forward pass of every batch row, with the perturbation of the LAST minibatch position that reads the row
-        zrow = torch.zeros(B, 2)
-        zrow[inds] = z
-        lp, _, val = R.logprob_entropy_value(P[:13], _encode_rows(P, obs.double()), act.double(), zrow.double())
-        u = torch.rand(B, generator=g)
-        mag = 0.25 + 0.35 * torch.rand(B, generator=g)                                    # |log ratio| in [0.25, 0.6]: ratio <= 0.78 or >= 1.28
-        inside = (0.05 * torch.randn(B, generator=g)).clamp(-0.12, 0.12)
-        target = torch.where(u < 0.5, inside, torch.where(u < 0.75, mag, -mag))
-        logprobs = (lp - target.double()).float()
-        u2 = torch.rand(B, generator=g)
-        mag2 = c * (1.25 + torch.rand(B, generator=g))
-        inside2 = c * (0.3 * torch.randn(B, generator=g)).clamp(-0.8, 0.8)
-        dv = torch.where(u2 < 0.5, inside2, torch.where(u2 < 0.75, mag2, -mag2))
-        values = (val.view(-1) - dv.double()).float()
-        returns = (val.view(-1) + 0.7 * torch.randn(B, generator=g).double()).float()
-        adv = torch.randn(B, generator=g) + 0.3
-        batch = {"b_obs": obs, "b_actions": act, "b_logprobs": logprobs, "b_advantages": adv, "b_returns": returns, "b_values": values}
-        batch = {k: v.to(device).contiguous() for k, v in batch.items()}
-        inds, z = inds.to(device), z.to(device).contiguous()
-        g64, s64, t = minibatch_grad(net, batch, inds, cfg, z, torch.float64)
-        near = ((t.ratio - (1 - c)).abs() < 1e-6) | ((t.ratio - (1 + c)).abs() < 1e-6) | (t.adv.abs() < 1e-6)
-        near |= ((t.dv.abs() - c).abs() < 1e-6)
-        if cfg.clip_vloss:
-            near |= ((t.dv.abs() > c) & ((t.v_unclipped - t.v_clipped).abs() < 1e-6))
-        if not bool(near.any()):
+
+        def attach(t, batch, inds):
             with torch.no_grad():
                 P64 = [p.detach().double() for p in all_tensors(net)]
                 t.relu_on = float((preact(P64, batch["b_obs"][inds].double()) > 0).double().mean())
-            out = (net, batch, inds, z, g64, s64, t)
-            if cache:
-                _CASES[key] = out
-            return out
-    raise AssertionError("could not build a case without samples at a branch point")
+        return P[:13], _encode_rows(P, obs.double()), attach
+    return G.build_case(D, M, mode, cfg, seed, device, lambda: make_net(N, ed, seed=seed, device=device), encode64, minibatch_grad,
+                        key=("deepsets", N, ed) if cache else None)
 
 
-def kernel_grad(net, batch, inds, cfg, z, **kw):
-    import torch
-    from evacuation_amd import trainer
-    stats = trainer.deepsets_minibatch_grad(net, batch, inds, cfg, rpo_noise=z, **kw)
-    torch.cuda.synchronize()
-    return [p.grad.clone() for p in all_tensors(net)], stats.clone()
-
-
-def fake_trainer(net, cfg):
-    return SimpleNamespace(net=net, cfg=cfg)
+kernel_grad = G.kernel_grad_of("deepsets_minibatch_grad")

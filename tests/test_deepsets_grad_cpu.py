@@ -12,12 +12,13 @@ import torch
 from evacuation_amd import _lib, build
 from evacuation_amd.policy import DeepSetsActorCritic, LinearActorCritic
 from tests import deepsets_grad_cases as DC
+from tests import encoder_grad_cases as G
+from tests.encoder_grad_cases import FAKE
 from tests.kernel_meta import kernel_resources
 from tests.trainer_cases import loss_cfg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BAD = _lib.ERR_INVALID_ARGUMENT
-FAKE = 0x1000                                    # 16-byte aligned, never followed
 
 
 @pytest.fixture(scope="module")
@@ -41,27 +42,16 @@ def test_symbols_are_declared_exported_and_bound(lib):
     assert os.path.join(build.CSRC, "evac_deepsets_train_api.hip") in build.SOURCES
 
 
-class Call:
+class Call(G.GradCall):
     """A call of evac_deepsets_minibatch_grad whose every argument is acceptable, to be spoiled one argument at a time."""
 
     def __init__(self, D=36, ed=3, M=4, B=8, norm_adv=1):
-        self.pol = _lib.EvacMlpPolicy(D, 64, *[FAKE] * 13)
+        super().__init__(D, M, B, norm_adv)
         self.enc = _lib.EvacDeepSets(ed, 24, *[FAKE] * 6)
-        self.cfg = _lib.EvacRpoLossConfig(0.2, 0.0, 0.5, 0.5, norm_adv, 1)
-        self.grads = _lib.EvacMlpPolicyGrads(*[FAKE] * 13)
         self.enc_grads = _lib.EvacDeepSetsGrads(*[FAKE] * 6)
-        self.B, self.M = B, M
-        self.ptr = {k: FAKE for k in ("b_obs", "b_actions", "b_logprobs", "b_advantages", "b_returns", "b_values", "mb_inds", "stats",
-                                      "workspace")}
-        self.null = set()                        # structs passed as NULL
 
     def __call__(self, lib):
-        ref = lambda name, s: None if name in self.null else C.byref(s)
-        p = self.ptr
-        return lib.evac_deepsets_minibatch_grad(ref("pol", self.pol), ref("enc", self.enc), ref("cfg", self.cfg), self.B, p["b_obs"],
-                                                p["b_actions"], p["b_logprobs"], p["b_advantages"], p["b_returns"], p["b_values"], self.M,
-                                                p["mb_inds"], None, 1, 2, ref("grads", self.grads), ref("enc_grads", self.enc_grads),
-                                                p["stats"], p["workspace"], None)
+        return self.grad_call(lib.evac_deepsets_minibatch_grad)
 
 
 def test_every_refusal_comes_before_a_device_is_touched(lib):
@@ -71,22 +61,7 @@ def test_every_refusal_comes_before_a_device_is_touched(lib):
         c = Call(**kw)
         spoiled.append((why, c))
         return c
-    # everything rpo_prepare refuses
-    for s in ("pol", "cfg", "grads"):
-        add(f"NULL {s}").null.add(s)
-    for k in ("b_obs", "b_actions", "b_logprobs", "b_advantages", "b_returns", "b_values", "mb_inds", "stats", "workspace"):
-        add(f"NULL {k}").ptr[k] = None
-    for f, _ in _lib.EvacMlpPolicy._fields_[2:]:
-        setattr(add(f"NULL policy.{f}").pol, f, None)
-        setattr(add(f"NULL grads.{f}").grads, f, None)
-    add("hidden != 64").pol.hidden = 32
-    add("obs_dim 0").pol.obs_dim = 0
-    add("obs_dim 397", D=397, ed=1)
-    add("batch_size 0", B=0)
-    add("M 0", M=0)
-    add("M 2^31", M=1 << 31)
-    add("norm_adv with one sample", M=1)
-    add("misaligned workspace").ptr["workspace"] = FAKE + 8
+    G.rpo_refusals(add, "ed")
     # the encoder's
     add("NULL encoder").null.add("enc")
     add("NULL encoder gradients").null.add("enc_grads")

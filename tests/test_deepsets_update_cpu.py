@@ -14,14 +14,14 @@ import torch
 from evacuation_amd import _lib, build
 from evacuation_amd.policy import DeepSetsActorCritic, LinearActorCritic, all_tensors
 from tests import deepsets_grad_cases as DC
+from tests import encoder_grad_cases as G
+from tests.encoder_grad_cases import BATCH, FAKE
 from tests.kernel_meta import kernel_resources
 from tests.optimizer_ref import AdamRef
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BAD = _lib.ERR_INVALID_ARGUMENT
-FAKE = 0x1000                                    # 16-byte aligned, never followed
 ENTRIES = ("evac_deepsets_adam_step", "evac_deepsets_minibatch_step", "evac_deepsets_update")
-BATCH = ("b_obs", "b_actions", "b_logprobs", "b_advantages", "b_returns", "b_values")
 
 
 @pytest.fixture(scope="module")
@@ -51,37 +51,31 @@ def test_symbols_are_declared_exported_and_bound(lib):
 
 
 # ------------------------------------------------------------------------------------------------ refusals
-class Call:
+class Call(G.GradCall):
     """A call of one of the three entries whose every argument is acceptable, to be spoiled one argument at a time (the pattern of
     tests/test_deepsets_grad_cpu.py)."""
 
     def __init__(self, entry, D=36, ed=3, M=4, B=8, norm_adv=1, epochs=2):
+        super().__init__(D, M, B, norm_adv)
         self.entry = entry
-        self.pol = _lib.EvacMlpPolicy(D, 64, *[FAKE] * 13)
         self.enc = _lib.EvacDeepSets(ed, 24, *[FAKE] * 6)
-        self.cfg = _lib.EvacRpoLossConfig(0.2, 0.0, 0.5, 0.5, norm_adv, 1)
-        self.grads = _lib.EvacMlpPolicyGrads(*[FAKE] * 13)
         self.enc_grads = _lib.EvacDeepSetsGrads(*[FAKE] * 6)
         self.params = _lib.EvacMlpPolicyGrads(*[FAKE] * 13)
         self.enc_params = _lib.EvacDeepSetsGrads(*[FAKE] * 6)
         self.state = _lib.EvacDeepSetsAdamState(FAKE, _lib.EvacMlpPolicyGrads(*[FAKE] * 13), _lib.EvacMlpPolicyGrads(*[FAKE] * 13),
                                                 _lib.EvacDeepSetsGrads(*[FAKE] * 6), _lib.EvacDeepSetsGrads(*[FAKE] * 6))
         self.adam = _lib.EvacAdamConfig(3e-4, 0.9, 0.999, 1e-5, 0.5)
-        self.D, self.ed, self.B, self.M, self.epochs = D, ed, B, M, epochs
-        self.ptr = {k: FAKE for k in BATCH + ("mb_inds", "stats", "workspace", "sumsq")}
-        self.null = set()                        # structs passed as NULL
+        self.D, self.ed, self.epochs = D, ed, epochs
+        self.ptr["sumsq"] = FAKE
 
     def __call__(self, lib):
-        ref = lambda name: None if name in self.null else C.byref(getattr(self, name))
-        p = self.ptr
+        ref, p = self.ref, self.ptr
         batch = [self.B] + [p[k] for k in BATCH]
         if self.entry == "evac_deepsets_adam_step":
             return lib.evac_deepsets_adam_step(ref("params"), ref("enc_params"), ref("grads"), ref("enc_grads"), ref("state"), ref("adam"),
                                                self.D, self.ed, p["sumsq"], None)
         if self.entry == "evac_deepsets_minibatch_step":
-            return lib.evac_deepsets_minibatch_step(ref("pol"), ref("enc"), ref("cfg"), *batch, self.M, p["mb_inds"], None, 1, 2, ref("grads"),
-                                                    ref("enc_grads"), p["stats"], p["workspace"], None, ref("params"), ref("enc_params"),
-                                                    ref("state"), ref("adam"))
+            return self.grad_call(lib.evac_deepsets_minibatch_step, ref("params"), ref("enc_params"), ref("state"), ref("adam"))
         return lib.evac_deepsets_update(ref("pol"), ref("enc"), ref("params"), ref("enc_params"), ref("grads"), ref("enc_grads"), ref("cfg"),
                                         ref("adam"), ref("state"), *batch, self.M, self.epochs, p["mb_inds"], None, 1, 2, 1, 0.01,
                                         p["stats"], p["workspace"], None)
@@ -128,20 +122,10 @@ def spoiled_calls(entry):
         add("NULL grad_sumsq").ptr["sumsq"] = None
         return spoiled
     # everything evac_deepsets_minibatch_grad refuses (rpo_prepare's, then the encoder's)
-    for s in ("pol", "cfg", "enc"):
-        add(f"NULL {s}").null.add(s)
-    for k in BATCH + ("mb_inds", "stats", "workspace"):
-        add(f"NULL {k}").ptr[k] = None
-    for f, _ in _lib.EvacMlpPolicy._fields_[2:]:
-        setattr(add(f"NULL policy.{f}").pol, f, None)
+    G.rpo_refusals(add, "ed", own_grads=False)
+    add("NULL enc").null.add("enc")
     for f in DC.ENCODER_NAMES:
         setattr(add(f"NULL encoder.{f}").enc, f, None)
-    add("hidden != 64").pol.hidden = 32
-    add("batch_size 0", B=0)
-    add("M 0", M=0)
-    add("M 2^31", M=1 << 31)
-    add("norm_adv with one sample", M=1)
-    add("misaligned workspace").ptr["workspace"] = FAKE + 8
     add("encoder hidden != 24").enc.hidden = 23
     add("encoder hidden 16").enc.hidden = 16
     add("misaligned rho_w").enc.rho_w = FAKE + 4

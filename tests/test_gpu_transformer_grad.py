@@ -7,30 +7,19 @@ the test) + 1e-7, for the tensors and for the statistics.  Then determinism and 
 device-drawn perturbation, the sum of squares, the blocks not in use, graph capture, RPOTrainer's wiring and the example.
 Everything is compared at the gradient: nothing after an optimiser step.  The table is printed (run with -s) and copied into
 DESIGN.md section 4.15."""
-import math
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 
+from tests import encoder_grad_cases as G
 from tests import transformer_grad_cases as TC
-from tests.test_gpu_trainer import assert_branch_shares, stat_errors
+from tests.encoder_grad_cases import ROOT, ea  # noqa: F401  (the fixture)
+from tests.test_gpu_trainer import assert_branch_shares
 from tests.trainer_cases import DEV, loss_cfg
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FACTOR = 4
-
-
-@pytest.fixture(scope="module")
-def ea():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    import evacuation_amd
-    return evacuation_amd
 
 
 def kernel_constant(name):
@@ -72,20 +61,8 @@ def test_the_cases_cover_every_axis():
     assert {c[3] for c in CASES} == {1, 2} and {c[4] for c in CASES} == {False, True}
 
 
-def check_against_float64(gk, sk, g32, s32, g64, s64, blocks, title):
-    """Every tensor and statistic of the kernel within FACTOR x the float32 yardstick's largest error + 1e-7."""
-    e32, ek = TC.tensor_errors(g32, g64, blocks), TC.tensor_errors(gk, g64, blocks)
-    se32, sek = stat_errors(s32, s64), stat_errors(sk, s64)
-    bound, sbound = FACTOR * max(e32) + 1e-7, FACTOR * max(se32) + 1e-7
-    print(f"\n{title}: e32(case) = {max(e32):.2e}, bound {bound:.2e}; statistics e32 = {max(se32):.2e}, bound {sbound:.2e}")
-    for name, a, b in zip(TC.names(blocks), e32, ek):
-        print(f"  {name:20s} torch f32 {a:.2e}   kernel {b:.2e}   ratio to e32(case) {b / max(e32):.2f}")
-    for name, a, b in zip(TC.R.STATS, se32, sek):
-        print(f"  {name:20s} torch f32 {a:.2e}   kernel {b:.2e}")
-    for name, b in zip(TC.names(blocks), ek):
-        assert b <= bound, (name, b, bound)
-    for name, b in zip(TC.R.STATS, sek):
-        assert b <= sbound, (name, b, sbound)
+ENC = G.Encoder(TC, lambda n: TC.names((n - 13) // 16), lambda got, g64: TC.tensor_errors(got, g64, (len(g64) - 13) // 16),
+                "transformer_minibatch_grad", "transformer_kernel_grad", "TransformerActorCritic", "transformer", FACTOR, 20)
 
 
 @pytest.mark.parametrize("N,ed,M,blocks,resid,mode,norm_adv,clip_vloss,ent,alpha", CASES)
@@ -99,9 +76,9 @@ def test_minibatch_grad_against_the_float64_yardstick(ea, N, ed, M, blocks, resi
     g32, s32, _ = TC.minibatch_grad(net, batch, inds, cfg, z)                 # torch, float32, on the GPU
     gk, sk = TC.kernel_grad(net, batch, inds, cfg, z)
     assert len(gk) == 13 + 16 * blocks
-    check_against_float64(gk, sk, g32, s32, g64, s64, blocks,
-                          f"case N={N} ed={ed} M={M} blocks={blocks} resid={int(resid)} {mode} norm_adv={norm_adv} "
-                          f"clip_vloss={clip_vloss} ent={ent} alpha={alpha}")
+    G.check_against_float64(ENC, gk, sk, g32, s32, g64, s64,
+                            f"case N={N} ed={ed} M={M} blocks={blocks} resid={int(resid)} {mode} norm_adv={norm_adv} "
+                            f"clip_vloss={clip_vloss} ent={ent} alpha={alpha}")
 
 
 def big_case():
@@ -111,30 +88,7 @@ def big_case():
 
 
 def test_deterministic_and_written_not_accumulated(ea):
-    import torch
-    cfg, net, batch, inds, z, *_ = big_case()
-    g1, s1 = TC.kernel_grad(net, batch, inds, cfg, z)
-    for p in TC.all_tensors(net):
-        p.grad.fill_(7.0)                                                     # written, not accumulated
-    junk = [torch.randn(1 << 20, device=DEV) for _ in range(5)]               # unrelated allocations and work
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        g2, s2 = TC.kernel_grad(net, batch, inds, cfg, z)
-    side.synchronize()
-    del junk
-    for name, a, b in zip(TC.names(2), g1, g2):
-        assert torch.equal(a, b), name
-    assert torch.equal(s1, s2)
-    # the perturbation drawn on the device: equal bits for equal (seed, draw_counter), another draw for another counter
-    seed, counter = 0x1234567890ABCDEF, (7 << 32) + 5
-    gd, sd = TC.kernel_grad(net, batch, inds, cfg, None, seed=seed, draw_counter=counter)
-    ge, se = TC.kernel_grad(net, batch, inds, cfg, None, seed=seed, draw_counter=counter)
-    for name, a, b in zip(TC.names(2), gd, ge):
-        assert torch.equal(a, b), name
-    assert torch.equal(sd, se)
-    _, so = TC.kernel_grad(net, batch, inds, cfg, None, seed=seed, draw_counter=counter + 1)
-    assert not torch.equal(so, sd)
+    G.check_deterministic_and_written_not_accumulated(ENC, *big_case()[:5])
 
 
 def test_the_encoder_matters(ea):
@@ -158,7 +112,7 @@ def test_a_block_that_is_not_in_use_is_neither_read_nor_written(ea):
     net, batch, inds, z, *_ = TC.build_case(10, 3, 2, 1, True, "repeat", cfg, seed=case_seed(10, 3, 2))
     g1, s1 = TC.kernel_grad(net, batch, inds, cfg, z)
     st = trainer._grad_state(net)
-    enc, enc_grads = st.binder.transformer(net), trainer.ensure_transformer_grads(net)
+    enc, enc_grads = st.binder.transformer(net), trainer.ensure_encoder_grads(net)
     assert enc.num_blocks == 1 and all(getattr(enc_grads.blocks[1], f) is None for f in TC.BLOCK_NAMES)
     assert all(getattr(enc.blocks[1], f) is None for f in TC.BLOCK_NAMES)
     canary = torch.full((16, 128), 3.0, device=DEV)
@@ -182,32 +136,8 @@ def test_a_block_that_is_not_in_use_is_neither_read_nor_written(ea):
 
 
 def test_in_place_contract_under_graph_capture(ea):
-    import torch
-    from evacuation_amd import trainer
     cfg = loss_cfg(1, 1, 0.01, 0.5)
-    net, batch, inds, z, *_ = TC.build_case(10, 3, 64, 2, False, "strided", cfg, seed=21, cache=False)
-    stats = torch.zeros(8, device=DEV)
-    trainer.transformer_minibatch_grad(net, batch, inds, cfg, rpo_noise=z, stats=stats)               # warm-up: binds, allocates
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        trainer.transformer_minibatch_grad(net, batch, inds, cfg, rpo_noise=z, stats=stats)
-    before = [p.grad.clone() for p in TC.all_tensors(net)]
-    with torch.no_grad():
-        for p in TC.all_tensors(net):
-            p.add_(0.05 * torch.randn_like(p))                                                        # in place: same addresses
-        inds.copy_(torch.arange(64, device=DEV) * 2)                                                  # other rows, same vector
-    graph.replay()
-    torch.cuda.synchronize()
-    replayed = [p.grad.clone() for p in TC.all_tensors(net)]
-    replayed_stats = stats.clone()
-    direct, direct_stats = TC.kernel_grad(net, batch, inds, cfg, z)
-    for name, a, b, c in zip(TC.names(2), replayed, direct, before):
-        assert torch.equal(a, b), name
-        assert not torch.equal(a, c), name
-    assert torch.equal(replayed_stats, direct_stats)
-    g64, _, _ = TC.minibatch_grad(net, batch, inds, cfg, z, torch.float64)                            # ... and they are the new inputs' gradients
-    assert max(TC.tensor_errors(replayed, g64, 2)) < 1e-3
+    G.check_in_place_contract_under_graph_capture(ENC, cfg, *TC.build_case(10, 3, 64, 2, False, "strided", cfg, seed=21, cache=False)[:4])
 
 
 def test_trainer_wiring(ea):
@@ -216,56 +146,17 @@ def test_trainer_wiring(ea):
     import torch
     from evacuation_amd import trainer
     from evacuation_amd.policy import TransformerActorCritic
-    cfg = trainer.RPOTrainingConfig(seed=3, num_envs=8, num_steps=16, total_timesteps=8 * 16, num_minibatches=2, update_epochs=2)
-    env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=10), ea.EnvWrappersConfig(positions="abs", statuses="cat", type="Box"),
-                                      num_envs=8, gamma=cfg.gamma, seed=3)
-    assert env.obs_dim == 36
-    torch.manual_seed(0)
-    net = TransformerActorCritic(env.obs_dim, 10).to(DEV)
-    tensors = TC.all_tensors(net)
-    assert len(tensors) == 45
-    initial = [p.detach().clone() for p in tensors]
-    gen = torch.Generator(device=DEV).manual_seed(99)
-    calls = []
 
-    def grad_fn(tr, batch, mb_inds, rpo_noise, draw_counter, stats):
-        params = [p.detach().clone() for p in tensors]
-        out = trainer.transformer_kernel_grad(tr, batch, mb_inds, rpo_noise, draw_counter, stats)
-        calls.append((params, {k: v.clone() for k, v in batch.items()}, mb_inds.clone(), rpo_noise.clone(), draw_counter,
-                      [p.grad.clone() for p in tensors], out.clone()))
-        return out
-    tr = trainer.RPOTrainer(env, net, cfg, grad_fn=grad_fn,
-                            rpo_noise_fn=lambda M: (torch.rand(M, 2, device=DEV, generator=gen) * 2 - 1) * cfg.rpo_alpha)
-    assert trainer.RPOTrainer(env, net, cfg).grad_fn is trainer.autograd_minibatch_grad           # the default stays autograd's
-    with pytest.raises(ValueError, match="`embedding`"):
-        trainer.RPOTrainer(env, net, cfg, optimizer="device", grad_fn=trainer.transformer_kernel_grad)
-    log = tr.update()
-    torch.cuda.synchronize()
-    assert len(calls) == 4 and [c[4] for c in calls] == [0, 1, 2, 3]
-    assert all(math.isfinite(v) for k, v in log.items() if isinstance(v, float) and k != "explained_variance"), log
-    final = [p.detach().clone() for p in tensors]
-    assert all(bool(torch.isfinite(b).all()) for b in final)
+    def the_device_optimiser_stays_refused(env, net, cfg):
+        with pytest.raises(ValueError, match="`embedding`"):
+            trainer.RPOTrainer(env, net, cfg, optimizer="device", grad_fn=trainer.transformer_kernel_grad)
+    initial, final, calls, cfg = G.check_trainer_wiring(ENC, ea, the_device_optimiser_stays_refused)
+    assert len(initial) == 45
     assert sum(not torch.equal(a, b) for a, b in zip(initial, final)) >= 43                           # (all but, at most, the two key biases)
-    for i, (params, batch, mb_inds, noise, counter, grads, stats) in enumerate(calls):
-        with torch.no_grad():
-            for p, q in zip(tensors, params):
-                p.copy_(q)                                                                            # the parameters of that moment
-        gd, sd = TC.kernel_grad(net, batch, mb_inds, cfg, noise, seed=cfg.seed, draw_counter=counter)
-        for name, a, b in zip(TC.names(2), grads, gd):
-            assert torch.equal(a, b), (i, name)
-        assert torch.equal(stats, sd)
-        g64, s64, _ = TC.minibatch_grad(net, batch, mb_inds, cfg, noise, torch.float64)
-        g32, s32, _ = TC.minibatch_grad(net, batch, mb_inds, cfg, noise)
-        check_against_float64(grads, stats, g32, s32, g64, s64, 2, f"trainer wiring, call {i}")
     # what the binder refuses, the entry refuses
     with pytest.raises(ValueError, match="num_heads 2"):
         trainer.transformer_minibatch_grad(TransformerActorCritic(36, 10, num_heads=2).to(DEV), calls[0][1], calls[0][2], cfg)
-    env.close()
 
 
 def test_train_rpo_example_with_the_device_gradient(ea):
-    cmd = [sys.executable, os.path.join(ROOT, "examples", "train_rpo.py"), "--network", "transformer", "--gradient", "device", "--envs", "8",
-           "--steps", "16", "--updates", "2", "--pedestrians", "10", "--minibatches", "2", "--epochs", "2"]
-    done = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=120)
-    assert done.returncode == 0, done.stdout[-2000:] + done.stderr[-2000:]
-    assert done.stdout.count("SPS:") == 2, done.stdout[-2000:]
+    G.check_train_rpo_example_with_the_device_gradient(ENC)

@@ -1,12 +1,13 @@
 """What the GPU tests of the trainer (tests/test_gpu_trainer.py) and of the optimiser step (tests/test_gpu_optimizer.py) both
 build: networks, loss settings, the branch-covering minibatch case, trainers on twin envs, the yardstick-driven ``grad_fn`` and
 the comparison of words as integers."""
+from tests import encoder_grad_cases as G
 from tests import trainer_ref as R
 
 DEV = "cuda:0"
 
 
-def make_net(D, seed=0, dtype=None):
+def make_net(D, seed=0, dtype=None, device=DEV):
     import torch
     from evacuation_amd.policy import LinearActorCritic
     torch.manual_seed(seed)
@@ -17,7 +18,7 @@ def make_net(D, seed=0, dtype=None):
         for seq in (net.actor_mean, net.critic):
             for i in (0, 2, 4):
                 seq[i].bias.uniform_(-0.2, 0.2)
-    return net.to(DEV)
+    return net.to(device)
 
 
 def make_initial_net(D, net_seed=0):
@@ -33,51 +34,16 @@ def loss_cfg(norm_adv=True, clip_vloss=True, ent_coef=0.0, rpo_alpha=0.5, clip_c
                              clip_coef=clip_coef, vf_coef=vf_coef)
 
 
-def build_case(D, M, mode, cfg, seed):
+def build_case(D, M, mode, cfg, seed, device=DEV):
     """A batch whose minibatch takes every branch of the loss by a known share of its samples: the old log-probabilities and
     values are set FROM the float64 forward pass so that the ratio lies inside the clip range for half of the batch rows, above
     it for a quarter and below it for a quarter (advantages of both signs everywhere), and the value difference likewise around
     +-clip_coef -- each with a margin, so no sample is within 1e-6 of a branch point of max / clamp (checked, regenerated from
     another seed otherwise).  ``mode``: 'repeat' (indices drawn with repetition from a batch of M rows) or 'strided' (every second
     row of a batch of 2 M + 3)."""
-    import torch
-    c = cfg.clip_coef
-    for attempt in range(8):
-        g = torch.Generator().manual_seed(seed + 1000 * attempt)
-        net = make_net(D, seed=seed)
-        B = max(M, 4) if mode == "repeat" else 2 * M + 3
-        inds = torch.randint(0, B, (M,), generator=g) if mode == "repeat" else torch.arange(M) * 2 + 1
-        obs = (0.6 * torch.randn(B, D, generator=g)).clamp(-1, 1)
-        act = torch.randn(B, 2, generator=g)
-        z = (torch.rand(M, 2, generator=g) * 2 - 1) * cfg.rpo_alpha
-        # the float64 forward pass of every batch row, with the perturbation of the LAST minibatch position that reads the row
-        zrow = torch.zeros(B, 2)
-        zrow[inds] = z
-        P = [p.detach().cpu().double() for p in R.mlp_tensors(net)]
-        lp, _, val = R.logprob_entropy_value(P, obs.double(), act.double(), zrow.double())
-        u = torch.rand(B, generator=g)
-        mag = 0.25 + 0.35 * torch.rand(B, generator=g)                                    # |log ratio| in [0.25, 0.6]: ratio <= 0.78 or >= 1.28
-        inside = (0.05 * torch.randn(B, generator=g)).clamp(-0.12, 0.12)
-        target = torch.where(u < 0.5, inside, torch.where(u < 0.75, mag, -mag))
-        logprobs = (lp - target.double()).float()
-        u2 = torch.rand(B, generator=g)
-        mag2 = c * (1.25 + torch.rand(B, generator=g))
-        inside2 = c * (0.3 * torch.randn(B, generator=g)).clamp(-0.8, 0.8)
-        dv = torch.where(u2 < 0.5, inside2, torch.where(u2 < 0.75, mag2, -mag2))
-        values = (val.view(-1) - dv.double()).float()
-        returns = (val.view(-1) + 0.7 * torch.randn(B, generator=g).double()).float()
-        adv = torch.randn(B, generator=g) + 0.3
-        batch = {"b_obs": obs, "b_actions": act, "b_logprobs": logprobs, "b_advantages": adv, "b_returns": returns, "b_values": values}
-        batch = {k: v.to(DEV).contiguous() for k, v in batch.items()}
-        inds, z = inds.to(DEV), z.to(DEV).contiguous()
-        g64, s64, t = R.minibatch_grad(net, batch, inds, cfg, z, torch.float64)
-        near = ((t.ratio - (1 - c)).abs() < 1e-6) | ((t.ratio - (1 + c)).abs() < 1e-6) | (t.adv.abs() < 1e-6)
-        near |= ((t.dv.abs() - c).abs() < 1e-6)
-        if cfg.clip_vloss:
-            near |= ((t.dv.abs() > c) & ((t.v_unclipped - t.v_clipped).abs() < 1e-6))
-        if not bool(near.any()):
-            return net, batch, inds, z, g64, s64, t
-    raise AssertionError("could not build a case without samples at a branch point")
+    def encode64(net, obs, g):                       # (no encoder: nothing to redraw, the actor-critic reads the observation)
+        return [p.detach().cpu().double() for p in R.mlp_tensors(net)], obs.double(), None
+    return G.build_case(D, M, mode, cfg, seed, device, lambda: make_net(D, seed=seed, device=device), encode64, R.minibatch_grad)
 
 
 def make_trainer(ea, n_ped, E, T, seed=1, net_seed=0, **kw):

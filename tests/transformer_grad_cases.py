@@ -7,9 +7,9 @@ score tensors are [rows, d_model, tokens, tokens]) and differentiated in two sta
 chunk's y with respect to the encoder's tensors.  It runs in float64 (the truth) and in float32 (whose error against float64
 sets every bound), on the device the batch is on."""
 import copy
-from types import SimpleNamespace
-
+from tests import encoder_grad_cases as G
 from tests import trainer_ref as R
+from tests.encoder_grad_cases import all_tensors, fake_trainer  # noqa: F401  (the test files reach them here)
 
 DEV = "cuda:0"
 BLOCK_NAMES = ("wq", "bq", "wk", "bk", "wv", "bv", "dense_w", "dense_b", "ff1_w", "ff1_b", "ff2_w", "ff2_b", "norm1_w", "norm1_b",
@@ -54,11 +54,6 @@ def assert_key_biases_are_zero(g64, blocks):
     for i in key_biases(blocks):
         limit = 1e-9 * own[i - 1] if own[i - 1] >= VANISHING * top else VANISHING * top
         assert own[i] <= limit, (i, own[i], limit)
-
-
-def all_tensors(net):
-    from evacuation_amd.policy import all_tensors as f
-    return f(net)
 
 
 def twin_of(net, dtype, device=None):
@@ -148,9 +143,6 @@ def internals(net64, obs, rows=ROWS):
     return torch.cat(pre_min), torch.cat(var_min), torch.cat(ys)
 
 
-_CASES = {}
-
-
 def build_case(N, ed, M, blocks, use_resid, mode, cfg, seed, device=DEV, cache=True):
     """tests/deepsets_grad_cases.build_case's recipe behind the attention encoder: a batch whose minibatch takes every branch of the
     loss by a known share of its samples -- old log-probabilities and values set FROM the float64 forward pass (half of the rows
@@ -168,79 +160,31 @@ def build_case(N, ed, M, blocks, use_resid, mode, cfg, seed, device=DEV, cache=T
     the batch's rows and how many were redrawn for either cause, over all rounds).
     ``cache``: the case is built once per process and shared (nobody changes it)."""
     import torch
-    key = (N, ed, M, blocks, use_resid, mode, cfg.norm_adv, cfg.clip_vloss, cfg.ent_coef, cfg.rpo_alpha, cfg.clip_coef, cfg.vf_coef,
-           seed, str(device))
-    if cache and key in _CASES:
-        return _CASES[key]
-    c = cfg.clip_coef
     D = (N + 2) * ed
-    for attempt in range(8):
-        g = torch.Generator().manual_seed(seed + 1000 * attempt)
-        net = make_net(N, ed, blocks, use_resid, seed=seed, device=device)
+
+    def encode64(net, obs, g):
         net64 = twin_of(net, torch.float64, "cpu")
-        B = max(M, 4) if mode == "repeat" else 2 * M + 3
-        inds = torch.randint(0, B, (M,), generator=g) if mode == "repeat" else torch.arange(M) * 2 + 1
-        obs = (0.6 * torch.randn(B, D, generator=g)).clamp(-1, 1)
-        redrawn_relu = redrawn_variance = 0
-        for _ in range(8):                                                # the relu's branch point, the variance floor
-            pre_min, var_min, _ = internals(net64, obs.double())
-            near = (pre_min < RELU_MARGIN) | (var_min < VARIANCE_FLOOR)
-            n = int(near.sum())
-            redrawn_relu += int((pre_min < RELU_MARGIN).sum())
-            redrawn_variance += int((var_min < VARIANCE_FLOOR).sum())
-            if n == 0:
-                break
-            obs[near] = (0.6 * torch.randn(n, D, generator=g)).clamp(-1, 1)
+        redrawn = [0, 0]
+
+        def near(o):                                                      # the relu's branch point, the variance floor
+            pre_min, var_min, _ = internals(net64, o.double())
+            redrawn[0] += int((pre_min < RELU_MARGIN).sum())
+            redrawn[1] += int((var_min < VARIANCE_FLOOR).sum())
+            return (pre_min < RELU_MARGIN) | (var_min < VARIANCE_FLOOR)
+        G.redraw_rows(obs, g, near)
         pre_min, var_min, y64 = internals(net64, obs.double())
         assert float(pre_min.min()) >= RELU_MARGIN, "rows at the relu's branch point after 8 rounds"
         assert float(var_min.min()) >= VARIANCE_FLOOR, f"a LayerNorm input variance of {float(var_min.min()):.3g}"
-        P = [p.detach() for p in all_tensors(net64)]
-        act = torch.randn(B, 2, generator=g)
-        z = (torch.rand(M, 2, generator=g) * 2 - 1) * cfg.rpo_alpha
-        # the float64 forward pass of every batch row, with the perturbation of the LAST minibatch position that reads the row
-        zrow = torch.zeros(B, 2)
-        zrow[inds] = z
-        lp, _, val = R.logprob_entropy_value(P[:13], y64, act.double(), zrow.double())
-        u = torch.rand(B, generator=g)
-        mag = 0.25 + 0.35 * torch.rand(B, generator=g)                                    # |log ratio| in [0.25, 0.6]: ratio <= 0.78 or >= 1.28
-        inside = (0.05 * torch.randn(B, generator=g)).clamp(-0.12, 0.12)
-        target = torch.where(u < 0.5, inside, torch.where(u < 0.75, mag, -mag))
-        logprobs = (lp - target.double()).float()
-        u2 = torch.rand(B, generator=g)
-        mag2 = c * (1.25 + torch.rand(B, generator=g))
-        inside2 = c * (0.3 * torch.randn(B, generator=g)).clamp(-0.8, 0.8)
-        dv = torch.where(u2 < 0.5, inside2, torch.where(u2 < 0.75, mag2, -mag2))
-        values = (val.view(-1) - dv.double()).float()
-        returns = (val.view(-1) + 0.7 * torch.randn(B, generator=g).double()).float()
-        adv = torch.randn(B, generator=g) + 0.3
-        batch = {"b_obs": obs, "b_actions": act, "b_logprobs": logprobs, "b_advantages": adv, "b_returns": returns, "b_values": values}
-        batch = {k: v.to(device).contiguous() for k, v in batch.items()}
-        inds, z = inds.to(device), z.to(device).contiguous()
-        g64, s64, t = minibatch_grad(net, batch, inds, cfg, z, torch.float64)
-        near = ((t.ratio - (1 - c)).abs() < 1e-6) | ((t.ratio - (1 + c)).abs() < 1e-6) | (t.adv.abs() < 1e-6)
-        near |= ((t.dv.abs() - c).abs() < 1e-6)
-        if cfg.clip_vloss:
-            near |= ((t.dv.abs() > c) & ((t.v_unclipped - t.v_clipped).abs() < 1e-6))
-        if not bool(near.any()):
+
+        def attach(t, batch, inds):
             t.pre_min, t.var_min = float(pre_min.min()), float(var_min.min())
-            t.rows, t.redrawn_relu, t.redrawn_variance = B, redrawn_relu, redrawn_variance
-            out = (net, batch, inds, z, g64, s64, t)
-            if cache:
-                _CASES[key] = out
-            return out
-    raise AssertionError("could not build a case without samples at a branch point")
+            t.rows, t.redrawn_relu, t.redrawn_variance = obs.shape[0], redrawn[0], redrawn[1]
+        return [p.detach() for p in all_tensors(net64)[:13]], y64, attach
+    return G.build_case(D, M, mode, cfg, seed, device, lambda: make_net(N, ed, blocks, use_resid, seed=seed, device=device), encode64,
+                        minibatch_grad, key=("transformer", N, ed, blocks, use_resid) if cache else None)
 
 
-def kernel_grad(net, batch, inds, cfg, z, **kw):
-    import torch
-    from evacuation_amd import trainer
-    stats = trainer.transformer_minibatch_grad(net, batch, inds, cfg, rpo_noise=z, **kw)
-    torch.cuda.synchronize()
-    return [p.grad.clone() for p in all_tensors(net)], stats.clone()
-
-
-def fake_trainer(net, cfg):
-    return SimpleNamespace(net=net, cfg=cfg)
+kernel_grad = G.kernel_grad_of("transformer_minibatch_grad")
 
 
 def tensor_errors(got, g64, blocks):
