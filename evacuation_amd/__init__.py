@@ -18,7 +18,7 @@ __all__ = ["EnvConfig", "EnvWrappersConfig", "Status", "setup_env", "EvacuationE
            "ShardedEvacuationEnv", "SplitBatchEnv", "NormalizedVectorEnv", "HostVectorEnv", "RandomAgent", "KernelOptions", "kernel_options",
            "RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad", "DeviceAdam", "rpo_minibatch_step", "rpo_update",
            "deepsets_minibatch_grad", "deepsets_kernel_grad", "WacuumCleaner", "PolicyEvaluator", "PopulationEvaluator", "EvaluationResult",
-           "PolicyPopulation", "PopulationAdam", "PopulationTrainer", "rpo_update_population"]
+           "PolicyPopulation", "PopulationAdam", "PopulationTrainer", "rpo_update_population", "episode_to_memory"]
 
 
 def __getattr__(name):   # lazy: keeps `import evacuation_amd` light and torch-free for config users
@@ -56,4 +56,7 @@ def __getattr__(name):   # lazy: keeps `import evacuation_amd` light and torch-f
     if name in ("PolicyPopulation", "PopulationAdam", "PopulationTrainer", "rpo_update_population"):   # S learners in one set of launches
         from . import population as _population
         return getattr(_population, name)
+    if name == "episode_to_memory":      # one episode of a recorded evaluation in the reference's frame format
+        from .trajectory import episode_to_memory
+        return episode_to_memory
     raise AttributeError(name)

@@ -64,6 +64,11 @@ class EvacTransformer(C.Structure):
         ("ln_eps", C.c_float), ("blocks", EvacTransformerBlock * 2)]
 
 
+class EvacEvalCapture(C.Structure):
+    """evac_eval_capture_t: where evac_policy_evaluate*_capture record the frames of envs 0..capture_envs-1"""
+    _fields_ = [("capture_envs", C.c_int32), ("max_frames", C.c_int32), ("frames", C.c_void_p), ("starts", C.c_void_p)]
+
+
 class EvacDeepSetsGrads(C.Structure):
     """evac_deepsets_grads_t: where evac_deepsets_minibatch_grad writes the gradients of the encoder's six tensors"""
     _fields_ = [(f, C.c_void_p) for f, _ in EvacDeepSets._fields_[2:]]
@@ -211,6 +216,11 @@ SIGNATURES = {
        for suffix, struct in (("_deepsets", EvacDeepSets), ("_transformer", EvacTransformer))
        for what, front in (("rollout", [_P, C.c_int32, C.POINTER(EvacMlpPolicy)] + [_P] * 11 + [C.c_float] * 4),
                            ("evaluate", [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float]))},
+    # the recording evaluation: the counterpart's arguments with evac_eval_capture_t in front of the stream
+    **{f"evac_policy_evaluate{suffix}_capture": (
+        C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float] + encoder +
+        [C.POINTER(EvacEvalCapture), _P])
+       for suffix, encoder in (("", []), ("_deepsets", [C.POINTER(EvacDeepSets)]), ("_transformer", [C.POINTER(EvacTransformer)]))},
     "evac_gae": (C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
     # the gradient entries: the linear network's, and an encoder's with its struct after the policy and its gradients' after the
     # policy's; a step has the optimiser's arguments behind the gradient's

@@ -1543,6 +1543,13 @@ static double as_written(float v) {
     }
     return (double)v;
 }
+// The scripted agent's turning points: extent - SWITCH_DISTANCE_TO_LEADER / 2 + step_size in double, rounded once
+// (baseline_wacuum_cleaner.py:18-28, constants.py:35), from the settings as the caller wrote them (as_written)
+static void vacuum_turning_points(evac_handle_t h, float& thr_x, float& thr_y) {
+    const double step = as_written(h->cfg.step_size);
+    thr_x = (float)(as_written(h->cfg.width) - 0.2 / 2 + step);
+    thr_y = (float)(as_written(h->cfg.height) - 0.2 / 2 + step);
+}
 
 // ---- evac_policy_evaluate: whole episodes under a fixed agent, one record per finished episode (evac_evaluate.h) ----
 // ... and evac_policy_evaluate_population (strides set, n_learners >= 1): the same checks, the learners' workgroups in one launch.
@@ -1567,11 +1574,7 @@ static int policy_evaluate(evac_handle_t h, const char* what, int32_t n_learners
     // (parts / chained / persistent handles: joined first, then ONE kernel on `stream` over the whole batch)
     if (const int st = settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
     DeviceGuard g(h->device);
-    // the sweep's turning points: extent - SWITCH_DISTANCE_TO_LEADER / 2 + step_size in double, rounded once
-    // (baseline_wacuum_cleaner.py:18-28, constants.py:35), from the settings as the caller wrote them (as_written)
-    const double step = as_written(h->cfg.step_size);
-    ev.thr_x = (float)(as_written(h->cfg.width) - 0.2 / 2 + step);
-    ev.thr_y = (float)(as_written(h->cfg.height) - 0.2 / 2 + step);
+    vacuum_turning_points(h, ev.thr_x, ev.thr_y);
     const dim3 grid((unsigned)policy_wgs(h->p.n_envs)), block(evac::PolicyFamily::kBlock);
     const bool grav = h->p.obs_pos == EVAC_POS_GRAV, norm = norm_state != nullptr, def = h->default_cfg;
     if (strides) {
@@ -1609,7 +1612,7 @@ int evac_policy_evaluate_population(evac_handle_t h, int32_t n_learners, const e
 
 }  // extern "C"
 
-// ---- evac_handle_host.h: the handle for the entries of other translation units (evac_deepsets_api.hip) ----
+// ---- evac_handle_host.h: the handle for the entries of other translation units (evac_deepsets_api.hip, ...) ----
 namespace evac_host {
 
 int handle_begin(evac_handle_t h, const char* what, HandleView* out) {
@@ -1622,5 +1625,6 @@ int handle_begin(evac_handle_t h, const char* what, HandleView* out) {
 int handle_settle(evac_handle_t h, hipStream_t stream) { return settle(h, stream); }
 int handle_fail(evac_handle_t h, int code, const std::string& msg) { return fail(h, code, msg); }
 int handle_check_launch(evac_handle_t h, const char* what) { return check_launch(h, what); }
+void handle_turning_points(evac_handle_t h, float* thr_x, float* thr_y) { vacuum_turning_points(h, *thr_x, *thr_y); }
 
 }  // namespace evac_host

@@ -1,7 +1,7 @@
 // Host side of the deep-sets leader (include/evac.h: evac_policy_rollout_deepsets, evac_policy_evaluate_deepsets; kernels in
 // evac_deepsets.h): the encoder's six tensors beside the actor-critic's thirteen.  The two entries' bodies -- the checks in their
 // order, the handle, the launch -- are evac_handle_host.h's encoder_rollout / encoder_evaluate, which evac_transformer_api.hip
-// shares; this unit holds what is the set encoder's own: its limits, its check, its kernels.
+// shares; this unit holds what is the set encoder's own: its limits and its kernels (its check: evac_deepsets_host.h).
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -10,6 +10,7 @@
 
 #define EVAC_TEMPLATE_KERNELS_ONLY      // (evac_device.h: its plain kernels live in evac_api.hip)
 #include "evac_deepsets.h"
+#include "evac_deepsets_host.h"
 #include "evac_handle_host.h"
 #include "evac_host.h"
 
@@ -18,25 +19,12 @@ static_assert(sizeof(evac::Params) + 8 + sizeof(evac::PolicyArgs) + sizeof(evac:
 static_assert(sizeof(evac::PolicyFamily::Smem) + sizeof(evac::PolicySmem<false>) + sizeof(evac::EvalSmem) + sizeof(evac::DeepSetsSmem) <=
                   160 * 1024, "the deep-sets kernels' LDS beyond a CU's 160 KiB");
 
-static_assert(evac::kSetHidden == kSetEncoderHidden && evac::kSetMaxElemDim == kSetEncoderMaxElemDim,
-              "deepsets_check: the widths the deep-sets kernels take");
-
 namespace {
 
-// evac_handle_host.h's trait of an encoder.  `check` comes after the policy's thirteen tensors; every refusal of a set encoder
-// is EVAC_ERR_INVALID_ARGUMENT.
-struct DeepSetsEncoder {
-    using Struct = evac_deepsets_t;
-    using Args = evac::DeepSetsArgs;
+// evac_handle_host.h's trait of an encoder: the set encoder's check (evac_deepsets_host.h), this unit's names and kernels.
+struct DeepSetsEncoder : DeepSetsEncoderHost {
     static constexpr const char* kRollout = "evac_policy_rollout_deepsets";
     static constexpr const char* kEvaluate = "evac_policy_evaluate_deepsets";
-    static int check(const evac::Params& p, const evac_deepsets_t& S, evac::DeepSetsArgs& da, std::string& why) {
-        // (the gravity observation's 6 floats are no whole number of rows for any N >= 5, and no set for the others)
-        const bool rows_fit = p.obs_pos != EVAC_POS_GRAV && (int64_t)S.set_elem_dim * (p.n_ped + 2) == (int64_t)p.obs_dim;
-        da = evac::DeepSetsArgs{S.phi_w1, S.phi_b1, S.phi_w2, S.phi_b2, S.rho_w, S.rho_b, (int)S.set_elem_dim};
-        why = deepsets_check(S, p.obs_dim, p.n_ped, rows_fit);
-        return why.empty() ? EVAC_OK : EVAC_ERR_INVALID_ARGUMENT;
-    }
     static auto rollout_kernel(bool norm, bool def) { return EVAC_PICK_BOOL2(evac::k_policy_rollout_deepsets, norm, def); }
     static auto evaluate_kernel(bool norm, bool def) { return EVAC_PICK_BOOL2(evac::k_policy_evaluate_deepsets, norm, def); }
 };

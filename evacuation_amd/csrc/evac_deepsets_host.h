@@ -1,0 +1,30 @@
+// Host side of the deep-sets leader, the part the units that run it on a handle's envs share (evac_deepsets_api.hip: collection
+// and evaluation; evac_capture_api.hip: the recording evaluation): the set encoder against the handle, as evac_handle_host.h's
+// trait of an encoder asks for it.  A unit derives its trait from this and adds its entries' names and kernels.
+#pragma once
+
+#include <cstdint>
+#include <string>
+
+#include "evac_deepsets.h"
+#include "evac_host.h"
+
+static_assert(evac::kSetHidden == kSetEncoderHidden && evac::kSetMaxElemDim == kSetEncoderMaxElemDim,
+              "deepsets_check: the widths the deep-sets kernels take");
+
+namespace {
+
+// `check` comes after the policy's thirteen tensors; every refusal of a set encoder is EVAC_ERR_INVALID_ARGUMENT.
+struct DeepSetsEncoderHost {
+    using Struct = evac_deepsets_t;
+    using Args = evac::DeepSetsArgs;
+    static int check(const evac::Params& p, const evac_deepsets_t& S, evac::DeepSetsArgs& da, std::string& why) {
+        // (the gravity observation's 6 floats are no whole number of rows for any N >= 5, and no set for the others)
+        const bool rows_fit = p.obs_pos != EVAC_POS_GRAV && (int64_t)S.set_elem_dim * (p.n_ped + 2) == (int64_t)p.obs_dim;
+        da = evac::DeepSetsArgs{S.phi_w1, S.phi_b1, S.phi_w2, S.phi_b2, S.rho_w, S.rho_b, (int)S.set_elem_dim};
+        why = deepsets_check(S, p.obs_dim, p.n_ped, rows_fit);
+        return why.empty() ? EVAC_OK : EVAC_ERR_INVALID_ARGUMENT;
+    }
+};
+
+}  // namespace

@@ -33,6 +33,77 @@ struct EvalSmem {
     int n_done[PolicyFamily::kEnvsPerBlock];       // episodes finished, per env of the workgroup
 };
 
+// Recording for rendering (include/evac.h: evac_eval_capture_t): the frames of envs 0 .. capture_envs - 1, in capture_state's
+// layout (evac_device.h).  frames[f] is the state after the env's step f, counted from the env's first step of the evaluation and
+// before any reset (Pedestrians.save / Agent.save in step); starts[k] is the state episode k begins with (Pedestrians.save in reset).
+struct EvalCaptureArgs {
+    float* frames;                        // [max_frames][capture_envs][N + 1][3]
+    float* starts;                        // [n_episodes][capture_envs][N + 1][3]
+    int capture_envs, max_frames;
+};
+
+struct EvalCaptureSmem {
+    EvalCaptureArgs a;                             // (read back where used, as EvalSmem::a)
+    // per env of the workgroup, set when the launch begins: where the frame of its step 0 of this launch goes (the env's own
+    // column of frames: the row of step t is t rows of all K envs further on), how many steps of this launch still have a row
+    // (0: the env is not recorded, or is past max_frames), and the env's column of starts (NULL: not recorded)
+    struct Env {
+        float* first;
+        float* start;
+        int rows;
+    } env[PolicyFamily::kEnvsPerBlock];
+};
+
+// The capture policy of policy_evaluate_body: none (the default; no code) ...
+struct NoCapture {
+    static constexpr bool kOn = false;
+};
+// ... or the frames above.  Arguments and the env's place in the frames live in LDS, as EvalSmem's n_done does: the step takes
+// every register, so a step reads back a pointer and a count and forms the row's address in scalar registers.
+struct EvalCapture {
+    static constexpr bool kOn = true;
+    EvalCaptureSmem& cs;
+    const EvalCaptureArgs& ka;
+
+    // by the whole workgroup, before the staging barrier (beside es.a)
+    __device__ __forceinline__ void stage() const {
+        if (threadIdx.x == 0) cs.a = ka;
+    }
+    // the wave's env starts this launch after `steps` steps of the evaluation
+    __device__ __forceinline__ void begin(const Params& p, const PolicyFamily::Ctx& w, int steps) const {
+        if (w.owner) {
+            const EvalCaptureArgs& a = cs.a;
+            const bool recorded = w.env < a.capture_envs;
+            cs.env[w.slot].first = a.frames + (((size_t)steps * a.capture_envs + w.env) * (p.n_ped + 1)) * 3;
+            cs.env[w.slot].start = recorded ? a.starts + ((size_t)w.env * (p.n_ped + 1)) * 3 : nullptr;
+            cs.env[w.slot].rows = recorded && steps < a.max_frames ? a.max_frames - steps : 0;
+        }
+        PolicyFamily::sync();
+    }
+    // At the top of every step: the lane's indices pass through an empty asm, so what is derived from them (LDS addresses, row
+    // offsets) is formed again inside the step and not kept in vector registers across it.  Those are the registers the
+    // capture's stores take: without this the encoder kernels with a normaliser spill.  The values do not change.
+    __device__ __forceinline__ void relieve(PolicyFamily::Ctx& w) const { asm volatile("" : "+v"(w.lane), "+v"(w.i)); }
+    // What LDS gives back is the same in every lane of the wave: read into scalar registers
+    static __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+    static __device__ __forceinline__ float* uni(float* ptr) {
+        const unsigned long long u = (unsigned long long)ptr;
+        return (float*)(((unsigned long long)(unsigned)uni((int)(u >> 32)) << 32) | (unsigned)uni((int)u));
+    }
+    // the state episode k < n_episodes begins with
+    __device__ __forceinline__ void start(const Params& p, const PolicyFamily::Ctx& w, bool active, const Ped& q, const Env& e, int k) const {
+        float* const col = uni(cs.env[w.slot].start);
+        if (col) capture_state(p, col, uni(cs.a.capture_envs), uni(k), 0, w.i, active, w.owner, q, e);     // (env 0: as in step)
+    }
+    // the state after step t of this launch, before any reset
+    __device__ __forceinline__ void step(const Params& p, const PolicyFamily::Ctx& w, bool active, const Ped& q, const Env& e, int t) const {
+        const EvalCaptureSmem::Env& c = cs.env[w.slot];
+        if (uni(t) >= uni(c.rows)) return;
+        // (`first` is the env's own column: env 0 of the K that capture_state strides over)
+        capture_state(p, uni(c.first), uni(cs.a.capture_envs), uni(t), 0, w.i, active, w.owner, q, e);
+    }
+};
+
 // The reference's sweep baseline (baseline_wacuum_cleaner.py:7-82) as a state machine over the leader's position alone:
 //   climb   until y >= thr_y (then one step right, and sweep)
 //   sweep   right until x >= thr_x, or left until x <= -thr_x; at a turn: one step down, the direction flips and the next 25 steps
@@ -98,13 +169,16 @@ __device__ __forceinline__ void eval_observation(const Params& p, PolicyFamily::
 // SHIFTED (the population form, k_evaluate_population): as policy_rollout_body's -- the wave's env is its place in the launch plus
 // `env_shift`, and it has work while that is below `env_end`; the env's global id, which keys every Philox stream of the body, is
 // further back by `id_shift` (a learner's share with the ids of learner 0's: the same episodes for every learner).
-template <bool POLICY, bool GRAV, bool NORM, class ENC = NoEncoder, bool SHIFTED = false>
+// CAP: the capture policy (NoCapture; EvalCapture, evac_capture_api.hip's kernels).  A launch sequence writes the frames of one long
+// launch: the row comes from the progress word and nothing new is carried.
+template <bool POLICY, bool GRAV, bool NORM, class ENC = NoEncoder, bool SHIFTED = false, class CAP = NoCapture>
 __device__ __forceinline__ void policy_evaluate_body(PolicyFamily::Smem& sm, PolicySmem<GRAV>* psp, EvalSmem& es, const Params& p,
                                                      const PolicyArgs& ka, const EvalArgs& kev, const ENC& enc = ENC{},
-                                                     int env_shift = 0, int env_end = 0, int id_shift = 0) {
+                                                     int env_shift = 0, int env_end = 0, int id_shift = 0, const CAP& cap = CAP{}) {
     using F = PolicyFamily;
     if constexpr (POLICY) stage_policy<GRAV>(*psp, ka, NormArgs{nullptr, 0.f, 0.f, 0.f, 0.f});
     if constexpr (ENC::kOn) enc.stage();
+    if constexpr (CAP::kOn) cap.stage();
     if (threadIdx.x == 0) es.a = kev;
     __syncthreads();
     typename F::Ctx w(sm);
@@ -135,6 +209,10 @@ __device__ __forceinline__ void policy_evaluate_body(PolicyFamily::Smem& sm, Pol
     Ped q;
     Env e;
     load_env(p, env, w.i, active, q, e);
+    if constexpr (CAP::kOn) {
+        cap.begin(p, w, pr.y);
+        if (pr.x == 0 && pr.y == 0) cap.start(p, w, active, q, e, 0);       // the evaluation's first launch for this env
+    }
     uint32_t gid = p.env_id_offset + (uint32_t)env;
     if constexpr (SHIFTED) gid = p.env_id_offset + (uint32_t)(env - id_shift);
     float* xs = nullptr;
@@ -144,6 +222,7 @@ __device__ __forceinline__ void policy_evaluate_body(PolicyFamily::Smem& sm, Pol
                                                    // launch's start and every reset take it by a full reduction
     int t = 0;                                     // steps of this launch
     while (t < ev.max_steps) {
+        if constexpr (CAP::kOn) cap.relieve(w);
         float a0, a1;
         if constexpr (POLICY) {
             PolicySmem<GRAV>& ps = *psp;
@@ -185,6 +264,7 @@ __device__ __forceinline__ void policy_evaluate_body(PolicyFamily::Smem& sm, Pol
         if (ballot(needs_row(p, q.st)) != 0ull) nz = philox_noise(p, gid, w.i, e.total);
         StepOut o;
         step_env<F, GRAV>(p, w, active, q, e, agent_direction(p, a0, a1), nz, o);
+        if constexpr (CAP::kOn) cap.step(p, w, active, q, e, t);
         t += 1;
         o6[0] = e.ax; o6[1] = e.ay; o6[2] = o.ex; o6[3] = o.ey; o6[4] = o.gx; o6[5] = o.gy;
         fresh = false;
@@ -199,6 +279,9 @@ __device__ __forceinline__ void policy_evaluate_body(PolicyFamily::Smem& sm, Pol
             }
             s0 = s1 = 0;                         // a scripted agent starts afresh with every episode
             reset_env(p, active, philox_reset_draw(p, gid, w.i, e.n_resets), q, e);
+            if constexpr (CAP::kOn) {
+                if (n_done + 1 < ev.n_episodes) cap.start(p, w, active, q, e, n_done + 1);
+            }
             F::invalidate(w);
             fresh = true;
             if (n_done + 1 >= ev.n_episodes) break;

@@ -1,6 +1,7 @@
 // What the entries that run a network on a handle's envs share (evac_api.hip: evac_policy_rollout*, evac_policy_evaluate*;
-// evac_deepsets_api.hip, evac_transformer_api.hip: their forms with an encoder).  The handle's struct stays evac_api.hip's own:
-// the four handle_* functions are defined there and are not exported from the library.  Below them, host-only and inline: what
+// evac_deepsets_api.hip, evac_transformer_api.hip: their forms with an encoder; evac_capture_api.hip: the evaluation entries that
+// record frames).  The handle's struct stays evac_api.hip's own:
+// the handle_* functions are defined there and are not exported from the library.  Below them, host-only and inline: what
 // every collection entry and every evaluation entry refuses, the one-wave limit, a population's shares of the envs, and the grid.
 // Each returns the text that follows the entry's name in its message (empty: accepted), as mlp_policy_check does; the entry
 // reports it through its own fail, at its own place in its order of checks.  Last, the whole bodies of the encoder entries as two
@@ -31,6 +32,8 @@ EVAC_HOST_LOCAL int handle_settle(evac_handle_t h, hipStream_t stream);
 // `msg` becomes evac_last_error(h); returns `code`
 EVAC_HOST_LOCAL int handle_fail(evac_handle_t h, int code, const std::string& msg);
 EVAC_HOST_LOCAL int handle_check_launch(evac_handle_t h, const char* what);
+// The scripted agent's turning points for this handle's room (EvalArgs::thr_x, thr_y)
+EVAC_HOST_LOCAL void handle_turning_points(evac_handle_t h, float* thr_x, float* thr_y);
 #undef EVAC_HOST_LOCAL
 
 }  // namespace evac_host
@@ -84,6 +87,16 @@ inline std::string evaluate_check(int32_t agent, int32_t n_episodes, int32_t max
     return {};
 }
 
+// What a recording evaluation entry refuses of its capture, after its counterpart's own checks, and the arguments its kernel takes.
+inline std::string capture_check(const evac_eval_capture_t* c, int n_envs, evac::EvalCaptureArgs& ca) {
+    if (!c) return ": capture is NULL";
+    if (c->capture_envs < 1 || c->capture_envs > n_envs) return ": capture_envs must be in 1.." + std::to_string(n_envs);
+    if (c->max_frames < 1) return ": max_frames must be >= 1";
+    if (!c->frames || !c->starts) return ": frames / starts is NULL";
+    ca = evac::EvalCaptureArgs{c->frames, c->starts, (int)c->capture_envs, (int)c->max_frames};
+    return {};
+}
+
 // A population's equal shares of a handle's envs into `q`: the learners' number, the envs divisible by it, every stride at least
 // its tensor.
 inline std::string learner_shares(int n_envs, int32_t n_learners, const evac_mlp_policy_strides_t* strides, int32_t obs_dim,
@@ -104,6 +117,7 @@ inline std::string learner_shares(int n_envs, int32_t n_learners, const evac_mlp
 //   check(p, S, args, why)           the encoder against the handle, after the policy's own check: EVAC_OK and `args` filled, or
 //                                    the code with the text that follows the entry's name in `why`
 //   rollout_kernel(norm, def), evaluate_kernel(norm, def)      the instantiations of the unit's two kernel templates
+// and, in the unit of the recording evaluation (evac_capture_api.hip) alone: kCapture, capture_kernel(norm).
 // What both entries refuse of the two networks, in this order: no policy, no encoder, the thirteen tensors (into `a`), Enc's own.
 template <class Enc>
 inline int encoder_networks_check(const evac::Params& p, const evac_mlp_policy_t* policy, const typename Enc::Struct* encoder,
@@ -137,13 +151,16 @@ inline int encoder_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_poli
     return evac_host::handle_check_launch(h, w.c_str());
 }
 
-// evac_policy_evaluate_<encoder>: the agent's code first, the one-wave limit last.
-template <class Enc>
+// evac_policy_evaluate_<encoder>: the agent's code first, the one-wave limit last.  CAPTURE: evac_policy_evaluate_<encoder>_capture,
+// the same with capture_check behind the one-wave limit and the capture behind the kernel's arguments.
+template <class Enc, bool CAPTURE = false>
 inline int encoder_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy, int32_t n_episodes, int32_t max_steps,
                             int32_t* progress, evac_episode_stats_t* episodes_out, const double* norm_state, float obs_clip, float epsilon,
-                            const typename Enc::Struct* encoder, void* stream) {
+                            const typename Enc::Struct* encoder, void* stream, const evac_eval_capture_t* capture = nullptr) {
     using evac_host::handle_fail;
-    const std::string w = Enc::kEvaluate;
+    std::string w;
+    if constexpr (CAPTURE) w = Enc::kCapture;
+    else w = Enc::kEvaluate;
     evac_host::HandleView v;
     if (const int rc = evac_host::handle_begin(h, w.c_str(), &v); rc != EVAC_OK) return rc;
     if (agent == EVAC_AGENT_VACUUM_CLEANER)
@@ -157,10 +174,18 @@ inline int encoder_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_polic
     if (!why.empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
     if (const int rc = encoder_networks_check<Enc>(v.p, policy, encoder, a, ea, why); rc != EVAC_OK) return handle_fail(h, rc, w + why);
     if (!(why = one_wave_check(v.p)).empty()) return handle_fail(h, EVAC_ERR_UNSUPPORTED, w + why);
+    evac::EvalCaptureArgs ca{};
+    if constexpr (CAPTURE) {
+        if (!(why = capture_check(capture, v.p.n_envs, ca)).empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
+    }
     if (const int st = evac_host::handle_settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
     DeviceGuard g(v.device);
-    hipLaunchKernelGGL(Enc::evaluate_kernel(norm_state != nullptr, v.default_cfg), dim3((unsigned)policy_wgs(v.p.n_envs)),
-                       dim3(evac::PolicyFamily::kBlock), 0, (hipStream_t)stream, v.p, a, ev, ea);
+    const dim3 grid((unsigned)policy_wgs(v.p.n_envs)), block(evac::PolicyFamily::kBlock);
+    if constexpr (CAPTURE) {
+        hipLaunchKernelGGL(Enc::capture_kernel(norm_state != nullptr), grid, block, 0, (hipStream_t)stream, v.p, a, ev, ea, ca);
+    } else {
+        hipLaunchKernelGGL(Enc::evaluate_kernel(norm_state != nullptr, v.default_cfg), grid, block, 0, (hipStream_t)stream, v.p, a, ev, ea);
+    }
     return evac_host::handle_check_launch(h, w.c_str());
 }
 

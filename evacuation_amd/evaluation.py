@@ -23,11 +23,14 @@ _SUMMARY_KEYS = ("episode_reward_mean", "episode_reward_std", "episode_length_me
 @dataclasses.dataclass
 class EvaluationResult:
     """``episodes``: ``STATS_FIELDS`` -> float32 [n_episodes, E] and ``STATS_INT_FIELDS`` -> int32 [n_episodes, E] (episode k
-    of env e); ``steps``: int32 [E], the env-steps each env took; ``n_pedestrians``: the room's N."""
+    of env e); ``steps``: int32 [E], the env-steps each env took; ``n_pedestrians``: the room's N; ``capture``: ``None``, or
+    the recorded frames of envs ``0..K-1`` (``policy_evaluate``'s ``capture``: ``{"frames": [F, K, N+1, 3], "starts":
+    [n_episodes, K, N+1, 3]}``), which ``episode_memory`` cuts into episodes."""
 
     episodes: Dict[str, torch.Tensor]
     steps: torch.Tensor
     n_pedestrians: int
+    capture: Optional[Dict[str, torch.Tensor]] = None
 
     @classmethod
     def from_records(cls, records: torch.Tensor, steps: torch.Tensor, n_pedestrians: int) -> "EvaluationResult":
@@ -36,6 +39,19 @@ class EvaluationResult:
         ints = stats_int_view(records)
         eps.update({k: ints[..., i] for i, k in enumerate(STATS_INT_FIELDS)})
         return cls(eps, steps, int(n_pedestrians))
+
+    def episode_memory(self, env: int, episode: int, status_cls=None):
+        """``(pedestrians.memory, agent.memory)`` of episode ``episode`` of recorded env ``env`` in the reference's format
+        (``trajectory.episode_to_memory``; feed them to ``trajectory.feed_reference_env``): with ``L`` the episode's recorded
+        length, ``L + 1`` pedestrian frames -- the start state first -- and ``L`` leader positions.  ``IndexError``: no
+        capture was made, ``env >= K``, or an episode the env has not finished; ``ValueError``: frames beyond ``max_frames``."""
+        from .trajectory import episode_to_memory
+        if self.capture is None:
+            raise IndexError("episode_memory: this evaluation recorded no frames (evaluate(..., capture_envs=K))")
+        frames, starts = self.capture["frames"], self.capture["starts"]
+        if not 0 <= int(env) < int(frames.shape[1]):
+            raise IndexError(f"episode_memory: env {int(env)} was not recorded (envs 0..{int(frames.shape[1]) - 1} were)")
+        return episode_to_memory(frames, starts, self.episodes["episode_length"][:, int(env)], env, episode, status_cls)
 
     def summary(self) -> Dict[str, float]:
         """Python floats over all episodes of all envs: mean and (population) std of ``episode_reward``, mean
@@ -113,14 +129,25 @@ class PolicyEvaluator(_Evaluator):
         self.num_envs = self.env.num_envs
 
     def evaluate(self, agent, n_episodes: int = 1, *, deterministic: bool = True, norm_state: Optional[torch.Tensor] = None,
-                 obs_clip: float = 1.0, epsilon: float = 1e-8, max_steps_per_launch: int = 4096) -> EvaluationResult:
+                 obs_clip: float = 1.0, epsilon: float = 1e-8, max_steps_per_launch: int = 4096, capture_envs: int = 0,
+                 max_frames: Optional[int] = None) -> EvaluationResult:
         """``n_episodes`` whole episodes per env under ``agent`` (a network with RPOLinearNetwork's attribute names -- with the
         reference's set encoder ``deep_sets`` or attention encoder ``embedding`` in front, if it has one -- or
         ``"vacuum_cleaner"``).  ``norm_state``: the trainer's statistics ([rows, 3 D + 4] float64, any number of rows: row
         ``e mod rows`` serves env ``e`` -- the trainer's normaliser is per env and the evaluation batch need not have its
         size), applied frozen.  Launches of at most ``max_steps_per_launch`` steps until every env has finished; the one host
-        read per launch is ``progress[:, 0].min()``."""
+        read per launch is ``progress[:, 0].min()``.  ``capture_envs = K > 0``: the frames of envs ``0..K-1`` are recorded in
+        the same launches (``policy_evaluate``'s ``capture``) and come back as ``result.capture`` -- ``max_frames`` rows per
+        env (default ``n_episodes x max_timesteps``, which every env fits), NaN where no step wrote -- for
+        ``result.episode_memory(env, episode)``."""
         env, E = self.env, self.num_envs
+        capture, K = None, int(capture_envs)
+        if K:
+            F = int(n_episodes) * int(env.env_config.max_timesteps) if max_frames is None else int(max_frames)
+            if not 1 <= K <= E or F < 1 or int(n_episodes) < 1:
+                raise ValueError(f"evaluate: capture_envs must be in 0..{E} and max_frames, n_episodes >= 1, got {K}, {F}, {n_episodes}")
+            nan = lambda rows: torch.full((rows, K, env.n_ped + 1, 3), float("nan"), dtype=torch.float32, device=env.device)  # noqa: E731
+            capture = {"frames": nan(F), "starts": nan(int(n_episodes))}       # (once per evaluation: every launch gets the same two)
         norm = None
         if norm_state is not None:
             W = 3 * env.obs_dim + 4
@@ -129,8 +156,10 @@ class PolicyEvaluator(_Evaluator):
             rows = torch.arange(E, device=env.device) % norm_state.shape[0]
             norm = (norm_state.to(env.device)[rows].contiguous(), float(obs_clip), float(epsilon))
         progress, out = self._run(n_episodes, max_steps_per_launch, lambda progress, out: env.policy_evaluate(
-            agent, n_episodes, max_steps_per_launch, progress, out, deterministic=deterministic, _norm=norm))
-        return EvaluationResult.from_records(out, progress[:, 1].clone(), env.n_ped)
+            agent, n_episodes, max_steps_per_launch, progress, out, deterministic=deterministic, _norm=norm, capture=capture))
+        result = EvaluationResult.from_records(out, progress[:, 1].clone(), env.n_ped)
+        result.capture = capture
+        return result
 
 
 def check_population_norm_state(norm_state, num_learners: int, obs_dim: int):

@@ -819,16 +819,17 @@ class RPOTrainer:
             self.evaluator = PolicyEvaluator(base.env_config, base.wrap_config, num_envs=n, seed=base.seed_value, device=base.device)
         return self.evaluator
 
-    def evaluate(self, n_episodes: int = 1, num_envs: Optional[int] = None, deterministic: bool = True):
+    def evaluate(self, n_episodes: int = 1, num_envs: Optional[int] = None, deterministic: bool = True, capture_envs: int = 0):
         """``n_episodes`` whole episodes per env of the current network on an evaluation batch of its own: the mean action
         (``deterministic``), the training env's observation statistics frozen at a copy of what they are now (when the
-        training env normalises).  Nothing of the training env is touched.  Returns an ``EvaluationResult``."""
+        training env normalises).  Nothing of the training env is touched.  Returns an ``EvaluationResult``; with
+        ``capture_envs = K > 0`` it holds the frames of the batch's envs ``0..K-1`` (``EvaluationResult.episode_memory``)."""
         ev = self.make_evaluator(num_envs)
         kw = {}
         if hasattr(self.env, "norm_state"):
             kw = {"norm_state": self.env.norm_state.clone(), "obs_clip": self.env.obs_clip, "epsilon": self.env.epsilon}
         with torch.no_grad():
-            return ev.evaluate(self.net, n_episodes, deterministic=deterministic, **kw)
+            return ev.evaluate(self.net, n_episodes, deterministic=deterministic, capture_envs=capture_envs, **kw)
 
     def learn(self, total_timesteps: Optional[int] = None, callback: Optional[Callable[[dict], None]] = None, *,
               eval_every: Optional[int] = None, eval_episodes: int = 1) -> list:

@@ -10,6 +10,10 @@ float array and one (N,) array of ``Status`` members per frame; ``Pedestrians.sa
 tensor ``[T, K, N+1, 3]``; ``capture_to_memory`` turns one env of it into those two dicts, so that the reference's
 unchanged matplotlib code can be fed from the GPU env (``feed_reference_env``).  Rendering itself stays on the host
 and out of scope.
+
+An evaluation records the same rows per env-step of the whole evaluation, and every episode's start state beside them
+(``policy_evaluate(capture=...)``: ``frames`` [F, K, N+1, 3], ``starts`` [n_episodes, K, N+1, 3]); ``episode_to_memory`` cuts one
+episode of one env out of them, through ``capture_to_memory``.
 """
 from __future__ import annotations
 
@@ -47,6 +51,33 @@ def capture_to_memory(rollout: dict, env_index: int = 0, initial: Optional[dict]
         ped_mem["statuses"].append(np.array([by_code[int(c)] for c in st[t]]))
     agent_mem = {"position": [agent[t].copy() for t in range(agent.shape[0])]}
     return ped_mem, agent_mem
+
+
+def episode_to_memory(frames, starts, episode_lengths, env_index: int, episode: int, status_cls=None
+                      ) -> Tuple[Dict[str, List[np.ndarray]], Dict[str, List[np.ndarray]]]:
+    """``(pedestrians.memory, agent.memory)`` of episode ``episode`` of env ``env_index`` of a recorded evaluation.
+
+    ``frames`` [F, K, N+1, 3] and ``starts`` [n_episodes, K, N+1, 3] as ``policy_evaluate(capture=...)`` fills them;
+    ``episode_lengths``: the ``episode_length`` records of that env's finished episodes, in order.  With ``L`` the episode's
+    length and ``s`` the sum of the earlier ones, the pedestrians' lists hold ``starts[episode]`` and then frames
+    ``s .. s+L-1`` (``L + 1`` entries: the ``save()`` inside ``reset`` and one per step), the leader's list the ``L`` step
+    frames -- built by ``capture_to_memory``, so dtypes and ``Status`` members are its.  (An evaluation that begins at a reset,
+    as ``PolicyEvaluator``'s: a record's length counts from the episode's own clock.)  ``IndexError``: an env that was not
+    recorded or an episode the env has not finished; ``ValueError``: the episode's frames lie beyond ``F``."""
+    lengths = [int(v) for v in _np(episode_lengths).reshape(-1)]
+    env_index, episode = int(env_index), int(episode)
+    if not 0 <= env_index < int(frames.shape[1]):
+        raise IndexError(f"episode_to_memory: env {env_index} was not recorded (envs 0..{int(frames.shape[1]) - 1} were)")
+    if not 0 <= episode < min(len(lengths), int(starts.shape[0])) or lengths[episode] < 1:
+        raise IndexError(f"episode_to_memory: env {env_index} has not finished an episode {episode}")
+    first, length = sum(lengths[:episode]), lengths[episode]
+    if first + length > int(frames.shape[0]):
+        raise ValueError(f"episode_to_memory: episode {episode} of env {env_index} is frames {first}..{first + length - 1}, "
+                         f"and {int(frames.shape[0])} were recorded (max_frames)")
+    n = int(frames.shape[2]) - 1
+    rows, begin = frames[first:first + length, env_index:env_index + 1], starts[episode, env_index:env_index + 1]
+    rollout = {"positions": rows[:, :, :n, 0:2], "statuses": rows[:, :, :n, 2], "agent_positions": rows[:, :, n, 0:2]}
+    return capture_to_memory(rollout, 0, {"pos": begin[:, :n, 0:2], "status": begin[:, :n, 2]}, status_cls)
 
 
 def feed_reference_env(ref_env, ped_memory, agent_memory) -> None:

@@ -105,6 +105,26 @@ def check_evaluate_args(agent, n_episodes, max_steps, norm) -> None:
         raise ValueError(f"policy_evaluate: n_episodes and max_steps must be >= 1, got {n_episodes} and {max_steps}")
 
 
+def check_evaluate_capture(capture, n_episodes, num_envs, n_ped, device) -> int:
+    """The checks of ``policy_evaluate``'s ``capture`` that need no device work: a dict of two contiguous float32 tensors on
+    ``device``, ``frames`` [F, K, N + 1, 3] with ``F >= 1`` and ``starts`` [n_episodes, K, N + 1, 3], ``K`` in ``1..num_envs``.
+    Returns ``K``."""
+    if not isinstance(capture, dict) or "frames" not in capture or "starts" not in capture:
+        raise ValueError("policy_evaluate: capture must be a dict with the tensors \"frames\" and \"starts\"")
+    frames, starts = capture["frames"], capture["starts"]
+    if not isinstance(frames, torch.Tensor) or not isinstance(starts, torch.Tensor) or frames.dim() != 4 or int(frames.shape[0]) < 1:
+        raise ValueError(f"policy_evaluate: capture[\"frames\"] must be a tensor of shape [F >= 1, K, {n_ped + 1}, 3]")
+    k_cap = int(frames.shape[1])
+    if not 1 <= k_cap <= int(num_envs):
+        raise ValueError(f"policy_evaluate: capture records K = {k_cap} envs; K must be in 1..{int(num_envs)}")
+    for name, t, shape in (("frames", frames, (int(frames.shape[0]), k_cap, n_ped + 1, 3)),
+                           ("starts", starts, (int(n_episodes), k_cap, n_ped + 1, 3))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != device or not t.is_contiguous():
+            raise ValueError(f"policy_evaluate: capture[\"{name}\"]: expected contiguous torch.float32 tensor of shape {shape} on "
+                             f"{device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return k_cap
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -663,7 +683,7 @@ class BatchedEvacuationEnv:
         return out
 
     def policy_evaluate(self, agent, n_episodes: int, max_steps: int, progress: Optional[torch.Tensor] = None,
-                        out: Optional[torch.Tensor] = None, *, deterministic: bool = True, _norm=None):
+                        out: Optional[torch.Tensor] = None, *, deterministic: bool = True, _norm=None, capture=None):
         """Whole episodes per env under a FIXED agent, ONE kernel launch (``evac_policy_evaluate``): every env steps from its
         current state until it has finished ``n_episodes`` episodes or taken ``max_steps`` steps in this call, and writes one
         episode record per finished episode into ``out`` [n_episodes, E, 10] -- nothing else (no storage, no values).
@@ -676,11 +696,20 @@ class BatchedEvacuationEnv:
         ``_norm = (norm_state, obs_clip, epsilon)``: the trainer's observation statistics applied FROZEN (read only) -- see
         ``NormalizedVectorEnv.policy_evaluate``.  No host synchronisation; capturable; the weights are read when the kernel runs.
         A network with a set encoder (``deep_sets``) goes to ``evac_policy_evaluate_deepsets``, one with an attention encoder
-        (``embedding``) to ``evac_policy_evaluate_transformer`` (evaluation is eval mode: any dropout probability is taken)."""
+        (``embedding``) to ``evac_policy_evaluate_transformer`` (evaluation is eval mode: any dropout probability is taken).
+        ``capture``: a dict ``{"frames": [F, K, N + 1, 3], "starts": [n_episodes, K, N + 1, 3]}`` of float32 device tensors records
+        envs ``0..K-1`` for rendering, in the same launch (``evac_policy_evaluate*_capture``; nothing else changes): ``frames[f, e]``
+        is the state after the env's step ``f`` of the evaluation, before any reset -- rows ``0..N-1`` hold (x, y, status), row
+        ``N`` the leader, ``rollout``'s ``trajectory`` layout -- and ``starts[k, e]`` the state episode ``k`` begins with.  Steps
+        ``f >= F`` are not recorded and rows no step reached are left as they were; pass the same tensors to every call of an
+        evaluation.  ``evaluation.EvaluationResult.episode_memory`` cuts them into the reference's per-episode memory."""
         check_evaluate_args(agent, n_episodes, max_steps, _norm)
-        return self._policy_evaluate("policy_evaluate", agent, None, n_episodes, max_steps, progress, out, deterministic, 0, _norm)
+        if capture is not None:
+            check_evaluate_capture(capture, n_episodes, self.num_envs, self.n_ped, self.device)
+        return self._policy_evaluate("policy_evaluate", agent, None, n_episodes, max_steps, progress, out, deterministic, 0, _norm, capture)
 
-    def _policy_evaluate(self, what, agent, population, n_episodes, max_steps, progress, out, deterministic, shared_episodes, _norm):
+    def _policy_evaluate(self, what, agent, population, n_episodes, max_steps, progress, out, deterministic, shared_episodes, _norm,
+                         capture=None):
         """What ``policy_evaluate`` and ``policy_evaluate_population`` share, after their own checks of the agent: the one-wave
         limit, the learners' shares, the agent's code and structs, ``progress`` / ``out`` / the frozen statistics made or checked, and the call."""
         self._one_wave(what)
@@ -709,6 +738,14 @@ class BatchedEvacuationEnv:
         if population is not None:
             rc = self.lib.evac_policy_evaluate_population(self._h, int(population.num_learners), pol, C.byref(population.strides), code,
                                                           int(bool(shared_episodes)), *args, self._stream())
+        elif capture is not None:         # (checked by policy_evaluate: check_evaluate_capture)
+            frames, starts = capture["frames"], capture["starts"]
+            cap = _lib.EvacEvalCapture(int(frames.shape[1]), int(frames.shape[0]), frames.data_ptr(), starts.data_ptr())
+            if enc is not None:
+                rc = getattr(self.lib, f"evac_policy_evaluate{enc[0]}_capture")(self._h, code, pol, *args, C.byref(enc[1]), C.byref(cap),
+                                                                               self._stream())
+            else:
+                rc = self.lib.evac_policy_evaluate_capture(self._h, code, pol, *args, C.byref(cap), self._stream())
         elif enc is not None:
             rc = getattr(self.lib, "evac_policy_evaluate" + enc[0])(self._h, code, pol, *args, C.byref(enc[1]), self._stream())
         else:
@@ -718,7 +755,7 @@ class BatchedEvacuationEnv:
 
     def policy_evaluate_population(self, population, n_episodes: int, max_steps: int, progress: Optional[torch.Tensor] = None,
                                    out: Optional[torch.Tensor] = None, *, deterministic: bool = True, shared_episodes: bool = True,
-                                   _norm=None):
+                                   _norm=None, capture=None):
         """``policy_evaluate`` for the S learners of ``population`` (a ``PolicyPopulation``) in ONE launch
         (``evac_policy_evaluate_population``): learner s acts in envs ``[s E_l, (s + 1) E_l)`` of this env, ``E_l = num_envs / S``.
         Arguments and results are ``policy_evaluate``'s over the whole batch -- ``progress`` [S E_l, 4], ``out`` [n_episodes,
@@ -727,8 +764,11 @@ class BatchedEvacuationEnv:
         ``shared_episodes=True``: that env has this env's ``env_id_offset``, so env i of every learner sees the same reset draws
         and pedestrian noise (the learners are compared on the same episodes); ``False``: its offset is further by ``s E_l``,
         the ids of ``policy_rollout_population``.  The networks alone: a scripted agent has no learners (``policy_evaluate``),
-        and a population or net with a set encoder or an attention encoder is a ``ValueError``."""
+        and a population or net with a set encoder or an attention encoder is a ``ValueError``.  So is a ``capture``: recording
+        is ``policy_evaluate``'s, one network at a time."""
         from .policy import refuse_deepsets
+        if capture is not None:
+            raise ValueError("policy_evaluate_population: a capture cannot be given (policy_evaluate records one network's episodes)")
         refuse_deepsets(population, "policy_evaluate_population")
         for net in getattr(population, "nets", ()):
             refuse_deepsets(net, "policy_evaluate_population")

@@ -75,12 +75,14 @@ class NormalizedVectorEnv:
         return self.env.policy_rollout_population(population, n_steps, next_obs, next_done, out=out, gammas=gammas,
                                                   _norm=(self.norm_state, self.gamma, self.obs_clip, self.reward_clip, self.epsilon))
 
-    def policy_evaluate(self, agent, n_episodes: int, max_steps: int, progress=None, out=None, *, deterministic: bool = True):
+    def policy_evaluate(self, agent, n_episodes: int, max_steps: int, progress=None, out=None, *, deterministic: bool = True,
+                        capture=None):
         """``BatchedEvacuationEnv.policy_evaluate`` with this env's observation statistics applied FROZEN: the policy reads
         ``clip((x - mean) / sqrt(var + epsilon), +-obs_clip)`` of ``norm_state``, which is only read -- nothing is counted, and
-        the episode records stay raw.  A scripted agent reads no observation and runs on the raw env."""
+        the episode records stay raw.  A scripted agent reads no observation and runs on the raw env.  ``capture``: as there."""
         norm = None if isinstance(agent, str) else (self.norm_state, self.obs_clip, self.epsilon)
-        return self.env.policy_evaluate(agent, n_episodes, max_steps, progress, out, deterministic=deterministic, _norm=norm)
+        return self.env.policy_evaluate(agent, n_episodes, max_steps, progress, out, deterministic=deterministic, _norm=norm,
+                                        capture=capture)
 
     def final_info_list(self, infos):
         return self.env.final_info_list(infos)

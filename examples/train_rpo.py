@@ -10,6 +10,7 @@ minibatches in one host call (``evac_rpo_update``).  Prints the reference's ``SP
                                  [--network linear|deep_sets|transformer] [--gradient autograd|device]
                                  [--blocks 2] [--use-resid]
                                  [--eval-every 1] [--eval-episodes 1] [--baseline] [--seeds 1,2,3]
+                                 [--capture 2 --capture-out DIR]
                                  [--sweep learning_rate=1e-4,3e-4,1e-3 --sweep ent_coef=0,0.01]
 
 ``--network deep_sets`` trains the reference's set-encoder network (``policy.DeepSetsActorCritic``, RPODeepSetsEmbedding) on the
@@ -30,6 +31,12 @@ by ``evac_transformer_minibatch_grad`` (``trainer.transformer_kernel_grad``), an
 ``--eval-every K`` evaluates the leader every K updates (``RPOTrainer.evaluate``: whole episodes, the mean action, the observation
 statistics frozen) and prints the summary; ``--baseline`` prints the same line for the reference's scripted sweep baseline
 (baseline_wacuum_cleaner.py) on the same evaluator, i.e. on the same episodes.
+
+``--capture K --capture-out DIR`` evaluates the trained leader once more after the last update with the frames of the evaluation
+batch's envs ``0..K-1`` recorded in the same launches (``RPOTrainer.evaluate(capture_envs=K)``) and writes one
+``env<e>_episode<k>.npz`` per recorded env and episode: ``positions`` [L + 1, N, 2] float64 and ``statuses`` [L + 1, N] int64 (the
+start state first), ``agent_positions`` [L, 2] float32 -- the lists of ``EvaluationResult.episode_memory``, which
+``trajectory.feed_reference_env`` hands to the reference's drawing code.  It draws nothing.  Not with ``--seeds`` or ``--sweep``.
 
 ``--seeds a,b,c`` trains one learner per seed as a POPULATION (``PopulationTrainer``): ``--envs`` envs per learner in one env of
 ``len(seeds) x --envs``, every learner's collection in one launch and every learner's minibatch step in the four launches of one
@@ -84,6 +91,19 @@ def make_trainer(args, **hooks):
     if network == "transformer" and getattr(args, "gradient", "autograd") == "device":
         hooks.setdefault("grad_fn", transformer_kernel_grad)
     return RPOTrainer(env, net, cfg, **hooks)
+
+
+def write_episodes(result, n_envs, n_episodes, out_dir):
+    """One ``env<e>_episode<k>.npz`` per recorded env and episode of an ``EvaluationResult`` with a capture."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for e in range(n_envs):
+        for k in range(n_episodes):
+            ped, agent = result.episode_memory(e, k)
+            np.savez(os.path.join(out_dir, f"env{e}_episode{k}.npz"), positions=np.stack(ped["positions"]),
+                     statuses=np.array([[s.value for s in row] for row in ped["statuses"]], dtype=np.int64),
+                     agent_positions=np.stack(agent["position"]))
+    print(f"capture: {n_envs * n_episodes} episodes of {n_envs} envs written to {out_dir}")
 
 
 def parse_sweep(specs):
@@ -269,7 +289,11 @@ def main():
     ap.add_argument("--gradient", choices=("autograd", "device"), default="autograd",
                     help="with --network deep_sets / transformer: the gradient of its 19 / 13 + 16 per block tensors by torch autograd or "
                          "by evac_deepsets_minibatch_grad / evac_transformer_minibatch_grad")
+    ap.add_argument("--capture", type=int, default=0, metavar="K", help="after the last update, record envs 0..K-1 of one more evaluation")
+    ap.add_argument("--capture-out", type=str, default=None, metavar="DIR", help="with --capture: where the episodes' .npz files go")
     args = ap.parse_args()
+    if bool(args.capture) != bool(args.capture_out) or args.capture < 0 or (args.capture and (args.seeds or args.sweep or args.compare)):
+        raise SystemExit("--capture K (>= 1) goes with --capture-out DIR, and with one learner (not --seeds, --sweep or --compare)")
     if args.gradient == "device" and args.network == "linear":
         raise SystemExit("--gradient device goes with --network deep_sets or transformer (the linear network's gradient is the device's "
                          "anyway)")
@@ -312,6 +336,8 @@ def main():
         if "eval" in log:
             eval_line("policy (mean)", log["eval"])
     tr.learn(callback=line, eval_every=args.eval_every, eval_episodes=args.eval_episodes)
+    if args.capture:
+        write_episodes(tr.evaluate(args.eval_episodes, capture_envs=args.capture), args.capture, args.eval_episodes, args.capture_out)
     tr.env.close()
 
 

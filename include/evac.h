@@ -582,6 +582,47 @@ int evac_policy_evaluate_transformer(evac_handle_t h, int32_t agent, const evac_
                                      const double* norm_state_or_null, float obs_clip, float epsilon,
                                      const evac_transformer_t* encoder, void* stream);
 
+/* ---- Recording an evaluation: the episodes' frames for rendering (Pedestrians.save / Agent.save, pedestrians.py:33-35,
+ * area.py:32-33) ----
+ * The three entries below are evac_policy_evaluate, evac_policy_evaluate_deepsets and evac_policy_evaluate_transformer with
+ * `capture` in front of the stream: arguments, contract, progress, records and state are the counterpart's bit for bit, and the
+ * launch also writes, for the envs e < capture_envs of the handle (K = capture_envs, N pedestrians; rows 0..N-1 of a frame hold
+ * (x, y, status) as floats, row N holds (leader x, leader y, 0) -- evac_rollout's capture layout):
+ *   frames[f][e]  the state after the env's step f and BEFORE any reset, f counted from the env's first step of the evaluation:
+ *                 the step a launch takes as its t-th (t = 0, 1, ...) has f = progress[e][1] at the launch's entry + t.  A frame
+ *                 with f >= max_frames is not written; n_episodes x max_timesteps frames hold every env.
+ *   starts[k][e]  the state episode k begins with, k < n_episodes: the state the launch finds when progress[e][0] == 0 and
+ *                 progress[e][1] == 0 (k = 0), and the state after the reset that ends episode k - 1.
+ * Rows that no step reached are left untouched.  Episode k of env e, with L_k its record's episode_length and s = L_0 + ... +
+ * L_{k-1}: what the reference's Pedestrians.memory holds is starts[k][e] and then frames[s .. s + L_k - 1][e]; the leader's
+ * memory is row N of those L_k frames (an evaluation that begins at a reset, as above: an env that begins it t steps into an
+ * episode takes L_0 - t steps in episode 0).  max_steps = 5 repeated equals one long call, frames included: the index comes
+ * from the progress word.
+ * Refusals, decided on the host before anything is launched: the counterpart's own, in its order, then
+ * EVAC_ERR_INVALID_ARGUMENT for a NULL capture, capture_envs outside 1..num_envs, max_frames < 1, a NULL frames or starts.
+ * ONE kernel on `stream` (k_evaluate_capture*, evac_capture_api.hip), no host synchronisation, capturable.  A diagnostic face:
+ * the generic configuration's kernels only, and no population form. */
+typedef struct evac_eval_capture {
+    int32_t capture_envs;   /* K: envs 0..K-1 of the handle, 1..num_envs */
+    int32_t max_frames;     /* F >= 1 */
+    float*  frames;         /* [F][K][N+1][3] */
+    float*  starts;         /* [n_episodes][K][N+1][3] */
+} evac_eval_capture_t;
+int evac_policy_evaluate_capture(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy_or_null,
+                                 int32_t n_episodes, int32_t max_steps,
+                                 int32_t* progress,                   /* [E][4] in/out; zero it to begin */
+                                 evac_episode_stats_t* episodes_out,  /* [n_episodes][E] */
+                                 const double* norm_state_or_null, float obs_clip, float epsilon,
+                                 const evac_eval_capture_t* capture, void* stream);
+int evac_policy_evaluate_deepsets_capture(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy,
+                                          int32_t n_episodes, int32_t max_steps, int32_t* progress, evac_episode_stats_t* episodes_out,
+                                          const double* norm_state_or_null, float obs_clip, float epsilon,
+                                          const evac_deepsets_t* encoder, const evac_eval_capture_t* capture, void* stream);
+int evac_policy_evaluate_transformer_capture(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy,
+                                             int32_t n_episodes, int32_t max_steps, int32_t* progress, evac_episode_stats_t* episodes_out,
+                                             const double* norm_state_or_null, float obs_clip, float epsilon,
+                                             const evac_transformer_t* encoder, const evac_eval_capture_t* capture, void* stream);
+
 /* ---- The trainer's update: the other half of RPOAgent.learn() (rpo_agent.py:205-283) for the network above ----
  * No handle: buffers, sizes and a stream; arguments are validated on the host before anything touches a device, and errors
  * come back through the return code alone (evac_last_error keeps its meaning for handles).

@@ -3,6 +3,7 @@
 
     python tools/eval_bench.py [--envs 4096] [--steps 128] [--reps 9] [--shape grav|wide|both] [--evaluate-only]
     python tools/eval_bench.py --learners S [--learner-envs 256] [--pairs 9]
+    python tools/eval_bench.py --capture K [--envs 4096] [--steps 128] [--reps 9]
 
 Per shape -- N = 60 with the gravity observation (D = 6), and with the rel + ohe Box observation (D = 372), both with the frozen
 normaliser -- the time per env-step of ``policy_evaluate(mean, max_steps = T)`` and of ``policy_rollout(T)`` from the same start
@@ -15,7 +16,13 @@ state: hipEvent times after warm-up, the two forms alternated inside every repet
 observation and the frozen normaliser, one episode per env at the default ``max_timesteps`` -- a loop of S
 ``PolicyEvaluator.evaluate`` calls (one learner after another) against ONE ``PopulationEvaluator.evaluate``, the same nets and
 statistics, one warm-up of each, then interleaved pairs whose order alternates: hipEvent time and host wall time, median and
-range, and the S ``summary()`` reads against one ``EvaluationResult.summaries``."""
+range, and the S ``summary()`` reads against one ``EvaluationResult.summaries``.
+
+``--capture K`` measures what recording costs (``policy_evaluate(capture=...)``, the ``k_evaluate_capture*`` kernels): N = 60, the
+gravity observation, the frozen normaliser -- ``policy_evaluate(mean, max_steps = T)`` without and with the frames of envs
+``0..K-1`` from the same start state, alternated inside every repetition, and one ``PolicyEvaluator.evaluate(n_episodes = 1)`` at
+the default ``max_timesteps`` without and with ``capture_envs = K`` (host wall time, the buffers' allocation included).  A
+report, not a threshold: recording is a diagnostic face."""
 import argparse
 import os
 import statistics
@@ -93,6 +100,54 @@ def kernel_against_rollout(shape, args):
           f"evaluation median {'within or below' if ok else 'ABOVE'} the rollout's range")
     env.close()
     return ok
+
+
+def capture_against_plain(args):
+    E, T, K = args.envs, args.steps, args.capture
+    cfg = ea.EnvConfig(number_of_pedestrians=60, is_new_exiting_reward=True, clip_action=True)
+    ev = ea.PolicyEvaluator(cfg, ea.EnvWrappersConfig(**SHAPES["grav"]), num_envs=E, seed=1)
+    env = ev.env
+    torch.manual_seed(0)
+    net = LinearActorCritic(6).to(DEV)
+    ns = torch.zeros((E, 22), dtype=torch.float64, device=DEV)
+    ns[:, 6:12] = 1.0
+    norm = (ns, 1.0, 1e-8)
+    cap = {"frames": torch.zeros((T, K, 61, 3), dtype=torch.float32, device=DEV), "starts": torch.zeros((T, K, 61, 3), dtype=torch.float32, device=DEV)}
+    with torch.no_grad():
+        progress, out = env.policy_evaluate(net, T, T, _norm=norm)
+        forms = {"plain": lambda: env.policy_evaluate(net, T, T, progress, out, _norm=norm),
+                 "capture": lambda: env.policy_evaluate(net, T, T, progress, out, _norm=norm, capture=cap)}
+
+        def rewind():
+            ev.restore()
+            progress.zero_()
+        for _ in range(2):
+            for fn in forms.values():
+                rewind(); fn()
+        torch.cuda.synchronize()
+        t = {"plain": [], "capture": []}
+        for rep in range(args.reps):                                           # alternated inside every repetition
+            for form in (("plain", "capture") if rep % 2 == 0 else ("capture", "plain")):
+                rewind()
+                torch.cuda.synchronize()
+                t[form].append(event_ms(forms[form]))
+        per = 1e6 / (E * T)
+        print(f"[capture] N = 60, D = 6, {E} envs x {T} steps, frozen normaliser, K = {K} recorded envs; median [min .. max] of {args.reps} repetitions")
+        print(f"    policy_evaluate(mean, {T})                {show(t['plain'])}   {show(t['plain'], per, 'ns / env-step')}")
+        print(f"    policy_evaluate(mean, {T}, capture)       {show(t['capture'])}   {show(t['capture'], per, 'ns / env-step')}")
+        print(f"    capture median / plain median = {statistics.median(t['capture']) / statistics.median(t['plain']):.3f}")
+        for name, kw in (("without capture", {}), (f"capture_envs = {K}", dict(capture_envs=K))):
+            ev.evaluate(net, 1, norm_state=ns, **kw)                           # warm-up
+            torch.cuda.synchronize()
+            wall = []
+            for _ in range(args.eval_reps):
+                t0 = time.perf_counter()
+                res = ev.evaluate(net, 1, norm_state=ns, **kw)
+                torch.cuda.synchronize()
+                wall.append((time.perf_counter() - t0) * 1e3)
+            print(f"evaluate(n_episodes=1), {E} envs, max_timesteps = {cfg.max_timesteps}, {name}: {show(wall)} host wall time, "
+                  f"{ev.launches} launch(es), {int(res.steps.sum())} env-steps")
+    ev.close()
 
 
 def whole_evaluation(args):
@@ -219,7 +274,11 @@ def main():
     ap.add_argument("--learners", type=int, default=0, help="measure the population evaluation with this many learners instead")
     ap.add_argument("--learner-envs", type=int, default=256)
     ap.add_argument("--pairs", type=int, default=9)
+    ap.add_argument("--capture", type=int, default=0, metavar="K", help="measure an evaluation without and with the frames of K envs instead")
     args = ap.parse_args()
+    if args.capture:
+        capture_against_plain(args)
+        return 0
     if args.learners:
         return 0 if population_against_loop(args) else 1
     ok = True
