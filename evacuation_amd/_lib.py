@@ -114,6 +114,11 @@ class EvacDeepSetsAdamState(C.Structure):
     _fields_ = EvacAdamState._fields_ + [("enc_exp_avg", EvacDeepSetsGrads), ("enc_exp_avg_sq", EvacDeepSetsGrads)]
 
 
+class EvacTransformerAdamState(C.Structure):
+    """evac_transformer_adam_state_t: evac_adam_state_t with the attention encoder's moments (16 per block) after the 13 tensors'"""
+    _fields_ = EvacAdamState._fields_ + [("enc_exp_avg", EvacTransformerGrads), ("enc_exp_avg_sq", EvacTransformerGrads)]
+
+
 class EvacLearnerHyper(C.Structure):
     """evac_learner_hyper_t: one learner's float-valued hyperparameters (a host array [S] for the sweep entries)"""
     _fields_ = [(f, C.c_double) for f in ("learning_rate", "target_kl", "gamma", "gae_lambda")] + [
@@ -245,6 +250,17 @@ SIGNATURES = {
                                        C.POINTER(EvacRpoLossConfig), C.POINTER(EvacAdamConfig), C.POINTER(EvacDeepSetsAdamState),
                                        C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, C.c_uint64, C.c_uint64,
                                        C.c_int32, C.c_double, _P, _P, _P]),
+    # the transformer leader's three: the deep-sets forms with its structs (the step takes num_blocks after elem_dim)
+    "evac_transformer_minibatch_step": (C.c_int, _grad_args(EvacTransformer, EvacTransformerGrads) + [
+        C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacTransformerGrads), C.POINTER(EvacTransformerAdamState), C.POINTER(EvacAdamConfig)]),
+    "evac_transformer_adam_step": (C.c_int, [C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacTransformerGrads), C.POINTER(EvacMlpPolicyGrads),
+                                             C.POINTER(EvacTransformerGrads), C.POINTER(EvacTransformerAdamState),
+                                             C.POINTER(EvacAdamConfig), C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "evac_transformer_update": (C.c_int, [C.POINTER(EvacMlpPolicy), C.POINTER(EvacTransformer), C.POINTER(EvacMlpPolicyGrads),
+                                          C.POINTER(EvacTransformerGrads), C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacTransformerGrads),
+                                          C.POINTER(EvacRpoLossConfig), C.POINTER(EvacAdamConfig), C.POINTER(EvacTransformerAdamState),
+                                          C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, C.c_uint64, C.c_uint64,
+                                          C.c_int32, C.c_double, _P, _P, _P]),
     "evac_rpo_population_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32]),
     "evac_rpo_update_population": (C.c_int, [C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacMlpPolicyGrads),
                                              C.POINTER(EvacMlpPolicyStrides), C.POINTER(EvacMlpPolicyStrides),

@@ -22,13 +22,6 @@ static_assert(offsetof(evac_deepsets_adam_state_t, exp_avg) == offsetof(evac_ada
                   offsetof(evac_deepsets_adam_state_t, exp_avg_sq) == offsetof(evac_adam_state_t, exp_avg_sq),
               "the state of the 13 tensors is evac_adam_state_t's");
 
-// The scalars of `o` (adam_prepare's, then set for a step by rpo_update_steps) into the 19-tensor arguments.
-inline void set_adam_scalars(const evac::AdamArgs& o, evac::SetAdamArgs& q) {
-    q.hdr = o.hdr; q.sumsq = o.sumsq; q.stats = o.stats;
-    q.lr = o.lr; q.beta1 = o.beta1; q.beta2 = o.beta2; q.target_kl = o.target_kl;
-    q.max_norm = o.max_norm; q.w = o.w; q.b2 = o.b2; q.u = o.u; q.eps = o.eps;
-    q.gated = o.gated; q.epoch_last = o.epoch_last; q.use_target_kl = o.use_target_kl;
-}
 // What evac_deepsets_adam_step checks and sets up: adam_prepare for the 13 tensors (into `o`), then the encoder's six.
 int set_adam_prepare(const evac_mlp_policy_grads_t* params, const evac_deepsets_grads_t* enc_params, const evac_mlp_policy_grads_t* grads,
                      const evac_deepsets_grads_t* enc_grads, const evac_deepsets_adam_state_t* state, const evac_adam_config_t* cfg,
@@ -57,7 +50,7 @@ int set_adam_prepare(const evac_mlp_policy_grads_t* params, const evac_deepsets_
         q.n[i] = i < evac::kAdamTensors ? o.end[i] - (i ? o.end[i - 1] : 0) : enc_n[i - evac::kAdamTensors];
         q.wg_end[i] = (wgs += (q.n[i] + evac::kAdamBlock - 1) / evac::kAdamBlock);
     }
-    set_adam_scalars(o, q);
+    encoder_adam_scalars(o, q);
     return EVAC_OK;
 }
 void set_adam_launch(const evac::SetAdamArgs& q, hipStream_t S) {
@@ -141,7 +134,7 @@ int evac_deepsets_update(const evac_mlp_policy_t* policy, const evac_deepsets_t*
     rpo_update_steps(a, o, batch_size, n_minibatch, n_epochs, perms, rpo_noise, stats_out, first_draw_counter,
                      [&s, &q, S](const evac::RpoArgs& step, const evac::AdamArgs& adam, uint64_t) {
                          const evac::RpoArgs inner = encoder_grad_step<SetGrad>(step, s);
-                         set_adam_scalars(adam, q);
+                         encoder_adam_scalars(adam, q);
                          SetGrad::launch(inner, s, S, (const evac::AdamHeader*)adam.hdr);
                          set_adam_launch(q, S);
                      });

@@ -1,8 +1,8 @@
 // Host side of the gradient behind an encoder, the part the deep-sets and the transformer leader's entries share
-// (evac_deepsets_train_api.hip, evac_deepsets_update_api.hip, evac_transformer_train_api.hip): the workspace's cursor and its
-// gathered columns, the halves of "prepare" and "step" that are the same in front of either encoder, the sizer's body and the whole
-// body of a gradient entry.  What differs sits in a trait per encoder (SetGrad in evac_deepsets_train_host.h, TfGrad in
-// evac_transformer_train_api.hip):
+// (evac_deepsets_train_api.hip, evac_deepsets_update_api.hip, evac_transformer_train_api.hip, evac_transformer_update_api.hip):
+// the workspace's cursor and its gathered columns, the halves of "prepare" and "step" that are the same in front of either
+// encoder, the sizer's body and the whole body of a gradient entry.  What differs sits in a trait per encoder (SetGrad in evac_deepsets_train_host.h, TfGrad in
+// evac_transformer_train_host.h):
 //
 //   Encoder, Grads, Args      the C structs and the kernels' argument struct (evac::SetArgs / evac::TfgArgs, whose equally named
 //                             fields the templates here reach by name: the two share no base, which would move kernel arguments)
@@ -108,6 +108,16 @@ inline evac::RpoArgs encoder_grad_step(const evac::RpoArgs& step, typename Enc::
     const typename Enc::Layout L = Enc::layout(step.D, step.M);
     Enc::shape(s, L, step.ws, step.M);
     return encoder_grad_point_step(step, s, L);
+}
+
+// The scalars of `o` (adam_prepare's, then set for a step by rpo_update_steps) into an encoder's optimiser arguments
+// (evac::SetAdamArgs, evac::TfAdamArgs: the fields AdamArgs names, under the same names).
+template <class EncAdamArgs>
+inline void encoder_adam_scalars(const evac::AdamArgs& o, EncAdamArgs& q) {
+    q.hdr = o.hdr; q.sumsq = o.sumsq; q.stats = o.stats;
+    q.lr = o.lr; q.beta1 = o.beta1; q.beta2 = o.beta2; q.target_kl = o.target_kl;
+    q.max_norm = o.max_norm; q.w = o.w; q.b2 = o.b2; q.u = o.u; q.eps = o.eps;
+    q.gated = o.gated; q.epoch_last = o.epoch_last; q.use_target_kl = o.use_target_kl;
 }
 
 // What follows the gradient in the same call: nothing (the step's entry: the optimiser's checks, and its launch).

@@ -1,5 +1,5 @@
 // Host side of the transformer leader, the part its translation units share (evac_transformer_api.hip: collection and evaluation;
-// evac_transformer_train_api.hip: the gradient): what the kernels take of evac_transformer_t, checked in two steps -- the sizes,
+// evac_transformer_train_api.hip: the gradient; evac_transformer_update_api.hip: the optimiser step and the whole update): what the kernels take of evac_transformer_t, checked in two steps -- the sizes,
 // then the blocks' pointers -- so that each entry can put its own checks (the handle's tokens, the observation's form) between
 // them.  Each unit asserts the limits below against its own device constants.
 #pragma once

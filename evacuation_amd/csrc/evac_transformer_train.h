@@ -22,6 +22,9 @@
 //                    (an INTEGER ticket) adds their sums of squares to stats[7] (k_rpo_finish wrote it before this launch).
 // Every sum has a fixed order, no floating-point atomics: the same bits on every run and stream.  f32 fmaf chains on the VALU
 // (no MFMA: every contraction is 6 or 3 wide).
+// The four are templates over an optional trailing argument, as k_rpo_* are: k_tf_*<> are evac_transformer_minibatch_grad's
+// kernels; k_tf_*<const AdamHeader*> are evac_transformer_update's, which return at once, touching nothing (k_tf_encode not even
+// the ticket), when the header's stop flag is set.
 #pragma once
 
 #include "evac_train.h"
@@ -301,7 +304,11 @@ struct TfgEncodeWave {
     alignas(16) float kv[64][kTfgDm];
 };
 
-__global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_encode(TfgArgs a) {
+template <class... Gate>
+__global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_encode(TfgArgs a, Gate... gate) {
+    if constexpr (sizeof...(Gate) != 0) {
+        if (rpo_stopped(gate...)) return;
+    }
     __shared__ TfgBlockSmem ts[kTfgMaxBlocks];
     __shared__ TfgEncodeWave ws[kTfgEncodeWaves];
     const int tid = (int)threadIdx.x, lane = tid & 63;
@@ -342,7 +349,11 @@ __global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_encode(TfgArgs a) {
 }
 
 // dX[m][j] = sum_k W1a[k][j] g1a[m][k] + sum_k W1c[k][j] g1c[m][k], k ascending, the actor first: one tile of 8 samples a workgroup
-__global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_dy(TfgArgs a) {
+template <class... Gate>
+__global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_dy(TfgArgs a, Gate... gate) {
+    if constexpr (sizeof...(Gate) != 0) {
+        if (rpo_stopped(gate...)) return;
+    }
     constexpr int H1 = kTrainHidden;
     __shared__ __attribute__((aligned(16))) float gs[2 * H1][kTfgTile];        // g1 of the tile's samples: [net, unit][sample]
     const int tid = (int)threadIdx.x;
@@ -405,7 +416,11 @@ __device__ __forceinline__ void tfg_add_sums6(float* acc, const float (&v)[kTfgD
     tfg_add_sums3(acc + 3, v[3], v[4], v[5], lane);
 }
 
-__global__ __launch_bounds__(kTfgBlock) void k_tf_backward(TfgArgs a, int b) {
+template <class... Gate>
+__global__ __launch_bounds__(kTfgBlock) void k_tf_backward(TfgArgs a, int b, Gate... gate) {
+    if constexpr (sizeof...(Gate) != 0) {
+        if (rpo_stopped(gate...)) return;
+    }
     __shared__ TfgBlockSmem t;
     __shared__ TfgWave wv[kTfgWaves];
     const int tid = (int)threadIdx.x, lane = tid & 63;
@@ -686,7 +701,11 @@ __device__ __forceinline__ int tfg_entry(int e, int dm, int& off) {
     return c < dm ? (off = c, 12 + which) : -1;
 }
 
-__global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_finish(TfgArgs a) {
+template <class... Gate>
+__global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_finish(TfgArgs a, Gate... gate) {
+    if constexpr (sizeof...(Gate) != 0) {
+        if (rpo_stopped(gate...)) return;
+    }
     __shared__ float buf[kTfgEncodeBlock];
     __shared__ float fin[kTfgMaxBlocks * kTfgFinishWgs];
     __shared__ int last;

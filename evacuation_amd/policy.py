@@ -245,12 +245,15 @@ def transformer_dropouts(net) -> list:
 
 
 def refuse_transformer(net, what: str) -> None:
-    """``ValueError`` where a network with an attention encoder cannot go: every gradient and optimiser kernel (the linear
-    network's and the set encoder's), ``DeviceAdam``, populations and sweeps.  It trains with ``RPOTrainer(optimizer="torch")``,
-    whose gradient for such a network is autograd's."""
+    """``ValueError`` where a network with an attention encoder cannot go: the gradient and optimiser entries of the linear
+    network and of the set encoder, ``DeviceAdam``, populations and sweeps.  It trains with ``RPOTrainer(optimizer="torch")``,
+    whose gradient for such a network is autograd's, or with its own entries (``trainer.transformer_minibatch_grad`` /
+    ``transformer_minibatch_step`` / ``transformer_update`` and ``TransformerAdam``:
+    ``RPOTrainer(grad_fn=transformer_kernel_grad, optimizer="device_transformer")``)."""
     if net is not None and is_transformer(net):
-        raise ValueError(f"{what}: the network has an attention encoder (`embedding`); the gradient and optimiser kernels do not know "
-                         "its tensors -- train it with RPOTrainer(optimizer=\"torch\"), whose gradient is autograd's")
+        raise ValueError(f"{what}: the network has an attention encoder (`embedding`); these gradient and optimiser kernels do not "
+                         "know its tensors -- train it with RPOTrainer(optimizer=\"torch\"), whose gradient is autograd's, or with "
+                         "RPOTrainer(grad_fn=transformer_kernel_grad, optimizer=\"device_transformer\")")
 
 
 def refuse_dropout(net, what: str) -> None:

@@ -5,7 +5,9 @@
 ``loss.backward()``, ``evac_rpo_minibatch_grad``: at most three launches, deterministic) and ``RPOTrainer``, one iteration of the
 reference's loop per ``update()``.  Gradient clipping and Adam are torch's by default (they work on ``.grad`` in place) or the
 library's own (``DeviceAdam``, ``evac_adam_step``: one launch), with which a minibatch step is one host call
-(``rpo_minibatch_step``) and a whole update's epochs and minibatches are one (``rpo_update``), ``target_kl`` included."""
+(``rpo_minibatch_step``) and a whole update's epochs and minibatches are one (``rpo_update``), ``target_kl`` included.  The
+deep-sets and the transformer leader have the same three forms for their 19 and 13 + 16 per block tensors (``deepsets_*``;
+``transformer_*`` with ``TransformerAdam``)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -228,8 +230,8 @@ def _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, sta
     """``evac_rpo_minibatch_grad``, or with ``opt`` ``evac_rpo_minibatch_step``: the same arguments and the optimiser's three;
     or with ``kind`` (the network's own row of ``ENCODER_KINDS``) ``evac_deepsets_minibatch_grad`` /
     ``evac_transformer_minibatch_grad``: the same arguments, the encoder after the policy and its gradients after the policy's,
-    and a workspace of its own size -- and with ``opt`` ``evac_deepsets_minibatch_step``: the optimiser's three, the encoder's
-    parameters after the policy's (the attention encoder has no optimiser form: a missing symbol)."""
+    and a workspace of its own size -- and with ``opt`` ``evac_deepsets_minibatch_step`` / ``evac_transformer_minibatch_step``: the
+    optimiser's three, the encoder's parameters after the policy's."""
     B, D, dev, st, pol, grads, b_args = _batch_args(net, batch, kind is not None)
     if kind is not None:
         enc, enc_grads = st.binder.bind_encoder(net)[1], ensure_encoder_grads(net)
@@ -280,7 +282,8 @@ def transformer_minibatch_grad(net, batch: Dict[str, torch.Tensor], mb_inds: tor
     ``evac_transformer_minibatch_grad`` -- the encoder forwards, the linear network's three gradient launches on the encoded
     observations, one launch per block backwards.  Same arguments, same 8 statistics (``stats[7]``: the sum of squares over all
     the tensors), deterministic, no host synchronisation, capturable.  The encoder is the eval-mode function: a dropout
-    probability other than 0 is refused.  The optimiser stays torch's (``RPOTrainer(grad_fn=transformer_kernel_grad)``)."""
+    probability other than 0 is refused.  The optimiser is torch's (``RPOTrainer(grad_fn=transformer_kernel_grad)``) or, in the
+    same call, the device's (``transformer_minibatch_step``)."""
     if not is_transformer(net):
         raise ValueError("transformer_minibatch_grad: the network has no attention encoder (`embedding`); its gradient is "
                          "rpo_minibatch_grad's or deepsets_minibatch_grad's")
@@ -301,6 +304,10 @@ def decode_header(header: torch.Tensor) -> dict:
     return {"t": t, "P1": P1 if t else 1.0, "P2": P2 if t else 1.0, "stop": stop, "steps_run": steps_run, "epochs_run": epochs_run}
 
 
+# evac_deepsets_adam_state_t / evac_transformer_adam_state_t by the suffix of the encoder's entries
+_ENCODER_ADAM_STATES = {"_deepsets": _lib.EvacDeepSetsAdamState, "_transformer": _lib.EvacTransformerAdamState}
+
+
 class DeviceAdam:
     """``clip_grad_norm_(max_grad_norm)`` and ``torch.optim.Adam(lr, betas, eps)`` (no weight decay, no amsgrad) for the 13
     tensors of ``net`` in one launch (``evac_adam_step``; the arithmetic is specified in include/evac.h) -- or, for a network
@@ -312,8 +319,13 @@ class DeviceAdam:
                  *, storage=None):
         """``storage`` = (header, exp_avg, exp_avg_sq): the state lives in the caller's tensors (``PopulationAdam``'s rows: 13
         tensors, so a ``ValueError`` for a network with a set encoder)."""
-        refuse_transformer(net, "DeviceAdam")
-        self.deepsets = is_deepsets(net)
+        refuse_transformer(net, "DeviceAdam")                                   # (its own optimiser is TransformerAdam)
+        self._setup(net, lr, betas, eps, max_grad_norm, storage)
+
+    def _setup(self, net, lr, betas, eps, max_grad_norm, storage=None) -> None:
+        """The constructor's body for the network's own kind (``encoder_kind``): the 13 tensors' state, then the encoder's."""
+        self.kind = encoder_kind(net)
+        self.deepsets = is_deepsets(net) and not is_transformer(net)
         if self.deepsets and storage is not None:
             raise ValueError("DeviceAdam: `storage` holds the 13 tensors of a population's row; a network with a set encoder "
                              "(`deep_sets`) has 19")
@@ -327,6 +339,7 @@ class DeviceAdam:
                 raise ValueError("DeviceAdam: the parameters must be contiguous float32 device tensors")
         self.obs_dim = int(self.params[0].shape[1])
         self.set_elem_dim = int(self.params[13].shape[1]) if self.deepsets else None
+        self.elem_dim = int(self.params[13].shape[1]) if self.kind is not None else None     # (phi_w1 [24][ed]; wq [3 dm][dm])
         self.param_groups = [group]
         if storage is None:
             self.header = torch.zeros(8, dtype=torch.int64, device=self.device)
@@ -336,10 +349,10 @@ class DeviceAdam:
             self.header, self.exp_avg, self.exp_avg_sq = storage[0], list(storage[1]), list(storage[2])
         self._state = _lib.EvacAdamState(self.header.data_ptr(), _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in self.exp_avg[:13])),
                                          _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in self.exp_avg_sq[:13])))
-        if self.deepsets:
-            self._state = _lib.EvacDeepSetsAdamState(self._state.header, self._state.exp_avg, self._state.exp_avg_sq,
-                                                     _lib.EvacDeepSetsGrads(*(t.data_ptr() for t in self.exp_avg[13:])),
-                                                     _lib.EvacDeepSetsGrads(*(t.data_ptr() for t in self.exp_avg_sq[13:])))
+        if self.kind is not None:                                               # (the encoder's moments after the 13 tensors')
+            self._state = _ENCODER_ADAM_STATES[self.kind.suffix](self._state.header, self._state.exp_avg, self._state.exp_avg_sq,
+                                                                 self.kind.grads(*(t.data_ptr() for t in self.exp_avg[13:])),
+                                                                 self.kind.grads(*(t.data_ptr() for t in self.exp_avg_sq[13:])))
         self._params, self._encoder_params = [None, None], [None, None]
         ensure_grads(net)
 
@@ -362,12 +375,14 @@ class DeviceAdam:
     def params_struct(self) -> "_lib.EvacMlpPolicyGrads":
         return _tensor_struct(self._params, self.params[:13])
 
-    def encoder_params_struct(self) -> "_lib.EvacDeepSetsGrads":
-        """The set encoder's six parameter tensors (a network with a set encoder only)."""
-        return _tensor_struct(self._encoder_params, self.params[13:], _lib.EvacDeepSetsGrads)
+    def encoder_params_struct(self):
+        """The encoder's parameter tensors as its gradients' struct (a network with an encoder only): the set encoder's six, or
+        ``TransformerAdam``'s 16 per block."""
+        return _tensor_struct(self._encoder_params, self.params[13:], self.kind.grads)
 
     def state_struct(self):
-        """``evac_adam_state_t``, or ``evac_deepsets_adam_state_t`` for a network with a set encoder."""
+        """``evac_adam_state_t``, or ``evac_deepsets_adam_state_t`` for a network with a set encoder
+        (``evac_transformer_adam_state_t``: ``TransformerAdam``)."""
         return self._state
 
     def step(self, grad_sumsq: torch.Tensor) -> None:
@@ -377,14 +392,19 @@ class DeviceAdam:
             raise ValueError("DeviceAdam.step: grad_sumsq must be a float32 scalar on the parameters' device")
         grads = ensure_grads(self.net)
         cfg = self.config()
-        if self.deepsets:
-            rc = _lib.load().evac_deepsets_adam_step(C.byref(self.params_struct()), C.byref(self.encoder_params_struct()), C.byref(grads),
-                                                     C.byref(ensure_encoder_grads(self.net)), C.byref(self._state), C.byref(cfg),
-                                                     self.obs_dim, self.set_elem_dim, _ptr(grad_sumsq), _stream(self.device))
+        if self.kind is not None:                                               # (evac_deepsets_adam_step / evac_transformer_adam_step)
+            rc = getattr(_lib.load(), _entry_name(self.kind, "adam_step"))(
+                C.byref(self.params_struct()), C.byref(self.encoder_params_struct()), C.byref(grads),
+                C.byref(ensure_encoder_grads(self.net)), C.byref(self._state), C.byref(cfg), self.obs_dim, *self._encoder_sizes(),
+                _ptr(grad_sumsq), _stream(self.device))
         else:
             rc = _lib.load().evac_adam_step(C.byref(self.params_struct()), C.byref(grads), C.byref(self._state), C.byref(cfg),
                                             self.obs_dim, _ptr(grad_sumsq), _stream(self.device))
         _lib.check(rc)
+
+    def _encoder_sizes(self) -> tuple:
+        """What the encoder's ``adam_step`` entry takes between ``obs_dim`` and ``grad_sumsq``: ``set_elem_dim``."""
+        return (self.set_elem_dim,)
 
     def zero_grad(self, set_to_none: bool = False) -> None:
         """Nothing to do: the gradient kernels write ``.grad``, they do not accumulate (kept for torch's interface)."""
@@ -449,6 +469,35 @@ def _check_opt(opt, net) -> None:
         raise ValueError("the DeviceAdam was made for another network")
 
 
+class TransformerAdam(DeviceAdam):
+    """``DeviceAdam`` for a network with the reference's attention encoder (``policy.TransformerActorCritic``): clip + Adam over
+    all 13 + 16 per block tensors in ``all_tensors`` order (29 with one block, 45 with two) in one launch
+    (``evac_transformer_adam_step``: one clip coefficient, one step count, one header).  The same interface: ``step``,
+    ``param_groups``, ``config``, the structs, ``read_header``, ``step_count``, ``state_dict`` / ``load_state_dict`` in torch's
+    format.  A class of its own because ``DeviceAdam(net)`` stays a ``ValueError`` for such a network."""
+
+    def __init__(self, net, lr: float = 3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm: float = 0.5):
+        if not is_transformer(net):
+            raise ValueError("TransformerAdam: the network has no attention encoder (`embedding`); its optimiser is DeviceAdam")
+        refuse_dropout(net, "TransformerAdam")
+        self._setup(net, lr, betas, eps, max_grad_norm)
+        self.num_blocks = (len(self.params) - 13) // 16
+
+    def _encoder_sizes(self) -> tuple:
+        return (self.elem_dim, self.num_blocks)
+
+
+def _check_transformer_opt(opt, net, what: str) -> None:
+    """``_check_opt`` for the attention encoder's own entries (``_check_opt`` refuses such a network for every other)."""
+    if not is_transformer(net):
+        raise ValueError(f"{what}: the network has no attention encoder (`embedding`); its entries are rpo_* or deepsets_*")
+    refuse_dropout(net, what)
+    if not isinstance(opt, TransformerAdam):
+        raise TypeError(f"expected a TransformerAdam, got {type(opt).__name__}")
+    if opt.net is not net:
+        raise ValueError("the TransformerAdam was made for another network")
+
+
 def rpo_minibatch_step(net, batch: Dict[str, torch.Tensor], mb_inds: torch.Tensor, cfg, opt: DeviceAdam, *,
                        rpo_noise: Optional[torch.Tensor] = None, seed: int = 0, draw_counter: int = 0,
                        stats: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -467,11 +516,13 @@ def update_steps(batch_size: int, minibatch_size: int, norm_adv: bool) -> list:
     return [min(M, B - s) for s in range(0, B, M) if min(M, B - s) >= least]
 
 
-def _update_call(net, batch, perms, cfg, opt, rpo_noise, seed, first_draw_counter, stats, minibatch_size, kind=None):
-    """``evac_rpo_update``, or with ``kind`` (the network's own row of ``ENCODER_KINDS``: the set encoder's) ``evac_deepsets_update``:
-    the same arguments with the encoder after the policy, its parameters after the policy's and its gradients after the policy's,
-    and a workspace of its own size."""
-    _check_opt(opt, net)
+def _update_call(net, batch, perms, cfg, opt, rpo_noise, seed, first_draw_counter, stats, minibatch_size, kind=None, checked=False):
+    """``evac_rpo_update``, or with ``kind`` (the network's own row of ``ENCODER_KINDS``) ``evac_deepsets_update`` /
+    ``evac_transformer_update``: the same arguments with the encoder after the policy, its parameters after the policy's and its
+    gradients after the policy's, and a workspace of its own size.  ``checked``: the caller has checked ``opt`` itself
+    (``transformer_update``: ``_check_opt`` refuses its network)."""
+    if not checked:
+        _check_opt(opt, net)
     B, D, dev, st, pol, grads, b_args = _batch_args(net, batch, kind is not None)
     name = _entry_name(kind, "update")
     if not isinstance(perms, torch.Tensor) or perms.dtype != torch.int64 or perms.device != dev or not perms.is_contiguous() or \
@@ -535,6 +586,28 @@ def deepsets_update(net, batch: Dict[str, torch.Tensor], perms: torch.Tensor, cf
     return _update_call(net, batch, perms, cfg, opt, rpo_noise, seed, first_draw_counter, stats, minibatch_size, encoder_kind(net))
 
 
+def transformer_minibatch_step(net, batch: Dict[str, torch.Tensor], mb_inds: torch.Tensor, cfg, opt: "TransformerAdam", *,
+                               rpo_noise: Optional[torch.Tensor] = None, seed: int = 0, draw_counter: int = 0,
+                               stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``rpo_minibatch_step`` for a network with an attention encoder: ``transformer_minibatch_grad`` with the same arguments,
+    then ``opt.step(stats[7])`` over all 13 + 16 per block tensors, in one host call (``evac_transformer_minibatch_step``: one
+    launch more than the gradient).  ``.grad`` is left clipped; ``stats`` are those of the gradient at the parameters before the
+    step.  No host synchronisation; capturable (``lr`` and ``draw_counter`` are frozen by a capture, the step count is not)."""
+    _check_transformer_opt(opt, net, "transformer_minibatch_step")
+    return _minibatch_call(net, batch, mb_inds, cfg, rpo_noise, seed, draw_counter, stats, opt, encoder_kind(net))
+
+
+def transformer_update(net, batch: Dict[str, torch.Tensor], perms: torch.Tensor, cfg, opt: "TransformerAdam", *,
+                       rpo_noise: Optional[torch.Tensor] = None, seed: int = 0, first_draw_counter: int = 0,
+                       stats: Optional[torch.Tensor] = None, minibatch_size: Optional[int] = None):
+    """``rpo_update`` for a network with an attention encoder (``evac_transformer_update``): the same arguments, the same
+    returns (``stats`` [steps, 8], the optimiser's header), the ``target_kl`` exit taken on the device; bit for bit the host loop
+    of ``transformer_minibatch_step``."""
+    _check_transformer_opt(opt, net, "transformer_update")
+    return _update_call(net, batch, perms, cfg, opt, rpo_noise, seed, first_draw_counter, stats, minibatch_size, encoder_kind(net),
+                        checked=True)
+
+
 def _kernel_grad(trainer: "RPOTrainer", batch, mb_inds, rpo_noise, draw_counter: int, stats: torch.Tensor) -> torch.Tensor:
     return rpo_minibatch_grad(trainer.net, batch, mb_inds, trainer.cfg, rpo_noise=rpo_noise, seed=trainer.cfg.seed,
                               draw_counter=draw_counter, stats=stats)
@@ -549,8 +622,9 @@ def deepsets_kernel_grad(trainer: "RPOTrainer", batch, mb_inds, rpo_noise, draw_
 
 def transformer_kernel_grad(trainer: "RPOTrainer", batch, mb_inds, rpo_noise, draw_counter: int, stats: torch.Tensor) -> torch.Tensor:
     """A ``grad_fn`` of ``RPOTrainer`` for a network with an attention encoder: ``transformer_minibatch_grad`` (collection and
-    gradient on the device, torch's clip and Adam).  Opt-in: the default for such a network stays ``autograd_minibatch_grad``,
-    and ``optimizer="device"`` stays refused with any ``grad_fn``."""
+    gradient on the device; torch's clip and Adam, or with ``optimizer="device_transformer"`` ``TransformerAdam``: the whole
+    update one ``transformer_update``).  Opt-in: the default for such a network stays ``autograd_minibatch_grad``, and
+    ``optimizer="device"`` stays refused with any ``grad_fn``."""
     return transformer_minibatch_grad(trainer.net, batch, mb_inds, trainer.cfg, rpo_noise=rpo_noise, seed=trainer.cfg.seed,
                                       draw_counter=draw_counter, stats=stats)
 
@@ -558,6 +632,10 @@ def transformer_kernel_grad(trainer: "RPOTrainer", batch, mb_inds, rpo_noise, dr
 # The gradient functions whose step and whole update exist as one host call (RPOTrainer with optimizer="device")
 _STEP_OF = ((_kernel_grad, rpo_minibatch_step), (deepsets_kernel_grad, deepsets_minibatch_step))
 _UPDATE_OF = ((_kernel_grad, rpo_update), (deepsets_kernel_grad, deepsets_update))
+# ... per optimiser kind of RPOTrainer: (the step's table, the update's); "device_transformer" (TransformerAdam) has its own pair
+_ONE_CALL_TABLES = {"device": (_STEP_OF, _UPDATE_OF),
+                    "device_transformer": (((transformer_kernel_grad, transformer_minibatch_step),),
+                                           ((transformer_kernel_grad, transformer_update),))}
 
 
 def _one_call_form(grad_fn, table):
@@ -639,8 +717,12 @@ class RPOTrainer:
     default, which for such a network is autograd's.  Or one with the reference's attention encoder
     (``policy.TransformerActorCritic``): collection and evaluation on the device, the gradient of its 13 + 16 per block tensors
     by ``autograd_minibatch_grad`` or, with ``grad_fn=transformer_kernel_grad``, the device's
-    (``evac_transformer_minibatch_grad``), and torch's Adam; ``optimizer="device"`` (with any ``grad_fn``) and a dropout
-    probability other than 0 (the device collects with the eval-mode function) are ``ValueError``s.
+    (``evac_transformer_minibatch_grad``), and torch's Adam -- or, with ``optimizer="device_transformer"`` and an explicit
+    ``grad_fn``, ``TransformerAdam`` over all its tensors: with ``transformer_kernel_grad`` the whole update is one
+    ``transformer_update``, or one ``transformer_minibatch_step`` per minibatch with ``one_call=False``; any other ``grad_fn`` is
+    followed by ``self.optimizer.step(stats[7])``.  ``optimizer="device"`` (with any ``grad_fn``) and a dropout probability other
+    than 0 (the device collects with the eval-mode function) are ``ValueError``s, as is ``optimizer="device_transformer"`` for a
+    network without an attention encoder or with ``grad_fn`` left at its default.
 
     ``env``: a ``NormalizedVectorEnv`` (the trainer's wrapper chain) or a ``BatchedEvacuationEnv`` with ``cfg.num_envs`` envs.
     The permutation of every epoch is drawn on the device from a generator seeded with ``cfg.seed`` (the reference shuffles on
@@ -659,14 +741,23 @@ class RPOTrainer:
     def __init__(self, env, net, cfg: RPOTrainingConfig, *, grad_fn: Optional[Callable] = None,
                  rpo_noise_fn: Optional[Callable[[int], torch.Tensor]] = None, optimizer: str = "torch", one_call: bool = True):
         cfg.check()
-        if optimizer not in ("torch", "device"):
-            raise ValueError(f"RPOTrainer: optimizer = {optimizer!r}: expected \"torch\" or \"device\"")
+        if optimizer not in ("torch", "device", "device_transformer"):
+            raise ValueError(f"RPOTrainer: optimizer = {optimizer!r}: expected \"torch\", \"device\" or \"device_transformer\"")
         self.optimizer_kind, self.one_call = optimizer, bool(one_call)
+        self.device_optimizer = optimizer != "torch"                            # (DeviceAdam or TransformerAdam)
         if env.num_envs != cfg.num_envs:
             raise ValueError(f"RPOTrainer: the env has {env.num_envs} envs, cfg.num_envs = {cfg.num_envs}")
         self.env, self.net, self.cfg = env, net, cfg
         if optimizer == "device":                                               # (no optimiser kernel knows an attention encoder's tensors)
             refuse_transformer(net, "RPOTrainer(optimizer=\"device\")")
+        if optimizer == "device_transformer":
+            if not is_transformer(net):
+                raise ValueError("RPOTrainer(optimizer=\"device_transformer\"): the network has no attention encoder (`embedding`); "
+                                 "its device optimiser is optimizer=\"device\"")
+            if grad_fn is None:                                                 # (the default gradient of such a net is autograd's)
+                raise ValueError("RPOTrainer(optimizer=\"device_transformer\") takes an explicit grad_fn "
+                                 "(transformer_kernel_grad: the whole update on the device); the default gradient of a network with "
+                                 "an attention encoder is autograd's")
         refuse_dropout(net, "RPOTrainer")                                       # (collection is the eval-mode function)
         if is_deepsets(net) and optimizer == "device" and grad_fn is None:     # (the default gradient of such a net is autograd's)
             refuse_deepsets(net, "RPOTrainer(optimizer=\"device\")")
@@ -676,8 +767,9 @@ class RPOTrainer:
         self.params = list(all_tensors(net))
         self.device = self.params[0].device
         ensure_grads(net)
-        if optimizer == "device":
-            self.optimizer = DeviceAdam(net, lr=cfg.learning_rate, eps=1e-5, max_grad_norm=cfg.max_grad_norm)
+        if self.device_optimizer:
+            make = TransformerAdam if optimizer == "device_transformer" else DeviceAdam
+            self.optimizer = make(net, lr=cfg.learning_rate, eps=1e-5, max_grad_norm=cfg.max_grad_norm)
         else:
             self.optimizer = torch.optim.Adam(self.params, lr=cfg.learning_rate, eps=1e-5)
         self.stats_rows = None
@@ -713,7 +805,7 @@ class RPOTrainer:
 
     def apply_gradient(self, stats: torch.Tensor):
         """``clip_grad_norm_`` (rpo_agent.py:279) from the sum of squares the gradient step left in ``stats[7]``, then Adam."""
-        if self.optimizer_kind == "device":
+        if self.device_optimizer:
             return self.optimizer.step(stats[7])
         coef = torch.clamp(self.cfg.max_grad_norm / (stats[7].sqrt() + 1e-6), max=1.0)
         torch._foreach_mul_([p.grad for p in self.params], coef)
@@ -727,7 +819,7 @@ class RPOTrainer:
         ``target_kl``; ``perms`` None: every epoch draws its permutation as it starts.  Returns what the log needs, on the device:
         the last step's statistics and the mean ``clipfrac``."""
         cfg = self.cfg
-        one_step = _one_call_form(self.grad_fn, _STEP_OF) if self.optimizer_kind == "device" else None
+        one_step = _one_call_form(self.grad_fn, _ONE_CALL_TABLES[self.optimizer_kind][0]) if self.device_optimizer else None
         sizes = update_steps(cfg.batch_size, cfg.minibatch_size, cfg.norm_adv)
         clipfracs = []
         for e in range(cfg.update_epochs):
@@ -754,7 +846,8 @@ class RPOTrainer:
         return [stats, torch.stack(clipfracs).mean().reshape(1)]
 
     def _epochs_one_call(self, batch, perms) -> list:
-        """The whole update as one ``rpo_update`` (``deepsets_update`` for ``deepsets_kernel_grad``).  Returns what the log needs, on the device: the optimiser's header (16 words)
+        """The whole update as one ``rpo_update`` (``deepsets_update`` for ``deepsets_kernel_grad``, ``transformer_update`` for
+        ``transformer_kernel_grad`` with ``optimizer="device_transformer"``).  Returns what the log needs, on the device: the optimiser's header (16 words)
         and every step's statistics."""
         cfg = self.cfg
         sizes = update_steps(cfg.batch_size, cfg.minibatch_size, cfg.norm_adv)
@@ -767,7 +860,7 @@ class RPOTrainer:
                 noise[k, :m] = self.rpo_noise_fn(m)
         if self.stats_rows is None or self.stats_rows.shape[0] != steps:
             self.stats_rows = torch.zeros(steps, 8, dtype=torch.float32, device=self.device)
-        update = _one_call_form(self.grad_fn, _UPDATE_OF)
+        update = _one_call_form(self.grad_fn, _ONE_CALL_TABLES[self.optimizer_kind][1])
         rows, header = update(self.net, batch, perms, cfg, self.optimizer, rpo_noise=noise, seed=cfg.seed,
                               first_draw_counter=self.minibatch_steps, stats=self.stats_rows)
         return [header.view(torch.float32), rows.reshape(-1)]
@@ -779,8 +872,8 @@ class RPOTrainer:
             self.optimizer.param_groups[0]["lr"] = frac * cfg.learning_rate
         storage = self.collect()
         batch = flatten_batch(storage, self.advantages, self.returns)
-        device = self.optimizer_kind == "device"
-        one_call = device and self.one_call and _one_call_form(self.grad_fn, _UPDATE_OF) is not None
+        device = self.device_optimizer
+        one_call = device and self.one_call and _one_call_form(self.grad_fn, _ONE_CALL_TABLES[self.optimizer_kind][1]) is not None
         perms = torch.stack([self._randperm() for _ in range(cfg.update_epochs)]) if device else None
         self.last_permutations = list(perms) if device else []
         sent = self._epochs_one_call(batch, perms) if one_call else self._epochs_by_minibatch(batch, perms)

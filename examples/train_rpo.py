@@ -25,8 +25,10 @@ host call (``evac_deepsets_update``: seven launches per step).  Not with ``--see
 RPOTransformerEmbedding; ``--blocks`` 1 or 2, ``--use-resid``) on the rel + ohe Box observation, at most 62 pedestrians:
 collection and evaluation on the device (``evac_policy_rollout_transformer`` / ``evac_policy_evaluate_transformer``, the
 eval-mode function: dropout 0), the gradient of its 13 + 16 per block tensors by torch autograd or, with ``--gradient device``,
-by ``evac_transformer_minibatch_grad`` (``trainer.transformer_kernel_grad``), and torch's Adam.  Not with ``--optimizer device``,
-``--seeds``, ``--sweep`` or ``--compare``: no optimiser kernel knows its tensors.
+by ``evac_transformer_minibatch_grad`` (``trainer.transformer_kernel_grad``), and torch's Adam -- or, with ``--gradient device
+--optimizer device``, the library's clip + Adam over all its tensors (``RPOTrainer(optimizer="device_transformer")``:
+``TransformerAdam``), the whole update in one host call (``evac_transformer_update``: 6 + blocks + 1 launches per step).  Not
+with ``--seeds``, ``--sweep`` or ``--compare``, nor with ``--optimizer device`` under the autograd gradient.
 
 ``--eval-every K`` evaluates the leader every K updates (``RPOTrainer.evaluate``: whole episodes, the mean action, the observation
 statistics frozen) and prints the summary; ``--baseline`` prints the same line for the reference's scripted sweep baseline
@@ -302,9 +304,11 @@ def main():
         raise SystemExit("--network deep_sets: the gradient and optimiser kernels (--optimizer device, --seeds, --sweep, --compare) are "
                          "the linear network's; its gradient is autograd's or --gradient device, and --optimizer device goes with "
                          "--gradient device")
-    if args.network == "transformer" and (args.compare or args.seeds or args.sweep or args.optimizer == "device"):
-        raise SystemExit("--network transformer: no optimiser kernel knows its tensors (--optimizer device, --seeds, --sweep, --compare); "
-                         "it trains with autograd's gradient or --gradient device, and torch's Adam")
+    if args.network == "transformer" and (args.compare or args.seeds or args.sweep or
+                                          (args.optimizer == "device" and args.gradient != "device")):
+        raise SystemExit("--network transformer: the population's and the comparison's kernels (--seeds, --sweep, --compare) do not "
+                         "know its tensors; it trains with autograd's gradient or --gradient device, and --optimizer device goes with "
+                         "--gradient device")
     if args.compare:
         return compare(args)
     seeds = [int(x) for x in args.seeds.split(",")] if args.seeds else None
@@ -312,7 +316,9 @@ def main():
     if grid:
         tr = make_population_trainer(args, seeds or [1], grid)
     else:
-        tr = make_population_trainer(args, seeds) if seeds else make_trainer(args, optimizer=args.optimizer)
+        # (the attention encoder's device optimiser is a kind of its own: optimizer="device" stays refused for such a network)
+        kind = "device_transformer" if args.network == "transformer" and args.optimizer == "device" else args.optimizer
+        tr = make_population_trainer(args, seeds) if seeds else make_trainer(args, optimizer=kind)
 
     def eval_line(name, s):
         print(f"eval {name:14s} episodic_return={s['episode_reward_mean']:9.2f} +- {s['episode_reward_std']:.2f}  length={s['episode_length_mean']:7.1f}  "

@@ -857,6 +857,69 @@ int evac_deepsets_update(const evac_mlp_policy_t* policy, const evac_deepsets_t*
                          const int64_t* perms, const float* rpo_noise_or_null, uint64_t seed, uint64_t first_draw_counter,
                          int32_t use_target_kl, double target_kl, float* stats_out, void* workspace, void* stream);
 
+/* ---- The same three entries for the transformer leader: clip + Adam over all 13 + 16 num_blocks tensors, the step, the update ----
+ * The optimiser's sequence above runs over the 13 tensors of evac_mlp_policy_grads_t followed by the 16 of every block in use in
+ * evac_transformer_block_grads_t order, blocks[0] first (29 tensors with one block, 45 with two), with ONE clip coefficient c
+ * (from the sum of squares over all 13 + 16 num_blocks), ONE step count t and ONE header: what clip_grad_norm_ and
+ * torch.optim.Adam do given all_tensors(net).  The state is evac_adam_state_t's with the encoder's moments after it; the
+ * header is the same 64 bytes under the same rules. */
+typedef struct evac_transformer_adam_state {
+    void* header;                                           /* evac_adam_state_t.header: same 64 bytes, same rules */
+    evac_mlp_policy_grads_t exp_avg, exp_avg_sq;            /* the 13 tensors' moments */
+    evac_transformer_grads_t enc_exp_avg, enc_exp_avg_sq;   /* the encoder's 16 per block, the parameters' layouts */
+} evac_transformer_adam_state_t;
+/* evac_transformer_adam_step: evac_adam_step for 13 + 16 num_blocks tensors.  params / enc_params: the parameter tensors,
+ * writable (the tensors evac_mlp_policy_t and evac_transformer_t name); a block's sizes follow evac_transformer_block_t for
+ * elem_dim = dm: wq, wk, wv [3 dm][dm], bq, bk, bv [3 dm], dense_w [dm][3 dm], dense_b [dm], ff1_w [96][dm], ff1_b [96],
+ * ff2_w [dm][96], ff2_b, norm1_w, norm1_b, norm2_w, norm2_b [dm].  Blocks at index num_blocks and above are neither read nor
+ * written (their pointers may be NULL everywhere).  grad_sumsq: one float in DEVICE memory, the sum of squares over all 13 + 16
+ * num_blocks gradients (stats_out[7] of evac_transformer_minibatch_grad), read when the kernel runs.  ONE launch on `stream`
+ * (every tensor starts at a workgroup boundary, one element per thread; the last workgroup to finish, by an integer ticket, is
+ * the one writer of the header), no host synchronisation, capturable.  The gradients are left holding g * c; a NaN sum of
+ * squares makes every parameter and moment a NaN and still counts as a step.
+ * Refusals, before anything touches a device and through the return code alone; the encoder's sizes are looked at before its
+ * pointers.  EVAC_ERR_INVALID_ARGUMENT: everything evac_adam_step refuses; a NULL enc_params or enc_grads; a NULL tensor of a
+ * block in use in either or in the encoder's moments; elem_dim outside 1..6, not dividing obs_dim, or leaving fewer than 3
+ * tokens.  EVAC_ERR_UNSUPPORTED: num_blocks outside 1..2, more than 64 tokens. */
+int evac_transformer_adam_step(const evac_mlp_policy_grads_t* params, const evac_transformer_grads_t* enc_params,
+                               const evac_mlp_policy_grads_t* grads, const evac_transformer_grads_t* enc_grads,
+                               const evac_transformer_adam_state_t* state, const evac_adam_config_t* cfg, int32_t obs_dim,
+                               int32_t elem_dim, int32_t num_blocks, const float* grad_sumsq, void* stream);
+/* evac_transformer_minibatch_step: evac_transformer_minibatch_grad with the same 20 arguments (same kernels, same bits in the
+ * gradients before the clip and in stats_out: its sum of squares is that of the UNCLIPPED gradient over 13 + 16 num_blocks
+ * tensors), then evac_transformer_adam_step on params / enc_params (the tensors of `policy` and `encoder`, writable) from
+ * stats_out[7].  One launch more than the gradient (6 + num_blocks + norm_adv), no host synchronisation, capturable: replaying
+ * the captured call n times equals n calls with the same arguments (what a capture freezes is what evac_rpo_minibatch_step's
+ * freezes).  Refusals: as evac_transformer_minibatch_grad, then as evac_transformer_adam_step, each with its own code. */
+int evac_transformer_minibatch_step(const evac_mlp_policy_t* policy, const evac_transformer_t* encoder,
+                                    const evac_rpo_loss_config_t* cfg, int64_t batch_size,
+                                    const float* b_obs, const float* b_actions, const float* b_logprobs,
+                                    const float* b_advantages, const float* b_returns, const float* b_values,
+                                    int64_t n_minibatch, const int64_t* mb_inds, const float* rpo_noise_or_null,
+                                    uint64_t seed, uint64_t draw_counter,
+                                    const evac_mlp_policy_grads_t* grads_out, const evac_transformer_grads_t* encoder_grads_out,
+                                    float* stats_out, void* workspace, void* stream,
+                                    const evac_mlp_policy_grads_t* params, const evac_transformer_grads_t* enc_params,
+                                    const evac_transformer_adam_state_t* state, const evac_adam_config_t* adam_cfg);
+/* evac_transformer_update: evac_rpo_update's contract word for word for the transformer leader: perms [n_epochs][B]; step k
+ * draws at first_draw_counter + k or reads rpo_noise[k]; stats_out[k]; the tail minibatch is run, or skipped below 2 samples (1
+ * without norm_adv); the call clears stop, steps_run, epochs_run on the stream before its first step; with use_target_kl the
+ * launch that finishes an epoch's last minibatch sets header.stop when its approx_kl > target_kl, and every later kernel of the
+ * call (the encoder's as well) returns at once, touching nothing; rows of stats_out beyond steps_run are left as they were.
+ * EQUIVALENCE: bit for bit the sequence of evac_transformer_minibatch_step calls a host loop would make, with a break after an
+ * epoch whose closing approx_kl > target_kl.  workspace: evac_transformer_workspace_bytes(obs_dim, M).  No host
+ * synchronisation; 6 + num_blocks + norm_adv launches per step.
+ * Refusals: as evac_transformer_minibatch_step, and EVAC_ERR_INVALID_ARGUMENT for n_epochs < 1. */
+int evac_transformer_update(const evac_mlp_policy_t* policy, const evac_transformer_t* encoder,
+                            const evac_mlp_policy_grads_t* params, const evac_transformer_grads_t* enc_params,
+                            const evac_mlp_policy_grads_t* grads, const evac_transformer_grads_t* enc_grads,
+                            const evac_rpo_loss_config_t* loss_cfg, const evac_adam_config_t* adam_cfg,
+                            const evac_transformer_adam_state_t* state, int64_t batch_size,
+                            const float* b_obs, const float* b_actions, const float* b_logprobs, const float* b_advantages,
+                            const float* b_returns, const float* b_values, int64_t n_minibatch, int32_t n_epochs,
+                            const int64_t* perms, const float* rpo_noise_or_null, uint64_t seed, uint64_t first_draw_counter,
+                            int32_t use_target_kl, double target_kl, float* stats_out, void* workspace, void* stream);
+
 /* evac_rpo_update_population: evac_rpo_update for n_learners learners in one set of launches: the learner is one more grid
  * dimension of each of the four kernels of a step, so the launch count per minibatch step is that of one learner.
  *   policy / params / grads / state: learner 0's tensors; learner s's are s x the strides further (param_strides for policy and

@@ -4,6 +4,7 @@ replaces.
 
     python tools/transformer_bench.py --part a|b|c|c-eager [--envs 4096] [--steps 128] [--blocks 2] [--use-resid] [--reps 7]
     python tools/transformer_bench.py --part grad-autograd|grad-device [--minibatch 16384] [--blocks 2] [--use-resid] [--reps 7]
+    python tools/transformer_bench.py --part update-torch|update-step|update-one-call [--envs 4096] [--steps 128] [--epochs 10]
 
 N = 60, the rel + ohe Box observation (D = 372, 62 tokens of 6), the trainer's normalisation chain, E envs, T steps per call;
 hipEvent times of whole calls after two warm-up calls, median and range of ``--reps`` calls, one JSON line:
@@ -16,6 +17,12 @@ hipEvent times of whole calls after two warm-up calls, median and range of ``--r
            the module): M = ``--minibatch`` samples of a batch of 2 M observations drawn as 0.6 randn clamped to +-1, no env
   grad-device    the same gradient by ``trainer.transformer_minibatch_grad`` (``evac_transformer_minibatch_grad``: 5 + blocks +
            norm_adv launches)
+  update-torch   one whole update's epochs (``--epochs`` x B / minibatch steps over a random batch of E x T rows, the perturbation
+           drawn on the device): per minibatch ``transformer_minibatch_grad``, the ``foreach`` clip and
+           ``torch.optim.Adam.step()``, as ``RPOTrainer(grad_fn=transformer_kernel_grad)`` does; events around the whole loop
+           after one warm-up update
+  update-step    the same with one ``transformer_minibatch_step`` per minibatch (``TransformerAdam``)
+  update-one-call  the same as one ``transformer_update``
 One part per process, so that a job script can give each its own time limit."""
 import argparse
 import json
@@ -79,16 +86,75 @@ def grad_part(args):
                       "launches": launches, "loss": round(float(stats[0]), 6), "grad_sumsq": float(stats[7]), "calls": len(ms)}))
 
 
+def update_part(args):
+    """One whole update's epochs at N = 60, rel + ohe Box (D = 372), three ways: whole updates between two events after one
+    warm-up update (tools/deepsets_bench.py's update parts with this network's entries)."""
+    from evacuation_amd import trainer
+    E, T, M = args.envs, args.steps, args.minibatch
+    D, B = (N_PED + 2) * 6, E * T
+    torch.manual_seed(0)
+    net = TransformerActorCritic(D, N_PED, num_blocks=args.blocks, use_resid=args.use_resid).to(DEV)
+    cfg = trainer.RPOTrainingConfig(num_envs=E, num_steps=T)
+    g = torch.Generator(device=DEV).manual_seed(1)
+    rnd = lambda *shape: torch.randn(*shape, device=DEV, generator=g)
+    batch = {"b_obs": (0.6 * rnd(B, D)).clamp(-1, 1), "b_actions": rnd(B, 2), "b_logprobs": -2.0 + 0.1 * rnd(B), "b_advantages": rnd(B),
+             "b_returns": rnd(B), "b_values": rnd(B)}
+    perms = torch.stack([torch.randperm(B, device=DEV, generator=g) for _ in range(args.epochs)]).contiguous()
+    sizes = trainer.update_steps(B, M, cfg.norm_adv)
+    steps = args.epochs * len(sizes)
+    params = list(trainer.all_tensors(net))
+    trainer.ensure_grads(net)
+    stats, rows = torch.zeros(8, device=DEV), torch.zeros(steps, 8, device=DEV)
+    if args.part == "update-torch":
+        opt = torch.optim.Adam(params, lr=cfg.learning_rate, eps=1e-5)
+
+        def step(inds, k):
+            trainer.transformer_minibatch_grad(net, batch, inds, cfg, seed=1, draw_counter=k, stats=stats)
+            coef = torch.clamp(cfg.max_grad_norm / (stats[7].sqrt() + 1e-6), max=1.0)       # RPOTrainer.apply_gradient
+            torch._foreach_mul_([p.grad for p in params], coef)
+            opt.step()
+    else:
+        opt = trainer.TransformerAdam(net, lr=cfg.learning_rate, eps=1e-5, max_grad_norm=cfg.max_grad_norm)
+
+        def step(inds, k):
+            trainer.transformer_minibatch_step(net, batch, inds, cfg, opt, seed=1, draw_counter=k, stats=stats)
+
+    def run():
+        if args.part == "update-one-call":
+            trainer.transformer_update(net, batch, perms, cfg, opt, seed=1, first_draw_counter=0, stats=rows, minibatch_size=M)
+            return
+        k = 0
+        for e in range(args.epochs):
+            start = 0
+            for m in sizes:
+                step(perms[e, start:start + m], k)
+                start += M
+                k += 1
+    run()
+    torch.cuda.synchronize()
+    ms = [event_ms(run) for _ in range(max(3, args.reps))]
+    med = statistics.median(ms)
+    print(json.dumps({"part": args.part, "envs": E, "steps": T, "batch": B, "minibatch": M, "epochs": args.epochs, "blocks": args.blocks,
+                      "use_resid": bool(args.use_resid), "minibatch_steps": steps, "launches_per_step": 6 + args.blocks + int(cfg.norm_adv),
+                      "ms_per_update_median": round(med, 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
+                      "us_per_minibatch_step": round(med / steps * 1e3, 2), "updates": len(ms),
+                      "finite": bool(all(torch.isfinite(p).all() for p in params))}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", required=True, choices=["a", "b", "c", "c-eager", "grad-autograd", "grad-device"])
+    ap.add_argument("--part", required=True, choices=["a", "b", "c", "c-eager", "grad-autograd", "grad-device", "update-torch", "update-step",
+                                                     "update-one-call"])
     ap.add_argument("--minibatch", type=int, default=16384)
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--blocks", type=int, default=2)
     ap.add_argument("--use-resid", action="store_true")
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--epochs", type=int, default=10, help="update-*: the epochs of one update")
     args = ap.parse_args()
+    if args.part.startswith("update-"):
+        return update_part(args)
     if args.part.startswith("grad-"):
         return grad_part(args)
     E, T = args.envs, args.steps
