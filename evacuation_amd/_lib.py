@@ -99,6 +99,11 @@ class EvacMlpPolicyStrides(C.Structure):
     _fields_ = [(f, C.c_int64) for f, _ in EvacMlpPolicy._fields_[2:]]
 
 
+class EvacDeepSetsStrides(C.Structure):
+    """evac_deepsets_strides_t: floats from learner s to learner s + 1, per tensor of evac_deepsets_t"""
+    _fields_ = [(f, C.c_int64) for f, _ in EvacDeepSets._fields_[2:]]
+
+
 class EvacAdamConfig(C.Structure):
     """evac_adam_config_t"""
     _fields_ = [(f, C.c_double) for f in ("lr", "beta1", "beta2", "eps", "max_grad_norm")]
@@ -268,6 +273,23 @@ SIGNATURES = {
                                              C.POINTER(EvacAdamConfig), C.POINTER(EvacAdamState), C.c_int64, _P, _P, _P, _P, _P, _P,
                                              C.c_int64, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                              C.c_int32, C.c_double, _P, _P, _P]),
+    # the population of deep-sets leaders: the linear population's arguments with the encoder's structs and strides beside the
+    # policy's
+    "evac_policy_rollout_population_deepsets": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyStrides),
+                                                          C.POINTER(EvacDeepSets), C.POINTER(EvacDeepSetsStrides), C.c_int32,
+                                                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float,
+                                                          C.c_float, _P]),
+    "evac_deepsets_population_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32]),
+    "evac_deepsets_update_population": (C.c_int, [C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacDeepSets),
+                                                  C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads),
+                                                  C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads),
+                                                  C.POINTER(EvacMlpPolicyStrides), C.POINTER(EvacDeepSetsStrides),
+                                                  C.POINTER(EvacMlpPolicyStrides), C.POINTER(EvacDeepSetsStrides),
+                                                  C.POINTER(EvacMlpPolicyStrides), C.POINTER(EvacDeepSetsStrides), C.c_int64,
+                                                  C.POINTER(EvacRpoLossConfig), C.POINTER(EvacAdamConfig),
+                                                  C.POINTER(EvacDeepSetsAdamState), C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64,
+                                                  C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                  C.c_int32, C.c_double, _P, _P, _P]),
     "evac_gae_learners": (C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.POINTER(EvacLearnerHyper),
                                     _P, _P, _P]),
     "evac_policy_rollout_sweep": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyStrides), C.c_int32,

@@ -11,23 +11,10 @@
 // by-value argument struct directly: scalar loads from the kernel-argument segment, no select chain, no private copy.
 #pragma once
 
+#include "evac_deepsets_adam_args.h"
 #include "evac_train.h"
 
 namespace evac {
-
-constexpr int kSetAdamTensors = kAdamTensors + 6;   // evac_mlp_policy_grads_t, then evac_deepsets_grads_t
-struct SetAdamArgs {
-    float *p[kSetAdamTensors], *g[kSetAdamTensors], *m[kSetAdamTensors], *v[kSetAdamTensors];
-    int wg_end[kSetAdamTensors];                // running workgroup counts: tensor i has workgroups [wg_end[i - 1], wg_end[i])
-    int n[kSetAdamTensors];                     // elements of tensor i
-    AdamHeader* hdr;
-    const float* sumsq;                         // the sum of squares of all gradient entries, 19 tensors (device)
-    const float* stats;                         // the step's statistics (approx_kl at [5]) for the early exit, or NULL
-    double lr, beta1, beta2, target_kl;
-    float max_norm, w, b2, u, eps;              // as AdamArgs'
-    int gated, epoch_last, use_target_kl;
-};
-static_assert(sizeof(SetAdamArgs) <= 1024, "k_adam_set's kernel arguments");
 
 __global__ __launch_bounds__(kAdamBlock) void k_adam_set(SetAdamArgs a) {
     if (a.gated && a.hdr->stop) return;

@@ -99,15 +99,58 @@ __device__ __forceinline__ float set_preact(const f4 w0, const f4 w1, const floa
     return v;
 }
 
+// The POPULATION form (include/evac.h: evac_deepsets_update_population): the learner is blockIdx.y, `a` holds learner 0's
+// pointers and the workgroup moves them to its learner's before anything else.  Parameters and gradients by the tensors' strides;
+// what lies in a learner's workspace slice (dY, s, t, g1, the partials, tickets and slots) by the slice; what the actor-critic's
+// kernels read as ONE common batch of S x M rows -- Y, the gathered columns and the index list -- by the learner's M rows.  The
+// caller's batch (obs .. val) is common and stays.  Every shift is a scalar multiply-add on a pointer from the kernel-argument
+// segment; gridDim.x is the lone kernel's, so the ticket tests hold per learner.
+struct SetLearnerStrides {
+    int64_t p[6], g[6];                         // floats from learner s to s + 1: the encoder's parameters, gradients
+    int64_t w1a, w1c;                           // ... the actor's and the critic's first layer
+    int64_t hdr, ws;                            // bytes: the optimiser's header, the workspace slice
+    int64_t inds, stats;                        // elements of perms / stats_out per learner
+};
+template <class T>
+__device__ __forceinline__ T* set_shift_bytes(T* p, int64_t bytes) { return (T*)((char*)p + bytes); }
+// Moves `a` to the workgroup's learner; returns the learner's header (the stop gate).
+__device__ __forceinline__ const AdamHeader* set_learner(SetArgs& a, const AdamHeader* h, const SetLearnerStrides& q) {
+    const int64_t s = (int64_t)blockIdx.y;
+    a.phi_w1 += s * q.p[0]; a.phi_b1 += s * q.p[1]; a.phi_w2 += s * q.p[2]; a.phi_b2 += s * q.p[3]; a.rho_w += s * q.p[4]; a.rho_b += s * q.p[5];
+    a.g_phi_w1 += s * q.g[0]; a.g_phi_b1 += s * q.g[1]; a.g_phi_w2 += s * q.g[2]; a.g_phi_b2 += s * q.g[3];
+    a.g_rho_w += s * q.g[4]; a.g_rho_b += s * q.g[5];
+    a.w1a += s * q.w1a; a.w1c += s * q.w1c;
+    a.inds += s * q.inds;
+    a.stats += s * q.stats;
+    const int64_t rows = s * a.M, slice = s * q.ws;
+    a.Y += rows * a.D;
+    a.act_g += 2 * rows; a.lp_g += rows; a.adv_g += rows; a.ret_g += rows; a.val_g += rows; a.ident += rows;
+    a.dY = set_shift_bytes(a.dY, slice); a.sv = set_shift_bytes(a.sv, slice); a.tv = set_shift_bytes(a.tv, slice);
+    a.g1 = set_shift_bytes(a.g1, slice); a.parts = set_shift_bytes(a.parts, slice); a.rparts = set_shift_bytes(a.rparts, slice);
+    a.tickets = set_shift_bytes(a.tickets, slice); a.slots = set_shift_bytes(a.slots, slice);
+    return (const AdamHeader*)((const char*)h + s * q.hdr);
+}
+// the first index of the workgroup's learner in the common index list (0 for a lone learner)
+template <class... Gate>
+__device__ __forceinline__ int64_t set_ident_base(int M) {
+    if constexpr (sizeof...(Gate) == 2) return (int64_t)blockIdx.y * M;
+    else return 0;
+}
+
 // The three kernels are templates over an optional trailing argument, as k_rpo_* of evac_train.h: k_set_*<> (SetArgs alone) are
 // evac_deepsets_minibatch_grad's and evac_deepsets_minibatch_step's; k_set_*<const AdamHeader*> are evac_deepsets_update's, which
 // return at once, touching nothing, when the header's stop flag is set (a gated k_set_encode then leaves k_set_finish's tickets
-// as they are: every later kernel of the call returns too).  The bodies stay inside the kernels: moved into __device__
+// as they are: every later kernel of the call returns too); k_set_*<const AdamHeader*, SetLearnerStrides> are the population's
+// (above), whose two lines -- the first `if constexpr` and set_ident_base -- the other two forms compile to what they had: the device assembly
+// of k_set_*<> and k_set_*<const AdamHeader*> is line for line what it was without them.  The bodies stay
+// inside the kernels: moved into __device__
 // functions (SetArgs by reference, by value, const or not) all three compiled to other instructions than as plain kernels, and
 // k_set_backward began to keep scalars in VGPR lanes; as written, k_set_*<> are instruction for instruction what they were.
 template <class... Gate>
 __global__ __launch_bounds__(kSetBlock) void k_set_encode(SetArgs a, Gate... gate) {
-    if constexpr (sizeof...(Gate) != 0) {
+    if constexpr (sizeof...(Gate) == 2) {
+        if (rpo_stopped(set_learner(a, gate...))) return;
+    } else if constexpr (sizeof...(Gate) != 0) {
         if (rpo_stopped(gate...)) return;
     }
     constexpr int H = kSetTrainHidden;
@@ -139,7 +182,7 @@ __global__ __launch_bounds__(kSetBlock) void k_set_encode(SetArgs a, Gate... gat
         else if (lane == 3) a.adv_g[m] = a.adv[idx];
         else if (lane == 4) a.ret_g[m] = a.ret[idx];
         else if (lane == 5) a.val_g[m] = a.val[idx];
-        else if (lane == 6) a.ident[m] = (int64_t)m;
+        else if (lane == 6) a.ident[m] = set_ident_base<Gate...>(M) + (int64_t)m;
         wave_sync();
         // A: the pooled hidden sums
         for (int base = 0; base < S; base += 64) {
@@ -196,7 +239,9 @@ __global__ __launch_bounds__(kSetBlock) void k_set_encode(SetArgs a, Gate... gat
 
 template <class... Gate>
 __global__ __launch_bounds__(kSetBlock) void k_set_backward(SetArgs a, Gate... gate) {
-    if constexpr (sizeof...(Gate) != 0) {
+    if constexpr (sizeof...(Gate) == 2) {
+        if (rpo_stopped(set_learner(a, gate...))) return;
+    } else if constexpr (sizeof...(Gate) != 0) {
         if (rpo_stopped(gate...)) return;
     }
     constexpr int H = kSetTrainHidden, H1 = kTrainHidden;
@@ -363,7 +408,9 @@ __device__ __forceinline__ float set_block_sum(float v, float* buf) {
 
 template <class... Gate>
 __global__ __launch_bounds__(kSetBlock) void k_set_finish(SetArgs a, Gate... gate) {
-    if constexpr (sizeof...(Gate) != 0) {
+    if constexpr (sizeof...(Gate) == 2) {
+        if (rpo_stopped(set_learner(a, gate...))) return;
+    } else if constexpr (sizeof...(Gate) != 0) {
         if (rpo_stopped(gate...)) return;
     }
     constexpr int H = kSetTrainHidden;

@@ -1,6 +1,6 @@
 // What the entries that run a network on a handle's envs share (evac_api.hip: evac_policy_rollout*, evac_policy_evaluate*;
-// evac_deepsets_api.hip, evac_transformer_api.hip: their forms with an encoder; evac_capture_api.hip: the evaluation entries that
-// record frames).  The handle's struct stays evac_api.hip's own:
+// evac_deepsets_api.hip, evac_transformer_api.hip: their forms with an encoder; evac_deepsets_population_api.hip: the collection of
+// a population of deep-sets leaders; evac_capture_api.hip: the evaluation entries that record frames).  The handle's struct stays evac_api.hip's own:
 // the handle_* functions are defined there and are not exported from the library.  Below them, host-only and inline: what
 // every collection entry and every evaluation entry refuses, the one-wave limit, a population's shares of the envs, and the grid.
 // Each returns the text that follows the entry's name in its message (empty: accepted), as mlp_policy_check does; the entry
@@ -128,10 +128,16 @@ inline int encoder_networks_check(const evac::Params& p, const evac_mlp_policy_t
     return Enc::check(p, *encoder, ea, why);
 }
 
+// A lone learner: nothing more to refuse, the whole handle in Enc's own kernel.
+struct NoLearners {
+    static constexpr bool kOn = false;
+};
 // evac_policy_rollout_<encoder> (`a`: collect_outputs).  Every refusal before the first HIP call; one kernel on `stream`.
-template <class Enc>
+// Learners (kOn): the population form of the entry (evac_deepsets_population_api.hip) -- check(p, policy, encoder) adds its
+// refusals behind the networks' and before the alignment of actions_out, in the same form, and launch(view, n_steps, a, na, ea, stream) enqueues its own kernel.
+template <class Enc, class Learners = NoLearners>
 inline int encoder_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_t* policy, evac::PolicyArgs a, const evac::NormArgs& na,
-                           const typename Enc::Struct* encoder, void* stream) {
+                           const typename Enc::Struct* encoder, void* stream, Learners learners = Learners{}) {
     using evac_host::handle_fail;
     const std::string w = Enc::kRollout;
     evac_host::HandleView v;
@@ -142,12 +148,19 @@ inline int encoder_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_poli
     why = collect_check(n_steps, a, false, policy);    // (the first refusal in the entry's order of checks)
     if (!why.empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
     if (const int rc = encoder_networks_check<Enc>(v.p, policy, encoder, a, ea, why); rc != EVAC_OK) return handle_fail(h, rc, w + why);
+    if constexpr (Learners::kOn) {
+        if (!(why = learners.check(v.p, *policy, *encoder)).empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
+    }
     why = collect_aligned(a);
     if (!why.empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
     if (const int st = evac_host::handle_settle(h, (hipStream_t)stream); st != EVAC_OK) return st;
     DeviceGuard g(v.device);
-    hipLaunchKernelGGL(Enc::rollout_kernel(na.state != nullptr, v.default_cfg), dim3((unsigned)policy_wgs(v.p.n_envs)),
-                       dim3(evac::PolicyFamily::kBlock), 0, (hipStream_t)stream, v.p, (int)n_steps, a, na, ea);
+    if constexpr (Learners::kOn) {
+        learners.launch(v, (int)n_steps, a, na, ea, (hipStream_t)stream);
+    } else {
+        hipLaunchKernelGGL(Enc::rollout_kernel(na.state != nullptr, v.default_cfg), dim3((unsigned)policy_wgs(v.p.n_envs)),
+                           dim3(evac::PolicyFamily::kBlock), 0, (hipStream_t)stream, v.p, (int)n_steps, a, na, ea);
+    }
     return evac_host::handle_check_launch(h, w.c_str());
 }
 

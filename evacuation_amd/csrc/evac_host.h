@@ -94,6 +94,20 @@ inline std::string deepsets_check(const evac_deepsets_t& S, int32_t obs_dim, int
     return {};
 }
 
+// A population's strides of the set encoder's six tensors into `out` (evac_deepsets_strides_t, for obs_dim D and element width
+// ed): as mlp_strides_ok, and rho_w's rows stay 16-byte aligned in every learner (its stride a multiple of 4 floats).
+inline bool deepsets_strides_ok(const evac_deepsets_strides_t* st, int32_t obs_dim, int32_t set_elem_dim, int32_t n_learners, int64_t* out) {
+    const int64_t H = kSetEncoderHidden, D = obs_dim;
+    const int64_t least[6] = {H * set_elem_dim, H, H * H, H, D * H, D};
+    for (int i = 0; i < 6; ++i) {
+        out[i] = (&st->phi_w1)[i];
+        if (n_learners > 1 && out[i] < least[i]) return false;
+    }
+    return n_learners <= 1 || out[4] % 4 == 0;
+}
+static_assert(sizeof(evac_deepsets_strides_t) == 6 * sizeof(int64_t) && offsetof(evac_deepsets_strides_t, rho_b) == 5 * sizeof(int64_t),
+              "deepsets_strides_ok walks the struct as 6 consecutive strides, phi_w1 first and rho_b last");
+
 // The instantiation of kernel template K over two or three bools that are known at run time (grav, norm, def of the callers).
 #define EVAC_PICK_BOOL2(K, b0, b1) ((b0) ? ((b1) ? K<true, true> : K<true, false>) : ((b1) ? K<false, true> : K<false, false>))
 #define EVAC_PICK_BOOL3(K, b0, b1, b2)                                                                                            \

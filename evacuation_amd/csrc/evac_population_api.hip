@@ -20,6 +20,15 @@ void population_launch_adv_stats(const RpoArgs& a, const LearnerStrides& q, cons
                                  int n_learners, hipStream_t stream) {
     hipLaunchKernelGGL(k_population_adv_stats, dim3(1, (unsigned)n_learners), dim3(kFinishBlock), 0, stream, a, q, d, gate);
 }
+void population_launch_grad(const RpoArgs& a, const LearnerStrides& q, const LearnerDraws& d, const AdamHeader* gate, dim3 grid,
+                            size_t lds, hipStream_t stream) {
+    hipLaunchKernelGGL(k_population_grad, grid, dim3(kGradBlock), lds, stream, a, q, d, gate);
+}
+void population_launch_finish(const RpoArgs& a, const LearnerStrides& q, const LearnerDraws& d, const AdamHeader* gate, dim3 grid,
+                              hipStream_t stream) {
+    hipLaunchKernelGGL(k_population_finish, grid, dim3(kFinishBlock), 0, stream, a, q, d, gate);
+}
+int population_raise_grad_lds(int D, int dev) { return rpo_raise_lds<k_population_grad>(D, dev); }
 }  // namespace evac
 
 extern "C" {
@@ -52,7 +61,7 @@ int evac_rpo_update_population(int32_t n_learners, const evac_mlp_policy_t* poli
     o.target_kl = target_kl;
     const int dev = device_of(workspace);
     DeviceGuard g(dev);
-    if (rpo_raise_lds<evac::k_population_grad>(a.D, dev) != EVAC_OK) return EVAC_ERR_HIP;
+    if (evac::population_raise_grad_lds(a.D, dev) != EVAC_OK) return EVAC_ERR_HIP;
     hipStream_t S = (hipStream_t)stream;
     evac::population_launch_begin(o.hdr, header_stride_bytes, n_learners, S);
     // (draw counter base 0: the kernels add the learner's first draw counter)
@@ -61,8 +70,8 @@ int evac_rpo_update_population(int32_t n_learners, const evac_mlp_policy_t* poli
                          const LearnerGrids grid = learner_grids(step, adam, (unsigned)n_learners);
                          const evac::AdamHeader* gate = adam.hdr;
                          if (step.norm_adv) evac::population_launch_adv_stats(step, q, d, gate, n_learners, S);
-                         hipLaunchKernelGGL(evac::k_population_grad, grid.grad, dim3(evac::kGradBlock), grid.lds, S, step, q, d, gate);
-                         hipLaunchKernelGGL(evac::k_population_finish, grid.finish, dim3(evac::kFinishBlock), 0, S, step, q, d, gate);
+                         evac::population_launch_grad(step, q, d, gate, grid.grad, grid.lds, S);
+                         evac::population_launch_finish(step, q, d, gate, grid.finish, S);
                          hipLaunchKernelGGL(evac::k_population_optimizer, grid.optimizer, dim3(evac::kAdamBlock), 0, S, adam, q);
                      });
     return hipGetLastError() == hipSuccess ? EVAC_OK : EVAC_ERR_HIP;

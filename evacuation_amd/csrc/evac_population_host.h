@@ -1,7 +1,7 @@
 // Host side of the population's update, the part its two translation units share (evac_population_api.hip: one configuration;
-// evac_sweep_api.hip: a configuration per learner): the checks and the learners' strides, a step's grids, and the two launches of
-// evac_population_api.hip that the sweep reuses (no hyperparameter enters them), reached through plain host functions so that
-// evac_population.h's kernels are defined in one translation unit alone.
+// evac_sweep_api.hip: a configuration per learner; evac_deepsets_population_api.hip: behind a set encoder): the checks and the
+// learners' strides, a step's grids, and the launches of evac_population_api.hip that the other units reuse (no hyperparameter
+// enters them), reached through plain host functions so that evac_population.h's kernels are defined in one translation unit alone.
 #pragma once
 
 #include "evac_learner.h"
@@ -12,6 +12,13 @@ namespace evac {
 void population_launch_begin(AdamHeader* hdr, int64_t header_stride_bytes, int n_learners, hipStream_t stream);
 void population_launch_adv_stats(const RpoArgs& a, const LearnerStrides& q, const LearnerDraws& d, const AdamHeader* gate,
                                  int n_learners, hipStream_t stream);
+// k_population_grad and k_population_finish on `stream`, for the population of deep-sets leaders (evac_deepsets_population_api.hip:
+// the same launches on the learners' encoded batch), and the raising of k_population_grad's dynamic-LDS limit (rpo_raise_lds)
+void population_launch_grad(const RpoArgs& a, const LearnerStrides& q, const LearnerDraws& d, const AdamHeader* gate, dim3 grid,
+                            size_t lds, hipStream_t stream);
+void population_launch_finish(const RpoArgs& a, const LearnerStrides& q, const LearnerDraws& d, const AdamHeader* gate, dim3 grid,
+                              hipStream_t stream);
+int population_raise_grad_lds(int D, int dev);
 }  // namespace evac
 
 namespace {

@@ -2,7 +2,8 @@
 // evac_population_api.hip: a population; evac_sweep_api.hip: ... with a configuration per learner; evac_deepsets_train_api.hip:
 // the gradient behind a set encoder; evac_deepsets_update_api.hip: its optimiser step and whole update;
 // evac_transformer_train_api.hip: the gradient behind an attention encoder; evac_transformer_update_api.hip: its optimiser step
-// and whole update -- what those four share beyond this file is in evac_encoder_train_host.h): what the entries check of
+// and whole update -- what those four share beyond this file is in evac_encoder_train_host.h; evac_deepsets_population_api.hip:
+// a population of deep-sets leaders): what the entries check of
 // their arguments, the kernels' argument structs, the walk over an update call's minibatch steps, the raising of a gradient
 // kernel's dynamic-LDS limit, and the launches of one minibatch's gradient.
 #pragma once

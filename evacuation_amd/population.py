@@ -14,6 +14,10 @@ update is a chain of small launches on a nearly idle chip; here learner s rides 
   one learner (``evac_rpo_update_population``).
 * ``PopulationTrainer``: one iteration of the reference's loop for all learners per ``update()``; ``evaluate()`` runs every
   learner's whole episodes in one set of launches (``evaluation.PopulationEvaluator``, ``evac_policy_evaluate_population``).
+* ``DeepSetsPopulation``: the same for the deep-sets leader -- 19 stacked tensors, ``nets[s]`` a ``DeepSetsActorCritic`` of
+  views.  ``PopulationAdam``, ``policy_rollout_population`` and ``PopulationTrainer`` take one as they take a ``PolicyPopulation``;
+  its update is ``deepsets_update_population`` (``evac_deepsets_update_population``: seven launches per minibatch step, as for one
+  such learner).  Sweeps and the one-launch evaluation of such learners are not built: ``evaluate()`` runs learner by learner.
 * Sweeps: every float-valued hyperparameter (``SWEEP_FIELDS``) may differ per learner -- ``PopulationTrainer(env, population,
   [cfg_0, .., cfg_S-1])``, ``rpo_update_population(cfg=[...])``, ``gae(gamma=[...])``, ``policy_rollout_population(gammas=[...])``;
   ``sweep_configs`` makes the cartesian product.  The learners' values ride in the kernel arguments beside their seeds
@@ -35,7 +39,8 @@ import torch
 from torch import nn
 
 from . import _lib
-from .policy import HIDDEN, LinearActorCritic, _check_structure, mlp_tensors, refuse_deepsets
+from .policy import (HIDDEN, SET_HIDDEN, DeepSetsActorCritic, LinearActorCritic, _check_encoder, _check_structure, all_tensors, mlp_tensors,
+                     refuse_deepsets, refuse_transformer)
 from .trainer import (BATCH_KEYS, DeviceAdam, RPOTrainingConfig, _f32, _loss_config, _stream, _u64, decode_header, flatten_batch, gae,
                       update_steps)
 from .vector_env import STATS_FIELDS, _ptr
@@ -97,6 +102,21 @@ def population_rows(inds: torch.Tensor, learner, envs_per_learner: int, num_lear
     return torch.div(inds, E_l, rounding_mode="floor") * (S * E_l) + learner * E_l + inds % E_l
 
 
+def _bind_row(net, tensors, grads, s: int) -> None:
+    """The parameters of ``net`` (``all_tensors`` order: 13, or 19 with a set encoder) become views of row s of ``tensors`` (and
+    their ``.grad`` views of row s of ``grads``)."""
+    a, c = net.actor_mean, net.critic
+    owners = [(a[0], "weight"), (a[0], "bias"), (a[2], "weight"), (a[2], "bias"), (a[4], "weight"), (a[4], "bias"),
+              (net, "actor_logstd"), (c[0], "weight"), (c[0], "bias"), (c[2], "weight"), (c[2], "bias"), (c[4], "weight"), (c[4], "bias")]
+    if len(tensors) == 19:
+        phi, rho = net.deep_sets.transform_phi, net.deep_sets.transform_rho
+        owners += [(phi[0], "weight"), (phi[0], "bias"), (phi[2], "weight"), (phi[2], "bias"), (rho[0], "weight"), (rho[0], "bias")]
+    for i, (mod, name) in enumerate(owners):
+        prm = nn.Parameter(tensors[i][s])
+        prm.grad = grads[i][s]
+        setattr(mod, name, prm)
+
+
 class PolicyPopulation:
     """S actor-critics of observation width ``obs_dim`` as 13 stacked tensors ``[S, ...]`` on ``device``; see the module's
     docstring.  ``tensors`` / ``grads``: the stacks, in ``evac_mlp_policy_t`` order; ``strides``: a learner's distance in each."""
@@ -128,17 +148,54 @@ class PolicyPopulation:
 
     def _bind(self, net: LinearActorCritic, s: int) -> None:
         """The parameters of ``net`` become views of row s (and their ``.grad`` views of the gradients' row s)."""
-        a, c = net.actor_mean, net.critic
-        owners = [(a[0], "weight"), (a[0], "bias"), (a[2], "weight"), (a[2], "bias"), (a[4], "weight"), (a[4], "bias"),
-                  (net, "actor_logstd"), (c[0], "weight"), (c[0], "bias"), (c[2], "weight"), (c[2], "bias"), (c[4], "weight"), (c[4], "bias")]
-        for i, (mod, name) in enumerate(owners):
-            prm = nn.Parameter(self.tensors[i][s])
-            prm.grad = self.grads[i][s]
-            setattr(mod, name, prm)
+        _bind_row(net, self.tensors, self.grads, s)
 
     def policy_struct(self) -> "_lib.EvacMlpPolicy":
         """``evac_mlp_policy_t`` of learner 0, the base the strides count from (every learner's views were checked when made)."""
         return self._policy
+
+
+class DeepSetsPopulation:
+    """S deep-sets leaders (``DeepSetsActorCritic(obs_dim, number_of_pedestrians)``) as 19 stacked tensors ``[S, ...]`` on
+    ``device``: the actor-critic's 13 in ``evac_mlp_policy_t`` order, then the set encoder's 6 in ``evac_deepsets_t`` order
+    (``all_tensors``).  ``nets[s]`` is a ``DeepSetsActorCritic`` whose parameters (and ``.grad``) are views of row s, initialised
+    exactly as ``torch.manual_seed(seeds[s]); DeepSetsActorCritic(obs_dim, number_of_pedestrians)``: ``policy_rollout``,
+    ``policy_evaluate``, ``PolicyEvaluator`` and ``DeviceAdam`` take a learner as they take any such network.  ``strides`` /
+    ``encoder_strides``: a learner's distance in each of the 13 / the 6."""
+
+    def __init__(self, obs_dim: int, number_of_pedestrians: int, seeds: Sequence[int], device="cuda:0"):
+        seeds = [int(s) for s in seeds]
+        if not 1 <= len(seeds) <= MAX_LEARNERS:
+            raise ValueError(f"DeepSetsPopulation: {len(seeds)} learners; expected 1..{MAX_LEARNERS}")
+        self.obs_dim, self.number_of_pedestrians = int(obs_dim), int(number_of_pedestrians)
+        self.seeds, self.device, self.num_learners = seeds, torch.device(device), len(seeds)
+        fresh = []
+        with torch.random.fork_rng(devices=[]):                # (the caller's generator is left where it was)
+            for seed in seeds:
+                torch.manual_seed(seed)
+                fresh.append(DeepSetsActorCritic(self.obs_dim, self.number_of_pedestrians))
+        with torch.no_grad():
+            self.tensors = [torch.stack([all_tensors(n)[i].detach() for n in fresh]).to(self.device).contiguous() for i in range(19)]
+        self.grads = [torch.zeros_like(t) for t in self.tensors]
+        self.nets: List[DeepSetsActorCritic] = []
+        for s, net in enumerate(fresh):
+            _bind_row(net, self.tensors, self.grads, s)
+            self.nets.append(net)
+            _check_structure(net, self.obs_dim, self.device)
+            self.set_elem_dim = _check_encoder(net, self.obs_dim, self.device, self.number_of_pedestrians)
+        sizes = [int(t[0].numel()) for t in self.tensors]
+        self.strides = _lib.EvacMlpPolicyStrides(*sizes[:13])
+        self.encoder_strides = _lib.EvacDeepSetsStrides(*sizes[13:])
+        self._policy = _lib.EvacMlpPolicy(self.obs_dim, HIDDEN, *(t.data_ptr() for t in self.tensors[:13]))
+        self._encoder = _lib.EvacDeepSets(self.set_elem_dim, SET_HIDDEN, *(t.data_ptr() for t in self.tensors[13:]))
+
+    def policy_struct(self) -> "_lib.EvacMlpPolicy":
+        """``evac_mlp_policy_t`` of learner 0, the base the strides count from (every learner's views were checked when made)."""
+        return self._policy
+
+    def encoder_struct(self) -> "_lib.EvacDeepSets":
+        """``evac_deepsets_t`` of learner 0, the base ``encoder_strides`` count from."""
+        return self._encoder
 
 
 class PopulationAdam:
@@ -146,10 +203,10 @@ class PopulationAdam:
     learner).  ``learners[s]`` is a ``DeviceAdam`` whose state is row s and whose ``param_groups`` are its own: ``lr`` and
     ``max_grad_norm`` (one value or a sequence of S) may differ per learner, the betas and eps are one value for all.
     ``param_groups[s]`` is learner s's group; ``state_dict(s)`` / ``load_state_dict(s, sd)`` are its, in ``DeviceAdam``'s
-    format, and touch no other learner."""
+    format, and touch no other learner.  For a ``DeepSetsPopulation`` the stacks are its 19 and ``learners[s]`` a ``DeviceAdam``
+    over all 19 tensors of row s."""
 
-    def __init__(self, population: PolicyPopulation, lr=3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5,
-                 max_grad_norm=0.5):
+    def __init__(self, population, lr=3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm=0.5):
         self.population = population
         S, dev = population.num_learners, population.device
         lrs, norms = _per_learner(lr, S, "lr"), _per_learner(max_grad_norm, S, "max_grad_norm")
@@ -161,6 +218,7 @@ class PopulationAdam:
                          for s, net in enumerate(population.nets)]
         self.header_stride_bytes = 64
         self.moment_strides = population.strides
+        self.encoder_moment_strides = population.encoder_strides if isinstance(population, DeepSetsPopulation) else None
 
     @property
     def param_groups(self) -> List[dict]:
@@ -208,10 +266,12 @@ def _batch_ptrs(batch: Dict[str, torch.Tensor]):
     return int(B), int(D), [int(B)] + [_ptr(batch[k]) for k in BATCH_KEYS]
 
 
-def population_workspace_bytes(obs_dim: int, minibatch_size: int, num_learners: int) -> int:
-    need = int(_lib.load().evac_rpo_population_workspace_bytes(int(obs_dim), int(minibatch_size), int(num_learners)))
+def population_workspace_bytes(obs_dim: int, minibatch_size: int, num_learners: int, *, deepsets: bool = False) -> int:
+    """The update's workspace for a ``PolicyPopulation``, or with ``deepsets`` for a ``DeepSetsPopulation``."""
+    sizer = f"evac_{'deepsets' if deepsets else 'rpo'}_population_workspace_bytes"
+    need = int(getattr(_lib.load(), sizer)(int(obs_dim), int(minibatch_size), int(num_learners)))
     if need < 0:
-        raise _lib.EvacError(need, f"evac_rpo_population_workspace_bytes({obs_dim}, {minibatch_size}, {num_learners})")
+        raise _lib.EvacError(need, f"{sizer}({obs_dim}, {minibatch_size}, {num_learners})")
     return need
 
 
@@ -243,6 +303,35 @@ def rpo_update_population(population: PolicyPopulation, batch: Dict[str, torch.T
     ``opt.learners[s].param_groups[0]``'s ``lr`` / ``max_grad_norm``, bit for bit ``rpo_update(..., cfg[s], DeviceAdam(lr, ...))``
     alone; ``norm_adv``, ``clip_vloss`` and the minibatch size are learner 0's and must be everybody's.  With one ``cfg`` the
     optimiser's per-learner values are honoured in the same way."""
+    if isinstance(population, DeepSetsPopulation):
+        raise ValueError("rpo_update_population: a DeepSetsPopulation's update is deepsets_update_population")
+    return _update_population(population, batch, rows, cfg, opt, minibatch_size, rpo_noise, seeds, first_draw_counters, stats, workspace,
+                              "rpo_update_population")
+
+
+def deepsets_update_population(population: DeepSetsPopulation, batch: Dict[str, torch.Tensor], rows: torch.Tensor, cfg,
+                               opt: PopulationAdam, *, minibatch_size: Optional[int] = None, rpo_noise: Optional[torch.Tensor] = None,
+                               seeds: Optional[Sequence[int]] = None, first_draw_counters: Optional[Sequence[int]] = None,
+                               stats: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """``deepsets_update`` for every learner of a ``DeepSetsPopulation`` in one host call (``evac_deepsets_update_population``):
+    ``rpo_update_population``'s arguments and returns, with ONE configuration -- learner s is, bit for bit,
+    ``deepsets_update(population.nets[s], its own rows, cfg, DeviceAdam(nets[s]), seed=seeds[s],
+    first_draw_counter=first_draw_counters[s])`` alone.  Seven launches per minibatch step (six without ``norm_adv``), no host
+    synchronisation.  A sequence of configurations, or an optimiser whose learners differ in ``lr`` / ``max_grad_norm``, is a
+    ``ValueError``: sweeps of deep-sets learners are not built."""
+    if not isinstance(population, DeepSetsPopulation):
+        raise ValueError("deepsets_update_population: a DeepSetsPopulation is expected (a PolicyPopulation's update is "
+                         "rpo_update_population)")
+    if isinstance(cfg, (list, tuple)) or not opt.uniform():
+        raise ValueError("deepsets_update_population: sweeps of deep-sets learners are not built: one configuration, and one lr / "
+                         "max_grad_norm, for all learners")
+    return _update_population(population, batch, rows, cfg, opt, minibatch_size, rpo_noise, seeds, first_draw_counters, stats, workspace,
+                              "deepsets_update_population")
+
+
+def _update_population(population, batch, rows, cfg, opt, minibatch_size, rpo_noise, seeds, first_draw_counters, stats, workspace, what):
+    """The body of ``rpo_update_population`` and ``deepsets_update_population`` (``what``: the caller's name)."""
+    deepsets = isinstance(population, DeepSetsPopulation)
     if opt.population is not population:
         raise ValueError("the PopulationAdam was made for another population")
     S, dev = population.num_learners, population.device
@@ -250,11 +339,11 @@ def rpo_update_population(population: PolicyPopulation, batch: Dict[str, torch.T
     if isinstance(cfg, (list, tuple)):
         cfgs = list(cfg)
         if len(cfgs) != S:
-            raise ValueError(f"rpo_update_population: {len(cfgs)} configurations for {S} learners")
+            raise ValueError(f"{what}: {len(cfgs)} configurations for {S} learners")
         for s, c in enumerate(cfgs):
             for f in ("norm_adv", "clip_vloss") + (("minibatch_size",) if minibatch_size is None else ()):
                 if getattr(c, f, True) != getattr(cfgs[0], f, True):
-                    raise ValueError(f"rpo_update_population: {f} of learner {s} differs from learner 0's")
+                    raise ValueError(f"{what}: {f} of learner {s} differs from learner 0's")
         cfg = cfgs[0]
     elif not opt.uniform():
         cfgs = [cfg] * S
@@ -266,7 +355,7 @@ def rpo_update_population(population: PolicyPopulation, batch: Dict[str, torch.T
     M = int(cfg.minibatch_size if minibatch_size is None else minibatch_size)
     norm_adv = bool(getattr(cfg, "norm_adv", True))
     if M < (2 if norm_adv else 1):
-        raise ValueError(f"rpo_update_population: minibatch_size = {M}")
+        raise ValueError(f"{what}: minibatch_size = {M}")
     M = min(M, B_l)
     steps = n_epochs * len(update_steps(B_l, M, norm_adv))
     if rpo_noise is not None:
@@ -275,25 +364,36 @@ def rpo_update_population(population: PolicyPopulation, batch: Dict[str, torch.T
         stats = torch.zeros(S, steps, 8, dtype=torch.float32, device=dev)
     else:
         _f32(stats, (S, steps, 8), "stats")
-    need = population_workspace_bytes(D, M, S)
+    need = population_workspace_bytes(D, M, S, deepsets=deepsets)
     if workspace is None or workspace.numel() < need or workspace.device != dev:
         workspace = torch.empty(need, dtype=torch.uint8, device=dev)
     seeds = population.seeds if seeds is None else [int(x) for x in seeds]
     counters = [0] * S if first_draw_counters is None else [int(x) for x in first_draw_counters]
     if len(seeds) != S or len(counters) != S:
-        raise ValueError(f"rpo_update_population: seeds and first_draw_counters must have {S} entries")
+        raise ValueError(f"{what}: seeds and first_draw_counters must have {S} entries")
     u64 = C.c_uint64 * S
     if D != population.obs_dim:
-        raise ValueError(f"rpo_update_population: b_obs has {D} columns, the population's observation has {population.obs_dim}")
+        raise ValueError(f"{what}: b_obs has {D} columns, the population's observation has {population.obs_dim}")
     pol = population.policy_struct()
-    params = _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in population.tensors))
-    grads = _lib.EvacMlpPolicyGrads(*(g.data_ptr() for g in population.grads))
+    params = _lib.EvacMlpPolicyGrads(*(t.data_ptr() for t in population.tensors[:13]))
+    grads = _lib.EvacMlpPolicyGrads(*(g.data_ptr() for g in population.grads[:13]))
     target_kl = getattr(cfg, "target_kl", None)
     lc, oc = _loss_config(cfg), opt.config()
-    head = [S, C.byref(pol), C.byref(params), C.byref(grads), C.byref(population.strides), C.byref(population.strides),
-            C.byref(opt.moment_strides), opt.header_stride_bytes, C.byref(lc), C.byref(oc), C.byref(opt.learners[0].state_struct()), *b_args,
+    rest = [opt.header_stride_bytes, C.byref(lc), C.byref(oc), C.byref(opt.learners[0].state_struct()), *b_args,
             B_l, M, n_epochs, _ptr(rows), _ptr(rpo_noise), u64(*(_u64(x) for x in seeds)), u64(*(_u64(x) for x in counters))]
     tail = [_ptr(stats), _ptr(workspace), _stream(dev)]
+    if deepsets:                              # (every struct of the 13 followed by the encoder's six's)
+        enc_params = _lib.EvacDeepSetsGrads(*(t.data_ptr() for t in population.tensors[13:]))
+        enc_grads = _lib.EvacDeepSetsGrads(*(g.data_ptr() for g in population.grads[13:]))
+        es = population.encoder_strides
+        rc = _lib.load().evac_deepsets_update_population(
+            S, C.byref(pol), C.byref(population.encoder_struct()), C.byref(params), C.byref(enc_params), C.byref(grads), C.byref(enc_grads),
+            C.byref(population.strides), C.byref(es), C.byref(population.strides), C.byref(es), C.byref(opt.moment_strides),
+            C.byref(opt.encoder_moment_strides), *rest, int(target_kl is not None), float(target_kl or 0.0), *tail)
+        _lib.check(rc)
+        return stats, opt.headers
+    head = [S, C.byref(pol), C.byref(params), C.byref(grads), C.byref(population.strides), C.byref(population.strides),
+            C.byref(opt.moment_strides), *rest]
     if cfgs is None:
         rc = _lib.load().evac_rpo_update_population(*head, int(target_kl is not None), float(target_kl or 0.0), *tail)
     else:
@@ -304,7 +404,9 @@ def rpo_update_population(population: PolicyPopulation, batch: Dict[str, torch.T
 
 class PopulationTrainer:
     """``RPOTrainer(optimizer="device", one_call=True)`` for every learner of ``population`` at once.  ``env``: a
-    ``NormalizedVectorEnv`` or ``BatchedEvacuationEnv`` of ``S x cfg.num_envs`` envs (learner s owns the s-th share); ``cfgs``: ONE
+    ``NormalizedVectorEnv`` or ``BatchedEvacuationEnv`` of ``S x cfg.num_envs`` envs (learner s owns the s-th share);
+    ``population``: a ``PolicyPopulation``, or a ``DeepSetsPopulation`` (learner s is then ``RPOTrainer(grad_fn=deepsets_kernel_grad,
+    optimizer="device", one_call=True)`` alone, under ONE configuration: differing ones are a ``ValueError``); ``cfgs``: ONE
     configuration for all, or a sequence of S that may differ in ``SWEEP_FIELDS`` (a differing ``STRUCTURAL_FIELDS`` entry is a
     ``ValueError``); ``seed`` unused -- learner s's permutations come from a generator seeded ``population.seeds[s]`` and
     its RPO perturbation from Philox keyed with the same seed.  With a sequence learner s anneals its own rate, its reward
@@ -313,11 +415,19 @@ class PopulationTrainer:
     transfer; returns a list of S logs with ``RPOTrainer.update()``'s keys, ``learning_rate`` the learner's own and ``config``
     its fields that differ from learner 0's."""
 
-    def __init__(self, env, population: PolicyPopulation, cfgs):
+    def __init__(self, env, population, cfgs):
         refuse_deepsets(population, "PopulationTrainer")       # (a network where the population goes)
+        self.deepsets = isinstance(population, DeepSetsPopulation)
         for net in getattr(population, "nets", ()):
-            refuse_deepsets(net, "PopulationTrainer")
+            (refuse_transformer if self.deepsets else refuse_deepsets)(net, "PopulationTrainer")
         S = population.num_learners
+        if self.deepsets and isinstance(cfgs, (list, tuple)):
+            if len(cfgs) != S:
+                raise ValueError(f"PopulationTrainer: {len(cfgs)} configurations for {S} learners")
+            if any(dataclasses.replace(c, seed=cfgs[0].seed) != cfgs[0] for c in cfgs):
+                raise ValueError("PopulationTrainer: sweeps of deep-sets learners are not built: a DeepSetsPopulation trains under "
+                                 "ONE configuration")
+            cfgs = cfgs[0]
         self.sweep = isinstance(cfgs, (list, tuple))
         if self.sweep:
             self.cfgs = list(cfgs)
@@ -395,12 +505,12 @@ class PopulationTrainer:
         steps = cfg.update_epochs * len(update_steps(B_l, cfg.minibatch_size, cfg.norm_adv))
         if self.stats_rows is None or self.stats_rows.shape[1] != steps:
             self.stats_rows = torch.zeros(S, steps, 8, dtype=torch.float32, device=self.device)
-        need = population_workspace_bytes(self.population.obs_dim, min(cfg.minibatch_size, B_l), S)
+        need = population_workspace_bytes(self.population.obs_dim, min(cfg.minibatch_size, B_l), S, deepsets=self.deepsets)
         if self.workspace is None or self.workspace.numel() < need:
             self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        stats, headers = rpo_update_population(self.population, batch, rows, self.cfgs if self.sweep else cfg, self.optimizer,
-                                               first_draw_counters=self.minibatch_steps, stats=self.stats_rows,
-                                               workspace=self.workspace)
+        update = deepsets_update_population if self.deepsets else rpo_update_population
+        stats, headers = update(self.population, batch, rows, self.cfgs if self.sweep else cfg, self.optimizer,
+                                first_draw_counters=self.minibatch_steps, stats=self.stats_rows, workspace=self.workspace)
         self.update_index += 1
         # the logged scalars of every learner, over its own columns (contiguous copies: the arrays RPOTrainer reduces), ONE transfer
         ret, val = self.returns.view(T, S, E_l), storage["values"].view(T, S, E_l)
@@ -463,8 +573,20 @@ class PopulationTrainer:
     def evaluate(self, n_episodes: int = 1, num_envs: Optional[int] = None, deterministic: bool = True) -> list:
         """``RPOTrainer.evaluate`` for every learner in ONE set of launches on the population evaluator, each with its own rows
         of the training env's observation statistics (frozen copies).  Returns S ``EvaluationResult``s, bit for bit those of
-        ``make_evaluator().evaluate(nets[s], ...)`` learner by learner."""
-        ev, S, E_l = self.make_population_evaluator(num_envs), self.num_learners, self.envs_per_learner
+        ``make_evaluator().evaluate(nets[s], ...)`` learner by learner.  A ``DeepSetsPopulation`` IS evaluated learner by learner
+        (``evac_policy_evaluate_deepsets`` on ``make_evaluator()``'s batch): the same results, S sets of launches."""
+        S, E_l = self.num_learners, self.envs_per_learner
+        if self.deepsets:                         # (no one-launch evaluation of deep-sets learners: one PolicyEvaluator, learner by learner)
+            ev, kw = self.make_evaluator(num_envs), {}
+            with torch.no_grad():
+                results = []
+                for s, net in enumerate(self.nets):
+                    if hasattr(self.env, "norm_state"):
+                        kw = {"norm_state": self.env.norm_state.view(S, E_l, -1)[s].clone(), "obs_clip": self.env.obs_clip,
+                              "epsilon": self.env.epsilon}
+                    results.append(ev.evaluate(net, n_episodes, deterministic=deterministic, **kw))
+                return results
+        ev = self.make_population_evaluator(num_envs)
         kw = {}
         if hasattr(self.env, "norm_state"):
             kw = {"norm_state": self.env.norm_state.view(S, E_l, -1).clone(), "obs_clip": self.env.obs_clip,

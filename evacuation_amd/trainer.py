@@ -318,7 +318,7 @@ class DeviceAdam:
     def __init__(self, net, lr: float = 3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm: float = 0.5,
                  *, storage=None):
         """``storage`` = (header, exp_avg, exp_avg_sq): the state lives in the caller's tensors (``PopulationAdam``'s rows: 13
-        tensors, so a ``ValueError`` for a network with a set encoder)."""
+        tensors, or all 19 for a network with a set encoder -- 13 for such a network is a ``ValueError``)."""
         refuse_transformer(net, "DeviceAdam")                                   # (its own optimiser is TransformerAdam)
         self._setup(net, lr, betas, eps, max_grad_norm, storage)
 
@@ -326,9 +326,9 @@ class DeviceAdam:
         """The constructor's body for the network's own kind (``encoder_kind``): the 13 tensors' state, then the encoder's."""
         self.kind = encoder_kind(net)
         self.deepsets = is_deepsets(net) and not is_transformer(net)
-        if self.deepsets and storage is not None:
-            raise ValueError("DeviceAdam: `storage` holds the 13 tensors of a population's row; a network with a set encoder "
-                             "(`deep_sets`) has 19")
+        if self.deepsets and storage is not None and (len(storage[1]) != 19 or len(storage[2]) != 19):
+            raise ValueError("DeviceAdam: `storage` holds the 13 tensors of a linear population's row; a network with a set encoder "
+                             "(`deep_sets`) has 19 (a DeepSetsPopulation's row)")
         group = {"lr": float(lr), "betas": (float(betas[0]), float(betas[1])), "eps": float(eps), "max_grad_norm": float(max_grad_norm)}
         self._check_group(group)
         self.net = net

@@ -618,13 +618,23 @@ class BatchedEvacuationEnv:
         (``evac_policy_rollout_population``): learner s acts in envs ``[s E_l, (s + 1) E_l)`` of this env, ``E_l = num_envs / S``.
         Arguments and storage are ``policy_rollout``'s, over the whole batch; learner s's columns hold, bit for bit, what
         ``policy_rollout(population.nets[s], ...)`` writes on an env of ``E_l`` envs with the same seed, ``env_id_offset`` further
-        by ``s E_l`` and the same start state.  ``gammas``: the learners' training gammas (a sequence of S).  Gamma enters
+        by ``s E_l`` and the same start state.  A ``DeepSetsPopulation`` runs every learner's set encoder in the same launch
+        (``evac_policy_rollout_population_deepsets``) and takes no ``gammas``.  ``gammas``: the learners' training gammas (a
+        sequence of S).  Gamma enters
         collection through the reward normaliser alone, so on this raw env ``gammas`` is accepted (and checked) and has no effect;
         ``NormalizedVectorEnv.policy_rollout_population`` runs learner s's chain with ``gammas[s]``."""
         if self.num_envs % population.num_learners:
             raise ValueError(f"policy_rollout_population: {self.num_envs} envs are not {population.num_learners} learners' equal shares")
+        if gammas is not None and self._is_set_population(population):
+            raise ValueError("policy_rollout_population: sweeps of deep-sets learners are not built (`gammas` is the sweep's)")
         hypers = None if gammas is None else _lib.learner_hypers(population.num_learners, gamma=[float(g) for g in gammas])
         return self._policy_rollout(population.nets[0], population, n_steps, next_obs, next_done, out, _norm, hypers)
+
+    @staticmethod
+    def _is_set_population(population) -> bool:
+        """A ``population.DeepSetsPopulation`` (the one predicate of the population's kind, as ``population.py`` has it)."""
+        from .population import DeepSetsPopulation
+        return isinstance(population, DeepSetsPopulation)
 
     def _one_wave(self, what: str) -> None:
         from .policy import MAX_PEDESTRIANS
@@ -651,7 +661,8 @@ class BatchedEvacuationEnv:
             raise ValueError("policy_rollout: n_steps must be >= 1")
         binder = self._binder()
         pol = binder(net)
-        if population is not None:
+        set_population = self._is_set_population(population)
+        if population is not None and not set_population:
             refuse_deepsets(net, "policy_rollout_population")
         enc = binder.bind_encoder(net)        # an encoder in front of the actor-critic: evac_policy_rollout_deepsets / _transformer
         next_obs = self._check_tensor(next_obs, (E, D), torch.float32, "next_obs")
@@ -668,7 +679,10 @@ class BatchedEvacuationEnv:
         args = [_ptr(next_obs), _ptr(next_done), _ptr(out["obs"]), _ptr(out["actions"]), _ptr(out["logprobs"]), _ptr(out["values"]),
                 _ptr(out["rewards"]), _ptr(out["dones"]), _ptr(out["next_value"]), _ptr(out["episode_stats"]), _ptr(state), gamma,
                 obs_clip, reward_clip, eps, self._stream()]
-        if enc is not None:
+        if set_population:                    # (learner 0's 19 tensors: the base the strides count from)
+            rc = self.lib.evac_policy_rollout_population_deepsets(self._h, population.num_learners, C.byref(pol), C.byref(population.strides),
+                                                                  C.byref(enc[1]), C.byref(population.encoder_strides), T, *args)
+        elif enc is not None:
             rc = getattr(self.lib, "evac_policy_rollout" + enc[0])(self._h, T, C.byref(pol), *args[:-1], C.byref(enc[1]), args[-1])
         elif population is None:
             rc = self.lib.evac_policy_rollout(self._h, T, C.byref(pol), *args)

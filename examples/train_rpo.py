@@ -18,8 +18,10 @@ rel + ohe Box observation: collection and evaluation on the device (``evac_polic
 ``evac_policy_evaluate_deepsets``), the gradient of its 19 tensors by torch autograd (``trainer.autograd_minibatch_grad``) or,
 with ``--gradient device``, by ``evac_deepsets_minibatch_grad`` (``trainer.deepsets_kernel_grad``: six launches), and torch's
 Adam -- or, with ``--gradient device --optimizer device``, the library's clip + Adam over all 19 tensors, the whole update in one
-host call (``evac_deepsets_update``: seven launches per step).  Not with ``--seeds``, ``--sweep`` or ``--compare``, nor with
-``--optimizer device`` under the autograd gradient: those kernels are the linear network's.
+host call (``evac_deepsets_update``: seven launches per step).  With ``--seeds`` the learners train as a population of such
+networks (``population.DeepSetsPopulation``, ``evac_deepsets_update_population``: the device gradient and optimiser, seven
+launches per step for all learners).  Not with ``--sweep`` (sweeps of deep-sets learners are not built) or ``--compare``, nor
+with ``--optimizer device`` under the autograd gradient: those kernels are the linear network's.
 
 ``--network transformer`` trains the reference's attention-encoder network (``policy.TransformerActorCritic``,
 RPOTransformerEmbedding; ``--blocks`` 1 or 2, ``--use-resid``) on the rel + ohe Box observation, at most 62 pedestrians:
@@ -124,10 +126,15 @@ def parse_sweep(specs):
 
 
 def make_population_trainer(args, seeds, grid=None):
-    from evacuation_amd.population import PolicyPopulation, PopulationTrainer, sweep_configs
+    from evacuation_amd.population import DeepSetsPopulation, PolicyPopulation, PopulationTrainer, sweep_configs
     cfg = RPOTrainingConfig(num_envs=args.envs, num_steps=args.steps, total_timesteps=args.envs * args.steps * max(args.updates, 1),
                             num_minibatches=args.minibatches, update_epochs=args.epochs)
     cfgs = cfg
+    if getattr(args, "network", "linear") == "deep_sets":        # a population of set-encoder networks (no sweep: main refuses it)
+        env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=args.pedestrians, is_new_exiting_reward=True),
+                                          ea.EnvWrappersConfig(positions="rel", statuses="ohe", type="Box"),
+                                          num_envs=args.envs * len(seeds), gamma=cfg.gamma, seed=1)
+        return PopulationTrainer(env, DeepSetsPopulation(env.obs_dim, args.pedestrians, seeds, DEV), cfgs)
     if grid is not None:                                         # one learner per (setting, seed)
         pairs = sweep_configs(cfg, grid, seeds)
         seeds, cfgs = [s for s, _ in pairs], [c for _, c in pairs]
@@ -299,9 +306,11 @@ def main():
     if args.gradient == "device" and args.network == "linear":
         raise SystemExit("--gradient device goes with --network deep_sets or transformer (the linear network's gradient is the device's "
                          "anyway)")
-    if args.network == "deep_sets" and (args.compare or args.seeds or args.sweep or
-                                        (args.optimizer == "device" and args.gradient != "device")):
-        raise SystemExit("--network deep_sets: the gradient and optimiser kernels (--optimizer device, --seeds, --sweep, --compare) are "
+    if args.network == "deep_sets" and args.sweep:
+        raise SystemExit("--network deep_sets --sweep: sweeps of deep-sets learners are not built (--seeds trains a population of them "
+                         "under one configuration)")
+    if args.network == "deep_sets" and (args.compare or (args.optimizer == "device" and args.gradient != "device" and not args.seeds)):
+        raise SystemExit("--network deep_sets: the gradient and optimiser kernels (--optimizer device, --compare) are "
                          "the linear network's; its gradient is autograd's or --gradient device, and --optimizer device goes with "
                          "--gradient device")
     if args.network == "transformer" and (args.compare or args.seeds or args.sweep or

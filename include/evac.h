@@ -1011,6 +1011,70 @@ int evac_rpo_update_sweep(int32_t n_learners, const evac_mlp_policy_t* policy, c
                           const uint64_t* first_draw_counters, const evac_learner_hyper_t* hypers, float* stats_out,
                           void* workspace, void* stream);
 
+/* ---- Populations of deep-sets leaders: S learners of ONE configuration, each with its own set encoder ----
+ * The two population entries above for the network of evac_deepsets_t: 19 stacked tensors per learner.  evac_deepsets_strides_t
+ * is evac_mlp_policy_strides_t's sibling for the encoder's six: floats from learner s to learner s + 1, per tensor.  Sweeps
+ * (per-learner hyperparameters) and a one-launch evaluation of such learners do not exist; evac_policy_evaluate_deepsets takes a
+ * learner's tensors as they are. */
+typedef struct evac_deepsets_strides {     /* floats from learner s to learner s + 1, per tensor of evac_deepsets_t */
+    int64_t phi_w1, phi_b1, phi_w2, phi_b2, rho_w, rho_b;
+} evac_deepsets_strides_t;
+/* evac_policy_rollout_population_deepsets: evac_policy_rollout_population with the set encoder in front of every learner's
+ * actor-critic.  `policy` / `encoder` hold learner 0's tensors, learner s's are s x strides / enc_strides further; storage,
+ * norm_state and env state as evac_policy_rollout_population's.  EQUIVALENCE: the call writes, bit for bit, what S calls of
+ * evac_policy_rollout_deepsets write -- call s with learner s's 19 tensors on a handle of E_l envs with the same seed,
+ * env_id_offset = this handle's + s E_l and learner s's share of the state -- into the learner's columns [s E_l, (s + 1) E_l) of
+ * every array.  ONE launch of ceil(E_l / 16) CU-wide workgroups per learner; a workgroup never mixes learners.
+ * Refused as evac_policy_rollout_deepsets and as evac_policy_rollout_population (EVAC_ERR_UNSUPPORTED above 64 pedestrians;
+ * EVAC_ERR_INVALID_ARGUMENT otherwise), and a NULL enc_strides, and with n_learners > 1 an encoder stride smaller than its
+ * tensor (0 included) or a rho_w stride that is no multiple of 4 floats (its rows are read as 16-byte vectors). */
+int evac_policy_rollout_population_deepsets(evac_handle_t h, int32_t n_learners, const evac_mlp_policy_t* policy,
+                                            const evac_mlp_policy_strides_t* strides, const evac_deepsets_t* encoder,
+                                            const evac_deepsets_strides_t* enc_strides, int32_t n_steps,
+                                            float* next_obs, float* next_done,
+                                            float* obs_out, float* actions_out, float* logprob_out,
+                                            float* value_out, float* reward_out, float* done_out,
+                                            float* next_value_out, evac_episode_stats_t* final_stats_or_null,
+                                            double* norm_state_or_null, float gamma, float obs_clip, float reward_clip,
+                                            float epsilon, void* stream);
+/* evac_deepsets_update_population: evac_deepsets_update for n_learners learners in one set of launches, with
+ * evac_rpo_update_population's argument list and contract: ONE common batch, perms [S][n_epochs][learner_batch_size] whose
+ * values are rows of the common arrays, rpo_noise_or_null [S][steps][M][2], stats_out [S][steps][8], HOST seeds [S] and
+ * first_draw_counters [S], the 64-byte headers header_stride_bytes apart.  It adds the encoder (learner 0's), its parameters,
+ * gradients and moments (evac_deepsets_adam_state_t) and their strides: enc_param_strides for encoder and enc_params,
+ * enc_grad_strides, enc_moment_strides for enc_exp_avg and enc_exp_avg_sq.
+ *   workspace: evac_deepsets_population_workspace_bytes(obs_dim, M, S) bytes, 16-byte aligned: S slices of
+ *   evac_deepsets_workspace_bytes(obs_dim, M) (a multiple of 256 bytes, every part of a slice a multiple of 256 bytes from the
+ *   base: no two learners' ticket words or partials share a 128-byte line, whatever the base's alignment), then the learners'
+ *   encoded observations, gathered columns and index lists as one common batch [S][M][..] that the actor-critic's kernels read with learner s's index list s M + m.
+ * EQUIVALENCE: learner s's 19 parameters, 2 x 19 moments, 19 gradients, header and statistics rows are, bit for bit, those of
+ * evac_deepsets_update called with learner s's tensors, perms[s], seeds[s], first_draw_counters[s] and the same common batch.
+ * A learner whose stop flag is set (target_kl) returns at the top of every later kernel, the encoder's three included, touching
+ * nothing, while the others go on.  No learner reads another's memory and nothing waits across learners: every ticket is an
+ * integer atomicAdd whose result is compared, and no kernel spins.  Launches per minibatch step are those of one learner: seven
+ * (six without norm_adv: the encoder forwards, the advantage statistics, the gradient, its finish, the encoder backwards, its
+ * finish, the optimiser), plus one launch per call that clears every learner's stop / steps_run / epochs_run.  No host
+ * synchronisation, capturable (seeds and counters are frozen by a capture).
+ * EVAC_ERR_INVALID_ARGUMENT, decided on the host before anything touches a device: as evac_deepsets_update and as
+ * evac_rpo_update_population, and a NULL encoder strides struct, and with n_learners > 1 an encoder stride smaller than its
+ * tensor (0 included) or a rho_w stride that is no multiple of 4 floats.
+ * evac_deepsets_population_workspace_bytes: the workspace's size, or EVAC_ERR_INVALID_ARGUMENT where
+ * evac_deepsets_workspace_bytes gives it or n_learners is outside 1..EVAC_MAX_LEARNERS. */
+int64_t evac_deepsets_population_workspace_bytes(int32_t obs_dim, int64_t n_minibatch, int32_t n_learners);
+int evac_deepsets_update_population(int32_t n_learners, const evac_mlp_policy_t* policy, const evac_deepsets_t* encoder,
+                                    const evac_mlp_policy_grads_t* params, const evac_deepsets_grads_t* enc_params,
+                                    const evac_mlp_policy_grads_t* grads, const evac_deepsets_grads_t* enc_grads,
+                                    const evac_mlp_policy_strides_t* param_strides, const evac_deepsets_strides_t* enc_param_strides,
+                                    const evac_mlp_policy_strides_t* grad_strides, const evac_deepsets_strides_t* enc_grad_strides,
+                                    const evac_mlp_policy_strides_t* moment_strides, const evac_deepsets_strides_t* enc_moment_strides,
+                                    int64_t header_stride_bytes, const evac_rpo_loss_config_t* loss_cfg,
+                                    const evac_adam_config_t* adam_cfg, const evac_deepsets_adam_state_t* state, int64_t batch_size,
+                                    const float* b_obs, const float* b_actions, const float* b_logprobs, const float* b_advantages,
+                                    const float* b_returns, const float* b_values, int64_t learner_batch_size, int64_t n_minibatch,
+                                    int32_t n_epochs, const int64_t* perms, const float* rpo_noise_or_null, const uint64_t* seeds,
+                                    const uint64_t* first_draw_counters, int32_t use_target_kl, double target_kl, float* stats_out,
+                                    void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

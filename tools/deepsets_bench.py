@@ -5,6 +5,7 @@ with torch's optimiser against the device's (evac_deepsets_minibatch_step, evac_
 
     python tools/deepsets_bench.py --part a|b|c|c-eager|grad-autograd|grad-device|step-device|update-torch|update-step|update-one-call
                                    [--envs 4096] [--steps 128] [--minibatch 16384] [--epochs 10] [--reps 7]
+    python tools/deepsets_bench.py --part update-population --learners S [--envs 3] [--steps 2048] [--minibatch 192] [--epochs 10]
 
 N = 60, the rel + ohe Box observation (D = 372), the trainer's normalisation chain, E envs, T steps per call; hipEvent times of
 whole calls after two warm-up calls, median and range of ``--reps`` calls, one JSON line:
@@ -23,6 +24,11 @@ whole calls after two warm-up calls, median and range of ``--reps`` calls, one J
            ``RPOTrainer(grad_fn=deepsets_kernel_grad)`` does; events around the whole loop after one warm-up update
   update-step    the same with one ``deepsets_minibatch_step`` per minibatch (``DeviceAdam``)
   update-one-call  the same as one ``deepsets_update``
+  update-population  one whole ``update()`` -- collection, advantages, permutations, every epoch's minibatch steps -- of
+           ``PopulationTrainer(env, DeepSetsPopulation(S learners), cfg)`` (``--envs`` envs PER LEARNER) against the loop of S lone
+           ``RPOTrainer(grad_fn=deepsets_kernel_grad, optimizer="device", one_call=True)`` updates on twin handles: wall-clock
+           times of whole updates between synchronisations (an update ends with its own host transfer) after two warm-up updates
+           of each form, the two forms alternated inside every repetition, median and range of ``--reps`` repetitions
 One part per process, so that a job script can give each its own time limit."""
 import argparse
 import json
@@ -111,6 +117,58 @@ def update_part(args):
                       "finite": bool(all(torch.isfinite(p).all() for p in params))}))
 
 
+def population_part(args):
+    """One population update against the per-learner loop, collection included; see the module's docstring."""
+    import dataclasses
+    import time
+
+    from evacuation_amd.population import DeepSetsPopulation, PopulationTrainer
+    from evacuation_amd.trainer import RPOTrainer, RPOTrainingConfig, deepsets_kernel_grad, update_steps
+    S, E_l, T = args.learners, args.envs, args.steps
+    cfg = RPOTrainingConfig(num_envs=E_l, num_steps=T, total_timesteps=E_l * T * 1000, num_minibatches=max(1, E_l * T // args.minibatch),
+                            update_epochs=args.epochs)
+    env_cfg = ea.EnvConfig(number_of_pedestrians=N_PED)
+    wrap = ea.EnvWrappersConfig(positions="rel", statuses="ohe", type="Box")
+    seeds = list(range(1, S + 1))
+    env = ea.NormalizedVectorEnv.make(env_cfg, wrap, num_envs=S * E_l, gamma=cfg.gamma, seed=1)
+    ptr = PopulationTrainer(env, DeepSetsPopulation(env.obs_dim, N_PED, seeds, DEV), cfg)
+    lone = []
+    for s, seed in enumerate(seeds):
+        e = ea.NormalizedVectorEnv.make(env_cfg, wrap, num_envs=E_l, gamma=cfg.gamma, seed=1, env_id_offset=s * E_l)
+        torch.manual_seed(seed)
+        lone.append(RPOTrainer(e, DeepSetsActorCritic(e.obs_dim, N_PED).to(DEV), dataclasses.replace(cfg, seed=seed),
+                               grad_fn=deepsets_kernel_grad, optimizer="device", one_call=True))
+
+    def wall_ms(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def loop():
+        for tr in lone:
+            tr.update()
+    for _ in range(2):
+        ptr.update()
+        loop()
+    pop_ms, loop_ms = [], []
+    for _ in range(max(3, args.reps)):
+        pop_ms.append(wall_ms(ptr.update))
+        loop_ms.append(wall_ms(loop))
+    pm, lm = statistics.median(pop_ms), statistics.median(loop_ms)
+    steps = cfg.update_epochs * len(update_steps(cfg.batch_size, cfg.minibatch_size, cfg.norm_adv))
+    finite = all(bool(torch.isfinite(t).all()) for t in ptr.population.tensors)
+    print(json.dumps({"part": args.part, "learners": S, "envs_per_learner": E_l, "steps": T, "minibatch": cfg.minibatch_size,
+                      "epochs": cfg.update_epochs, "minibatch_steps": steps, "obs_dim": env.obs_dim,
+                      "population_ms_median": round(pm, 3), "population_ms_min": round(min(pop_ms), 3), "population_ms_max": round(max(pop_ms), 3),
+                      "loop_ms_median": round(lm, 3), "loop_ms_min": round(min(loop_ms), 3), "loop_ms_max": round(max(loop_ms), 3),
+                      "loop_over_population": round(lm / pm, 3), "updates": len(pop_ms), "finite": finite}))
+    for tr in lone:
+        tr.env.close()
+    env.close()
+
+
 def grad_part(args):
     """One minibatch gradient of all 19 tensors (step-device: and the optimiser's step): whole calls between two events after two
     warm-up calls."""
@@ -148,13 +206,16 @@ def grad_part(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", required=True, choices=["a", "b", "c", "c-eager", "grad-autograd", "grad-device", "step-device", "update-torch",
-                                                     "update-step", "update-one-call"])
+                                                     "update-step", "update-one-call", "update-population"])
+    ap.add_argument("--learners", type=int, default=4, help="update-population: the learners of the population")
     ap.add_argument("--minibatch", type=int, default=16384)
     ap.add_argument("--epochs", type=int, default=10, help="update-*: the epochs of one update")
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--reps", type=int, default=7)
     args = ap.parse_args()
+    if args.part == "update-population":
+        return population_part(args)
     if args.part.startswith("update-"):
         return update_part(args)
     if args.part.startswith("grad-") or args.part == "step-device":
