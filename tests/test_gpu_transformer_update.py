@@ -25,12 +25,11 @@ import pytest
 from tests import transformer_grad_cases as TC
 from tests.optimizer_ref import AdamRef
 from tests.trainer_cases import DEV, loss_cfg, same_bits
+from tests.workspace_guard import CANARY, Guarded
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(1, 2, 1, False), (10, 3, 2, False), (62, 6, 2, True)]
-CANARY = -12345.0
-GUARD = 64                                       # floats between two tensors of a guarded buffer
 
 
 @pytest.fixture(scope="module")
@@ -84,32 +83,6 @@ def assert_same_state(a, b, what):
 
 
 # ------------------------------------------------------------------------------------------------ evac_transformer_adam_step
-class Guarded:
-    """Copies of ``arrays`` in one device buffer of canaries, ``GUARD`` floats in front of the first and behind every one."""
-
-    def __init__(self, arrays):
-        import torch
-        sizes = [int(a.size) for a in arrays]
-        self.buf = torch.full((GUARD + sum(n + GUARD for n in sizes),), CANARY, dtype=torch.float32, device=DEV)
-        self.mask = torch.ones_like(self.buf, dtype=torch.bool)
-        self.views, at = [], GUARD
-        for a, n in zip(arrays, sizes):
-            v = self.buf[at:at + n]
-            v.copy_(torch.from_numpy(np.ascontiguousarray(a).reshape(-1)))
-            self.mask[at:at + n] = False
-            self.views.append(v)
-            at += n + GUARD
-
-    def ptrs(self):
-        return [v.data_ptr() for v in self.views]
-
-    def canaries_intact(self):
-        return bool((self.buf[self.mask] == CANARY).all())
-
-    def host(self, shapes):
-        return [v.cpu().numpy().reshape(s) for v, s in zip(self.views, shapes)]
-
-
 @pytest.mark.parametrize("N,dm,blocks,resid", SHAPES)
 def test_adam_step_is_bit_equal_to_the_yardstick(ea, N, dm, blocks, resid):
     """Three consecutive steps of the C entry on random parameters and gradients, the sum of squares above the clip threshold,
