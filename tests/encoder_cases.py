@@ -5,7 +5,7 @@ tests.  Each file keeps its cases, its ``make_net``, its tests and their bounds.
 import numpy as np
 import pytest
 
-from tests.test_gpu_policy_rollout import OFFSET, SEED, base, snapshot, start
+from tests.test_gpu_policy_rollout import OFFSET, SEED, base, i32, raw, replay_env_side, snapshot, start
 
 
 @pytest.fixture(scope="module")
@@ -35,16 +35,18 @@ def _frozen(env, E):
 
 class EncoderCases:
     """``cases``: name -> (EnvConfig kwargs, EnvWrappersConfig kwargs, normalised chain, KernelOptions overrides, ...);
-    ``make_net(case)``: the file's network of a case; ``t_steps``: the length of the shared rollout."""
+    ``make_net(case)``: the file's network of a case; ``t_steps``: the length of the shared rollout; ``cfg_over``: fields of
+    every case's EnvConfig to replace (tests/test_gpu_policy_long.py: max_timesteps)."""
 
-    def __init__(self, cases, make_net, t_steps):
-        self.cases, self.make_net, self.t_steps = cases, make_net, t_steps
+    def __init__(self, cases, make_net, t_steps, **cfg_over):
+        self.cases, self.make_net, self.t_steps, self.cfg_over = cases, make_net, t_steps, cfg_over
         self._runs = {}
 
     def make_env(self, ea, case, E, raw_env=False, **options):
         from evacuation_amd.options import KernelOptions
         cfg_kw, wrap_kw, norm, opts = self.cases[case][:4]
         opts = {**opts, **options}
+        cfg_kw = {**cfg_kw, **self.cfg_over}
         env = ea.BatchedEvacuationEnv(ea.EnvConfig(**cfg_kw), ea.EnvWrappersConfig(**wrap_kw), num_envs=E, seed=SEED, env_id_offset=OFFSET,
                                       options=KernelOptions().replace(**opts) if opts else None)
         return ea.NormalizedVectorEnv(env) if norm and not raw_env else env
@@ -68,6 +70,30 @@ class EncoderCases:
             env.close()
         return self._runs[key]
 
+    def policy_noise(self, total0, T):
+        """The restated Philox draws of steps 0..T-1 of envs whose step counts start at ``total0``: float64 [T, E, 2]."""
+        from tests import policy_ref as R
+        gid = (OFFSET + np.arange(total0.shape[0])).astype(np.uint32)
+        steps = np.arange(T, dtype=np.int64)
+        return R.policy_normal(SEED, gid[None, :], (total0[None, :] + steps[:, None]).astype(np.uint32))
+
+    def env_side_bit_for_bit(self, ea, case, E):
+        """Test 2 of the two files: a twin handle (subwave = 0) replays the shared rollout's recorded actions through step()."""
+        import torch
+        net, ro, obs0, _, fin, ns0 = self.rollout_of(ea, case, E)
+        twin = self.make_env(ea, case, E, subwave=0)
+        obs_b, _ = start(twin)
+        assert i32(obs0).equal(i32(obs_b))
+        if ns0 is not None:
+            twin.norm_state.copy_(ns0)
+        n_done = replay_env_side(ea, twin, ro, obs0, self.t_steps, case)
+        assert n_done >= E // 5                       # autoresets inside the call
+        torch.cuda.synchronize()
+        end = snapshot(twin)
+        for k in fin:                                 # ped, status, agent, clock, acc (and norm_state)
+            assert raw(fin[k]).equal(raw(end[k])), (case, k)
+        twin.close()
+
     def run(self, ea, case, E, T_split, net):
         env = self.make_env(ea, case, E)
         obs, done = start(env)
@@ -75,6 +101,38 @@ class EncoderCases:
         fin = snapshot(env)
         env.close()
         return outs, fin
+
+    def evaluation_is_the_rollout(self, ea, case, mode, E=48, T=40):
+        """Test 4a of the two files: policy_evaluate(max_steps = T) against policy_rollout(T) on a twin handle -- in mean mode
+        with the twin's actor_logstd at -inf (expf gives 0 exactly).  Returns the rollout's [T, E] episode ends."""
+        import copy
+
+        import torch
+        a, b = self.twins(ea, case, E)
+        net = self.make_net(case)
+        twin_net = net
+        if mode == "mean":
+            twin_net = copy.deepcopy(net)
+            with torch.no_grad():
+                twin_net.actor_logstd.fill_(float("-inf"))
+        obs = b.observe().clone()
+        done = torch.zeros(E, dtype=torch.float32, device=b.device)
+        ro = b.policy_rollout(twin_net, T, obs, done)
+        progress, rec = a.policy_evaluate(net, T, T, deterministic=(mode == "mean"))
+        torch.cuda.synchronize()
+        for k in ("ped", "status", "agent", "clock", "acc"):
+            assert raw(getattr(a, k)).equal(raw(getattr(b, k))), (case, mode, k)
+        assert progress[:, 1].eq(T).all() and progress[:, 2:].eq(0).all()
+        ended = torch.cat([ro["dones"][1:].bool(), ro["next_done"].bool()[None]], dim=0)
+        assert int(ended.sum()) >= E // 5
+        assert progress[:, 0].equal(ended.sum(0).to(torch.int32))
+        for e in range(E):
+            rows = ro["episode_stats"][ended[:, e], e]
+            n = rows.shape[0]
+            assert i32(rec[:n, e]).equal(i32(rows)), (case, mode, e)
+            assert i32(rec[n:, e]).eq(0).all(), (case, mode, e)
+        a.close(); b.close()
+        return ended.cpu().numpy()
 
     def twins(self, ea, case, E):
         a, b = self.make_env(ea, case, E, raw_env=True, subwave=0), self.make_env(ea, case, E, raw_env=True, subwave=0)

@@ -48,9 +48,9 @@ def ea():
     return evacuation_amd
 
 
-def make_env(ea, case, E, offset):
+def make_env(ea, case, E, offset, **cfg_over):
     cfg_kw, wrap_kw, norm = CASES[case]
-    env = ea.BatchedEvacuationEnv(ea.EnvConfig(**cfg_kw), ea.EnvWrappersConfig(**wrap_kw), num_envs=E, seed=SEED, env_id_offset=offset)
+    env = ea.BatchedEvacuationEnv(ea.EnvConfig(**{**cfg_kw, **cfg_over}), ea.EnvWrappersConfig(**wrap_kw), num_envs=E, seed=SEED, env_id_offset=offset)
     return ea.NormalizedVectorEnv(env) if norm else env
 
 
@@ -76,14 +76,12 @@ def all_tensors(net):
 
 
 # ------------------------------------------------------------------------------------------------ 1. collection
-@pytest.mark.parametrize("case,S,E_l", [(c, S, E_l) for c in ("n60_rel_ohe_box_norm_clip", "n10_abs_cat_box_raw")
-                                         for S, E_l in ((3, 3), (2, 40), (1, 17))] + [("n64_rel_ohe_box_norm_clip", 2, 5)])
-def test_collection_equals_standalone_rollouts(ea, case, S, E_l):
-    """(3, 3): thirteen of sixteen waves leave; (2, 40): three workgroups per learner, the last part-filled; (1, 17)."""
+def collection_equals_standalone_rollouts(ea, case, S, E_l, T=30, **cfg_over):
+    """Learner s's storage, norm_state, records and final state are those of policy_rollout(nets[s]) alone.  Returns the
+    population call's storage."""
     import torch
     from evacuation_amd.population import DeepSetsPopulation
-    T = 30
-    pop_env = make_env(ea, case, S * E_l, OFFSET)
+    pop_env = make_env(ea, case, S * E_l, OFFSET, **cfg_over)
     b = base(pop_env)
     pop = visible(DeepSetsPopulation(b.obs_dim, b.n_ped, [11 + 7 * s for s in range(S)], DEV))
     obs, done, now = start_population(pop_env)
@@ -97,7 +95,7 @@ def test_collection_equals_standalone_rollouts(ea, case, S, E_l):
     fin = snapshot(pop_env)
     for s in range(S):
         cols = slice(s * E_l, (s + 1) * E_l)
-        env = make_env(ea, case, E_l, OFFSET + s * E_l)
+        env = make_env(ea, case, E_l, OFFSET + s * E_l, **cfg_over)
         o, _ = env.reset()
         assert i32(o).equal(i32(obs0[cols])), (case, s, "the reset observation")       # the same start state
         base(env).set_state(now=now[cols].clone())
@@ -120,6 +118,14 @@ def test_collection_equals_standalone_rollouts(ea, case, S, E_l):
     if S > 1:                                                        # the learners did act differently
         assert not i32(ro["actions"][:, :E_l]).equal(i32(ro["actions"][:, E_l:2 * E_l]))
     pop_env.close()
+    return ro
+
+
+@pytest.mark.parametrize("case,S,E_l", [(c, S, E_l) for c in ("n60_rel_ohe_box_norm_clip", "n10_abs_cat_box_raw")
+                                         for S, E_l in ((3, 3), (2, 40), (1, 17))] + [("n64_rel_ohe_box_norm_clip", 2, 5)])
+def test_collection_equals_standalone_rollouts(ea, case, S, E_l):
+    """(3, 3): thirteen of sixteen waves leave; (2, 40): three workgroups per learner, the last part-filled; (1, 17)."""
+    collection_equals_standalone_rollouts(ea, case, S, E_l)
 
 
 # ------------------------------------------------------------------------------------------------ 2. update

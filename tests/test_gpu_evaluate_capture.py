@@ -56,17 +56,18 @@ def raw(t):
     return t.contiguous().view(-1).view(torch.uint8)
 
 
-def make_env(ea, kind):
+def make_env(ea, kind, max_t=MAX_T):
     """A raw handle of the kind, reset, every fifth env one step before truncation and its neighbour two: every handle of a kind
-    starts from the same state.  (One-wave step kernels for the plain rollout too, as the evaluation's.)"""
+    starts from the same state.  (One-wave step kernels for the plain rollout too, as the evaluation's.)  ``max_t``, ``episodes``
+    of the helpers below: tests/test_gpu_policy_long.py runs them with longer episodes."""
     from evacuation_amd.options import KernelOptions
     _, N, cfg_kw, wrap_kw = KINDS[kind]
-    env = ea.BatchedEvacuationEnv(ea.EnvConfig(number_of_pedestrians=N, max_timesteps=MAX_T, **cfg_kw), ea.EnvWrappersConfig(**wrap_kw),
+    env = ea.BatchedEvacuationEnv(ea.EnvConfig(number_of_pedestrians=N, max_timesteps=max_t, **cfg_kw), ea.EnvWrappersConfig(**wrap_kw),
                                   num_envs=E, seed=SEED, env_id_offset=OFFSET, options=KernelOptions().replace(subwave=0))
     env.reset()
     now = env.get_state()["now"].clone()
-    now[::5] = MAX_T - 1
-    now[1::5] = MAX_T - 2
+    now[::5] = max_t - 1
+    now[1::5] = max_t - 2
     env.set_state(now=now)
     return env
 
@@ -130,23 +131,23 @@ def agent_of(ea, kind, mode):
     return make_net(ea, kind, sigma_zero=(mode == "sample0")), {"deterministic": mode == "mean"}
 
 
-def evaluate(ea, kind, mode, *, capture=True, norm=False, max_steps=100000, episodes=EPISODES, buffers=None):
+def evaluate(ea, kind, mode, *, capture=True, norm=False, max_steps=100000, episodes=EPISODES, buffers=None, max_t=MAX_T):
     """One evaluation of a fresh handle of the kind until every env has finished ``episodes`` episodes.  ``mode``: "mean",
     "sample", "sample0" (sample mode of the network with sigma = 0); ignored by the scripted agent."""
     import torch
-    env = make_env(ea, kind)
+    env = make_env(ea, kind, max_t)
     agent, kw = agent_of(ea, kind, mode)
     if norm:
         kw["_norm"] = frozen_statistics(env)
     start = {k: v.clone() for k, v in env.get_state().items()}
     if capture:
-        kw["capture"] = buffers if buffers is not None else nan_buffers(env, episodes=episodes)
+        kw["capture"] = buffers if buffers is not None else nan_buffers(env, rows=episodes * max_t, episodes=episodes)
     progress = out = None
     calls = 0
     while progress is None or int(progress[:, 0].min()) < episodes:
         progress, out = env.policy_evaluate(agent, episodes, max_steps, progress, out, **kw)
         calls += 1
-        assert calls <= FRAMES + 1
+        assert calls <= episodes * max_t + 1
     torch.cuda.synchronize()
     run = types.SimpleNamespace(progress=progress, records=out, state={k: getattr(env, k).clone() for k in STATE}, start=start,
                                 final=env.get_state(), calls=calls, n_ped=env.n_ped, **(kw.get("capture") or {}))
@@ -157,13 +158,13 @@ def evaluate(ea, kind, mode, *, capture=True, norm=False, max_steps=100000, epis
 _runs = {}
 
 
-def recorded(ea, kind, mode, norm=False):
-    """The one long recorded evaluation per (kind, mode, norm), shared by the tests and left unchanged."""
-    key = (kind, "" if KINDS[kind][0] is None else mode, norm)
+def recorded(ea, kind, mode, norm=False, episodes=EPISODES, max_t=MAX_T):
+    """The one long recorded evaluation per (kind, mode, norm, episodes, max_t), shared by the tests and left unchanged."""
+    key = (kind, "" if KINDS[kind][0] is None else mode, norm, episodes, max_t)
     if key not in _runs:
-        _runs[key] = evaluate(ea, kind, mode, norm=norm)
+        _runs[key] = evaluate(ea, kind, mode, norm=norm, episodes=episodes, max_t=max_t)
         run = _runs[key]
-        assert run.calls == 1 and run.progress[:, 0].eq(EPISODES).all() and int(run.progress[:, 1].max()) <= FRAMES
+        assert run.calls == 1 and run.progress[:, 0].eq(episodes).all() and int(run.progress[:, 1].max()) <= episodes * max_t
         assert int(run.progress[:, 1].min()) < int(run.progress[:, 1].max())          # (the envs' episodes end at different frames)
     return _runs[key]
 
@@ -177,21 +178,21 @@ def episode_lengths(run):
     return lengths
 
 
-def replay(ea, kind, actions):
+def replay(ea, kind, actions, max_t=MAX_T):
     """The plain rollout's trajectory of envs 0..K-1 under ``actions`` [T, E, 2], from the kind's start state."""
     import torch
-    env = make_env(ea, kind)
+    env = make_env(ea, kind, max_t)
     traj = env.rollout(int(actions.shape[0]), actions=actions, capture_envs=K)["trajectory"].clone()
     torch.cuda.synchronize()
     env.close()
     return traj
 
 
-def assert_frames_are(run, traj, what):
+def assert_frames_are(run, traj, what, episodes=EPISODES):
     steps = run.progress[:, 1].cpu().numpy()
     for e in range(K):
         n = int(steps[e])
-        assert n >= EPISODES and raw(run.frames[:n, e]).equal(raw(traj[:n, e])), (what, e)
+        assert n >= episodes and raw(run.frames[:n, e]).equal(raw(traj[:n, e])), (what, e)
 
 
 CASES_6 = [(k, m, False) for k in NETWORKS for m in ("mean", "sample")] + [(k, "mean", True) for k in NETWORKS] + \
@@ -212,25 +213,32 @@ def test_recording_changes_nothing(ea, kind, mode, norm):
 _replays = {}
 
 
-def rollout_replay(ea, kind, sigma_zero):
+def rollout_replay(ea, kind, sigma_zero, episodes=EPISODES, max_t=MAX_T):
     """policy_rollout's stored actions on a twin handle, replayed through the plain rollout's capture on a third."""
     import torch
-    if (kind, sigma_zero) not in _replays:
-        env = make_env(ea, kind)
-        ro = env.policy_rollout(make_net(ea, kind, sigma_zero), FRAMES, env.observe().clone(), torch.zeros(E, dtype=torch.float32, device=env.device))
+    if (kind, sigma_zero, episodes, max_t) not in _replays:
+        env = make_env(ea, kind, max_t)
+        ro = env.policy_rollout(make_net(ea, kind, sigma_zero), episodes * max_t, env.observe().clone(), torch.zeros(E, dtype=torch.float32, device=env.device))
         actions = ro["actions"].clone()
         torch.cuda.synchronize()
         env.close()
-        _replays[kind, sigma_zero] = replay(ea, kind, actions)
-    return _replays[kind, sigma_zero]
+        _replays[kind, sigma_zero, episodes, max_t] = replay(ea, kind, actions, max_t)
+    return _replays[kind, sigma_zero, episodes, max_t]
+
+
+def sample_mode_frames_are_the_plain_rollouts(ea, kind, episodes=EPISODES, max_t=MAX_T):
+    """Test 7.  Returns the recorded run."""
+    run = recorded(ea, kind, "sample", episodes=episodes, max_t=max_t)
+    # all episode ends but the last inside every env's frames (two at three episodes)
+    assert (episode_lengths(run)[:episodes - 1].sum(0) < run.progress[:, 1].cpu().numpy()).all()
+    assert_frames_are(run, rollout_replay(ea, kind, False, episodes, max_t), kind, episodes)
+    return run
 
 
 @pytest.mark.parametrize("kind", [k for k in KINDS if KINDS[k][0] is not None])
 def test_sample_mode_frames_are_the_plain_rollouts_under_the_policy_rollouts_actions(ea, kind):
     """7."""
-    run = recorded(ea, kind, "sample")
-    assert (episode_lengths(run)[:2].sum(0) < run.progress[:, 1].cpu().numpy()).all()       # two episode ends inside every env's frames
-    assert_frames_are(run, rollout_replay(ea, kind, False), kind)
+    sample_mode_frames_are_the_plain_rollouts(ea, kind)
 
 
 @pytest.mark.parametrize("kind", [k for k in KINDS if KINDS[k][0] is not None])
@@ -306,13 +314,11 @@ def test_terminal_frames_against_the_records(ea, kind, mode, norm):
                 assert int((status == code).sum()) == int(rec[k, e, STATS_FIELDS.index(name)]), (kind, mode, e, k, name)
 
 
-@pytest.mark.parametrize("kind,mode,norm", [("linear", "sample", False), ("deepsets", "mean", True), ("transformer_n62", "mean", True),
-                                            ("scripted", "mean", False)])
-def test_resumption_and_bounds(ea, kind, mode, norm):
-    """12."""
+def resumption_and_bounds(ea, kind, mode, norm, episodes=EPISODES, max_t=MAX_T):
+    """Test 12.  Returns the one-call run."""
     import torch
-    one = recorded(ea, kind, mode, norm)
-    many = evaluate(ea, kind, mode, norm=norm, max_steps=5)
+    one = recorded(ea, kind, mode, norm, episodes, max_t)
+    many = evaluate(ea, kind, mode, norm=norm, max_steps=5, episodes=episodes, max_t=max_t)
     assert many.calls >= 6
     assert raw(many.frames).equal(raw(one.frames)) and raw(many.starts).equal(raw(one.starts)), (kind, mode)
     assert many.progress.equal(one.progress) and raw(many.records).equal(raw(one.records))
@@ -320,14 +326,23 @@ def test_resumption_and_bounds(ea, kind, mode, norm):
     for e in range(K):
         n = int(steps[e])
         assert not torch.isnan(one.frames[:n, e]).any() and torch.isnan(one.frames[n:, e]).all(), (kind, mode, e)
-    # max_frames = 7: the first 7 rows of a backing tensor of 36
-    env = make_env(ea, kind)
-    backing = nan_buffers(env)
+    # max_frames = 7: the first 7 rows of a backing tensor of episodes x max_t (36)
+    env = make_env(ea, kind, max_t)
+    backing = nan_buffers(env, rows=episodes * max_t, episodes=episodes)
     env.close()
-    short = evaluate(ea, kind, mode, norm=norm, buffers={"frames": backing["frames"][:7], "starts": backing["starts"]})
+    short = evaluate(ea, kind, mode, norm=norm, buffers={"frames": backing["frames"][:7], "starts": backing["starts"]}, episodes=episodes,
+                     max_t=max_t)
     assert torch.isnan(backing["frames"][7:]).all()
     assert raw(backing["frames"][:7]).equal(raw(one.frames[:7])) and raw(short.starts).equal(raw(one.starts)), (kind, mode)
     assert raw(short.records).equal(raw(one.records))
+    return one
+
+
+@pytest.mark.parametrize("kind,mode,norm", [("linear", "sample", False), ("deepsets", "mean", True), ("transformer_n62", "mean", True),
+                                            ("scripted", "mean", False)])
+def test_resumption_and_bounds(ea, kind, mode, norm):
+    """12."""
+    resumption_and_bounds(ea, kind, mode, norm)
 
 
 def test_c_abi_refusals(ea):

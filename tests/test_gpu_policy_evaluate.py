@@ -38,14 +38,11 @@ def twins(ea, case, E, **cfg_over):
     return a, b
 
 
-@pytest.mark.parametrize("mode", ["sample", "mean"])
-@pytest.mark.parametrize("case", list(CASES))
-def test_evaluation_is_the_policy_rollout(ea, case, mode):
-    """1. / 2.: policy_evaluate(max_steps = T, n_episodes large) against policy_rollout(T) on a twin handle -- in mean mode with
-    the twin's actor_logstd at -inf (expf gives 0 exactly, so mu + 0 z = mu)."""
+def evaluation_is_the_policy_rollout(ea, case, mode, E=64, T=40, **cfg_over):
+    """policy_evaluate(max_steps = T, n_episodes large) against policy_rollout(T) on a twin handle -- in mean mode with the twin's
+    actor_logstd at -inf (expf gives 0 exactly, so mu + 0 z = mu).  Returns the rollout's [T, E] episode ends."""
     import torch
-    E, T = 64, 40
-    a, b = twins(ea, case, E)
+    a, b = twins(ea, case, E, **cfg_over)
     net = make_net(ea, a.obs_dim)
     twin_net = net
     if mode == "mean":
@@ -68,6 +65,14 @@ def test_evaluation_is_the_policy_rollout(ea, case, mode):
         assert i32(rec[:n, e]).equal(i32(rows)), (case, mode, e)
         assert i32(rec[n:, e]).eq(0).all(), (case, mode, e)
     a.close(); b.close()
+    return ended.cpu().numpy()
+
+
+@pytest.mark.parametrize("mode", ["sample", "mean"])
+@pytest.mark.parametrize("case", list(CASES))
+def test_evaluation_is_the_policy_rollout(ea, case, mode):
+    """1. / 2."""
+    evaluation_is_the_policy_rollout(ea, case, mode)
 
 
 def test_episode_bookkeeping(ea):

@@ -45,9 +45,10 @@ def ea():
     return evacuation_amd
 
 
-def make_env(ea, case, E, options=None):
+def make_env(ea, case, E, options=None, seed=SEED, **cfg_over):
+    """The case's env; ``cfg_over`` replaces fields of its EnvConfig (tests/test_gpu_policy_long.py: max_timesteps)."""
     cfg_kw, wrap_kw, norm = CASES[case]
-    env = ea.BatchedEvacuationEnv(ea.EnvConfig(**cfg_kw), ea.EnvWrappersConfig(**wrap_kw), num_envs=E, seed=SEED,
+    env = ea.BatchedEvacuationEnv(ea.EnvConfig(**{**cfg_kw, **cfg_over}), ea.EnvWrappersConfig(**wrap_kw), num_envs=E, seed=seed,
                                   env_id_offset=OFFSET, options=options)
     return ea.NormalizedVectorEnv(env) if norm else env
 
@@ -118,7 +119,7 @@ def assert_same(ro, rb, what):
         assert i32(ro[k]).equal(i32(rb[k])), (what, k)
 
 
-def check_policy_outputs(ea, env, net, ro, total0):
+def check_policy_outputs(ea, env, net, ro, total0, seed=SEED):
     """1. every step's policy outputs against the float64 restatement on the recorded observation"""
     from tests import policy_ref as R
     b = base(env)
@@ -129,8 +130,10 @@ def check_policy_outputs(ea, env, net, ro, total0):
     lp, val = ro["logprobs"].cpu().double().numpy(), ro["values"].cpu().double().numpy()
     sd = np.exp(P["logstd"])
     zs = []
+    steps = np.arange(obs.shape[0], dtype=np.int64)
+    z_all = R.policy_normal(seed, gid[None, :], (total0[None, :] + steps[:, None]).astype(np.uint32))     # [T, E, 2]: one Philox pass
     for t in range(obs.shape[0]):
-        z = R.policy_normal(SEED, gid, (total0 + t).astype(np.uint32))
+        z = z_all[t]
         mean, a64, lp64, v64 = R.policy_step(P, obs[t], z)
         np.testing.assert_allclose(act[t], a64, rtol=1e-5, atol=1e-5, err_msg=f"actions, step {t}")
         np.testing.assert_allclose(lp[t], lp64, rtol=1e-5, atol=1e-5, err_msg=f"logprobs, step {t}")
@@ -169,14 +172,14 @@ def replay_env_side(ea, twin, ro, obs0, T, what):
     return n_done
 
 
-@pytest.mark.parametrize("case", list(CASES))
-def test_policy_rollout_teacher_forced_and_env_side_bit_for_bit(ea, case):
+def teacher_forced_and_env_side_bit_for_bit(ea, case, E=64, T=40, seed=SEED, **cfg_over):
+    """1. and 2. of one rollout of T steps.  Returns its storage and the twin's norm_state (or None)."""
     import torch
-    E, T = 64, 40
     # (the twin steps with the one-wave family the policy rollout runs for every N <= 64: the sub-wave step kernels of N <= 32
     # sum the exit distances of the intrinsic reward in another order, which may move episode_intrinsic_reward by an ulp)
     from evacuation_amd.options import KernelOptions
-    a, b = make_env(ea, case, E), make_env(ea, case, E, options=KernelOptions().replace(subwave=0))
+    a = make_env(ea, case, E, seed=seed, **cfg_over)
+    b = make_env(ea, case, E, options=KernelOptions().replace(subwave=0), seed=seed, **cfg_over)
     D = base(a).obs_dim
     net = make_net(ea, D)
     obs_a, done_a = start(a)
@@ -196,8 +199,15 @@ def test_policy_rollout_teacher_forced_and_env_side_bit_for_bit(ea, case):
     for k in sa:
         assert sa[k].view(torch.uint8).equal(sb[k].view(torch.uint8)), (case, k)
     assert base(a).clock.equal(base(b).clock) and i32(base(a).acc).equal(i32(base(b).acc)), case
-    check_policy_outputs(ea, a, net, ro, total0)
+    check_policy_outputs(ea, a, net, ro, total0, seed)
+    out = {k: v.clone() for k, v in ro.items()}, (b.norm_state.clone() if hasattr(b, "norm_state") else None)
     a.close(); b.close()
+    return out
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_policy_rollout_teacher_forced_and_env_side_bit_for_bit(ea, case):
+    teacher_forced_and_env_side_bit_for_bit(ea, case)
 
 
 def test_policy_noise_is_standard_normal(ea):
@@ -218,8 +228,8 @@ def test_policy_noise_is_standard_normal(ea):
     env.close()
 
 
-def _run(ea, case, E, T_split, options=None, net=None):
-    env = make_env(ea, case, E, options=options)
+def _run(ea, case, E, T_split, options=None, net=None, **cfg_over):
+    env = make_env(ea, case, E, options=options, **cfg_over)
     net = net or make_net(ea, base(env).obs_dim)
     obs, done = start(env)
     outs = [env.policy_rollout(net, T, obs, done) for T in T_split]
@@ -228,17 +238,27 @@ def _run(ea, case, E, T_split, options=None, net=None):
     return outs, fin
 
 
-def test_split_calls_equal_one_call(ea):
+PER_STEP = ("obs", "actions", "logprobs", "values", "rewards", "dones", "episode_stats")
+
+
+def assert_split_equals_one(one, f1, parts, f2, what):
+    """The storage of one call against that of split calls joined along the step axis, the last call's next_* and the two final
+    snapshots (norm_state among them), bit for bit."""
     import torch
+    for k in PER_STEP:
+        assert i32(one[k]).equal(i32(torch.cat([p[k] for p in parts]))), (what, k)
+    for k in ("next_obs", "next_done", "next_value"):
+        assert i32(one[k]).equal(i32(parts[-1][k])), (what, k)
+    assert set(f1) == set(f2)
+    for k in f1:
+        assert raw(f1[k]).equal(raw(f2[k])), (what, k)
+
+
+def test_split_calls_equal_one_call(ea):
     for case in ("n60_grav_norm_clip", "n32_abs_cat_dict_norm"):
         (one,), f1 = _run(ea, case, 48, [33])
-        (p7, p26), f2 = _run(ea, case, 48, [7, 26])
-        for k in ("obs", "actions", "logprobs", "values", "rewards", "dones", "episode_stats"):
-            assert i32(one[k]).equal(i32(torch.cat([p7[k], p26[k]]))), (case, k)
-        for k in ("next_obs", "next_done", "next_value"):
-            assert i32(one[k]).equal(i32(p26[k])), (case, k)
-        for k in f1:
-            assert raw(f1[k]).equal(raw(f2[k])), (case, k)
+        parts, f2 = _run(ea, case, 48, [7, 26])
+        assert_split_equals_one(one, f1, parts, f2, case)
 
 
 @pytest.mark.parametrize("case,opts", [

@@ -33,9 +33,9 @@ def ea():
     return evacuation_amd
 
 
-def make_env(ea, case, E, offset):
+def make_env(ea, case, E, offset, **cfg_over):
     cfg_kw, wrap_kw, norm = CASES[case]
-    env = ea.BatchedEvacuationEnv(ea.EnvConfig(**cfg_kw), ea.EnvWrappersConfig(**wrap_kw), num_envs=E, seed=SEED, env_id_offset=offset)
+    env = ea.BatchedEvacuationEnv(ea.EnvConfig(**{**cfg_kw, **cfg_over}), ea.EnvWrappersConfig(**wrap_kw), num_envs=E, seed=SEED, env_id_offset=offset)
     return ea.NormalizedVectorEnv(env) if norm else env
 
 
@@ -85,15 +85,11 @@ def restore(env, s):
 
 
 # ------------------------------------------------------------------------------------------------ 1. collection
-@pytest.mark.parametrize("S,E_l", [(1, 48), (3, 3), (5, 16), (4, 40)])
-@pytest.mark.parametrize("case", ["n60_grav_norm_clip", "n60_rel_ohe_box_norm_clip", "n32_abs_cat_dict_norm", "n10_grav_raw"])
-def test_collection_equals_standalone_rollouts(ea, case, S, E_l):
-    """Gravity D = 6, the generic "rel + ohe Box" observation at N = 60 and an N <= 32 room, with the normalisation chain, and a
-    raw gravity env without it: the storage, norm_state, the episode records and the final state of learner s's envs are those of
-    policy_rollout(nets[s]) alone."""
+def collection_equals_standalone_rollouts(ea, case, S, E_l, T=30, **cfg_over):
+    """The storage, norm_state, the episode records and the final state of learner s's envs are those of policy_rollout(nets[s])
+    alone.  Returns the population call's storage."""
     import torch
-    T = 30
-    pop_env = make_env(ea, case, S * E_l, OFFSET)
+    pop_env = make_env(ea, case, S * E_l, OFFSET, **cfg_over)
     D = base(pop_env).obs_dim
     pop = make_population(ea, D, [11 + 7 * s for s in range(S)])
     obs, done, now = start_population(pop_env)
@@ -107,7 +103,7 @@ def test_collection_equals_standalone_rollouts(ea, case, S, E_l):
     fin = snapshot(pop_env)
     for s in range(S):
         cols = slice(s * E_l, (s + 1) * E_l)
-        env = make_env(ea, case, E_l, OFFSET + s * E_l)
+        env = make_env(ea, case, E_l, OFFSET + s * E_l, **cfg_over)
         o, _ = env.reset()
         assert i32(o).equal(i32(obs0[cols])), (case, s, "the reset observation")       # the same start state
         base(env).set_state(now=now[cols].clone())
@@ -130,6 +126,15 @@ def test_collection_equals_standalone_rollouts(ea, case, S, E_l):
     if S > 1:                                                        # the learners did act differently
         assert not i32(ro["actions"][:, :E_l]).equal(i32(ro["actions"][:, E_l:2 * E_l]))
     pop_env.close()
+    return ro
+
+
+@pytest.mark.parametrize("S,E_l", [(1, 48), (3, 3), (5, 16), (4, 40)])
+@pytest.mark.parametrize("case", ["n60_grav_norm_clip", "n60_rel_ohe_box_norm_clip", "n32_abs_cat_dict_norm", "n10_grav_raw"])
+def test_collection_equals_standalone_rollouts(ea, case, S, E_l):
+    """Gravity D = 6, the generic "rel + ohe Box" observation at N = 60 and an N <= 32 room, with the normalisation chain, and a
+    raw gravity env without it."""
+    collection_equals_standalone_rollouts(ea, case, S, E_l)
 
 
 def test_collection_errors(ea):

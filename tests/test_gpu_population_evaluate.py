@@ -33,17 +33,17 @@ def make_population(ea, D, S):
     return make(ea, D, [11 + 7 * s for s in range(S)])
 
 
-def raw_env_at(ea, case, E, offset):
+def raw_env_at(ea, case, E, offset, **cfg_over):
     """EC.make_raw_env with an env_id_offset of the caller's."""
     from evacuation_amd.options import KernelOptions
     cfg_kw, wrap_kw, _ = CASES[case]
-    return ea.BatchedEvacuationEnv(ea.EnvConfig(**cfg_kw), ea.EnvWrappersConfig(**wrap_kw), num_envs=E, seed=SEED,
+    return ea.BatchedEvacuationEnv(ea.EnvConfig(**{**cfg_kw, **cfg_over}), ea.EnvWrappersConfig(**wrap_kw), num_envs=E, seed=SEED,
                                    env_id_offset=offset, options=KernelOptions().replace(subwave=0))
 
 
-def start(ea, case, S, E_l):
+def start(ea, case, S, E_l, **cfg_over):
     """The population's handle, reset, with clocks spread over the WHOLE batch so that episodes end early."""
-    env = EC.make_raw_env(ea, case, S * E_l)
+    env = EC.make_raw_env(ea, case, S * E_l, **cfg_over)
     env.reset()
     EC.spread_clocks(env)
     return env
@@ -60,12 +60,12 @@ def norm_rows(env, seed=5):
     return ns.to(env.device)
 
 
-def learner_alone(ea, case, pop, s, E_l, state0, shared, K, T, deterministic, ns):
+def learner_alone(ea, case, pop, s, E_l, state0, shared, K, T, deterministic, ns, **cfg_over):
     """evac_policy_evaluate of learner s on a handle of E_l envs: the same seed, env_id_offset = OFFSET (+ s E_l when the ids are
     not shared), the state of the learner's share, its rows of norm_state.  Returns (progress, records, final state)."""
     import torch
     cols = slice(s * E_l, (s + 1) * E_l)
-    twin = raw_env_at(ea, case, E_l, OFFSET + (0 if shared else s * E_l))
+    twin = raw_env_at(ea, case, E_l, OFFSET + (0 if shared else s * E_l), **cfg_over)
     twin.reset()
     for k in EC.STATE:
         getattr(twin, k).copy_(state0[k][cols])
@@ -77,10 +77,10 @@ def learner_alone(ea, case, pop, s, E_l, state0, shared, K, T, deterministic, ns
     return progress, rec, fin
 
 
-def assert_learners_alone(ea, case, S, E_l, shared, deterministic, frozen, K=2, T=4096):
+def assert_learners_alone(ea, case, S, E_l, shared, deterministic, frozen, K=2, T=4096, **cfg_over):
     """One population call against S calls of the one-learner entry.  Returns (progress, records) of the population call."""
     import torch
-    env = start(ea, case, S, E_l)
+    env = start(ea, case, S, E_l, **cfg_over)
     pop = make_population(ea, env.obs_dim, S)
     ns = norm_rows(env) if frozen else None
     ns0 = None if ns is None else ns.clone()
@@ -92,7 +92,7 @@ def assert_learners_alone(ea, case, S, E_l, shared, deterministic, frozen, K=2, 
     fin = EC.state_of(env)
     for s in range(S):
         cols = slice(s * E_l, (s + 1) * E_l)
-        p1, r1, f1 = learner_alone(ea, case, pop, s, E_l, state0, shared, K, T, deterministic, ns)
+        p1, r1, f1 = learner_alone(ea, case, pop, s, E_l, state0, shared, K, T, deterministic, ns, **cfg_over)
         what = (case, S, E_l, s, shared, deterministic)
         assert raw(progress[cols]).equal(raw(p1)), what
         assert raw(rec[:, cols]).equal(raw(r1)), what

@@ -77,19 +77,18 @@ def sweep_gammas(S):
     return [0.99, 0.9, 0.5, 0.95, 0.8][:S]
 
 
-def make_env(ea, case, E, offset, gamma=None):
+def make_env(ea, case, E, offset, gamma=None, **cfg_over):
     cfg_kw, wrap_kw, norm = CASES[case]
-    env = ea.BatchedEvacuationEnv(ea.EnvConfig(**cfg_kw), ea.EnvWrappersConfig(**wrap_kw), num_envs=E, seed=SEED, env_id_offset=offset)
+    env = ea.BatchedEvacuationEnv(ea.EnvConfig(**{**cfg_kw, **cfg_over}), ea.EnvWrappersConfig(**wrap_kw), num_envs=E, seed=SEED, env_id_offset=offset)
     return (ea.NormalizedVectorEnv(env) if gamma is None else ea.NormalizedVectorEnv(env, gamma=gamma)) if norm else env
 
 
-@pytest.mark.parametrize("S,E_l", [(3, 3), (4, 40)])
-@pytest.mark.parametrize("case", ["n60_grav_norm_clip", "n60_rel_ohe_box_norm_clip"])
-def test_collection_normalises_rewards_with_each_learners_gamma(ea, case, S, E_l):
+def collection_normalises_rewards_with_each_learners_gamma(ea, case, S, E_l, T=30, gammas=None, **cfg_over):
+    """Learner s's storage, norm_state, records and final state are those of policy_rollout(nets[s]) alone on an env of the
+    learner's own gamma.  Returns the sweep call's storage."""
     import torch
-    T = 30
-    gammas = sweep_gammas(S)
-    pop_env = make_env(ea, case, S * E_l, OFFSET, gamma=0.75)        # (the env's own gamma is nobody's: it must not be used)
+    gammas = gammas or sweep_gammas(S)
+    pop_env = make_env(ea, case, S * E_l, OFFSET, gamma=0.75, **cfg_over)        # (the env's own gamma is nobody's: it must not be used)
     D = base(pop_env).obs_dim
     pop = make_population(ea, D, [11 + 7 * s for s in range(S)])
     obs, done, now = start_population(pop_env)
@@ -103,7 +102,7 @@ def test_collection_normalises_rewards_with_each_learners_gamma(ea, case, S, E_l
     alone_rewards = []
     for s in range(S):
         cols = slice(s * E_l, (s + 1) * E_l)
-        env = make_env(ea, case, E_l, OFFSET + s * E_l, gamma=gammas[s])
+        env = make_env(ea, case, E_l, OFFSET + s * E_l, gamma=gammas[s], **cfg_over)
         o, _ = env.reset()
         assert i32(o).equal(i32(obs0[cols])), (case, s, "the reset observation")
         base(env).set_state(now=now[cols].clone())
@@ -125,7 +124,7 @@ def test_collection_normalises_rewards_with_each_learners_gamma(ea, case, S, E_l
         env.close()
     pop_env.close()
     # gamma does enter: the same learner (net, envs, start state) under another learner's gamma gets other normalised rewards
-    env = make_env(ea, case, E_l, OFFSET, gamma=gammas[1])
+    env = make_env(ea, case, E_l, OFFSET, gamma=gammas[1], **cfg_over)
     o, _ = env.reset()
     base(env).set_state(now=now[:E_l].clone())
     other = env.policy_rollout(pop.nets[0], T, o.clone(), torch.zeros(E_l, dtype=torch.float32, device=DEV))
@@ -134,6 +133,13 @@ def test_collection_normalises_rewards_with_each_learners_gamma(ea, case, S, E_l
     assert not i32(other["rewards"]).equal(i32(alone_rewards[0]))                        # ... and other rewards
     assert not i32(ro["rewards"][:, :E_l]).equal(i32(ro["rewards"][:, E_l:2 * E_l]))
     env.close()
+    return ro
+
+
+@pytest.mark.parametrize("S,E_l", [(3, 3), (4, 40)])
+@pytest.mark.parametrize("case", ["n60_grav_norm_clip", "n60_rel_ohe_box_norm_clip"])
+def test_collection_normalises_rewards_with_each_learners_gamma(ea, case, S, E_l):
+    collection_normalises_rewards_with_each_learners_gamma(ea, case, S, E_l)
 
 
 def test_equal_gammas_are_the_population_kernel(ea):

@@ -47,6 +47,8 @@ CASES = {
 # the seed of each case's net (make_net): one for which the recorded observations meet the variance precondition of test 1
 NET_SEEDS = {"n62_rel_ohe_box_norm_clip": 0, "n60_rel_ohe_box_raw_resid": 0, "n60_rel_ohe_box_raw_resid_generic": 0,
              "n10_abs_cat_box_raw": 1, "n31_rel_no_box_norm": 1}
+# ... and for the rollouts of tests/test_gpu_policy_long.py (150 steps at max_timesteps = 70; 3 envs x 2048 steps at 700)
+LONG_NET_SEEDS = {"n62_rel_ohe_box_norm_clip": 0, "n10_abs_cat_box_raw": 1}
 MIN_NORM_VARIANCE = 1e-4
 T_STEPS = 40
 
@@ -80,18 +82,15 @@ _cases = EncoderCases(CASES, make_net, T_STEPS)
 make_env, rollout_of, _run, _twins = _cases.make_env, _cases.rollout_of, _cases.run, _cases.twins
 
 
-@pytest.mark.parametrize("E", [64, 20])
-@pytest.mark.parametrize("case", list(CASES))
-def test_policy_outputs_teacher_forced(ea, case, E):
-    """1."""
+def check_policy_outputs_teacher_forced(cases, ea, case, E):
+    """Test 1 on the shared rollout of ``cases`` (an EncoderCases of this file's CASES and make_net)."""
     import torch
     from torch.distributions.normal import Normal
     from tests import policy_ref as R
     from tests import transformer_ref as TR
-    net, ro, _, total0, _, _ = rollout_of(ea, case, E)
+    net, ro, _, total0, _, _ = cases.rollout_of(ea, case, E)
     P = TR.params64(net)
     cpu = copy.deepcopy(net).to("cpu")
-    gid = (OFFSET + np.arange(E)).astype(np.uint32)
     obs, act = ro["obs"].cpu().double().numpy(), ro["actions"].cpu().double().numpy()
     lp, val = ro["logprobs"].cpu().double().numpy(), ro["values"].cpu().double().numpy()
     next_obs = ro["next_obs"].cpu().double().numpy()
@@ -102,7 +101,7 @@ def test_policy_outputs_teacher_forced(ea, case, E):
     assert least >= MIN_NORM_VARIANCE, (case, E, least)
     sd = np.exp(P["logstd"])
     T = obs.shape[0]
-    z = np.stack([R.policy_normal(SEED, gid, (total0 + t).astype(np.uint32)) for t in range(T)])
+    z = cases.policy_noise(total0, T)
     mean64, act64, lp64, val64 = R.policy_step(P, y64, z)
     nv64 = R.value(P, next_y64)
     # the yardstick's own float32 error: the module's torch forward on the CPU, on the same observations (and, for the
@@ -130,22 +129,16 @@ def test_policy_outputs_teacher_forced(ea, case, E):
 
 @pytest.mark.parametrize("E", [64, 20])
 @pytest.mark.parametrize("case", list(CASES))
+def test_policy_outputs_teacher_forced(ea, case, E):
+    """1."""
+    check_policy_outputs_teacher_forced(_cases, ea, case, E)
+
+
+@pytest.mark.parametrize("E", [64, 20])
+@pytest.mark.parametrize("case", list(CASES))
 def test_env_side_bit_for_bit(ea, case, E):
     """2."""
-    import torch
-    net, ro, obs0, _, fin, ns0 = rollout_of(ea, case, E)
-    twin = make_env(ea, case, E, subwave=0)
-    obs_b, _ = start(twin)
-    assert i32(obs0).equal(i32(obs_b))
-    if ns0 is not None:
-        twin.norm_state.copy_(ns0)
-    n_done = replay_env_side(ea, twin, ro, obs0, T_STEPS, case)
-    assert n_done >= E // 5                       # autoresets inside the call
-    torch.cuda.synchronize()
-    end = snapshot(twin)
-    for k in fin:                                 # ped, status, agent, clock, acc (and norm_state)
-        assert raw(fin[k]).equal(raw(end[k])), (case, k)
-    twin.close()
+    _cases.env_side_bit_for_bit(ea, case, E)
 
 
 PER_STEP = ("obs", "actions", "logprobs", "values", "rewards", "dones", "episode_stats")
@@ -179,32 +172,7 @@ STATE = ("ped", "status", "agent", "clock", "acc")
 def test_evaluation_is_the_rollout(ea, case, mode):
     """4a. policy_evaluate(max_steps = T) against policy_rollout(T) on a twin handle -- in mean mode with the twin's actor_logstd
     at -inf (expf gives 0 exactly)."""
-    import torch
-    E, T = 48, 40
-    a, b = _twins(ea, case, E)
-    net = make_net(case)
-    twin_net = net
-    if mode == "mean":
-        twin_net = copy.deepcopy(net)
-        with torch.no_grad():
-            twin_net.actor_logstd.fill_(float("-inf"))
-    obs = b.observe().clone()
-    done = torch.zeros(E, dtype=torch.float32, device=b.device)
-    ro = b.policy_rollout(twin_net, T, obs, done)
-    progress, rec = a.policy_evaluate(net, T, T, deterministic=(mode == "mean"))
-    torch.cuda.synchronize()
-    for k in STATE:
-        assert raw(getattr(a, k)).equal(raw(getattr(b, k))), (case, mode, k)
-    assert progress[:, 1].eq(T).all() and progress[:, 2:].eq(0).all()
-    ended = torch.cat([ro["dones"][1:].bool(), ro["next_done"].bool()[None]], dim=0)
-    assert int(ended.sum()) >= E // 5
-    assert progress[:, 0].equal(ended.sum(0).to(torch.int32))
-    for e in range(E):
-        rows = ro["episode_stats"][ended[:, e], e]
-        n = rows.shape[0]
-        assert i32(rec[:n, e]).equal(i32(rows)), (case, mode, e)
-        assert i32(rec[n:, e]).eq(0).all(), (case, mode, e)
-    a.close(); b.close()
+    _cases.evaluation_is_the_rollout(ea, case, mode)
 
 
 @pytest.mark.parametrize("case,frozen", [("n62_rel_ohe_box_norm_clip", True), ("n31_rel_no_box_norm", True), ("n10_abs_cat_box_raw", False)])
