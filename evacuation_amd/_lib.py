@@ -279,6 +279,9 @@ SIGNATURES = {
                                                           C.POINTER(EvacDeepSets), C.POINTER(EvacDeepSetsStrides), C.c_int32,
                                                           _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float,
                                                           C.c_float, _P]),
+    "evac_policy_evaluate_population_deepsets": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyStrides),
+                                                           C.POINTER(EvacDeepSets), C.POINTER(EvacDeepSetsStrides), C.c_int32, C.c_int32,
+                                                           C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P]),
     "evac_deepsets_population_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32]),
     "evac_deepsets_update_population": (C.c_int, [C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacDeepSets),
                                                   C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacDeepSetsGrads),

@@ -31,6 +31,11 @@ struct DeepSetsArgs {
     int elem_dim;
 };
 
+// A population's encoders (evac_deepsets_population.h, evac_deepsets_population_evaluate.h): learner s's six tensors
+struct DeepSetsStrides {
+    int64_t stride[6];                          // floats from learner s to learner s + 1, in evac_deepsets_t order
+};
+
 struct DeepSetsSmem {
     alignas(16) float y[PolicyFamily::kEnvsPerBlock][kPolicyMaxObs];      // the encoded observation the actor-critic reads
     f4 wa[kSetHidden][2];                                                  // (W_a[k][0..3]), (W_a[k][4], W_a[k][5], b_a[k], -); columns >= ed are 0

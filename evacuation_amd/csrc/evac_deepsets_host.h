@@ -7,6 +7,7 @@
 #include <string>
 
 #include "evac_deepsets.h"
+#include "evac_handle_host.h"
 #include "evac_host.h"
 
 static_assert(evac::kSetHidden == kSetEncoderHidden && evac::kSetMaxElemDim == kSetEncoderMaxElemDim,
@@ -24,6 +25,25 @@ struct DeepSetsEncoderHost {
         da = evac::DeepSetsArgs{S.phi_w1, S.phi_b1, S.phi_w2, S.phi_b2, S.rho_w, S.rho_b, (int)S.set_elem_dim};
         why = deepsets_check(S, p.obs_dim, p.n_ped, rows_fit);
         return why.empty() ? EVAC_OK : EVAC_ERR_INVALID_ARGUMENT;
+    }
+};
+
+// The learners of a population of such networks, for evac_handle_host.h's Learners of encoder_rollout / encoder_evaluate
+// (evac_deepsets_population_api.hip, evac_deepsets_population_evaluate_api.hip): their shares of the handle's envs and the strides
+// of their 19 tensors, refused behind the networks.  A unit derives its Learners from this and adds its launch.
+struct DeepSetsLearnerShares {
+    static constexpr bool kOn = true;
+    int32_t n_learners;
+    const evac_mlp_policy_strides_t* strides;
+    const evac_deepsets_strides_t* enc_strides;
+    evac::PopulationArgs q{};
+    evac::DeepSetsStrides dq{};
+
+    std::string check(const evac::Params& p, const evac_mlp_policy_t& policy, const evac_deepsets_t& encoder) {
+        std::string why = learner_shares(p.n_envs, n_learners, strides, policy.obs_dim, q);
+        if (why.empty() && !deepsets_strides_ok(enc_strides, p.obs_dim, encoder.set_elem_dim, n_learners, dq.stride))
+            why = ": an encoder stride is smaller than its tensor, or rho_w's is no multiple of 4 floats";
+        return why;
     }
 };
 

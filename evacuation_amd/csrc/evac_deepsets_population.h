@@ -22,10 +22,7 @@
 
 namespace evac {
 
-// ---- collection ----
-struct DeepSetsStrides {
-    int64_t stride[6];                          // floats from learner s to learner s + 1, in evac_deepsets_t order
-};
+// ---- collection (DeepSetsStrides: evac_deepsets.h) ----
 template <bool NORM, bool DEF>
 __global__ __launch_bounds__(PolicyFamily::kBlock, 4) void k_collect_population_deepsets(Params p, int n_steps, PolicyArgs a, NormArgs na,
                                                                                           PopulationArgs q, DeepSetsArgs da,

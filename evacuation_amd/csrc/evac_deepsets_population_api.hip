@@ -35,21 +35,8 @@ namespace {
 struct DeepSetsPopulationEncoder : DeepSetsEncoderHost {
     static constexpr const char* kRollout = "evac_policy_rollout_population_deepsets";
 };
-// ... and its learners: their shares of the handle's envs, the strides of their 19 tensors, the launch
-struct DeepSetsLearners {
-    static constexpr bool kOn = true;
-    int32_t n_learners;
-    const evac_mlp_policy_strides_t* strides;
-    const evac_deepsets_strides_t* enc_strides;
-    evac::PopulationArgs q{};
-    evac::DeepSetsStrides dq{};
-
-    std::string check(const evac::Params& p, const evac_mlp_policy_t& policy, const evac_deepsets_t& encoder) {
-        std::string why = learner_shares(p.n_envs, n_learners, strides, policy.obs_dim, q);
-        if (why.empty() && !deepsets_strides_ok(enc_strides, p.obs_dim, encoder.set_elem_dim, n_learners, dq.stride))
-            why = ": an encoder stride is smaller than its tensor, or rho_w's is no multiple of 4 floats";
-        return why;
-    }
+// ... and its learners: their shares of the handle's envs and the strides of their 19 tensors (evac_deepsets_host.h), the launch
+struct DeepSetsLearners : DeepSetsLearnerShares {
     void launch(const evac_host::HandleView& v, int n_steps, const evac::PolicyArgs& a, const evac::NormArgs& na,
                 const evac::DeepSetsArgs& ea, hipStream_t S) const {
         const auto fn = EVAC_PICK_BOOL2(evac::k_collect_population_deepsets, na.state != nullptr, v.default_cfg);
@@ -97,7 +84,7 @@ int evac_policy_rollout_population_deepsets(evac_handle_t h, int32_t n_learners,
                                                       collect_outputs(next_obs, next_done, obs_out, actions_out, logprob_out, value_out,
                                                                       reward_out, done_out, next_value_out, final_stats),
                                                       evac::NormArgs{norm_state, gamma, obs_clip, reward_clip, epsilon}, encoder, stream,
-                                                      DeepSetsLearners{n_learners, strides, enc_strides});
+                                                      DeepSetsLearners{{n_learners, strides, enc_strides}});
 }
 
 int64_t evac_deepsets_population_workspace_bytes(int32_t obs_dim, int64_t n_minibatch, int32_t n_learners) {

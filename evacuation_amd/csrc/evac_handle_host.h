@@ -1,6 +1,6 @@
 // What the entries that run a network on a handle's envs share (evac_api.hip: evac_policy_rollout*, evac_policy_evaluate*;
 // evac_deepsets_api.hip, evac_transformer_api.hip: their forms with an encoder; evac_deepsets_population_api.hip: the collection of
-// a population of deep-sets leaders; evac_capture_api.hip: the evaluation entries that record frames).  The handle's struct stays evac_api.hip's own:
+// a population of deep-sets leaders; evac_deepsets_population_evaluate_api.hip: its evaluation; evac_capture_api.hip: the evaluation entries that record frames).  The handle's struct stays evac_api.hip's own:
 // the handle_* functions are defined there and are not exported from the library.  Below them, host-only and inline: what
 // every collection entry and every evaluation entry refuses, the one-wave limit, a population's shares of the envs, and the grid.
 // Each returns the text that follows the entry's name in its message (empty: accepted), as mlp_policy_check does; the entry
@@ -166,13 +166,19 @@ inline int encoder_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_poli
 
 // evac_policy_evaluate_<encoder>: the agent's code first, the one-wave limit last.  CAPTURE: evac_policy_evaluate_<encoder>_capture,
 // the same with capture_check behind the one-wave limit and the capture behind the kernel's arguments.
-template <class Enc, bool CAPTURE = false>
+// Learners (kOn): the population form of the entry (evac_deepsets_population_evaluate_api.hip; Enc::kEvaluatePopulation its name) --
+// check(p, policy, encoder) adds its refusals behind the networks' and before the one-wave limit, and launch(view, a, ev, ea, stream)
+// enqueues its own kernel.
+template <class Enc, bool CAPTURE = false, class Learners = NoLearners>
 inline int encoder_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy, int32_t n_episodes, int32_t max_steps,
                             int32_t* progress, evac_episode_stats_t* episodes_out, const double* norm_state, float obs_clip, float epsilon,
-                            const typename Enc::Struct* encoder, void* stream, const evac_eval_capture_t* capture = nullptr) {
+                            const typename Enc::Struct* encoder, void* stream, const evac_eval_capture_t* capture = nullptr,
+                            Learners learners = Learners{}) {
+    static_assert(!(CAPTURE && Learners::kOn), "recording is one network's");
     using evac_host::handle_fail;
     std::string w;
     if constexpr (CAPTURE) w = Enc::kCapture;
+    else if constexpr (Learners::kOn) w = Enc::kEvaluatePopulation;
     else w = Enc::kEvaluate;
     evac_host::HandleView v;
     if (const int rc = evac_host::handle_begin(h, w.c_str(), &v); rc != EVAC_OK) return rc;
@@ -186,6 +192,9 @@ inline int encoder_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_polic
     std::string why = evaluate_check(agent, n_episodes, max_steps, progress, episodes_out, norm_state, obs_clip, epsilon, ev);
     if (!why.empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
     if (const int rc = encoder_networks_check<Enc>(v.p, policy, encoder, a, ea, why); rc != EVAC_OK) return handle_fail(h, rc, w + why);
+    if constexpr (Learners::kOn) {
+        if (!(why = learners.check(v.p, *policy, *encoder)).empty()) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + why);
+    }
     if (!(why = one_wave_check(v.p)).empty()) return handle_fail(h, EVAC_ERR_UNSUPPORTED, w + why);
     evac::EvalCaptureArgs ca{};
     if constexpr (CAPTURE) {
@@ -196,6 +205,8 @@ inline int encoder_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_polic
     const dim3 grid((unsigned)policy_wgs(v.p.n_envs)), block(evac::PolicyFamily::kBlock);
     if constexpr (CAPTURE) {
         hipLaunchKernelGGL(Enc::capture_kernel(norm_state != nullptr), grid, block, 0, (hipStream_t)stream, v.p, a, ev, ea, ca);
+    } else if constexpr (Learners::kOn) {
+        learners.launch(v, a, ev, ea, (hipStream_t)stream);
     } else {
         hipLaunchKernelGGL(Enc::evaluate_kernel(norm_state != nullptr, v.default_cfg), grid, block, 0, (hipStream_t)stream, v.p, a, ev, ea);
     }

@@ -5,7 +5,8 @@ and episodes cut at the ``num_steps`` window.  ``PolicyEvaluator`` answers "how 
 whole episodes under the network's MEAN action (or its sampled one) with the observation statistics FROZEN, or under the
 reference's scripted sweep baseline (src/agents/baseline_wacuum_cleaner.py) -- from the same start states, reset draws and
 pedestrian-noise streams for every agent, so two agents are compared on the same episodes.  ``PopulationEvaluator`` does the
-same for the S learners of a ``PolicyPopulation`` in one set of launches (``evac_policy_evaluate_population``)."""
+same for the S learners of a ``PolicyPopulation`` or a ``DeepSetsPopulation`` in one set of launches
+(``evac_policy_evaluate_population``, ``evac_policy_evaluate_population_deepsets``)."""
 from __future__ import annotations
 
 import dataclasses
@@ -181,9 +182,10 @@ def check_population_norm_state(norm_state, num_learners: int, obs_dim: int):
 
 
 class PopulationEvaluator(_Evaluator):
-    """``PolicyEvaluator`` for the S learners of a ``PolicyPopulation`` in one set of launches
-    (``evac_policy_evaluate_population``): ONE handle of ``num_learners x num_envs`` envs, reset once; learner s evaluates in
-    envs ``[s E_l, (s + 1) E_l)`` with the global ids of envs ``[0, E_l)``, so every learner's result is, bit for bit, what
+    """``PolicyEvaluator`` for the S learners of a ``PolicyPopulation`` or a ``DeepSetsPopulation`` in one set of launches
+    (``evac_policy_evaluate_population`` / ``evac_policy_evaluate_population_deepsets``): ONE handle of
+    ``num_learners x num_envs`` envs, reset once; learner s evaluates in envs ``[s E_l, (s + 1) E_l)`` with the global ids of
+    envs ``[0, E_l)``, so every learner's result is, bit for bit, what
     ``PolicyEvaluator(num_envs=E_l, seed=seed).evaluate(nets[s], ...)`` gives -- the learners are compared on the same episodes.
     The snapshot is the reset state of envs ``[0, E_l)`` tiled S times: envs of one seed and the same global ids are identical,
     so no second handle is needed to take it from."""
@@ -207,13 +209,16 @@ class PopulationEvaluator(_Evaluator):
 
     def evaluate(self, population, n_episodes: int = 1, *, deterministic: bool = True, norm_state=None, obs_clip: float = 1.0,
                  epsilon: float = 1e-8, max_steps_per_launch: int = 4096) -> List[EvaluationResult]:
-        """``n_episodes`` whole episodes per env under every learner of ``population``: S ``EvaluationResult``s whose tensors are
-        views of ONE records tensor [n_episodes, S, E_l, 10].  ``norm_state``: float64 [S, rows, 3 D + 4] or a list of S tensors
+        """``n_episodes`` whole episodes per env under every learner of ``population`` (either kind): S ``EvaluationResult``s
+        whose tensors are views of ONE records tensor [n_episodes, S, E_l, 10].  ``norm_state``: float64 [S, rows, 3 D + 4] or a list of S tensors
         [rows_s, 3 D + 4]; row ``i mod rows`` of learner s serves its env i, applied frozen.  Launches of at most
         ``max_steps_per_launch`` steps until every env of every learner has finished; the one host read per launch is
         ``progress[:, 0].min()`` over all learners."""
-        from .policy import refuse_deepsets
-        refuse_deepsets(population, "PopulationEvaluator.evaluate")      # (a network where the population goes)
+        from .policy import refuse_deepsets, refuse_transformer
+        from .population import DeepSetsPopulation
+        refuse_transformer(population, "PopulationEvaluator.evaluate")   # (a network where the population goes)
+        if not isinstance(population, DeepSetsPopulation):
+            refuse_deepsets(population, "PopulationEvaluator.evaluate")
         env, S, E_l = self.env, self.num_learners, self.num_envs
         if int(getattr(population, "num_learners", -1)) != S:
             raise ValueError(f"evaluate: the population has {getattr(population, 'num_learners', None)} learners, the evaluator {S}")

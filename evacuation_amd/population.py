@@ -17,7 +17,8 @@ update is a chain of small launches on a nearly idle chip; here learner s rides 
 * ``DeepSetsPopulation``: the same for the deep-sets leader -- 19 stacked tensors, ``nets[s]`` a ``DeepSetsActorCritic`` of
   views.  ``PopulationAdam``, ``policy_rollout_population`` and ``PopulationTrainer`` take one as they take a ``PolicyPopulation``;
   its update is ``deepsets_update_population`` (``evac_deepsets_update_population``: seven launches per minibatch step, as for one
-  such learner).  Sweeps and the one-launch evaluation of such learners are not built: ``evaluate()`` runs learner by learner.
+  such learner), its evaluation ``evac_policy_evaluate_population_deepsets`` (``PopulationEvaluator`` and ``evaluate()`` take
+  it as they take a ``PolicyPopulation``).  Sweeps of such learners are not built.
 * Sweeps: every float-valued hyperparameter (``SWEEP_FIELDS``) may differ per learner -- ``PopulationTrainer(env, population,
   [cfg_0, .., cfg_S-1])``, ``rpo_update_population(cfg=[...])``, ``gae(gamma=[...])``, ``policy_rollout_population(gammas=[...])``;
   ``sweep_configs`` makes the cartesian product.  The learners' values ride in the kernel arguments beside their seeds
@@ -573,19 +574,9 @@ class PopulationTrainer:
     def evaluate(self, n_episodes: int = 1, num_envs: Optional[int] = None, deterministic: bool = True) -> list:
         """``RPOTrainer.evaluate`` for every learner in ONE set of launches on the population evaluator, each with its own rows
         of the training env's observation statistics (frozen copies).  Returns S ``EvaluationResult``s, bit for bit those of
-        ``make_evaluator().evaluate(nets[s], ...)`` learner by learner.  A ``DeepSetsPopulation`` IS evaluated learner by learner
-        (``evac_policy_evaluate_deepsets`` on ``make_evaluator()``'s batch): the same results, S sets of launches."""
+        ``make_evaluator().evaluate(nets[s], ...)`` learner by learner.  A ``DeepSetsPopulation`` likewise
+        (``evac_policy_evaluate_population_deepsets``)."""
         S, E_l = self.num_learners, self.envs_per_learner
-        if self.deepsets:                         # (no one-launch evaluation of deep-sets learners: one PolicyEvaluator, learner by learner)
-            ev, kw = self.make_evaluator(num_envs), {}
-            with torch.no_grad():
-                results = []
-                for s, net in enumerate(self.nets):
-                    if hasattr(self.env, "norm_state"):
-                        kw = {"norm_state": self.env.norm_state.view(S, E_l, -1)[s].clone(), "obs_clip": self.env.obs_clip,
-                              "epsilon": self.env.epsilon}
-                    results.append(ev.evaluate(net, n_episodes, deterministic=deterministic, **kw))
-                return results
         ev = self.make_population_evaluator(num_envs)
         kw = {}
         if hasattr(self.env, "norm_state"):

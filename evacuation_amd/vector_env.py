@@ -749,7 +749,11 @@ class BatchedEvacuationEnv:
         if state is not None:
             self._check_tensor(state, (E, 3 * D + 4), torch.float64, "norm_state")
         args = [K, T, _ptr(progress), _ptr(out), _ptr(state), obs_clip, eps]
-        if population is not None:
+        if population is not None and self._is_set_population(population):       # (learner 0's 19 tensors: the base the strides count from)
+            rc = self.lib.evac_policy_evaluate_population_deepsets(self._h, int(population.num_learners), pol, C.byref(population.strides),
+                                                                   C.byref(population.encoder_struct()), C.byref(population.encoder_strides),
+                                                                   code, int(bool(shared_episodes)), *args, self._stream())
+        elif population is not None:
             rc = self.lib.evac_policy_evaluate_population(self._h, int(population.num_learners), pol, C.byref(population.strides), code,
                                                           int(bool(shared_episodes)), *args, self._stream())
         elif capture is not None:         # (checked by policy_evaluate: check_evaluate_capture)
@@ -770,22 +774,25 @@ class BatchedEvacuationEnv:
     def policy_evaluate_population(self, population, n_episodes: int, max_steps: int, progress: Optional[torch.Tensor] = None,
                                    out: Optional[torch.Tensor] = None, *, deterministic: bool = True, shared_episodes: bool = True,
                                    _norm=None, capture=None):
-        """``policy_evaluate`` for the S learners of ``population`` (a ``PolicyPopulation``) in ONE launch
-        (``evac_policy_evaluate_population``): learner s acts in envs ``[s E_l, (s + 1) E_l)`` of this env, ``E_l = num_envs / S``.
+        """``policy_evaluate`` for the S learners of ``population`` (a ``PolicyPopulation``, or a ``DeepSetsPopulation``, whose
+        learners' set encoders run in the same launch) in ONE launch (``evac_policy_evaluate_population`` /
+        ``evac_policy_evaluate_population_deepsets``): learner s acts in envs ``[s E_l, (s + 1) E_l)`` of this env, ``E_l = num_envs / S``.
         Arguments and results are ``policy_evaluate``'s over the whole batch -- ``progress`` [S E_l, 4], ``out`` [n_episodes,
         S E_l, 10], ``_norm``'s state [S E_l, 3 D + 4] -- and learner s's columns hold, bit for bit, what
         ``policy_evaluate(population.nets[s], ...)`` writes on an env of ``E_l`` envs with the same seed and the same start state.
         ``shared_episodes=True``: that env has this env's ``env_id_offset``, so env i of every learner sees the same reset draws
         and pedestrian noise (the learners are compared on the same episodes); ``False``: its offset is further by ``s E_l``,
-        the ids of ``policy_rollout_population``.  The networks alone: a scripted agent has no learners (``policy_evaluate``),
-        and a population or net with a set encoder or an attention encoder is a ``ValueError``.  So is a ``capture``: recording
-        is ``policy_evaluate``'s, one network at a time."""
-        from .policy import refuse_deepsets
+        the ids of ``policy_rollout_population``.  The populations alone: a scripted agent has no learners (``policy_evaluate``),
+        and a bare network, an attention encoder anywhere, or set-encoder nets in anything but a ``DeepSetsPopulation`` are a
+        ``ValueError``.  So is a ``capture``: recording is ``policy_evaluate``'s, one network at a time."""
+        from .policy import refuse_deepsets, refuse_transformer
         if capture is not None:
             raise ValueError("policy_evaluate_population: a capture cannot be given (policy_evaluate records one network's episodes)")
-        refuse_deepsets(population, "policy_evaluate_population")
+        refuse_transformer(population, "policy_evaluate_population")
+        refuse = refuse_transformer if self._is_set_population(population) else refuse_deepsets
+        refuse(population, "policy_evaluate_population")
         for net in getattr(population, "nets", ()):
-            refuse_deepsets(net, "policy_evaluate_population")
+            refuse(net, "policy_evaluate_population")
         if isinstance(population, str) or not hasattr(population, "strides"):
             raise ValueError("policy_evaluate_population: a PolicyPopulation is expected (a scripted agent has no learners: "
                              "policy_evaluate runs it)")

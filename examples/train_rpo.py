@@ -20,7 +20,8 @@ with ``--gradient device``, by ``evac_deepsets_minibatch_grad`` (``trainer.deeps
 Adam -- or, with ``--gradient device --optimizer device``, the library's clip + Adam over all 19 tensors, the whole update in one
 host call (``evac_deepsets_update``: seven launches per step).  With ``--seeds`` the learners train as a population of such
 networks (``population.DeepSetsPopulation``, ``evac_deepsets_update_population``: the device gradient and optimiser, seven
-launches per step for all learners).  Not with ``--sweep`` (sweeps of deep-sets learners are not built) or ``--compare``, nor
+launches per step for all learners; ``--eval-every`` evaluates all of them in one set of launches,
+``evac_policy_evaluate_population_deepsets``).  Not with ``--sweep`` (sweeps of deep-sets learners are not built) or ``--compare``, nor
 with ``--optimizer device`` under the autograd gradient: those kernels are the linear network's.
 
 ``--network transformer`` trains the reference's attention-encoder network (``policy.TransformerActorCritic``,

@@ -1013,9 +1013,9 @@ int evac_rpo_update_sweep(int32_t n_learners, const evac_mlp_policy_t* policy, c
 
 /* ---- Populations of deep-sets leaders: S learners of ONE configuration, each with its own set encoder ----
  * The two population entries above for the network of evac_deepsets_t: 19 stacked tensors per learner.  evac_deepsets_strides_t
- * is evac_mlp_policy_strides_t's sibling for the encoder's six: floats from learner s to learner s + 1, per tensor.  Sweeps
- * (per-learner hyperparameters) and a one-launch evaluation of such learners do not exist; evac_policy_evaluate_deepsets takes a
- * learner's tensors as they are. */
+ * is evac_mlp_policy_strides_t's sibling for the encoder's six: floats from learner s to learner s + 1, per tensor.  The
+ * one-launch evaluation of such learners is evac_policy_evaluate_population_deepsets, below.  Sweeps (per-learner
+ * hyperparameters) of such learners do not exist. */
 typedef struct evac_deepsets_strides {     /* floats from learner s to learner s + 1, per tensor of evac_deepsets_t */
     int64_t phi_w1, phi_b1, phi_w2, phi_b2, rho_w, rho_b;
 } evac_deepsets_strides_t;
@@ -1037,6 +1037,31 @@ int evac_policy_rollout_population_deepsets(evac_handle_t h, int32_t n_learners,
                                             float* next_value_out, evac_episode_stats_t* final_stats_or_null,
                                             double* norm_state_or_null, float gamma, float obs_clip, float reward_clip,
                                             float epsilon, void* stream);
+/* evac_policy_evaluate_population_deepsets: evac_policy_evaluate_population with the set encoder in front of every learner's
+ * actor, i.e. evac_policy_evaluate_deepsets under the policy agents for n_learners learners in ONE launch.  `policy` / `encoder`
+ * hold learner 0's tensors, learner s's are s x strides / enc_strides further (the actor and the encoder alone are read); learner s
+ * evaluates in envs [s E_l, (s + 1) E_l) of the handle, and progress [S E_l][4], episodes_out [n_episodes][S E_l] and norm_state
+ * [S E_l][evac_norm_state_doubles(h)] are indexed by the handle's env.  EQUIVALENCE: the call writes, bit for bit, what S calls of
+ * evac_policy_evaluate_deepsets write -- call s with learner s's 19 tensors on a handle of E_l envs with the same seed, learner
+ * s's share of the state and its rows of norm_state -- into learner s's columns of progress and episodes_out and its share of the
+ * state.  With shared_episodes != 0 that handle's env_id_offset is this handle's: env i of EVERY learner has the global id of
+ * env i, so all learners meet the same reset draws and pedestrian noise (and, in sample mode, the same z).  With
+ * shared_episodes == 0 it is this handle's + s E_l, the id convention of evac_policy_rollout_population_deepsets: sample mode
+ * with max_steps = T is then that call's env side bit for bit.
+ * ceil(E_l / 16) CU-wide workgroups per learner; a workgroup never mixes learners; the launch lasts as long as its longest env.
+ * EVAC_ERR_UNSUPPORTED / EVAC_ERR_INVALID_ARGUMENT, decided on the host before anything is launched, in this order: a NULL
+ * strides / enc_strides; EVAC_AGENT_VACUUM_CLEANER (no network: evac_policy_evaluate runs it) and an unknown agent; as
+ * evac_policy_evaluate_deepsets of the counts, the buffers and the two networks; n_learners outside 1..EVAC_MAX_LEARNERS, a
+ * number of envs that n_learners does not divide, and with n_learners > 1 a policy or encoder stride smaller than its tensor
+ * (0 included) or a rho_w stride that is no multiple of 4 floats; last, rooms of more than 64 pedestrians.  The handle is joined
+ * first; ONE kernel on `stream`, no host synchronisation, capturable. */
+int evac_policy_evaluate_population_deepsets(evac_handle_t h, int32_t n_learners, const evac_mlp_policy_t* policy,
+                                             const evac_mlp_policy_strides_t* strides, const evac_deepsets_t* encoder,
+                                             const evac_deepsets_strides_t* enc_strides, int32_t agent, int32_t shared_episodes,
+                                             int32_t n_episodes, int32_t max_steps,
+                                             int32_t* progress,                   /* [S E_l][4] in/out; zero it to begin */
+                                             evac_episode_stats_t* episodes_out,  /* [n_episodes][S E_l] */
+                                             const double* norm_state_or_null, float obs_clip, float epsilon, void* stream);
 /* evac_deepsets_update_population: evac_deepsets_update for n_learners learners in one set of launches, with
  * evac_rpo_update_population's argument list and contract: ONE common batch, perms [S][n_epochs][learner_batch_size] whose
  * values are rows of the common arrays, rpo_noise_or_null [S][steps][M][2], stats_out [S][steps][8], HOST seeds [S] and
