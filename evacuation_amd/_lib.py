@@ -104,6 +104,16 @@ class EvacDeepSetsStrides(C.Structure):
     _fields_ = [(f, C.c_int64) for f, _ in EvacDeepSets._fields_[2:]]
 
 
+class EvacTransformerBlockStrides(C.Structure):
+    """evac_transformer_block_strides_t: floats from learner s to learner s + 1, per tensor of evac_transformer_block_t"""
+    _fields_ = [(f, C.c_int64) for f, _ in EvacTransformerBlock._fields_]
+
+
+class EvacTransformerStrides(C.Structure):
+    """evac_transformer_strides_t: the blocks' strides (blocks at index num_blocks and above are never looked at)"""
+    _fields_ = [("blocks", EvacTransformerBlockStrides * 2)]
+
+
 class EvacAdamConfig(C.Structure):
     """evac_adam_config_t"""
     _fields_ = [(f, C.c_double) for f in ("lr", "beta1", "beta2", "eps", "max_grad_norm")]
@@ -293,6 +303,14 @@ SIGNATURES = {
                                                   C.POINTER(EvacDeepSetsAdamState), C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64,
                                                   C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                                   C.c_int32, C.c_double, _P, _P, _P]),
+    # the population of transformer leaders on a handle's envs: the deep-sets forms with the attention encoder's struct and strides
+    "evac_policy_rollout_population_transformer": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyStrides),
+                                                             C.POINTER(EvacTransformer), C.POINTER(EvacTransformerStrides), C.c_int32,
+                                                             _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float,
+                                                             C.c_float, C.c_float, _P]),
+    "evac_policy_evaluate_population_transformer": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyStrides),
+                                                              C.POINTER(EvacTransformer), C.POINTER(EvacTransformerStrides), C.c_int32,
+                                                              C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P]),
     "evac_gae_learners": (C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.POINTER(EvacLearnerHyper),
                                     _P, _P, _P]),
     "evac_policy_rollout_sweep": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyStrides), C.c_int32,

@@ -59,10 +59,28 @@ struct TransformerSmem {
 
 static_assert(kTfMaxModelDim * kWave <= kPolicyMaxObs, "TransformerEncoder: k, v of 64 tokens in the observation's LDS row");
 
-struct TransformerEncoder {
+// a tensor's place in TransformerBlockArgs
+enum TransformerTensor {
+    kTf_wq, kTf_bq, kTf_wk, kTf_bk, kTf_wv, kTf_bv, kTf_dense_w, kTf_dense_b, kTf_ff1_w, kTf_ff1_b, kTf_ff2_w, kTf_ff2_b,
+    kTf_norm1_w, kTf_norm1_b, kTf_norm2_w, kTf_norm2_b, kTfBlockTensors
+};
+static_assert(sizeof(TransformerBlockArgs) == kTfBlockTensors * sizeof(const float*), "TransformerTensor names every tensor of a block");
+
+// Whose tensors stage() reads: of(tensor i of block b as the launch passed it) is the one to read.  A lone network: that one.
+// (A population's learner: evac_transformer_population.h.)
+struct TransformerOwnTensors {
+    __device__ __forceinline__ const float* of(const float* tensor, int, int) const { return tensor; }
+    static constexpr bool kFresh = false;
+    static __device__ __forceinline__ int fresh(int v) { return v; }            // (encode()'s lane and row: as they are)
+    static __device__ __forceinline__ float* fresh(float* v) { return v; }
+};
+
+template <class Tensors>
+struct TransformerEncoderOf {
     static constexpr bool kOn = true;
     TransformerSmem& ts;
     const TransformerArgs& ka;
+    Tensors whose{};
 
     // by the whole workgroup, before the staging barrier (beside stage_policy)
     __device__ __forceinline__ void stage() const {
@@ -71,12 +89,13 @@ struct TransformerEncoder {
         const float qscale = 1.44269504088896341f / sqrtf((float)dm);   // softmax_j(s / sqrt(dm)) as exp2: log2(e) / sqrt(dm) into W_q, b_q
         for (int b = 0; b < ka.num_blocks; ++b) {
             const TransformerBlockArgs& B = ka.blk[b];
+            const auto T = [&](const float* tensor, int i) { return whose.of(tensor, b, i); };
             TransformerBlockSmem& t = ts.blk[b];
             float* qkv = (float*)t.qkv;
             for (int idx = tid; idx < kTfMaxModelDim * 3 * kTfHeads * 8; idx += kStep) {
                 const int e = idx & 7, r = idx >> 3, h = r % kTfHeads, m = (r / kTfHeads) % 3, c = r / (3 * kTfHeads);
-                const float* W = m == 0 ? B.wq : (m == 1 ? B.wk : B.wv);
-                const float* bias = m == 0 ? B.bq : (m == 1 ? B.bk : B.bv);
+                const float* W = m == 0 ? T(B.wq, kTf_wq) : (m == 1 ? T(B.wk, kTf_wk) : T(B.wv, kTf_wv));
+                const float* bias = m == 0 ? T(B.bq, kTf_bq) : (m == 1 ? T(B.bk, kTf_bk) : T(B.bv, kTf_bv));
                 float v = 0.0f;
                 if (c < dm) {
                     const int row = h * dm + c;
@@ -89,24 +108,29 @@ struct TransformerEncoder {
             float* dn = (float*)t.dn;
             for (int idx = tid; idx < kTfMaxModelDim * kTfHeads * 8; idx += kStep) {
                 const int e = idx & 7, r = idx >> 3, h = r % kTfHeads, c = r / kTfHeads;
-                dn[idx] = (c < dm && e < dm) ? B.dense_w[e * (kTfHeads * dm) + c * kTfHeads + h] : 0.0f;
+                dn[idx] = (c < dm && e < dm) ? T(B.dense_w, kTf_dense_w)[e * (kTfHeads * dm) + c * kTfHeads + h] : 0.0f;
             }
             float* ff = (float*)t.ff;
             for (int idx = tid; idx < kTfFeedForward * 16; idx += kStep) {
                 const int e = idx & 15, u = idx >> 4;
                 float v = 0.0f;
                 if (e < 8) {
-                    if (e < dm) v = B.ff1_w[u * dm + e];
-                    else if (e == 6) v = B.ff1_b[u];
+                    if (e < dm) v = T(B.ff1_w, kTf_ff1_w)[u * dm + e];
+                    else if (e == 6) v = T(B.ff1_b, kTf_ff1_b)[u];
                 } else if (e - 8 < dm) {
-                    v = B.ff2_w[(e - 8) * kTfFeedForward + u];
+                    v = T(B.ff2_w, kTf_ff2_w)[(e - 8) * kTfFeedForward + u];
                 }
                 ff[idx] = v;
             }
             float* vec = (float*)t.vec;
             for (int idx = tid; idx < 6 * 8; idx += kStep) {
                 const int e = idx & 7, r = idx >> 3;
-                const float* src = r == 0 ? B.dense_b : (r == 1 ? B.norm1_w : (r == 2 ? B.norm1_b : (r == 3 ? B.ff2_b : (r == 4 ? B.norm2_w : B.norm2_b))));
+                const float* src = r == 0 ? T(B.dense_b, kTf_dense_b)
+                                 : r == 1 ? T(B.norm1_w, kTf_norm1_w)
+                                 : r == 2 ? T(B.norm1_b, kTf_norm1_b)
+                                 : r == 3 ? T(B.ff2_b, kTf_ff2_b)
+                                 : r == 4 ? T(B.norm2_w, kTf_norm2_w)
+                                          : T(B.norm2_b, kTf_norm2_b);
                 vec[idx] = e < dm ? src[e] : 0.0f;
             }
         }
@@ -147,6 +171,10 @@ struct TransformerEncoder {
     // The row x is overwritten (k, v of the channel at hand).
     __device__ __forceinline__ void encode(float* xs, int slot, int lane, int D, int S) const {
         using F = PolicyFamily;
+        // (Tensors::fresh: the value again.  A population's learner makes it opaque, so that the addresses formed from the lane and
+        // the row are formed anew at every call and for every channel, not carried in registers through the step loop.)
+        lane = Tensors::fresh(lane);
+        xs = Tensors::fresh(xs);
         const int dm = ts.elem_dim, nb = ts.num_blocks;
         const bool resid = ts.use_resid != 0;
         const bool valid = lane < S;
@@ -178,6 +206,7 @@ struct TransformerEncoder {
                     vv[h] = affine6(t.qkv[c][2][h][0], t.qkv[c][2][h][1], x);
                 }
                 F::sync();                                          // (the channel before has been read)
+                if constexpr (Tensors::kFresh) kv = (f2*)xs + 3 * Tensors::fresh(lane);
                 kv[0] = f2{kk[0], kk[1]};
                 kv[1] = f2{kk[2], vv[0]};
                 kv[2] = f2{vv[1], vv[2]};
@@ -241,6 +270,8 @@ struct TransformerEncoder {
         F::sync();
     }
 };
+
+using TransformerEncoder = TransformerEncoderOf<TransformerOwnTensors>;
 
 // DEF: the reference's default configuration as compile-time constants (default_config_constants; bit-identical)
 template <bool NORM, bool DEF>

@@ -5,13 +5,18 @@
 #pragma once
 
 #include <cstdint>
+#include <cstring>
 #include <string>
 
 #include "evac_transformer.h"
+#include "evac_transformer_population.h"       // (TransformerStrides; its kernel templates are instantiated by their own units)
+#include "evac_handle_host.h"
 #include "evac_transformer_host.h"
 
 static_assert(sizeof(evac_transformer_block_t) == sizeof(evac::TransformerBlockArgs) && evac::kTfMaxBlocks == 2,
               "evac_transformer_block_t and the kernels' block arguments: the same 16 pointers in the same order");
+static_assert(sizeof(evac_transformer_block_strides_t) == sizeof(evac::TransformerBlockStrides),
+              "evac_transformer_block_strides_t and the kernels' block strides: the same 16 strides in the same order");
 static_assert(evac::kTfHeads == kTransformerHeads && evac::kTfFeedForward == kTransformerFeedForward &&
                   evac::kTfMaxModelDim == kTransformerMaxModelDim && evac::kTfMaxBlocks == kTransformerMaxBlocks &&
                   evac::kWave == kTransformerMaxTokens && evac::kTfLnEps == kTransformerLnEps,
@@ -44,6 +49,28 @@ struct TransformerEncoderHost {
         ta.num_blocks = (int)T.num_blocks;
         ta.use_resid = T.use_resid != 0;
         return EVAC_OK;
+    }
+};
+
+// The learners of a population of such networks, for evac_handle_host.h's Learners of encoder_rollout / encoder_evaluate
+// (evac_transformer_population_api.hip, evac_transformer_population_evaluate_api.hip): their shares of the handle's envs and the
+// strides of their 13 + 16 num_blocks tensors, refused behind the networks.  A unit derives its Learners from this and adds its
+// launch.
+struct TransformerLearnerShares {
+    static constexpr bool kOn = true;
+    int32_t n_learners;
+    const evac_mlp_policy_strides_t* strides;
+    const evac_transformer_strides_t* enc_strides;
+    evac::PopulationArgs q{};
+    evac::TransformerStrides tq{};
+
+    std::string check(const evac::Params& p, const evac_mlp_policy_t& policy, const evac_transformer_t& encoder) {
+        std::string why = learner_shares(p.n_envs, n_learners, strides, policy.obs_dim, q);
+        if (!why.empty()) return why;
+        if (!transformer_strides_ok(enc_strides, encoder.elem_dim, encoder.num_blocks, n_learners))
+            return ": an encoder stride of a block in use is smaller than its tensor";
+        for (int b = 0; b < encoder.num_blocks; ++b) std::memcpy(&tq.blk[b], &enc_strides->blocks[b], sizeof tq.blk[b]);
+        return why;
     }
 };
 

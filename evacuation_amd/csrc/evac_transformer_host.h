@@ -4,6 +4,7 @@
 // them.  Each unit asserts the limits below against its own device constants.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <string>
 
@@ -43,5 +44,23 @@ inline int transformer_check_blocks(const evac_transformer_t& T, std::string& wh
             return why = ": a tensor pointer of the encoder's block " + std::to_string(b) + " is NULL", EVAC_ERR_INVALID_ARGUMENT;
     return EVAC_OK;
 }
+
+// A population's encoder strides (sizes and blocks checked first): with more than one learner every stride of a block in use is
+// at least its tensor; the strides of a block not in use are never looked at.  No alignment condition: the kernels read the
+// encoder's tensors as scalars.
+inline bool transformer_strides_ok(const evac_transformer_strides_t* st, int32_t elem_dim, int32_t num_blocks, int32_t n_learners) {
+    if (n_learners <= 1) return true;
+    const int64_t dm = elem_dim, H = kTransformerHeads, F = kTransformerFeedForward;
+    const int64_t least[16] = {H * dm * dm, H * dm, H * dm * dm, H * dm, H * dm * dm, H * dm, dm * H * dm, dm,
+                               F * dm,      F,      dm * F,      dm,     dm,          dm,     dm,          dm};
+    for (int b = 0; b < num_blocks; ++b)
+        for (int i = 0; i < 16; ++i)
+            if ((&st->blocks[b].wq)[i] < least[i]) return false;
+    return true;
+}
+static_assert(sizeof(evac_transformer_block_strides_t) == 16 * sizeof(int64_t) &&
+                  offsetof(evac_transformer_block_strides_t, norm2_b) == 15 * sizeof(int64_t) &&
+                  sizeof(evac_transformer_strides_t) == kTransformerMaxBlocks * sizeof(evac_transformer_block_strides_t),
+              "transformer_strides_ok walks a block as 16 consecutive strides, wq first and norm2_b last");
 
 }  // namespace

@@ -5,8 +5,9 @@ and episodes cut at the ``num_steps`` window.  ``PolicyEvaluator`` answers "how 
 whole episodes under the network's MEAN action (or its sampled one) with the observation statistics FROZEN, or under the
 reference's scripted sweep baseline (src/agents/baseline_wacuum_cleaner.py) -- from the same start states, reset draws and
 pedestrian-noise streams for every agent, so two agents are compared on the same episodes.  ``PopulationEvaluator`` does the
-same for the S learners of a ``PolicyPopulation`` or a ``DeepSetsPopulation`` in one set of launches
-(``evac_policy_evaluate_population``, ``evac_policy_evaluate_population_deepsets``)."""
+same for the S learners of a ``PolicyPopulation``, a ``DeepSetsPopulation`` or a ``TransformerPopulation`` in one set of launches
+(``evac_policy_evaluate_population``, ``evac_policy_evaluate_population_deepsets``,
+``evac_policy_evaluate_population_transformer``)."""
 from __future__ import annotations
 
 import dataclasses
@@ -182,8 +183,9 @@ def check_population_norm_state(norm_state, num_learners: int, obs_dim: int):
 
 
 class PopulationEvaluator(_Evaluator):
-    """``PolicyEvaluator`` for the S learners of a ``PolicyPopulation`` or a ``DeepSetsPopulation`` in one set of launches
-    (``evac_policy_evaluate_population`` / ``evac_policy_evaluate_population_deepsets``): ONE handle of
+    """``PolicyEvaluator`` for the S learners of a ``PolicyPopulation``, a ``DeepSetsPopulation`` or a ``TransformerPopulation`` in
+    one set of launches (``evac_policy_evaluate_population`` / ``evac_policy_evaluate_population_deepsets`` /
+    ``evac_policy_evaluate_population_transformer``): ONE handle of
     ``num_learners x num_envs`` envs, reset once; learner s evaluates in envs ``[s E_l, (s + 1) E_l)`` with the global ids of
     envs ``[0, E_l)``, so every learner's result is, bit for bit, what
     ``PolicyEvaluator(num_envs=E_l, seed=seed).evaluate(nets[s], ...)`` gives -- the learners are compared on the same episodes.
@@ -209,7 +211,8 @@ class PopulationEvaluator(_Evaluator):
 
     def evaluate(self, population, n_episodes: int = 1, *, deterministic: bool = True, norm_state=None, obs_clip: float = 1.0,
                  epsilon: float = 1e-8, max_steps_per_launch: int = 4096) -> List[EvaluationResult]:
-        """``n_episodes`` whole episodes per env under every learner of ``population`` (either kind): S ``EvaluationResult``s
+        """``n_episodes`` whole episodes per env under every learner of ``population`` (any of the three kinds; a bare network, or
+        a stand-in holding networks with an encoder, is a ``ValueError``): S ``EvaluationResult``s
         whose tensors are views of ONE records tensor [n_episodes, S, E_l, 10].  ``norm_state``: float64 [S, rows, 3 D + 4] or a list of S tensors
         [rows_s, 3 D + 4]; row ``i mod rows`` of learner s serves its env i, applied frozen.  Launches of at most
         ``max_steps_per_launch`` steps until every env of every learner has finished; the one host read per launch is

@@ -246,7 +246,8 @@ def transformer_dropouts(net) -> list:
 
 def refuse_transformer(net, what: str) -> None:
     """``ValueError`` where a network with an attention encoder cannot go: the gradient and optimiser entries of the linear
-    network and of the set encoder, ``DeviceAdam``, populations and sweeps.  It trains with ``RPOTrainer(optimizer="torch")``,
+    network and of the set encoder, ``DeviceAdam``, sweeps, and populations -- but for ``population.TransformerPopulation``, which
+    the entries that run learners on a handle's envs take.  It trains with ``RPOTrainer(optimizer="torch")``,
     whose gradient for such a network is autograd's, or with its own entries (``trainer.transformer_minibatch_grad`` /
     ``transformer_minibatch_step`` / ``transformer_update`` and ``TransformerAdam``:
     ``RPOTrainer(grad_fn=transformer_kernel_grad, optimizer="device_transformer")``)."""

@@ -19,6 +19,12 @@ update is a chain of small launches on a nearly idle chip; here learner s rides 
   its update is ``deepsets_update_population`` (``evac_deepsets_update_population``: seven launches per minibatch step, as for one
   such learner), its evaluation ``evac_policy_evaluate_population_deepsets`` (``PopulationEvaluator`` and ``evaluate()`` take
   it as they take a ``PolicyPopulation``).  Sweeps of such learners are not built.
+* ``TransformerPopulation``: the transformer leader's 13 + 16 per block stacked tensors, ``nets[s]`` a ``TransformerActorCritic``
+  of views.  What runs such learners ON A HANDLE'S ENVS takes one -- ``policy_rollout_population``
+  (``evac_policy_rollout_population_transformer``), ``policy_evaluate_population`` and ``PopulationEvaluator``
+  (``evac_policy_evaluate_population_transformer``).  Their UPDATE is not built: ``PopulationAdam`` and ``PopulationTrainer``
+  refuse one, and each learner trains alone (``RPOTrainer(grad_fn=transformer_kernel_grad, optimizer="device_transformer")``
+  on ``nets[s]``).
 * Sweeps: every float-valued hyperparameter (``SWEEP_FIELDS``) may differ per learner -- ``PopulationTrainer(env, population,
   [cfg_0, .., cfg_S-1])``, ``rpo_update_population(cfg=[...])``, ``gae(gamma=[...])``, ``policy_rollout_population(gammas=[...])``;
   ``sweep_configs`` makes the cartesian product.  The learners' values ride in the kernel arguments beside their seeds
@@ -40,8 +46,9 @@ import torch
 from torch import nn
 
 from . import _lib
-from .policy import (HIDDEN, SET_HIDDEN, DeepSetsActorCritic, LinearActorCritic, _check_encoder, _check_structure, all_tensors, mlp_tensors,
-                     refuse_deepsets, refuse_transformer)
+from .policy import (HIDDEN, SET_HIDDEN, DeepSetsActorCritic, LinearActorCritic, TransformerActorCritic, _check_encoder,
+                     _check_structure, _check_transformer, _transformer_struct, all_tensors, mlp_tensors, refuse_deepsets,
+                     refuse_transformer)
 from .trainer import (BATCH_KEYS, DeviceAdam, RPOTrainingConfig, _f32, _loss_config, _stream, _u64, decode_header, flatten_batch, gae,
                       update_steps)
 from .vector_env import STATS_FIELDS, _ptr
@@ -104,14 +111,19 @@ def population_rows(inds: torch.Tensor, learner, envs_per_learner: int, num_lear
 
 
 def _bind_row(net, tensors, grads, s: int) -> None:
-    """The parameters of ``net`` (``all_tensors`` order: 13, or 19 with a set encoder) become views of row s of ``tensors`` (and
-    their ``.grad`` views of row s of ``grads``)."""
+    """The parameters of ``net`` (``all_tensors`` order: 13, or 19 with a set encoder, or 13 + 16 per block with an attention
+    encoder) become views of row s of ``tensors`` (and their ``.grad`` views of row s of ``grads``)."""
     a, c = net.actor_mean, net.critic
     owners = [(a[0], "weight"), (a[0], "bias"), (a[2], "weight"), (a[2], "bias"), (a[4], "weight"), (a[4], "bias"),
               (net, "actor_logstd"), (c[0], "weight"), (c[0], "bias"), (c[2], "weight"), (c[2], "bias"), (c[4], "weight"), (c[4], "bias")]
     if len(tensors) == 19:
         phi, rho = net.deep_sets.transform_phi, net.deep_sets.transform_rho
         owners += [(phi[0], "weight"), (phi[0], "bias"), (phi[2], "weight"), (phi[2], "bias"), (rho[0], "weight"), (rho[0], "bias")]
+    elif len(tensors) > 13:                   # (``policy._BLOCK_TENSORS``' order, block by block)
+        for blk in net.embedding:
+            at = blk.attention
+            owners += [(m, name) for m in (at.Wq, at.Wk, at.Wv, at.dense, blk.ff[0], blk.ff[3], blk.norm1, blk.norm2)
+                       for name in ("weight", "bias")]
     for i, (mod, name) in enumerate(owners):
         prm = nn.Parameter(tensors[i][s])
         prm.grad = grads[i][s]
@@ -199,15 +211,78 @@ class DeepSetsPopulation:
         return self._encoder
 
 
+class TransformerPopulation:
+    """S transformer leaders (``TransformerActorCritic(obs_dim, number_of_pedestrians, num_blocks=..., use_resid=...)``, dropout 0)
+    as ``13 + 16 num_blocks`` stacked tensors ``[S, ...]`` on ``device``: the actor-critic's 13 in ``evac_mlp_policy_t`` order,
+    then each block's 16 in ``evac_transformer_block_t`` order (``all_tensors``).  ``nets[s]`` is a ``TransformerActorCritic``
+    whose parameters (and ``.grad``) are views of row s, initialised exactly as ``torch.manual_seed(seeds[s]);
+    TransformerActorCritic(obs_dim, number_of_pedestrians, num_blocks=..., use_resid=...)``: ``policy_rollout``,
+    ``policy_evaluate``, ``PolicyEvaluator`` and ``TransformerAdam`` take a learner as they take any such network.  ``strides``
+    / ``encoder_strides``: a learner's distance in each of the 13 / of the blocks' 16.  The blocks' number, the token width and
+    ``use_resid`` are one value per population.  The entries that run the learners on a handle's envs take the object
+    (``policy_rollout_population``, ``policy_evaluate_population``, ``PopulationEvaluator``); the learners' update is not
+    built (``UPDATE_NOT_BUILT``)."""
+
+    UPDATE_NOT_BUILT = ("the update of transformer learners is not built (the gradient, clip and Adam of a TransformerPopulation in "
+                        "one set of launches); what takes one is policy_rollout_population, policy_evaluate_population and "
+                        "PopulationEvaluator, and each learner trains alone with RPOTrainer(grad_fn=transformer_kernel_grad, "
+                        "optimizer=\"device_transformer\") on nets[s]")
+
+    def __init__(self, obs_dim: int, number_of_pedestrians: int, seeds: Sequence[int], device="cuda:0", num_blocks: int = 2,
+                 use_resid: bool = False):
+        seeds = [int(s) for s in seeds]
+        if not 1 <= len(seeds) <= MAX_LEARNERS:
+            raise ValueError(f"TransformerPopulation: {len(seeds)} learners; expected 1..{MAX_LEARNERS}")
+        self.obs_dim, self.number_of_pedestrians = int(obs_dim), int(number_of_pedestrians)
+        if self.number_of_pedestrians < 0 or self.obs_dim % (self.number_of_pedestrians + 2):
+            raise ValueError(f"TransformerPopulation: an observation of {self.obs_dim} floats is not a whole number of floats for each "
+                             f"of the {self.number_of_pedestrians} + 2 tokens (a Box observation is needed)")
+        self.seeds, self.device, self.num_learners = seeds, torch.device(device), len(seeds)
+        fresh = []
+        with torch.random.fork_rng(devices=[]):                # (the caller's generator is left where it was)
+            for seed in seeds:
+                torch.manual_seed(seed)
+                fresh.append(TransformerActorCritic(self.obs_dim, self.number_of_pedestrians, num_blocks=int(num_blocks),
+                                                    use_resid=bool(use_resid)))
+        count = len(all_tensors(fresh[0]))                      # 13 + 16 per block
+        with torch.no_grad():
+            self.tensors = [torch.stack([all_tensors(n)[i].detach() for n in fresh]).to(self.device).contiguous() for i in range(count)]
+        self.grads = [torch.zeros_like(t) for t in self.tensors]
+        self.nets: List[TransformerActorCritic] = []
+        for s, net in enumerate(fresh):
+            _bind_row(net, self.tensors, self.grads, s)
+            self.nets.append(net)
+            _check_structure(net, self.obs_dim, self.device)
+            found = _check_transformer(net, self.obs_dim, self.device, self.number_of_pedestrians)
+        self.token_dim, self.num_blocks, self.use_resid = found
+        sizes = [int(t[0].numel()) for t in self.tensors]
+        self.strides = _lib.EvacMlpPolicyStrides(*sizes[:13])
+        self.encoder_strides = _lib.EvacTransformerStrides()
+        for b in range(self.num_blocks):
+            self.encoder_strides.blocks[b] = _lib.EvacTransformerBlockStrides(*sizes[13 + 16 * b:29 + 16 * b])
+        self._policy = _lib.EvacMlpPolicy(self.obs_dim, HIDDEN, *(t.data_ptr() for t in self.tensors[:13]))
+        self._encoder = _transformer_struct(found, self.tensors[13:])
+
+    def policy_struct(self) -> "_lib.EvacMlpPolicy":
+        """``evac_mlp_policy_t`` of learner 0, the base the strides count from (every learner's views were checked when made)."""
+        return self._policy
+
+    def encoder_struct(self) -> "_lib.EvacTransformer":
+        """``evac_transformer_t`` of learner 0, the base ``encoder_strides`` count from."""
+        return self._encoder
+
+
 class PopulationAdam:
     """``DeviceAdam`` for every learner of ``population``: the moments stacked ``[S, ...]``, ``headers`` ``[S, 8]`` (64 bytes a
     learner).  ``learners[s]`` is a ``DeviceAdam`` whose state is row s and whose ``param_groups`` are its own: ``lr`` and
     ``max_grad_norm`` (one value or a sequence of S) may differ per learner, the betas and eps are one value for all.
     ``param_groups[s]`` is learner s's group; ``state_dict(s)`` / ``load_state_dict(s, sd)`` are its, in ``DeviceAdam``'s
     format, and touch no other learner.  For a ``DeepSetsPopulation`` the stacks are its 19 and ``learners[s]`` a ``DeviceAdam``
-    over all 19 tensors of row s."""
+    over all 19 tensors of row s.  A ``TransformerPopulation`` is a ``ValueError``: its update is not built."""
 
     def __init__(self, population, lr=3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm=0.5):
+        if isinstance(population, TransformerPopulation):
+            raise ValueError(f"PopulationAdam: {TransformerPopulation.UPDATE_NOT_BUILT}")
         self.population = population
         S, dev = population.num_learners, population.device
         lrs, norms = _per_learner(lr, S, "lr"), _per_learner(max_grad_norm, S, "max_grad_norm")
@@ -414,10 +489,12 @@ class PopulationTrainer:
     normaliser runs with its own gamma (whatever the env was wrapped with) and its advantages, loss, clip and ``target_kl`` are
     its own.  ``update()``: anneal, one collection launch, one ``gae``, the permutations, one ``rpo_update_population``, ONE host
     transfer; returns a list of S logs with ``RPOTrainer.update()``'s keys, ``learning_rate`` the learner's own and ``config``
-    its fields that differ from learner 0's."""
+    its fields that differ from learner 0's.  A ``TransformerPopulation`` is a ``ValueError``: its update is not built."""
 
     def __init__(self, env, population, cfgs):
         refuse_deepsets(population, "PopulationTrainer")       # (a network where the population goes)
+        if isinstance(population, TransformerPopulation):
+            raise ValueError(f"PopulationTrainer: {TransformerPopulation.UPDATE_NOT_BUILT}")
         self.deepsets = isinstance(population, DeepSetsPopulation)
         for net in getattr(population, "nets", ()):
             (refuse_transformer if self.deepsets else refuse_deepsets)(net, "PopulationTrainer")

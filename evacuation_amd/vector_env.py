@@ -619,14 +619,18 @@ class BatchedEvacuationEnv:
         Arguments and storage are ``policy_rollout``'s, over the whole batch; learner s's columns hold, bit for bit, what
         ``policy_rollout(population.nets[s], ...)`` writes on an env of ``E_l`` envs with the same seed, ``env_id_offset`` further
         by ``s E_l`` and the same start state.  A ``DeepSetsPopulation`` runs every learner's set encoder in the same launch
-        (``evac_policy_rollout_population_deepsets``) and takes no ``gammas``.  ``gammas``: the learners' training gammas (a
-        sequence of S).  Gamma enters
+        (``evac_policy_rollout_population_deepsets``) and takes no ``gammas``; a ``TransformerPopulation`` runs every learner's
+        attention encoder in the same launch (``evac_policy_rollout_population_transformer``), takes no ``gammas`` either, and,
+        as ``policy_rollout``, no dropout probability other than 0.  ``gammas``: the learners' training gammas (a sequence of
+        S).  Gamma enters
         collection through the reward normaliser alone, so on this raw env ``gammas`` is accepted (and checked) and has no effect;
         ``NormalizedVectorEnv.policy_rollout_population`` runs learner s's chain with ``gammas[s]``."""
         if self.num_envs % population.num_learners:
             raise ValueError(f"policy_rollout_population: {self.num_envs} envs are not {population.num_learners} learners' equal shares")
         if gammas is not None and self._is_set_population(population):
             raise ValueError("policy_rollout_population: sweeps of deep-sets learners are not built (`gammas` is the sweep's)")
+        if gammas is not None and self._is_transformer_population(population):
+            raise ValueError("policy_rollout_population: sweeps of transformer learners are not built (`gammas` is the sweep's)")
         hypers = None if gammas is None else _lib.learner_hypers(population.num_learners, gamma=[float(g) for g in gammas])
         return self._policy_rollout(population.nets[0], population, n_steps, next_obs, next_done, out, _norm, hypers)
 
@@ -635,6 +639,13 @@ class BatchedEvacuationEnv:
         """A ``population.DeepSetsPopulation`` (the one predicate of the population's kind, as ``population.py`` has it)."""
         from .population import DeepSetsPopulation
         return isinstance(population, DeepSetsPopulation)
+
+    @staticmethod
+    def _is_transformer_population(population) -> bool:
+        """A ``population.TransformerPopulation``: the one thing with attention encoders that the population entries take (a
+        bare network, or a stand-in that merely holds such networks, is refused by name as before)."""
+        from .population import TransformerPopulation
+        return isinstance(population, TransformerPopulation)
 
     def _one_wave(self, what: str) -> None:
         from .policy import MAX_PEDESTRIANS
@@ -652,9 +663,11 @@ class BatchedEvacuationEnv:
 
     def _policy_rollout(self, net, population, n_steps, next_obs, next_done, out, _norm, hypers=None):
         from .policy import refuse_deepsets, refuse_dropout, refuse_transformer
-        if population is not None:
+        tf_population = BatchedEvacuationEnv._is_transformer_population(population)
+        if population is not None and not tf_population:
             refuse_transformer(net, "policy_rollout_population")
-        refuse_dropout(net, "policy_rollout")
+        for learner in (population.nets if tf_population else (net,)):
+            refuse_dropout(learner, "policy_rollout")
         self._one_wave("policy_rollout")
         T, E, D = int(n_steps), self.num_envs, self.obs_dim
         if T < 1:
@@ -662,7 +675,7 @@ class BatchedEvacuationEnv:
         binder = self._binder()
         pol = binder(net)
         set_population = self._is_set_population(population)
-        if population is not None and not set_population:
+        if population is not None and not set_population and not tf_population:
             refuse_deepsets(net, "policy_rollout_population")
         enc = binder.bind_encoder(net)        # an encoder in front of the actor-critic: evac_policy_rollout_deepsets / _transformer
         next_obs = self._check_tensor(next_obs, (E, D), torch.float32, "next_obs")
@@ -682,6 +695,10 @@ class BatchedEvacuationEnv:
         if set_population:                    # (learner 0's 19 tensors: the base the strides count from)
             rc = self.lib.evac_policy_rollout_population_deepsets(self._h, population.num_learners, C.byref(pol), C.byref(population.strides),
                                                                   C.byref(enc[1]), C.byref(population.encoder_strides), T, *args)
+        elif tf_population:                   # (learner 0's 13 + 16 num_blocks tensors likewise)
+            rc = self.lib.evac_policy_rollout_population_transformer(self._h, population.num_learners, C.byref(pol),
+                                                                     C.byref(population.strides), C.byref(enc[1]),
+                                                                     C.byref(population.encoder_strides), T, *args)
         elif enc is not None:
             rc = getattr(self.lib, "evac_policy_rollout" + enc[0])(self._h, T, C.byref(pol), *args[:-1], C.byref(enc[1]), args[-1])
         elif population is None:
@@ -753,6 +770,11 @@ class BatchedEvacuationEnv:
             rc = self.lib.evac_policy_evaluate_population_deepsets(self._h, int(population.num_learners), pol, C.byref(population.strides),
                                                                    C.byref(population.encoder_struct()), C.byref(population.encoder_strides),
                                                                    code, int(bool(shared_episodes)), *args, self._stream())
+        elif population is not None and self._is_transformer_population(population):
+            rc = self.lib.evac_policy_evaluate_population_transformer(self._h, int(population.num_learners), pol, C.byref(population.strides),
+                                                                      C.byref(population.encoder_struct()),
+                                                                      C.byref(population.encoder_strides), code, int(bool(shared_episodes)),
+                                                                      *args, self._stream())
         elif population is not None:
             rc = self.lib.evac_policy_evaluate_population(self._h, int(population.num_learners), pol, C.byref(population.strides), code,
                                                           int(bool(shared_episodes)), *args, self._stream())
@@ -774,25 +796,27 @@ class BatchedEvacuationEnv:
     def policy_evaluate_population(self, population, n_episodes: int, max_steps: int, progress: Optional[torch.Tensor] = None,
                                    out: Optional[torch.Tensor] = None, *, deterministic: bool = True, shared_episodes: bool = True,
                                    _norm=None, capture=None):
-        """``policy_evaluate`` for the S learners of ``population`` (a ``PolicyPopulation``, or a ``DeepSetsPopulation``, whose
-        learners' set encoders run in the same launch) in ONE launch (``evac_policy_evaluate_population`` /
-        ``evac_policy_evaluate_population_deepsets``): learner s acts in envs ``[s E_l, (s + 1) E_l)`` of this env, ``E_l = num_envs / S``.
+        """``policy_evaluate`` for the S learners of ``population`` (a ``PolicyPopulation``, or a ``DeepSetsPopulation`` or
+        ``TransformerPopulation``, whose learners' encoders run in the same launch) in ONE launch
+        (``evac_policy_evaluate_population`` / ``evac_policy_evaluate_population_deepsets`` /
+        ``evac_policy_evaluate_population_transformer``): learner s acts in envs ``[s E_l, (s + 1) E_l)`` of this env, ``E_l = num_envs / S``.
         Arguments and results are ``policy_evaluate``'s over the whole batch -- ``progress`` [S E_l, 4], ``out`` [n_episodes,
         S E_l, 10], ``_norm``'s state [S E_l, 3 D + 4] -- and learner s's columns hold, bit for bit, what
         ``policy_evaluate(population.nets[s], ...)`` writes on an env of ``E_l`` envs with the same seed and the same start state.
         ``shared_episodes=True``: that env has this env's ``env_id_offset``, so env i of every learner sees the same reset draws
         and pedestrian noise (the learners are compared on the same episodes); ``False``: its offset is further by ``s E_l``,
         the ids of ``policy_rollout_population``.  The populations alone: a scripted agent has no learners (``policy_evaluate``),
-        and a bare network, an attention encoder anywhere, or set-encoder nets in anything but a ``DeepSetsPopulation`` are a
-        ``ValueError``.  So is a ``capture``: recording is ``policy_evaluate``'s, one network at a time."""
+        and a bare network, attention-encoder nets in anything but a ``TransformerPopulation``, or set-encoder nets in anything
+        but a ``DeepSetsPopulation`` are a ``ValueError``.  So is a ``capture``: recording is ``policy_evaluate``'s, one network at a time."""
         from .policy import refuse_deepsets, refuse_transformer
         if capture is not None:
             raise ValueError("policy_evaluate_population: a capture cannot be given (policy_evaluate records one network's episodes)")
         refuse_transformer(population, "policy_evaluate_population")
-        refuse = refuse_transformer if self._is_set_population(population) else refuse_deepsets
-        refuse(population, "policy_evaluate_population")
-        for net in getattr(population, "nets", ()):
-            refuse(net, "policy_evaluate_population")
+        if not BatchedEvacuationEnv._is_transformer_population(population):
+            refuse = refuse_transformer if BatchedEvacuationEnv._is_set_population(population) else refuse_deepsets
+            refuse(population, "policy_evaluate_population")
+            for net in getattr(population, "nets", ()):
+                refuse(net, "policy_evaluate_population")
         if isinstance(population, str) or not hasattr(population, "strides"):
             raise ValueError("policy_evaluate_population: a PolicyPopulation is expected (a scripted agent has no learners: "
                              "policy_evaluate runs it)")

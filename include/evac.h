@@ -1100,6 +1100,62 @@ int evac_deepsets_update_population(int32_t n_learners, const evac_mlp_policy_t*
                                     const uint64_t* first_draw_counters, int32_t use_target_kl, double target_kl, float* stats_out,
                                     void* workspace, void* stream);
 
+/* ---- Populations of transformer leaders on a handle's envs: S learners, each with its own attention encoder ----
+ * Collection and whole-episode evaluation for the network of evac_transformer_t: 13 + 16 num_blocks stacked tensors per learner
+ * (45 with two blocks).  evac_transformer_strides_t is evac_mlp_policy_strides_t's sibling for the encoder's blocks: floats from
+ * learner s to learner s + 1, per tensor of evac_transformer_block_t; the strides of a block at index num_blocks and above are
+ * never looked at.  num_blocks, elem_dim and use_resid are one value per population.  The UPDATE of such a population (gradient
+ * and optimiser with the learner as a grid dimension) does not exist: each learner trains through evac_transformer_update on its
+ * own tensors.  Sweeps (per-learner hyperparameters) of such learners do not exist. */
+typedef struct evac_transformer_block_strides {   /* floats from learner s to learner s + 1, per tensor of evac_transformer_block_t */
+    int64_t wq, bq, wk, bk, wv, bv, dense_w, dense_b, ff1_w, ff1_b, ff2_w, ff2_b, norm1_w, norm1_b, norm2_w, norm2_b;
+} evac_transformer_block_strides_t;
+typedef struct evac_transformer_strides { evac_transformer_block_strides_t blocks[2]; } evac_transformer_strides_t;
+/* evac_policy_rollout_population_transformer: evac_policy_rollout_population with the attention encoder in front of every
+ * learner's actor-critic.  `policy` / `encoder` hold learner 0's tensors, learner s's are s x strides / enc_strides further;
+ * storage, norm_state and env state as evac_policy_rollout_population's.  EQUIVALENCE: the call writes, bit for bit, what S calls
+ * of evac_policy_rollout_transformer write -- call s with learner s's tensors on a handle of E_l envs with the same seed,
+ * env_id_offset = this handle's + s E_l and learner s's share of the state -- into the learner's columns [s E_l, (s + 1) E_l) of
+ * every array.  ONE launch of ceil(E_l / 16) CU-wide workgroups per learner; a workgroup never mixes learners.
+ * Refused as evac_policy_rollout_transformer and as evac_policy_rollout_population (EVAC_ERR_UNSUPPORTED for more than 62
+ * pedestrians -- one wave holds the N + 2 tokens --, the gravity observation and the encoder's sizes; EVAC_ERR_INVALID_ARGUMENT
+ * otherwise), and a NULL enc_strides, and with n_learners > 1 an encoder stride of a block in use smaller than its tensor (0
+ * included).  No alignment is asked of the encoder's strides: its tensors are read as scalars. */
+int evac_policy_rollout_population_transformer(evac_handle_t h, int32_t n_learners, const evac_mlp_policy_t* policy,
+                                               const evac_mlp_policy_strides_t* strides, const evac_transformer_t* encoder,
+                                               const evac_transformer_strides_t* enc_strides, int32_t n_steps,
+                                               float* next_obs, float* next_done,
+                                               float* obs_out, float* actions_out, float* logprob_out,
+                                               float* value_out, float* reward_out, float* done_out,
+                                               float* next_value_out, evac_episode_stats_t* final_stats_or_null,
+                                               double* norm_state_or_null, float gamma, float obs_clip, float reward_clip,
+                                               float epsilon, void* stream);
+/* evac_policy_evaluate_population_transformer: evac_policy_evaluate_population with the attention encoder in front of every
+ * learner's actor, i.e. evac_policy_evaluate_transformer under the policy agents for n_learners learners in ONE launch.  `policy`
+ * / `encoder` hold learner 0's tensors, learner s's are s x strides / enc_strides further (the actor and the encoder alone are
+ * read); learner s evaluates in envs [s E_l, (s + 1) E_l) of the handle, and progress [S E_l][4], episodes_out [n_episodes][S E_l]
+ * and norm_state [S E_l][evac_norm_state_doubles(h)] are indexed by the handle's env.  EQUIVALENCE: the call writes, bit for bit,
+ * what S calls of evac_policy_evaluate_transformer write -- call s with learner s's tensors on a handle of E_l envs with the same
+ * seed, learner s's share of the state and its rows of norm_state -- into learner s's columns of progress and episodes_out and its
+ * share of the state.  With shared_episodes != 0 that handle's env_id_offset is this handle's: env i of EVERY learner has the
+ * global id of env i, so all learners meet the same reset draws and pedestrian noise (and, in sample mode, the same z).  With
+ * shared_episodes == 0 it is this handle's + s E_l, the id convention of evac_policy_rollout_population_transformer: sample mode
+ * with max_steps = T is then that call's env side bit for bit.
+ * ceil(E_l / 16) CU-wide workgroups per learner; a workgroup never mixes learners; the launch lasts as long as its longest env.
+ * EVAC_ERR_UNSUPPORTED / EVAC_ERR_INVALID_ARGUMENT, decided on the host before anything is launched, in this order: a NULL
+ * strides / enc_strides; EVAC_AGENT_VACUUM_CLEANER (no network: evac_policy_evaluate runs it) and an unknown agent; as
+ * evac_policy_evaluate_transformer of the counts, the buffers and the two networks; n_learners outside 1..EVAC_MAX_LEARNERS, a
+ * number of envs that n_learners does not divide, and with n_learners > 1 a policy stride, or an encoder stride of a block in use,
+ * smaller than its tensor (0 included); last, rooms of more than 64 pedestrians.  The handle is joined first; ONE kernel on
+ * `stream`, no host synchronisation, capturable. */
+int evac_policy_evaluate_population_transformer(evac_handle_t h, int32_t n_learners, const evac_mlp_policy_t* policy,
+                                                const evac_mlp_policy_strides_t* strides, const evac_transformer_t* encoder,
+                                                const evac_transformer_strides_t* enc_strides, int32_t agent, int32_t shared_episodes,
+                                                int32_t n_episodes, int32_t max_steps,
+                                                int32_t* progress,                   /* [S E_l][4] in/out; zero it to begin */
+                                                evac_episode_stats_t* episodes_out,  /* [n_episodes][S E_l] */
+                                                const double* norm_state_or_null, float obs_clip, float epsilon, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 """Measure the policy evaluation kernel (evac_policy_evaluate) against the policy rollout.
 
     python tools/eval_bench.py [--envs 4096] [--steps 128] [--reps 9] [--shape grav|wide|both] [--evaluate-only]
-    python tools/eval_bench.py --learners S [--learner-envs 256] [--pairs 9] [--network linear|deep_sets]
+    python tools/eval_bench.py --learners S [--learner-envs 256] [--pairs 9] [--network linear|deep_sets|transformer]
     python tools/eval_bench.py --capture K [--envs 4096] [--steps 128] [--reps 9]
 
 Per shape -- N = 60 with the gravity observation (D = 6), and with the rel + ohe Box observation (D = 372), both with the frozen
@@ -18,7 +18,9 @@ observation and the frozen normaliser, one episode per env at the default ``max_
 statistics, one warm-up of each, then interleaved pairs whose order alternates: hipEvent time and host wall time, median and
 range, and the S ``summary()`` reads against one ``EvaluationResult.summaries``.  ``--network deep_sets``: the same for a
 ``DeepSetsPopulation`` on the rel + ohe Box observation (D = 372), its learners made visible as the tests make them -- the loop is
-what ``PopulationTrainer.evaluate()`` ran for such a population before ``evac_policy_evaluate_population_deepsets``.  The exit
+what ``PopulationTrainer.evaluate()`` ran for such a population before ``evac_policy_evaluate_population_deepsets``.  ``--network transformer``:
+the same for a ``TransformerPopulation`` (two blocks) on that observation, against the loop of the lone entry
+(``evac_policy_evaluate_transformer``); a report, whatever the ratio.  The exit
 code says whether the population call's whole host-wall range lies below the loop's.
 
 ``--capture K`` measures what recording costs (``policy_evaluate(capture=...)``, the ``k_evaluate_capture*`` kernels): N = 60, the
@@ -207,16 +209,34 @@ def visible_deepsets_population(D, N, S):
     return pop
 
 
+def visible_transformer_population(D, N, S):
+    """Freshly seeded transformer learners (two blocks) whose actions are told apart (tests/test_gpu_transformer_population.py: visible)."""
+    from evacuation_amd.population import TransformerPopulation
+    pop = TransformerPopulation(D, N, list(range(1, S + 1)), DEV)
+    with torch.no_grad():
+        for s, net in enumerate(pop.nets):
+            g = torch.Generator().manual_seed(1000 + s)
+            net.actor_mean[4].weight.mul_(60.0)
+            net.actor_logstd.copy_(torch.tensor([[-0.5 + 0.1 * s, 0.3 - 0.05 * s]]))
+            for m in list(net.actor_mean) + list(net.critic):
+                if isinstance(m, torch.nn.Linear):
+                    m.bias.copy_((0.2 * torch.randn(m.bias.shape, generator=g)).to(DEV))
+    return pop
+
+
 def population_against_loop(args):
     from evacuation_amd.evaluation import EvaluationResult, PopulationEvaluator
     S, E_l = args.learners, args.learner_envs
-    deep_sets = args.network == "deep_sets"
+    deep_sets, transformer = args.network == "deep_sets", args.network == "transformer"
     cfg = ea.EnvConfig(number_of_pedestrians=60, is_new_exiting_reward=True, clip_action=True)
-    wrap = ea.EnvWrappersConfig(**SHAPES["wide" if deep_sets else "grav"])
+    wrap = ea.EnvWrappersConfig(**SHAPES["wide" if deep_sets or transformer else "grav"])
     one = ea.PolicyEvaluator(cfg, wrap, num_envs=E_l, seed=1)
     every = PopulationEvaluator(cfg, wrap, num_learners=S, num_envs=E_l, seed=1)
     D = every.env.obs_dim
-    pop = visible_deepsets_population(D, 60, S) if deep_sets else ea.PolicyPopulation(6, list(range(1, S + 1)), DEV)
+    if transformer:
+        pop = visible_transformer_population(D, 60, S)
+    else:
+        pop = visible_deepsets_population(D, 60, S) if deep_sets else ea.PolicyPopulation(6, list(range(1, S + 1)), DEV)
     g = torch.Generator().manual_seed(0)
     ns = torch.zeros((S, E_l, 3 * D + 4), dtype=torch.float64)               # frozen rows that differ per learner and env
     ns[..., :D] = torch.randn((S, E_l, D), generator=g, dtype=torch.float64) * 0.1
@@ -283,7 +303,7 @@ def population_against_loop(args):
     print(f"    the population call's whole host-wall range lies {'below' if below else 'NOT below'} the loop's")
     one.close()
     every.close()
-    return below if deep_sets else r_wall >= 1.0
+    return True if transformer else (below if deep_sets else r_wall >= 1.0)
 
 
 def main():
@@ -297,7 +317,7 @@ def main():
     ap.add_argument("--learners", type=int, default=0, help="measure the population evaluation with this many learners instead")
     ap.add_argument("--learner-envs", type=int, default=256)
     ap.add_argument("--pairs", type=int, default=9)
-    ap.add_argument("--network", choices=("linear", "deep_sets"), default="linear", help="with --learners: the learners' network")
+    ap.add_argument("--network", choices=("linear", "deep_sets", "transformer"), default="linear", help="with --learners: the learners' network")
     ap.add_argument("--capture", type=int, default=0, metavar="K", help="measure an evaluation without and with the frames of K envs instead")
     args = ap.parse_args()
     if args.capture:

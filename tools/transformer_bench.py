@@ -5,6 +5,7 @@ replaces.
     python tools/transformer_bench.py --part a|b|c|c-eager [--envs 4096] [--steps 128] [--blocks 2] [--use-resid] [--reps 7]
     python tools/transformer_bench.py --part grad-autograd|grad-device [--minibatch 16384] [--blocks 2] [--use-resid] [--reps 7]
     python tools/transformer_bench.py --part update-torch|update-step|update-one-call [--envs 4096] [--steps 128] [--epochs 10]
+    python tools/transformer_bench.py --part collect-population --learners S [--learner-envs 3] [--steps 2048] [--pairs 9]
 
 N = 60, the rel + ohe Box observation (D = 372, 62 tokens of 6), the trainer's normalisation chain, E envs, T steps per call;
 hipEvent times of whole calls after two warm-up calls, median and range of ``--reps`` calls, one JSON line:
@@ -23,6 +24,11 @@ hipEvent times of whole calls after two warm-up calls, median and range of ``--r
            after one warm-up update
   update-step    the same with one ``transformer_minibatch_step`` per minibatch (``TransformerAdam``)
   update-one-call  the same as one ``transformer_update``
+  collect-population  the collection phase of S learners (``--learners``) of ``--learner-envs`` envs and ``--steps`` steps each (the
+           reference's 3 x 2048 by default): ONE ``policy_rollout_population`` of a ``TransformerPopulation`` on a handle of S E_l
+           envs (``evac_policy_rollout_population_transformer``) against the loop of S ``policy_rollout(nets[s])`` on handles of E_l
+           envs at the learners' ids (``evac_policy_rollout_transformer``), the same nets; one warm-up of each, the first calls'
+           storage compared bit for bit, then ``--pairs`` interleaved pairs whose order alternates: hipEvent and host wall time
 One part per process, so that a job script can give each its own time limit."""
 import argparse
 import json
@@ -86,6 +92,62 @@ def grad_part(args):
                       "launches": launches, "loss": round(float(stats[0]), 6), "grad_sumsq": float(stats[7]), "calls": len(ms)}))
 
 
+def collect_population_part(args):
+    """S learners' collection in one launch against the per-learner loop of the lone entry, interleaved; one JSON line."""
+    import time
+    from evacuation_amd.population import TransformerPopulation
+    S, E_l, T = args.learners, args.learner_envs, args.steps or 2048
+    cfg, wrap = ea.EnvConfig(number_of_pedestrians=N_PED), ea.EnvWrappersConfig(positions="rel", statuses="ohe", type="Box")
+    make = lambda E, offset: ea.NormalizedVectorEnv.make(cfg, wrap, num_envs=E, gamma=0.99, seed=1, env_id_offset=offset)
+    every, lone = make(S * E_l, 0), [make(E_l, s * E_l) for s in range(S)]
+    D = every.obs_dim
+    pop = TransformerPopulation(D, N_PED, list(range(1, S + 1)), DEV, num_blocks=args.blocks, use_resid=args.use_resid)
+    with torch.no_grad():                        # learners that are told apart (tests/test_gpu_transformer_population.py: visible)
+        for s, net in enumerate(pop.nets):
+            net.actor_mean[4].weight.mul_(60.0)
+            net.actor_logstd.copy_(torch.tensor([[-0.5 + 0.1 * s, 0.3 - 0.05 * s]]))
+    zeros = lambda E: torch.zeros(E, dtype=torch.float32, device=DEV)
+    obs, done = every.reset()[0].clone(), zeros(S * E_l)
+    obs_l, done_l = [e.reset()[0].clone() for e in lone], [zeros(E_l) for _ in lone]
+    with torch.no_grad():
+        out = every.policy_rollout_population(pop, T, obs, done)
+        out_l = [e.policy_rollout(pop.nets[s], T, obs_l[s], done_l[s]) for s, e in enumerate(lone)]
+        torch.cuda.synchronize()
+        for s in range(S):                       # the two forms give the same storage
+            for k in ("obs", "actions", "logprobs", "values", "rewards", "dones"):
+                assert out[k][:, s * E_l:(s + 1) * E_l].contiguous().view(torch.int32).equal(out_l[s][k].contiguous().view(torch.int32)), (s, k)
+
+        def together():
+            every.policy_rollout_population(pop, T, obs, done, out=out)
+
+        def loop():
+            for s, e in enumerate(lone):
+                e.policy_rollout(pop.nets[s], T, obs_l[s], done_l[s], out=out_l[s])
+
+        def timed(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ms = event_ms(fn)
+            return ms, (time.perf_counter() - t0) * 1e3
+        ev, wall = {"loop": [], "population": []}, {"loop": [], "population": []}
+        for pair in range(args.pairs):
+            for form in (("loop", "population") if pair % 2 == 0 else ("population", "loop")):
+                e_ms, w_ms = timed(loop if form == "loop" else together)
+                ev[form].append(e_ms)
+                wall[form].append(w_ms)
+    med = {f: statistics.median(ev[f]) for f in ev}
+    row = {"part": args.part, "learners": S, "learner_envs": E_l, "steps": T, "obs_dim": D, "blocks": args.blocks,
+           "use_resid": bool(args.use_resid), "pairs": args.pairs}
+    for f in ("loop", "population"):
+        row[f] = {"ms_median": round(med[f], 3), "ms_min": round(min(ev[f]), 3), "ms_max": round(max(ev[f]), 3),
+                  "host_ms_median": round(statistics.median(wall[f]), 3)}
+    row["loop_over_population"] = round(med["loop"] / med["population"], 3)
+    row["population_range_below_loop"] = max(ev["population"]) < min(ev["loop"])
+    print(json.dumps(row))
+    for e in [every] + lone:
+        e.close()
+
+
 def update_part(args):
     """One whole update's epochs at N = 60, rel + ohe Box (D = 372), three ways: whole updates between two events after one
     warm-up update (tools/deepsets_bench.py's update parts with this network's entries)."""
@@ -144,15 +206,21 @@ def update_part(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", required=True, choices=["a", "b", "c", "c-eager", "grad-autograd", "grad-device", "update-torch", "update-step",
-                                                     "update-one-call"])
+                                                     "update-one-call", "collect-population"])
     ap.add_argument("--minibatch", type=int, default=16384)
     ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--steps", type=int, default=128)
+    ap.add_argument("--steps", type=int, default=None, help="default 128; collect-population: 2048")
     ap.add_argument("--blocks", type=int, default=2)
     ap.add_argument("--use-resid", action="store_true")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--epochs", type=int, default=10, help="update-*: the epochs of one update")
+    ap.add_argument("--learners", type=int, default=4, help="collect-population: the learners")
+    ap.add_argument("--learner-envs", type=int, default=3, help="collect-population: a learner's envs")
+    ap.add_argument("--pairs", type=int, default=9, help="collect-population: interleaved pairs")
     args = ap.parse_args()
+    if args.part == "collect-population":
+        return collect_population_part(args)
+    args.steps = args.steps or 128
     if args.part.startswith("update-"):
         return update_part(args)
     if args.part.startswith("grad-"):
