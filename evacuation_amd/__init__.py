@@ -18,8 +18,9 @@ __all__ = ["EnvConfig", "EnvWrappersConfig", "Status", "setup_env", "EvacuationE
            "ShardedEvacuationEnv", "SplitBatchEnv", "NormalizedVectorEnv", "HostVectorEnv", "RandomAgent", "KernelOptions", "kernel_options",
            "RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad", "DeviceAdam", "rpo_minibatch_step", "rpo_update",
            "deepsets_minibatch_grad", "deepsets_kernel_grad", "WacuumCleaner", "PolicyEvaluator", "PopulationEvaluator", "EvaluationResult",
-           "PolicyPopulation", "DeepSetsPopulation", "TransformerPopulation", "PopulationAdam", "PopulationTrainer",
-           "rpo_update_population", "deepsets_update_population", "episode_to_memory"]
+           "PolicyPopulation", "DeepSetsPopulation", "TransformerPopulation", "PopulationAdam", "TransformerPopulationAdam",
+           "PopulationTrainer", "rpo_update_population", "deepsets_update_population", "transformer_update_population",
+           "episode_to_memory"]
 
 
 def __getattr__(name):   # lazy: keeps `import evacuation_amd` light and torch-free for config users
@@ -54,8 +55,8 @@ def __getattr__(name):   # lazy: keeps `import evacuation_amd` light and torch-f
                 "deepsets_minibatch_grad", "deepsets_kernel_grad"):   # the trainer's update on the device
         from . import trainer as _trainer
         return getattr(_trainer, name)
-    if name in ("PolicyPopulation", "DeepSetsPopulation", "TransformerPopulation", "PopulationAdam", "PopulationTrainer",
-                "rpo_update_population", "deepsets_update_population"):   # S learners in one set of launches
+    if name in ("PolicyPopulation", "DeepSetsPopulation", "TransformerPopulation", "PopulationAdam", "TransformerPopulationAdam",
+                "PopulationTrainer", "rpo_update_population", "deepsets_update_population", "transformer_update_population"):   # S learners in one set of launches
         from . import population as _population
         return getattr(_population, name)
     if name == "episode_to_memory":      # one episode of a recorded evaluation in the reference's frame format

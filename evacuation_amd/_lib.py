@@ -311,6 +311,18 @@ SIGNATURES = {
     "evac_policy_evaluate_population_transformer": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyStrides),
                                                               C.POINTER(EvacTransformer), C.POINTER(EvacTransformerStrides), C.c_int32,
                                                               C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P]),
+    # its update: evac_deepsets_update_population's arguments with the attention encoder's structs
+    "evac_transformer_population_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32]),
+    "evac_transformer_update_population": (C.c_int, [C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacTransformer),
+                                                     C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacTransformerGrads),
+                                                     C.POINTER(EvacMlpPolicyGrads), C.POINTER(EvacTransformerGrads),
+                                                     C.POINTER(EvacMlpPolicyStrides), C.POINTER(EvacTransformerStrides),
+                                                     C.POINTER(EvacMlpPolicyStrides), C.POINTER(EvacTransformerStrides),
+                                                     C.POINTER(EvacMlpPolicyStrides), C.POINTER(EvacTransformerStrides), C.c_int64,
+                                                     C.POINTER(EvacRpoLossConfig), C.POINTER(EvacAdamConfig),
+                                                     C.POINTER(EvacTransformerAdamState), C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64,
+                                                     C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                     C.c_int32, C.c_double, _P, _P, _P]),
     "evac_gae_learners": (C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.POINTER(EvacLearnerHyper),
                                     _P, _P, _P]),
     "evac_policy_rollout_sweep": (C.c_int, [_P, C.c_int32, C.POINTER(EvacMlpPolicy), C.POINTER(EvacMlpPolicyStrides), C.c_int32,

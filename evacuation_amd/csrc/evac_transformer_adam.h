@@ -11,26 +11,10 @@
 // adam_element and adam_close of evac_train.h.
 #pragma once
 
+#include "evac_transformer_adam_args.h"
 #include "evac_train.h"
 
 namespace evac {
-
-constexpr int kTfAdamBlockTensors = 16;                                    // evac_transformer_block_grads_t
-constexpr int kTfAdamMaxBlocks = 2;
-constexpr int kTfAdamTensors = kAdamTensors + kTfAdamBlockTensors * kTfAdamMaxBlocks;   // 45
-struct TfAdamArgs {
-    float *p[kTfAdamTensors], *g[kTfAdamTensors], *m[kTfAdamTensors], *v[kTfAdamTensors];
-    int wg_end[kTfAdamTensors];                 // running workgroup counts: tensor i has workgroups [wg_end[i - 1], wg_end[i])
-    int n[kTfAdamTensors];                      // elements of tensor i
-    AdamHeader* hdr;
-    const float* sumsq;                         // the sum of squares of all gradient entries, nt tensors (device)
-    const float* stats;                         // the step's statistics (approx_kl at [5]) for the early exit, or NULL
-    double lr, beta1, beta2, target_kl;
-    float max_norm, w, b2, u, eps;              // as AdamArgs'
-    int gated, epoch_last, use_target_kl;
-    int nt;                                     // tensors in use: 13 + 16 num_blocks
-};
-static_assert(sizeof(TfAdamArgs) <= 4096, "k_adam_tf's kernel arguments: the kernel-argument segment holds 4 KB");
 
 __global__ __launch_bounds__(kAdamBlock) void k_adam_tf(TfAdamArgs a) {
     if (a.gated && a.hdr->stop) return;

@@ -24,7 +24,8 @@
 // (no MFMA: every contraction is 6 or 3 wide).
 // The four are templates over an optional trailing argument, as k_rpo_* are: k_tf_*<> are evac_transformer_minibatch_grad's
 // kernels; k_tf_*<const AdamHeader*> are evac_transformer_update's, which return at once, touching nothing (k_tf_encode not even
-// the ticket), when the header's stop flag is set.
+// the ticket), when the header's stop flag is set; k_tf_*<const AdamHeader*, TfgLearnerStrides> are a population's
+// (evac_transformer_update_population: the learner is blockIdx.y; see TfgLearner below), instantiated by its unit alone.
 #pragma once
 
 #include "evac_train.h"
@@ -92,9 +93,88 @@ struct TfgArgs {
     int P, chunk;                                // workgroups of k_tf_backward, `chunk` samples each
 };
 
-__device__ __forceinline__ int64_t tfg_index(const TfgArgs& a, int64_t m) {         // (indices outside the batch never leave it)
-    const int64_t i = a.inds[m];
-    return i < 0 ? 0 : (i >= a.B ? a.B - 1 : i);
+__device__ __forceinline__ int64_t tfg_index(const int64_t* inds, int64_t B, int64_t m) {   // (indices outside the batch never leave it)
+    const int64_t i = inds[m];
+    return i < 0 ? 0 : (i >= B ? B - 1 : i);
+}
+
+// WHOSE tensors a kernel works on.  The lone forms: the arguments' own (TfgOwn: every pointer as the launch passed it).  The
+// POPULATION form (include/evac.h: evac_transformer_update_population): the learner is blockIdx.y and `a` holds learner 0's
+// pointers.  TfgArgs::blk[b] is indexed at run time, so `a` is never moved in place (a changed copy of it, or of one block's
+// pointers, would be a private one and go to scratch: DESIGN.md sections 4.18, 4.19): a block's tensor gets its learner's shift
+// WHERE IT IS NAMED, the stride read from the kernel-argument segment beside the pointer, and so do the fields that are no
+// arrays (TfgLearner's functions: scalar multiply-adds the compiler shares between uses).  Parameters and gradients by the tensors' strides; what lies in a learner's
+// workspace slice (dX, X1, g1, the partials, tickets and slots) by the slice; what the actor-critic's kernels read as ONE common
+// batch of S x M rows -- Y, the gathered columns and the index list -- by the learner's M rows.  The caller's batch (obs .. val)
+// is common and stays.  gridDim.x is the lone kernel's, so the ticket tests hold per learner.
+struct TfgLearnerStrides {
+    int64_t p[kTfgMaxBlocks][kTfgTensors], g[kTfgMaxBlocks][kTfgTensors];   // floats from learner s to s + 1: the blocks' parameters, gradients
+    int64_t w1a, w1c;                           // ... the actor's and the critic's first layer
+    int64_t hdr, ws;                            // bytes: the optimiser's header, the workspace slice
+    int64_t inds, stats;                        // elements of perms / stats_out per learner
+};
+// Both name every field they may shift through a function, so that the lone forms read the arguments where they always did.
+struct TfgOwn {
+    const TfgArgs& a;
+    __device__ __forceinline__ const float* w(const TfgBlock& B, int, int i) const { return B.w[i]; }
+    __device__ __forceinline__ float* g(const TfgBlock& B, int, int i) const { return B.g[i]; }
+    __device__ __forceinline__ const float* w1a() const { return a.w1a; }
+    __device__ __forceinline__ const float* w1c() const { return a.w1c; }
+    __device__ __forceinline__ const int64_t* inds() const { return a.inds; }
+    __device__ __forceinline__ float* Y() const { return a.Y; }
+    __device__ __forceinline__ float* dX() const { return a.dX; }
+    __device__ __forceinline__ float* X1() const { return a.X1; }
+    __device__ __forceinline__ float* act_g() const { return a.act_g; }
+    __device__ __forceinline__ float* lp_g() const { return a.lp_g; }
+    __device__ __forceinline__ float* adv_g() const { return a.adv_g; }
+    __device__ __forceinline__ float* ret_g() const { return a.ret_g; }
+    __device__ __forceinline__ float* val_g() const { return a.val_g; }
+    __device__ __forceinline__ int64_t* ident() const { return a.ident; }
+    __device__ __forceinline__ int64_t ident_of(int64_t m) const { return m; }
+    __device__ __forceinline__ const float* g1() const { return a.g1; }
+    __device__ __forceinline__ float* parts() const { return a.parts; }
+    __device__ __forceinline__ unsigned* tickets() const { return a.tickets; }
+    __device__ __forceinline__ float* slots() const { return a.slots; }
+    __device__ __forceinline__ float* stats() const { return a.stats; }
+};
+template <class T>
+__device__ __forceinline__ T* tfg_shift_bytes(T* p, int64_t bytes) { return (T*)((char*)p + bytes); }
+struct TfgLearner {
+    const TfgArgs& a;
+    const TfgLearnerStrides& q;
+    int64_t s;
+    __device__ __forceinline__ int64_t rows() const { return s * a.M; }
+    __device__ __forceinline__ int64_t slice() const { return s * q.ws; }
+    __device__ __forceinline__ const float* w(const TfgBlock& B, int b, int i) const { return B.w[i] + s * q.p[b][i]; }
+    __device__ __forceinline__ float* g(const TfgBlock& B, int b, int i) const { return B.g[i] + s * q.g[b][i]; }
+    __device__ __forceinline__ const float* w1a() const { return a.w1a + s * q.w1a; }
+    __device__ __forceinline__ const float* w1c() const { return a.w1c + s * q.w1c; }
+    __device__ __forceinline__ const int64_t* inds() const { return a.inds + s * q.inds; }
+    __device__ __forceinline__ float* Y() const { return a.Y + rows() * a.D; }
+    __device__ __forceinline__ float* dX() const { return tfg_shift_bytes(a.dX, slice()); }
+    __device__ __forceinline__ float* X1() const { return tfg_shift_bytes(a.X1, slice()); }
+    __device__ __forceinline__ float* act_g() const { return a.act_g + 2 * rows(); }
+    __device__ __forceinline__ float* lp_g() const { return a.lp_g + rows(); }
+    __device__ __forceinline__ float* adv_g() const { return a.adv_g + rows(); }
+    __device__ __forceinline__ float* ret_g() const { return a.ret_g + rows(); }
+    __device__ __forceinline__ float* val_g() const { return a.val_g + rows(); }
+    __device__ __forceinline__ int64_t* ident() const { return a.ident + rows(); }
+    __device__ __forceinline__ int64_t ident_of(int64_t m) const { return rows() + m; }   // the learner's rows in the common index list
+    __device__ __forceinline__ const float* g1() const { return tfg_shift_bytes(a.g1, slice()); }
+    __device__ __forceinline__ float* parts() const { return tfg_shift_bytes(a.parts, slice()); }
+    __device__ __forceinline__ unsigned* tickets() const { return tfg_shift_bytes(a.tickets, slice()); }
+    __device__ __forceinline__ float* slots() const { return tfg_shift_bytes(a.slots, slice()); }
+    __device__ __forceinline__ float* stats() const { return a.stats + s * q.stats; }
+};
+__device__ __forceinline__ TfgOwn tfg_whose(const TfgArgs& a) { return {a}; }
+__device__ __forceinline__ TfgOwn tfg_whose(const TfgArgs& a, const AdamHeader*) { return {a}; }
+__device__ __forceinline__ TfgLearner tfg_whose(const TfgArgs& a, const AdamHeader*, const TfgLearnerStrides& q) {
+    return {a, q, (int64_t)blockIdx.y};
+}
+// the stop gate: the header, the learner's in a population
+__device__ __forceinline__ const AdamHeader* tfg_gate(const AdamHeader* h) { return h; }
+__device__ __forceinline__ const AdamHeader* tfg_gate(const AdamHeader* h, const TfgLearnerStrides& q) {
+    return (const AdamHeader*)((const char*)h + (int64_t)blockIdx.y * q.hdr);
 }
 
 // A block's weights as the kernels read them (TransformerBlockSmem's layout: 8 640 bytes), every row zero-padded to 6 columns.
@@ -105,8 +185,9 @@ struct TfgBlockSmem {
     f4 vec[6][2];                      // dense_b, norm1_w, norm1_b, ff2_b, norm2_w, norm2_b
 };
 
-// by the whole workgroup of `step` threads, before a barrier: TransformerEncoder::stage for one block
-__device__ __forceinline__ void tfg_stage(const TfgBlock& B, TfgBlockSmem& t, int dm, int tid, int step) {
+// by the whole workgroup of `step` threads, before a barrier: TransformerEncoder::stage for block b, `who`'s tensors
+template <class Who>
+__device__ __forceinline__ void tfg_stage(const Who& who, const TfgBlock& B, int b, TfgBlockSmem& t, int dm, int tid, int step) {
     const float qscale = 1.44269504088896341f / sqrtf((float)dm);
     float* qkv = (float*)t.qkv;
     for (int idx = tid; idx < kTfgDm * 3 * kTfgHeads * 8; idx += step) {
@@ -114,8 +195,8 @@ __device__ __forceinline__ void tfg_stage(const TfgBlock& B, TfgBlockSmem& t, in
         float v = 0.0f;
         if (c < dm) {
             const int row = h * dm + c;
-            if (e < dm) v = B.w[2 * m][row * dm + e];
-            else if (e == 6) v = B.w[2 * m + 1][row];
+            if (e < dm) v = who.w(B, b, 2 * m)[row * dm + e];
+            else if (e == 6) v = who.w(B, b, 2 * m + 1)[row];
             if (m == 0) v *= qscale;
         }
         qkv[idx] = v;
@@ -123,24 +204,24 @@ __device__ __forceinline__ void tfg_stage(const TfgBlock& B, TfgBlockSmem& t, in
     float* dn = (float*)t.dn;
     for (int idx = tid; idx < kTfgDm * kTfgHeads * 8; idx += step) {
         const int e = idx & 7, r = idx >> 3, h = r % kTfgHeads, c = r / kTfgHeads;
-        dn[idx] = (c < dm && e < dm) ? B.w[6][e * (kTfgHeads * dm) + c * kTfgHeads + h] : 0.0f;
+        dn[idx] = (c < dm && e < dm) ? who.w(B, b, 6)[e * (kTfgHeads * dm) + c * kTfgHeads + h] : 0.0f;
     }
     float* ff = (float*)t.ff;
     for (int idx = tid; idx < kTfgFeedForward * 16; idx += step) {
         const int e = idx & 15, u = idx >> 4;
         float v = 0.0f;
         if (e < 8) {
-            if (e < dm) v = B.w[8][u * dm + e];
-            else if (e == 6) v = B.w[9][u];
+            if (e < dm) v = who.w(B, b, 8)[u * dm + e];
+            else if (e == 6) v = who.w(B, b, 9)[u];
         } else if (e - 8 < dm) {
-            v = B.w[10][(e - 8) * kTfgFeedForward + u];
+            v = who.w(B, b, 10)[(e - 8) * kTfgFeedForward + u];
         }
         ff[idx] = v;
     }
     float* vec = (float*)t.vec;
     for (int idx = tid; idx < 6 * 8; idx += step) {
         const int e = idx & 7, r = idx >> 3;
-        const float* src = B.w[r == 0 ? 7 : (r == 1 ? 12 : (r == 2 ? 13 : (r == 3 ? 11 : (r == 4 ? 14 : 15))))];
+        const float* src = who.w(B, b, r == 0 ? 7 : (r == 1 ? 12 : (r == 2 ? 13 : (r == 3 ? 11 : (r == 4 ? 14 : 15)))));
         vec[idx] = e < dm ? src[e] : 0.0f;
     }
 }
@@ -307,28 +388,29 @@ struct TfgEncodeWave {
 template <class... Gate>
 __global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_encode(TfgArgs a, Gate... gate) {
     if constexpr (sizeof...(Gate) != 0) {
-        if (rpo_stopped(gate...)) return;
+        if (rpo_stopped(tfg_gate(gate...))) return;
     }
+    const auto who = tfg_whose(a, gate...);
     __shared__ TfgBlockSmem ts[kTfgMaxBlocks];
     __shared__ TfgEncodeWave ws[kTfgEncodeWaves];
     const int tid = (int)threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int D = a.D, M = a.M, dm = a.dm, S = a.S, nb = a.nb;
     const bool resid = a.resid != 0;
-    if (blockIdx.x == 0 && tid < 16) a.tickets[tid] = 0u;
-    for (int b = 0; b < nb; ++b) tfg_stage(a.blk[b], ts[b], dm, tid, kTfgEncodeBlock);
+    if (blockIdx.x == 0 && tid < 16) who.tickets()[tid] = 0u;
+    for (int b = 0; b < nb; ++b) tfg_stage(who, a.blk[b], b, ts[b], dm, tid, kTfgEncodeBlock);
     __syncthreads();
     TfgEncodeWave& w = ws[wave];
 #pragma unroll 1
     for (int64_t m = (int64_t)blockIdx.x * kTfgEncodeWaves + wave; m < M; m += (int64_t)gridDim.x * kTfgEncodeWaves) {   // (M up to 2^31 - 1)
-        const int64_t idx = tfg_index(a, m);
+        const int64_t idx = tfg_index(who.inds(), a.B, m);
         tfg_load_row(a.obs + (size_t)idx * (size_t)D, w.x, lane, S, dm);
-        if (lane < 2) a.act_g[2 * (size_t)m + lane] = a.actions[2 * (size_t)idx + lane];
-        else if (lane == 2) a.lp_g[m] = a.logprobs[idx];
-        else if (lane == 3) a.adv_g[m] = a.adv[idx];
-        else if (lane == 4) a.ret_g[m] = a.ret[idx];
-        else if (lane == 5) a.val_g[m] = a.val[idx];
-        else if (lane == 6) a.ident[m] = (int64_t)m;
+        if (lane < 2) who.act_g()[2 * (size_t)m + lane] = a.actions[2 * (size_t)idx + lane];
+        else if (lane == 2) who.lp_g()[m] = a.logprobs[idx];
+        else if (lane == 3) who.adv_g()[m] = a.adv[idx];
+        else if (lane == 4) who.ret_g()[m] = a.ret[idx];
+        else if (lane == 5) who.val_g()[m] = a.val[idx];
+        else if (lane == 6) who.ident()[m] = who.ident_of((int64_t)m);
         wave_sync();
         float out[kTfgDm];
         TfgKept kept;
@@ -336,14 +418,14 @@ __global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_encode(TfgArgs a, Gate..
         for (int b = 0; b < nb; ++b) {
             tfg_forward<false>(ts[b], w.x, w.kv, nullptr, nullptr, lane, S, dm, resid, out, kept);
             if (b + 1 < nb) {
-                tfg_store_row(a.X1 + (size_t)m * (size_t)D, out, lane, S, dm);
+                tfg_store_row(who.X1() + (size_t)m * (size_t)D, out, lane, S, dm);
                 wave_sync();
 #pragma unroll
                 for (int c = 0; c < kTfgDm; ++c) w.x[lane][c] = (lane < S && c < dm) ? out[c] : 0.0f;
                 wave_sync();
             }
         }
-        tfg_store_row(a.Y + (size_t)m * (size_t)D, out, lane, S, dm);
+        tfg_store_row(who.Y() + (size_t)m * (size_t)D, out, lane, S, dm);
         wave_sync();
     }
 }
@@ -352,8 +434,9 @@ __global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_encode(TfgArgs a, Gate..
 template <class... Gate>
 __global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_dy(TfgArgs a, Gate... gate) {
     if constexpr (sizeof...(Gate) != 0) {
-        if (rpo_stopped(gate...)) return;
+        if (rpo_stopped(tfg_gate(gate...))) return;
     }
+    const auto who = tfg_whose(a, gate...);
     constexpr int H1 = kTrainHidden;
     __shared__ __attribute__((aligned(16))) float gs[2 * H1][kTfgTile];        // g1 of the tile's samples: [net, unit][sample]
     const int tid = (int)threadIdx.x;
@@ -365,7 +448,7 @@ __global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_dy(TfgArgs a, Gate... ga
         for (int i = tid; i < 2 * H1 * kTfgTile; i += kTfgEncodeBlock) {
             const int q = i / (2 * H1), r = i - q * (2 * H1);
             const int net = r / H1, k = r - net * H1;
-            gs[r][q] = q < nq ? a.g1[((size_t)net * (size_t)M + (size_t)(m0 + q)) * H1 + k] : 0.0f;
+            gs[r][q] = q < nq ? who.g1()[((size_t)net * (size_t)M + (size_t)(m0 + q)) * H1 + k] : 0.0f;
         }
         __syncthreads();
 #pragma unroll 1
@@ -375,7 +458,7 @@ __global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_dy(TfgArgs a, Gate... ga
             for (int q = 0; q < kTfgTile; ++q) acc[q] = 0.0f;
 #pragma unroll 1
             for (int net = 0; net < 2; ++net) {
-                const float* __restrict__ w1 = (net == 0 ? a.w1a : a.w1c) + j;
+                const float* __restrict__ w1 = (net == 0 ? who.w1a() : who.w1c()) + j;
 #pragma unroll 8
                 for (int k = 0; k < H1; ++k) {
                     const float w = w1[(size_t)k * (size_t)D];
@@ -386,7 +469,7 @@ __global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_dy(TfgArgs a, Gate... ga
             }
 #pragma unroll
             for (int q = 0; q < kTfgTile; ++q)
-                if (q < nq) a.dX[(size_t)(m0 + q) * (size_t)D + j] = acc[q];
+                if (q < nq) who.dX()[(size_t)(m0 + q) * (size_t)D + j] = acc[q];
         }
         __syncthreads();
     }
@@ -419,15 +502,16 @@ __device__ __forceinline__ void tfg_add_sums6(float* acc, const float (&v)[kTfgD
 template <class... Gate>
 __global__ __launch_bounds__(kTfgBlock) void k_tf_backward(TfgArgs a, int b, Gate... gate) {
     if constexpr (sizeof...(Gate) != 0) {
-        if (rpo_stopped(gate...)) return;
+        if (rpo_stopped(tfg_gate(gate...))) return;
     }
+    const auto who = tfg_whose(a, gate...);
     __shared__ TfgBlockSmem t;
     __shared__ TfgWave wv[kTfgWaves];
     const int tid = (int)threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int D = a.D, M = a.M, dm = a.dm, S = a.S;
     const bool resid = a.resid != 0, valid = lane < S;
-    tfg_stage(a.blk[b], t, dm, tid, kTfgBlock);
+    tfg_stage(who, a.blk[b], b, t, dm, tid, kTfgBlock);
     TfgWave& w = wv[wave];
     for (int e = lane; e < kTfgPart; e += 64) w.acc[e] = 0.0f;
     __syncthreads();
@@ -438,8 +522,8 @@ __global__ __launch_bounds__(kTfgBlock) void k_tf_backward(TfgArgs a, int b, Gat
 #pragma unroll 1
     for (int64_t m = m_begin + wave; m < m_end; m += kTfgWaves) {
         // the block's input and the gradient of its output, this token's
-        const float* __restrict__ xin = b == 0 ? a.obs + (size_t)tfg_index(a, m) * (size_t)D : a.X1 + (size_t)m * (size_t)D;
-        float* __restrict__ dxr = a.dX + (size_t)m * (size_t)D;
+        const float* __restrict__ xin = b == 0 ? a.obs + (size_t)tfg_index(who.inds(), a.B, m) * (size_t)D : who.X1() + (size_t)m * (size_t)D;
+        float* __restrict__ dxr = who.dX() + (size_t)m * (size_t)D;
         tfg_load_row(xin, w.x, lane, S, dm);
         float dout[kTfgDm];
 #pragma unroll
@@ -659,7 +743,7 @@ __global__ __launch_bounds__(kTfgBlock) void k_tf_backward(TfgArgs a, int b, Gat
     }
     // the workgroup's partial: per entry the waves in wave order
     __syncthreads();
-    float* part = a.parts + ((size_t)b * (size_t)a.P + (size_t)blockIdx.x) * kTfgPart;
+    float* part = who.parts() + ((size_t)b * (size_t)a.P + (size_t)blockIdx.x) * kTfgPart;
     for (int e = tid; e < kTfgPart; e += kTfgBlock) {
         float s = 0.0f;
 #pragma unroll
@@ -704,8 +788,9 @@ __device__ __forceinline__ int tfg_entry(int e, int dm, int& off) {
 template <class... Gate>
 __global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_finish(TfgArgs a, Gate... gate) {
     if constexpr (sizeof...(Gate) != 0) {
-        if (rpo_stopped(gate...)) return;
+        if (rpo_stopped(tfg_gate(gate...))) return;
     }
+    const auto who = tfg_whose(a, gate...);
     __shared__ float buf[kTfgEncodeBlock];
     __shared__ float fin[kTfgMaxBlocks * kTfgFinishWgs];
     __shared__ int last;
@@ -718,11 +803,11 @@ __global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_finish(TfgArgs a, Gate..
         int off = 0;
         const int tensor = tfg_entry(e, dm, off);
         if (tensor >= 0) {                                          // the partials of k_tf_backward in workgroup order
-            const float* src = a.parts + (size_t)b * (size_t)P * kTfgPart + e;
+            const float* src = who.parts() + (size_t)b * (size_t)P * kTfgPart + e;
             float s = 0.0f;
 #pragma unroll 8
             for (int p = 0; p < P; ++p) s += src[(size_t)p * kTfgPart];
-            a.blk[b].g[tensor][off] = s;
+            who.g(a.blk[b], b, tensor)[off] = s;
             sq = s * s;
         }
     }
@@ -734,21 +819,21 @@ __global__ __launch_bounds__(kTfgEncodeBlock) void k_tf_finish(TfgArgs a, Gate..
         if (tid < s) buf[tid] += buf[tid + s];
         __syncthreads();
     }
-    if (tid == 0) a.slots[blockIdx.x] = buf[0];
+    if (tid == 0) who.slots()[blockIdx.x] = buf[0];
     __threadfence();                           // (release: every thread's stores, before the workgroup takes its ticket)
     __syncthreads();
-    if (tid == 0) last = atomicAdd(a.tickets, 1u) == gridDim.x - 1u;
+    if (tid == 0) last = atomicAdd(who.tickets(), 1u) == gridDim.x - 1u;
     __syncthreads();
     if (!last) return;
     __threadfence();
     // the last workgroup to finish: the encoder's sum of squares joins the 13 tensors' (k_rpo_finish wrote stats[7] before this launch)
-    if (tid < kTfgMaxBlocks * kTfgFinishWgs) fin[tid] = tid < (int)gridDim.x ? a.slots[tid] : 0.0f;
+    if (tid < kTfgMaxBlocks * kTfgFinishWgs) fin[tid] = tid < (int)gridDim.x ? who.slots()[tid] : 0.0f;
     __syncthreads();
     if (tid == 0) {
         float s = 0.0f;
 #pragma unroll
         for (int i = 0; i < kTfgMaxBlocks * kTfgFinishWgs; ++i) s += fin[i];
-        a.stats[7] = a.stats[7] + s;
+        who.stats()[7] = who.stats()[7] + s;
     }
 }
 

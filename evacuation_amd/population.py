@@ -22,9 +22,12 @@ update is a chain of small launches on a nearly idle chip; here learner s rides 
 * ``TransformerPopulation``: the transformer leader's 13 + 16 per block stacked tensors, ``nets[s]`` a ``TransformerActorCritic``
   of views.  What runs such learners ON A HANDLE'S ENVS takes one -- ``policy_rollout_population``
   (``evac_policy_rollout_population_transformer``), ``policy_evaluate_population`` and ``PopulationEvaluator``
-  (``evac_policy_evaluate_population_transformer``).  Their UPDATE is not built: ``PopulationAdam`` and ``PopulationTrainer``
-  refuse one, and each learner trains alone (``RPOTrainer(grad_fn=transformer_kernel_grad, optimizer="device_transformer")``
-  on ``nets[s]``).
+  (``evac_policy_evaluate_population_transformer``).  Their UPDATE is opt-in under names of its own, as ``TransformerAdam``
+  stands beside ``DeviceAdam``: ``TransformerPopulationAdam`` (the 29 or 45 stacks of moments, ``learners[s]`` a
+  ``TransformerAdam`` on row s), ``transformer_update_population`` (``evac_transformer_update_population``: 6 + num_blocks +
+  norm_adv launches per minibatch step, as for one such learner) and ``PopulationTrainer(..., optimizer="device_transformer")``,
+  under ONE configuration.  The default faces -- ``PopulationAdam(population)`` and ``PopulationTrainer(env, population, cfg)``
+  -- keep refusing one; sweeps of such learners are not built.
 * Sweeps: every float-valued hyperparameter (``SWEEP_FIELDS``) may differ per learner -- ``PopulationTrainer(env, population,
   [cfg_0, .., cfg_S-1])``, ``rpo_update_population(cfg=[...])``, ``gae(gamma=[...])``, ``policy_rollout_population(gammas=[...])``;
   ``sweep_configs`` makes the cartesian product.  The learners' values ride in the kernel arguments beside their seeds
@@ -47,10 +50,10 @@ from torch import nn
 
 from . import _lib
 from .policy import (HIDDEN, SET_HIDDEN, DeepSetsActorCritic, LinearActorCritic, TransformerActorCritic, _check_encoder,
-                     _check_structure, _check_transformer, _transformer_struct, all_tensors, mlp_tensors, refuse_deepsets,
-                     refuse_transformer)
-from .trainer import (BATCH_KEYS, DeviceAdam, RPOTrainingConfig, _f32, _loss_config, _stream, _u64, decode_header, flatten_batch, gae,
-                      update_steps)
+                     _check_structure, _check_transformer, _transformer_grads, _transformer_struct, all_tensors, mlp_tensors,
+                     refuse_deepsets, refuse_dropout, refuse_transformer)
+from .trainer import (BATCH_KEYS, DeviceAdam, RPOTrainingConfig, TransformerAdam, _f32, _loss_config, _stream, _u64, decode_header,
+                      flatten_batch, gae, update_steps)
 from .vector_env import STATS_FIELDS, _ptr
 
 MAX_LEARNERS = _lib.MAX_LEARNERS
@@ -220,13 +223,16 @@ class TransformerPopulation:
     ``policy_evaluate``, ``PolicyEvaluator`` and ``TransformerAdam`` take a learner as they take any such network.  ``strides``
     / ``encoder_strides``: a learner's distance in each of the 13 / of the blocks' 16.  The blocks' number, the token width and
     ``use_resid`` are one value per population.  The entries that run the learners on a handle's envs take the object
-    (``policy_rollout_population``, ``policy_evaluate_population``, ``PopulationEvaluator``); the learners' update is not
-    built (``UPDATE_NOT_BUILT``)."""
+    (``policy_rollout_population``, ``policy_evaluate_population``, ``PopulationEvaluator``); the learners' update in one set
+    of launches is opt-in (``TransformerPopulationAdam``, ``transformer_update_population``,
+    ``PopulationTrainer(..., optimizer="device_transformer")``): the default faces refuse one with ``UPDATE_NOT_BUILT``."""
 
-    UPDATE_NOT_BUILT = ("the update of transformer learners is not built (the gradient, clip and Adam of a TransformerPopulation in "
-                        "one set of launches); what takes one is policy_rollout_population, policy_evaluate_population and "
-                        "PopulationEvaluator, and each learner trains alone with RPOTrainer(grad_fn=transformer_kernel_grad, "
-                        "optimizer=\"device_transformer\") on nets[s]")
+    UPDATE_NOT_BUILT = ("the update of transformer learners is not built into PopulationAdam(population) and "
+                        "PopulationTrainer(env, population, cfg): these two default faces do not take a TransformerPopulation.  Its "
+                        "gradient, clip and Adam in one set of launches are opt-in: TransformerPopulationAdam, "
+                        "transformer_update_population and PopulationTrainer(..., optimizer=\"device_transformer\"); what else takes one "
+                        "is policy_rollout_population, policy_evaluate_population and PopulationEvaluator, and a learner trains alone "
+                        "with RPOTrainer(grad_fn=transformer_kernel_grad, optimizer=\"device_transformer\") on nets[s]")
 
     def __init__(self, obs_dim: int, number_of_pedestrians: int, seeds: Sequence[int], device="cuda:0", num_blocks: int = 2,
                  use_resid: bool = False):
@@ -278,23 +284,29 @@ class PopulationAdam:
     ``max_grad_norm`` (one value or a sequence of S) may differ per learner, the betas and eps are one value for all.
     ``param_groups[s]`` is learner s's group; ``state_dict(s)`` / ``load_state_dict(s, sd)`` are its, in ``DeviceAdam``'s
     format, and touch no other learner.  For a ``DeepSetsPopulation`` the stacks are its 19 and ``learners[s]`` a ``DeviceAdam``
-    over all 19 tensors of row s.  A ``TransformerPopulation`` is a ``ValueError``: its update is not built."""
+    over all 19 tensors of row s.  A ``TransformerPopulation`` is a ``ValueError``: its optimiser is
+    ``TransformerPopulationAdam``."""
 
     def __init__(self, population, lr=3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm=0.5):
         if isinstance(population, TransformerPopulation):
             raise ValueError(f"PopulationAdam: {TransformerPopulation.UPDATE_NOT_BUILT}")
+        self._setup(population, lr, betas, eps, max_grad_norm, DeviceAdam)
+
+    def _setup(self, population, lr, betas, eps, max_grad_norm, make) -> None:
+        """The constructor's body; ``make``: the learners' optimiser (``DeviceAdam``, ``TransformerAdam``)."""
         self.population = population
         S, dev = population.num_learners, population.device
         lrs, norms = _per_learner(lr, S, "lr"), _per_learner(max_grad_norm, S, "max_grad_norm")
         self.headers = torch.zeros(S, 8, dtype=torch.int64, device=dev)
         self.exp_avg = [torch.zeros_like(t) for t in population.tensors]
         self.exp_avg_sq = [torch.zeros_like(t) for t in population.tensors]
-        self.learners = [DeviceAdam(net, lr=lrs[s], betas=betas, eps=eps, max_grad_norm=norms[s],
-                                    storage=(self.headers[s], [m[s] for m in self.exp_avg], [v[s] for v in self.exp_avg_sq]))
+        self.learners = [make(net, lr=lrs[s], betas=betas, eps=eps, max_grad_norm=norms[s],
+                              storage=(self.headers[s], [m[s] for m in self.exp_avg], [v[s] for v in self.exp_avg_sq]))
                          for s, net in enumerate(population.nets)]
         self.header_stride_bytes = 64
         self.moment_strides = population.strides
-        self.encoder_moment_strides = population.encoder_strides if isinstance(population, DeepSetsPopulation) else None
+        self.encoder_moment_strides = (population.encoder_strides
+                                       if isinstance(population, (DeepSetsPopulation, TransformerPopulation)) else None)
 
     @property
     def param_groups(self) -> List[dict]:
@@ -332,6 +344,19 @@ class PopulationAdam:
         self.learners[learner].load_state_dict(sd)
 
 
+class TransformerPopulationAdam(PopulationAdam):
+    """``PopulationAdam`` for a ``TransformerPopulation``: the same interface and body over its 13 + 16 per block stacks (29 or
+    45), ``learners[s]`` a ``TransformerAdam`` whose state is row s, ``encoder_moment_strides`` the population's
+    ``encoder_strides``.  A class of its own because ``PopulationAdam(population)`` stays a ``ValueError`` for such a
+    population.  Anything but a ``TransformerPopulation`` is a ``ValueError``."""
+
+    def __init__(self, population, lr=3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm=0.5):
+        if not isinstance(population, TransformerPopulation):
+            raise ValueError(f"TransformerPopulationAdam: a TransformerPopulation is expected, got {type(population).__name__} "
+                             "(a PolicyPopulation's or DeepSetsPopulation's optimiser is PopulationAdam)")
+        self._setup(population, lr, betas, eps, max_grad_norm, TransformerAdam)
+
+
 def _batch_ptrs(batch: Dict[str, torch.Tensor]):
     b_obs = batch["b_obs"]
     B, D = b_obs.shape
@@ -342,9 +367,13 @@ def _batch_ptrs(batch: Dict[str, torch.Tensor]):
     return int(B), int(D), [int(B)] + [_ptr(batch[k]) for k in BATCH_KEYS]
 
 
-def population_workspace_bytes(obs_dim: int, minibatch_size: int, num_learners: int, *, deepsets: bool = False) -> int:
-    """The update's workspace for a ``PolicyPopulation``, or with ``deepsets`` for a ``DeepSetsPopulation``."""
-    sizer = f"evac_{'deepsets' if deepsets else 'rpo'}_population_workspace_bytes"
+def population_workspace_bytes(obs_dim: int, minibatch_size: int, num_learners: int, *, deepsets: bool = False,
+                               transformer: bool = False) -> int:
+    """The update's workspace for a ``PolicyPopulation``, or with ``deepsets`` for a ``DeepSetsPopulation``, or with
+    ``transformer`` for a ``TransformerPopulation`` (both at once is a ``ValueError``)."""
+    if deepsets and transformer:
+        raise ValueError("population_workspace_bytes: deepsets and transformer name two kinds of population")
+    sizer = f"evac_{'transformer' if transformer else 'deepsets' if deepsets else 'rpo'}_population_workspace_bytes"
     need = int(getattr(_lib.load(), sizer)(int(obs_dim), int(minibatch_size), int(num_learners)))
     if need < 0:
         raise _lib.EvacError(need, f"{sizer}({obs_dim}, {minibatch_size}, {num_learners})")
@@ -405,9 +434,36 @@ def deepsets_update_population(population: DeepSetsPopulation, batch: Dict[str, 
                               "deepsets_update_population")
 
 
+def transformer_update_population(population: TransformerPopulation, batch: Dict[str, torch.Tensor], rows: torch.Tensor, cfg,
+                                  opt: TransformerPopulationAdam, *, minibatch_size: Optional[int] = None,
+                                  rpo_noise: Optional[torch.Tensor] = None, seeds: Optional[Sequence[int]] = None,
+                                  first_draw_counters: Optional[Sequence[int]] = None, stats: Optional[torch.Tensor] = None,
+                                  workspace: Optional[torch.Tensor] = None):
+    """``transformer_update`` for every learner of a ``TransformerPopulation`` in one host call
+    (``evac_transformer_update_population``): ``deepsets_update_population``'s arguments and returns, with ONE configuration --
+    learner s is, bit for bit, ``transformer_update(population.nets[s], its own rows, cfg, TransformerAdam(nets[s]),
+    seed=seeds[s], first_draw_counter=first_draw_counters[s])`` alone.  ``6 + num_blocks`` launches per minibatch step and one
+    more with ``norm_adv``, no host synchronisation.  A sequence of configurations, or an optimiser whose learners differ in
+    ``lr`` / ``max_grad_norm``, is a ``ValueError``: sweeps of transformer learners are not built."""
+    if not isinstance(population, TransformerPopulation):
+        raise ValueError("transformer_update_population: a TransformerPopulation is expected (a PolicyPopulation's update is "
+                         "rpo_update_population, a DeepSetsPopulation's deepsets_update_population)")
+    if not isinstance(opt, TransformerPopulationAdam):
+        raise ValueError(f"transformer_update_population: a TransformerPopulationAdam is expected, got {type(opt).__name__}")
+    if isinstance(cfg, (list, tuple)) or not opt.uniform():
+        raise ValueError("transformer_update_population: sweeps of transformer learners are not built: one configuration, and one "
+                         "lr / max_grad_norm, for all learners")
+    for net in population.nets:
+        refuse_dropout(net, "transformer_update_population")
+    return _update_population(population, batch, rows, cfg, opt, minibatch_size, rpo_noise, seeds, first_draw_counters, stats, workspace,
+                              "transformer_update_population")
+
+
 def _update_population(population, batch, rows, cfg, opt, minibatch_size, rpo_noise, seeds, first_draw_counters, stats, workspace, what):
-    """The body of ``rpo_update_population`` and ``deepsets_update_population`` (``what``: the caller's name)."""
+    """The body of ``rpo_update_population``, ``deepsets_update_population`` and ``transformer_update_population`` (``what``: the
+    caller's name)."""
     deepsets = isinstance(population, DeepSetsPopulation)
+    transformer = isinstance(population, TransformerPopulation)
     if opt.population is not population:
         raise ValueError("the PopulationAdam was made for another population")
     S, dev = population.num_learners, population.device
@@ -440,7 +496,7 @@ def _update_population(population, batch, rows, cfg, opt, minibatch_size, rpo_no
         stats = torch.zeros(S, steps, 8, dtype=torch.float32, device=dev)
     else:
         _f32(stats, (S, steps, 8), "stats")
-    need = population_workspace_bytes(D, M, S, deepsets=deepsets)
+    need = population_workspace_bytes(D, M, S, deepsets=deepsets, transformer=transformer)
     if workspace is None or workspace.numel() < need or workspace.device != dev:
         workspace = torch.empty(need, dtype=torch.uint8, device=dev)
     seeds = population.seeds if seeds is None else [int(x) for x in seeds]
@@ -458,11 +514,13 @@ def _update_population(population, batch, rows, cfg, opt, minibatch_size, rpo_no
     rest = [opt.header_stride_bytes, C.byref(lc), C.byref(oc), C.byref(opt.learners[0].state_struct()), *b_args,
             B_l, M, n_epochs, _ptr(rows), _ptr(rpo_noise), u64(*(_u64(x) for x in seeds)), u64(*(_u64(x) for x in counters))]
     tail = [_ptr(stats), _ptr(workspace), _stream(dev)]
-    if deepsets:                              # (every struct of the 13 followed by the encoder's six's)
-        enc_params = _lib.EvacDeepSetsGrads(*(t.data_ptr() for t in population.tensors[13:]))
-        enc_grads = _lib.EvacDeepSetsGrads(*(g.data_ptr() for g in population.grads[13:]))
+    if deepsets or transformer:               # (every struct of the 13 followed by the encoder's)
+        enc_struct = _transformer_grads if transformer else _lib.EvacDeepSetsGrads
+        enc_params = enc_struct(*(t.data_ptr() for t in population.tensors[13:]))
+        enc_grads = enc_struct(*(g.data_ptr() for g in population.grads[13:]))
         es = population.encoder_strides
-        rc = _lib.load().evac_deepsets_update_population(
+        entry = _lib.load().evac_transformer_update_population if transformer else _lib.load().evac_deepsets_update_population
+        rc = entry(
             S, C.byref(pol), C.byref(population.encoder_struct()), C.byref(params), C.byref(enc_params), C.byref(grads), C.byref(enc_grads),
             C.byref(population.strides), C.byref(es), C.byref(population.strides), C.byref(es), C.byref(opt.moment_strides),
             C.byref(opt.encoder_moment_strides), *rest, int(target_kl is not None), float(target_kl or 0.0), *tail)
@@ -489,21 +547,35 @@ class PopulationTrainer:
     normaliser runs with its own gamma (whatever the env was wrapped with) and its advantages, loss, clip and ``target_kl`` are
     its own.  ``update()``: anneal, one collection launch, one ``gae``, the permutations, one ``rpo_update_population``, ONE host
     transfer; returns a list of S logs with ``RPOTrainer.update()``'s keys, ``learning_rate`` the learner's own and ``config``
-    its fields that differ from learner 0's.  A ``TransformerPopulation`` is a ``ValueError``: its update is not built."""
+    its fields that differ from learner 0's.  A ``TransformerPopulation`` is a ``ValueError`` by default; with
+    ``optimizer="device_transformer"`` it trains as a ``DeepSetsPopulation`` does, under ONE configuration (learner s is then
+    ``RPOTrainer(grad_fn=transformer_kernel_grad, optimizer="device_transformer", one_call=True)`` alone; ``self.optimizer`` is a
+    ``TransformerPopulationAdam``, the update ``transformer_update_population``; a dropout probability other than 0 in any
+    learner is a ``ValueError``).  That value with any other population is a ``ValueError``."""
 
-    def __init__(self, env, population, cfgs):
+    def __init__(self, env, population, cfgs, *, optimizer: Optional[str] = None):
+        if optimizer not in (None, "device_transformer"):
+            raise ValueError(f"PopulationTrainer: optimizer = {optimizer!r}: expected None or \"device_transformer\"")
         refuse_deepsets(population, "PopulationTrainer")       # (a network where the population goes)
-        if isinstance(population, TransformerPopulation):
+        self.transformer = isinstance(population, TransformerPopulation)
+        if self.transformer and optimizer is None:
             raise ValueError(f"PopulationTrainer: {TransformerPopulation.UPDATE_NOT_BUILT}")
+        if optimizer is not None and not self.transformer:
+            raise ValueError("PopulationTrainer(optimizer=\"device_transformer\") trains a TransformerPopulation; "
+                             f"got {type(population).__name__}")
         self.deepsets = isinstance(population, DeepSetsPopulation)
         for net in getattr(population, "nets", ()):
-            (refuse_transformer if self.deepsets else refuse_deepsets)(net, "PopulationTrainer")
+            if self.transformer:
+                refuse_dropout(net, "PopulationTrainer")
+            else:
+                (refuse_transformer if self.deepsets else refuse_deepsets)(net, "PopulationTrainer")
         S = population.num_learners
-        if self.deepsets and isinstance(cfgs, (list, tuple)):
+        if (self.deepsets or self.transformer) and isinstance(cfgs, (list, tuple)):
             if len(cfgs) != S:
                 raise ValueError(f"PopulationTrainer: {len(cfgs)} configurations for {S} learners")
             if any(dataclasses.replace(c, seed=cfgs[0].seed) != cfgs[0] for c in cfgs):
-                raise ValueError("PopulationTrainer: sweeps of deep-sets learners are not built: a DeepSetsPopulation trains under "
+                kind = "transformer learners" if self.transformer else "deep-sets learners"
+                raise ValueError(f"PopulationTrainer: sweeps of {kind} are not built: a {type(population).__name__} trains under "
                                  "ONE configuration")
             cfgs = cfgs[0]
         self.sweep = isinstance(cfgs, (list, tuple))
@@ -523,7 +595,8 @@ class PopulationTrainer:
         self.env, self.population, self.cfg = env, population, cfg
         self.nets, self.device = population.nets, population.device
         self.num_learners, self.envs_per_learner = S, int(cfg.num_envs)
-        self.optimizer = PopulationAdam(population, lr=[c.learning_rate for c in self.cfgs], eps=1e-5,
+        make_optimizer = TransformerPopulationAdam if self.transformer else PopulationAdam
+        self.optimizer = make_optimizer(population, lr=[c.learning_rate for c in self.cfgs], eps=1e-5,
                                         max_grad_norm=[c.max_grad_norm for c in self.cfgs])
         self.generators = []
         for seed in population.seeds:
@@ -583,10 +656,12 @@ class PopulationTrainer:
         steps = cfg.update_epochs * len(update_steps(B_l, cfg.minibatch_size, cfg.norm_adv))
         if self.stats_rows is None or self.stats_rows.shape[1] != steps:
             self.stats_rows = torch.zeros(S, steps, 8, dtype=torch.float32, device=self.device)
-        need = population_workspace_bytes(self.population.obs_dim, min(cfg.minibatch_size, B_l), S, deepsets=self.deepsets)
+        need = population_workspace_bytes(self.population.obs_dim, min(cfg.minibatch_size, B_l), S, deepsets=self.deepsets,
+                                          transformer=self.transformer)
         if self.workspace is None or self.workspace.numel() < need:
             self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        update = deepsets_update_population if self.deepsets else rpo_update_population
+        update = (transformer_update_population if self.transformer else
+                  deepsets_update_population if self.deepsets else rpo_update_population)
         stats, headers = update(self.population, batch, rows, self.cfgs if self.sweep else cfg, self.optimizer,
                                 first_draw_counters=self.minibatch_steps, stats=self.stats_rows, workspace=self.workspace)
         self.update_index += 1
@@ -652,7 +727,8 @@ class PopulationTrainer:
         """``RPOTrainer.evaluate`` for every learner in ONE set of launches on the population evaluator, each with its own rows
         of the training env's observation statistics (frozen copies).  Returns S ``EvaluationResult``s, bit for bit those of
         ``make_evaluator().evaluate(nets[s], ...)`` learner by learner.  A ``DeepSetsPopulation`` likewise
-        (``evac_policy_evaluate_population_deepsets``)."""
+        (``evac_policy_evaluate_population_deepsets``), and a ``TransformerPopulation``
+        (``evac_policy_evaluate_population_transformer``)."""
         S, E_l = self.num_learners, self.envs_per_learner
         ev = self.make_population_evaluator(num_envs)
         kw = {}

@@ -476,11 +476,19 @@ class TransformerAdam(DeviceAdam):
     ``param_groups``, ``config``, the structs, ``read_header``, ``step_count``, ``state_dict`` / ``load_state_dict`` in torch's
     format.  A class of its own because ``DeviceAdam(net)`` stays a ``ValueError`` for such a network."""
 
-    def __init__(self, net, lr: float = 3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm: float = 0.5):
+    def __init__(self, net, lr: float = 3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm: float = 0.5,
+                 *, storage=None):
+        """``storage`` = (header, exp_avg, exp_avg_sq), as ``DeviceAdam`` takes it: the state lives in the caller's tensors
+        (``TransformerPopulationAdam``'s rows), as many moments of each kind as the network has tensors (29 or 45) -- any other
+        count is a ``ValueError``."""
         if not is_transformer(net):
             raise ValueError("TransformerAdam: the network has no attention encoder (`embedding`); its optimiser is DeviceAdam")
         refuse_dropout(net, "TransformerAdam")
-        self._setup(net, lr, betas, eps, max_grad_norm)
+        count = len(all_tensors(net))
+        if storage is not None and (len(storage) != 3 or len(storage[1]) != count or len(storage[2]) != count):
+            raise ValueError(f"TransformerAdam: `storage` is (header, {count} exp_avg, {count} exp_avg_sq) for this network's 13 + 16 per "
+                             "block tensors (a TransformerPopulation's row)")
+        self._setup(net, lr, betas, eps, max_grad_norm, storage)
         self.num_blocks = (len(self.params) - 13) // 16
 
     def _encoder_sizes(self) -> tuple:

@@ -30,8 +30,11 @@ collection and evaluation on the device (``evac_policy_rollout_transformer`` / `
 eval-mode function: dropout 0), the gradient of its 13 + 16 per block tensors by torch autograd or, with ``--gradient device``,
 by ``evac_transformer_minibatch_grad`` (``trainer.transformer_kernel_grad``), and torch's Adam -- or, with ``--gradient device
 --optimizer device``, the library's clip + Adam over all its tensors (``RPOTrainer(optimizer="device_transformer")``:
-``TransformerAdam``), the whole update in one host call (``evac_transformer_update``: 6 + blocks + 1 launches per step).  Not
-with ``--seeds``, ``--sweep`` or ``--compare``, nor with ``--optimizer device`` under the autograd gradient.
+``TransformerAdam``), the whole update in one host call (``evac_transformer_update``: 6 + blocks + 1 launches per step).  With
+``--gradient device --optimizer device --seeds`` the learners train as a population of such networks
+(``population.TransformerPopulation``, ``PopulationTrainer(..., optimizer="device_transformer")``,
+``evac_transformer_update_population``: the same launches per step for all learners); ``--seeds`` with any other gradient /
+optimiser choice is refused.  Not with ``--sweep`` or ``--compare``, nor with ``--optimizer device`` under the autograd gradient.
 
 ``--eval-every K`` evaluates the leader every K updates (``RPOTrainer.evaluate``: whole episodes, the mean action, the observation
 statistics frozen) and prints the summary; ``--baseline`` prints the same line for the reference's scripted sweep baseline
@@ -127,7 +130,8 @@ def parse_sweep(specs):
 
 
 def make_population_trainer(args, seeds, grid=None):
-    from evacuation_amd.population import DeepSetsPopulation, PolicyPopulation, PopulationTrainer, sweep_configs
+    from evacuation_amd.population import (DeepSetsPopulation, PolicyPopulation, PopulationTrainer, TransformerPopulation,
+                                           sweep_configs)
     cfg = RPOTrainingConfig(num_envs=args.envs, num_steps=args.steps, total_timesteps=args.envs * args.steps * max(args.updates, 1),
                             num_minibatches=args.minibatches, update_epochs=args.epochs)
     cfgs = cfg
@@ -136,6 +140,12 @@ def make_population_trainer(args, seeds, grid=None):
                                           ea.EnvWrappersConfig(positions="rel", statuses="ohe", type="Box"),
                                           num_envs=args.envs * len(seeds), gamma=cfg.gamma, seed=1)
         return PopulationTrainer(env, DeepSetsPopulation(env.obs_dim, args.pedestrians, seeds, DEV), cfgs)
+    if getattr(args, "network", "linear") == "transformer":      # a population of attention-encoder networks (main: device + device)
+        env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=args.pedestrians, is_new_exiting_reward=True),
+                                          ea.EnvWrappersConfig(positions="rel", statuses="ohe", type="Box"),
+                                          num_envs=args.envs * len(seeds), gamma=cfg.gamma, seed=1)
+        population = TransformerPopulation(env.obs_dim, args.pedestrians, seeds, DEV, num_blocks=args.blocks, use_resid=args.use_resid)
+        return PopulationTrainer(env, population, cfgs, optimizer="device_transformer")
     if grid is not None:                                         # one learner per (setting, seed)
         pairs = sweep_configs(cfg, grid, seeds)
         seeds, cfgs = [s for s, _ in pairs], [c for _, c in pairs]
@@ -314,11 +324,12 @@ def main():
         raise SystemExit("--network deep_sets: the gradient and optimiser kernels (--optimizer device, --compare) are "
                          "the linear network's; its gradient is autograd's or --gradient device, and --optimizer device goes with "
                          "--gradient device")
-    if args.network == "transformer" and (args.compare or args.seeds or args.sweep or
+    tf_population = args.seeds and args.gradient == "device" and args.optimizer == "device"
+    if args.network == "transformer" and (args.compare or (args.seeds and not tf_population) or args.sweep or
                                           (args.optimizer == "device" and args.gradient != "device")):
-        raise SystemExit("--network transformer: the population's and the comparison's kernels (--seeds, --sweep, --compare) do not "
-                         "know its tensors; it trains with autograd's gradient or --gradient device, and --optimizer device goes with "
-                         "--gradient device")
+        raise SystemExit("--network transformer: the sweep's and the comparison's kernels (--sweep, --compare) do not know its tensors, "
+                         "and --seeds trains a population of them with --gradient device --optimizer device alone; it trains with "
+                         "autograd's gradient or --gradient device, and --optimizer device goes with --gradient device")
     if args.compare:
         return compare(args)
     seeds = [int(x) for x in args.seeds.split(",")] if args.seeds else None

@@ -1105,8 +1105,8 @@ int evac_deepsets_update_population(int32_t n_learners, const evac_mlp_policy_t*
  * (45 with two blocks).  evac_transformer_strides_t is evac_mlp_policy_strides_t's sibling for the encoder's blocks: floats from
  * learner s to learner s + 1, per tensor of evac_transformer_block_t; the strides of a block at index num_blocks and above are
  * never looked at.  num_blocks, elem_dim and use_resid are one value per population.  The UPDATE of such a population (gradient
- * and optimiser with the learner as a grid dimension) does not exist: each learner trains through evac_transformer_update on its
- * own tensors.  Sweeps (per-learner hyperparameters) of such learners do not exist. */
+ * and optimiser with the learner as a grid dimension) is evac_transformer_update_population below, under one configuration for
+ * all learners.  Sweeps (per-learner hyperparameters) of such learners do not exist. */
 typedef struct evac_transformer_block_strides {   /* floats from learner s to learner s + 1, per tensor of evac_transformer_block_t */
     int64_t wq, bq, wk, bk, wv, bv, dense_w, dense_b, ff1_w, ff1_b, ff2_w, ff2_b, norm1_w, norm1_b, norm2_w, norm2_b;
 } evac_transformer_block_strides_t;
@@ -1155,6 +1155,47 @@ int evac_policy_evaluate_population_transformer(evac_handle_t h, int32_t n_learn
                                                 int32_t* progress,                   /* [S E_l][4] in/out; zero it to begin */
                                                 evac_episode_stats_t* episodes_out,  /* [n_episodes][S E_l] */
                                                 const double* norm_state_or_null, float obs_clip, float epsilon, void* stream);
+/* evac_transformer_update_population: evac_transformer_update for n_learners learners in one set of launches, with
+ * evac_deepsets_update_population's argument list and contract word for word, the attention encoder's types where the set
+ * encoder's stood: ONE common batch, perms [S][n_epochs][learner_batch_size] whose values are rows of the common arrays,
+ * rpo_noise_or_null [S][steps][M][2], stats_out [S][steps][8], HOST seeds [S] and first_draw_counters [S], the 64-byte headers
+ * header_stride_bytes apart; the encoder (learner 0's), its parameters, gradients and moments (evac_transformer_adam_state_t)
+ * and their strides: enc_param_strides for encoder and enc_params, enc_grad_strides, enc_moment_strides for enc_exp_avg and
+ * enc_exp_avg_sq.
+ *   workspace: evac_transformer_population_workspace_bytes(obs_dim, M, S) bytes, 16-byte aligned: S slices of
+ *   evac_transformer_workspace_bytes(obs_dim, M) rounded up to whole 256-byte parts (every part of a slice a multiple of 256
+ *   bytes from the base: no two learners' ticket words or partials share a 128-byte line, whatever the base's alignment), then
+ *   the learners' encoded observations, gathered columns and index lists as one common batch [S][M][..] that the actor-critic's
+ *   kernels read with learner s's index list s M + m.
+ * EQUIVALENCE: learner s's 13 + 16 num_blocks parameters, twice as many moments, as many gradients, header and statistics rows
+ * are, bit for bit, those of evac_transformer_update called with learner s's tensors, perms[s], seeds[s],
+ * first_draw_counters[s] and the same common batch.  A learner whose stop flag is set (target_kl) returns at the top of every
+ * later kernel, the encoder's four included (k_tf_encode then does not clear the finish's ticket either), touching nothing,
+ * while the others go on.  No learner reads another's memory and nothing waits across learners: every ticket is an integer
+ * atomicAdd whose result is compared, and no kernel spins.  Launches per minibatch step are those of one learner:
+ * 6 + num_blocks + norm_adv (the encoder forwards, the advantage statistics, the gradient, its finish, dX, one launch per block
+ * backwards, the encoder's finish, the optimiser), plus one launch per call that clears every learner's stop / steps_run /
+ * epochs_run.  No host synchronisation, no device allocation, capturable (seeds and counters are frozen by a capture).
+ * EVAC_ERR_INVALID_ARGUMENT / EVAC_ERR_UNSUPPORTED, decided on the host before anything touches a device, in this order: as
+ * evac_transformer_minibatch_grad of the gradient's arguments; a NULL state; as evac_rpo_update_population; a NULL encoder
+ * strides struct; with n_learners > 1 an encoder stride of a block in use smaller than its tensor (0 included; the strides of a
+ * block not in use are never looked at, and no alignment is asked); as evac_transformer_adam_step.
+ * evac_transformer_population_workspace_bytes: the workspace's size, or EVAC_ERR_INVALID_ARGUMENT where
+ * evac_transformer_workspace_bytes gives it or n_learners is outside 1..EVAC_MAX_LEARNERS. */
+int64_t evac_transformer_population_workspace_bytes(int32_t obs_dim, int64_t n_minibatch, int32_t n_learners);
+int evac_transformer_update_population(int32_t n_learners, const evac_mlp_policy_t* policy, const evac_transformer_t* encoder,
+                                       const evac_mlp_policy_grads_t* params, const evac_transformer_grads_t* enc_params,
+                                       const evac_mlp_policy_grads_t* grads, const evac_transformer_grads_t* enc_grads,
+                                       const evac_mlp_policy_strides_t* param_strides, const evac_transformer_strides_t* enc_param_strides,
+                                       const evac_mlp_policy_strides_t* grad_strides, const evac_transformer_strides_t* enc_grad_strides,
+                                       const evac_mlp_policy_strides_t* moment_strides, const evac_transformer_strides_t* enc_moment_strides,
+                                       int64_t header_stride_bytes, const evac_rpo_loss_config_t* loss_cfg,
+                                       const evac_adam_config_t* adam_cfg, const evac_transformer_adam_state_t* state, int64_t batch_size,
+                                       const float* b_obs, const float* b_actions, const float* b_logprobs, const float* b_advantages,
+                                       const float* b_returns, const float* b_values, int64_t learner_batch_size, int64_t n_minibatch,
+                                       int32_t n_epochs, const int64_t* perms, const float* rpo_noise_or_null, const uint64_t* seeds,
+                                       const uint64_t* first_draw_counters, int32_t use_target_kl, double target_kl, float* stats_out,
+                                       void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,8 @@ replaces.
     python tools/transformer_bench.py --part grad-autograd|grad-device [--minibatch 16384] [--blocks 2] [--use-resid] [--reps 7]
     python tools/transformer_bench.py --part update-torch|update-step|update-one-call [--envs 4096] [--steps 128] [--epochs 10]
     python tools/transformer_bench.py --part collect-population --learners S [--learner-envs 3] [--steps 2048] [--pairs 9]
+    python tools/transformer_bench.py --part update-population --learners S [--learner-envs 3] [--steps 2048] [--minibatch 192]
+                                      [--epochs 10] [--pairs 9]
 
 N = 60, the rel + ohe Box observation (D = 372, 62 tokens of 6), the trainer's normalisation chain, E envs, T steps per call;
 hipEvent times of whole calls after two warm-up calls, median and range of ``--reps`` calls, one JSON line:
@@ -29,6 +31,13 @@ hipEvent times of whole calls after two warm-up calls, median and range of ``--r
            envs (``evac_policy_rollout_population_transformer``) against the loop of S ``policy_rollout(nets[s])`` on handles of E_l
            envs at the learners' ids (``evac_policy_rollout_transformer``), the same nets; one warm-up of each, the first calls'
            storage compared bit for bit, then ``--pairs`` interleaved pairs whose order alternates: hipEvent and host wall time
+  update-population  one whole update of S learners (``--learners``) of ``--learner-envs`` x ``--steps`` rows each (the reference's
+           3 x 2048 by default) in minibatches of ``--minibatch`` (192 by default here) over ``--epochs`` epochs: ONE
+           ``transformer_update_population`` of a ``TransformerPopulation`` (``evac_transformer_update_population``) against the
+           loop of S ``transformer_update`` calls (``evac_transformer_update``), one per learner on a batch of its own that holds
+           its rows of the common random batch, with the same permutations, seeds and draw counters; both forms start from the same tensors and
+           the first updates' parameters are compared bit for bit, then ``--pairs`` interleaved pairs whose order alternates:
+           hipEvent and host wall time
 One part per process, so that a job script can give each its own time limit."""
 import argparse
 import json
@@ -148,6 +157,77 @@ def collect_population_part(args):
         e.close()
 
 
+def update_population_part(args):
+    """S learners' whole update in one set of launches against the per-learner loop of the lone entry, interleaved; one JSON line."""
+    import time
+    from evacuation_amd import trainer
+    from evacuation_amd.population import TransformerPopulation, TransformerPopulationAdam, population_rows, transformer_update_population
+    S, E_l, T = args.learners, args.learner_envs, args.steps or 2048
+    M = 192 if args.minibatch == 16384 else args.minibatch       # (the reference's minibatch unless one is named)
+    D, B_l = (N_PED + 2) * 6, E_l * T
+    B = S * B_l
+    cfg = trainer.RPOTrainingConfig(num_envs=E_l, num_steps=T)
+    seeds = list(range(1, S + 1))
+    pop = TransformerPopulation(D, N_PED, seeds, DEV, num_blocks=args.blocks, use_resid=args.use_resid)
+    opt = TransformerPopulationAdam(pop, lr=cfg.learning_rate, eps=1e-5, max_grad_norm=cfg.max_grad_norm)
+    lone = []                                                    # the loop's learners: tensors of their own, the same values
+    for net in pop.nets:
+        twin = TransformerActorCritic(D, N_PED, num_blocks=args.blocks, use_resid=args.use_resid).to(DEV)
+        with torch.no_grad():
+            for p, q in zip(trainer.all_tensors(twin), trainer.all_tensors(net)):
+                p.copy_(q)
+        lone.append(twin)
+    lone_opt = [trainer.TransformerAdam(net, lr=cfg.learning_rate, eps=1e-5, max_grad_norm=cfg.max_grad_norm) for net in lone]
+    g = torch.Generator(device=DEV).manual_seed(1)
+    rnd = lambda *shape: torch.randn(*shape, device=DEV, generator=g)
+    batch = {"b_obs": (0.6 * rnd(B, D)).clamp(-1, 1), "b_actions": rnd(B, 2), "b_logprobs": -2.0 + 0.1 * rnd(B), "b_advantages": rnd(B),
+             "b_returns": rnd(B), "b_values": rnd(B)}
+    # learner s's own batch [T x E_l]: its columns of the common one [T x S E_l]
+    own = [{k: v.reshape(T, S, E_l, *v.shape[1:])[:, s].reshape(B_l, *v.shape[1:]).contiguous() for k, v in batch.items()}
+           for s in range(S)]
+    perms = torch.stack([torch.stack([torch.randperm(B_l, device=DEV, generator=g) for _ in range(args.epochs)]) for _ in range(S)])
+    rows = population_rows(perms, torch.arange(S, device=DEV).reshape(S, 1, 1), E_l, S).contiguous()
+    steps = args.epochs * len(trainer.update_steps(B_l, M, cfg.norm_adv))
+    stats, stats_l = torch.zeros(S, steps, 8, device=DEV), [torch.zeros(steps, 8, device=DEV) for _ in range(S)]
+    need = ea.population.population_workspace_bytes(D, min(M, B_l), S, transformer=True)
+    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+
+    def together():
+        transformer_update_population(pop, batch, rows, cfg, opt, minibatch_size=M, first_draw_counters=[0] * S, stats=stats, workspace=ws)
+
+    def loop():
+        for s in range(S):
+            trainer.transformer_update(lone[s], own[s], perms[s], cfg, lone_opt[s], seed=seeds[s], first_draw_counter=0, stats=stats_l[s],
+                                       minibatch_size=M)
+    together()
+    loop()
+    torch.cuda.synchronize()
+    same = all(a.detach().view(torch.int32).equal(b.detach().view(torch.int32))
+               for s in range(S) for a, b in zip(trainer.all_tensors(pop.nets[s]), trainer.all_tensors(lone[s])))
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ms = event_ms(fn)
+        return ms, (time.perf_counter() - t0) * 1e3
+    ev, wall = {"loop": [], "population": []}, {"loop": [], "population": []}
+    for pair in range(args.pairs):
+        for form in (("loop", "population") if pair % 2 == 0 else ("population", "loop")):
+            e_ms, w_ms = timed(loop if form == "loop" else together)
+            ev[form].append(e_ms)
+            wall[form].append(w_ms)
+    med = {f: statistics.median(ev[f]) for f in ev}
+    row = {"part": args.part, "learners": S, "learner_rows": B_l, "minibatch": M, "epochs": args.epochs, "minibatch_steps": steps,
+           "launches_per_step": 6 + args.blocks + int(cfg.norm_adv), "obs_dim": D, "blocks": args.blocks, "use_resid": bool(args.use_resid),
+           "pairs": args.pairs, "first_update_same_bits": bool(same)}
+    for f in ("loop", "population"):
+        row[f] = {"ms_median": round(med[f], 3), "ms_min": round(min(ev[f]), 3), "ms_max": round(max(ev[f]), 3),
+                  "host_ms_median": round(statistics.median(wall[f]), 3)}
+    row["loop_over_population"] = round(med["loop"] / med["population"], 3)
+    row["population_range_below_loop"] = max(ev["population"]) < min(ev["loop"])
+    print(json.dumps(row))
+
+
 def update_part(args):
     """One whole update's epochs at N = 60, rel + ohe Box (D = 372), three ways: whole updates between two events after one
     warm-up update (tools/deepsets_bench.py's update parts with this network's entries)."""
@@ -206,7 +286,7 @@ def update_part(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", required=True, choices=["a", "b", "c", "c-eager", "grad-autograd", "grad-device", "update-torch", "update-step",
-                                                     "update-one-call", "collect-population"])
+                                                     "update-one-call", "collect-population", "update-population"])
     ap.add_argument("--minibatch", type=int, default=16384)
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=None, help="default 128; collect-population: 2048")
@@ -214,12 +294,14 @@ def main():
     ap.add_argument("--use-resid", action="store_true")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--epochs", type=int, default=10, help="update-*: the epochs of one update")
-    ap.add_argument("--learners", type=int, default=4, help="collect-population: the learners")
-    ap.add_argument("--learner-envs", type=int, default=3, help="collect-population: a learner's envs")
-    ap.add_argument("--pairs", type=int, default=9, help="collect-population: interleaved pairs")
+    ap.add_argument("--learners", type=int, default=4, help="collect-population, update-population: the learners")
+    ap.add_argument("--learner-envs", type=int, default=3, help="collect-population, update-population: a learner's envs")
+    ap.add_argument("--pairs", type=int, default=9, help="collect-population, update-population: interleaved pairs")
     args = ap.parse_args()
     if args.part == "collect-population":
         return collect_population_part(args)
+    if args.part == "update-population":
+        return update_population_part(args)
     args.steps = args.steps or 128
     if args.part.startswith("update-"):
         return update_part(args)
