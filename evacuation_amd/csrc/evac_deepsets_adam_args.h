@@ -21,4 +21,11 @@ struct SetAdamArgs {
 };
 static_assert(sizeof(SetAdamArgs) <= 1024, "k_adam_set's kernel arguments");
 
+// ... and what k_adam_set_population takes behind it: the learners' strides (the host fills them in evac_deepsets_adam_host.h)
+struct SetAdamStrides {
+    int64_t p[kSetAdamTensors], g[kSetAdamTensors], m[kSetAdamTensors];   // floats: parameters, gradients, moments (both of them)
+    int64_t hdr;                                // bytes
+    int64_t stats;                              // floats of stats_out per learner
+};
+
 }  // namespace evac

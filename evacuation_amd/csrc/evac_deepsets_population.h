@@ -41,12 +41,8 @@ __global__ __launch_bounds__(PolicyFamily::kBlock, 4) void k_collect_population_
                                                             (s + 1) * q.envs_per_learner, DeepSetsEncoder{ds, da});
 }
 
-// ---- the optimiser step: grid (wg_end[18], S); `a` as evac_deepsets_update sets it (gated), learner 0's ----
-struct SetAdamStrides {
-    int64_t p[kSetAdamTensors], g[kSetAdamTensors], m[kSetAdamTensors];   // floats: parameters, gradients, moments (both of them)
-    int64_t hdr;                                // bytes
-    int64_t stats;                              // floats of stats_out per learner
-};
+// ---- the optimiser step: grid (wg_end[18], S); `a` as evac_deepsets_update sets it (gated), learner 0's; SetAdamStrides:
+// evac_deepsets_adam_args.h ----
 // What adam_scalars / adam_element / adam_close read of the arguments, for one learner: `a` itself stays as the launch passed it
 // (a changed copy of a struct whose arrays are indexed at run time would be a private one: 856 bytes of scratch, measured).
 struct SetAdamLearner {

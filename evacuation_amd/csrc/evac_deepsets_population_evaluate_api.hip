@@ -47,12 +47,6 @@ int evac_policy_evaluate_population_deepsets(evac_handle_t h, int32_t n_learners
                                              const evac_deepsets_strides_t* enc_strides, int32_t agent, int32_t shared_episodes,
                                              int32_t n_episodes, int32_t max_steps, int32_t* progress, evac_episode_stats_t* episodes_out,
                                              const double* norm_state, float obs_clip, float epsilon, void* stream) {
-    if (!strides || !enc_strides) {
-        evac_host::HandleView v;
-        if (const int rc = evac_host::handle_begin(h, DeepSetsPopulationEncoder::kEvaluatePopulation, &v); rc != EVAC_OK) return rc;
-        return evac_host::handle_fail(h, EVAC_ERR_INVALID_ARGUMENT,
-                                      std::string(DeepSetsPopulationEncoder::kEvaluatePopulation) + ": strides / enc_strides is NULL");
-    }
     return encoder_evaluate<DeepSetsPopulationEncoder, false, DeepSetsEvaluateLearners>(
         h, agent, policy, n_episodes, max_steps, progress, episodes_out, norm_state, obs_clip, epsilon, encoder, stream, nullptr,
         DeepSetsEvaluateLearners{{n_learners, strides, enc_strides}, (int)(shared_episodes != 0)});

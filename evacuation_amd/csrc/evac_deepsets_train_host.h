@@ -1,7 +1,8 @@
-// Host side of the deep-sets leader's training entries, the part its two translation units share (evac_deepsets_train_api.hip:
-// the gradient; evac_deepsets_update_api.hip: the gradient with the optimiser, and the whole update): the workspace's layout, what
-// the entries check of the encoder, its fields of the kernels' argument struct and the launches of one minibatch's gradient, as
-// the trait SetGrad of evac_encoder_train_host.h's templates.
+// Host side of the deep-sets leader's training entries, the part its translation units share (evac_deepsets_train_api.hip: the
+// gradient; evac_deepsets_update_api.hip: the gradient with the optimiser, and the whole update; evac_deepsets_population_api.hip:
+// a population's update): the workspace's layout, what the entries check of the encoder, its fields of the kernels' argument
+// struct and the encoder's launches in front of and behind the actor-critic's, as the trait SetGrad of
+// evac_encoder_train_host.h's templates.
 #pragma once
 
 #include "evac_deepsets_train.h"
@@ -17,6 +18,7 @@ struct SetGrad {
     using Encoder = evac_deepsets_t;
     using Grads = evac_deepsets_grads_t;
     using Args = evac::SetArgs;
+    using LearnerStrides = evac::SetLearnerStrides;       // (a population's: behind the gate in `tail`)
 
     // The workspace: evac_rpo_minibatch_grad's own (for a batch of M rows of D floats) | tickets and slots | Y | dY | s | t | the
     // gathered actions, log-probabilities, advantages, returns, values | the index vector | the partials | the dW_r segments;
@@ -67,18 +69,19 @@ struct SetGrad {
         s.seglen = (int)((M + s.Sr - 1) / s.Sr);
     }
 
-    // The launches of one minibatch's gradient, all 19 tensors: the encoder forwards, rpo_launch on the encoded observations, the
-    // encoder backwards, its finish.  `gate` as rpo_launch's.
-    template <class... Gate>
-    static void launch(const evac::RpoArgs& a, const Args& s, hipStream_t S, Gate... gate) {
-        const int64_t M = s.M;
-        const int64_t enc_wgs = (M + evac::kSetWaves - 1) / evac::kSetWaves;
-        hipLaunchKernelGGL(evac::k_set_encode<Gate...>, dim3((unsigned)(enc_wgs > evac::kSetEncodeMaxWgs ? evac::kSetEncodeMaxWgs : enc_wgs)),
-                           dim3(evac::kSetBlock), 0, S, s, gate...);
-        rpo_launch(a, S, gate...);
-        hipLaunchKernelGGL(evac::k_set_backward<Gate...>, dim3((unsigned)s.P), dim3(evac::kSetBlock), 0, S, s, gate...);
+    // The encoder's launches of one minibatch's gradient, in front of the actor-critic's (the encoder forwards) and behind them
+    // (the encoder backwards, its finish): a grid of `y` rows, one per learner; `tail` is what the kernels take behind `s`.
+    template <class... Tail>
+    static void encode(const Args& s, unsigned y, hipStream_t S, Tail... tail) {
+        const int64_t enc_wgs = (s.M + evac::kSetWaves - 1) / evac::kSetWaves;
+        hipLaunchKernelGGL(evac::k_set_encode<Tail...>, dim3((unsigned)(enc_wgs > evac::kSetEncodeMaxWgs ? evac::kSetEncodeMaxWgs : enc_wgs), y),
+                           dim3(evac::kSetBlock), 0, S, s, tail...);
+    }
+    template <class... Tail>
+    static void backward(const Args& s, unsigned y, hipStream_t S, Tail... tail) {
+        hipLaunchKernelGGL(evac::k_set_backward<Tail...>, dim3((unsigned)s.P, y), dim3(evac::kSetBlock), 0, S, s, tail...);
         const int rtiles = (s.D + evac::kSetRTile - 1) / evac::kSetRTile;
-        hipLaunchKernelGGL(evac::k_set_finish<Gate...>, dim3((unsigned)(rtiles * s.Sr + 1)), dim3(evac::kSetBlock), 0, S, s, gate...);
+        hipLaunchKernelGGL(evac::k_set_finish<Tail...>, dim3((unsigned)(rtiles * s.Sr + 1), y), dim3(evac::kSetBlock), 0, S, s, tail...);
     }
 };
 

@@ -1,16 +1,36 @@
-// Host side of the gradient behind an encoder, the part the deep-sets and the transformer leader's entries share
-// (evac_deepsets_train_api.hip, evac_deepsets_update_api.hip, evac_transformer_train_api.hip, evac_transformer_update_api.hip):
-// the workspace's cursor and its gathered columns, the halves of "prepare" and "step" that are the same in front of either
-// encoder, the sizer's body and the whole body of a gradient entry.  What differs sits in a trait per encoder (SetGrad in evac_deepsets_train_host.h, TfGrad in
-// evac_transformer_train_host.h):
+// Host side of training behind an encoder, the part the deep-sets and the transformer leader's entries share
+// (evac_{deepsets,transformer}_train_api.hip: the gradient; evac_{deepsets,transformer}_update_api.hip: the optimiser step, the
+// gradient with the optimiser and the whole update; through evac_encoder_population_host.h the two population updates): the
+// workspace's cursor and its gathered columns, the halves of "prepare" and "step" that are the same in front of either encoder,
+// the sizer's body, the launches of one minibatch's gradient, and the whole bodies of a gradient entry, an optimiser step, a
+// minibatch step and an update.  What differs sits in two traits per encoder.
 //
+// The gradient's (SetGrad in evac_deepsets_train_host.h, TfGrad in evac_transformer_train_host.h):
 //   Encoder, Grads, Args      the C structs and the kernels' argument struct (evac::SetArgs / evac::TfgArgs, whose equally named
 //                             fields the templates here reach by name: the two share no base, which would move kernel arguments)
 //   Layout, layout(D, M)      the workspace's parts; `header`, `Y`, `cols`, `parts` and `total` are read here
 //   check(E, G, D, s)         the encoder's own refusals in its own order, then `s` = Args{} with the encoder's own fields
 //   shape(s, L, ws, M)        the encoder's own parts of the workspace and its own step fields (chunk, P, ..)
-//   launch(a, s, S, gate...)  the launches of one minibatch's gradient
+//   encode(s, y, S, tail...)  the encoder's launches in front of the actor-critic's, a grid of y rows (one per learner) ...
+//   backward(s, y, S, tail...)   ... and behind them.  `tail` is what the kernels take behind `s`: nothing, the stop gate, or the
+//                             gate and the learners' strides; it names the kernels' instantiation.
+//   LearnerStrides            those strides (evac::SetLearnerStrides / evac::TfgLearnerStrides)
+//
+// The optimiser's (SetAdam in evac_deepsets_adam_host.h, TfAdam in evac_transformer_adam_host.h):
+//   State, Grads, Args        the C structs and the kernel's argument struct (evac::SetAdamArgs / evac::TfAdamArgs)
+//   Dims, dims(E)             the encoder's sizes that size its tensors, from the C struct of the encoder
+//   check(D, dims)            the encoder's own size refusals in its own order
+//   fresh(dims)               Args{}, with the tensor count where the kernel reads it
+//   count(dims), tensor(G, i), size(i, D, dims)   the encoder's tensors behind the actor-critic's 13: how many, the i-th pointer
+//                             of a Grads, its elements
+//   launch(kernel, q, learners, S, rest...)   one launch of the unit's own kernel (k_adam_* / k_adam_*_population, each defined in
+//                             one unit alone) over a grid of `learners` rows
+//   Strides, EncoderStrides, strides(E, D, n_learners, p, g, m, sq, aq)   a population's: the population kernel's strides, the C
+//                             struct of an encoder's, and the check of the three of them (parameters, gradients, moments) with
+//                             their copy into the gradient's LearnerStrides `sq` and into `aq` behind the 13
 #pragma once
+
+#include <cstddef>
 
 #include "evac_train_host.h"
 
@@ -120,6 +140,15 @@ inline void encoder_adam_scalars(const evac::AdamArgs& o, EncAdamArgs& q) {
     q.gated = o.gated; q.epoch_last = o.epoch_last; q.use_target_kl = o.use_target_kl;
 }
 
+// The launches of one minibatch's gradient: the encoder forwards, rpo_launch on the encoded observations, the encoder backwards.
+// `gate` as rpo_launch's.
+template <class Enc, class... Gate>
+inline void encoder_grad_launch(const evac::RpoArgs& a, const typename Enc::Args& s, hipStream_t S, Gate... gate) {
+    Enc::encode(s, 1u, S, gate...);
+    rpo_launch(a, S, gate...);
+    Enc::backward(s, 1u, S, gate...);
+}
+
 // What follows the gradient in the same call: nothing (the step's entry: the optimiser's checks, and its launch).
 struct NothingMore {
     int operator()() const { return EVAC_OK; }
@@ -147,8 +176,130 @@ inline int encoder_minibatch_grad(const evac_mlp_policy_t* policy, const typenam
     const int dev = device_of(workspace);
     DeviceGuard g(dev);
     if (rpo_raise_lds<evac::k_rpo_grad<>>(a.D, dev) != EVAC_OK) return EVAC_ERR_HIP;
-    Enc::launch(inner, s, (hipStream_t)stream);
+    encoder_grad_launch<Enc>(inner, s, (hipStream_t)stream);
     then((hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? EVAC_OK : EVAC_ERR_HIP;
+}
+
+// What an encoder's optimiser step checks and sets up: adam_prepare for the 13 tensors (into `o`), then the encoder's -- its
+// sizes (Opt::check) before its pointers, parameters, gradients and both moments alike -- and every tensor's elements and
+// workgroups.
+template <class Opt>
+inline int encoder_adam_prepare(const evac_mlp_policy_grads_t* params, const typename Opt::Grads* enc_params,
+                                const evac_mlp_policy_grads_t* grads, const typename Opt::Grads* enc_grads,
+                                const typename Opt::State* state, const evac_adam_config_t* cfg, int32_t obs_dim,
+                                const typename Opt::Dims& dims, evac::AdamArgs& o, typename Opt::Args& q) {
+    if (!state || !enc_params || !enc_grads) return EVAC_ERR_INVALID_ARGUMENT;
+    const evac_adam_state_t linear{state->header, state->exp_avg, state->exp_avg_sq};
+    if (const int rc = adam_prepare(params, grads, &linear, cfg, obs_dim, o); rc != EVAC_OK) return rc;
+    if (const int rc = Opt::check(obs_dim, dims); rc != EVAC_OK) return rc;
+    q = Opt::fresh(dims);
+    const int ne = Opt::count(dims);
+    const typename Opt::Grads* sets[4] = {enc_params, enc_grads, &state->enc_exp_avg, &state->enc_exp_avg_sq};
+    float* const* lin[4] = {o.p, o.g, o.m, o.v};
+    float** dst[4] = {q.p, q.g, q.m, q.v};
+    for (int k = 0; k < 4; ++k) {
+        for (int i = 0; i < evac::kAdamTensors; ++i) dst[k][i] = lin[k][i];
+        for (int i = 0; i < ne; ++i) {
+            if (!Opt::tensor(*sets[k], i)) return EVAC_ERR_INVALID_ARGUMENT;
+            dst[k][evac::kAdamTensors + i] = Opt::tensor(*sets[k], i);
+        }
+    }
+    int wgs = 0;
+    for (int i = 0; i < evac::kAdamTensors + ne; ++i) {
+        q.n[i] = i < evac::kAdamTensors ? o.end[i] - (i ? o.end[i - 1] : 0) : Opt::size(i - evac::kAdamTensors, obs_dim, dims);
+        q.wg_end[i] = (wgs += (q.n[i] + evac::kAdamBlock - 1) / evac::kAdamBlock);
+    }
+    encoder_adam_scalars(o, q);
+    return EVAC_OK;
+}
+
+// The whole body of evac_deepsets_adam_step / evac_transformer_adam_step; `kernel` is the unit's k_adam_set / k_adam_tf.
+template <class Opt, class Kernel>
+inline int encoder_adam_step(Kernel kernel, const evac_mlp_policy_grads_t* params, const typename Opt::Grads* enc_params,
+                             const evac_mlp_policy_grads_t* grads, const typename Opt::Grads* enc_grads, const typename Opt::State* state,
+                             const evac_adam_config_t* cfg, int32_t obs_dim, const typename Opt::Dims& dims, const float* grad_sumsq,
+                             void* stream) {
+    evac::AdamArgs o;
+    typename Opt::Args q;
+    if (const int rc = encoder_adam_prepare<Opt>(params, enc_params, grads, enc_grads, state, cfg, obs_dim, dims, o, q); rc != EVAC_OK)
+        return rc;
+    if (!grad_sumsq) return EVAC_ERR_INVALID_ARGUMENT;
+    q.sumsq = grad_sumsq;
+    DeviceGuard g(device_of(state->header));
+    Opt::launch(kernel, q, 1u, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? EVAC_OK : EVAC_ERR_HIP;
+}
+
+// The whole body of evac_deepsets_minibatch_step / evac_transformer_minibatch_step: encoder_minibatch_grad with the optimiser's
+// checks behind the gradient's and its launch behind the gradient's, reading the sum of squares the gradient left at stats_out[7].
+template <class Enc, class Opt, class Kernel>
+inline int encoder_minibatch_step(Kernel kernel, const evac_mlp_policy_t* policy, const typename Enc::Encoder* encoder,
+                                  const evac_rpo_loss_config_t* cfg, int64_t batch_size, const float* b_obs, const float* b_actions,
+                                  const float* b_logprobs, const float* b_advantages, const float* b_returns, const float* b_values,
+                                  int64_t n_minibatch, const int64_t* mb_inds, const float* rpo_noise, uint64_t seed, uint64_t draw_counter,
+                                  const evac_mlp_policy_grads_t* grads_out, const typename Enc::Grads* encoder_grads_out, float* stats_out,
+                                  void* workspace, void* stream, const evac_mlp_policy_grads_t* params,
+                                  const typename Enc::Grads* enc_params, const typename Opt::State* state,
+                                  const evac_adam_config_t* adam_cfg) {
+    evac::AdamArgs o;
+    typename Opt::Args q;
+    return encoder_minibatch_grad<Enc>(
+        policy, encoder, cfg, batch_size, b_obs, b_actions, b_logprobs, b_advantages, b_returns, b_values, n_minibatch, mb_inds, rpo_noise,
+        seed, draw_counter, grads_out, encoder_grads_out, stats_out, workspace, stream,
+        [&] {                                                                  // (behind the gradient's checks: policy and encoder are set)
+            const int rc = encoder_adam_prepare<Opt>(params, enc_params, grads_out, encoder_grads_out, state, adam_cfg, policy->obs_dim,
+                                                     Opt::dims(*encoder), o, q);
+            if (rc == EVAC_OK) q.sumsq = stats_out + 7;
+            return rc;
+        },
+        [&q, kernel](hipStream_t S) { Opt::launch(kernel, q, 1u, S); });
+}
+
+// The whole body of evac_deepsets_update / evac_transformer_update: the gradient's checks, the optimiser's, then every step's
+// launches (gated by the optimiser's header) over rpo_update_steps.
+template <class Enc, class Opt, class Kernel>
+inline int encoder_update(Kernel kernel, const evac_mlp_policy_t* policy, const typename Enc::Encoder* encoder,
+                          const evac_mlp_policy_grads_t* params, const typename Enc::Grads* enc_params, const evac_mlp_policy_grads_t* grads,
+                          const typename Enc::Grads* enc_grads, const evac_rpo_loss_config_t* loss_cfg, const evac_adam_config_t* adam_cfg,
+                          const typename Opt::State* state, int64_t batch_size, const float* b_obs, const float* b_actions,
+                          const float* b_logprobs, const float* b_advantages, const float* b_returns, const float* b_values,
+                          int64_t n_minibatch, int32_t n_epochs, const int64_t* perms, const float* rpo_noise, uint64_t seed,
+                          uint64_t first_draw_counter, int32_t use_target_kl, double target_kl, float* stats_out, void* workspace,
+                          void* stream) {
+    if (n_epochs < 1) return EVAC_ERR_INVALID_ARGUMENT;
+    evac::RpoArgs a;
+    typename Enc::Args s;
+    if (const int rc = encoder_grad_prepare<Enc>(policy, encoder, loss_cfg, batch_size, b_obs, b_actions, b_logprobs, b_advantages,
+                                                 b_returns, b_values, n_minibatch, perms, rpo_noise, seed, grads, enc_grads, stats_out,
+                                                 workspace, a, s);
+        rc != EVAC_OK)
+        return rc;
+    evac::AdamArgs o;
+    typename Opt::Args q;
+    if (const int rc = encoder_adam_prepare<Opt>(params, enc_params, grads, enc_grads, state, adam_cfg, policy->obs_dim,
+                                                 Opt::dims(*encoder), o, q);
+        rc != EVAC_OK)
+        return rc;
+    o.gated = 1;
+    o.use_target_kl = use_target_kl != 0;
+    o.target_kl = target_kl;
+    const int dev = device_of(workspace);
+    DeviceGuard g(dev);
+    if (rpo_raise_lds<evac::k_rpo_grad<const evac::AdamHeader*>>(a.D, dev) != EVAC_OK) return EVAC_ERR_HIP;
+    hipStream_t S = (hipStream_t)stream;
+    // stop, steps_run, epochs_run (and the ticket, zero anyway)
+    if (hipMemsetAsync((char*)state->header + offsetof(evac::AdamHeader, stop), 0, 16, S) != hipSuccess) {
+        (void)hipGetLastError();
+        return EVAC_ERR_HIP;
+    }
+    rpo_update_steps(a, o, batch_size, n_minibatch, n_epochs, perms, rpo_noise, stats_out, first_draw_counter,
+                     [&s, &q, S, kernel](const evac::RpoArgs& step, const evac::AdamArgs& adam, uint64_t) {
+                         const evac::RpoArgs inner = encoder_grad_step<Enc>(step, s);
+                         encoder_adam_scalars(adam, q);
+                         encoder_grad_launch<Enc>(inner, s, S, (const evac::AdamHeader*)adam.hdr);
+                         Opt::launch(kernel, q, 1u, S);
+                     });
     return hipGetLastError() == hipSuccess ? EVAC_OK : EVAC_ERR_HIP;
 }
 

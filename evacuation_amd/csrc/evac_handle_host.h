@@ -1,6 +1,7 @@
 // What the entries that run a network on a handle's envs share (evac_api.hip: evac_policy_rollout*, evac_policy_evaluate*;
-// evac_deepsets_api.hip, evac_transformer_api.hip: their forms with an encoder; evac_deepsets_population_api.hip: the collection of
-// a population of deep-sets leaders; evac_deepsets_population_evaluate_api.hip: its evaluation; evac_capture_api.hip: the evaluation entries that record frames).  The handle's struct stays evac_api.hip's own:
+// evac_deepsets_api.hip, evac_transformer_api.hip: their forms with an encoder; evac_{deepsets,transformer}_population_api.hip: the
+// collection of a population of such leaders; evac_{deepsets,transformer}_population_evaluate_api.hip: its evaluation;
+// evac_capture_api.hip: the evaluation entries that record frames).  The handle's struct stays evac_api.hip's own:
 // the handle_* functions are defined there and are not exported from the library.  Below them, host-only and inline: what
 // every collection entry and every evaluation entry refuses, the one-wave limit, a population's shares of the envs, and the grid.
 // Each returns the text that follows the entry's name in its message (empty: accepted), as mlp_policy_check does; the entry
@@ -132,9 +133,12 @@ inline int encoder_networks_check(const evac::Params& p, const evac_mlp_policy_t
 struct NoLearners {
     static constexpr bool kOn = false;
 };
+// What a population form refuses first behind the handle: its Learners' `strides` / `enc_strides` (the two C structs) missing.
+constexpr const char* kNullStrides = ": strides / enc_strides is NULL";
 // evac_policy_rollout_<encoder> (`a`: collect_outputs).  Every refusal before the first HIP call; one kernel on `stream`.
-// Learners (kOn): the population form of the entry (evac_deepsets_population_api.hip) -- check(p, policy, encoder) adds its
-// refusals behind the networks' and before the alignment of actions_out, in the same form, and launch(view, n_steps, a, na, ea, stream) enqueues its own kernel.
+// Learners (kOn): the population form of the entry (evac_{deepsets,transformer}_population_api.hip) -- a NULL `strides` /
+// `enc_strides` of it is refused first behind the handle, check(p, policy, encoder) adds its refusals behind the networks' and
+// before the alignment of actions_out, in the same form, and launch(view, n_steps, a, na, ea, stream) enqueues its own kernel.
 template <class Enc, class Learners = NoLearners>
 inline int encoder_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_policy_t* policy, evac::PolicyArgs a, const evac::NormArgs& na,
                            const typename Enc::Struct* encoder, void* stream, Learners learners = Learners{}) {
@@ -142,6 +146,9 @@ inline int encoder_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_poli
     const std::string w = Enc::kRollout;
     evac_host::HandleView v;
     if (const int rc = evac_host::handle_begin(h, w.c_str(), &v); rc != EVAC_OK) return rc;
+    if constexpr (Learners::kOn) {
+        if (!learners.strides || !learners.enc_strides) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + kNullStrides);
+    }
     std::string why = one_wave_check(v.p);
     if (!why.empty()) return handle_fail(h, EVAC_ERR_UNSUPPORTED, w + why);
     typename Enc::Args ea{};
@@ -166,9 +173,10 @@ inline int encoder_rollout(evac_handle_t h, int32_t n_steps, const evac_mlp_poli
 
 // evac_policy_evaluate_<encoder>: the agent's code first, the one-wave limit last.  CAPTURE: evac_policy_evaluate_<encoder>_capture,
 // the same with capture_check behind the one-wave limit and the capture behind the kernel's arguments.
-// Learners (kOn): the population form of the entry (evac_deepsets_population_evaluate_api.hip; Enc::kEvaluatePopulation its name) --
-// check(p, policy, encoder) adds its refusals behind the networks' and before the one-wave limit, and launch(view, a, ev, ea, stream)
-// enqueues its own kernel.
+// Learners (kOn): the population form of the entry (evac_{deepsets,transformer}_population_evaluate_api.hip;
+// Enc::kEvaluatePopulation its name) -- a NULL `strides` / `enc_strides` of it is refused first behind the handle,
+// check(p, policy, encoder) adds its refusals behind the networks' and before the one-wave limit, and
+// launch(view, a, ev, ea, stream) enqueues its own kernel.
 template <class Enc, bool CAPTURE = false, class Learners = NoLearners>
 inline int encoder_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_policy_t* policy, int32_t n_episodes, int32_t max_steps,
                             int32_t* progress, evac_episode_stats_t* episodes_out, const double* norm_state, float obs_clip, float epsilon,
@@ -182,6 +190,9 @@ inline int encoder_evaluate(evac_handle_t h, int32_t agent, const evac_mlp_polic
     else w = Enc::kEvaluate;
     evac_host::HandleView v;
     if (const int rc = evac_host::handle_begin(h, w.c_str(), &v); rc != EVAC_OK) return rc;
+    if constexpr (Learners::kOn) {
+        if (!learners.strides || !learners.enc_strides) return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + kNullStrides);
+    }
     if (agent == EVAC_AGENT_VACUUM_CLEANER)
         return handle_fail(h, EVAC_ERR_INVALID_ARGUMENT, w + ": the scripted agent has no network (use evac_policy_evaluate)");
     if (agent != EVAC_AGENT_POLICY_MEAN && agent != EVAC_AGENT_POLICY_SAMPLE)

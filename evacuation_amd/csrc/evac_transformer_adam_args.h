@@ -24,4 +24,11 @@ struct TfAdamArgs {
 };
 static_assert(sizeof(TfAdamArgs) <= 4096, "k_adam_tf's kernel arguments: the kernel-argument segment holds 4 KB");
 
+// ... and what k_adam_tf_population takes behind it: the learners' strides (the host fills them in evac_transformer_adam_host.h)
+struct TfAdamStrides {
+    int64_t p[kTfAdamTensors], g[kTfAdamTensors], m[kTfAdamTensors];   // floats: parameters, gradients, moments (both of them)
+    int64_t hdr;                                // bytes
+    int64_t stats;                              // floats of stats_out per learner
+};
+
 }  // namespace evac

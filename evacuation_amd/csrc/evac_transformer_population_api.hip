@@ -48,12 +48,6 @@ int evac_policy_rollout_population_transformer(evac_handle_t h, int32_t n_learne
                                                float* value_out, float* reward_out, float* done_out, float* next_value_out,
                                                evac_episode_stats_t* final_stats, double* norm_state, float gamma, float obs_clip,
                                                float reward_clip, float epsilon, void* stream) {
-    if (!strides || !enc_strides) {
-        evac_host::HandleView v;
-        if (const int rc = evac_host::handle_begin(h, TransformerPopulationEncoder::kRollout, &v); rc != EVAC_OK) return rc;
-        return evac_host::handle_fail(h, EVAC_ERR_INVALID_ARGUMENT,
-                                      std::string(TransformerPopulationEncoder::kRollout) + ": strides / enc_strides is NULL");
-    }
     return encoder_rollout<TransformerPopulationEncoder>(h, n_steps, policy,
                                                          collect_outputs(next_obs, next_done, obs_out, actions_out, logprob_out, value_out,
                                                                          reward_out, done_out, next_value_out, final_stats),

@@ -48,12 +48,6 @@ int evac_policy_evaluate_population_transformer(evac_handle_t h, int32_t n_learn
                                                 int32_t n_episodes, int32_t max_steps, int32_t* progress,
                                                 evac_episode_stats_t* episodes_out, const double* norm_state, float obs_clip, float epsilon,
                                                 void* stream) {
-    if (!strides || !enc_strides) {
-        evac_host::HandleView v;
-        if (const int rc = evac_host::handle_begin(h, TransformerPopulationEncoder::kEvaluatePopulation, &v); rc != EVAC_OK) return rc;
-        return evac_host::handle_fail(h, EVAC_ERR_INVALID_ARGUMENT,
-                                      std::string(TransformerPopulationEncoder::kEvaluatePopulation) + ": strides / enc_strides is NULL");
-    }
     return encoder_evaluate<TransformerPopulationEncoder, false, TransformerEvaluateLearners>(
         h, agent, policy, n_episodes, max_steps, progress, episodes_out, norm_state, obs_clip, epsilon, encoder, stream, nullptr,
         TransformerEvaluateLearners{{n_learners, strides, enc_strides}, (int)(shared_episodes != 0)});

@@ -19,13 +19,8 @@
 
 namespace evac {
 
-// ---- the optimiser step: grid (wg_end[nt - 1], S); `a` as evac_transformer_update sets it (gated), learner 0's ----
-struct TfAdamStrides {
-    int64_t p[kTfAdamTensors], g[kTfAdamTensors], m[kTfAdamTensors];   // floats: parameters, gradients, moments (both of them)
-    int64_t hdr;                                // bytes
-    int64_t stats;                              // floats of stats_out per learner
-};
-static_assert(sizeof(TfAdamArgs) + sizeof(TfAdamStrides) <= 4096, "k_adam_tf_population: arguments beyond the kernel-argument segment");
+// ---- the optimiser step: grid (wg_end[nt - 1], S); `a` as evac_transformer_update sets it (gated), learner 0's; TfAdamStrides:
+// evac_transformer_adam_args.h ----
 // What adam_scalars / adam_element / adam_close read of the arguments, for one learner: `a` itself stays as the launch passed it
 // (a changed copy of a struct whose arrays are indexed at run time would be a private one, in scratch).
 struct TfAdamLearner {

@@ -1,7 +1,8 @@
-// Host side of the transformer leader's training entries, the part its two translation units share
+// Host side of the transformer leader's training entries, the part its translation units share
 // (evac_transformer_train_api.hip: the gradient; evac_transformer_update_api.hip: the gradient with the optimiser, and the whole
-// update): the workspace's layout, what the entries check of the encoder, its fields of the kernels' argument struct and the
-// launches of one minibatch's gradient, as the trait TfGrad of evac_encoder_train_host.h's templates.
+// update; evac_transformer_population_update_api.hip: a population's update): the workspace's layout, what the entries check of
+// the encoder, its fields of the kernels' argument struct and the encoder's launches in front of and behind the actor-critic's,
+// as the trait TfGrad of evac_encoder_train_host.h's templates.
 #pragma once
 
 #include <string>
@@ -26,6 +27,7 @@ struct TfGrad {
     using Encoder = evac_transformer_t;
     using Grads = evac_transformer_grads_t;
     using Args = evac::TfgArgs;
+    using LearnerStrides = evac::TfgLearnerStrides;       // (a population's: behind the gate in `tail`)
 
     // The workspace: evac_rpo_minibatch_grad's own (for a batch of M rows of D floats) | the ticket and the slots | Y | dX | X1 |
     // the gathered actions, log-probabilities, advantages, returns, values | the index vector | the partials of two blocks; every
@@ -80,22 +82,24 @@ struct TfGrad {
         s.P = (int)((M + s.chunk - 1) / s.chunk);                                 // (P <= p0: the workspace's bound)
     }
 
-    // The launches of one minibatch's gradient, all 13 + 16 num_blocks tensors: the encoder forwards, rpo_launch on the encoded
-    // observations, dY, one launch per block backwards, the finish.  `gate` as rpo_launch's.
-    template <class... Gate>
-    static void launch(const evac::RpoArgs& a, const Args& s, hipStream_t S, Gate... gate) {
-        const int64_t M = s.M;
-        const int64_t enc_wgs = (M + evac::kTfgEncodeWaves - 1) / evac::kTfgEncodeWaves;
-        hipLaunchKernelGGL(evac::k_tf_encode<Gate...>, dim3((unsigned)(enc_wgs > evac::kTfgEncodeMaxWgs ? evac::kTfgEncodeMaxWgs : enc_wgs)),
-                           dim3(evac::kTfgEncodeBlock), 0, S, s, gate...);
-        rpo_launch(a, S, gate...);
-        const int64_t tiles = (M + evac::kTfgTile - 1) / evac::kTfgTile;
-        hipLaunchKernelGGL(evac::k_tf_dy<Gate...>, dim3((unsigned)(tiles > 65536 ? 65536 : tiles)), dim3(evac::kTfgEncodeBlock), 0, S, s,
-                           gate...);
+    // The encoder's launches of one minibatch's gradient, in front of the actor-critic's (the encoder forwards) and behind them
+    // (dY, one launch per block backwards, the finish): a grid of `y` rows, one per learner; `tail` is what the kernels take
+    // behind `s`.
+    template <class... Tail>
+    static void encode(const Args& s, unsigned y, hipStream_t S, Tail... tail) {
+        const int64_t enc_wgs = (s.M + evac::kTfgEncodeWaves - 1) / evac::kTfgEncodeWaves;
+        hipLaunchKernelGGL(evac::k_tf_encode<Tail...>, dim3((unsigned)(enc_wgs > evac::kTfgEncodeMaxWgs ? evac::kTfgEncodeMaxWgs : enc_wgs), y),
+                           dim3(evac::kTfgEncodeBlock), 0, S, s, tail...);
+    }
+    template <class... Tail>
+    static void backward(const Args& s, unsigned y, hipStream_t S, Tail... tail) {
+        const int64_t tiles = (s.M + evac::kTfgTile - 1) / evac::kTfgTile;
+        hipLaunchKernelGGL(evac::k_tf_dy<Tail...>, dim3((unsigned)(tiles > 65536 ? 65536 : tiles), y), dim3(evac::kTfgEncodeBlock), 0, S, s,
+                           tail...);
         for (int b = s.nb - 1; b >= 0; --b)
-            hipLaunchKernelGGL(evac::k_tf_backward<Gate...>, dim3((unsigned)s.P), dim3(evac::kTfgBlock), 0, S, s, b, gate...);
-        hipLaunchKernelGGL(evac::k_tf_finish<Gate...>, dim3((unsigned)(s.nb * evac::kTfgFinishWgs)), dim3(evac::kTfgEncodeBlock), 0, S, s,
-                           gate...);
+            hipLaunchKernelGGL(evac::k_tf_backward<Tail...>, dim3((unsigned)s.P, y), dim3(evac::kTfgBlock), 0, S, s, b, tail...);
+        hipLaunchKernelGGL(evac::k_tf_finish<Tail...>, dim3((unsigned)(s.nb * evac::kTfgFinishWgs), y), dim3(evac::kTfgEncodeBlock), 0, S, s,
+                           tail...);
     }
 };
 
