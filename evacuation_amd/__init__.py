@@ -19,7 +19,8 @@ __all__ = ["EnvConfig", "EnvWrappersConfig", "Status", "setup_env", "EvacuationE
            "RPOTrainer", "RPOTrainingConfig", "gae", "rpo_minibatch_grad", "DeviceAdam", "rpo_minibatch_step", "rpo_update",
            "deepsets_minibatch_grad", "deepsets_kernel_grad", "WacuumCleaner", "PolicyEvaluator", "PopulationEvaluator", "EvaluationResult",
            "PolicyPopulation", "DeepSetsPopulation", "TransformerPopulation", "PopulationAdam", "TransformerPopulationAdam",
-           "PopulationTrainer", "rpo_update_population", "deepsets_update_population", "transformer_update_population",
+           "PopulationTrainer", "rpo_update_population", "deepsets_update_population", "transformer_update_population", "deepsets_update_sweep",
+           "transformer_update_sweep",
            "episode_to_memory"]
 
 
@@ -56,7 +57,8 @@ def __getattr__(name):   # lazy: keeps `import evacuation_amd` light and torch-f
         from . import trainer as _trainer
         return getattr(_trainer, name)
     if name in ("PolicyPopulation", "DeepSetsPopulation", "TransformerPopulation", "PopulationAdam", "TransformerPopulationAdam",
-                "PopulationTrainer", "rpo_update_population", "deepsets_update_population", "transformer_update_population"):   # S learners in one set of launches
+                "PopulationTrainer", "rpo_update_population", "deepsets_update_population", "transformer_update_population", "deepsets_update_sweep",
+                "transformer_update_sweep"):   # S learners in one set of launches
         from . import population as _population
         return getattr(_population, name)
     if name == "episode_to_memory":      # one episode of a recorded evaluation in the reference's frame format

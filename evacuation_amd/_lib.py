@@ -335,6 +335,15 @@ SIGNATURES = {
                                         C.c_int64, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                         C.POINTER(EvacLearnerHyper), _P, _P, _P]),
 }
+# the sweeps of the encoder leaders: the population entries' arguments with evac_learner_hyper_t[S] in front of the stream
+# (collection) or in place of use_target_kl, target_kl (the update); the sizers are the population's
+for _enc in ("deepsets", "transformer"):
+    _res, _args = SIGNATURES[f"evac_policy_rollout_population_{_enc}"]
+    SIGNATURES[f"evac_policy_rollout_sweep_{_enc}"] = (_res, _args[:-1] + [C.POINTER(EvacLearnerHyper), _args[-1]])
+    _res, _args = SIGNATURES[f"evac_{_enc}_update_population"]
+    SIGNATURES[f"evac_{_enc}_update_sweep"] = (_res, _args[:-5] + [C.POINTER(EvacLearnerHyper)] + _args[-3:])
+    SIGNATURES[f"evac_{_enc}_sweep_workspace_bytes"] = SIGNATURES[f"evac_{_enc}_population_workspace_bytes"]
+del _enc, _res, _args
 
 _lib = None
 

@@ -12,14 +12,15 @@ LIB_PATH = os.path.join(HERE, "libevac.so")
 # the env | the trainer's update | the update of a population of learners | ... with a configuration per learner | the deep-sets leader
 # | its gradient | its optimiser step and whole update | the transformer leader | its gradient | its optimiser step and whole
 # update | a population of deep-sets leaders | its evaluation | a population of transformer leaders: its collection | its
-# evaluation | its update | the recording evaluation
+# evaluation | its update | a sweep of deep-sets leaders | of transformer leaders | the recording evaluation
 SOURCES = [os.path.join(CSRC, f) for f in ("evac_api.hip", "evac_train_api.hip", "evac_population_api.hip", "evac_sweep_api.hip",
                                            "evac_deepsets_api.hip", "evac_deepsets_train_api.hip",
                                            "evac_deepsets_update_api.hip", "evac_transformer_api.hip",
                                            "evac_transformer_train_api.hip", "evac_transformer_update_api.hip",
                                            "evac_deepsets_population_api.hip", "evac_deepsets_population_evaluate_api.hip",
                                            "evac_transformer_population_api.hip", "evac_transformer_population_evaluate_api.hip",
-                                           "evac_transformer_population_update_api.hip", "evac_capture_api.hip")]
+                                           "evac_transformer_population_update_api.hip", "evac_deepsets_sweep_api.hip",
+                                           "evac_transformer_sweep_api.hip", "evac_capture_api.hip")]
 # what the library is built from: every source and header under csrc/, and the public header last
 DEPENDS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [
     os.path.join(os.path.dirname(HERE), "include", "evac.h")]

@@ -13,6 +13,14 @@
 static_assert(evac::kSetHidden == kSetEncoderHidden && evac::kSetMaxElemDim == kSetEncoderMaxElemDim,
               "deepsets_check: the widths the deep-sets kernels take");
 
+namespace evac {
+// k_collect_population_deepsets on `stream` (evac_deepsets_population_api.hip; the sweep's unit launches it on a raw env, where no
+// gamma enters collection): a plain host function, so that the kernel is instantiated in one translation unit alone
+void deepsets_population_launch_collect(const evac_host::HandleView& v, int n_steps, const PolicyArgs& a, const NormArgs& na,
+                                        int n_learners, const PopulationArgs& q, const DeepSetsArgs& ea, const DeepSetsStrides& dq,
+                                        hipStream_t stream);
+}  // namespace evac
+
 namespace {
 
 // `check` comes after the policy's thirteen tensors; every refusal of a set encoder is EVAC_ERR_INVALID_ARGUMENT.

@@ -21,6 +21,15 @@ static_assert(sizeof(evac::Params) + 8 + sizeof(evac::PolicyArgs) + sizeof(evac:
                       sizeof(evac::DeepSetsArgs) + sizeof(evac::DeepSetsStrides) <= 4096,
               "k_collect_population_deepsets: arguments beyond the kernel-argument segment");
 
+namespace evac {
+void deepsets_population_launch_collect(const evac_host::HandleView& v, int n_steps, const PolicyArgs& a, const NormArgs& na,
+                                        int n_learners, const PopulationArgs& q, const DeepSetsArgs& ea, const DeepSetsStrides& dq,
+                                        hipStream_t stream) {
+    const auto fn = EVAC_PICK_BOOL2(k_collect_population_deepsets, na.state != nullptr, v.default_cfg);
+    hipLaunchKernelGGL(fn, dim3((unsigned)(n_learners * q.wgs)), dim3(PolicyFamily::kBlock), 0, stream, v.p, n_steps, a, na, q, ea, dq);
+}
+}  // namespace evac
+
 namespace {
 
 // evac_handle_host.h's trait of an encoder, for the population's collection entry (the lone kernels are evac_deepsets_api.hip's)
@@ -31,8 +40,7 @@ struct DeepSetsPopulationEncoder : DeepSetsEncoderHost {
 struct DeepSetsLearners : DeepSetsLearnerShares {
     void launch(const evac_host::HandleView& v, int n_steps, const evac::PolicyArgs& a, const evac::NormArgs& na,
                 const evac::DeepSetsArgs& ea, hipStream_t S) const {
-        const auto fn = EVAC_PICK_BOOL2(evac::k_collect_population_deepsets, na.state != nullptr, v.default_cfg);
-        hipLaunchKernelGGL(fn, dim3((unsigned)(n_learners * q.wgs)), dim3(evac::PolicyFamily::kBlock), 0, S, v.p, n_steps, a, na, q, ea, dq);
+        evac::deepsets_population_launch_collect(v, n_steps, a, na, n_learners, q, ea, dq, S);
     }
 };
 

@@ -8,20 +8,9 @@
 #pragma once
 
 #include "evac_learner.h"
+#include "evac_sweep_args.h"                    // LearnerLoss, LearnerSteps, LearnerDiscounts
 
 namespace evac {
-
-struct LearnerLoss {                            // RpoArgs.clip / ent / vf / alpha per learner: 1 KiB
-    float clip[kMaxLearners], ent[kMaxLearners], vf[kMaxLearners], alpha[kMaxLearners];
-};
-struct LearnerSteps {                           // AdamArgs.lr / target_kl / max_norm / use_target_kl per learner: 1.3 KiB
-    double lr[kMaxLearners], target_kl[kMaxLearners];
-    float max_norm[kMaxLearners];
-    uint64_t use_target_kl;                     // bit s: learner s has a target
-};
-struct LearnerDiscounts {                       // k_gae's gamma and gl per learner: 512 bytes
-    float gamma[kMaxLearners], gl[kMaxLearners];
-};
 
 __device__ __forceinline__ RpoArgs learner_loss_args(RpoArgs a, const LearnerLoss& h, int s) {
     a.clip = h.clip[s]; a.ent = h.ent[s]; a.vf = h.vf[s]; a.alpha = h.alpha[s];

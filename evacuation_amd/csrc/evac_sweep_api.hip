@@ -11,6 +11,7 @@
 
 #include "evac_population_host.h"
 #include "evac_sweep.h"
+#include "evac_sweep_host.h"
 
 static_assert(sizeof(evac_learner_hyper_t) == 56, "evac_learner_hyper_t: four doubles, five floats, one int32");
 // every kernel's arguments against the 4 KiB of the kernel-argument segment
@@ -20,6 +21,19 @@ static_assert(sizeof(evac::AdamArgs) + sizeof(evac::LearnerStrides) + sizeof(eva
               "k_sweep_optimizer: arguments beyond the kernel-argument segment");
 static_assert(4 + 8 + 5 * sizeof(void*) + 8 + sizeof(evac::LearnerDiscounts) + 2 * sizeof(void*) + 8 <= 4096,
               "k_sweep_advantages: arguments beyond the kernel-argument segment");
+
+// The launches the sweeps of the encoder leaders reuse on their common encoded batch (evac_sweep_host.h)
+namespace evac {
+void sweep_launch_grad(const RpoArgs& a, const LearnerStrides& q, const LearnerDraws& d, const LearnerLoss& h, const AdamHeader* gate,
+                       dim3 grid, size_t lds, hipStream_t stream) {
+    hipLaunchKernelGGL(k_sweep_grad, grid, dim3(kGradBlock), lds, stream, a, q, d, h, gate);
+}
+void sweep_launch_finish(const RpoArgs& a, const LearnerStrides& q, const LearnerDraws& d, const LearnerLoss& h, const AdamHeader* gate,
+                         dim3 grid, hipStream_t stream) {
+    hipLaunchKernelGGL(k_sweep_finish, grid, dim3(kFinishBlock), 0, stream, a, q, d, h, gate);
+}
+int sweep_raise_grad_lds(int D, int dev) { return rpo_raise_lds<k_sweep_grad>(D, dev); }
+}  // namespace evac
 
 extern "C" {
 
@@ -63,16 +77,9 @@ int evac_rpo_update_sweep(int32_t n_learners, const evac_mlp_policy_t* policy, c
                                       stats_out, workspace, a, o, q, d);
     if (rc != EVAC_OK) return rc;
     if (!learner_hypers_ok(hypers, n_learners)) return EVAC_ERR_INVALID_ARGUMENT;
-    evac::LearnerLoss hl{};
-    evac::LearnerSteps hs{};
-    for (int s = 0; s < n_learners; ++s) {
-        const evac_learner_hyper_t& y = hypers[s];
-        hl.clip[s] = y.clip_coef; hl.ent[s] = y.ent_coef; hl.vf[s] = y.vf_coef; hl.alpha[s] = y.rpo_alpha;
-        hs.lr[s] = y.learning_rate;
-        hs.max_norm[s] = y.max_grad_norm;
-        hs.target_kl[s] = y.use_target_kl ? y.target_kl : 0.0;
-        if (y.use_target_kl) hs.use_target_kl |= (uint64_t)1 << s;
-    }
+    evac::LearnerLoss hl;
+    evac::LearnerSteps hs;
+    learner_values(hypers, n_learners, hl, hs);
     const int dev = device_of(workspace);
     DeviceGuard g(dev);
     if (rpo_raise_lds<evac::k_sweep_grad>(a.D, dev) != EVAC_OK) return EVAC_ERR_HIP;

@@ -22,6 +22,14 @@ static_assert(evac::kTfHeads == kTransformerHeads && evac::kTfFeedForward == kTr
                   evac::kWave == kTransformerMaxTokens && evac::kTfLnEps == kTransformerLnEps,
               "evac_transformer_host.h's limits are the kernels'");
 
+namespace evac {
+// k_collect_population_transformer on `stream` (evac_transformer_population_api.hip; the sweep's unit launches it on a raw env,
+// where no gamma enters collection): a plain host function, so that the kernel is instantiated in one translation unit alone
+void transformer_population_launch_collect(const evac_host::HandleView& v, int n_steps, const PolicyArgs& a, const NormArgs& na,
+                                           int n_learners, const PopulationArgs& q, const TransformerArgs& ea,
+                                           const TransformerStrides& tq, hipStream_t stream);
+}  // namespace evac
+
 namespace {
 
 // `check` comes after the policy's thirteen tensors: what the kernels take of the encoder's sizes, then the handle's tokens, then

@@ -3,7 +3,7 @@
 // (evac_transformer_env_host.h's TransformerLearnerShares, which the evaluation entry of
 // evac_transformer_population_evaluate_api.hip shares): every refusal before the first HIP call, the handle joined, one kernel on the
 // stream, no synchronisation.  A unit of its own: the kernel list of evac_transformer_api.hip stays what it is.  The update of
-// such a population is not built.
+// such a population is evac_transformer_population_update_api.hip's, its sweep evac_transformer_sweep_api.hip's.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -22,6 +22,15 @@ static_assert(sizeof(evac::Params) + 8 + sizeof(evac::PolicyArgs) + sizeof(evac:
 static_assert(sizeof(evac::PolicyFamily::Smem) + sizeof(evac::PolicySmem<false>) + sizeof(evac::TransformerSmem) <= 160 * 1024,
               "k_collect_population_transformer: LDS beyond a CU's 160 KiB");
 
+namespace evac {
+void transformer_population_launch_collect(const evac_host::HandleView& v, int n_steps, const PolicyArgs& a, const NormArgs& na,
+                                           int n_learners, const PopulationArgs& q, const TransformerArgs& ea,
+                                           const TransformerStrides& tq, hipStream_t stream) {
+    const auto fn = EVAC_PICK_BOOL2(k_collect_population_transformer, na.state != nullptr, v.default_cfg);
+    hipLaunchKernelGGL(fn, dim3((unsigned)(n_learners * q.wgs)), dim3(PolicyFamily::kBlock), 0, stream, v.p, n_steps, a, na, q, ea, tq);
+}
+}  // namespace evac
+
 namespace {
 
 // evac_handle_host.h's trait of an encoder, for the population's collection entry (the lone kernels are evac_transformer_api.hip's)
@@ -32,8 +41,7 @@ struct TransformerPopulationEncoder : TransformerEncoderHost {
 struct TransformerLearners : TransformerLearnerShares {
     void launch(const evac_host::HandleView& v, int n_steps, const evac::PolicyArgs& a, const evac::NormArgs& na,
                 const evac::TransformerArgs& ea, hipStream_t S) const {
-        const auto fn = EVAC_PICK_BOOL2(evac::k_collect_population_transformer, na.state != nullptr, v.default_cfg);
-        hipLaunchKernelGGL(fn, dim3((unsigned)(n_learners * q.wgs)), dim3(evac::PolicyFamily::kBlock), 0, S, v.p, n_steps, a, na, q, ea, tq);
+        evac::transformer_population_launch_collect(v, n_steps, a, na, n_learners, q, ea, tq, S);
     }
 };
 

@@ -18,7 +18,7 @@ update is a chain of small launches on a nearly idle chip; here learner s rides 
   views.  ``PopulationAdam``, ``policy_rollout_population`` and ``PopulationTrainer`` take one as they take a ``PolicyPopulation``;
   its update is ``deepsets_update_population`` (``evac_deepsets_update_population``: seven launches per minibatch step, as for one
   such learner), its evaluation ``evac_policy_evaluate_population_deepsets`` (``PopulationEvaluator`` and ``evaluate()`` take
-  it as they take a ``PolicyPopulation``).  Sweeps of such learners are not built.
+  it as they take a ``PolicyPopulation``).  A sweep of such learners is opt-in: the last item.
 * ``TransformerPopulation``: the transformer leader's 13 + 16 per block stacked tensors, ``nets[s]`` a ``TransformerActorCritic``
   of views.  What runs such learners ON A HANDLE'S ENVS takes one -- ``policy_rollout_population``
   (``evac_policy_rollout_population_transformer``), ``policy_evaluate_population`` and ``PopulationEvaluator``
@@ -27,12 +27,17 @@ update is a chain of small launches on a nearly idle chip; here learner s rides 
   ``TransformerAdam`` on row s), ``transformer_update_population`` (``evac_transformer_update_population``: 6 + num_blocks +
   norm_adv launches per minibatch step, as for one such learner) and ``PopulationTrainer(..., optimizer="device_transformer")``,
   under ONE configuration.  The default faces -- ``PopulationAdam(population)`` and ``PopulationTrainer(env, population, cfg)``
-  -- keep refusing one; sweeps of such learners are not built.
+  -- keep refusing one; a sweep of such learners is opt-in: the last item.
 * Sweeps: every float-valued hyperparameter (``SWEEP_FIELDS``) may differ per learner -- ``PopulationTrainer(env, population,
   [cfg_0, .., cfg_S-1])``, ``rpo_update_population(cfg=[...])``, ``gae(gamma=[...])``, ``policy_rollout_population(gammas=[...])``;
   ``sweep_configs`` makes the cartesian product.  The learners' values ride in the kernel arguments beside their seeds
   (``evac_rpo_update_sweep``, ``evac_gae_learners``, ``evac_policy_rollout_sweep``).  What fixes launch geometry, step counts
   or storage shape (``STRUCTURAL_FIELDS``) stays one value for all.
+* Sweeps of the two encoder populations, opt-in under names of their own (every default face keeps its refusal):
+  ``policy_rollout_sweep(population, .., gammas)`` on both envs (``evac_policy_rollout_sweep_deepsets`` / ``_transformer``),
+  ``deepsets_update_sweep`` / ``transformer_update_sweep`` (``evac_deepsets_update_sweep`` / ``evac_transformer_update_sweep``: the
+  population's launches, the loss coefficients in the kernel arguments, the optimiser's values in a table at the workspace's
+  tail that one small launch per call fills) and ``PopulationTrainer(env, population, cfgs, ..., encoder_sweep=True)``.
 
 Learner s is BIT FOR BIT the ``RPOTrainer(optimizer="device", one_call=True)`` it would be alone on an env of ``E_l`` envs with the
 population env's seed and ``env_id_offset`` further by ``s E_l``, with its own configuration, ``cfg.seed = seeds[s]`` and the
@@ -368,12 +373,15 @@ def _batch_ptrs(batch: Dict[str, torch.Tensor]):
 
 
 def population_workspace_bytes(obs_dim: int, minibatch_size: int, num_learners: int, *, deepsets: bool = False,
-                               transformer: bool = False) -> int:
+                               transformer: bool = False, sweep: bool = False) -> int:
     """The update's workspace for a ``PolicyPopulation``, or with ``deepsets`` for a ``DeepSetsPopulation``, or with
-    ``transformer`` for a ``TransformerPopulation`` (both at once is a ``ValueError``)."""
+    ``transformer`` for a ``TransformerPopulation`` (both at once is a ``ValueError``).  ``sweep``: what
+    ``deepsets_update_sweep`` / ``transformer_update_sweep`` need (``evac_*_sweep_workspace_bytes``: the population's, then the
+    table of the learners' optimiser values); a ``PolicyPopulation``'s sweep needs no more than its population."""
     if deepsets and transformer:
         raise ValueError("population_workspace_bytes: deepsets and transformer name two kinds of population")
-    sizer = f"evac_{'transformer' if transformer else 'deepsets' if deepsets else 'rpo'}_population_workspace_bytes"
+    kind = "transformer" if transformer else "deepsets" if deepsets else "rpo"
+    sizer = f"evac_{kind}_{'sweep' if sweep and kind != 'rpo' else 'population'}_workspace_bytes"
     need = int(getattr(_lib.load(), sizer)(int(obs_dim), int(minibatch_size), int(num_learners)))
     if need < 0:
         raise _lib.EvacError(need, f"{sizer}({obs_dim}, {minibatch_size}, {num_learners})")
@@ -423,7 +431,7 @@ def deepsets_update_population(population: DeepSetsPopulation, batch: Dict[str, 
     ``deepsets_update(population.nets[s], its own rows, cfg, DeviceAdam(nets[s]), seed=seeds[s],
     first_draw_counter=first_draw_counters[s])`` alone.  Seven launches per minibatch step (six without ``norm_adv``), no host
     synchronisation.  A sequence of configurations, or an optimiser whose learners differ in ``lr`` / ``max_grad_norm``, is a
-    ``ValueError``: sweeps of deep-sets learners are not built."""
+    ``ValueError`` here ("sweeps of deep-sets learners are not built" into this entry): that is ``deepsets_update_sweep``."""
     if not isinstance(population, DeepSetsPopulation):
         raise ValueError("deepsets_update_population: a DeepSetsPopulation is expected (a PolicyPopulation's update is "
                          "rpo_update_population)")
@@ -444,7 +452,8 @@ def transformer_update_population(population: TransformerPopulation, batch: Dict
     learner s is, bit for bit, ``transformer_update(population.nets[s], its own rows, cfg, TransformerAdam(nets[s]),
     seed=seeds[s], first_draw_counter=first_draw_counters[s])`` alone.  ``6 + num_blocks`` launches per minibatch step and one
     more with ``norm_adv``, no host synchronisation.  A sequence of configurations, or an optimiser whose learners differ in
-    ``lr`` / ``max_grad_norm``, is a ``ValueError``: sweeps of transformer learners are not built."""
+    ``lr`` / ``max_grad_norm``, is a ``ValueError`` here ("sweeps of transformer learners are not built" into this entry): that is
+    ``transformer_update_sweep``."""
     if not isinstance(population, TransformerPopulation):
         raise ValueError("transformer_update_population: a TransformerPopulation is expected (a PolicyPopulation's update is "
                          "rpo_update_population, a DeepSetsPopulation's deepsets_update_population)")
@@ -459,9 +468,48 @@ def transformer_update_population(population: TransformerPopulation, batch: Dict
                               "transformer_update_population")
 
 
-def _update_population(population, batch, rows, cfg, opt, minibatch_size, rpo_noise, seeds, first_draw_counters, stats, workspace, what):
-    """The body of ``rpo_update_population``, ``deepsets_update_population`` and ``transformer_update_population`` (``what``: the
-    caller's name)."""
+def deepsets_update_sweep(population: DeepSetsPopulation, batch: Dict[str, torch.Tensor], rows: torch.Tensor, cfg, opt: PopulationAdam,
+                          *, minibatch_size: Optional[int] = None, rpo_noise: Optional[torch.Tensor] = None,
+                          seeds: Optional[Sequence[int]] = None, first_draw_counters: Optional[Sequence[int]] = None,
+                          stats: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """``deepsets_update_population`` with a configuration per learner (``evac_deepsets_update_sweep``): the same arguments and
+    returns; ``cfg`` is one configuration or a sequence of S, and the optimiser's per-learner ``lr`` / ``max_grad_norm`` are
+    honoured.  Learner s is, bit for bit, ``deepsets_update(population.nets[s], its own rows, cfg[s], DeviceAdam(nets[s],
+    lr=.., max_grad_norm=..), seed=seeds[s], first_draw_counter=first_draw_counters[s])`` alone: its loss runs with
+    ``cfg[s]``'s ``clip_coef`` / ``ent_coef`` / ``vf_coef`` / ``rpo_alpha`` / ``target_kl``.  ``norm_adv``, ``clip_vloss`` and the
+    minibatch size are learner 0's and must be everybody's.  The population's launches and one small one per call; the
+    workspace is ``population_workspace_bytes(..., deepsets=True, sweep=True)``."""
+    if not isinstance(population, DeepSetsPopulation):
+        raise ValueError("deepsets_update_sweep: a DeepSetsPopulation is expected (a PolicyPopulation's sweep is "
+                         "rpo_update_population with a sequence of configurations)")
+    return _update_population(population, batch, rows, cfg, opt, minibatch_size, rpo_noise, seeds, first_draw_counters, stats, workspace,
+                              "deepsets_update_sweep", sweep=True)
+
+
+def transformer_update_sweep(population: TransformerPopulation, batch: Dict[str, torch.Tensor], rows: torch.Tensor, cfg,
+                             opt: TransformerPopulationAdam, *, minibatch_size: Optional[int] = None,
+                             rpo_noise: Optional[torch.Tensor] = None, seeds: Optional[Sequence[int]] = None,
+                             first_draw_counters: Optional[Sequence[int]] = None, stats: Optional[torch.Tensor] = None,
+                             workspace: Optional[torch.Tensor] = None):
+    """``transformer_update_population`` with a configuration per learner (``evac_transformer_update_sweep``), as
+    ``deepsets_update_sweep`` is ``deepsets_update_population``'s: learner s is, bit for bit, ``transformer_update(
+    population.nets[s], its own rows, cfg[s], TransformerAdam(nets[s], lr=.., max_grad_norm=..), seed=seeds[s],
+    first_draw_counter=first_draw_counters[s])`` alone.  A dropout probability other than 0 is a ``ValueError``."""
+    if not isinstance(population, TransformerPopulation):
+        raise ValueError("transformer_update_sweep: a TransformerPopulation is expected (a PolicyPopulation's sweep is "
+                         "rpo_update_population with a sequence of configurations, a DeepSetsPopulation's deepsets_update_sweep)")
+    if not isinstance(opt, TransformerPopulationAdam):
+        raise ValueError(f"transformer_update_sweep: a TransformerPopulationAdam is expected, got {type(opt).__name__}")
+    for net in population.nets:
+        refuse_dropout(net, "transformer_update_sweep")
+    return _update_population(population, batch, rows, cfg, opt, minibatch_size, rpo_noise, seeds, first_draw_counters, stats, workspace,
+                              "transformer_update_sweep", sweep=True)
+
+
+def _update_population(population, batch, rows, cfg, opt, minibatch_size, rpo_noise, seeds, first_draw_counters, stats, workspace, what,
+                       sweep=False):
+    """The body of ``rpo_update_population``, ``deepsets_update_population``, ``transformer_update_population`` and the two
+    encoder sweeps (``what``: the caller's name; ``sweep``: an encoder population goes to its ``evac_*_update_sweep``)."""
     deepsets = isinstance(population, DeepSetsPopulation)
     transformer = isinstance(population, TransformerPopulation)
     if opt.population is not population:
@@ -477,7 +525,7 @@ def _update_population(population, batch, rows, cfg, opt, minibatch_size, rpo_no
                 if getattr(c, f, True) != getattr(cfgs[0], f, True):
                     raise ValueError(f"{what}: {f} of learner {s} differs from learner 0's")
         cfg = cfgs[0]
-    elif not opt.uniform():
+    elif sweep or not opt.uniform():
         cfgs = [cfg] * S
     B, D, b_args = _batch_ptrs(batch)
     if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int64 or rows.device != batch["b_obs"].device or \
@@ -496,7 +544,7 @@ def _update_population(population, batch, rows, cfg, opt, minibatch_size, rpo_no
         stats = torch.zeros(S, steps, 8, dtype=torch.float32, device=dev)
     else:
         _f32(stats, (S, steps, 8), "stats")
-    need = population_workspace_bytes(D, M, S, deepsets=deepsets, transformer=transformer)
+    need = population_workspace_bytes(D, M, S, deepsets=deepsets, transformer=transformer, sweep=sweep)
     if workspace is None or workspace.numel() < need or workspace.device != dev:
         workspace = torch.empty(need, dtype=torch.uint8, device=dev)
     seeds = population.seeds if seeds is None else [int(x) for x in seeds]
@@ -519,11 +567,12 @@ def _update_population(population, batch, rows, cfg, opt, minibatch_size, rpo_no
         enc_params = enc_struct(*(t.data_ptr() for t in population.tensors[13:]))
         enc_grads = enc_struct(*(g.data_ptr() for g in population.grads[13:]))
         es = population.encoder_strides
-        entry = _lib.load().evac_transformer_update_population if transformer else _lib.load().evac_deepsets_update_population
+        entry = getattr(_lib.load(), f"evac_{'transformer' if transformer else 'deepsets'}_update_{'sweep' if sweep else 'population'}")
+        values = [learner_hypers(cfgs, opt)] if sweep else [int(target_kl is not None), float(target_kl or 0.0)]
         rc = entry(
             S, C.byref(pol), C.byref(population.encoder_struct()), C.byref(params), C.byref(enc_params), C.byref(grads), C.byref(enc_grads),
             C.byref(population.strides), C.byref(es), C.byref(population.strides), C.byref(es), C.byref(opt.moment_strides),
-            C.byref(opt.encoder_moment_strides), *rest, int(target_kl is not None), float(target_kl or 0.0), *tail)
+            C.byref(opt.encoder_moment_strides), *rest, *values, *tail)
         _lib.check(rc)
         return stats, opt.headers
     head = [S, C.byref(pol), C.byref(params), C.byref(grads), C.byref(population.strides), C.byref(population.strides),
@@ -551,9 +600,14 @@ class PopulationTrainer:
     ``optimizer="device_transformer"`` it trains as a ``DeepSetsPopulation`` does, under ONE configuration (learner s is then
     ``RPOTrainer(grad_fn=transformer_kernel_grad, optimizer="device_transformer", one_call=True)`` alone; ``self.optimizer`` is a
     ``TransformerPopulationAdam``, the update ``transformer_update_population``; a dropout probability other than 0 in any
-    learner is a ``ValueError``).  That value with any other population is a ``ValueError``."""
+    learner is a ``ValueError``).  That value with any other population is a ``ValueError``.  ``encoder_sweep=True``: a
+    ``DeepSetsPopulation`` (or, with ``optimizer="device_transformer"``, a ``TransformerPopulation``) trains under S
+    configurations that may differ in ``SWEEP_FIELDS`` as a ``PolicyPopulation``'s may -- collection through
+    ``policy_rollout_sweep``, ``gae`` per learner, the update ``deepsets_update_sweep`` / ``transformer_update_sweep`` -- and
+    learner s is the lone trainer above with ``cfgs[s]`` on an env wrapped with its own gamma; the keyword with a
+    ``PolicyPopulation`` is a ``ValueError`` (its default path already sweeps)."""
 
-    def __init__(self, env, population, cfgs, *, optimizer: Optional[str] = None):
+    def __init__(self, env, population, cfgs, *, optimizer: Optional[str] = None, encoder_sweep: bool = False):
         if optimizer not in (None, "device_transformer"):
             raise ValueError(f"PopulationTrainer: optimizer = {optimizer!r}: expected None or \"device_transformer\"")
         refuse_deepsets(population, "PopulationTrainer")       # (a network where the population goes)
@@ -564,20 +618,26 @@ class PopulationTrainer:
             raise ValueError("PopulationTrainer(optimizer=\"device_transformer\") trains a TransformerPopulation; "
                              f"got {type(population).__name__}")
         self.deepsets = isinstance(population, DeepSetsPopulation)
+        self.encoder_sweep = bool(encoder_sweep)
+        if self.encoder_sweep and not (self.deepsets or self.transformer):
+            raise ValueError("PopulationTrainer(encoder_sweep=True) is for a DeepSetsPopulation or a TransformerPopulation: with a "
+                             f"{type(population).__name__} the default path already sweeps (pass the sequence of configurations)")
         for net in getattr(population, "nets", ()):
             if self.transformer:
                 refuse_dropout(net, "PopulationTrainer")
             else:
                 (refuse_transformer if self.deepsets else refuse_deepsets)(net, "PopulationTrainer")
         S = population.num_learners
-        if (self.deepsets or self.transformer) and isinstance(cfgs, (list, tuple)):
+        if (self.deepsets or self.transformer) and isinstance(cfgs, (list, tuple)) and not self.encoder_sweep:
             if len(cfgs) != S:
                 raise ValueError(f"PopulationTrainer: {len(cfgs)} configurations for {S} learners")
             if any(dataclasses.replace(c, seed=cfgs[0].seed) != cfgs[0] for c in cfgs):
                 kind = "transformer learners" if self.transformer else "deep-sets learners"
                 raise ValueError(f"PopulationTrainer: sweeps of {kind} are not built: a {type(population).__name__} trains under "
-                                 "ONE configuration")
+                                 "ONE configuration (unless encoder_sweep=True is given: the sweep is opt-in)")
             cfgs = cfgs[0]
+        if self.encoder_sweep and not isinstance(cfgs, (list, tuple)):
+            cfgs = [cfgs] * S
         self.sweep = isinstance(cfgs, (list, tuple))
         if self.sweep:
             self.cfgs = list(cfgs)
@@ -628,9 +688,13 @@ class PopulationTrainer:
         if self.start_time is None:
             self.start_time = time.time()
         with torch.no_grad():
-            kw = {"gammas": [c.gamma for c in self.cfgs]} if self.sweep else {}
-            self.storage = self.env.policy_rollout_population(self.population, self.cfg.num_steps, self.next_obs, self.next_done,
-                                                              out=self.storage, **kw)
+            if self.encoder_sweep:
+                self.storage = self.env.policy_rollout_sweep(self.population, self.cfg.num_steps, self.next_obs, self.next_done,
+                                                             [c.gamma for c in self.cfgs], out=self.storage)
+            else:
+                kw = {"gammas": [c.gamma for c in self.cfgs]} if self.sweep else {}
+                self.storage = self.env.policy_rollout_population(self.population, self.cfg.num_steps, self.next_obs, self.next_done,
+                                                                  out=self.storage, **kw)
             out = None if self.advantages is None else (self.advantages, self.returns)
             if self.sweep:
                 self.advantages, self.returns = gae(self.storage, [c.gamma for c in self.cfgs], [c.gae_lambda for c in self.cfgs],
@@ -657,11 +721,14 @@ class PopulationTrainer:
         if self.stats_rows is None or self.stats_rows.shape[1] != steps:
             self.stats_rows = torch.zeros(S, steps, 8, dtype=torch.float32, device=self.device)
         need = population_workspace_bytes(self.population.obs_dim, min(cfg.minibatch_size, B_l), S, deepsets=self.deepsets,
-                                          transformer=self.transformer)
+                                          transformer=self.transformer, sweep=self.encoder_sweep)
         if self.workspace is None or self.workspace.numel() < need:
             self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        update = (transformer_update_population if self.transformer else
-                  deepsets_update_population if self.deepsets else rpo_update_population)
+        if self.encoder_sweep:
+            update = transformer_update_sweep if self.transformer else deepsets_update_sweep
+        else:
+            update = (transformer_update_population if self.transformer else
+                      deepsets_update_population if self.deepsets else rpo_update_population)
         stats, headers = update(self.population, batch, rows, self.cfgs if self.sweep else cfg, self.optimizer,
                                 first_draw_counters=self.minibatch_steps, stats=self.stats_rows, workspace=self.workspace)
         self.update_index += 1

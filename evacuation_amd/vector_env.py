@@ -634,6 +634,21 @@ class BatchedEvacuationEnv:
         hypers = None if gammas is None else _lib.learner_hypers(population.num_learners, gamma=[float(g) for g in gammas])
         return self._policy_rollout(population.nets[0], population, n_steps, next_obs, next_done, out, _norm, hypers)
 
+    def policy_rollout_sweep(self, population, n_steps: int, next_obs: torch.Tensor, next_done: torch.Tensor, gammas,
+                             out: Optional[TDict] = None, _norm=None):
+        """``policy_rollout_population`` with the learners' training gammas (a sequence of S), for every kind of population.  A
+        ``DeepSetsPopulation`` or ``TransformerPopulation`` goes to ``evac_policy_rollout_sweep_deepsets`` / ``_transformer``
+        (learner s's columns hold, bit for bit, what ``policy_rollout(population.nets[s], ...)`` writes on its own env wrapped
+        with ``gammas[s]``); a ``PolicyPopulation`` is forwarded to ``policy_rollout_population(gammas=)``.  On this raw env
+        ``gammas`` is checked and has no effect; ``NormalizedVectorEnv.policy_rollout_sweep`` runs learner s's chain with
+        ``gammas[s]``.  A transformer learner with a dropout probability other than 0 is refused, as there."""
+        if not (self._is_set_population(population) or self._is_transformer_population(population)):
+            return self.policy_rollout_population(population, n_steps, next_obs, next_done, out=out, _norm=_norm, gammas=gammas)
+        if self.num_envs % population.num_learners:
+            raise ValueError(f"policy_rollout_sweep: {self.num_envs} envs are not {population.num_learners} learners' equal shares")
+        hypers = _lib.learner_hypers(population.num_learners, gamma=[float(g) for g in gammas])
+        return self._policy_rollout(population.nets[0], population, n_steps, next_obs, next_done, out, _norm, hypers)
+
     @staticmethod
     def _is_set_population(population) -> bool:
         """A ``population.DeepSetsPopulation`` (the one predicate of the population's kind, as ``population.py`` has it)."""
@@ -692,7 +707,11 @@ class BatchedEvacuationEnv:
         args = [_ptr(next_obs), _ptr(next_done), _ptr(out["obs"]), _ptr(out["actions"]), _ptr(out["logprobs"]), _ptr(out["values"]),
                 _ptr(out["rewards"]), _ptr(out["dones"]), _ptr(out["next_value"]), _ptr(out["episode_stats"]), _ptr(state), gamma,
                 obs_clip, reward_clip, eps, self._stream()]
-        if set_population:                    # (learner 0's 19 tensors: the base the strides count from)
+        if (set_population or tf_population) and hypers is not None:       # (policy_rollout_sweep: the learners' gammas)
+            entry = self.lib.evac_policy_rollout_sweep_transformer if tf_population else self.lib.evac_policy_rollout_sweep_deepsets
+            rc = entry(self._h, population.num_learners, C.byref(pol), C.byref(population.strides), C.byref(enc[1]),
+                       C.byref(population.encoder_strides), T, *args[:-1], hypers, args[-1])
+        elif set_population:                  # (learner 0's 19 tensors: the base the strides count from)
             rc = self.lib.evac_policy_rollout_population_deepsets(self._h, population.num_learners, C.byref(pol), C.byref(population.strides),
                                                                   C.byref(enc[1]), C.byref(population.encoder_strides), T, *args)
         elif tf_population:                   # (learner 0's 13 + 16 num_blocks tensors likewise)

@@ -75,6 +75,13 @@ class NormalizedVectorEnv:
         return self.env.policy_rollout_population(population, n_steps, next_obs, next_done, out=out, gammas=gammas,
                                                   _norm=(self.norm_state, self.gamma, self.obs_clip, self.reward_clip, self.epsilon))
 
+    def policy_rollout_sweep(self, population, n_steps: int, next_obs, next_done, gammas, out=None):
+        """``BatchedEvacuationEnv.policy_rollout_sweep`` through the trainer's chain: learner s's reward normaliser runs with
+        ``gammas[s]`` in place of this env's ``gamma``, for every kind of population (a ``DeepSetsPopulation`` /
+        ``TransformerPopulation``: ``evac_policy_rollout_sweep_deepsets`` / ``_transformer``)."""
+        return self.env.policy_rollout_sweep(population, n_steps, next_obs, next_done, gammas, out=out,
+                                             _norm=(self.norm_state, self.gamma, self.obs_clip, self.reward_clip, self.epsilon))
+
     def policy_evaluate(self, agent, n_episodes: int, max_steps: int, progress=None, out=None, *, deterministic: bool = True,
                         capture=None):
         """``BatchedEvacuationEnv.policy_evaluate`` with this env's observation statistics applied FROZEN: the policy reads

@@ -21,7 +21,9 @@ Adam -- or, with ``--gradient device --optimizer device``, the library's clip + 
 host call (``evac_deepsets_update``: seven launches per step).  With ``--seeds`` the learners train as a population of such
 networks (``population.DeepSetsPopulation``, ``evac_deepsets_update_population``: the device gradient and optimiser, seven
 launches per step for all learners; ``--eval-every`` evaluates all of them in one set of launches,
-``evac_policy_evaluate_population_deepsets``).  Not with ``--sweep`` (sweeps of deep-sets learners are not built) or ``--compare``, nor
+``evac_policy_evaluate_population_deepsets``); ``--gradient device --optimizer device --sweep field=a,b`` trains the settings as
+one such population with a configuration per learner (``PopulationTrainer(..., encoder_sweep=True)``,
+``evac_deepsets_update_sweep``).  Not with ``--compare``, nor
 with ``--optimizer device`` under the autograd gradient: those kernels are the linear network's.
 
 ``--network transformer`` trains the reference's attention-encoder network (``policy.TransformerActorCritic``,
@@ -34,7 +36,8 @@ by ``evac_transformer_minibatch_grad`` (``trainer.transformer_kernel_grad``), an
 ``--gradient device --optimizer device --seeds`` the learners train as a population of such networks
 (``population.TransformerPopulation``, ``PopulationTrainer(..., optimizer="device_transformer")``,
 ``evac_transformer_update_population``: the same launches per step for all learners); ``--seeds`` with any other gradient /
-optimiser choice is refused.  Not with ``--sweep`` or ``--compare``, nor with ``--optimizer device`` under the autograd gradient.
+optimiser choice is refused; with ``--sweep field=a,b`` the settings train as one such population with a configuration per
+learner (``encoder_sweep=True``, ``evac_transformer_update_sweep``).  Not with ``--compare``, nor with ``--optimizer device`` under the autograd gradient.
 
 ``--eval-every K`` evaluates the leader every K updates (``RPOTrainer.evaluate``: whole episodes, the mean action, the observation
 statistics frozen) and prints the summary; ``--baseline`` prints the same line for the reference's scripted sweep baseline
@@ -135,20 +138,22 @@ def make_population_trainer(args, seeds, grid=None):
     cfg = RPOTrainingConfig(num_envs=args.envs, num_steps=args.steps, total_timesteps=args.envs * args.steps * max(args.updates, 1),
                             num_minibatches=args.minibatches, update_epochs=args.epochs)
     cfgs = cfg
-    if getattr(args, "network", "linear") == "deep_sets":        # a population of set-encoder networks (no sweep: main refuses it)
+    encoder = getattr(args, "network", "linear") in ("deep_sets", "transformer")
+    if grid is not None:                                         # one learner per (setting, seed)
+        pairs = sweep_configs(cfg, grid, seeds)
+        seeds, cfgs = [s for s, _ in pairs], [c for _, c in pairs]
+    sweep = {"encoder_sweep": True} if encoder and grid is not None else {}
+    if getattr(args, "network", "linear") == "deep_sets":        # a population of set-encoder networks (a sweep: main asks device + device)
         env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=args.pedestrians, is_new_exiting_reward=True),
                                           ea.EnvWrappersConfig(positions="rel", statuses="ohe", type="Box"),
                                           num_envs=args.envs * len(seeds), gamma=cfg.gamma, seed=1)
-        return PopulationTrainer(env, DeepSetsPopulation(env.obs_dim, args.pedestrians, seeds, DEV), cfgs)
+        return PopulationTrainer(env, DeepSetsPopulation(env.obs_dim, args.pedestrians, seeds, DEV), cfgs, **sweep)
     if getattr(args, "network", "linear") == "transformer":      # a population of attention-encoder networks (main: device + device)
         env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=args.pedestrians, is_new_exiting_reward=True),
                                           ea.EnvWrappersConfig(positions="rel", statuses="ohe", type="Box"),
                                           num_envs=args.envs * len(seeds), gamma=cfg.gamma, seed=1)
         population = TransformerPopulation(env.obs_dim, args.pedestrians, seeds, DEV, num_blocks=args.blocks, use_resid=args.use_resid)
-        return PopulationTrainer(env, population, cfgs, optimizer="device_transformer")
-    if grid is not None:                                         # one learner per (setting, seed)
-        pairs = sweep_configs(cfg, grid, seeds)
-        seeds, cfgs = [s for s, _ in pairs], [c for _, c in pairs]
+        return PopulationTrainer(env, population, cfgs, optimizer="device_transformer", **sweep)
     env = ea.NormalizedVectorEnv.make(ea.EnvConfig(number_of_pedestrians=args.pedestrians, is_new_exiting_reward=True),
                                       ea.EnvWrappersConfig(positions="grav", alpha=3), num_envs=args.envs * len(seeds), gamma=cfg.gamma,
                                       seed=1)
@@ -317,18 +322,19 @@ def main():
     if args.gradient == "device" and args.network == "linear":
         raise SystemExit("--gradient device goes with --network deep_sets or transformer (the linear network's gradient is the device's "
                          "anyway)")
-    if args.network == "deep_sets" and args.sweep:
-        raise SystemExit("--network deep_sets --sweep: sweeps of deep-sets learners are not built (--seeds trains a population of them "
-                         "under one configuration)")
+    device_both = args.gradient == "device" and args.optimizer == "device"
+    if args.network == "deep_sets" and args.sweep and not device_both:
+        raise SystemExit("--network deep_sets --sweep goes with --gradient device --optimizer device (the sweep of deep-sets learners is "
+                         "PopulationTrainer(..., encoder_sweep=True), on the device)")
     if args.network == "deep_sets" and (args.compare or (args.optimizer == "device" and args.gradient != "device" and not args.seeds)):
         raise SystemExit("--network deep_sets: the gradient and optimiser kernels (--optimizer device, --compare) are "
                          "the linear network's; its gradient is autograd's or --gradient device, and --optimizer device goes with "
                          "--gradient device")
-    tf_population = args.seeds and args.gradient == "device" and args.optimizer == "device"
-    if args.network == "transformer" and (args.compare or (args.seeds and not tf_population) or args.sweep or
+    tf_population = (args.seeds or args.sweep) and device_both
+    if args.network == "transformer" and (args.compare or ((args.seeds or args.sweep) and not tf_population) or
                                           (args.optimizer == "device" and args.gradient != "device")):
-        raise SystemExit("--network transformer: the sweep's and the comparison's kernels (--sweep, --compare) do not know its tensors, "
-                         "and --seeds trains a population of them with --gradient device --optimizer device alone; it trains with "
+        raise SystemExit("--network transformer: the comparison's kernels (--compare) do not know its tensors, and --seeds / --sweep "
+                         "train a population of them with --gradient device --optimizer device alone; it trains with "
                          "autograd's gradient or --gradient device, and --optimizer device goes with --gradient device")
     if args.compare:
         return compare(args)

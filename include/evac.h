@@ -1197,6 +1197,71 @@ int evac_transformer_update_population(int32_t n_learners, const evac_mlp_policy
                                        const uint64_t* first_draw_counters, int32_t use_target_kl, double target_kl, float* stats_out,
                                        void* workspace, void* stream);
 
+/* ---- SWEEPS OF THE ENCODER LEADERS: a population of deep-sets or transformer leaders with a configuration per learner ----
+ * What evac_policy_rollout_sweep / evac_rpo_update_sweep are to the linear population's entries, for the two encoder leaders:
+ * `hypers` is the HOST array evac_learner_hyper_t[n_learners] above, and learner s is, bit for bit, the lone learner with its
+ * own values (evac_deepsets_update / evac_transformer_update with hypers[s]'s clip_coef, ent_coef, vf_coef, rpo_alpha,
+ * target_kl and an optimiser at its learning_rate / max_grad_norm; collection on a handle wrapped with its gamma).  The number
+ * types are the lone entries': learning_rate and target_kl double, the four coefficients and max_grad_norm float32, the reward
+ * normaliser's gamma (float)gamma.  evac_gae_learners serves these populations as it serves the linear one.
+ *   evac_policy_rollout_sweep_deepsets / _transformer: evac_policy_rollout_population_deepsets / _transformer's arguments with
+ *   `hypers` in front of the stream; only gamma of it is read, in place of the argument `gamma`.  With a NULL norm_state gamma
+ *   does not enter collection: `hypers` is checked all the same and the population's kernel runs.  Refusals: the population
+ *   entry's in its order; behind the learners' strides a NULL `hypers` or values that evac_learner_hyper_t refuses
+ *   (EVAC_ERR_INVALID_ARGUMENT), before the alignment of actions_out.
+ *   evac_deepsets_update_sweep / evac_transformer_update_sweep: evac_*_update_population's arguments with `hypers` in place of
+ *   use_target_kl, target_kl (loss_cfg's four coefficients and adam_cfg's lr / max_grad_norm are checked and then replaced per
+ *   learner; norm_adv, clip_vloss, betas and eps are everybody's).  The launches are the population entry's, the gradient and
+ *   its finish with every learner's coefficients in their arguments, plus ONE small launch per call that copies the learners'
+ *   lr / max_grad_norm / target_kl into a table in the last bytes of the workspace, which the optimiser's kernel reads at its
+ *   learner's index.  No host synchronisation, no device allocation, capturable (a capture freezes the learners' values as it
+ *   freezes the seeds).  Refusals: the population entry's in its order, then a NULL `hypers` or refused values
+ *   (EVAC_ERR_INVALID_ARGUMENT), all on the host before anything touches a device.
+ *   workspace: evac_*_sweep_workspace_bytes(obs_dim, M, S) bytes, 16-byte aligned: the population entry's layout, unchanged,
+ *   then the table (1288 bytes rounded up to whole 256-byte parts).  The sizers refuse what the population's refuse. */
+int evac_policy_rollout_sweep_deepsets(evac_handle_t h, int32_t n_learners, const evac_mlp_policy_t* policy,
+                                       const evac_mlp_policy_strides_t* strides, const evac_deepsets_t* encoder,
+                                       const evac_deepsets_strides_t* enc_strides, int32_t n_steps, float* next_obs, float* next_done,
+                                       float* obs_out, float* actions_out, float* logprob_out, float* value_out, float* reward_out,
+                                       float* done_out, float* next_value_out, evac_episode_stats_t* final_stats_or_null,
+                                       double* norm_state_or_null, float gamma, float obs_clip, float reward_clip, float epsilon,
+                                       const evac_learner_hyper_t* hypers, void* stream);
+int evac_policy_rollout_sweep_transformer(evac_handle_t h, int32_t n_learners, const evac_mlp_policy_t* policy,
+                                          const evac_mlp_policy_strides_t* strides, const evac_transformer_t* encoder,
+                                          const evac_transformer_strides_t* enc_strides, int32_t n_steps, float* next_obs,
+                                          float* next_done, float* obs_out, float* actions_out, float* logprob_out, float* value_out,
+                                          float* reward_out, float* done_out, float* next_value_out,
+                                          evac_episode_stats_t* final_stats_or_null, double* norm_state_or_null, float gamma,
+                                          float obs_clip, float reward_clip, float epsilon, const evac_learner_hyper_t* hypers,
+                                          void* stream);
+int64_t evac_deepsets_sweep_workspace_bytes(int32_t obs_dim, int64_t n_minibatch, int32_t n_learners);
+int64_t evac_transformer_sweep_workspace_bytes(int32_t obs_dim, int64_t n_minibatch, int32_t n_learners);
+int evac_deepsets_update_sweep(int32_t n_learners, const evac_mlp_policy_t* policy, const evac_deepsets_t* encoder,
+                               const evac_mlp_policy_grads_t* params, const evac_deepsets_grads_t* enc_params,
+                               const evac_mlp_policy_grads_t* grads, const evac_deepsets_grads_t* enc_grads,
+                               const evac_mlp_policy_strides_t* param_strides, const evac_deepsets_strides_t* enc_param_strides,
+                               const evac_mlp_policy_strides_t* grad_strides, const evac_deepsets_strides_t* enc_grad_strides,
+                               const evac_mlp_policy_strides_t* moment_strides, const evac_deepsets_strides_t* enc_moment_strides,
+                               int64_t header_stride_bytes, const evac_rpo_loss_config_t* loss_cfg, const evac_adam_config_t* adam_cfg,
+                               const evac_deepsets_adam_state_t* state, int64_t batch_size, const float* b_obs, const float* b_actions,
+                               const float* b_logprobs, const float* b_advantages, const float* b_returns, const float* b_values,
+                               int64_t learner_batch_size, int64_t n_minibatch, int32_t n_epochs, const int64_t* perms,
+                               const float* rpo_noise_or_null, const uint64_t* seeds, const uint64_t* first_draw_counters,
+                               const evac_learner_hyper_t* hypers, float* stats_out, void* workspace, void* stream);
+int evac_transformer_update_sweep(int32_t n_learners, const evac_mlp_policy_t* policy, const evac_transformer_t* encoder,
+                                  const evac_mlp_policy_grads_t* params, const evac_transformer_grads_t* enc_params,
+                                  const evac_mlp_policy_grads_t* grads, const evac_transformer_grads_t* enc_grads,
+                                  const evac_mlp_policy_strides_t* param_strides, const evac_transformer_strides_t* enc_param_strides,
+                                  const evac_mlp_policy_strides_t* grad_strides, const evac_transformer_strides_t* enc_grad_strides,
+                                  const evac_mlp_policy_strides_t* moment_strides, const evac_transformer_strides_t* enc_moment_strides,
+                                  int64_t header_stride_bytes, const evac_rpo_loss_config_t* loss_cfg, const evac_adam_config_t* adam_cfg,
+                                  const evac_transformer_adam_state_t* state, int64_t batch_size, const float* b_obs,
+                                  const float* b_actions, const float* b_logprobs, const float* b_advantages, const float* b_returns,
+                                  const float* b_values, int64_t learner_batch_size, int64_t n_minibatch, int32_t n_epochs,
+                                  const int64_t* perms, const float* rpo_noise_or_null, const uint64_t* seeds,
+                                  const uint64_t* first_draw_counters, const evac_learner_hyper_t* hypers, float* stats_out,
+                                  void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,8 @@ with torch's optimiser against the device's (evac_deepsets_minibatch_step, evac_
 
     python tools/deepsets_bench.py --part a|b|c|c-eager|grad-autograd|grad-device|step-device|update-torch|update-step|update-one-call
                                    [--envs 4096] [--steps 128] [--minibatch 16384] [--epochs 10] [--reps 7]
+    python tools/deepsets_bench.py --part update-sweep|collect-sweep --learners S --envs 3 --steps 2048 --minibatch 192
+                                   (a configuration per learner against the one-configuration population: tools/encoder_sweep_bench.py)
     python tools/deepsets_bench.py --part update-population --learners S [--envs 3] [--steps 2048] [--minibatch 192] [--epochs 10]
 
 N = 60, the rel + ohe Box observation (D = 372), the trainer's normalisation chain, E envs, T steps per call; hipEvent times of
@@ -206,7 +208,8 @@ def grad_part(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", required=True, choices=["a", "b", "c", "c-eager", "grad-autograd", "grad-device", "step-device", "update-torch",
-                                                     "update-step", "update-one-call", "update-population"])
+                                                     "update-step", "update-one-call", "update-population", "update-sweep",
+                                                     "collect-sweep"])
     ap.add_argument("--learners", type=int, default=4, help="update-population: the learners of the population")
     ap.add_argument("--minibatch", type=int, default=16384)
     ap.add_argument("--epochs", type=int, default=10, help="update-*: the epochs of one update")
@@ -214,6 +217,10 @@ def main():
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--reps", type=int, default=7)
     args = ap.parse_args()
+    if args.part in ("update-sweep", "collect-sweep"):               # (tools/encoder_sweep_bench.py: shared with transformer_bench.py)
+        import encoder_sweep_bench
+        part = encoder_sweep_bench.collect_sweep_part if args.part == "collect-sweep" else encoder_sweep_bench.update_sweep_part
+        return part(args, "deepsets")
     if args.part == "update-population":
         return population_part(args)
     if args.part.startswith("update-"):

@@ -6,6 +6,8 @@ replaces.
     python tools/transformer_bench.py --part grad-autograd|grad-device [--minibatch 16384] [--blocks 2] [--use-resid] [--reps 7]
     python tools/transformer_bench.py --part update-torch|update-step|update-one-call [--envs 4096] [--steps 128] [--epochs 10]
     python tools/transformer_bench.py --part collect-population --learners S [--learner-envs 3] [--steps 2048] [--pairs 9]
+    python tools/transformer_bench.py --part update-sweep|collect-sweep --learners S [--learner-envs 3] [--steps 2048] [--minibatch 192]
+                                   (a configuration per learner against the one-configuration population: tools/encoder_sweep_bench.py)
     python tools/transformer_bench.py --part update-population --learners S [--learner-envs 3] [--steps 2048] [--minibatch 192]
                                       [--epochs 10] [--pairs 9]
 
@@ -286,7 +288,8 @@ def update_part(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", required=True, choices=["a", "b", "c", "c-eager", "grad-autograd", "grad-device", "update-torch", "update-step",
-                                                     "update-one-call", "collect-population", "update-population"])
+                                                     "update-one-call", "collect-population", "update-population", "collect-sweep",
+                                                     "update-sweep"])
     ap.add_argument("--minibatch", type=int, default=16384)
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=None, help="default 128; collect-population: 2048")
@@ -298,6 +301,12 @@ def main():
     ap.add_argument("--learner-envs", type=int, default=3, help="collect-population, update-population: a learner's envs")
     ap.add_argument("--pairs", type=int, default=9, help="collect-population, update-population: interleaved pairs")
     args = ap.parse_args()
+    if args.part in ("collect-sweep", "update-sweep"):               # (tools/encoder_sweep_bench.py: shared with deepsets_bench.py)
+        import encoder_sweep_bench
+        args.envs, args.steps = args.learner_envs, args.steps or 2048
+        args.minibatch = 192 if args.minibatch == 16384 else args.minibatch
+        part = encoder_sweep_bench.collect_sweep_part if args.part == "collect-sweep" else encoder_sweep_bench.update_sweep_part
+        return part(args, "transformer")
     if args.part == "collect-population":
         return collect_population_part(args)
     if args.part == "update-population":
